@@ -23,8 +23,16 @@ interleaved 8-row bands, every rank renders (1/N) of it.
 scene; 1920x1080x4096 on the 10k-sphere stress scene): a fixed frame split over the N GPUs ("strong").
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM, as
-north_star asks; this path is VALU-bound so `valu` carries the binding fraction) and, at
-N=1, `cpu_baseline` (the oracle timed on the host cores on a bounded sample).
+north_star asks; this path is VALU-bound so `valu` carries the binding fraction).
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  --full adds
+what the headline figure does not need: at N=1 `cpu_baseline` (the oracle timed on the host cores on
+a bounded sample), the other configs as side legs after C3's timed region (`other_configs`) and the
+check of C3's first frame against the oracle's committed counters; at N > 1 the render-only timing,
+the check of one gathered frame against the unsharded frame, and the C ABI's own gathers.
+
+--dump-outputs DIR writes the framebuffer the timed steps accumulated (the mean of the K timed frames
+of a fresh accumulation: the accumulation is restarted before the clock starts) as DIR/*.npy.
 """
 import argparse
 import json
@@ -295,6 +303,26 @@ def other_config_rates(M, schedules, budget_s):
     return out
 
 
+DUMP_BYTES_MAX = 60_000_000    # --dump-outputs: array data in all (the files, .npy headers included, stay under 64 MB)
+
+
+def dump_outputs(out_dir, fb):
+    """--dump-outputs: the (H, W, 4) f32 framebuffer (row 0 = bottom) as out_dir/framebuffer.npy; an image larger than
+    DUMP_BYTES_MAX (the N > 1 workloads from 2716x1528 up) as a fixed, seeded sample of whole rows instead:
+    framebuffer_rows.npy (k, W, 4) f32 and their row numbers, framebuffer_row_index.npy (k,) f64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    fb = np.ascontiguousarray(fb, dtype=np.float32)
+    if fb.nbytes <= DUMP_BYTES_MAX:
+        np.save(os.path.join(out_dir, "framebuffer.npy"), fb)
+        return
+    row_bytes = fb.nbytes // fb.shape[0]
+    k = (DUMP_BYTES_MAX - 8 * fb.shape[0]) // row_bytes
+    rows = np.sort(np.random.default_rng(20261016).choice(fb.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, "framebuffer_rows.npy"), fb[rows])
+    np.save(os.path.join(out_dir, "framebuffer_row_index.npy"), rows.astype(np.float64))
+
+
 def tests_per_launch(hits, steps, world, n_spheres):
     """What the reference's linear scan (shader.wgsl:314-329: one sphere test per sphere per world_hit) executes per launch."""
     return hits / steps / world * n_spheres if steps else 0.0
@@ -322,6 +350,14 @@ def main():
                          "hashed states, a pixel's samples summed in blocks of 64 that different lanes may render (north_star's "
                          "counter-based RNG: an EXTENSION with different images, never a headline line; it keeps the pixel-starved 1/8 "
                          "shares of an 8-GPU C5 run busy, DESIGN.md 4 / 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: cpu_baseline and other_configs (N = 1), "
+                         "the first-frame check against the oracle (C3), render_only_*, the gathered-frame check and the C ABI legs "
+                         "(N > 1); off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the framebuffer they accumulated (rank 0: the gathered image) to DIR as "
+                         "float32 .npy; the accumulation is restarted before the timed steps, so the image is the mean of exactly "
+                         "--steps frames and the same for the same arguments")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--schedule", default="hint", choices=["hint", "measure"],
                     help="hint (default): pin the launch schedule profiles/schedules.json holds for this workload, if any "
@@ -330,15 +366,17 @@ def main():
     ap.add_argument("--hint", default="", help="div,mult: pin THIS launch schedule instead (e.g. 1,1 under rocprofv3 --pmc, which runs the "
                                                "launches one at a time: a full-width launch then has the chip the counters are divided by)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1 headline run: skip the side legs after the timed region that put C1, C2, C4, C5 and C5's 1/8 share into "
-                         "the line (other_configs)")
+                    help="N = 1 headline run with --full: skip the side legs after the timed region that put C1, C2, C4, C5 and C5's "
+                         "1/8 share into the line (other_configs)")
     ap.add_argument("--no-abi-legs", action="store_true",
-                    help="N > 1: skip the two non-fatal legs after the timed run that drive the C ABI's own gathers (mrt_gather_rccl on a "
-                         "communicator made here; native_runner --gpus N in one process), reported as abi_rccl_gather / abi_single_process")
-    ap.add_argument("--verify", action="store_true", help="N > 1: fail if the verification below fails (default: only report it)")
+                    help="N > 1 with --full: skip the two non-fatal legs after the timed run that drive the C ABI's own gathers "
+                         "(mrt_gather_rccl on a communicator made here; native_runner --gpus N in one process), reported as "
+                         "abi_rccl_gather / abi_single_process")
+    ap.add_argument("--verify", action="store_true",
+                    help="N > 1: run the verification below (also without --full) and fail if it fails (default: only report it)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="N > 1: skip the check after the timed run in which the ranks render and gather one more frame and rank 0 "
-                         "compares it bit for bit with the frame it renders alone (reported as gathered_image_equals_unsharded_frame)")
+                    help="N > 1 with --full: skip the check after the timed run in which the ranks render and gather one more frame and "
+                         "rank 0 compares it bit for bit with the frame it renders alone (reported as gathered_image_equals_unsharded_frame)")
     a = ap.parse_args()
     force_dist = os.environ.get("MRT_BENCH_FORCE_DIST") == "1"      # rehearses the RCCL path on one GPU
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or force_dist):
@@ -448,7 +486,7 @@ def main():
     # in tests/golden/fullsize_rows.json (C3): when this run renders that workload, its first frame must reproduce them
     first_frame_check = None
     golden = None
-    if world == 1 and headline and a.config == "c3" and a.warmup > 0 and a.frames_per_step == 1:      # (the checked frame is the first warm-up step)
+    if a.full and world == 1 and headline and a.config == "c3" and a.warmup > 0 and a.frames_per_step == 1:      # (the checked frame is the first warm-up step)
         try:
             golden = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_rows.json")))["configs"]["c3"]["frame0_counters"]
         except Exception:
@@ -494,21 +532,29 @@ def main():
                 step()
             settle_frames += int(fill.item())
             fence()
+    if a.dump_outputs:
+        # the dumped image must not depend on how many untimed frames the warm-up and the settling ran: the timed steps
+        # start a fresh accumulation (the pipeline is empty here already; mrt_reset clears the framebuffers and counters)
+        st.reset()
     schedule_before = st.get_schedule()
     c0 = st.read_counters()
     fence()
     t0 = time.perf_counter()
+    last = None
     for _ in range(a.steps):
-        step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     c1 = st.read_counters()
     schedule_after = st.get_schedule()
     kernel_ms = st.kernel_ms_history(min(a.steps, 64))
+    if a.dump_outputs and rank == 0:
+        # (N > 1: the gathered image may be a view of the staging buffer the next gather overwrites -- written out now)
+        dump_outputs(a.dump_outputs, last.cpu().numpy() if last is not None else st.read_framebuffer())
     # multi-GPU numbers with and without the gather -- a second, separately timed run of the same
     # K steps that only renders (reported as render_only_*, never as `value`)
     elapsed_render_only = None
-    if use_dist:
+    if use_dist and a.full:
         fence()
         t0 = time.perf_counter()
         for _ in range(a.steps):
@@ -531,7 +577,7 @@ def main():
     # gathered as in the timed steps, and rank 0 compares the assembled image bit for bit with the frame it renders alone.
     gather_verified = None
     ref_np = None                       # rank 0: the frame one context renders alone (frame 0 of a fresh accumulation)
-    if use_dist and not a.no_verify:
+    if use_dist and (a.full or a.verify) and not a.no_verify:
         st.reset()
         fence()
         one = step()
@@ -704,10 +750,10 @@ def main():
             out["render_only_value"] = total_samples / render_only_max * 1e-6
             out["render_only_ms_per_step"] = render_only_max / max(1, a.steps) * 1e3
             out["render_only_note"] = "the same K steps without the gather to rank 0, timed separately after the headline run"
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(spheres, cam, width, height, a.depth, seed)
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
-        if world == 1 and not use_dist and headline and a.config == "c3" and not a.no_other_configs and a.steps > 0:
+        if a.full and world == 1 and not use_dist and headline and a.config == "c3" and not a.no_other_configs and a.steps > 0:
             st.close()          # (everything of the headline's context has been read; its streams need not sit beside the side legs')
             out["other_configs"] = other_config_rates(M, schedules if a.schedule == "hint" else {}, 90.0)
 
@@ -741,7 +787,7 @@ def main():
         t.start()
         return t
 
-    if use_dist and backend == "nccl" and not a.no_abi_legs:
+    if a.full and use_dist and backend == "nccl" and not a.no_abi_legs:
         dog = watchdog(240.0, "abi_rccl_gather")
         leg = None
         try:
@@ -763,7 +809,7 @@ def main():
         except Exception:               # noqa: BLE001
             pass
         dog.cancel()
-    if rank == 0 and use_dist and world > 1 and not a.no_abi_legs and (backend == "nccl" or os.environ.get("MRT_BENCH_ABI_DEVICES")):
+    if a.full and rank == 0 and use_dist and world > 1 and not a.no_abi_legs and (backend == "nccl" or os.environ.get("MRT_BENCH_ABI_DEVICES")):
         dog2 = watchdog(300.0, "abi_single_process")
         try:
             in_flight["call"] = "native_runner --gpus N (mrt_gather: hipMemcpyPeerAsync per band)"

@@ -11,21 +11,21 @@ O=gpurun_out/final; mkdir -p $O
 PART=${1:-a}
 if [ "$PART" = "a" ]; then
 python -m pytest tests -m gpu -q > $O/gputests.log 2>&1 || true; tail -2 $O/gputests.log
-python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
-python bench.py --config c4 --steps 16 --warmup 2 > $O/bench_c4.json 2>/dev/null
-python bench.py --config c5 --steps 16 --warmup 4 > $O/bench_c5.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full --config c4 --steps 16 --warmup 2 > $O/bench_c4.json 2>/dev/null
+python bench.py --full --config c5 --steps 16 --warmup 4 > $O/bench_c5.json 2>/dev/null
 python bench.py --config c5 --rng counter --no-cpu-baseline --steps 12 --warmup 2 > $O/bench_c5_counter.json 2>/dev/null
-python bench.py --config c1 --steps 3000 --warmup 5 > $O/bench_c1.json 2>/dev/null
+python bench.py --full --config c1 --steps 3000 --warmup 5 > $O/bench_c1.json 2>/dev/null
 python bench.py --config c1 --no-cpu-baseline --frames-per-step 32 --steps 20 --warmup 2 > $O/bench_c1_x32.json 2>/dev/null
-python bench.py --config c2 --steps 150 --warmup 5 > $O/bench_c2.json 2>/dev/null
+python bench.py --full --config c2 --steps 150 --warmup 5 > $O/bench_c2.json 2>/dev/null
 python bench.py --config c2 --no-cpu-baseline --steps 150 --warmup 5 > $O/bench_c2_again.json 2>/dev/null          # the same command again: a pinned schedule reproduces
 python bench.py --config c2 --no-cpu-baseline --steps 150 --warmup 5 --schedule measure > $O/bench_c2_measure.json 2>/dev/null
-python bench.py --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 --schedule measure > $O/bench_n1_measure.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --no-other-configs --steps 20 --warmup 5 --schedule measure > $O/bench_n1_measure.json 2>/dev/null
 python bench.py --config c2 --no-cpu-baseline --frames-per-step 32 --steps 4 --warmup 1 > $O/bench_c2_x32.json 2>/dev/null
 python bench.py --config interactive --no-cpu-baseline --steps 3000 --warmup 5 > $O/bench_interactive.json 2>/dev/null
 python bench.py --config interactive --no-cpu-baseline --frames-per-step 32 --steps 20 --warmup 2 > $O/bench_interactive_x32.json 2>/dev/null
-MRT_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline --verify > $O/bench_forced_dist.json 2>/dev/null
-MRT_BENCH_ABI_DEVICES=0,0 MRT_BENCH_BACKEND=gloo python bench.py --gpus 2 --no-cpu-baseline --verify --steps 2 --warmup 1 > $O/rehearsal_gloo_n2.json 2>/dev/null
+MRT_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline --verify > $O/bench_forced_dist.json 2>/dev/null
+MRT_BENCH_ABI_DEVICES=0,0 MRT_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --no-cpu-baseline --verify --steps 2 --warmup 1 > $O/rehearsal_gloo_n2.json 2>/dev/null
 echo benches done
 bash scripts/profile.sh c3 --steps 4 --warmup 2 --hint 1,1 > $O/profile_c3.log 2>&1      # (full-width launches: the profiler runs them one at a time)
 bash scripts/profile.sh c5 --config c5 --steps 2 --warmup 2 > $O/profile_c5.log 2>&1

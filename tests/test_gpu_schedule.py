@@ -17,40 +17,63 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_forced_schedule_transitions_mid_accumulation_are_bit_identical(mrt, oracle):
+_TRANSITIONS = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+import myraytracer_amd as mrt
+spheres, cam = mrt.scene_cover(1, True)
+w, h, spp, depth, frames = 192, 104, 6, 50, 12
+plan = [(1, 1), (1, 1), (4, 1), (4, 1), (8, 1), (8, 1), (8, 2), (2, 1), (2, 1), (2, 2), (2, 2), (2, 1)]
+assert len(plan) == frames
+args = mrt.Args(w, h, spp, depth, 1.0)
+with mrt.State(args, seed=11) as st:
+    st.set_world(spheres); st.set_camera(cam)
+    seen = []
+    for div, mult in plan:
+        st.set_schedule_hint(div, mult)
+        st.redraw()
+        sch = st.get_schedule()
+        assert (sch["div"], sch["mult"], sch["settled"]) == (div, mult, True)
+        # (held to the frames this process can run side by side, where the library has measured that)
+        assert sch["frames_in_flight"] == min(max(2, div) * mult, sch["max_concurrent_frames"] or 16)
+        seen.append(sch["frames_in_flight"])
+    got = st.read_framebuffer()
+    counters = st.read_counters()
+with mrt.State(args, seed=11) as st:                 # one frame after the other, nothing in flight
+    st.set_world(spheres); st.set_camera(cam)
+    st.debug_set_frames_in_flight(1)
+    for _ in range(frames):
+        st.redraw()
+        st.sync()
+    serial = st.read_framebuffer()
+    serial_counters = st.read_counters()
+keys = ("samples", "world_hit_calls", "rng_draws")
+np.savez(sys.argv[2], seen=np.array(seen), got=got, serial=serial, counters=np.array([counters[k] for k in keys], np.uint64),
+         serial_counters=np.array([serial_counters[k] for k in keys], np.uint64))
+"""
+
+
+def test_forced_schedule_transitions_mid_accumulation_are_bit_identical(mrt, oracle, tmp_path):
     """12 frames of the cover scene, the schedule changed under the accumulation: full width -> a quarter (4 frames in flight)
     -> an eighth (8, then 16 over-subscribed) -> a half (2) -> twice the frames at a half (4) -> back; every change waits for the frames under way and
-    re-allocates slots (api.cpp, set_frame_slots).  The accumulated image must be the one 12 serial frames give, and the oracle's."""
-    spheres, cam = mrt.scene_cover(1, True)
-    w, h, spp, depth, frames = 192, 104, 6, 50, 12
-    plan = [(1, 1), (1, 1), (4, 1), (4, 1), (8, 1), (8, 1), (8, 2), (2, 1), (2, 1), (2, 2), (2, 2), (2, 1)]
-    assert len(plan) == frames
-    args = mrt.Args(w, h, spp, depth, 1.0)
-    with mrt.State(args, seed=11) as st:
-        st.set_world(spheres); st.set_camera(cam)
-        seen = []
-        for div, mult in plan:
-            st.set_schedule_hint(div, mult)
-            st.redraw()
-            sch = st.get_schedule()
-            assert (sch["div"], sch["mult"], sch["settled"]) == (div, mult, True)
-            # (held to the frames this process can run side by side, where the library has measured that)
-            assert sch["frames_in_flight"] == min(max(2, div) * mult, sch["max_concurrent_frames"] or 16)
-            seen.append(sch["frames_in_flight"])
-        got = st.read_framebuffer()
-        counters = st.read_counters()
+    re-allocates slots (api.cpp, set_frame_slots).  The accumulated image must be the one 12 serial frames give, and the oracle's.
+    Eight and sixteen frames in flight need as many hardware queues: the frames run in a fresh process with the package's own
+    GPU_MAX_HW_QUEUES=20, whatever the caller's environment holds (HIP's default of 4 would hold every setting to 4 frames)."""
+    out = str(tmp_path / "transitions.npz")
+    r = subprocess.run([sys.executable, "-c", _TRANSITIONS, ROOT, out], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, GPU_MAX_HW_QUEUES="20"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = np.load(out)
+    seen, got, serial = [int(x) for x in res["seen"]], res["got"], res["serial"]
+    counters = dict(zip(("samples", "world_hit_calls", "rng_draws"), (int(x) for x in res["counters"])))
+    serial_counters = dict(zip(("samples", "world_hit_calls", "rng_draws"), (int(x) for x in res["serial_counters"])))
     assert max(seen) >= 8 and seen[0] == 2, seen
-    with mrt.State(args, seed=11) as st:                 # one frame after the other, nothing in flight
-        st.set_world(spheres); st.set_camera(cam)
-        st.debug_set_frames_in_flight(1)
-        for _ in range(frames):
-            st.redraw()
-            st.sync()
-        serial = st.read_framebuffer()
-        serial_counters = st.read_counters()
     assert np.array_equal(got.view(np.uint32), serial.view(np.uint32)), mismatch_report(got, serial)
     for k in ("samples", "world_hit_calls", "rng_draws"):
         assert counters[k] == serial_counters[k]
+    spheres, cam = mrt.scene_cover(1, True)
+    w, h, spp, depth, frames = 192, 104, 6, 50, 12
     cnt = oracle.Counters()
     ref = oracle_render(oracle, spheres, cam, w, h, spp, depth, 11, frames, 1.0, counters=cnt)
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), mismatch_report(got, ref)
