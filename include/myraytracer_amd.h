@@ -35,7 +35,8 @@ extern "C" {
  * mrt_debug_build_hierarchy accept top_target 0 = automatic ("ABI history"). */
 /* 4: round 5 -- MRT_ERR_STALLED and mrt_set_wait_timeout (every blocking host wait has a deadline), mrt_set_schedule_hint /
  * mrt_get_schedule (the launch schedule a run settled at can be read and pinned); mrt_create no longer touches the process
- * environment (GPU_MAX_HW_QUEUES is the host's to set: INTEGRATION.md 2a). */
+ * environment (GPU_MAX_HW_QUEUES is the host's to set: INTEGRATION.md 2a).  Version 4 later gained, additions only: the
+ * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -271,6 +272,51 @@ int mrt_read_counters(mrt_ctx* ctx, mrt_counters* out);   /* accumulated since c
  * counters are wave totals kept on the scalar side.  0 launches the instantiation without it (rng_draws then stops
  * advancing); 1 (default) counts.  Takes effect at the next redraw; the images are the same. */
 int mrt_set_draw_counting(mrt_ctx* ctx, int enabled);
+
+/* ------------------------------------------------------------------ present pass
+ *
+ * The reference's pass 2 of State::redraw (lib.rs:270-297): sample_framebuffer.wgsl draws the accumulated RGBA32F texture onto
+ * the window surface, rows flipped (:24), in the surface's 8-bit sRGB format (lib.rs:349-351, :1133).  mrt_present queues the
+ * same conversion on the GPU -- colour through the sRGB OETF, alpha linear, both clamped and rounded to 8 bits, bit-identical
+ * to mrt_srgb8 (and, for alpha, round(255 clamp(a, 0, 1)), NaN -> 0) for every float -- and an asynchronous copy of the
+ * 4-byte pixels into pinned memory the library owns; mrt_present_acquire hands out a finished image without waiting for the
+ * frames still in flight.  A caller that presents every frame keeps its frames in flight (mrt_read_framebuffer, the exact-float
+ * read-back, waits for them).  Images live in a ring of `depth` entries, each a device staging buffer, a pinned host buffer
+ * and an event: automatic depth = the frames in flight + 2 (grown at present time, never shrunk), all entries' pinned bytes
+ * held to 256 MB (18 entries of 1920x1080, 7 of 3840x2160).  When every entry but the one the caller holds has a copy still
+ * in flight, mrt_present waits for the oldest on the host (bounded, mrt_set_wait_timeout): a ring capped by the budget or by
+ * mrt_set_present_ring thus narrows the frames in flight. */
+enum { MRT_PRESENT_RGBA8_SRGB = 1, MRT_PRESENT_BGRA8_SRGB = 2 };   /* Rgba8UnormSrgb / Bgra8UnormSrgb surfaces */
+enum {
+    MRT_PRESENT_FLIP_Y = 1,    /* rows top-down, as on the surface (sample_framebuffer.wgsl:24) and in mrt_write_ppm */
+    MRT_PRESENT_GATHERED = 2   /* the root's full frame from the latest mrt_gather / mrt_gather_rccl, not this ctx's framebuffer */
+};
+enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
+typedef struct {               /* 40 bytes */
+    uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
+    uint32_t frames_done;      /* mrt_frames_done at the present: the accumulation the image shows */
+    uint32_t width, rows, row_bytes;   /* rows of width pixels, row_bytes = 4 width apart */
+    uint32_t format, flags;    /* as passed to mrt_present */
+    uint32_t dropped;          /* images finished but never acquired since the previous acquire (skipped or overwritten) */
+    uint32_t ring_depth;       /* the ring's current depth */
+} mrt_present_info;
+/* Queues the present of the most recent frame (after mrt_render(k): its last frame) on the ctx's stream, behind that frame's
+ * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB; flags: MRT_PRESENT_FLIP_Y |
+ * MRT_PRESENT_GATHERED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed local rows in
+ * mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full frame
+ * (MRT_ERR_STATE before the first gather).  Must not be called while the ctx's stream is being captured into a graph. */
+int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
+/* A finished image: *pixels = rows x row_bytes bytes, valid until mrt_present_release, the next acquire, mrt_reset,
+ * mrt_set_shard or mrt_destroy.  MRT_ACQUIRE_NEWEST (a viewer, mailbox): the most recent finished image; older finished ones are
+ * skipped (info->dropped).  MRT_ACQUIRE_OLDEST (a capture, FIFO): the oldest; nothing is skipped while the caller keeps at most
+ * depth - 1 presents outstanding.  wait == 0: returns MRT_OK with *pixels = NULL when none has finished; wait != 0: polls
+ * (bounded) for one that is queued (*pixels = NULL only if none is).  MRT_ERR_STATE before the first present.  info may be
+ * NULL.  Releases the image held before. */
+int mrt_present_acquire(mrt_ctx* ctx, int mode, int wait, const uint8_t** pixels, mrt_present_info* info);
+int mrt_present_release(mrt_ctx* ctx);            /* MRT_ERR_STATE if no image is held */
+/* Pins the ring's depth (2..18, held to the 256 MB budget); 0 = automatic.  Waits (bounded) for the copies in flight and
+ * discards the images not yet acquired; MRT_ERR_STATE while the caller holds one. */
+int mrt_set_present_ring(mrt_ctx* ctx, uint32_t depth);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

@@ -16,6 +16,18 @@
 extern "C" {
 #endif
 
+/* Diagnostic, host only: the thresholds the present pass searches (mrt_present): out[k], k = 1..255, is the smallest float v
+ * with mrt_srgb8(v) >= k; out[0] = -inf.  A value's code is the number of out[1..255] that are <= it (0 for NaN). */
+int mrt_debug_srgb8_thresholds(float out[256]);
+/* Diagnostic: the present kernel on caller-supplied texels, synchronously: rgba = rows x width RGBA32F texels (row 0 first),
+ * out = rows x width x 4 bytes; format MRT_PRESENT_*_SRGB, flags 0 or MRT_PRESENT_FLIP_Y. */
+int mrt_debug_present_encode(mrt_ctx* ctx, const float* rgba, uint32_t width, uint32_t rows, int format, uint32_t flags,
+                             uint8_t* out);
+/* Diagnostic / tuning: where mrt_present's device-to-host copy runs: 0 a stream of its own (created at the first present in
+ * this mode; it shares the process' hardware queues with the render side streams), 1 (default, the faster one measured:
+ * profiles/present_rates.txt) the ctx's stream, right behind the present kernel.  The images are the same. */
+int mrt_debug_set_present_copy(mrt_ctx* ctx, int mode);
+
 /* Diagnostic: make mrt_gather on this root use the cross-device form of the copy (one hipMemcpyPeerAsync per
  * band) even when a shard shares the root's device, so that its indexing runs on a one-GPU box. */
 int mrt_debug_set_gather_per_band(mrt_ctx* root_ctx, int enabled);

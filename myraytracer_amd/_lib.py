@@ -38,7 +38,14 @@ EXPORTS = [
     "mrt_srgb8", "mrt_write_png", "mrt_gather", "mrt_gather_rccl", "mrt_gathered_device_ptr", "mrt_read_gathered",
     "mrt_shard_global_row", "mrt_shard_local_rows", "mrt_unshard_rows", "mrt_debug_last_set_world_ms", "mrt_debug_world_hit", "mrt_debug_set_frame_batching", "mrt_debug_set_gather_per_band", "mrt_debug_arith", "mrt_debug_arith_pairs", "mrt_debug_set_boxes", "mrt_debug_build_boxes", "mrt_set_draw_counting", "mrt_debug_last_launch", "mrt_debug_set_frames_in_flight", "mrt_debug_lds_layout", "mrt_debug_build_boxes_top_down",
     "mrt_set_wait_timeout", "mrt_get_schedule", "mrt_set_schedule_hint", "mrt_debug_width_policy", "mrt_debug_stream_concurrency", "mrt_debug_wave_log_frame",
+    "mrt_present", "mrt_present_acquire", "mrt_present_release", "mrt_set_present_ring", "mrt_debug_srgb8_thresholds",
+    "mrt_debug_present_encode", "mrt_debug_set_present_copy",
 ]
+
+# the present pass (include/myraytracer_amd.h)
+PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
+PRESENT_FLIP_Y, PRESENT_GATHERED = 1, 2
+ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 
 
 class MrtArgs(C.Structure):
@@ -74,6 +81,12 @@ class MrtDielectricRange(C.Structure):
 class MrtWorld(C.Structure):
     _fields_ = [("spheres", MrtSphereRange), ("lambertians", MrtLambertianRange),
                 ("metals", MrtMetalRange), ("dielectrics", MrtDielectricRange)]
+
+
+class MrtPresentInfo(C.Structure):
+    _fields_ = [("seq", C.c_uint64), ("frames_done", C.c_uint32), ("width", C.c_uint32), ("rows", C.c_uint32),
+                ("row_bytes", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("dropped", C.c_uint32),
+                ("ring_depth", C.c_uint32)]
 
 
 class MrtSphere(C.Structure):
@@ -270,6 +283,13 @@ def load():
         "mrt_debug_width_policy": (i32, [i32, P(u32), P(u32), C.c_double, C.c_double]),
         "mrt_debug_stream_concurrency": (i32, [vp, u32, P(f32)]),
         "mrt_debug_wave_log_frame": (i32, [vp, u32, vp, sz, P(sz)]),
+        "mrt_present": (i32, [vp, i32, u32]),
+        "mrt_present_acquire": (i32, [vp, i32, i32, P(P(C.c_uint8)), P(MrtPresentInfo)]),
+        "mrt_present_release": (i32, [vp]),
+        "mrt_set_present_ring": (i32, [vp, u32]),
+        "mrt_debug_srgb8_thresholds": (i32, [P(f32)]),
+        "mrt_debug_present_encode": (i32, [vp, vp, u32, u32, i32, u32, vp]),
+        "mrt_debug_set_present_copy": (i32, [vp, i32]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

@@ -498,6 +498,53 @@ class State:
         self._check(self._L.mrt_read_gathered(self._ctx, out.ctypes.data, out.size), "mrt_read_gathered")
         return out
 
+    # -- present pass (the reference's pass 2, lib.rs:270-297 / sample_framebuffer.wgsl): 8-bit sRGB images, read back without
+    #    waiting for the frames in flight
+    _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB}
+
+    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False):
+        """mrt_present: queue the most recent frame's 8-bit sRGB image ("rgba8" / "bgra8"; flip = rows top-down; gathered = the
+        root's full frame of the last gather).  Asynchronous."""
+        if fmt not in self._PRESENT_FORMATS:
+            raise ValueError(f"present: format {fmt!r} (rgba8, bgra8)")
+        flags = (_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0)
+        self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
+
+    def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):
+        """mrt_present_acquire: (uint8 [rows, width, 4], info dict) or None if no image has finished (wait=False) or none is
+        queued.  newest: the most recent finished image (older ones are dropped), else the oldest.  copy=False returns a view
+        of the library's pinned buffer, valid until release_presented() / the next acquire / reset / close."""
+        px = C.POINTER(C.c_uint8)()
+        info = _lib.MrtPresentInfo()
+        mode = _lib.ACQUIRE_NEWEST if newest else _lib.ACQUIRE_OLDEST
+        self._check(self._L.mrt_present_acquire(self._ctx, mode, int(wait), C.byref(px), C.byref(info)), "mrt_present_acquire")
+        if not px:
+            return None
+        img = np.ctypeslib.as_array(px, shape=(info.rows, info.width, 4))
+        d = {k: int(getattr(info, k)) for k, _ in _lib.MrtPresentInfo._fields_}
+        return (img.copy() if copy else img), d
+
+    def release_presented(self):
+        self._check(self._L.mrt_present_release(self._ctx), "mrt_present_release")
+
+    def set_present_ring(self, depth: int):
+        """Pin the ring of presented images to `depth` entries (2..18); 0 = automatic (frames in flight + 2)."""
+        self._check(self._L.mrt_set_present_ring(self._ctx, depth), "mrt_set_present_ring")
+
+    def debug_set_present_copy(self, mode: int):
+        """Where the present's device-to-host copy runs: 0 = a stream of its own, 1 = the context's stream (default)."""
+        self._check(self._L.mrt_debug_set_present_copy(self._ctx, mode), "mrt_debug_set_present_copy")
+
+    def debug_present_encode(self, rgba: np.ndarray, fmt: str = "rgba8", flip: bool = False) -> np.ndarray:
+        """The present kernel on caller-supplied texels: float32 [rows, width, 4] -> uint8 [rows, width, 4], synchronously."""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        rows, width, _ = rgba.shape
+        out = np.empty((rows, width, 4), np.uint8)
+        self._check(self._L.mrt_debug_present_encode(self._ctx, rgba.ctypes.data, width, rows, self._PRESENT_FORMATS[fmt],
+                                                     _lib.PRESENT_FLIP_Y if flip else 0, out.ctypes.data),
+                    "mrt_debug_present_encode")
+        return out
+
 
 def gather(states: Sequence[State], root: int = 0):
     """mrt_gather: one process, len(states) contexts (states[i] = shard i of n); the full frame lands on states[root]."""
@@ -507,6 +554,15 @@ def gather(states: Sequence[State], root: int = 0):
     if st:
         ctx = states[root]._ctx if 0 <= root < len(states) else None
         raise MrtError(st, "mrt_gather", (L.mrt_last_error(ctx) or b"").decode())
+
+
+def srgb8_thresholds() -> np.ndarray:
+    """The present pass's table (host): t[k], k = 1..255, the smallest float32 v with mrt_srgb8(v) >= k; t[0] = -inf."""
+    out = np.empty(256, np.float32)
+    st = _lib.load().mrt_debug_srgb8_thresholds(out.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise MrtError(st, "mrt_debug_srgb8_thresholds")
+    return out
 
 
 def shard_global_row(local_row: int, rank: int, world: int) -> int:

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "mrt_internal.h"
@@ -24,9 +25,53 @@ static unsigned char srgb8(float v) {
     return (unsigned char)(e * 255.0 + 0.5);
 }
 
+// alpha as an sRGB-format target stores it: linearly, clamp and round to nearest (NaN -> 0)
+static unsigned char unorm8(float v) {
+    if (!(v > 0.0f)) return 0;
+    if (v >= 1.0f) return 255;
+    return (unsigned char)((double)v * 255.0 + 0.5);
+}
+
+namespace mrt {
+
+// The device's form of the two conversions above (present.hip): t[k], k = 1..255, is the smallest float v with code(v) >= k,
+// found by bisection over the bit patterns of [0, 1] (those of non-negative floats are ordered like their values); the code
+// of any float is then the number of thresholds <= v -- NaN compares false with every one of them and gets 0, as here.  Exact
+// because both conversions are non-decreasing over every float in [0, 1] (checked exhaustively for srgb8: no code is lower
+// than its predecessor's and none is skipped) and constant below and above.  t[0] = -inf: every value but NaN reaches code 0.
+const float* present_thresholds() {
+    static const std::vector<float> table = [] {
+        std::vector<float> t(512);
+        for (int which = 0; which < 2; which++) {
+            float* out = t.data() + 256 * which;
+            out[0] = -INFINITY;
+            for (int k = 1; k < 256; k++) {
+                uint32_t lo = 0u, hi = 0x3F800000u;            // code(lo) < k <= code(hi): 0.0f and 1.0f
+                while (hi - lo > 1u) {
+                    const uint32_t mid = lo + (hi - lo) / 2u;
+                    float v;
+                    std::memcpy(&v, &mid, 4);
+                    if ((which == 0 ? srgb8(v) : unorm8(v)) >= k) hi = mid; else lo = mid;
+                }
+                std::memcpy(&out[k], &hi, 4);
+            }
+        }
+        return t;
+    }();
+    return table.data();
+}
+
+}  // namespace mrt
+
 extern "C" {
 
 uint8_t mrt_srgb8(float linear) { return srgb8(linear); }
+
+int mrt_debug_srgb8_thresholds(float out[256]) {
+    if (!out) return MRT_ERR_INVALID_ARG;
+    std::memcpy(out, mrt::present_thresholds(), 256 * sizeof(float));
+    return MRT_OK;
+}
 
 int mrt_write_pfm(const char* path, const float* rgba, uint32_t width, uint32_t height) {
     if (!path || !rgba || !width || !height) return MRT_ERR_INVALID_ARG;

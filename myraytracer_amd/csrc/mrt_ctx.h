@@ -144,6 +144,27 @@ struct mrt_ctx {
     hipEvent_t ev_gather_root = nullptr;
     bool gather_per_band = false;              // mrt_debug_set_gather_per_band: the cross-device copy loop on one device
 
+    // present pass (mrt_present, api.cpp): a ring of images, each the present kernel's output on the device, its copy in pinned
+    // host memory and the event that says the copy has landed.  An entry is free, queued (presented, not acquired: its copy may
+    // still be in flight) or held by the caller (mrt_present_acquire); entries are added, never freed before mrt_destroy.
+    struct PresentEntry {
+        uint8_t* d_img = nullptr;
+        uint8_t* h_img = nullptr;
+        hipEvent_t copied = nullptr;
+        enum { kFree, kQueued, kHeld } state = kFree;
+        mrt_present_info info{};
+    };
+    std::vector<PresentEntry> present_ring;
+    size_t present_entry_bytes = 0;                 // the capacity of every entry
+    uint32_t present_depth_pin = 0;                 // mrt_set_present_ring: 0 = automatic
+    uint32_t present_depth = 0;                     // the entries in use: present_ring[0, present_depth)
+    uint64_t present_seq = 0;
+    uint32_t present_dropped = 0;                   // since the last acquire
+    int present_copy_mode = 1;                      // mrt_debug_set_present_copy: 0 = own stream, 1 = the ctx's stream (measured)
+    hipStream_t present_stream = nullptr;           // the copies (mode 0), created at the first present in that mode
+    hipEvent_t ev_presented = nullptr;              // "the present kernel is done", on the ctx's stream (mode 0)
+    float* d_present_tables = nullptr;              // present_thresholds() on the device
+
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     // ring of HIP event pairs around the render kernel of the most recent redraws, frame f at f % kEventRing

@@ -163,4 +163,11 @@ int launch_arith_check(int mode, const uint32_t r[4], unsigned long long count, 
                        void* stream);
 int launch_arith_pairs(const float* d_x, const float* d_y, uint32_t n, uint32_t* d_out, void* stream);
 
+// present.hip: `rows` rows of `width` RGBA32F texels -> 4 B per pixel (8-bit sRGB colour, linear alpha; bgra: B, G, R, A order),
+// top-down with `flip`; d_tables: the 2 x 256 floats of present_thresholds() in device memory
+int launch_present(const float* src, uint8_t* dst, uint32_t width, uint32_t rows, uint32_t flip, uint32_t bgra,
+                   const float* d_tables, void* stream);
+// image_io.cpp, host: {colour, alpha} x 256 thresholds -- t[k] = the smallest float whose code is >= k (t[0] = -inf)
+const float* present_thresholds();
+
 }  // namespace mrt

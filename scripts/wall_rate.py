@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Dev helper (GPU box): pipelined wall-clock Msamples/s of one workload under the tuning switches.
    [MRT_HIER=levels,top] [MRT_BOXES=0|1] [MRT_RNG=1] [MRT_HINT=div,mult] [MRT_READ_EVERY=1] [MRT_SHARD=rank,world] [MRT_STEADY=1]
+   [MRT_PRESENT_EVERY=1 (a viewer on the present pass: mrt_present after every redraw, the newest image acquired without waiting)]
+   [MRT_PRESENT_COPY=0|1 (the present's copy on a stream of its own / on the context's stream)]
    python scripts/wall_rate.py scene w h spp steps"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +24,10 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     if os.environ.get("MRT_HINT"):              # "div,mult": pin the launch schedule
         st.set_schedule_hint(*[int(x) for x in os.environ["MRT_HINT"].split(",")])
     read_every = bool(os.environ.get("MRT_READ_EVERY"))     # a viewer: the framebuffer is read back after every redraw
+    present_every = bool(os.environ.get("MRT_PRESENT_EVERY"))
+    if os.environ.get("MRT_PRESENT_COPY"):
+        st.debug_set_present_copy(int(os.environ["MRT_PRESENT_COPY"]))
+    acquired = 0
     st.set_world(sp)
     if cam is not None: st.set_camera(cam)
     if os.environ.get("MRT_RNG"): st.set_rng_mode(int(os.environ["MRT_RNG"]))
@@ -35,13 +41,19 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
         st.redraw()
         stamps.append(time.perf_counter())         # (a call returns when the oldest frame in flight has ended: the back-pressure)
         if read_every: st.read_framebuffer()
+        if present_every:
+            st.present("bgra8", flip=shard is None)
+            acquired += st.acquire_presented(newest=True, wait=False, copy=False) is not None
     st.sync()
     dt = time.perf_counter() - t0
+    present_note = f"presented every frame ({acquired} of {steps} acquired without waiting, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), "
     c1 = st.read_counters()
     util = (c1["world_hit_calls"] - c0["world_hit_calls"]) / max(1, c1["lane_slots"] - c0["lane_slots"])
     print(f"{scene} {w}x{h}x{spp} HIER={os.environ.get('MRT_HIER')} BOXES={os.environ.get('MRT_BOXES')} RNG={os.environ.get('MRT_RNG')}: "
           f"{w * h * spp * steps / dt * 1e-6 / (shard[1] if shard else 1):.0f} Msamples/s, {dt / steps * 1e3:.1f} ms/step, lane util {util:.3f}, top {c1['sweep_records']}, "
-          f"{'read back every frame, ' if read_every else ''}schedule {st.get_schedule()}", flush=True)
+          f"{'read back every frame, ' if read_every else ''}"
+          f"{present_note if present_every else ''}"
+          f"schedule {st.get_schedule()}", flush=True)
     if os.environ.get("MRT_STEADY") and not read_every:
         # the pipelined rate WITHOUT the run's fill and drain: calls are paced by completions, so between the return of call a and
         # the return of the last call exactly (steps - 1 - a) frames have ended, with the pipeline full at both instants
