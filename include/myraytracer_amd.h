@@ -36,7 +36,9 @@ extern "C" {
 /* 4: round 5 -- MRT_ERR_STALLED and mrt_set_wait_timeout (every blocking host wait has a deadline), mrt_set_schedule_hint /
  * mrt_get_schedule (the launch schedule a run settled at can be read and pinned); mrt_create no longer touches the process
  * environment (GPU_MAX_HW_QUEUES is the host's to set: INTEGRATION.md 2a).  Version 4 later gained, additions only: the
- * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info). */
+ * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info);
+ * the noise estimate (mrt_set_noise_tracking, mrt_noise_query, mrt_noise_result, mrt_read_noise, mrt_read_noise_tiles,
+ * mrt_noise_factor, mrt_noise_report). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -317,6 +319,60 @@ int mrt_present_release(mrt_ctx* ctx);            /* MRT_ERR_STATE if no image i
 /* Pins the ring's depth (2..18, held to the 256 MB budget); 0 = automatic.  Waits (bounded) for the copies in flight and
  * discards the images not yet acquired; MRT_ERR_STATE while the caller holds one. */
 int mrt_set_present_ring(mrt_ctx* ctx, uint32_t depth);
+
+/* ------------------------------------------------------------------ noise estimate (no reference counterpart)
+ *
+ * Frames are independent draws (each has its own rng_shuffle, lib.rs:305).  With noise tracking on, the blend also keeps, per
+ * framebuffer texel, S: the weighted population variance of the frames' mean luminances, by West's recursion with the blend's
+ * own weights w (float32, in this order):
+ *     lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b
+ *     d      = lum(mean) - lum(prev.rgb)                  prev = the framebuffer texel the blend reads
+ *     S'     = (w == 0.0f) ? 0.0f : w * (S + (1.0f - w) * (d * d))
+ * The host tracks c2 = sum of the squared normalised frame weights in double, from the float weights actually used:
+ * c2' = w^2 c2 + (1 - w)^2, 1 at w == 0.  The estimated variance of the displayed luminance is S * K, K = c2 / (1 - c2):
+ * 1 / (n - 1) for uniform accumulation (max_framebuffer_weight 1), -> (1 - w) / (2 w) for the EMA at a saturated weight w,
+ * +inf for n < 2 ("no estimate yet": rmse = rel_rmse = max_se = +inf, every finite pixel is above the threshold).
+ * Per finite pixel of a report, in float32: var = S * (float)K, se = sqrtf(var), L = lum(framebuffer), rel = se / fmaxf(L, floor),
+ * above = rel > threshold; a pixel whose S or L is not finite counts in non_finite only.
+ * Assumptions: a caller who pins the same shuffle for every frame (mrt_set_rng_shuffle) makes the frames identical and the
+ * estimate reads 0; mrt_set_camera / mrt_set_world do not restart the accumulation (mrt_reset does), so after such a change
+ * without a reset the image blends two pictures and the estimate counts their difference as noise ("not converged"). */
+typedef struct {                 /* 96 bytes */
+    uint64_t seq;                /* the query's number on this ctx: 1, 2, ...; 0 = no report */
+    uint32_t frames_done;        /* mrt_frames_done at the query: the accumulation the report describes */
+    uint32_t reserved;
+    uint64_t pixels;             /* finite pixels (image rows of this ctx; shard padding excluded) */
+    uint64_t non_finite;         /* pixels whose S or luminance is NaN / Inf (in nothing else) */
+    uint64_t above;              /* finite pixels with rel > threshold */
+    float threshold, floor;      /* as passed to mrt_noise_query */
+    double noise_factor;         /* K */
+    double sum_var;              /* sum of S * K over the finite pixels (double) */
+    double sum_lum;              /* sum of L over the finite pixels */
+    double rmse;                 /* sqrt(sum_var / pixels) */
+    double rel_rmse;             /* rmse / (sum_lum / pixels) */
+    float max_se;                /* the largest se */
+    uint32_t reserved2;
+} mrt_noise_report;
+/* Turns noise tracking on (allocates S, zeroed) or off (frees it).  Only while mrt_frames_done == 0 (after mrt_create or
+ * mrt_reset), else MRT_ERR_STATE.  Tracking survives mrt_reset (S is zeroed with the framebuffers, unread reports are
+ * discarded) and mrt_set_shard (S is reallocated for the new shard's rows, zeroed). */
+int mrt_set_noise_tracking(mrt_ctx* ctx, int enabled);
+/* Queues the noise report of the most recent frame on the ctx's stream, behind that frame's blend -- the reduction and a copy
+ * into pinned memory the library owns -- and returns at once.  Reports live in a ring of 8; when the oldest is still in
+ * flight the call waits for it (bounded, mrt_set_wait_timeout).  rel_threshold, rel_floor: finite, rel_floor >= 0.
+ * MRT_ERR_STATE if tracking is off.  Must not be called while the ctx's stream is being captured into a graph. */
+int mrt_noise_query(mrt_ctx* ctx, float rel_threshold, float rel_floor);
+/* The newest finished report.  wait == 0: out->seq == 0 when none has finished; wait != 0: polls (bounded) for the newest
+ * queued report first.  Never waits for frames queued after that query.  out->seq == 0 before the first query. */
+int mrt_noise_result(mrt_ctx* ctx, int wait, mrt_noise_report* out);
+/* S in mrt_read_framebuffer's texel order (world 1: height rows of width; a shard: its packed local rows), one float per
+ * texel; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE if tracking is off. */
+int mrt_read_noise(mrt_ctx* ctx, float* out, size_t cap);
+/* The per-8x8-tile maximum of rel of the latest queued query, tiles_rows rows of tiles_x (tile = band x tiles_x + column, a
+ * shard's packed bands); waits for that query only.  MRT_ERR_STATE before the first query. */
+int mrt_read_noise_tiles(mrt_ctx* ctx, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
+/* Host only: K after frames_done uninterrupted frames with the weights of mrt_frame_weight (+inf for frames_done < 2). */
+double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

@@ -27,6 +27,11 @@ int mrt_debug_present_encode(mrt_ctx* ctx, const float* rgba, uint32_t width, ui
  * this mode; it shares the process' hardware queues with the render side streams), 1 (default, the faster one measured:
  * profiles/present_rates.txt) the ctx's stream, right behind the present kernel.  The images are the same. */
 int mrt_debug_set_present_copy(mrt_ctx* ctx, int mode);
+/* Diagnostic: the noise reduction (mrt_noise_query) on caller-supplied buffers, synchronously: S = rows x width floats, rgba =
+ * rows x width RGBA32F texels (row 0 first), K the noise factor (+inf allowed); *out as a report (seq 0, frames_done 0), and
+ * tiles_out (may be NULL) gets ceil(rows / 8) x ceil(width / 8) tile maxima. */
+int mrt_debug_noise_reduce(mrt_ctx* ctx, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,
+                           float threshold, float floor, mrt_noise_report* out, float* tiles_out);
 
 /* Diagnostic: make mrt_gather on this root use the cross-device form of the copy (one hipMemcpyPeerAsync per
  * band) even when a shard shares the root's device, so that its indexing runs on a one-GPU box. */

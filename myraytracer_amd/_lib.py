@@ -40,6 +40,8 @@ EXPORTS = [
     "mrt_set_wait_timeout", "mrt_get_schedule", "mrt_set_schedule_hint", "mrt_debug_width_policy", "mrt_debug_stream_concurrency", "mrt_debug_wave_log_frame",
     "mrt_present", "mrt_present_acquire", "mrt_present_release", "mrt_set_present_ring", "mrt_debug_srgb8_thresholds",
     "mrt_debug_present_encode", "mrt_debug_set_present_copy",
+    "mrt_set_noise_tracking", "mrt_noise_query", "mrt_noise_result", "mrt_read_noise", "mrt_read_noise_tiles", "mrt_noise_factor",
+    "mrt_debug_noise_reduce",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -87,6 +89,13 @@ class MrtPresentInfo(C.Structure):
     _fields_ = [("seq", C.c_uint64), ("frames_done", C.c_uint32), ("width", C.c_uint32), ("rows", C.c_uint32),
                 ("row_bytes", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("dropped", C.c_uint32),
                 ("ring_depth", C.c_uint32)]
+
+
+class MrtNoiseReport(C.Structure):
+    _fields_ = [("seq", C.c_uint64), ("frames_done", C.c_uint32), ("reserved", C.c_uint32), ("pixels", C.c_uint64),
+                ("non_finite", C.c_uint64), ("above", C.c_uint64), ("threshold", C.c_float), ("floor", C.c_float),
+                ("noise_factor", C.c_double), ("sum_var", C.c_double), ("sum_lum", C.c_double), ("rmse", C.c_double),
+                ("rel_rmse", C.c_double), ("max_se", C.c_float), ("reserved2", C.c_uint32)]
 
 
 class MrtSphere(C.Structure):
@@ -290,6 +299,13 @@ def load():
         "mrt_debug_srgb8_thresholds": (i32, [P(f32)]),
         "mrt_debug_present_encode": (i32, [vp, vp, u32, u32, i32, u32, vp]),
         "mrt_debug_set_present_copy": (i32, [vp, i32]),
+        "mrt_set_noise_tracking": (i32, [vp, i32]),
+        "mrt_noise_query": (i32, [vp, f32, f32]),
+        "mrt_noise_result": (i32, [vp, i32, P(MrtNoiseReport)]),
+        "mrt_read_noise": (i32, [vp, vp, sz]),
+        "mrt_read_noise_tiles": (i32, [vp, vp, sz, P(u32), P(u32)]),
+        "mrt_noise_factor": (C.c_double, [u32, f32]),
+        "mrt_debug_noise_reduce": (i32, [vp, vp, vp, u32, u32, C.c_double, f32, f32, P(MrtNoiseReport), vp]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

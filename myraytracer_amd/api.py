@@ -545,6 +545,98 @@ class State:
                     "mrt_debug_present_encode")
         return out
 
+    # -- noise estimate (include/myraytracer_amd.h, "noise estimate"): the per-texel luminance variance of the accumulation and
+    #    an image-level report, computed on the device and read back without waiting for the frames in flight
+    def set_noise_tracking(self, enabled: bool):
+        """Turn noise tracking on / off; only while frames_done == 0 (after creation or reset()).  Survives reset()."""
+        self._check(self._L.mrt_set_noise_tracking(self._ctx, int(enabled)), "mrt_set_noise_tracking")
+
+    def noise_query(self, threshold: float = 0.02, floor: float = 0.01):
+        """Queue the noise report of the most recent frame (asynchronous).  threshold: the relative standard error above which a
+        pixel counts as noisy; floor: the luminance below which the relative error is taken against the floor instead."""
+        self._check(self._L.mrt_noise_query(self._ctx, threshold, floor), "mrt_noise_query")
+
+    def noise_result(self, wait: bool = True) -> Optional[dict]:
+        """The newest finished report as a dict, or None if none has finished (wait=False) or none was queued.  wait=True waits
+        (bounded) for the newest queued report, never for frames queued after it."""
+        r = _lib.MrtNoiseReport()
+        self._check(self._L.mrt_noise_result(self._ctx, int(wait), C.byref(r)), "mrt_noise_result")
+        return noise_report_dict(r) if r.seq else None
+
+    def read_noise(self) -> np.ndarray:
+        """S, the per-texel luminance variance of the accumulation: (H, W) f32 (world == 1, row 0 = bottom) or this shard's
+        packed (local_rows, W).  Waits for the frames in flight, as read_framebuffer does."""
+        _, world, rows, width = self.shard_info()
+        out = np.empty((self.args.height if world == 1 else rows, width), np.float32)
+        self._check(self._L.mrt_read_noise(self._ctx, out.ctypes.data, out.size), "mrt_read_noise")
+        return out
+
+    def read_noise_tiles(self) -> np.ndarray:
+        """The latest query's per-8x8-tile maximum of the relative error: (tile rows, tiles_x) f32, numbered as the framebuffer's
+        bands (a shard's packed bands).  Waits for that query only."""
+        tx, tr = C.c_uint32(), C.c_uint32()
+        self._L.mrt_read_noise_tiles(self._ctx, None, 0, C.byref(tx), C.byref(tr))     # (the shape; the status comes below)
+        out = np.empty((tr.value, tx.value), np.float32)
+        self._check(self._L.mrt_read_noise_tiles(self._ctx, out.ctypes.data, out.size, C.byref(tx), C.byref(tr)),
+                    "mrt_read_noise_tiles")
+        return out
+
+    def render_until(self, target_rel_rmse: float, max_frames: int, check_every: int = 16, threshold: float = 0.02,
+                     floor: float = 0.01) -> Tuple[int, dict]:
+        """Render chunks of check_every frames until a noise report's rel_rmse <= target_rel_rmse or frames_done reaches
+        max_frames; returns (frames_done, report).  Keeps the pipeline full by lagging one check: chunk k + 1 is queued before
+        report k is waited for, so the stop overshoots the first report that meets the target by at most check_every frames
+        (the one lagged chunk); the report returned is that one (report['frames_done'] <= frames_done).  With seeded input
+        the stopping frame is deterministic.  At max_frames, the report is that of the final image.  Turns tracking on if it
+        is off and frames_done == 0."""
+        if check_every < 1 or max_frames < 0:
+            raise ValueError("render_until: check_every >= 1, max_frames >= 0")
+        if self.frames_done == 0:
+            self.set_noise_tracking(True)
+
+        def chunk():
+            n = min(check_every, max_frames - self.frames_done)
+            if n > 0:
+                self.render(n)
+
+        chunk()
+        self.noise_query(threshold, floor)
+        while True:
+            chunk()                                        # the lagged chunk: in flight while the previous report is read
+            rep = self.noise_result(wait=True)             # the newest queued: the check before that chunk
+            if rep["rel_rmse"] <= target_rel_rmse:
+                return self.frames_done, rep
+            if rep["frames_done"] >= max_frames:
+                return self.frames_done, rep
+            self.noise_query(threshold, floor)
+
+    def debug_noise_reduce(self, S: np.ndarray, rgba: np.ndarray, K: float, threshold: float = 0.02, floor: float = 0.01):
+        """The noise reduction on caller-supplied buffers (S: (rows, W) f32, rgba: (rows, W, 4) f32), synchronously:
+        (report dict, tile map (ceil(rows / 8), ceil(W / 8)) f32)."""
+        S = np.ascontiguousarray(S, np.float32)
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        rows, width = S.shape
+        assert rgba.shape == (rows, width, 4)
+        tiles = np.empty(((rows + 7) // 8, (width + 7) // 8), np.float32)
+        r = _lib.MrtNoiseReport()
+        self._check(self._L.mrt_debug_noise_reduce(self._ctx, S.ctypes.data, rgba.ctypes.data, width, rows, K, threshold, floor,
+                                                   C.byref(r), tiles.ctypes.data), "mrt_debug_noise_reduce")
+        return noise_report_dict(r), tiles
+
+
+def noise_report_dict(r) -> dict:
+    d = {k: getattr(r, k) for k, _ in _lib.MrtNoiseReport._fields_ if not k.startswith("reserved")}
+    for k in ("seq", "frames_done", "pixels", "non_finite", "above"):
+        d[k] = int(d[k])
+    for k in ("threshold", "floor", "noise_factor", "sum_var", "sum_lum", "rmse", "rel_rmse", "max_se"):
+        d[k] = float(d[k])
+    return d
+
+
+def noise_factor(frames_done: int, max_w: float) -> float:
+    """K after frames_done uninterrupted frames with mrt_frame_weight's weights (+inf for fewer than 2)."""
+    return float(_lib.load().mrt_noise_factor(frames_done, max_w))
+
 
 def gather(states: Sequence[State], root: int = 0):
     """mrt_gather: one process, len(states) contexts (states[i] = shard i of n); the full frame lands on states[root]."""

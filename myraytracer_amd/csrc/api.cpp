@@ -34,6 +34,9 @@ static_assert(sizeof(mrt_sphere) == 36, "mrt_sphere layout");
 static_assert(sizeof(mrt_camera) == 52, "mrt_camera layout");
 static_assert(sizeof(mrt_camera_raw) == 80, "mrt_camera_raw layout");
 static_assert(sizeof(mrt::SphereRec) == 16, "SphereRec layout");
+static_assert(sizeof(mrt_noise_report) == 96 && offsetof(mrt_noise_report, pixels) == 16 && offsetof(mrt_noise_report, threshold) == 40 &&
+              offsetof(mrt_noise_report, noise_factor) == 48 && offsetof(mrt_noise_report, max_se) == 88, "mrt_noise_report layout");
+static_assert(sizeof(mrt::NoiseSums) == 48, "NoiseSums layout");
 static_assert(sizeof(mrt_present_info) == 40 && offsetof(mrt_present_info, frames_done) == 8 &&
               offsetof(mrt_present_info, ring_depth) == 36, "mrt_present_info layout");
 
@@ -61,7 +64,28 @@ using mrt::fail;
 using mrt::local_texels;
 using mrt::total_bands;
 
+// noise tracking's per-texel buffers, sized like the framebuffers (mrt_set_noise_tracking)
+void free_noise_buffers(mrt_ctx* c) {
+    if (c->d_noise_s) (void)hipFree(c->d_noise_s);
+    if (c->d_noise_tiles) (void)hipFree(c->d_noise_tiles);
+    if (c->d_noise_partials) (void)hipFree(c->d_noise_partials);
+    c->d_noise_s = nullptr; c->d_noise_tiles = nullptr; c->d_noise_partials = nullptr;
+}
+
+int alloc_noise_buffers(mrt_ctx* c) {
+    free_noise_buffers(c);
+    const size_t n = local_texels(c) ? local_texels(c) : 1;
+    HIP_TRY(c, hipMalloc((void**)&c->d_noise_s, n * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(c->d_noise_s, 0, n * sizeof(float), c->stream));
+    HIP_TRY(c, hipMalloc((void**)&c->d_noise_tiles, (size_t)(c->n_tiles ? c->n_tiles : 1) * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(c->d_noise_tiles, 0, (size_t)(c->n_tiles ? c->n_tiles : 1) * sizeof(float), c->stream));
+    HIP_TRY(c, hipMalloc(&c->d_noise_partials, std::max<size_t>(mrt::noise_partials_bytes(c->args.width, c->local_bands), 64)));
+    c->noise_first = c->noise_seq + 1;          // (reports of the old geometry are discarded)
+    return MRT_OK;
+}
+
 void free_frame_buffers(mrt_ctx* c) {
+    free_noise_buffers(c);
     if (c->d_seeds) (void)hipFree(c->d_seeds);
     if (c->d_fb[0]) (void)hipFree(c->d_fb[0]);
     if (c->d_fb[1]) (void)hipFree(c->d_fb[1]);
@@ -136,6 +160,7 @@ int alloc_frame_buffers(mrt_ctx* c) {
                                    c->shard_world, c->local_bands, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "fill_seeds launch failed: %s", hipGetErrorString((hipError_t)e));
     c->target = 0;
+    if (c->noise_on) MRT_TRY(alloc_noise_buffers(c));
     return MRT_OK;
 }
 
@@ -148,6 +173,7 @@ void reset_locals(mrt_ctx* c) {
     c->locals.ray_depth = c->args.ray_depth;
     c->locals.framebuffer_weight = 0.0f;
     c->frames_done = 0;
+    c->noise_c2 = 1.0;
 }
 
 uint64_t splitmix64_at(uint64_t seed, uint64_t k) {
@@ -930,6 +956,11 @@ void mrt_destroy(mrt_ctx* c) {
     if (c->d_present_tables) (void)hipFree(c->d_present_tables);
     if (c->ev_presented) (void)hipEventDestroy(c->ev_presented);
     if (c->present_stream) (void)hipStreamDestroy(c->present_stream);
+    for (auto& E : c->noise_ring)
+        if (E.copied) (void)hipEventDestroy(E.copied);
+    if (c->d_noise_sums) (void)hipFree(c->d_noise_sums);
+    if (c->h_noise_sums) (void)hipHostFree(c->h_noise_sums);
+    if (c->noise_stream) (void)hipStreamDestroy(c->noise_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1607,8 +1638,9 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
         p.prev = c->d_fb[c->target ^ 1];         // framebuffers.secondary (lib.rs:265)
         p.locals.framebuffer_weight = c->locals.framebuffer_weight;
         if (!counter) { p.pix_acc = (char*)S.d_pix_acc + (size_t)b * n * 16; p.n_blocks = 1; }
-        int fe = mrt::launch_finalize(p, c->stream);
+        int fe = mrt::launch_finalize(p, c->stream, c->d_noise_s);
         if (fe) return fail(c, MRT_ERR_HIP, "finalize launch failed: %s", hipGetErrorString((hipError_t)fe));
+        c->noise_c2 = mrt::noise_c2_next(c->noise_c2, p.locals.framebuffer_weight);   // (the weight this blend used)
         c->target ^= 1;                                                       // framebuffers.swap(), lib.rs:299
         if (c->frames_done != UINT32_MAX) c->frames_done++;                   // saturating_add, lib.rs:300
         c->locals.framebuffer_weight = mrt_frame_weight(c->frames_done, c->args.max_framebuffer_weight);  // :301-304
@@ -2024,6 +2056,8 @@ int mrt_reset(mrt_ctx* c) {
     const size_t bytes = local_texels(c) * 4 * sizeof(float);
     HIP_TRY(c, hipMemsetAsync(c->d_fb[0], 0, bytes, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_fb[1], 0, bytes, c->stream));
+    if (c->d_noise_s) HIP_TRY(c, hipMemsetAsync(c->d_noise_s, 0, local_texels(c) * sizeof(float), c->stream));
+    c->noise_first = c->noise_seq + 1;          // (the reports not yet read are discarded)
     HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
     for (auto& S : c->slot)          // the tile queues' counters (normally left at zero by every finalize pass)
         if (S.d_sort_scratch) HIP_TRY(c, hipMemsetAsync(S.d_sort_scratch + 1024, 0, sizeof(uint32_t), c->stream));
@@ -2431,6 +2465,204 @@ int mrt_debug_present_encode(mrt_ctx* c, const float* rgba, uint32_t width, uint
     (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
     if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_present_encode failed: %s", hipGetErrorString(e));
+    return MRT_OK;
+}
+
+}  // extern "C"
+
+// ---- noise estimate (include/myraytracer_amd.h, "noise estimate") ----------------------------------------------------------
+// While tracking is on, every blend also updates S (finalize_tracked_kernel, kernels.hip) and the host follows c2 (noise_c2).
+// mrt_noise_query queues, on the ctx's stream right behind the most recent frame's blend, the reduction (noise.hip) into the
+// ring entry's device sums and the copy of those 48 bytes into pinned host memory, and records the entry's event; nothing
+// here waits for the frames in flight.  Ordering: S and the framebuffer the reduction reads are next written by blends queued
+// after it on the same stream; the scratch and the tile map are written only by reductions, in stream order.
+namespace {
+
+using NoiseEntry = mrt_ctx::NoiseEntry;
+constexpr uint32_t kNoiseRing = mrt_ctx::kNoiseRing;
+
+// the ring's pinned sums, device sums and events, kept from the first enable to mrt_destroy
+int ensure_noise_ring(mrt_ctx* c) {
+    if (!c->d_noise_sums) HIP_TRY(c, hipMalloc((void**)&c->d_noise_sums, kNoiseRing * sizeof(mrt::NoiseSums)));
+    if (!c->h_noise_sums) HIP_TRY(c, hipHostMalloc((void**)&c->h_noise_sums, kNoiseRing * sizeof(mrt::NoiseSums), hipHostMallocDefault));
+    for (auto& E : c->noise_ring)
+        if (!E.copied) HIP_TRY(c, hipEventCreateWithFlags(&E.copied, hipEventDisableTiming));
+    return MRT_OK;
+}
+
+// the report of the sums and what the host knew at query time; K = +inf is "no estimate yet" (every derived figure +inf,
+// without forming 0 * inf)
+void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s) {
+    r->pixels = s.pixels; r->non_finite = s.non_finite; r->above = s.above;
+    r->sum_lum = s.sum_l;
+    if (std::isinf(r->noise_factor)) {
+        r->sum_var = r->rmse = r->rel_rmse = INFINITY;
+        r->max_se = INFINITY;
+        return;
+    }
+    r->sum_var = s.sum_s * r->noise_factor;
+    r->max_se = s.max_se;
+    r->rmse = s.pixels ? std::sqrt(r->sum_var / (double)s.pixels) : 0.0;
+    r->rel_rmse = r->rmse > 0.0 ? r->rmse / (s.sum_l / (double)s.pixels) : 0.0;
+}
+
+bool noise_args_ok(float threshold, float floor_) { return std::isfinite(threshold) && std::isfinite(floor_) && floor_ >= 0.0f; }
+
+}  // namespace
+
+extern "C" {
+
+double mrt_noise_factor(uint32_t frames_done, float max_w) {
+    double c2 = 1.0;
+    for (uint32_t k = 0; k < frames_done; k++) {
+        const float w = mrt_frame_weight(k, max_w);
+        const double next = mrt::noise_c2_next(c2, w);
+        // a saturated weight stays saturated (mrt_frame_weight is non-decreasing up to there): c2 is at its fixed point
+        if (k != 0 && w == max_w && max_w < 0.99999988f && next == c2) break;
+        c2 = next;
+    }
+    return mrt::noise_factor_of(c2);
+}
+
+int mrt_set_noise_tracking(mrt_ctx* c, int enabled) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (c->frames_done != 0) return fail(c, MRT_ERR_STATE, "mrt_set_noise_tracking: frames already rendered; call mrt_reset first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((enabled != 0) == c->noise_on) return MRT_OK;
+    MRT_TRY(mrt::wait_all(c, __func__));
+    if (enabled) {
+        MRT_TRY(ensure_noise_ring(c));
+        MRT_TRY(alloc_noise_buffers(c));
+        c->noise_on = true;
+    } else {
+        free_noise_buffers(c);
+        c->noise_on = false;
+        c->noise_first = c->noise_seq + 1;
+    }
+    return MRT_OK;
+}
+
+int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_noise_query: noise tracking is off (mrt_set_noise_tracking)");
+    if (!noise_args_ok(threshold, floor_))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t seq = c->noise_seq + 1;
+    const uint32_t i = (uint32_t)(seq % kNoiseRing);
+    NoiseEntry& E = c->noise_ring[i];
+    if (seq > kNoiseRing) {           // the ring is full when the entry's previous report is still in flight
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_noise_query: the ring is full (report %llu)", (unsigned long long)(seq - kNoiseRing));
+        MRT_TRY(mrt::wait_event(c, E.copied, what));
+    }
+    const double K = mrt::noise_factor_of(c->noise_c2);
+    const int e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                           c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials,
+                                           c->d_noise_tiles, c->d_noise_sums + i, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(c->h_noise_sums + i, c->d_noise_sums + i, sizeof(mrt::NoiseSums), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(E.copied, c->stream));
+    E.report = mrt_noise_report{};
+    E.report.seq = seq;
+    E.report.frames_done = c->frames_done;
+    E.report.threshold = threshold; E.report.floor = floor_;
+    E.report.noise_factor = K;
+    c->noise_seq = seq;
+    return MRT_OK;
+}
+
+int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = mrt_noise_report{};
+    if (c->noise_seq < c->noise_first) return MRT_OK;                 // nothing queued (since the last reset)
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (wait) {
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_noise_result: report %llu", (unsigned long long)c->noise_seq);
+        MRT_TRY(mrt::wait_event(c, c->noise_ring[c->noise_seq % kNoiseRing].copied, what));
+    }
+    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    for (uint64_t seq = c->noise_seq; seq >= oldest; seq--) {        // the newest whose copy has landed (stream order)
+        const uint32_t i = (uint32_t)(seq % kNoiseRing);
+        const hipError_t q = hipEventQuery(c->noise_ring[i].copied);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+        if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_noise_result: %s", hipGetErrorString(q));
+        *out = c->noise_ring[i].report;
+        noise_fill(out, c->h_noise_sums[i]);
+        return MRT_OK;
+    }
+    return MRT_OK;
+}
+
+int mrt_read_noise(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_read_noise: noise tracking is off (mrt_set_noise_tracking)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->shard_world == 1) {
+        const size_t n = (size_t)c->args.width * c->args.height;
+        if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_noise: need %zu floats", n);
+        return copy_rows(c, c->d_noise_s, out, sizeof(float), false);
+    }
+    const size_t n = local_texels(c);
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_noise: need %zu floats", n);
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_noise_s, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
+    return MRT_OK;
+}
+
+int mrt_read_noise_tiles(mrt_ctx* c, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (tiles_x) *tiles_x = c->tiles_x;
+    if (tiles_rows) *tiles_rows = c->local_bands;
+    if (!c->noise_on || c->noise_seq < c->noise_first)
+        return fail(c, MRT_ERR_STATE, "mrt_read_noise_tiles: no noise query since tracking was enabled or the last reset");
+    if (!out) return MRT_ERR_INVALID_ARG;
+    const size_t n = c->n_tiles;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_noise_tiles: need %zu floats", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
+    // behind the latest query only: its copy's event, then the tile map on a stream of its own
+    HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[c->noise_seq % kNoiseRing].copied, 0));
+    if (n) HIP_TRY(c, hipMemcpyAsync(out, c->d_noise_tiles, n * sizeof(float), hipMemcpyDeviceToHost, c->noise_stream));
+    return mrt::wait_stream(c, c->noise_stream, __func__);
+}
+
+int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,
+                           float threshold, float floor_, mrt_noise_report* out, float* tiles_out) {
+    if (!c || !S || !rgba || !out || !width || !rows || (uint64_t)width * rows > (1ull << 28) || !noise_args_ok(threshold, floor_) ||
+        std::isnan(K) || K < 0.0)
+        return MRT_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * rows;
+    const uint32_t bands = (rows + mrt::kBandRows - 1) / mrt::kBandRows, tx = (width + mrt::kTileW - 1) / mrt::kTileW;
+    const size_t tiles = (size_t)bands * tx;
+    float *d_s = nullptr, *d_rgba = nullptr, *d_tiles = nullptr;
+    void* d_part = nullptr;
+    mrt::NoiseSums* d_sums = nullptr;
+    mrt::NoiseSums h{};
+    hipError_t e = hipMalloc((void**)&d_s, n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_rgba, n * 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_tiles, tiles * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_part, mrt::noise_partials_bytes(width, bands));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, sizeof h);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = (hipError_t)mrt::launch_noise_reduce(d_s, d_rgba, width, bands, rows, 0, 1, (float)K, threshold, floor_, d_part, d_tiles,
+                                                 d_sums, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_sums, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && tiles_out) e = hipMemcpyAsync(tiles_out, d_tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    int ws = MRT_OK;
+    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_noise_reduce");
+    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
+    for (void* p : {(void*)d_s, (void*)d_rgba, (void*)d_tiles, d_part, (void*)d_sums})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_noise_reduce failed: %s", hipGetErrorString(e));
+    *out = mrt_noise_report{};
+    out->threshold = threshold; out->floor = floor_;
+    out->noise_factor = K;
+    noise_fill(out, h);
     return MRT_OK;
 }
 

@@ -67,6 +67,8 @@ __device__ __forceinline__ V3 reflect3(V3 d, V3 n) {
 }
 // WGSL mix(e1, e2, e3) = e1*(1-e3) + e2*e3
 __device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
+// luminance as noise tracking defines it (finalize_tracked_kernel; noise.hip has the same)
+__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 // ---- Xoshiro128+ (shader.wgsl:36-94) -------------------------------------------------
 struct Rng { uint32_t s0, s1, s2, s3; uint32_t draws; };
@@ -1349,6 +1351,51 @@ __global__ void __launch_bounds__(64) finalize_kernel(const KParams P) {
     if (lane == 0 && tile == 0) *P.tile_queue = 0u;
 }
 
+// finalize_kernel<false> with noise tracking (mrt_set_noise_tracking): the same blend, which also updates the per-texel
+// luminance variance S (noise_s, the framebuffer's texel index; shard padding rows stay 0) by West's weighted recursion with
+// the blend's own weights:
+//   lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b,   d = lum(mean) - lum(prev.rgb),
+//   S' = (w == 0.0f) ? 0.0f : w * (S + (1.0f - w) * (d * d))
+// (a select at w == 0: NaN / Inf from before a reset does not survive it).  A kernel of its own rather than a template
+// argument of finalize_kernel, whose arguments and code (byte-identical) are thereby left as they were.
+__global__ void __launch_bounds__(64) finalize_tracked_kernel(const KParams P, float* __restrict__ noise_s) {
+    const uint32_t lane = threadIdx.x, tile = blockIdx.x;
+    const uint32_t W = P.locals.shape[0], H = P.locals.shape[1];
+    const uint32_t tile_x = tile % P.tiles_x, band = tile / P.tiles_x;
+    const uint32_t px = tile_x * kTileW + (lane & 7u);
+    const uint32_t py = (band * P.shard_world + P.shard_rank) * kBandRows + (lane >> 3);
+    const size_t texel = (size_t)(band * kBandRows + (lane >> 3)) * W + px;
+    uint32_t cost = 0;
+    if (px < W && py < H) {
+        PixAcc sa = reinterpret_cast<const PixAcc*>(P.pix_acc)[texel];
+        for (uint32_t b = 1; b < P.n_blocks; b++) {
+            const PixAcc sb = reinterpret_cast<const PixAcc*>(P.pix_acc)[(size_t)b * P.pix_stride + texel];
+            sa.r += sb.r; sa.g += sb.g; sa.b += sb.b; sa.cost += sb.cost;
+        }
+        cost = sa.cost;
+        const float n = (float)P.locals.samples_per_frame;
+        const V3 mean = v3(sa.r / n, sa.g / n, sa.b / n);
+        const float w = P.locals.framebuffer_weight;
+        const float4 prev = reinterpret_cast<const float4*>(P.prev)[texel];
+        float4 res;
+        res.x = mixf(mean.x, prev.x, w);
+        res.y = mixf(mean.y, prev.y, w);
+        res.z = mixf(mean.z, prev.z, w);
+        res.w = mixf(1.0f, prev.w, w);
+        reinterpret_cast<float4*>(P.out)[texel] = res;
+        const float d = lumf(mean.x, mean.y, mean.z) - lumf(prev.x, prev.y, prev.z);
+        const float s = noise_s[texel];
+        noise_s[texel] = w == 0.0f ? 0.0f : w * (s + (1.0f - w) * (d * d));
+    } else if (px < W) {
+        reinterpret_cast<float4*>(P.out)[texel] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // shard padding rows
+        noise_s[texel] = 0.0f;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const uint32_t o2 = __shfl_xor(cost, off); cost = cost > o2 ? cost : o2; }
+    if (lane == 0 && P.tile_cost) P.tile_cost[tile] = cost;
+    if (lane == 0 && tile == 0) *P.tile_queue = 0u;
+}
+
 // Seed texture (Subject::new, lib.rs:389-415) generated on the device: SplitMix64 (mrt_device.h) used as a
 // counter-based generator keyed by the GLOBAL pixel index, two outputs per pixel.
 __global__ void __launch_bounds__(256) fill_seeds_kernel(uint32_t* seeds, uint64_t seed, uint32_t W, uint32_t H,
@@ -1484,9 +1531,10 @@ int launch_debug_world_hit(const KParams& p, uint32_t n_waves, void* stream) {
 }
 
 // colour sums -> framebuffer (+ per-tile costs), one wave per 8x8 tile
-int launch_finalize(const KParams& p, void* stream) {
+int launch_finalize(const KParams& p, void* stream, float* noise_s) {
     if (p.n_tiles == 0) return 0;
-    hipLaunchKernelGGL((finalize_kernel<false>), dim3(p.n_tiles), dim3(64), 0, (hipStream_t)stream, p);
+    if (noise_s) hipLaunchKernelGGL(finalize_tracked_kernel, dim3(p.n_tiles), dim3(64), 0, (hipStream_t)stream, p, noise_s);
+    else hipLaunchKernelGGL((finalize_kernel<false>), dim3(p.n_tiles), dim3(64), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 

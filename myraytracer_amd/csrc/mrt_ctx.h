@@ -165,6 +165,26 @@ struct mrt_ctx {
     hipEvent_t ev_presented = nullptr;              // "the present kernel is done", on the ctx's stream (mode 0)
     float* d_present_tables = nullptr;              // present_thresholds() on the device
 
+    // noise estimate (mrt_set_noise_tracking / mrt_noise_query, api.cpp): S, updated by every blend while tracking is on; the
+    // reduction's scratch and tile map; a ring of reports, each the reduction's sums on the device, their copy in pinned host
+    // memory and the event that says the copy has landed.  Entry seq % kNoiseRing holds query seq.
+    static constexpr uint32_t kNoiseRing = 8;
+    struct NoiseEntry {
+        hipEvent_t copied = nullptr;
+        mrt_noise_report report{};                  // what the host knows at query time (seq, frames_done, K, threshold, floor)
+    };
+    bool noise_on = false;                          // mrt_set_noise_tracking
+    float* d_noise_s = nullptr;                     // local texels (allocated with the framebuffers while noise_on)
+    double noise_c2 = 1.0;                          // sum of the squared normalised weights of the frames blended so far
+    void* d_noise_partials = nullptr;
+    float* d_noise_tiles = nullptr;                 // n_tiles, the latest query's
+    mrt::NoiseSums* d_noise_sums = nullptr;         // kNoiseRing entries
+    mrt::NoiseSums* h_noise_sums = nullptr;         // pinned, kNoiseRing entries
+    NoiseEntry noise_ring[kNoiseRing];
+    uint64_t noise_seq = 0;                         // queries so far
+    uint64_t noise_first = 1;                       // the oldest query whose report may still be returned (mrt_reset)
+    hipStream_t noise_stream = nullptr;             // mrt_read_noise_tiles' copy, created on first use
+
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     // ring of HIP event pairs around the render kernel of the most recent redraws, frame f at f % kEventRing

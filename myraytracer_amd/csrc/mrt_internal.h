@@ -136,8 +136,9 @@ void set_global_error(const char* msg);
 // host-callable launchers (kernels.hip)
 // queue reset + n_waves persistent render waves (a pilot launch also runs its cost-only finalize)
 int launch_render(const KParams& p, bool pilot, uint32_t n_waves, void* stream, uint32_t* which = nullptr);
-// the per-tile finalize pass of a rendered frame: colour sums -> framebuffer, tile costs
-int launch_finalize(const KParams& p, void* stream);
+// the per-tile finalize pass of a rendered frame: colour sums -> framebuffer, tile costs; with noise_s (noise tracking: local
+// texels like the framebuffer) the blend also updates the per-texel luminance variance there (finalize_tracked_kernel)
+int launch_finalize(const KParams& p, void* stream, float* noise_s = nullptr);
 int launch_debug_world_hit(const KParams& p, uint32_t n_waves, void* stream);
 int render_waves_per_cu(int* out);
 // host only: {LDS bytes of one render workgroup, workgroups per CU} for p's scene layout; the work-stack capacity (entries)
@@ -169,5 +170,26 @@ int launch_present(const float* src, uint8_t* dst, uint32_t width, uint32_t rows
                    const float* d_tables, void* stream);
 // image_io.cpp, host: {colour, alpha} x 256 thresholds -- t[k] = the smallest float whose code is >= k (t[0] = -inf)
 const float* present_thresholds();
+
+// noise.hip: the noise report's sums over a context's texels (or a caller's buffers): S = local_bands x 8 rows of `width` floats,
+// rgba the framebuffer in the same texel order; local rows whose image row (shard rank of world) is >= height are skipped.
+// tiles: the per-8x8-tile maximum of rel_p, numbered as finalize_kernel numbers them (band x tiles_x + tile column).
+// partials: noise_partials_bytes(width, local_bands) of scratch.  Two kernels on `stream`; *out (device) gets the sums.
+struct NoiseSums {                  // 48 B
+    double sum_s, sum_l;
+    unsigned long long pixels, non_finite, above;
+    float max_se;
+    uint32_t pad;
+};
+size_t noise_partials_bytes(uint32_t width, uint32_t local_bands);
+// host: c2 after a blend of weight w (include/myraytracer_amd.h, "noise estimate"): w^2 c2 + (1 - w)^2, 1 at w == 0; and K
+inline double noise_c2_next(double c2, float w) {
+    const double wd = (double)w;
+    return w == 0.0f ? 1.0 : wd * wd * c2 + (1.0 - wd) * (1.0 - wd);
+}
+inline double noise_factor_of(double c2) { return c2 >= 1.0 ? __builtin_inf() : c2 / (1.0 - c2); }
+int launch_noise_reduce(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
+                        uint32_t rank, uint32_t world, float K, float threshold, float floor_, void* partials, float* tiles,
+                        NoiseSums* out, void* stream);
 
 }  // namespace mrt

@@ -8,7 +8,9 @@
 // process: one context per GPU, interleaved 8-row bands, one mrt_gather per frame onto the first device
 // (SURVEY.md 8e).  A device may be listed more than once (--devices 0,0 rehearses the path on one GPU).
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +25,9 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult]\n");
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N]]\n"
+        "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
+        "                      every --check-every frames (default 16); prints the final report\n");
 }
 
 int main(int argc, char** argv) {
@@ -34,7 +38,8 @@ int main(int argc, char** argv) {
     mrt_args args;
     mrt_args_default(&args);
     uint32_t frames = 1, warmup = 0, rng_mode = MRT_RNG_PIXEL_STREAM; uint64_t seed = 1; int device = 0;
-    uint32_t hint_div = 0, hint_mult = 0;
+    uint32_t hint_div = 0, hint_mult = 0, check_every = 16;
+    double target_noise = -1.0;
     std::string scene = "default", scene_file, save_scene, out;
     std::vector<int> devices;
     for (int i = 1; i < argc; i++) {
@@ -64,6 +69,8 @@ int main(int argc, char** argv) {
         }
         else if (a == "--out") out = v;
         else if (a == "--device") device = std::atoi(v.c_str());
+        else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
+        else if (a == "--check-every") check_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (a == "--gpus") { devices.clear(); for (int d = 0; d < std::atoi(v.c_str()); d++) devices.push_back(d); }
         else if (a == "--devices") {
             devices.clear();
@@ -112,7 +119,9 @@ int main(int argc, char** argv) {
         TRY(ctxs[i], mrt_set_camera(ctxs[i], &cam));
         if (rng_mode != MRT_RNG_PIXEL_STREAM) TRY(ctxs[i], mrt_set_rng_mode(ctxs[i], rng_mode));
         if (hint_div) TRY(ctxs[i], mrt_set_schedule_hint(ctxs[i], hint_div, hint_mult));
+        if (target_noise >= 0.0) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
     }
+    if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
         if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));
@@ -129,13 +138,59 @@ int main(int argc, char** argv) {
     auto t0 = std::chrono::steady_clock::now();
     // only the final accumulated image is wanted, so every GPU renders all its frames (mrt_render may share a launch
     // among several frames when its shard is too small to fill the GPU) and the shards are gathered once
-    for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, frames));                   // asynchronous: all GPUs render at once
+    mrt_noise_report report{};
+    if (target_noise < 0.0) {
+        for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, frames));               // asynchronous: all GPUs render at once
+    } else {
+        // --target-noise: chunks of check_every frames; chunk k + 1 is queued before report k is waited for (the pipeline stays
+        // full), so the stop overshoots the first report that meets the target by at most one chunk
+        uint32_t done = 0;
+        auto chunk = [&]() -> int {
+            const uint32_t k = std::min(check_every, frames - done);
+            for (mrt_ctx* c : ctxs)
+                if (k) { const int s_ = mrt_render(c, k); if (s_ != MRT_OK) return s_; }
+            done += k;
+            return MRT_OK;
+        };
+        auto query = [&]() -> int {
+            for (mrt_ctx* c : ctxs) { const int s_ = mrt_noise_query(c, 0.02f, 0.01f); if (s_ != MRT_OK) return s_; }
+            return MRT_OK;
+        };
+        TRY(ctxs[0], chunk());
+        TRY(ctxs[0], query());
+        for (;;) {
+            TRY(ctxs[0], chunk());
+            // every context's report of the previous check, combined: counts and sums added, the largest max_se
+            mrt_noise_report r{};
+            for (uint32_t i = 0; i < n_gpus; i++) {
+                mrt_noise_report part{};
+                TRY(ctxs[i], mrt_noise_result(ctxs[i], 1, &part));
+                if (i == 0) { r = part; continue; }
+                r.pixels += part.pixels; r.non_finite += part.non_finite; r.above += part.above;
+                r.sum_var += part.sum_var; r.sum_lum += part.sum_lum;
+                r.max_se = std::max(r.max_se, part.max_se);
+            }
+            if (n_gpus > 1 && !std::isinf(r.noise_factor)) {
+                r.rmse = r.pixels ? std::sqrt(r.sum_var / (double)r.pixels) : 0.0;
+                r.rel_rmse = r.rmse > 0.0 ? r.rmse / (r.sum_lum / (double)r.pixels) : 0.0;
+            }
+            report = r;
+            if (r.rel_rmse <= target_noise || r.frames_done >= frames) break;
+            TRY(ctxs[0], query());
+        }
+        frames = done;
+    }
     if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));         // every shard's bands -> the first GPU
     for (mrt_ctx* c : ctxs) TRY(c, mrt_sync(c));
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const double samples = (double)args.width * args.height * args.samples_per_frame * frames;
     std::printf("%ux%u, %u spp x %u frames, depth %u, %d spheres, %u GPU(s): %.3f s, %.1f Msamples/s\n", args.width, args.height,
                 args.samples_per_frame, frames, args.ray_depth, n, n_gpus, sec, samples / sec * 1e-6);
+    if (target_noise >= 0.0)
+        std::printf("noise: %u frames used (target rel_rmse %g); report at frame %u: rel_rmse %.5g, rmse %.5g, max_se %.5g, "
+                    "%llu of %llu pixels above rel %.3g (%llu not finite)\n", frames, target_noise, report.frames_done,
+                    report.rel_rmse, report.rmse, (double)report.max_se, (unsigned long long)report.above,
+                    (unsigned long long)report.pixels, (double)report.threshold, (unsigned long long)report.non_finite);
     if (!out.empty()) {
         std::vector<float> fb((size_t)args.width * args.height * 4);
         if (n_gpus > 1) TRY(ctxs[0], mrt_read_gathered(ctxs[0], fb.data(), fb.size()));

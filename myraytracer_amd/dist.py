@@ -9,7 +9,8 @@ per row is very uneven (sky rows end at bounce 0).  Each of the 7 peers has its 
 link to the root, so a direct gather (grouped send/recv) uses all links at once; there is
 nothing to reduce, hence no ring collective.
 """
-from typing import Optional, Tuple
+import math
+from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -106,3 +107,32 @@ def gathered_tensor(root_state, device: Optional[torch.device] = None) -> torch.
         raise RuntimeError("nothing gathered yet")
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
     return torch.as_tensor(_DevicePtr(ptr, (root_state.args.height, root_state.args.width, 4)), device=dev)
+
+
+def combine_noise_reports(reports: Sequence[dict]) -> dict:
+    """The whole image's noise report from its shards' (State.noise_result of every rank, or all_gather_object'ed): counts and
+    sums added, max_se the largest, rmse / rel_rmse recomputed as the library computes them.  Refuses reports of different
+    accumulations (frames_done or noise_factor differ) or query parameters.  Host only, no collective."""
+    reports = list(reports)
+    if not reports:
+        raise ValueError("combine_noise_reports: no reports")
+    first = reports[0]
+    for r in reports[1:]:
+        for k in ("frames_done", "noise_factor", "threshold", "floor"):
+            if r[k] != first[k]:
+                raise ValueError(f"combine_noise_reports: {k} differs ({first[k]} vs {r[k]}): not one accumulation")
+    out = dict(first)
+    for k in ("pixels", "non_finite", "above"):
+        out[k] = sum(int(r[k]) for r in reports)
+    for k in ("sum_var", "sum_lum"):
+        out[k] = math.fsum(float(r[k]) for r in reports)
+    out["max_se"] = max(float(r["max_se"]) for r in reports)
+    out["seq"] = max(int(r["seq"]) for r in reports)
+    n = out["pixels"]
+    if math.isinf(out["noise_factor"]):
+        out["sum_var"] = out["rmse"] = out["rel_rmse"] = out["max_se"] = math.inf
+    else:
+        out["rmse"] = math.sqrt(out["sum_var"] / n) if n else 0.0
+        mean_lum = out["sum_lum"] / n if n else 0.0
+        out["rel_rmse"] = 0.0 if out["rmse"] <= 0.0 else (out["rmse"] / mean_lum if mean_lum else math.inf)
+    return out

@@ -3,6 +3,8 @@
    [MRT_HIER=levels,top] [MRT_BOXES=0|1] [MRT_RNG=1] [MRT_HINT=div,mult] [MRT_READ_EVERY=1] [MRT_SHARD=rank,world] [MRT_STEADY=1]
    [MRT_PRESENT_EVERY=1 (a viewer on the present pass: mrt_present after every redraw, the newest image acquired without waiting)]
    [MRT_PRESENT_COPY=0|1 (the present's copy on a stream of its own / on the context's stream)]
+   [MRT_NOISE=1 (noise tracking on, no queries)] [MRT_NOISE_EVERY=k (tracking on, mrt_noise_query every k frames, the newest
+    report taken without waiting)]
    python scripts/wall_rate.py scene w h spp steps"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,6 +30,10 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     if os.environ.get("MRT_PRESENT_COPY"):
         st.debug_set_present_copy(int(os.environ["MRT_PRESENT_COPY"]))
     acquired = 0
+    noise_every = int(os.environ.get("MRT_NOISE_EVERY", "0"))
+    if noise_every or os.environ.get("MRT_NOISE"):
+        st.set_noise_tracking(True)
+    reports = 0
     st.set_world(sp)
     if cam is not None: st.set_camera(cam)
     if os.environ.get("MRT_RNG"): st.set_rng_mode(int(os.environ["MRT_RNG"]))
@@ -37,13 +43,16 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     c0 = st.read_counters()
     t0 = time.perf_counter()
     stamps = []
-    for _ in range(steps):
+    for k in range(steps):
         st.redraw()
         stamps.append(time.perf_counter())         # (a call returns when the oldest frame in flight has ended: the back-pressure)
         if read_every: st.read_framebuffer()
         if present_every:
             st.present("bgra8", flip=shard is None)
             acquired += st.acquire_presented(newest=True, wait=False, copy=False) is not None
+        if noise_every and (k + 1) % noise_every == 0:
+            st.noise_query()
+            reports += st.noise_result(wait=False) is not None
     st.sync()
     dt = time.perf_counter() - t0
     present_note = f"presented every frame ({acquired} of {steps} acquired without waiting, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), "
@@ -53,6 +62,8 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
           f"{w * h * spp * steps / dt * 1e-6 / (shard[1] if shard else 1):.0f} Msamples/s, {dt / steps * 1e3:.1f} ms/step, lane util {util:.3f}, top {c1['sweep_records']}, "
           f"{'read back every frame, ' if read_every else ''}"
           f"{present_note if present_every else ''}"
+          f"{'noise tracking on, ' if os.environ.get('MRT_NOISE') and not noise_every else ''}"
+          f"{f'noise query every {noise_every} frames ({reports} results ready without waiting), ' if noise_every else ''}"
           f"schedule {st.get_schedule()}", flush=True)
     if os.environ.get("MRT_STEADY") and not read_every:
         # the pipelined rate WITHOUT the run's fill and drain: calls are paced by completions, so between the return of call a and
