@@ -38,7 +38,8 @@ extern "C" {
  * environment (GPU_MAX_HW_QUEUES is the host's to set: INTEGRATION.md 2a).  Version 4 later gained, additions only: the
  * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info);
  * the noise estimate (mrt_set_noise_tracking, mrt_noise_query, mrt_noise_result, mrt_read_noise, mrt_read_noise_tiles,
- * mrt_noise_factor, mrt_noise_report). */
+ * mrt_noise_factor, mrt_noise_report); the denoiser (mrt_denoise_params, mrt_denoise_params_default, mrt_set_denoise_params,
+ * mrt_get_denoise_params, mrt_read_denoised, MRT_PRESENT_DENOISED). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -293,6 +294,8 @@ enum {
     MRT_PRESENT_FLIP_Y = 1,    /* rows top-down, as on the surface (sample_framebuffer.wgsl:24) and in mrt_write_ppm */
     MRT_PRESENT_GATHERED = 2   /* the root's full frame from the latest mrt_gather / mrt_gather_rccl, not this ctx's framebuffer */
 };
+/* the denoised frame (mrt_read_denoised's image; "denoiser" below), not the framebuffer itself */
+#define MRT_PRESENT_DENOISED 8u
 enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
 typedef struct {               /* 40 bytes */
     uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
@@ -304,9 +307,11 @@ typedef struct {               /* 40 bytes */
 } mrt_present_info;
 /* Queues the present of the most recent frame (after mrt_render(k): its last frame) on the ctx's stream, behind that frame's
  * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB; flags: MRT_PRESENT_FLIP_Y |
- * MRT_PRESENT_GATHERED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed local rows in
- * mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full frame
- * (MRT_ERR_STATE before the first gather).  Must not be called while the ctx's stream is being captured into a graph. */
+ * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
+ * local rows in mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full
+ * frame (MRT_ERR_STATE before the first gather); DENOISED, the `height` rows of the denoised frame, queued on the same stream
+ * right before the encode (the guide rebuild if the guides are stale, then the filter; refusals as mrt_read_denoised's, and
+ * DENOISED | GATHERED: MRT_ERR_INVALID_ARG).  Must not be called while the ctx's stream is being captured into a graph. */
 int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
 /* A finished image: *pixels = rows x row_bytes bytes, valid until mrt_present_release, the next acquire, mrt_reset,
  * mrt_set_shard or mrt_destroy.  MRT_ACQUIRE_NEWEST (a viewer, mailbox): the most recent finished image; older finished ones are
@@ -373,6 +378,55 @@ int mrt_read_noise(mrt_ctx* ctx, float* out, size_t cap);
 int mrt_read_noise_tiles(mrt_ctx* ctx, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
 /* Host only: K after frames_done uninterrupted frames with the weights of mrt_frame_weight (+inf for frames_done < 2). */
 double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
+
+/* ------------------------------------------------------------------ denoiser (no reference counterpart)
+ *
+ * A variance-guided edge-aware a-trous filter (the spatial filter of SVGF; the accumulation is its temporal part) over the most
+ * recent frame, for a preview of a progressive render.  It needs noise tracking (mrt_set_noise_tracking: var = S * K below) and an
+ * unsharded context (world == 1: a shard's rows are interleaved bands without spatial neighbours); else MRT_ERR_STATE.
+ *
+ * Guides, per pixel, from ONE ray through the mean of the render's sample positions: the camera ray of u = v = 0.5
+ * (fs_main :373-381) through the look-at camera's lens centre (no defocus offset), normalised as the render normalises (MRT-F32),
+ * and its closest hit over [0.001, 1e4) found by the render kernel's own sweep and walk (mrt_debug_world_hit's):
+ *     index   the sphere hit, -1 on a miss
+ *     t       the hit's distance; +inf on a miss
+ *     normal  sphere_hit's normal facing the ray: (o + t d - centre) / radius, negated unless dot(normal, d) <= 0; -d on a miss
+ *     albedo  Lambertian / Metal: the material's albedo; Dielectric: (1, 1, 1); an unknown type: (0, 0, 0); a miss: (1, 1, 1)
+ * They are marked stale by mrt_set_camera, mrt_set_world* and mrt_set_shard and rebuilt, queued on the ctx's stream, at the next
+ * denoise (no host wait).
+ *
+ * Filter (float32, in this order; only + - * /, sqrtf, fminf, fmaxf).  Per texel, c = (r, g, b) and var: iteration 0 reads the
+ * framebuffer and var = S * (float)K.  Iteration i (0 .. iterations - 1) has step h = 2^i and taps q = p + h (dx, dy), dy then dx
+ * from -2 to 2, with k = {1/16, 1/4, 3/8, 1/4, 1/16}; a tap outside the image or not finite (a channel of c or var) is skipped:
+ *     tukey(x)   = x < 1 ? (1 - x * x)^2 : 0
+ *     L(c)       = (0.2126f * r + 0.7152f * g) + 0.0722f * b
+ *     w_lum      = tukey(|L_p - L_q| * (1 / (sigma_l * sqrtf(var_p) + 1e-6f)))           (1 when K = +inf)
+ *     w_normal   = max(0, (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z), squared normal_exp times
+ *     w_depth    = 1 if both miss, 0 if exactly one does, else tukey(|t_p - t_q| * (1 / (sigma_z * t_p)))
+ *     w_albedo   = tukey(max(|dr|, |dg|, |db|) * (1 / sigma_a))
+ *     w          = ((((k_x * k_y) * w_lum) * w_normal) * w_depth) * w_albedo;  the centre tap: k_2 * k_2 = 9/64, no stops
+ *     c'  = sum w c_q / sum w,   var' = sum (w * w) var_q / (sum w * sum w)     (sums in tap order, from 0)
+ * Passed through unchanged (c and var): a texel that is not finite, and -- K finite only -- a texel whose var is 0.  K = +inf (fewer
+ * than 2 frames) has no luminance stop and var = 0 for every finite S (no 0 * inf is formed).  Alpha is the framebuffer's. */
+typedef struct {                 /* 48 bytes */
+    uint32_t size;               /* sizeof(mrt_denoise_params): the version of this struct */
+    uint32_t iterations;         /* 1 .. 8 (default 5: steps 1 .. 16) */
+    float sigma_l;               /* luminance stop, in standard deviations: finite, > 0 (default 8) */
+    uint32_t normal_exp;         /* 0 .. 16 squarings: w_normal = dot^(2^normal_exp) (default 7: dot^128) */
+    float sigma_z;               /* relative distance stop: finite, > 0 (default 0.05) */
+    float sigma_a;               /* albedo stop: finite, > 0 (default 0.1) */
+    uint32_t reserved[6];        /* 0 */
+} mrt_denoise_params;
+/* Host only: the defaults. */
+void mrt_denoise_params_default(mrt_denoise_params* out);
+/* The parameters every later denoise of this ctx uses (MRT_ERR_INVALID_ARG outside the ranges above, size or reserved wrong).
+ * ctx NULL: checks the parameters only (host only). */
+int mrt_set_denoise_params(mrt_ctx* ctx, const mrt_denoise_params* params);
+int mrt_get_denoise_params(mrt_ctx* ctx, mrt_denoise_params* out);
+/* Denoises the most recent frame (queued on the ctx's stream behind its blend) and reads it back: height * width * 4 floats,
+ * row 0 = bottom, as mrt_read_framebuffer; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE with tracking off or on a
+ * shard, MRT_ERR_NO_SCENE without a scene. */
+int mrt_read_denoised(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

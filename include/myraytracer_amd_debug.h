@@ -32,6 +32,15 @@ int mrt_debug_set_present_copy(mrt_ctx* ctx, int mode);
  * tiles_out (may be NULL) gets ceil(rows / 8) x ceil(width / 8) tile maxima. */
 int mrt_debug_noise_reduce(mrt_ctx* ctx, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,
                            float threshold, float floor, mrt_noise_report* out, float* tiles_out);
+/* Diagnostic: the denoiser's filter (include/myraytracer_amd.h, "denoiser") on caller-supplied buffers, synchronously: rgba =
+ * rows x width RGBA32F texels, S = rows x width floats, K the noise factor (+inf allowed), guides = rows x width x 8 floats
+ * {normal x, y, z, t, albedo r, g, b, sphere index as int32 bits}; out = rows x width RGBA32F.  params NULL: the ctx's. */
+int mrt_debug_denoise(mrt_ctx* ctx, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,
+                      const mrt_denoise_params* params, float* out);
+/* Diagnostic: the ctx's guides (rebuilt first if stale), height x width pixels, row 0 = bottom: rays 6 floats (origin,
+ * direction), index 1 int32, t 1 float, normal 3 floats, albedo 3 floats per pixel; any pointer may be NULL.  cap_pixels >=
+ * width * height.  Synchronous.  MRT_ERR_STATE on a shard, MRT_ERR_NO_SCENE without a scene. */
+int mrt_debug_read_guides(mrt_ctx* ctx, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap_pixels);
 
 /* Diagnostic: make mrt_gather on this root use the cross-device form of the copy (one hipMemcpyPeerAsync per
  * band) even when a shard shares the root's device, so that its indexing runs on a one-GPU box. */

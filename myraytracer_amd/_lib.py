@@ -42,11 +42,13 @@ EXPORTS = [
     "mrt_debug_present_encode", "mrt_debug_set_present_copy",
     "mrt_set_noise_tracking", "mrt_noise_query", "mrt_noise_result", "mrt_read_noise", "mrt_read_noise_tiles", "mrt_noise_factor",
     "mrt_debug_noise_reduce",
+    "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
+    "mrt_debug_read_guides",
 ]
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
-PRESENT_FLIP_Y, PRESENT_GATHERED = 1, 2
+PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED = 1, 2, 8
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 
 
@@ -96,6 +98,11 @@ class MrtNoiseReport(C.Structure):
                 ("non_finite", C.c_uint64), ("above", C.c_uint64), ("threshold", C.c_float), ("floor", C.c_float),
                 ("noise_factor", C.c_double), ("sum_var", C.c_double), ("sum_lum", C.c_double), ("rmse", C.c_double),
                 ("rel_rmse", C.c_double), ("max_se", C.c_float), ("reserved2", C.c_uint32)]
+
+
+class MrtDenoiseParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_l", C.c_float), ("normal_exp", C.c_uint32),
+                ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("reserved", C.c_uint32 * 6)]
 
 
 class MrtSphere(C.Structure):
@@ -306,6 +313,12 @@ def load():
         "mrt_read_noise_tiles": (i32, [vp, vp, sz, P(u32), P(u32)]),
         "mrt_noise_factor": (C.c_double, [u32, f32]),
         "mrt_debug_noise_reduce": (i32, [vp, vp, vp, u32, u32, C.c_double, f32, f32, P(MrtNoiseReport), vp]),
+        "mrt_denoise_params_default": (None, [P(MrtDenoiseParams)]),
+        "mrt_set_denoise_params": (i32, [vp, P(MrtDenoiseParams)]),
+        "mrt_get_denoise_params": (i32, [vp, P(MrtDenoiseParams)]),
+        "mrt_read_denoised": (i32, [vp, vp, sz]),
+        "mrt_debug_denoise": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), vp]),
+        "mrt_debug_read_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

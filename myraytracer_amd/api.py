@@ -502,12 +502,13 @@ class State:
     #    waiting for the frames in flight
     _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB}
 
-    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False):
+    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False):
         """mrt_present: queue the most recent frame's 8-bit sRGB image ("rgba8" / "bgra8"; flip = rows top-down; gathered = the
-        root's full frame of the last gather).  Asynchronous."""
+        root's full frame of the last gather; denoise = the denoised frame, read_denoised's image).  Asynchronous."""
         if fmt not in self._PRESENT_FORMATS:
             raise ValueError(f"present: format {fmt!r} (rgba8, bgra8)")
-        flags = (_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0)
+        flags = ((_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0) |
+                 (_lib.PRESENT_DENOISED if denoise else 0))
         self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
 
     def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):
@@ -622,6 +623,83 @@ class State:
         self._check(self._L.mrt_debug_noise_reduce(self._ctx, S.ctypes.data, rgba.ctypes.data, width, rows, K, threshold, floor,
                                                    C.byref(r), tiles.ctypes.data), "mrt_debug_noise_reduce")
         return noise_report_dict(r), tiles
+
+    # -- denoiser (include/myraytracer_amd.h, "denoiser"): an edge-aware a-trous filter guided by S and by first-hit guides
+    def set_denoise_params(self, **kw):
+        """Change the named fields of the denoise parameters (iterations, sigma_l, normal_exp, sigma_z, sigma_a); the others keep
+        their current values."""
+        p = _lib.MrtDenoiseParams()
+        self._check(self._L.mrt_get_denoise_params(self._ctx, C.byref(p)), "mrt_get_denoise_params")
+        for k, v in kw.items():
+            if k not in DENOISE_FIELDS:
+                raise ValueError(f"set_denoise_params: unknown field {k!r} ({', '.join(DENOISE_FIELDS)})")
+            setattr(p, k, v)
+        self._check(self._L.mrt_set_denoise_params(self._ctx, C.byref(p)), "mrt_set_denoise_params")
+
+    def denoise_params(self) -> dict:
+        p = _lib.MrtDenoiseParams()
+        self._check(self._L.mrt_get_denoise_params(self._ctx, C.byref(p)), "mrt_get_denoise_params")
+        return denoise_params_dict(p)
+
+    def read_denoised(self) -> np.ndarray:
+        """The most recent frame, denoised: (H, W, 4) f32, row 0 = bottom.  Needs noise tracking and world == 1; waits for the
+        frames in flight, as read_framebuffer does."""
+        out = np.empty((self.args.height, self.args.width, 4), np.float32)
+        self._check(self._L.mrt_read_denoised(self._ctx, out.ctypes.data, out.size), "mrt_read_denoised")
+        return out
+
+    def debug_read_guides(self) -> dict:
+        """The denoiser's guides (rebuilt first if stale), row 0 = bottom: rays (H, W, 6), index (H, W) i32, t (H, W),
+        normal (H, W, 3), albedo (H, W, 3)."""
+        h, w = self.args.height, self.args.width
+        g = {"rays": np.empty((h, w, 6), np.float32), "index": np.empty((h, w), np.int32), "t": np.empty((h, w), np.float32),
+             "normal": np.empty((h, w, 3), np.float32), "albedo": np.empty((h, w, 3), np.float32)}
+        self._check(self._L.mrt_debug_read_guides(self._ctx, g["rays"].ctypes.data, g["index"].ctypes.data, g["t"].ctypes.data,
+                                                  g["normal"].ctypes.data, g["albedo"].ctypes.data, h * w), "mrt_debug_read_guides")
+        return g
+
+    def debug_denoise(self, rgba: np.ndarray, S: np.ndarray, K: float, guides: dict, params: Optional[dict] = None) -> np.ndarray:
+        """The filter on caller-supplied buffers, synchronously: rgba (rows, W, 4) f32, S (rows, W) f32, guides as
+        debug_read_guides returns them (index, t, normal, albedo); params: fields over the State's parameters."""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        S = np.ascontiguousarray(S, np.float32)
+        rows, width = S.shape
+        assert rgba.shape == (rows, width, 4)
+        g = pack_guides(guides)
+        assert g.shape == (rows, width, 8)
+        p = _lib.MrtDenoiseParams()
+        self._check(self._L.mrt_get_denoise_params(self._ctx, C.byref(p)), "mrt_get_denoise_params")
+        for k, v in (params or {}).items():
+            setattr(p, k, v)
+        out = np.empty_like(rgba)
+        self._check(self._L.mrt_debug_denoise(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows, C.byref(p),
+                                              out.ctypes.data), "mrt_debug_denoise")
+        return out
+
+
+DENOISE_FIELDS = ("iterations", "sigma_l", "normal_exp", "sigma_z", "sigma_a")
+
+
+def denoise_params_dict(p) -> dict:
+    return {k: (float(getattr(p, k)) if k.startswith("sigma") else int(getattr(p, k))) for k in DENOISE_FIELDS}
+
+
+def denoise_params_default() -> dict:
+    """mrt_denoise_params_default as a dict (host only)."""
+    p = _lib.MrtDenoiseParams()
+    _lib.load().mrt_denoise_params_default(C.byref(p))
+    return denoise_params_dict(p)
+
+
+def pack_guides(guides: dict) -> np.ndarray:
+    """{index, t, normal, albedo} -> (rows, W, 8) f32 {normal, t, albedo, index bits}: the layout mrt_debug_denoise reads."""
+    idx = np.ascontiguousarray(guides["index"], np.int32)
+    g = np.empty(idx.shape + (8,), np.float32)
+    g[..., 0:3] = guides["normal"]
+    g[..., 3] = guides["t"]
+    g[..., 4:7] = guides["albedo"]
+    g[..., 7] = idx.view(np.float32)
+    return g
 
 
 def noise_report_dict(r) -> dict:

@@ -1,0 +1,222 @@
+// The denoiser (include/myraytracer_amd.h, "denoiser"): first-hit guide buffers and a variance-guided,
+// edge-aware a-trous filter over the framebuffer (the spatial filter of SVGF without its temporal part: the accumulation is
+// the temporal part).  A translation unit of its own, outside the render path's (kernels.hip).
+//
+// Guides (once per camera / scene): guide_rays_kernel writes one ray per pixel through the mean of the render's sample
+// positions; the closest hits come from the DBG instantiation of render_kernel (launch_debug_world_hit, no candidate bitmap);
+// guide_fill_kernel turns them into the per-texel record the filter reads.
+// Filter: atrous_kernel, one launch per iteration, colour and variance ping-ponged as one float4.  Only + - * /, sqrtf, fminf,
+// fmaxf in a fixed order (-ffp-contract=off; hipcc's `/` and sqrtf are correctly rounded), so tests/denoise_ref.py restates it
+// bit for bit in float32 numpy.
+#include <hip/hip_runtime.h>
+#include "mrt_internal.h"
+
+namespace mrt {
+namespace {
+
+constexpr uint32_t kTileX = 32, kTileY = 8;          // one workgroup: 32 x 8 pixels (4 waves of 32 x 2)
+
+__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// Tukey's biweight: compact support, no transcendental
+__device__ __forceinline__ float tukey(float x) {
+    const float u = 1.0f - x * x;
+    return x < 1.0f ? u * u : 0.0f;
+}
+__device__ __forceinline__ bool finite4(float4 v) {
+    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z) && __builtin_isfinite(v.w);
+}
+
+// One ray per image pixel (world 1: texel = y * width + x), as render_kernel's new_sample_head makes a sample's camera ray
+// with u = v = 0.5 (fs_main :373-381) and, for the look-at camera, the lens centre; normalised as the render normalises
+// (WGSL normalize: v / sqrt(dot(v, v)), dot = fma(z, z, fma(y, y, x * x))).  6 floats per ray: origin, direction.
+__global__ void __launch_bounds__(256) guide_rays_kernel(float* __restrict__ rays, uint32_t width, uint32_t height,
+                                                         const mrt_camera_raw cam) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
+    if (x >= width) return;
+    const float pixel_side = 2.0f / (float)height;
+    const float base_x = (((float)x + 0.5f) - 0.5f * (float)width) * pixel_side;
+    const float base_y = (((float)y + 0.5f) - 0.5f * (float)height) * pixel_side;
+    const float vx = base_x + 0.5f * pixel_side, vy = base_y + 0.5f * pixel_side;
+    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {vx, vy, -1.0f};
+    if (cam.mode != 0) {
+        for (int k = 0; k < 3; k++) {
+            d[k] = (vx * cam.su[k] + vy * cam.sv[k]) - cam.fw[k];
+            o[k] = cam.origin[k];
+        }
+    }
+    const float len = __builtin_sqrtf(__builtin_fmaf(d[2], d[2], __builtin_fmaf(d[1], d[1], d[0] * d[0])));
+    float* r = rays + 6u * ((size_t)y * width + x);
+    r[0] = o[0]; r[1] = o[1]; r[2] = o[2];
+    r[3] = d[0] / len; r[4] = d[1] / len; r[5] = d[2] / len;
+}
+
+// hits {sphere | -1, bits of t} -> guides {n.x, n.y, n.z, t} {albedo r, g, b, bits of the sphere index}.  The normal is
+// sphere_hit's (shader.wgsl:298-309): at = o + t d, (at - centre) / radius, negated unless dot(normal, d) <= 0.
+// Albedo: Lambertian / Metal albedo, (1, 1, 1) for a Dielectric, (0, 0, 0) for an unknown type.  A miss: t = +inf,
+// normal = -d, albedo (1, 1, 1).
+__global__ void __launch_bounds__(256) guide_fill_kernel(const float* __restrict__ rays, const int32_t* __restrict__ hits,
+                                                         const float4* __restrict__ shade, const int32_t* __restrict__ mat_ty,
+                                                         float4* __restrict__ guides, uint32_t width) {
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
+    if (x >= width) return;
+    const size_t i = (size_t)y * width + x;
+    const float* r = rays + 6u * i;
+    const float ox = r[0], oy = r[1], oz = r[2], dx = r[3], dy = r[4], dz = r[5];
+    const int32_t s = hits[2u * i];
+    float4 g0, g1;
+    if (s < 0) {
+        g0 = make_float4(-dx, -dy, -dz, __builtin_inff());
+        g1 = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(-1));
+    } else {
+        const float t = __int_as_float(hits[2u * i + 1u]);
+        const float4 sh0 = shade[2u * s], sh1 = shade[2u * s + 1u];
+        float nx = ((ox + t * dx) - sh0.x) / sh0.w;
+        float ny = ((oy + t * dy) - sh0.y) / sh0.w;
+        float nz = ((oz + t * dz) - sh0.z) / sh0.w;
+        if (!(__builtin_fmaf(nz, dz, __builtin_fmaf(ny, dy, nx * dx)) <= 0.0f)) { nx = -nx; ny = -ny; nz = -nz; }
+        const int32_t ty = mat_ty[s];
+        const float a = ty == MRT_DIELECTRIC ? 1.0f : 0.0f;
+        const bool coloured = ty == MRT_LAMBERTIAN || ty == MRT_METAL;
+        g0 = make_float4(nx, ny, nz, t);
+        g1 = make_float4(coloured ? sh1.x : a, coloured ? sh1.y : a, coloured ? sh1.z : a, __int_as_float(s));
+    }
+    guides[2u * i] = g0;
+    guides[2u * i + 1u] = g1;
+}
+
+struct AtrousArgs {
+    const float4* fb;            // the frame (FIRST: its colour; LAST: its alpha)
+    const float* S;              // FIRST: the luminance variance S, var = S * K
+    const float4* in;            // not FIRST: (r, g, b, var) of the previous iteration
+    const float4* guides;        // 2 per texel
+    float4* out;                 // (r, g, b, var), LAST: (r, g, b, alpha of fb)
+    uint32_t width, height, step;
+    float K;                     // FIRST only; +inf: no luminance stop
+    uint32_t lum_stop;           // K finite
+    float sigma_l, sigma_z, inv_sigma_a;
+    uint32_t normal_exp;
+};
+
+// (r, g, b, var) of texel i.  FIRST: var = S * K; without a luminance stop (K = +inf) var = 0 for a finite S (so that 0 * inf
+// is never formed) and S itself otherwise (non-finite: the texel passes through).
+template <bool FIRST>
+__device__ __forceinline__ float4 load_cv(const AtrousArgs& A, size_t i) {
+    if (!FIRST) return A.in[i];
+    const float4 c = A.fb[i];
+    const float s = A.S[i];
+    const float var = A.lum_stop ? s * A.K : (__builtin_isfinite(s) ? 0.0f : s);
+    return make_float4(c.x, c.y, c.z, var);
+}
+
+// grid (ceil(W / 32), ceil(H / 8)), 32 x 8 threads; one pixel per thread.  Taps at offsets {-2..2} x step, rows then columns in
+// increasing order, B3-spline weights {1/16, 1/4, 3/8, 1/4, 1/16}; outside the image or not finite: skipped.  The centre tap
+// weighs (3/8)^2 without stops; any other tap k_x k_y w_lum w_normal w_depth w_albedo, multiplied in that order.
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = load_cv<FIRST>(A, i);
+    float4 res = cp;
+    // passed through: not finite, or (with a luminance stop) a variance of 0
+    if (finite4(cp) && !(A.lum_stop && cp.w == 0.0f)) {
+        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+        const bool miss_p = __float_as_int(gp1.w) < 0;
+        const float lp = lumf(cp.x, cp.y, cp.z);
+        const float inv_l = A.lum_stop ? 1.0f / (A.sigma_l * sqrtf(cp.w) + 1.0e-6f) : 0.0f;
+        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+        const float kern[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+        float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+        const int step = (int)A.step;
+#pragma unroll
+        for (int ty = 0; ty < 5; ty++) {
+            const int yq = (int)y + (ty - 2) * step;
+            if (yq < 0 || yq >= (int)A.height) continue;
+#pragma unroll
+            for (int tx = 0; tx < 5; tx++) {
+                const int xq = (int)x + (tx - 2) * step;
+                if (xq < 0 || xq >= (int)A.width) continue;
+                const float kxy = kern[tx] * kern[ty];
+                float w;
+                float4 cq;
+                if (tx == 2 && ty == 2) {
+                    cq = cp;
+                    w = kxy;
+                } else {
+                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                    cq = load_cv<FIRST>(A, q);
+                    if (!finite4(cq)) continue;
+                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                    const bool miss_q = __float_as_int(gq1.w) < 0;
+                    const float wl = A.lum_stop ? tukey(fabsf(lp - lumf(cq.x, cq.y, cq.z)) * inv_l) : 1.0f;
+                    float wn = fmaxf(0.0f, (gp0.x * gq0.x + gp0.y * gq0.y) + gp0.z * gq0.z);
+                    for (uint32_t e = 0; e < A.normal_exp; e++) wn = wn * wn;
+                    const float wz = miss_p != miss_q ? 0.0f : miss_p ? 1.0f : tukey(fabsf(gp0.w - gq0.w) * inv_z);
+                    const float da = fmaxf(fmaxf(fabsf(gp1.x - gq1.x), fabsf(gp1.y - gq1.y)), fabsf(gp1.z - gq1.z));
+                    const float wa = tukey(da * A.inv_sigma_a);
+                    w = kxy * wl;
+                    w = w * wn;
+                    w = w * wz;
+                    w = w * wa;
+                }
+                sw = sw + w;
+                sr = sr + w * cq.x;
+                sg = sg + w * cq.y;
+                sb = sb + w * cq.z;
+                sv = sv + (w * w) * cq.w;
+            }
+        }
+        res = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+    }
+    if (LAST) res.w = A.fb[i].w;
+    A.out[i] = res;
+}
+
+}  // namespace
+
+int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream) {
+    if (width == 0 || height == 0) return 0;
+    hipLaunchKernelGGL(guide_rays_kernel, dim3((width + 255) / 256, height), dim3(256), 0, (hipStream_t)stream, rays, width,
+                       height, cam);
+    return (int)hipGetLastError();
+}
+
+int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade, const int32_t* mat_ty, float* guides,
+                      uint32_t width, uint32_t height, void* stream) {
+    if (width == 0 || height == 0) return 0;
+    hipLaunchKernelGGL(guide_fill_kernel, dim3((width + 255) / 256, height), dim3(256), 0, (hipStream_t)stream, rays, hits,
+                       reinterpret_cast<const float4*>(shade), mat_ty, reinterpret_cast<float4*>(guides), width);
+    return (int)hipGetLastError();
+}
+
+int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, void* stream) {
+    if (width == 0 || height == 0) return 0;
+    AtrousArgs A;
+    A.fb = reinterpret_cast<const float4*>(fb);
+    A.S = S;
+    A.guides = reinterpret_cast<const float4*>(guides);
+    A.width = width; A.height = height;
+    A.K = K;
+    A.lum_stop = __builtin_isinf(K) ? 0u : 1u;
+    A.sigma_l = prm.sigma_l; A.sigma_z = prm.sigma_z;
+    A.inv_sigma_a = 1.0f / prm.sigma_a;
+    A.normal_exp = prm.normal_exp;
+    const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
+    hipStream_t st = (hipStream_t)stream;
+    float4* buf[2] = {reinterpret_cast<float4*>(ping), reinterpret_cast<float4*>(pong)};
+    const uint32_t n = prm.iterations;
+    for (uint32_t it = 0; it < n; it++) {
+        const bool first = it == 0, last = it + 1 == n;
+        A.step = 1u << it;
+        A.in = first ? nullptr : buf[(it - 1) & 1u];
+        A.out = last ? reinterpret_cast<float4*>(out) : buf[it & 1u];
+        if (first && last) hipLaunchKernelGGL((atrous_kernel<true, true>), grid, block, 0, st, A);
+        else if (first) hipLaunchKernelGGL((atrous_kernel<true, false>), grid, block, 0, st, A);
+        else if (last) hipLaunchKernelGGL((atrous_kernel<false, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, st, A);
+    }
+    return (int)hipGetLastError();
+}
+
+}  // namespace mrt

@@ -185,6 +185,21 @@ struct mrt_ctx {
     uint64_t noise_first = 1;                       // the oldest query whose report may still be returned (mrt_reset)
     hipStream_t noise_stream = nullptr;             // mrt_read_noise_tiles' copy, created on first use
 
+    // denoiser (mrt_read_denoised / MRT_PRESENT_DENOISED, api.cpp; denoise.hip): the parameters, the first-hit guides of the
+    // current camera and scene (width x height pixels, y * width + x; rebuilt on the ctx's stream at the next denoise after
+    // mrt_set_camera / mrt_set_world* / mrt_set_shard mark them stale) and the filter's buffers, all allocated at the first use
+    mrt_denoise_params denoise = mrt::denoise_defaults();
+    bool guides_stale = true;
+    float* d_guide_rays = nullptr;                  // 6 floats per pixel
+    int32_t* d_guide_hits = nullptr;                // {sphere | -1, bits of t} per pixel (the DBG render kernel's output)
+    // the DBG kernel's candidate bitmap, which nothing reads: one word per pixel + one per 32 spheres, every pixel's row starting
+    // one word after the previous pixel's (dbg_words = 1) -- a full bitmap would be ceil(spheres / 32) words per pixel
+    uint32_t* d_guide_cand = nullptr;
+    size_t guide_cand_words = 0;
+    uint32_t* d_guide_queue = nullptr;              // the DBG launch's tile queue counter
+    float* d_guides = nullptr;                      // 2 float4 per pixel
+    float* d_den[3] = {nullptr, nullptr, nullptr};  // ping, pong, the denoised frame: a float4 per pixel
+
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     // ring of HIP event pairs around the render kernel of the most recent redraws, frame f at f % kEventRing

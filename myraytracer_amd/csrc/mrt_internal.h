@@ -192,4 +192,21 @@ int launch_noise_reduce(const float* S, const float* rgba, uint32_t width, uint3
                         uint32_t rank, uint32_t world, float K, float threshold, float floor_, void* partials, float* tiles,
                         NoiseSums* out, void* stream);
 
+// denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
+// launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
+// pixel (launch_debug_world_hit) -> 2 float4 per pixel {normal, t} {albedo, bits of the index}; shade / mat_ty: KParams' shade and
+// the spheres' material types (i32_data + material_ty_base_idx).  launch_denoise: prm.iterations launches; ping / pong: scratch of
+// width x height float4 each (unused for 1 iteration / ping only for 2); out: width x height RGBA32F.
+int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream);
+int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade, const int32_t* mat_ty, float* guides,
+                      uint32_t width, uint32_t height, void* stream);
+int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, void* stream);
+inline mrt_denoise_params denoise_defaults() {
+    mrt_denoise_params p{};
+    p.size = sizeof(mrt_denoise_params);
+    p.iterations = 5; p.sigma_l = 8.0f; p.normal_exp = 7; p.sigma_z = 0.05f; p.sigma_a = 0.1f;   // tuned: profiles/denoise_quality.txt
+    return p;
+}
+
 }  // namespace mrt

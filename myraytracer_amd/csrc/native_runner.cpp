@@ -25,9 +25,10 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult] [--target-noise REL [--check-every N]]\n"
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N]] [--denoise-out FILE]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
-        "                      every --check-every frames (default 16); prints the final report\n");
+        "                      every --check-every frames (default 16); prints the final report\n"
+        "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png; one GPU)\n");
 }
 
 int main(int argc, char** argv) {
@@ -40,7 +41,7 @@ int main(int argc, char** argv) {
     uint32_t frames = 1, warmup = 0, rng_mode = MRT_RNG_PIXEL_STREAM; uint64_t seed = 1; int device = 0;
     uint32_t hint_div = 0, hint_mult = 0, check_every = 16;
     double target_noise = -1.0;
-    std::string scene = "default", scene_file, save_scene, out;
+    std::string scene = "default", scene_file, save_scene, out, denoise_out;
     std::vector<int> devices;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], v;
@@ -68,6 +69,7 @@ int main(int argc, char** argv) {
             if (std::sscanf(v.c_str(), "%u,%u", &hint_div, &hint_mult) != 2) { std::fprintf(stderr, "--schedule wants div,mult\n"); return 2; }
         }
         else if (a == "--out") out = v;
+        else if (a == "--denoise-out") denoise_out = v;
         else if (a == "--device") device = std::atoi(v.c_str());
         else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
         else if (a == "--check-every") check_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
@@ -119,8 +121,9 @@ int main(int argc, char** argv) {
         TRY(ctxs[i], mrt_set_camera(ctxs[i], &cam));
         if (rng_mode != MRT_RNG_PIXEL_STREAM) TRY(ctxs[i], mrt_set_rng_mode(ctxs[i], rng_mode));
         if (hint_div) TRY(ctxs[i], mrt_set_schedule_hint(ctxs[i], hint_div, hint_mult));
-        if (target_noise >= 0.0) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
+        if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
     }
+    if (!denoise_out.empty() && n_gpus > 1) { std::fprintf(stderr, "--denoise-out wants one GPU (a shard has no neighbours)\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
@@ -191,16 +194,25 @@ int main(int argc, char** argv) {
                     "%llu of %llu pixels above rel %.3g (%llu not finite)\n", frames, target_noise, report.frames_done,
                     report.rel_rmse, report.rmse, (double)report.max_se, (unsigned long long)report.above,
                     (unsigned long long)report.pixels, (double)report.threshold, (unsigned long long)report.non_finite);
+    auto write_image = [&](const std::string& path, const std::vector<float>& fb) -> int {
+        const std::string ext = path.size() > 4 ? path.substr(path.size() - 4) : "";
+        int s2 = ext == ".ppm" ? mrt_write_ppm(path.c_str(), fb.data(), args.width, args.height)
+               : ext == ".png" ? mrt_write_png(path.c_str(), fb.data(), args.width, args.height)
+                               : mrt_write_pfm(path.c_str(), fb.data(), args.width, args.height);
+        if (s2 != MRT_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        std::printf("wrote %s\n", path.c_str());
+        return 0;
+    };
     if (!out.empty()) {
         std::vector<float> fb((size_t)args.width * args.height * 4);
         if (n_gpus > 1) TRY(ctxs[0], mrt_read_gathered(ctxs[0], fb.data(), fb.size()));
         else TRY(ctxs[0], mrt_read_framebuffer(ctxs[0], fb.data(), fb.size()));
-        const std::string ext = out.size() > 4 ? out.substr(out.size() - 4) : "";
-        int s2 = ext == ".ppm" ? mrt_write_ppm(out.c_str(), fb.data(), args.width, args.height)
-               : ext == ".png" ? mrt_write_png(out.c_str(), fb.data(), args.width, args.height)
-                               : mrt_write_pfm(out.c_str(), fb.data(), args.width, args.height);
-        if (s2 != MRT_OK) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); destroy_all(); return 1; }
-        std::printf("wrote %s\n", out.c_str());
+        if (write_image(out, fb)) { destroy_all(); return 1; }
+    }
+    if (!denoise_out.empty()) {
+        std::vector<float> fb((size_t)args.width * args.height * 4);
+        TRY(ctxs[0], mrt_read_denoised(ctxs[0], fb.data(), fb.size()));
+        if (write_image(denoise_out, fb)) { destroy_all(); return 1; }
     }
     destroy_all();
     return 0;

@@ -3,6 +3,8 @@
    [MRT_HIER=levels,top] [MRT_BOXES=0|1] [MRT_RNG=1] [MRT_HINT=div,mult] [MRT_READ_EVERY=1] [MRT_SHARD=rank,world] [MRT_STEADY=1]
    [MRT_PRESENT_EVERY=1 (a viewer on the present pass: mrt_present after every redraw, the newest image acquired without waiting)]
    [MRT_PRESENT_COPY=0|1 (the present's copy on a stream of its own / on the context's stream)]
+   [MRT_PRESENT_DENOISE=1 (the presents are denoised: noise tracking on, MRT_PRESENT_DENOISED; with MRT_PRESENT_EVERY=k, every k
+    frames)]
    [MRT_NOISE=1 (noise tracking on, no queries)] [MRT_NOISE_EVERY=k (tracking on, mrt_noise_query every k frames, the newest
     report taken without waiting)]
    python scripts/wall_rate.py scene w h spp steps"""
@@ -26,12 +28,13 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     if os.environ.get("MRT_HINT"):              # "div,mult": pin the launch schedule
         st.set_schedule_hint(*[int(x) for x in os.environ["MRT_HINT"].split(",")])
     read_every = bool(os.environ.get("MRT_READ_EVERY"))     # a viewer: the framebuffer is read back after every redraw
-    present_every = bool(os.environ.get("MRT_PRESENT_EVERY"))
+    present_every = int(os.environ.get("MRT_PRESENT_EVERY", "0") or "0")      # 1: after every redraw; k: every k-th
+    present_denoise = bool(os.environ.get("MRT_PRESENT_DENOISE"))
     if os.environ.get("MRT_PRESENT_COPY"):
         st.debug_set_present_copy(int(os.environ["MRT_PRESENT_COPY"]))
     acquired = 0
     noise_every = int(os.environ.get("MRT_NOISE_EVERY", "0"))
-    if noise_every or os.environ.get("MRT_NOISE"):
+    if noise_every or os.environ.get("MRT_NOISE") or present_denoise:
         st.set_noise_tracking(True)
     reports = 0
     st.set_world(sp)
@@ -47,15 +50,16 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
         st.redraw()
         stamps.append(time.perf_counter())         # (a call returns when the oldest frame in flight has ended: the back-pressure)
         if read_every: st.read_framebuffer()
-        if present_every:
-            st.present("bgra8", flip=shard is None)
+        if present_every and (k + 1) % present_every == 0:
+            st.present("bgra8", flip=shard is None, denoise=present_denoise)
             acquired += st.acquire_presented(newest=True, wait=False, copy=False) is not None
         if noise_every and (k + 1) % noise_every == 0:
             st.noise_query()
             reports += st.noise_result(wait=False) is not None
     st.sync()
     dt = time.perf_counter() - t0
-    present_note = f"presented every frame ({acquired} of {steps} acquired without waiting, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), "
+    present_note = (f"presented{' denoised' if present_denoise else ''} every {'frame' if present_every == 1 else f'{present_every} frames'} "
+                    f"({acquired} of {steps // max(present_every, 1)} acquired without waiting, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), ")
     c1 = st.read_counters()
     util = (c1["world_hit_calls"] - c0["world_hit_calls"]) / max(1, c1["lane_slots"] - c0["lane_slots"])
     print(f"{scene} {w}x{h}x{spp} HIER={os.environ.get('MRT_HIER')} BOXES={os.environ.get('MRT_BOXES')} RNG={os.environ.get('MRT_RNG')}: "
