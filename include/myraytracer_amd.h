@@ -39,7 +39,8 @@ extern "C" {
  * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info);
  * the noise estimate (mrt_set_noise_tracking, mrt_noise_query, mrt_noise_result, mrt_read_noise, mrt_read_noise_tiles,
  * mrt_noise_factor, mrt_noise_report); the denoiser (mrt_denoise_params, mrt_denoise_params_default, mrt_set_denoise_params,
- * mrt_get_denoise_params, mrt_read_denoised, MRT_PRESENT_DENOISED). */
+ * mrt_get_denoise_params, mrt_read_denoised, MRT_PRESENT_DENOISED); adaptive sampling (mrt_render_tiles, mrt_render_adaptive,
+ * mrt_read_tile_frames). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -378,6 +379,39 @@ int mrt_read_noise(mrt_ctx* ctx, float* out, size_t cap);
 int mrt_read_noise_tiles(mrt_ctx* ctx, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
 /* Host only: K after frames_done uninterrupted frames with the weights of mrt_frame_weight (+inf for frames_done < 2). */
 double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
+
+/* ------------------------------------------------------------------ adaptive sampling (no reference counterpart)
+ *
+ * More frames where the noise estimate says the image is still noisy.  Tiles are the 8x8 tiles of mrt_read_noise_tiles:
+ * tile = band * tiles_x + column, band = row / 8, row 0 at the bottom.  Each tile has a frame count n_t: the frames blended into
+ * it since mrt_create or mrt_reset.
+ *   Subset frame: renders every pixel of the listed tiles at samples_per_frame and blends them.  It takes the next frame number
+ *     as mrt_redraw does (frames_done += 1, shuffle mrt_frame_shuffle(seed, frames_done)).  In tile t the blend weight is
+ *     w = mrt_frame_weight(n_t, max_framebuffer_weight), the weight a uniform accumulation of n_t frames would use; S is updated
+ *     with the same w by the noise estimate's recursion; then n_t += 1 (saturating).  Tiles not listed keep their framebuffer
+ *     texels and S bit for bit.
+ *   Divergence: until the first subset frame of an accumulation every n_t == frames_done and nothing differs from a uniform
+ *     accumulation.  After it, mrt_redraw / mrt_render frames are whole frames blended per tile; mrt_reset returns to the
+ *     uniform state.
+ *   Noise reports after divergence: per finite pixel var_p = S_p * (float)K(n_t), K(n) = mrt_noise_factor(n, max_w) (K = +inf:
+ *     se_p = +inf); se, rel, above and the tile map follow as before; sum_var = sum of S_p * K(n_t) in double; noise_factor = the
+ *     largest K over the tiles (the least-sampled tile's).  Before divergence reports are unchanged.
+ *   Denoising after divergence (mrt_read_denoised, MRT_PRESENT_DENOISED) is refused with MRT_ERR_STATE; presents and read-backs
+ *   work unchanged.  Shards (world > 1) are refused with MRT_ERR_STATE. */
+/* Queues `frames` consecutive subset frames over the n tiles of `tiles` (asynchronous, with mrt_render's back-pressure).
+ * n == 0: MRT_OK, nothing queued.  An id >= the tile count, a duplicate id or tiles == NULL: MRT_ERR_INVALID_ARG; a shard:
+ * MRT_ERR_STATE; no scene: MRT_ERR_NO_SCENE; counter-RNG mode with samples_per_frame > MRT_COUNTER_BLOCK: MRT_ERR_INVALID_ARG.
+ * A list of every tile renders whole frames: while the accumulation is uniform, exactly mrt_render's. */
+int mrt_render_tiles(mrt_ctx* ctx, const uint32_t* tiles, size_t n, uint32_t frames);
+/* Selects the tiles whose tile-map entry in one noise report is > that report's threshold (the tiles holding a pixel counted in
+ * its `above`) and renders `frames` subset frames over them (mrt_render_tiles).  report_seq == 0: the newest finished report,
+ * without waiting (none finished: every tile); report_seq == k: report k, waiting (bounded) for that query only.  A report not
+ * queued, or older than the ring of 8: MRT_ERR_STATE; tracking off: MRT_ERR_STATE.  *used_seq = the report used (0: none),
+ * *tiles_selected = the selection's size (either may be NULL).  No tile selected: MRT_OK and nothing queued (converged). */
+int mrt_render_adaptive(mrt_ctx* ctx, uint32_t frames, uint64_t report_seq, uint64_t* used_seq, uint32_t* tiles_selected);
+/* n_t per tile, tiles_rows rows of tiles_x (frames_done everywhere while the accumulation is uniform); synchronises as
+ * mrt_read_framebuffer does. */
+int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
 
 /* ------------------------------------------------------------------ denoiser (no reference counterpart)
  *

@@ -44,6 +44,7 @@ EXPORTS = [
     "mrt_debug_noise_reduce",
     "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
     "mrt_debug_read_guides",
+    "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -319,6 +320,9 @@ def load():
         "mrt_read_denoised": (i32, [vp, vp, sz]),
         "mrt_debug_denoise": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), vp]),
         "mrt_debug_read_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
+        "mrt_render_tiles": (i32, [vp, vp, sz, u32]),
+        "mrt_render_adaptive": (i32, [vp, u32, C.c_uint64, P(C.c_uint64), P(u32)]),
+        "mrt_read_tile_frames": (i32, [vp, vp, sz, P(u32), P(u32)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

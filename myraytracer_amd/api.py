@@ -583,33 +583,68 @@ class State:
         return out
 
     def render_until(self, target_rel_rmse: float, max_frames: int, check_every: int = 16, threshold: float = 0.02,
-                     floor: float = 0.01) -> Tuple[int, dict]:
+                     floor: float = 0.01, adaptive: bool = False) -> Tuple[int, dict]:
         """Render chunks of check_every frames until a noise report's rel_rmse <= target_rel_rmse or frames_done reaches
         max_frames; returns (frames_done, report).  Keeps the pipeline full by lagging one check: chunk k + 1 is queued before
         report k is waited for, so the stop overshoots the first report that meets the target by at most check_every frames
         (the one lagged chunk); the report returned is that one (report['frames_done'] <= frames_done).  With seeded input
         the stopping frame is deterministic.  At max_frames, the report is that of the final image.  Turns tracking on if it
-        is off and frames_done == 0."""
+        is off and frames_done == 0.
+
+        adaptive=True: every chunk after the first is render_adaptive over the tiles that the report queued one chunk
+        earlier counts as noisy (that report has been waited for already, so a chunk stays in flight), and the loop also
+        stops at a report with above == 0 (no tile left above `threshold`).  frames_done counts subset frames as frames."""
         if check_every < 1 or max_frames < 0:
             raise ValueError("render_until: check_every >= 1, max_frames >= 0")
         if self.frames_done == 0:
             self.set_noise_tracking(True)
 
-        def chunk():
+        def chunk(select_from=None):
             n = min(check_every, max_frames - self.frames_done)
             if n > 0:
-                self.render(n)
+                if select_from is None:
+                    self.render(n)
+                else:
+                    self.render_adaptive(n, select_from)
 
         chunk()
         self.noise_query(threshold, floor)
+        earlier = None                                     # adaptive: the report one chunk before the newest
         while True:
-            chunk()                                        # the lagged chunk: in flight while the previous report is read
+            chunk(earlier["seq"] if adaptive and earlier is not None else None)   # the lagged chunk
             rep = self.noise_result(wait=True)             # the newest queued: the check before that chunk
             if rep["rel_rmse"] <= target_rel_rmse:
                 return self.frames_done, rep
             if rep["frames_done"] >= max_frames:
                 return self.frames_done, rep
+            if adaptive and rep["above"] == 0:
+                return self.frames_done, rep
+            earlier = rep
             self.noise_query(threshold, floor)
+
+    # -- adaptive sampling (include/myraytracer_amd.h, "adaptive sampling"): frames over a list of 8x8 tiles, each tile blended
+    #    at its own frame count
+    def render_tiles(self, tiles, frames: int = 1):
+        """Queue `frames` subset frames over the listed tile ids (tile = band * tiles_x + column, row 0 at the bottom)."""
+        t = np.ascontiguousarray(np.asarray(tiles).ravel(), np.uint32)
+        self._check(self._L.mrt_render_tiles(self._ctx, t.ctypes.data if t.size else None, t.size, frames), "mrt_render_tiles")
+
+    def render_adaptive(self, frames: int = 1, report_seq: int = 0) -> Tuple[int, int]:
+        """Subset frames over the tiles whose entry in noise report `report_seq` (0: the newest finished one, every tile if none
+        has finished) is above its threshold; returns (the report used, 0 for none; the tiles selected).  Nothing is queued when
+        no tile is selected."""
+        used, sel = C.c_uint64(), C.c_uint32()
+        self._check(self._L.mrt_render_adaptive(self._ctx, frames, report_seq, C.byref(used), C.byref(sel)), "mrt_render_adaptive")
+        return int(used.value), int(sel.value)
+
+    def tile_frames(self) -> np.ndarray:
+        """Every tile's frame count n_t: (tile rows, tiles_x) uint32.  Waits for the frames in flight, as read_framebuffer does."""
+        tx, tr = C.c_uint32(), C.c_uint32()
+        self._L.mrt_read_tile_frames(self._ctx, None, 0, C.byref(tx), C.byref(tr))     # (the shape; the status comes below)
+        out = np.empty((tr.value, tx.value), np.uint32)
+        self._check(self._L.mrt_read_tile_frames(self._ctx, out.ctypes.data, out.size, C.byref(tx), C.byref(tr)),
+                    "mrt_read_tile_frames")
+        return out
 
     def debug_noise_reduce(self, S: np.ndarray, rgba: np.ndarray, K: float, threshold: float = 0.02, floor: float = 0.01):
         """The noise reduction on caller-supplied buffers (S: (rows, W) f32, rgba: (rows, W, 4) f32), synchronously:

@@ -83,8 +83,9 @@ int alloc_noise_buffers(mrt_ctx* c) {
     const size_t n = local_texels(c) ? local_texels(c) : 1;
     HIP_TRY(c, hipMalloc((void**)&c->d_noise_s, n * sizeof(float)));
     HIP_TRY(c, hipMemsetAsync(c->d_noise_s, 0, n * sizeof(float), c->stream));
-    HIP_TRY(c, hipMalloc((void**)&c->d_noise_tiles, (size_t)(c->n_tiles ? c->n_tiles : 1) * sizeof(float)));
-    HIP_TRY(c, hipMemsetAsync(c->d_noise_tiles, 0, (size_t)(c->n_tiles ? c->n_tiles : 1) * sizeof(float), c->stream));
+    const size_t map_floats = (size_t)mrt_ctx::kNoiseRing * (c->n_tiles ? c->n_tiles : 1);     // a tile map per report of the ring
+    HIP_TRY(c, hipMalloc((void**)&c->d_noise_tiles, map_floats * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(c->d_noise_tiles, 0, map_floats * sizeof(float), c->stream));
     HIP_TRY(c, hipMalloc(&c->d_noise_partials, std::max<size_t>(mrt::noise_partials_bytes(c->args.width, c->local_bands), 64)));
     c->noise_first = c->noise_seq + 1;          // (reports of the old geometry are discarded)
     return MRT_OK;
@@ -101,9 +102,22 @@ void free_denoise_buffers(mrt_ctx* c) {
     c->guides_stale = true;
 }
 
+// adaptive sampling's per-tile state (mrt_render_tiles): back to a uniform accumulation
+void free_tile_frames(mrt_ctx* c) {
+    if (c->d_tile_frames) (void)hipFree(c->d_tile_frames);
+    if (c->d_k_f32) (void)hipFree(c->d_k_f32);
+    if (c->d_k_f64) (void)hipFree(c->d_k_f64);
+    c->d_tile_frames = nullptr; c->d_k_f32 = nullptr; c->d_k_f64 = nullptr;
+    c->k_len = 0;
+    c->k_table.clear(); c->k_c2 = 1.0;
+    c->tiles_diverged = false;
+    c->tile_frames.clear();
+}
+
 void free_frame_buffers(mrt_ctx* c) {
     free_noise_buffers(c);
     free_denoise_buffers(c);
+    free_tile_frames(c);
     if (c->d_seeds) (void)hipFree(c->d_seeds);
     if (c->d_fb[0]) (void)hipFree(c->d_fb[0]);
     if (c->d_fb[1]) (void)hipFree(c->d_fb[1]);
@@ -112,6 +126,9 @@ void free_frame_buffers(mrt_ctx* c) {
         if (S.d_tile_order) (void)hipFree(S.d_tile_order);
         if (S.d_sort_scratch) (void)hipFree(S.d_sort_scratch);
         if (S.d_pix_acc) (void)hipFree(S.d_pix_acc);
+        if (S.d_tile_list) (void)hipFree(S.d_tile_list);
+        if (S.h_tile_list) (void)hipHostFree(S.h_tile_list);
+        S.d_tile_list = S.h_tile_list = nullptr;
         S.d_tile_cost = S.d_tile_order = S.d_sort_scratch = nullptr;
         S.d_pix_acc = nullptr;
         S.pix_acc_layers = 0; S.cost_first_layer = 0; S.cost_layers = 1;
@@ -1517,6 +1534,26 @@ static int set_frame_slots(mrt_ctx* c, uint32_t want) {
     return MRT_OK;
 }
 
+// Adaptive sampling's blend of one frame (after the render on the slot's stream): the n tiles of the slot's device list (list
+// null: every tile) at their own weights, in place on the current framebuffer, on the ctx's stream; the host's copy of the
+// counts follows.  p: the frame's parameters (its colour sums: p.pix_acc / p.n_blocks).
+static int blend_tiles(mrt_ctx* c, const mrt::KParams& p, mrt_ctx::FrameSlot& S, const uint32_t* d_list, uint32_t n) {
+    mrt::TileBlendArgs a{};
+    a.pix_acc = p.pix_acc; a.pix_stride = p.pix_stride; a.n_blocks = p.n_blocks;
+    a.fb = c->d_fb[c->target ^ 1];
+    a.noise_s = c->d_noise_s;
+    a.tile_frames = c->d_tile_frames;
+    a.list = d_list;
+    a.tile_cost = S.d_tile_cost;
+    a.tile_queue = S.d_sort_scratch + 1024;
+    a.n = n; a.width = c->args.width; a.height = c->args.height; a.tiles_x = c->tiles_x;
+    a.spp = c->locals.samples_per_frame;
+    a.max_w = c->args.max_framebuffer_weight;
+    const int e = mrt::launch_tile_blend(a, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "per-tile blend launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
 extern "C" {
 
 // State::redraw, lib.rs:241-307 (raytrace pass + swap + weight/shuffle update; the present
@@ -1658,13 +1695,19 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
         p.prev = c->d_fb[c->target ^ 1];         // framebuffers.secondary (lib.rs:265)
         p.locals.framebuffer_weight = c->locals.framebuffer_weight;
         if (!counter) { p.pix_acc = (char*)S.d_pix_acc + (size_t)b * n * 16; p.n_blocks = 1; }
-        int fe = mrt::launch_finalize(p, c->stream, c->d_noise_s);
-        if (fe) return fail(c, MRT_ERR_HIP, "finalize launch failed: %s", hipGetErrorString((hipError_t)fe));
-        c->noise_c2 = mrt::noise_c2_next(c->noise_c2, p.locals.framebuffer_weight);   // (the weight this blend used)
-        c->target ^= 1;                                                       // framebuffers.swap(), lib.rs:299
+        if (c->tiles_diverged) {                 // adaptive sampling has begun: every tile at its own weight, in place (no swap)
+            MRT_TRY(blend_tiles(c, p, S, nullptr, c->n_tiles));
+        } else {
+            int fe = mrt::launch_finalize(p, c->stream, c->d_noise_s);
+            if (fe) return fail(c, MRT_ERR_HIP, "finalize launch failed: %s", hipGetErrorString((hipError_t)fe));
+            c->noise_c2 = mrt::noise_c2_next(c->noise_c2, p.locals.framebuffer_weight);   // (the weight this blend used)
+            c->target ^= 1;                                                   // framebuffers.swap(), lib.rs:299
+        }
         if (c->frames_done != UINT32_MAX) c->frames_done++;                   // saturating_add, lib.rs:300
         c->locals.framebuffer_weight = mrt_frame_weight(c->frames_done, c->args.max_framebuffer_weight);  // :301-304
         mrt_frame_shuffle(c->seed, c->frames_done, c->locals.rng_shuffle);    // :305 (deterministic stand-in)
+        if (c->tiles_diverged)
+            for (uint32_t& t : c->tile_frames) t += t != UINT32_MAX ? 1u : 0u;
     }
     HIP_TRY(c, hipEventRecord(S.finalize_done, c->stream));
     S.queue_dirty = false;
@@ -1712,6 +1755,157 @@ int mrt_render(mrt_ctx* c, uint32_t frames) {
         const bool in_lane = !starved && c->locals.samples_per_frame < 4u;      // (a batch of 1 is a plain redraw, whatever its form)
         int st = redraw_frames(c, batch, c->batch_form == 0 ? in_lane : c->batch_form == 1);
         if (st != MRT_OK) return st;
+        frames -= batch;
+    }
+    return MRT_OK;
+}
+
+// ---- adaptive sampling (include/myraytracer_amd.h, "adaptive sampling") ------------------------------------------------------
+// A subset frame renders its listed tiles through the unchanged render kernel: n_tiles = the list's length (the queue's length;
+// with one queue layer it is never a layer stride, hence no counter mode beyond MRT_COUNTER_BLOCK samples), tile_order = the list,
+// heaviest first by the slot's tile costs when the render has more tiles than waves.  No pilot launch, and the launch-width
+// controller neither sees nor restarts for these frames (their sizes vary): they use the setting in force.  Then blend_tiles.
+
+// the first subset frame since create / reset: every tile's count starts at frames_done (behind everything on the ctx's stream)
+static int begin_tile_frames(mrt_ctx* c) {
+    if (c->tiles_diverged) return MRT_OK;
+    if (!c->d_tile_frames) HIP_TRY(c, hipMalloc((void**)&c->d_tile_frames, (size_t)c->n_tiles * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)c->d_tile_frames, (int)c->frames_done, c->n_tiles, c->stream));
+    c->tile_frames.assign(c->n_tiles, c->frames_done);
+    c->tiles_diverged = true;
+    return MRT_OK;
+}
+
+// `batch` consecutive subset frames over the n tiles of `tiles` in ONE render launch (batch > 1: the in-lane form only)
+static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t batch) {
+    mrt::KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.locals = c->locals;
+    fill_scene_params(c, p);
+    p.shard_rank = c->shard_rank; p.shard_world = c->shard_world;
+    p.seeds = c->d_seeds;
+    p.counters = c->d_counters;
+    p.count_draws = c->count_draws ? 1u : 0u;
+    p.wave_log = nullptr;
+    p.tiles_x = c->tiles_x; p.n_tiles = n;
+    p.pilot_spp = c->pilot_spp;
+    c->last_slot = (uint32_t)(c->frame_seq % c->frame_slots);
+    mrt_ctx::FrameSlot& S = c->slot[c->last_slot];
+    {   // back-pressure, as a frame of mrt_render: the slot's previous render kernel has completed (its list copy with it)
+        char what[128];
+        std::snprintf(what, sizeof what, "mrt_render_tiles: back-pressure of slot %u (next frame %llu)", c->last_slot,
+                      (unsigned long long)c->frame_seq);
+        if (S.render_pending) MRT_TRY(mrt::wait_event(c, S.render_done, what));
+        S.render_pending = false;
+    }
+    if (!S.d_tile_list) HIP_TRY(c, hipMalloc((void**)&S.d_tile_list, (size_t)c->n_tiles * sizeof(uint32_t)));
+    if (!S.h_tile_list) HIP_TRY(c, hipHostMalloc((void**)&S.h_tile_list, (size_t)c->n_tiles * sizeof(uint32_t), hipHostMallocDefault));
+    std::memcpy(S.h_tile_list, tiles, (size_t)n * sizeof(uint32_t));
+    p.tile_queue = S.d_sort_scratch + 1024;
+    p.tile_cost = S.d_tile_cost;
+    const size_t texels = local_texels(c) ? local_texels(c) : 1;
+    if (S.pix_acc_layers < batch) {
+        MRT_TRY(mrt::wait_stream(c, S.stream, "mrt_render_tiles: regrowing a slot's colour sums (its side stream)"));
+        MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
+        if (S.d_pix_acc) (void)hipFree(S.d_pix_acc);
+        S.d_pix_acc = nullptr; S.pix_acc_layers = 0;
+        HIP_TRY(c, hipMalloc(&S.d_pix_acc, (size_t)batch * texels * 16));
+        S.pix_acc_layers = batch;
+    }
+    S.cost_first_layer = batch - 1u;
+    S.cost_layers = 1u;
+    p.n_blocks = batch;
+    p.pix_stride = (uint32_t)texels;
+    p.queue_layers = 1u;
+    p.lane_frames = batch;
+    for (uint32_t b = 0; b < batch; b++) {
+        if (b == 0) std::memcpy(p.layer_shuffle[0], c->locals.rng_shuffle, 16);
+        else mrt_frame_shuffle(c->seed, c->frames_done > UINT32_MAX - b ? UINT32_MAX : c->frames_done + b, p.layer_shuffle[b]);
+    }
+    p.pix_acc = S.d_pix_acc;
+    if (c->inputs_dirty) {
+        HIP_TRY(c, hipEventRecord(c->ev_inputs, c->stream));
+        c->inputs_dirty = false;
+    }
+    HIP_TRY(c, hipStreamWaitEvent(S.stream, c->ev_inputs, 0));
+    HIP_TRY(c, hipStreamWaitEvent(S.stream, S.finalize_done, 0));
+    if (S.queue_dirty) HIP_TRY(c, hipMemsetAsync(p.tile_queue, 0, sizeof(uint32_t), S.stream));
+    HIP_TRY(c, hipMemcpyAsync(S.d_tile_list, S.h_tile_list, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, S.stream));
+    // launch width: the setting in force (the controller's last launch), and round 3's 8 waves per CU for chains of a few bounces
+    const uint32_t chain_spp = c->locals.samples_per_frame * batch;
+    uint32_t launch_waves = c->n_waves;
+    if (chain_spp < 4u && c->waves_per_cu_override == 0) launch_waves = std::min(launch_waves, c->cus * 8u);
+    if (c->width.div != 0 && c->waves_per_cu_override == 0 && c->frame_slots_override == 0) {
+        const uint32_t whole = std::min(c->n_waves, mrt::render_resident_waves(p));
+        launch_waves = std::max(whole / std::max(c->last_launch_div, 1u), 1u);
+    }
+    p.tile_order = S.d_tile_list;                // (a subset launch always passes its list: null would mean tiles 0 .. n - 1)
+    if (c->lpt_enabled && S.cost_valid && n > launch_waves && chain_spp >= 4u) {
+        int se = mrt::launch_sort_tile_list(S.d_tile_cost, S.d_tile_list, S.d_tile_order, S.d_sort_scratch, n, S.stream);
+        if (se) return fail(c, MRT_ERR_HIP, "tile list sort launch failed: %s", hipGetErrorString((hipError_t)se));
+        p.tile_order = S.d_tile_order;
+    }
+    const uint32_t ev = (uint32_t)(c->frame_seq % mrt_ctx::kEventRing);
+    S.queue_dirty = true;
+    HIP_TRY(c, hipEventRecord(c->ev_start[ev], S.stream));
+    int e = mrt::launch_render(p, false, launch_waves, S.stream, &c->last_launch[0]);
+    if (e) return fail(c, MRT_ERR_HIP, "render launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipEventRecord(c->ev_stop[ev], S.stream));
+    HIP_TRY(c, hipEventRecord(S.render_done, S.stream));
+    S.render_pending = true;
+    S.render_seq = c->frame_seq;
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, S.render_done, 0));
+    for (uint32_t b = 0; b < batch; b++) {
+        p.pix_acc = (char*)S.d_pix_acc + (size_t)b * texels * 16;
+        p.n_blocks = 1;
+        MRT_TRY(blend_tiles(c, p, S, S.d_tile_list, n));
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t& t = c->tile_frames[tiles[i]];
+            t += t != UINT32_MAX ? 1u : 0u;
+        }
+        if (c->frames_done != UINT32_MAX) c->frames_done++;
+        c->locals.framebuffer_weight = mrt_frame_weight(c->frames_done, c->args.max_framebuffer_weight);
+        mrt_frame_shuffle(c->seed, c->frames_done, c->locals.rng_shuffle);
+    }
+    HIP_TRY(c, hipEventRecord(S.finalize_done, c->stream));
+    S.queue_dirty = false;
+    c->frame_seq++;
+    c->shuffle_overridden = false;
+    return MRT_OK;
+}
+
+int mrt_render_tiles(mrt_ctx* c, const uint32_t* tiles, size_t n, uint32_t frames) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (n == 0 || frames == 0) return MRT_OK;
+    if (!tiles) return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_tiles: tiles is NULL");
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_render_tiles: a shard (world %u) renders whole frames only", c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_render_tiles: no scene (call mrt_set_world first)");
+    const bool counter = c->locals.rng_mode == MRT_RNG_COUNTER;
+    if (counter && c->locals.samples_per_frame > MRT_COUNTER_BLOCK)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_tiles: counter mode renders at most %u samples per frame by tiles (%u)",
+                    (unsigned)MRT_COUNTER_BLOCK, c->locals.samples_per_frame);
+    if (n > c->n_tiles) return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_tiles: %zu tiles listed, the image has %u", n, c->n_tiles);
+    {
+        std::vector<uint8_t> seen(c->n_tiles, 0);
+        for (size_t i = 0; i < n; i++) {
+            if (tiles[i] >= c->n_tiles) return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_tiles: tile %u of %u", tiles[i], c->n_tiles);
+            if (seen[tiles[i]]++) return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_tiles: tile %u listed twice", tiles[i]);
+        }
+    }
+    // every tile: whole frames (today's path while the accumulation is uniform; blended per tile after a subset frame)
+    if (n == c->n_tiles) return mrt_render(c, frames);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(begin_tile_frames(c));
+    while (frames != 0) {
+        // The frames of one call share one launch in the in-lane form (a lane renders its pixel for every frame of the batch);
+        // never the layered form.  At 1080p x 1 spp the adaptive run to the same stop took 84 ms so, 119-175 ms with a launch
+        // per frame (most lists are short; profiles/adaptive_rates.txt).  mrt_debug_set_frame_batching(0): a launch per frame.
+        uint32_t batch = 1;
+        if (c->batch_frames && c->batch_form != 2 && !counter && !c->shuffle_overridden && c->locals.samples_per_frame != 0u) {
+            const uint64_t layer_bytes = (uint64_t)std::max<size_t>(local_texels(c), 1) * 16u;
+            batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)frames, (uint64_t)mrt::kMaxFrameBatch, kBatchBytes / layer_bytes}));
+        }
+        MRT_TRY(render_subset(c, tiles, (uint32_t)n, batch));
         frames -= batch;
     }
     return MRT_OK;
@@ -2087,6 +2281,8 @@ int mrt_reset(mrt_ctx* c) {
     c->locals.samples_per_frame = spp;
     c->locals.rng_mode = mode;
     c->target = 0;
+    c->tiles_diverged = false;                  // (every tile at 0 frames again: the per-tile counts are re-initialised on use)
+    c->tile_frames.clear();
     return MRT_OK;
 }
 
@@ -2518,8 +2714,8 @@ int ensure_noise_ring(mrt_ctx* c) {
 }
 
 // the report of the sums and what the host knew at query time; K = +inf is "no estimate yet" (every derived figure +inf,
-// without forming 0 * inf)
-void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s) {
+// without forming 0 * inf).  per_tile: reduced with K per tile (adaptive sampling), whose sum_s is sum_var already.
+void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s, bool per_tile = false) {
     r->pixels = s.pixels; r->non_finite = s.non_finite; r->above = s.above;
     r->sum_lum = s.sum_l;
     if (std::isinf(r->noise_factor)) {
@@ -2527,13 +2723,38 @@ void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s) {
         r->max_se = INFINITY;
         return;
     }
-    r->sum_var = s.sum_s * r->noise_factor;
+    r->sum_var = per_tile ? s.sum_s : s.sum_s * r->noise_factor;
     r->max_se = s.max_se;
     r->rmse = s.pixels ? std::sqrt(r->sum_var / (double)s.pixels) : 0.0;
     r->rel_rmse = r->rmse > 0.0 ? r->rmse / (s.sum_l / (double)s.pixels) : 0.0;
 }
 
 bool noise_args_ok(float threshold, float floor_) { return std::isfinite(threshold) && std::isfinite(floor_) && floor_ >= 0.0f; }
+
+// Adaptive sampling: K(n) = mrt_noise_factor(n, max_w) for n < len on the device (as float and as double), grown by doubling.
+// The host table continues the c2 recursion of mrt_noise_factor; a larger device table replaces the old one after the ctx's
+// stream -- the only one whose reductions read it -- has drained (a handful of times per accumulation).
+int ensure_k_table(mrt_ctx* c, uint32_t len) {
+    if (len <= c->k_len) return MRT_OK;
+    uint32_t cap = std::max<uint32_t>(c->k_len ? c->k_len : 4096u, 4096u);
+    while (cap < len) cap = cap > 0x7FFFFFFFu ? 0xFFFFFFFFu : 2u * cap;
+    const float max_w = c->args.max_framebuffer_weight;
+    while (c->k_table.size() < cap) {
+        c->k_table.push_back(mrt::noise_factor_of(c->k_c2));     // K after k_table.size() frames
+        c->k_c2 = mrt::noise_c2_next(c->k_c2, mrt_frame_weight((uint32_t)(c->k_table.size() - 1), max_w));
+    }
+    std::vector<float> kf(c->k_table.begin(), c->k_table.end());
+    MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_noise_query: growing the K table"));
+    if (c->d_k_f32) (void)hipFree(c->d_k_f32);
+    if (c->d_k_f64) (void)hipFree(c->d_k_f64);
+    c->d_k_f32 = nullptr; c->d_k_f64 = nullptr; c->k_len = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f32, (size_t)cap * sizeof(float)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f64, (size_t)cap * sizeof(double)));
+    HIP_TRY(c, hipMemcpy(c->d_k_f32, kf.data(), (size_t)cap * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_k_f64, c->k_table.data(), (size_t)cap * sizeof(double), hipMemcpyHostToDevice));
+    c->k_len = cap;
+    return MRT_OK;
+}
 
 }  // namespace
 
@@ -2583,10 +2804,23 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
         std::snprintf(what, sizeof what, "mrt_noise_query: the ring is full (report %llu)", (unsigned long long)(seq - kNoiseRing));
         MRT_TRY(mrt::wait_event(c, E.copied, what));
     }
-    const double K = mrt::noise_factor_of(c->noise_c2);
-    const int e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
-                                           c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials,
-                                           c->d_noise_tiles, c->d_noise_sums + i, c->stream);
+    float* map = c->d_noise_tiles + (size_t)i * (c->n_tiles ? c->n_tiles : 1);
+    double K = mrt::noise_factor_of(c->noise_c2);
+    int e = 0;
+    if (!c->tiles_diverged) {
+        e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                     c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials, map,
+                                     c->d_noise_sums + i, c->stream);
+    } else {                        // adaptive sampling: K per tile; the report's K is the largest (the least-sampled tile's)
+        uint32_t most = 0;
+        for (uint32_t t : c->tile_frames) most = std::max(most, t);
+        MRT_TRY(ensure_k_table(c, most + 1u));
+        K = 0.0;
+        for (uint32_t t : c->tile_frames) K = std::max(K, c->k_table[t]);
+        e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                           c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials, map,
+                                           c->d_noise_sums + i, c->stream);
+    }
     if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(c, hipMemcpyAsync(c->h_noise_sums + i, c->d_noise_sums + i, sizeof(mrt::NoiseSums), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(E.copied, c->stream));
@@ -2595,6 +2829,7 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
     E.report.frames_done = c->frames_done;
     E.report.threshold = threshold; E.report.floor = floor_;
     E.report.noise_factor = K;
+    E.per_tile = c->tiles_diverged;
     c->noise_seq = seq;
     return MRT_OK;
 }
@@ -2616,7 +2851,7 @@ int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
         if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
         if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_noise_result: %s", hipGetErrorString(q));
         *out = c->noise_ring[i].report;
-        noise_fill(out, c->h_noise_sums[i]);
+        noise_fill(out, c->h_noise_sums[i], c->noise_ring[i].per_tile);
         return MRT_OK;
     }
     return MRT_OK;
@@ -2651,8 +2886,73 @@ int mrt_read_noise_tiles(mrt_ctx* c, float* out, size_t cap, uint32_t* tiles_x, 
     if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
     // behind the latest query only: its copy's event, then the tile map on a stream of its own
     HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[c->noise_seq % kNoiseRing].copied, 0));
-    if (n) HIP_TRY(c, hipMemcpyAsync(out, c->d_noise_tiles, n * sizeof(float), hipMemcpyDeviceToHost, c->noise_stream));
+    const float* map = c->d_noise_tiles + (size_t)(c->noise_seq % kNoiseRing) * n;
+    if (n) HIP_TRY(c, hipMemcpyAsync(out, map, n * sizeof(float), hipMemcpyDeviceToHost, c->noise_stream));
     return mrt::wait_stream(c, c->noise_stream, __func__);
+}
+
+// Adaptive sampling's selection: the tiles whose entry in report `report_seq`'s tile map is > its threshold (the tiles holding a
+// pixel counted in its `above`), from that report's own map (one per ring entry), then mrt_render_tiles.  Waits for that query only.
+int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64_t* used_seq, uint32_t* tiles_selected) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (used_seq) *used_seq = 0;
+    if (tiles_selected) *tiles_selected = 0;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: noise tracking is off (mrt_set_noise_tracking)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    uint64_t seq = 0;
+    if (report_seq == 0) {                      // the newest finished report, without waiting; none: every tile
+        for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
+            const hipError_t q = hipEventQuery(c->noise_ring[k % kNoiseRing].copied);
+            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+            if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_render_adaptive: %s", hipGetErrorString(q));
+            seq = k;
+            break;
+        }
+    } else {
+        if (report_seq > c->noise_seq || report_seq < oldest)
+            return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: report %llu is not among the reports held (%llu .. %llu)",
+                        (unsigned long long)report_seq, (unsigned long long)oldest, (unsigned long long)c->noise_seq);
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_render_adaptive: report %llu", (unsigned long long)report_seq);
+        MRT_TRY(mrt::wait_event(c, c->noise_ring[report_seq % kNoiseRing].copied, what));
+        seq = report_seq;
+    }
+    const uint32_t nt = c->n_tiles;
+    c->selection.clear();
+    if (seq == 0) {
+        for (uint32_t t = 0; t < nt; t++) c->selection.push_back(t);
+    } else {
+        // the map was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
+        if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
+        c->h_select_map.resize(nt);
+        HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[seq % kNoiseRing].copied, 0));
+        HIP_TRY(c, hipMemcpyAsync(c->h_select_map.data(), c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float),
+                                  hipMemcpyDeviceToHost, c->noise_stream));
+        MRT_TRY(mrt::wait_stream(c, c->noise_stream, __func__));
+        const float threshold = c->noise_ring[seq % kNoiseRing].report.threshold;
+        for (uint32_t t = 0; t < nt; t++)
+            if (c->h_select_map[t] > threshold) c->selection.push_back(t);
+    }
+    if (used_seq) *used_seq = seq;
+    if (tiles_selected) *tiles_selected = (uint32_t)c->selection.size();
+    if (c->selection.empty()) return MRT_OK;              // converged at that threshold: nothing to render
+    return mrt_render_tiles(c, c->selection.data(), c->selection.size(), frames);
+}
+
+// n_t per tile (frames_done everywhere while the accumulation is uniform); synchronises as mrt_read_framebuffer does
+int mrt_read_tile_frames(mrt_ctx* c, uint32_t* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (tiles_x) *tiles_x = c->tiles_x;
+    if (tiles_rows) *tiles_rows = c->local_bands;
+    if (!out) return MRT_ERR_INVALID_ARG;
+    const size_t n = c->n_tiles;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_tile_frames: need %zu values", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->tiles_diverged && n) HIP_TRY(c, hipMemcpyAsync(out, c->d_tile_frames, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
+    if (!c->tiles_diverged) std::fill(out, out + n, c->frames_done);
+    return MRT_OK;
 }
 
 int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,
@@ -2768,6 +3068,8 @@ int denoise_check(mrt_ctx* c, const char* who, bool tracking) {
     if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) cannot be denoised", who, c->shard_world);
     if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
     if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
+    if (c->tiles_diverged)          // (K differs per tile: the filter has no definition for that yet)
+        return fail(c, MRT_ERR_STATE, "%s: the accumulation is adaptive (mrt_render_tiles since the last reset)", who);
     return MRT_OK;
 }
 

@@ -96,6 +96,10 @@ struct mrt_ctx {
         bool stats_pending = false;
         bool render_pending = false;           // a render kernel of this slot has been launched and not yet been seen complete
         uint64_t render_seq = 0;               // its frame (diagnostics of a stalled wait)
+        // adaptive sampling: a subset frame's tile list, written by the host into pinned memory and copied on the slot's stream
+        // before the render (the host rewrites it only after the slot's previous render kernel has completed)
+        uint32_t* h_tile_list = nullptr;
+        uint32_t* d_tile_list = nullptr;
     } slot[kMaxFrameSlots];
     // Launch width (redraw_frames; the policy itself: width_policy.h): a frame is launched on 1 / width.div of the persistent
     // waves the chip holds and max(2, width.div) x width.mult frames are in flight, so that the chip stays full.  Narrow launches
@@ -172,12 +176,13 @@ struct mrt_ctx {
     struct NoiseEntry {
         hipEvent_t copied = nullptr;
         mrt_noise_report report{};                  // what the host knows at query time (seq, frames_done, K, threshold, floor)
+        bool per_tile = false;                      // reduced with K per tile (adaptive sampling): the sums' sum_s is sum_var
     };
     bool noise_on = false;                          // mrt_set_noise_tracking
     float* d_noise_s = nullptr;                     // local texels (allocated with the framebuffers while noise_on)
     double noise_c2 = 1.0;                          // sum of the squared normalised weights of the frames blended so far
     void* d_noise_partials = nullptr;
-    float* d_noise_tiles = nullptr;                 // n_tiles, the latest query's
+    float* d_noise_tiles = nullptr;                 // kNoiseRing x n_tiles: query seq's map at entry seq % kNoiseRing
     mrt::NoiseSums* d_noise_sums = nullptr;         // kNoiseRing entries
     mrt::NoiseSums* h_noise_sums = nullptr;         // pinned, kNoiseRing entries
     NoiseEntry noise_ring[kNoiseRing];
@@ -199,6 +204,21 @@ struct mrt_ctx {
     uint32_t* d_guide_queue = nullptr;              // the DBG launch's tile queue counter
     float* d_guides = nullptr;                      // 2 float4 per pixel
     float* d_den[3] = {nullptr, nullptr, nullptr};  // ping, pong, the denoised frame: a float4 per pixel
+
+    // adaptive sampling (mrt_render_tiles / mrt_render_adaptive, api.cpp; adaptive.hip): every tile's frame count n_t.  Until the
+    // first subset frame every n_t is frames_done and nothing differs from a uniform accumulation.  From it on (tiles_diverged,
+    // until mrt_reset) every blend is per tile (launch_tile_blend) and IN PLACE on d_fb[target ^ 1] (target no longer swaps), and
+    // noise reports take K per tile from the tables K(n) = mrt_noise_factor(n, max_w), n < k_len, grown on demand.
+    bool tiles_diverged = false;
+    std::vector<uint32_t> tile_frames;              // the host's copy of n_t (what the blends queued so far make it)
+    uint32_t* d_tile_frames = nullptr;              // n_t per tile, incremented by the per-tile blend
+    std::vector<double> k_table;                    // K(n) for n < k_table.size(), and c2 after k_table.size() frames
+    double k_c2 = 1.0;
+    float* d_k_f32 = nullptr;                       // K(n) as float / double on the device, k_len entries
+    double* d_k_f64 = nullptr;
+    uint32_t k_len = 0;
+    std::vector<float> h_select_map;                // mrt_render_adaptive: the report's tile map
+    std::vector<uint32_t> selection;                // ... and the tiles it selects
 
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;

@@ -153,6 +153,8 @@ constexpr uint32_t kBoxLdsCap = 1024;    // never more boxes (32 B each) than th
 // tile_order.hip: order[] = tile ids sorted by cost[] descending (bucket sort; ties in any order).
 // scratch: 1024 u32.
 int launch_sort_tiles(const uint32_t* cost, uint32_t* order, uint32_t* scratch, uint32_t n_tiles, void* stream);
+// the same for a subset frame (adaptive sampling): order[] = the n ids of list[] sorted by cost[id] descending
+int launch_sort_tile_list(const uint32_t* cost, const uint32_t* list, uint32_t* order, uint32_t* scratch, uint32_t n, void* stream);
 // one single-wave kernel that stays resident for `ticks` of the 100 MHz clock (at most max_polls polls); out (optional, device-
 // visible) gets its {start, end} ticks
 int launch_hold(unsigned long long ticks, uint32_t max_polls, unsigned long long* out, void* stream);
@@ -191,6 +193,31 @@ inline double noise_factor_of(double c2) { return c2 >= 1.0 ? __builtin_inf() : 
 int launch_noise_reduce(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
                         uint32_t rank, uint32_t world, float K, float threshold, float floor_, void* partials, float* tiles,
                         NoiseSums* out, void* stream);
+// the same after adaptive sampling has diverged (one context, world 1): pixel p of tile t takes K_t = Kf[tile_frames[t]] for var_p
+// (+inf: se_p = +inf) and sums (double)S_p * Kd[tile_frames[t]] -- sum_var itself -- into out->sum_s (tiles whose K is +inf add
+// nothing: the report is "no estimate yet" then).  Kf / Kd: K(n) = mrt_noise_factor(n, max_w) for n < k_len, as float and double.
+int launch_noise_reduce_tiles(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
+                              const uint32_t* tile_frames, const float* Kf, const double* Kd, float threshold, float floor_,
+                              void* partials, float* tiles, NoiseSums* out, void* stream);
+
+// adaptive.hip (include/myraytracer_amd.h, "adaptive sampling"): the per-tile blend of a frame whose tiles have their own frame
+// counts.  One wave per tile of `list` (null: every tile 0 .. n - 1), in place on `fb` (and S with noise_s): w =
+// mrt_frame_weight(tile_frames[t], max_w) as the same float expression, the blend and S update of finalize_kernel<false> /
+// finalize_tracked_kernel, then tile_frames[t] += 1 (saturating) and tile_cost[t]; the first wave zeroes *tile_queue.  One
+// context of world 1: local rows are image rows.
+struct TileBlendArgs {
+    const void* pix_acc;        // PixAcc per texel and layer (kernels.hip): n_blocks layers pix_stride apart, added in order
+    uint32_t pix_stride, n_blocks;
+    float* fb;                  // RGBA32F, width x (8 x bands) texels, blended in place
+    float* noise_s;             // S per texel, or null (tracking off)
+    uint32_t* tile_frames;      // n_t per tile
+    const uint32_t* list;       // the listed tiles, or null = 0 .. n - 1
+    uint32_t* tile_cost;        // per tile: its heaviest pixel's loop trips (the slot's next queue order)
+    uint32_t* tile_queue;       // the slot's queue counter, zeroed
+    uint32_t n, width, height, tiles_x, spp;
+    float max_w;
+};
+int launch_tile_blend(const TileBlendArgs& a, void* stream);
 
 // denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per

@@ -25,9 +25,12 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult] [--target-noise REL [--check-every N]] [--denoise-out FILE]\n"
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive]] [--denoise-out FILE]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
+        "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
+        "                      check earlier finds noisy, and the loop also stops when no pixel is above rel 0.02; prints frames,\n"
+        "                      samples and tiles selected per check\n"
         "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png; one GPU)\n");
 }
 
@@ -41,6 +44,7 @@ int main(int argc, char** argv) {
     uint32_t frames = 1, warmup = 0, rng_mode = MRT_RNG_PIXEL_STREAM; uint64_t seed = 1; int device = 0;
     uint32_t hint_div = 0, hint_mult = 0, check_every = 16;
     double target_noise = -1.0;
+    bool adaptive = false;
     std::string scene = "default", scene_file, save_scene, out, denoise_out;
     std::vector<int> devices;
     for (int i = 1; i < argc; i++) {
@@ -48,6 +52,7 @@ int main(int argc, char** argv) {
         size_t eq = a.find('=');
         if (eq != std::string::npos) { v = a.substr(eq + 1); a = a.substr(0, eq); }
         else if (a == "--help" || a == "-h") { usage(); return 0; }
+        else if (a == "--adaptive") { adaptive = true; continue; }
         else if (i + 1 < argc) v = argv[++i];
         else { usage(); return 2; }
         if (a == "--width") args.width = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
@@ -125,6 +130,7 @@ int main(int argc, char** argv) {
     }
     if (!denoise_out.empty() && n_gpus > 1) { std::fprintf(stderr, "--denoise-out wants one GPU (a shard has no neighbours)\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
+    if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
         if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));
@@ -147,12 +153,30 @@ int main(int argc, char** argv) {
     } else {
         // --target-noise: chunks of check_every frames; chunk k + 1 is queued before report k is waited for (the pipeline stays
         // full), so the stop overshoots the first report that meets the target by at most one chunk
+        // --adaptive: every chunk after the first renders the tiles that the report one check before the newest finds noisy
+        // (State.render_until(adaptive=True)'s loop); subset frames count as frames
         uint32_t done = 0;
+        uint64_t earlier = 0;             // that report (0: none yet)
+        uint32_t selected = 0;            // the tiles of the latest chunk
+        uint64_t tile_frames = 0;         // tiles x frames queued: at most 64 x spp samples each
         auto chunk = [&]() -> int {
             const uint32_t k = std::min(check_every, frames - done);
-            for (mrt_ctx* c : ctxs)
-                if (k) { const int s_ = mrt_render(c, k); if (s_ != MRT_OK) return s_; }
-            done += k;
+            for (mrt_ctx* c : ctxs) {
+                if (!k) continue;
+                int s_ = MRT_OK;
+                if (adaptive && earlier != 0) {
+                    uint64_t used = 0;
+                    s_ = mrt_render_adaptive(c, k, earlier, &used, &selected);
+                } else {
+                    s_ = mrt_render(c, k);
+                    uint32_t tx = 0, tr = 0;
+                    (void)mrt_read_tile_frames(c, nullptr, 0, &tx, &tr);      // (the shape only)
+                    selected = tx * tr;
+                }
+                if (s_ != MRT_OK) return s_;
+            }
+            tile_frames += (uint64_t)selected * (mrt_frames_done(ctxs[0]) - done);
+            done = mrt_frames_done(ctxs[0]);
             return MRT_OK;
         };
         auto query = [&]() -> int {
@@ -178,7 +202,12 @@ int main(int argc, char** argv) {
                 r.rel_rmse = r.rmse > 0.0 ? r.rmse / (r.sum_lum / (double)r.pixels) : 0.0;
             }
             report = r;
-            if (r.rel_rmse <= target_noise || r.frames_done >= frames) break;
+            if (adaptive)       // (no host wait here: the counted samples come after the loop)
+                std::printf("check: report at frame %u: %llu pixels above, rel_rmse %.5g; %u frames queued, %u tiles in the latest chunk, "
+                            "%llu samples at most\n", r.frames_done, (unsigned long long)r.above, r.rel_rmse, done, selected,
+                            (unsigned long long)(tile_frames * 64u * args.samples_per_frame));
+            if (r.rel_rmse <= target_noise || r.frames_done >= frames || (adaptive && r.above == 0)) break;
+            earlier = r.seq;
             TRY(ctxs[0], query());
         }
         frames = done;
@@ -186,7 +215,12 @@ int main(int argc, char** argv) {
     if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));         // every shard's bands -> the first GPU
     for (mrt_ctx* c : ctxs) TRY(c, mrt_sync(c));
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const double samples = (double)args.width * args.height * args.samples_per_frame * frames;
+    double samples = (double)args.width * args.height * args.samples_per_frame * frames;
+    if (adaptive) {                       // subset frames: the samples the render kernels counted
+        mrt_counters cnt{};
+        TRY(ctxs[0], mrt_read_counters(ctxs[0], &cnt));
+        samples = (double)cnt.samples;
+    }
     std::printf("%ux%u, %u spp x %u frames, depth %u, %d spheres, %u GPU(s): %.3f s, %.1f Msamples/s\n", args.width, args.height,
                 args.samples_per_frame, frames, args.ray_depth, n, n_gpus, sec, samples / sec * 1e-6);
     if (target_noise >= 0.0)

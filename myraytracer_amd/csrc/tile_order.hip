@@ -101,6 +101,23 @@ __global__ void __launch_bounds__(64) hold_kernel(unsigned long long ticks, uint
     if (threadIdx.x == 0 && out) { out[0] = t0; out[1] = now; }
 }
 
+// a subset frame's queue (adaptive sampling): the same sort over the n tiles of list[] -- key cost[list[i]], output list[i]
+__global__ void __launch_bounds__(256) tile_list_hist_kernel(const uint32_t* __restrict__ cost, const uint32_t* __restrict__ list,
+                                                             uint32_t* hist, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool ok = i < n;
+    (void)wave_bucket_add(hist, ok ? cost_bucket(cost[list[i]]) : 0u, ok);
+}
+
+__global__ void __launch_bounds__(256) tile_list_scatter_kernel(const uint32_t* __restrict__ cost, const uint32_t* __restrict__ list,
+                                                                uint32_t* offsets, uint32_t* __restrict__ order, uint32_t n) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool ok = i < n;
+    const uint32_t id = ok ? list[i] : 0u;
+    const uint32_t pos = wave_bucket_add(offsets, ok ? cost_bucket(cost[id]) : 0u, ok);
+    if (ok) order[pos] = id;
+}
+
 }  // namespace
 
 int launch_hold(unsigned long long ticks, uint32_t max_polls, unsigned long long* out, void* stream) {
@@ -117,6 +134,18 @@ int launch_sort_tiles(const uint32_t* cost, uint32_t* order, uint32_t* scratch, 
     hipLaunchKernelGGL(tile_hist_kernel, dim3(blocks), dim3(256), 0, st, cost, scratch, n_tiles);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(64), 0, st, scratch);
     hipLaunchKernelGGL(tile_scatter_kernel, dim3(blocks), dim3(256), 0, st, cost, scratch, order, n_tiles);
+    return (int)hipGetLastError();
+}
+
+int launch_sort_tile_list(const uint32_t* cost, const uint32_t* list, uint32_t* order, uint32_t* scratch, uint32_t n, void* stream) {
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(scratch, 0, kBuckets * sizeof(uint32_t), st);
+    if (e != hipSuccess) return (int)e;
+    const uint32_t blocks = (n + 255u) / 256u;
+    hipLaunchKernelGGL(tile_list_hist_kernel, dim3(blocks), dim3(256), 0, st, cost, list, scratch, n);
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(64), 0, st, scratch);
+    hipLaunchKernelGGL(tile_list_scatter_kernel, dim3(blocks), dim3(256), 0, st, cost, list, scratch, order, n);
     return (int)hipGetLastError();
 }
 
