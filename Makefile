@@ -12,8 +12,12 @@ CLI      := $(LIBDIR)/native_runner
 # -mllvm -amdgpu-mfma-vgpr-form: the matrix-core sweep reads its MFMA results with VALU ops; in AGPRs
 # every value would cost a v_accvgpr_read first.
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -ffp-contract=off -fno-vectorize -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form -Wall -Wextra -Wno-unused-parameter
-SRCS     := $(CSRC)/kernels.hip $(CSRC)/tile_order.hip $(CSRC)/debug_kernels.hip $(CSRC)/present.hip $(CSRC)/noise.hip $(CSRC)/denoise.hip $(CSRC)/adaptive.hip $(CSRC)/api.cpp $(CSRC)/multi_gpu.cpp $(CSRC)/scenes.cpp $(CSRC)/image_io.cpp
-HDRS     := $(CSRC)/mrt_internal.h $(CSRC)/mrt_ctx.h $(CSRC)/mrt_device.h $(CSRC)/width_policy.h include/myraytracer_amd.h include/myraytracer_amd_debug.h
+# the sources and headers: scripts/source_hash.py holds the one list (the build id is the hash over the same files)
+SRCS     := $(shell python3 scripts/source_hash.py --srcs)
+HDRS     := $(shell python3 scripts/source_hash.py --hdrs)
+ifeq ($(strip $(SRCS)),)
+$(error scripts/source_hash.py --srcs printed no sources)
+endif
 
 all: $(LIB) $(CLI) oracle
 

@@ -9,7 +9,7 @@ import importlib.util
 import os
 import sys
 
-# Up to 8 frames of a pixel-starved shard run at a time, each on a HIP stream of its own (api.cpp, redraw_frames); they only
+# Up to 8 frames of a pixel-starved shard run at a time, each on a HIP stream of its own (frames.cpp, redraw_frames); they only
 # run side by side on hardware queues of their own, and HIP's default is 4 per process.  Read by the runtime when it
 # initialises -- set here, at import, before anything (torch included) has made a HIP call.  Never overrides the caller's value.
 # (The C library itself never touches the environment: it measures what it got and holds its schedule to that.)

@@ -1,6 +1,6 @@
 // Adaptive sampling (mrt_render_tiles / mrt_render_adaptive, include/myraytracer_amd.h "adaptive sampling"): the blend of a frame
 // whose tiles each have their own frame count n_t.  Once a subset frame has been blended, the framebuffer is blended in place
-// (api.cpp): a subset frame then costs its listed tiles, not the image, and the unlisted tiles keep their texels and S bit for bit.
+// (frames.cpp): a subset frame then costs its listed tiles, not the image, and the unlisted tiles keep their texels and S bit for bit.
 // A translation unit of its own, so that kernels.hip -- render_kernel and finalize_kernel / finalize_tracked_kernel -- is unchanged.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"

@@ -1,0 +1,207 @@
+// The denoiser of include/myraytracer_amd.h: the first-hit guides and the filter (denoise.hip).
+#include <cmath>
+#include <cstring>
+
+#include "mrt_ctx.h"
+
+using mrt::fail, mrt::fill_scene_params;
+
+namespace mrt {
+
+// the denoiser's guides and buffers (sized for the image; allocated at the first denoise, ensure_denoise_buffers)
+void free_denoise_buffers(mrt_ctx* c) {
+    free_device(c->d_guide_rays, c->d_guide_hits, c->d_guide_cand, c->d_guide_queue, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2]);
+    c->guide_cand_words = 0;
+    c->guides_stale = true;
+}
+
+}  // namespace mrt
+
+// ---- denoiser (include/myraytracer_amd.h, "denoiser") ----------------------------------------------------------------------
+// queue_denoise queues, on the ctx's stream right behind the most recent frame's blend, the guide rebuild when the guides are
+// stale (denoise.hip: the centre rays; render_kernel's DBG instantiation: their closest hits; the guide records) and the filter's
+// iterations into d_den[2]; nothing here waits on the host.  Ordering: every reader of d_den[2] (the present kernel, the read-back
+// copy) is queued behind it on the same stream, and the next denoise is queued behind those readers.
+namespace {
+
+bool denoise_params_ok(const mrt_denoise_params* p) {
+    if (p->size != sizeof(mrt_denoise_params) || p->iterations < 1 || p->iterations > 8 || p->normal_exp > 16) return false;
+    for (float v : {p->sigma_l, p->sigma_z, p->sigma_a})
+        if (!(std::isfinite(v) && v > 0.0f)) return false;
+    for (uint32_t r : p->reserved)
+        if (r != 0) return false;
+    return true;
+}
+
+int ensure_denoise_buffers(mrt_ctx* c) {
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (!c->d_guides) {
+        HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
+        HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
+        HIP_TRY(c, hipMalloc((void**)&c->d_guide_queue, 64));
+        for (auto& d : c->d_den) HIP_TRY(c, hipMalloc((void**)&d, n * 16));
+        HIP_TRY(c, hipMalloc((void**)&c->d_guides, n * 32));
+        c->guides_stale = true;
+    }
+    const size_t words = n + ((size_t)c->n_spheres + 31) / 32 + 1;
+    if (c->guide_cand_words < words) {
+        if (c->d_guide_cand) {          // (a larger scene than before: the old bitmap may still be written by a queued rebuild)
+            MRT_TRY(mrt::wait_stream(c, c->stream, "denoiser: regrowing the guide pass' bitmap"));
+            mrt::free_device(c->d_guide_cand);
+            c->guide_cand_words = 0;
+        }
+        HIP_TRY(c, hipMalloc((void**)&c->d_guide_cand, words * sizeof(uint32_t)));
+        c->guide_cand_words = words;
+    }
+    return MRT_OK;
+}
+
+// the guides of the current camera and scene, queued on the ctx's stream
+int rebuild_guides(mrt_ctx* c) {
+    const uint32_t W = c->args.width, H = c->args.height;
+    int e = mrt::launch_guide_rays(c->d_guide_rays, W, H, c->cam_raw, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "guide rays launch failed: %s", hipGetErrorString((hipError_t)e));
+    // mrt_debug_world_hit's launch over the image itself: pixel (x, y) is ray y * W + x (world 1, texel order)
+    mrt::KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.locals = c->locals;
+    p.locals.shape[0] = W; p.locals.shape[1] = H;
+    p.locals.samples_per_frame = 1; p.locals.ray_depth = 1;
+    fill_scene_params(c, p);
+    p.shard_rank = 0; p.shard_world = 1;
+    p.seeds = c->d_seeds;
+    p.tiles_x = c->tiles_x; p.n_tiles = c->n_tiles;
+    p.tile_queue = c->d_guide_queue;
+    p.n_blocks = 1; p.pix_stride = 0; p.queue_layers = 1; p.lane_frames = 1;
+    p.dbg_rays = c->d_guide_rays; p.dbg_hit = c->d_guide_hits;
+    p.dbg_cand = c->d_guide_cand; p.dbg_words = 1;
+    e = mrt::launch_debug_world_hit(p, c->n_waves, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "guide hits launch failed: %s", hipGetErrorString((hipError_t)e));
+    e = mrt::launch_guide_fill(c->d_guide_rays, c->d_guide_hits, c->d_shade, c->d_i32 + c->world.spheres.material_ty_base_idx,
+                               c->d_guides, W, H, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "guide fill launch failed: %s", hipGetErrorString((hipError_t)e));
+    c->guides_stale = false;
+    return MRT_OK;
+}
+
+// the refusals of every denoise on a ctx; `tracking`: the filter's (the guides alone do not need noise tracking)
+int denoise_check(mrt_ctx* c, const char* who, bool tracking) {
+    if (tracking && !c->noise_on) return fail(c, MRT_ERR_STATE, "%s: noise tracking is off (mrt_set_noise_tracking)", who);
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) cannot be denoised", who, c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
+    if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
+    if (c->tiles_diverged)          // (K differs per tile: the filter has no definition for that yet)
+        return fail(c, MRT_ERR_STATE, "%s: the accumulation is adaptive (mrt_render_tiles since the last reset)", who);
+    return MRT_OK;
+}
+
+int ensure_guides(mrt_ctx* c) {
+    MRT_TRY(ensure_denoise_buffers(c));
+    if (c->guides_stale) MRT_TRY(rebuild_guides(c));
+    return MRT_OK;
+}
+
+// the most recent frame, denoised into d_den[2] (after denoise_check)
+int queue_denoise(mrt_ctx* c) {
+    MRT_TRY(ensure_guides(c));
+    const float K = (float)mrt::noise_factor_of(c->noise_c2);
+    const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, K, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
+                                      c->args.width, c->args.height, c->denoise, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
+}  // namespace
+
+namespace mrt {
+// mrt_present's part (present.cpp): checks, then queues the denoise; *src = the denoised frame
+int present_denoised(mrt_ctx* c, const float** src) {
+    MRT_TRY(queue_denoise(c));
+    *src = c->d_den[2];
+    return MRT_OK;
+}
+int present_denoised_check(mrt_ctx* c) { return denoise_check(c, "mrt_present", true); }
+}  // namespace mrt
+
+extern "C" {
+
+void mrt_denoise_params_default(mrt_denoise_params* out) {
+    if (out) *out = mrt::denoise_defaults();
+}
+
+int mrt_set_denoise_params(mrt_ctx* c, const mrt_denoise_params* params) {
+    if (!params) return MRT_ERR_INVALID_ARG;
+    if (!denoise_params_ok(params))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_denoise_params: size %u (%zu), iterations %u (1..8), normal_exp %u (0..16), "
+                    "sigma_l %g, sigma_z %g, sigma_a %g (finite, > 0), reserved 0", params->size, sizeof(mrt_denoise_params),
+                    params->iterations, params->normal_exp, params->sigma_l, params->sigma_z, params->sigma_a);
+    if (c) c->denoise = *params;          // (ctx NULL: a check of the parameters alone)
+    return MRT_OK;
+}
+
+int mrt_get_denoise_params(mrt_ctx* c, mrt_denoise_params* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = c->denoise;
+    return MRT_OK;
+}
+
+int mrt_read_denoised(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(denoise_check(c, "mrt_read_denoised", true));
+    const size_t n = (size_t)c->args.width * c->args.height * 4;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_denoised: need %zu floats", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(queue_denoise(c));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+int mrt_debug_read_guides(mrt_ctx* c, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(denoise_check(c, "mrt_debug_read_guides", false));
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_guides: need %zu pixels", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(ensure_guides(c));
+    std::vector<float> g(n * 8);
+    if (rays) HIP_TRY(c, hipMemcpyAsync(rays, c->d_guide_rays, n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g.data(), c->d_guides, n * 32, hipMemcpyDeviceToHost, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
+    for (size_t i = 0; i < n; i++) {
+        const float* r = g.data() + 8 * i;
+        if (index) std::memcpy(index + i, r + 7, 4);
+        if (t) t[i] = r[3];
+        if (normal) std::memcpy(normal + 3 * i, r, 12);
+        if (albedo) std::memcpy(albedo + 3 * i, r + 4, 12);
+    }
+    return MRT_OK;
+}
+
+int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,
+                      const mrt_denoise_params* params, float* out) {
+    if (!c || !rgba || !S || !guides || !out || !width || !rows || (uint64_t)width * rows > (1ull << 26) || std::isnan(K) || K < 0.0)
+        return MRT_ERR_INVALID_ARG;
+    const mrt_denoise_params prm = params ? *params : c->denoise;
+    if (!denoise_params_ok(&prm)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_denoise: bad parameters");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * rows;
+    float *d_fb = nullptr, *d_s = nullptr, *d_g = nullptr, *d_b[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipMalloc((void**)&d_fb, n * 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_s, n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_g, n * 32);
+    for (auto& b : d_b)
+        if (e == hipSuccess) e = hipMalloc((void**)&b, n * 16);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(d_fb, d_s, (float)K, d_g, d_b[0], d_b[1], d_b[2], width, rows, prm, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_b[2], n * 16, hipMemcpyDeviceToHost, c->stream);
+    int ws = MRT_OK;
+    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");
+    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
+    mrt::free_device(d_fb, d_s, d_g, d_b[0], d_b[1], d_b[2]);
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_denoise failed: %s", hipGetErrorString(e));
+    return MRT_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,557 @@
+// The host-side hierarchy builder: what mrt_set_world_raw (world.cpp) uploads for a scene besides the spheres themselves -- the
+// clusters, the upper levels, the boxes of large scenes, the matrix-core sweep's operand -- and the host-only diagnostics over
+// them.  Nothing here calls into the GPU runtime.
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstring>
+
+#include "hierarchy.h"
+
+namespace mrt {
+
+namespace {
+
+// Clusters.  The kernel's sweep does not need the spheres themselves, only a conservative "could this
+// ray touch it" test, so spatially close spheres are tested in CLUSTERS of up to kClusterK through one
+// bounding sphere and the per-sphere discriminants are evaluated only for the members of the few clusters
+// that pass.  A ray's expected number of candidates is proportional to the sum of the bounds' cross
+// sections, so the grouping minimises sum(R^2): spheres are split kd-tree fashion (widest axis of the
+// centres, at a multiple of kClusterK near the median) down to groups of <= 8, and such a group is cut
+// into 4 + rest by trying every choice.  Spheres far larger than the median (a ground sphere) stay alone;
+// factor == 0 (diagnostic) gives every sphere a cluster of its own.  Consecutive clusters are kd siblings, which is what
+// the upper levels (build_hierarchy) group.  R is 1.5 % above the enclosing radius measured from the
+// f32-rounded centre: part of the conservativeness argument in DESIGN.md §4.  Clusters are padded to
+// kClusterK members and the list to a multiple of kGroup with never-hit records (-r^2 = +inf gives a
+// discriminant of -inf).
+void build_clusters(const float* centers4, const float* radii, uint32_t n, float factor,
+                    std::vector<mrt::SphereRec>& clusters, std::vector<mrt::SphereRec>& members,
+                    std::vector<uint32_t>& member_index, std::vector<uint32_t>& direct) {
+    clusters.clear(); members.clear(); member_index.clear(); direct.clear();
+    const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
+    std::vector<double> rs(n);
+    for (uint32_t i = 0; i < n; i++) rs[i] = std::fabs((double)radii[i]);
+    double big = 1e300;
+    if (n > 1) {
+        std::vector<double> sorted = rs;
+        std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
+        big = 8.0 * sorted[n / 2];
+    }
+    // enclosing sphere of a set: centre of the members' common bounding box, R = max(|c_m - centre| + r_m)
+    auto enclose = [&](const uint32_t* idx, uint32_t cnt, double ctr[3]) -> double {
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (uint32_t m = 0; m < cnt; m++)
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::min(lo[k], (double)centers4[4 * idx[m] + k] - rs[idx[m]]);
+                hi[k] = std::max(hi[k], (double)centers4[4 * idx[m] + k] + rs[idx[m]]);
+            }
+        // the record stores the centre as f32: measure R from the ROUNDED centre so that it stays an enclosure
+        for (int k = 0; k < 3; k++) ctr[k] = (double)(float)(0.5 * (lo[k] + hi[k]));
+        double R = 0;
+        for (uint32_t m = 0; m < cnt; m++) {
+            double d2 = 0;
+            for (int k = 0; k < 3; k++) { const double d = (double)centers4[4 * idx[m] + k] - ctr[k]; d2 += d * d; }
+            R = std::max(R, std::sqrt(d2) + rs[idx[m]]);
+        }
+        return R;
+    };
+    std::vector<std::vector<uint32_t>> groups;
+    std::vector<uint32_t> pool;                      // spheres that may share a cluster
+    std::vector<uint32_t> alone;
+    for (uint32_t i = 0; i < n; i++) (factor > 0.0f && rs[i] <= big ? pool : alone).push_back(i);
+    // iterative kd split of pool[lo, hi)
+    std::vector<std::pair<uint32_t, uint32_t>> stack;
+    if (!pool.empty()) stack.push_back({0u, (uint32_t)pool.size()});
+    std::vector<std::pair<uint32_t, uint32_t>> leaves;      // in kd order
+    while (!stack.empty()) {
+        const auto [lo, hi] = stack.back();
+        stack.pop_back();
+        const uint32_t m = hi - lo;
+        if (m <= 2 * mrt::kClusterK) { leaves.push_back({lo, hi}); continue; }
+        double bl[3] = {1e300, 1e300, 1e300}, bh[3] = {-1e300, -1e300, -1e300};
+        for (uint32_t q = lo; q < hi; q++)
+            for (int k = 0; k < 3; k++) {
+                bl[k] = std::min(bl[k], (double)centers4[4 * pool[q] + k]);
+                bh[k] = std::max(bh[k], (double)centers4[4 * pool[q] + k]);
+            }
+        int ax = 0;
+        for (int k = 1; k < 3; k++) if (bh[k] - bl[k] > bh[ax] - bl[ax]) ax = k;
+        std::stable_sort(pool.begin() + lo, pool.begin() + hi, [&](uint32_t x, uint32_t y) {
+            const float cx = centers4[4 * x + ax], cy = centers4[4 * y + ax];
+            return cx < cy || (cx == cy && x < y);
+        });
+        uint32_t h = (m / 2 + mrt::kClusterK - 1) / mrt::kClusterK * mrt::kClusterK;
+        if (h >= m) h = m - mrt::kClusterK;
+        stack.push_back({lo + h, hi});              // popped second: keeps the leaves in left-to-right order
+        stack.push_back({lo, lo + h});
+    }
+    for (const auto& [lo, hi] : leaves) {
+        const uint32_t m = hi - lo;
+        if (m <= mrt::kClusterK) { groups.emplace_back(pool.begin() + lo, pool.begin() + hi); continue; }
+        // 5..8 spheres: the first one plus the 3 others that minimise R_A^2 + R_B^2
+        uint32_t bestmask = 0;
+        double best = 1e300;
+        for (uint32_t mask = 0; mask < (1u << m); mask++) {
+            if (!(mask & 1u) || __builtin_popcount(mask) != (int)mrt::kClusterK) continue;
+            uint32_t A[8], B[8], na = 0, nb = 0;
+            for (uint32_t q = 0; q < m; q++) ((mask >> q) & 1u ? A[na++] : B[nb++]) = pool[lo + q];
+            double ctr[3];
+            const double ra = enclose(A, na, ctr), rb = enclose(B, nb, ctr);
+            if (ra * ra + rb * rb < best) { best = ra * ra + rb * rb; bestmask = mask; }
+        }
+        std::vector<uint32_t> A, B;
+        for (uint32_t q = 0; q < m; q++) ((bestmask >> q) & 1u ? A : B).push_back(pool[lo + q]);
+        groups.push_back(A);
+        groups.push_back(B);
+    }
+    // Refinement: swap one member between two clusters whose bounds overlap (or move one into a cluster
+    // with a free slot) whenever that lowers R_a^2 + R_b^2, until nothing improves (C3: sum R^2 185 -> 175).
+    // Every pair for up to 4,096 clusters, otherwise the 32 following clusters in kd order.
+    {
+        const size_t ng = groups.size();
+        std::vector<double> gr(ng);
+        std::vector<std::array<double, 3>> gc(ng);
+        auto refresh = [&](size_t g) { double c3[3]; gr[g] = enclose(groups[g].data(), (uint32_t)groups[g].size(), c3); gc[g] = {c3[0], c3[1], c3[2]}; };
+        for (size_t g = 0; g < ng; g++) refresh(g);
+        const size_t window = ng <= 4096 ? ng : 32;
+        for (int pass = 0; pass < (ng <= 4096 ? 4 : 2); pass++) {
+            size_t improved = 0;
+            for (size_t a = 0; a < ng; a++) {
+                for (size_t b = a + 1; b < ng && b <= a + window; b++) {
+                    double d2 = 0;
+                    for (int k = 0; k < 3; k++) d2 += (gc[a][k] - gc[b][k]) * (gc[a][k] - gc[b][k]);
+                    if (d2 > (gr[a] + gr[b]) * (gr[a] + gr[b])) continue;
+                    const double base = gr[a] * gr[a] + gr[b] * gr[b];
+                    double best = base - 1e-12 * base;
+                    std::vector<uint32_t> bestA, bestB;
+                    std::vector<uint32_t> A, B;
+                    double c3[3];
+                    auto consider = [&]() {
+                        const double ra = enclose(A.data(), (uint32_t)A.size(), c3), rb = enclose(B.data(), (uint32_t)B.size(), c3);
+                        if (ra * ra + rb * rb < best) { best = ra * ra + rb * rb; bestA = A; bestB = B; }
+                    };
+                    for (size_t i = 0; i < groups[a].size(); i++)
+                        for (size_t j = 0; j < groups[b].size(); j++) {
+                            A = groups[a]; B = groups[b];
+                            std::swap(A[i], B[j]);
+                            consider();
+                        }
+                    if (groups[b].size() < mrt::kClusterK && groups[a].size() > 1)
+                        for (size_t i = 0; i < groups[a].size(); i++) {
+                            A = groups[a]; B = groups[b];
+                            B.push_back(A[i]); A.erase(A.begin() + (long)i);
+                            consider();
+                        }
+                    if (groups[a].size() < mrt::kClusterK && groups[b].size() > 1)
+                        for (size_t j = 0; j < groups[b].size(); j++) {
+                            A = groups[a]; B = groups[b];
+                            A.push_back(B[j]); B.erase(B.begin() + (long)j);
+                            consider();
+                        }
+                    if (!bestA.empty()) {
+                        groups[a] = bestA; groups[b] = bestB;
+                        refresh(a); refresh(b);
+                        improved++;
+                    }
+                }
+            }
+            if (!improved) break;
+        }
+    }
+    // the largest of the big spheres are tested by every ray directly (KParams::direct); the others get a
+    // cluster of their own
+    std::stable_sort(alone.begin(), alone.end(), [&](uint32_t x, uint32_t y) { return rs[x] > rs[y]; });
+    for (uint32_t q = 0; q < alone.size(); q++) {
+        if (factor > 0.0f && q < mrt::kMaxDirect && rs[alone[q]] > big) direct.push_back(alone[q]);
+        else groups.push_back({alone[q]});
+    }
+    for (auto& g : groups) {
+        std::sort(g.begin(), g.end());
+        double ctr[3];
+        const double R = enclose(g.data(), (uint32_t)g.size(), ctr);
+        const float Rf = (float)(R * mrt::kBoundInflate) + 1e-30f;     // rounding R to f32 moves it by 6e-8 R, the 1.5 % is for the proof
+        clusters.push_back(mrt::SphereRec{(float)ctr[0], (float)ctr[1], (float)ctr[2], -(Rf * Rf)});
+        for (uint32_t m = 0; m < mrt::kClusterK; m++) {
+            if (m < g.size()) {
+                const float r = radii[g[m]];
+                members.push_back(mrt::SphereRec{centers4[4 * g[m]], centers4[4 * g[m] + 1], centers4[4 * g[m] + 2], -(r * r)});
+                member_index.push_back(g[m]);
+            } else {
+                members.push_back(never);
+                member_index.push_back(0u);
+            }
+        }
+    }
+    while (clusters.empty() || clusters.size() % mrt::kGroup != 0) {
+        clusters.push_back(never);                                    // S = -inf: never a candidate
+        for (uint32_t m = 0; m < mrt::kClusterK; m++) { members.push_back(never); member_index.push_back(0u); }
+    }
+}
+
+// The boxes of every node (levels 1 .. top), for the walk of large scenes (kernels.hip, box_may_touch).  Node j of level k
+// covers the members [j 4^k, (j+1) 4^k) of the hierarchy part of level 0.  The test is "the LINE of the ray passes the box
+// grown by K on every side", three separating axes d x e_i; it must hold whenever the reference's discriminant of a member
+// under the node is computed >= 0, i.e. whenever the line passes within h of the member's centre,
+// h^2 <= r^2 + E, E = 14 eps |oc|^2 / a: h - r <= E / (2 r) (the quadratic form) and <= sqrt(E) (the linear form).  With
+// |oc| <= |p| + |e| (p: origin - box centre, e: half extents) and |d_j| + |d_k| <= 1.4143:
+//     quadratic   K = kc |p|^2 + kpad,  kc = 1.3e-6 / r_min,  kpad = kc |e|^2 + 4.4e-14 / kc
+//     linear      K = kc |p|_1 + kpad,  kc = 1.5e-3,          kpad = kc |e|_1
+// (each with >= 9 % to spare over 1.4143 x the bound; the 4.4e-14 / kc makes the quadratic form cover the test's own
+// rounding, 4 eps |p|_1, by the inequality of the means).  The quadratic form is far smaller at moderate distances, the
+// linear one at large distances from tiny spheres; the scene takes the one that is smaller at its own reach.
+// kc is ONE value per scene (round 5; r_min = the scene's smallest radius, which only makes K larger for the other boxes): the
+// kernel takes it from its arguments, and kpad -- the only other per-box part of K -- is folded into the extents the kernel
+// reads (pack_boxes), so a box is 24 bytes on the device.
+void build_boxes(const float* centers4, const float* radii, const std::vector<mrt::SphereRec>& members, Hierarchy& H) {
+    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, -3.0e38f, -3.0e38f, -3.0e38f, 0.0f, 0.0f};
+    H.boxes.clear();
+    // the scene's reach and median radius decide the form of the slack
+    double lo_all[3] = {1e300, 1e300, 1e300}, hi_all[3] = {-1e300, -1e300, -1e300};
+    std::vector<double> rr;
+    for (size_t m = 0; m < members.size(); m++) {
+        if (!std::isfinite(members[m].neg_r2)) continue;
+        const uint32_t i = H.member_index[m];
+        rr.push_back(std::fabs((double)radii[i]));
+        for (int k = 0; k < 3; k++) {
+            lo_all[k] = std::min(lo_all[k], (double)centers4[4 * i + k]);
+            hi_all[k] = std::max(hi_all[k], (double)centers4[4 * i + k]);
+        }
+    }
+    double reach = 0.0, r_small = 1e300;
+    if (!rr.empty()) {
+        for (int k = 0; k < 3; k++) reach += (hi_all[k] - lo_all[k]) * (hi_all[k] - lo_all[k]);
+        reach = std::sqrt(reach);
+        r_small = *std::min_element(rr.begin(), rr.end());
+    }
+    // (by the scene's SMALLEST radius, since kc is one value per scene: a scene with a few tiny spheres takes the linear form)
+    H.box_quad = 1.3e-6 / std::max(r_small, 1e-300) * reach < 1.5e-3 * 2.0;      // quadratic slack at the reach < 2 x the linear one
+    const double kc_scene = H.box_quad ? 1.3e-6 / std::max(r_small, 1e-30) : 1.5e-3;
+    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
+    for (uint32_t k = 1; k <= H.levels; k++) {
+        H.box_base[k] = (uint32_t)H.boxes.size();
+        const size_t n_k = k == H.levels ? H.top.size() : (size_t)((k + 1 < H.levels ? H.level_base[k + 1] : (uint32_t)H.nodes.size()) - H.level_base[k]);
+        const size_t span = (size_t)1 << (2 * k);
+        for (size_t j = 0; j < n_k; j++) {
+            const size_t m0 = j * span, m1 = std::min(members.size(), (j + 1) * span);
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            bool any = false;
+            for (size_t m = m0; m < m1; m++) {
+                if (!std::isfinite(members[m].neg_r2)) continue;
+                const uint32_t i = H.member_index[m];
+                const double r = std::fabs((double)radii[i]);
+                for (int q = 0; q < 3; q++) {
+                    lo[q] = std::min(lo[q], (double)centers4[4 * i + q] - r);
+                    hi[q] = std::max(hi[q], (double)centers4[4 * i + q] + r);
+                }
+                any = true;
+            }
+            if (!any) { H.boxes.push_back(never_box); continue; }
+            mrt::BoxFull b;
+            float c[3], e[3];
+            double e1 = 0.0, e2 = 0.0;
+            for (int q = 0; q < 3; q++) {
+                c[q] = (float)(0.5 * (lo[q] + hi[q]));
+                const double ext = std::max(hi[q] - (double)c[q], (double)c[q] - lo[q]) * (1.0 + 1e-6) + 1e-37;   // (the 1e-6: the three roundings of the test's right-hand side)
+                e[q] = up(ext);
+                e1 += (double)e[q];
+                e2 += (double)e[q] * (double)e[q];
+            }
+            b.cx = c[0]; b.cy = c[1]; b.cz = c[2]; b.ex = e[0]; b.ey = e[1]; b.ez = e[2];
+            b.kc = H.box_quad ? up(kc_scene) : 1.5e-3f;
+            b.kpad = H.box_quad ? up((double)b.kc * e2 + 4.4e-14 / kc_scene) : up(1.5e-3 * e1);
+            H.boxes.push_back(b);
+        }
+    }
+    H.box_kc = H.box_quad ? up(kc_scene) : 1.5e-3f;
+}
+
+uint16_t bf16_rne(float x) {
+    uint32_t u;
+    std::memcpy(&u, &x, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);      // NaN stays NaN
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+float bf16_value(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; }
+
+}  // namespace
+
+// What the kernel reads of a box (mrt_internal.h, BoxRec): the centre and the extents with kpad folded in, e' = e + kpad rounded
+// up.  The test on the axis d x e_i then has the slack kc X + kpad (|d_j| + |d_k|) instead of kc X + kpad; what is needed there is
+// rho |d x e_i| + (the test's rounding) (|d_j| + |d_k|), rho the distance beyond the box the line of a candidate can pass, and
+// |d x e_i| <= s = |d_j| + |d_k| <= 1.4143: both sides are linear in s on [0, 1] and on [1, 1.4143], at s = 0 the left side is
+// kc X >= 0, and at s = 1 and s = 1.4143 the inequality is the one build_boxes provides (kc X + kpad >= 1.4143 rho + the
+// rounding: tests/test_hierarchy_host.py checks it box by box).
+void pack_boxes(const std::vector<mrt::BoxFull>& full, std::vector<mrt::BoxRec>& out) {
+    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
+    out.resize(full.size());
+    for (size_t i = 0; i < full.size(); i++) {
+        const mrt::BoxFull& b = full[i];
+        const bool real = b.ex >= 0.0f && b.ex < 1.0e37f;           // (never-hit: -3e38; opened wide: 3e37)
+        out[i] = mrt::BoxRec{b.cx, b.cy, b.cz, real ? up((double)b.ex + (double)b.kpad) : b.ex, real ? up((double)b.ey + (double)b.kpad) : b.ey,
+                             real ? up((double)b.ez + (double)b.kpad) : b.ez};
+    }
+}
+
+// The boxes in the order the kernel walks them (KParams::boxes): depth t of the hierarchy (0 = the swept top = level
+// `levels`, levels - 1 = the clusters = level 1) at o_t = n_top (4^t - 1) / 3, n_top = the padded top: the children of node g
+// are 4 g + n_top .. + 3 whatever its depth, so a work item needs no level.  Slots without a node hold never-hit boxes.
+// `open`: every real box opened wide (extents 3e37: the test never rejects) -- the A/B form of mrt_debug_set_boxes(0).
+void boxes_top_down(const Hierarchy& H, bool open, std::vector<mrt::BoxFull>& out, uint32_t* cluster_first, uint32_t* cluster_parent_first) {
+    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, -3.0e38f, -3.0e38f, -3.0e38f, 0.0f, 0.0f};
+    const size_t n_top = H.top.size();
+    size_t o[mrt::kMaxLevels + 1];
+    o[0] = 0;
+    for (uint32_t t = 0; t < H.levels; t++) o[t + 1] = o[t] + (n_top << (2 * t));
+    out.assign(o[H.levels], never_box);
+    for (uint32_t t = 0; t < H.levels; t++) {
+        const uint32_t k = H.levels - t;                 // the level at this depth
+        const size_t first = H.box_base[k], last = k < H.levels ? H.box_base[k + 1] : H.boxes.size();
+        for (size_t j = 0; j < last - first && j < (n_top << (2 * t)); j++) {
+            mrt::BoxFull b = H.boxes[first + j];
+            if (open && b.ex >= 0.0f) b.ex = b.ey = b.ez = 3.0e37f;
+            out[o[t] + j] = b;
+        }
+    }
+    *cluster_first = (uint32_t)o[H.levels - 1];
+    *cluster_parent_first = H.levels >= 2 ? (uint32_t)o[H.levels - 2] : 0u;
+}
+
+constexpr uint32_t kBoxMinMembers = 4096;     // member slots from which the walk tests boxes by default (fill_scene_params)
+void build_hierarchy(const float* centers4, const float* radii, uint32_t n, float factor, uint32_t max_levels,
+                     uint32_t top_target, Hierarchy& H) {
+    const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
+    std::vector<mrt::SphereRec> members, cur;
+    std::vector<uint32_t> direct;
+    build_clusters(centers4, radii, n, factor, cur, members, H.member_index, direct);
+    H.nodes = members;
+    // the direct spheres follow the clusters' members in level 0 (no cluster, no bound above them)
+    H.n_direct = (uint32_t)direct.size();
+    H.direct_first = (uint32_t)members.size();
+    for (uint32_t j = 0; j < mrt::kClusterK; j++) {
+        mrt::SphereRec rec = never;
+        uint32_t idx = 0;
+        if (j < direct.size()) {
+            idx = direct[j];
+            const float r = radii[idx];
+            rec = mrt::SphereRec{centers4[4 * idx], centers4[4 * idx + 1], centers4[4 * idx + 2], -(r * r)};
+        }
+        H.direct[j] = rec;
+        H.direct_index[j] = idx;
+        if (!direct.empty()) { H.nodes.push_back(rec); H.member_index.push_back(idx); }
+    }
+    static_assert(mrt::kMaxDirect == mrt::kClusterK, "level 0 stays a multiple of kClusterK");
+    H.n_members = (uint32_t)H.nodes.size();
+    H.levels = 1;
+    H.level_base[0] = 0;
+    // scenes whose members fit 10-bit ids (the kernel's SMALL variant) keep one level: with <= 256 clusters
+    // the sweep is cheap and the bounds of 16 spheres are loose (C3: a ray touches 10 of 38 such bounds)
+    if (H.n_members <= 1024u) max_levels = 1;      // (same test as scene_is_small() in kernels.hip)
+    // top_target 0 = automatic: levels are added while the top has more than 256 records -- 128 where the walk tests boxes
+    // below the top, which make a smaller top cheaper (round 3: 4,901 spheres 34.1 -> 33.3 ms per 64-spp frame, 10,001 spheres
+    // 48.2 -> 47.3; without boxes 1,297 / 2,501 spheres lose 20 % with a top of <= 64)
+    if (top_target == 0) top_target = H.n_members > kBoxMinMembers ? 128u : 256u;
+    while (H.levels < max_levels && cur.size() > top_target) {
+        const size_t span = (size_t)1 << (2 * (H.levels + 1));        // members under one node of the new level
+        const size_t n_par = (cur.size() + 3) / 4;
+        std::vector<mrt::SphereRec> par;
+        par.reserve(n_par + mrt::kGroup);
+        for (size_t j = 0; j < n_par; j++) {
+            const size_t m0 = j * span, m1 = std::min(members.size(), (j + 1) * span);
+            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+            bool any = false;
+            for (size_t m = m0; m < m1; m++) {
+                if (!std::isfinite(members[m].neg_r2)) continue;
+                const uint32_t i = H.member_index[m];
+                const double r = std::fabs((double)radii[i]);
+                for (int k = 0; k < 3; k++) {
+                    lo[k] = std::min(lo[k], (double)centers4[4 * i + k] - r);
+                    hi[k] = std::max(hi[k], (double)centers4[4 * i + k] + r);
+                }
+                any = true;
+            }
+            if (!any) { par.push_back(never); continue; }
+            double ctr[3], R = 0;
+            for (int k = 0; k < 3; k++) ctr[k] = (double)(float)(0.5 * (lo[k] + hi[k]));
+            for (size_t m = m0; m < m1; m++) {
+                if (!std::isfinite(members[m].neg_r2)) continue;
+                const uint32_t i = H.member_index[m];
+                double d2 = 0;
+                for (int k = 0; k < 3; k++) { const double d = (double)centers4[4 * i + k] - ctr[k]; d2 += d * d; }
+                R = std::max(R, std::sqrt(d2) + std::fabs((double)radii[i]));
+            }
+            const float Rf = (float)(R * mrt::kBoundInflate) + 1e-30f;
+            par.push_back(mrt::SphereRec{(float)ctr[0], (float)ctr[1], (float)ctr[2], -(Rf * Rf)});
+        }
+        while (cur.size() % 4 != 0) cur.push_back(never);
+        H.level_base[H.levels] = (uint32_t)H.nodes.size();
+        H.nodes.insert(H.nodes.end(), cur.begin(), cur.end());
+        cur.swap(par);
+        H.levels++;
+    }
+    while (cur.empty() || cur.size() % 32 != 0) cur.push_back(never);      // 32 = one tile of the matrix-core sweep
+    H.top.swap(cur);
+    build_boxes(centers4, radii, members, H);
+}
+
+// The top level once more, as the A operand of the matrix-core sweep (kernels.hip, mfma_sweep_tile): per
+// tile of 32 records 64 lanes x 8 bf16, lane l = row (l & 31), k = 8 (l >> 5) + j:
+//     k 0..2 C_hi, 3..5 C_hi, 6..8 C_lo, 9..11 (1,1,1), 12..14 Ck (hi, mid, lo), 15: 0
+// where row m of tile t is record 32 t + 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3) -- the order in which the
+// MFMA result registers come out, so that the two 16-bit sign words per tile are the masks of chunks 2t and
+// 2t + 1.  Ck = C.C - R^2 - 2^-13 (C.C + R^2): the record's share of the slack that covers what the bf16
+// split drops.  A never-hit record gets Ck = 3e38 (finite: an infinity would turn the other
+// GEMM's 0 x Ck into NaN).  Also returns what set_world needs to decide whether the slack is negligible:
+// the largest C.C and the median R^2.
+void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t>& out, float origin[3], double* max_c2,
+                    double* med_r2, size_t* n_real) {
+    const size_t tiles = top.size() / 32;
+    out.assign(tiles * 512, 0);
+    std::vector<double> r2s;
+    *max_c2 = 0.0;
+    // the GEMMs run in coordinates relative to the centre of the records' bounding box (the slack grows with the
+    // squared distances from THAT point, wherever the scene sits); the kernel subtracts it from the ray origin
+    double lo[3] = {1e300, 1e300, 1e300}, hi3[3] = {-1e300, -1e300, -1e300};
+    for (const auto& r : top) {
+        if (!std::isfinite(r.neg_r2)) continue;
+        const double c[3] = {r.cx, r.cy, r.cz};
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], c[k]); hi3[k] = std::max(hi3[k], c[k]); }
+    }
+    for (int k = 0; k < 3; k++) origin[k] = lo[k] <= hi3[k] ? (float)(0.5 * (lo[k] + hi3[k])) : 0.0f;
+    const uint16_t one = bf16_rne(1.0f);
+    for (size_t t = 0; t < tiles; t++)
+        for (uint32_t m = 0; m < 32; m++) {
+            const mrt::SphereRec& r = top[32 * t + 16 * ((m >> 2) & 1u) + 4 * (m >> 3) + (m & 3u)];
+            float ck = 3.0e38f;
+            // centre relative to the origin: exact in double, then rounded to f32 -- the rounding moves the bound by
+            // at most 2 eps |c|, which its radius absorbs
+            const float c[3] = {(float)((double)r.cx - origin[0]), (float)((double)r.cy - origin[1]), (float)((double)r.cz - origin[2])};
+            if (std::isfinite(r.neg_r2)) {
+                const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
+                const double R = std::sqrt(-(double)r.neg_r2) + 2.0 * 0x1p-24 * std::sqrt(c2), R2 = R * R;
+                const double v = c2 - R2 - kMfmaSlack * (c2 + R2);
+                ck = (float)v;
+                if ((double)ck > v) ck = std::nextafterf(ck, -INFINITY);
+                *max_c2 = std::max(*max_c2, c2);
+                r2s.push_back(R2);
+            }
+            uint16_t hi[3], lo16[3];
+            for (int k = 0; k < 3; k++) { hi[k] = bf16_rne(c[k]); lo16[k] = bf16_rne(c[k] - bf16_value(hi[k])); }
+            const uint16_t k0 = bf16_rne(ck);
+            const float ck1 = ck - bf16_value(k0);
+            const uint16_t k1 = bf16_rne(ck1), k2 = bf16_rne(ck1 - bf16_value(k1));
+            const uint16_t kvals[16] = {hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo16[0], lo16[1], lo16[2], one, one, one, k0, k1, k2, 0};
+            uint16_t* o = out.data() + t * 512;
+            for (int k = 0; k < 16; k++) o[((k >> 3) * 32 + m) * 8 + (k & 7)] = kvals[k];
+        }
+    *n_real = r2s.size();
+    *med_r2 = 0.0;
+    if (!r2s.empty()) { std::nth_element(r2s.begin(), r2s.begin() + r2s.size() / 2, r2s.end()); *med_r2 = r2s[r2s.size() / 2]; }
+}
+
+// KParams::mfma_scale / mfma_neg_k2_pair for rays and records within `all` of the sweep's origin (mrt_debug_mfma_scale)
+void mfma_scales(double all, float scale[4], uint32_t* neg_k2_pair) {
+    if (!(all > 1e-30)) all = 1.0;
+    int e = 0;
+    (void)std::frexp(5.01 * all, &e);                       // 5.01 all < 2^e
+    const double K = std::ldexp(1.0, -(e + 1)), K2 = K * K;
+    scale[0] = (float)((double)mrt::kBoundStretch * K);
+    scale[1] = (float)(2.0 * K2);
+    scale[2] = (float)(-(1.0 - kMfmaSlack) * K2);
+    scale[3] = (float)(16.0 * all * all);
+    const uint32_t nk2 = (uint32_t)bf16_rne((float)-K2);    // a power of two: exact
+    *neg_k2_pair = nk2 | (nk2 << 16);
+}
+
+}  // namespace mrt
+
+using mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::boxes_top_down, mrt::pack_boxes, mrt::mfma_scales;
+
+extern "C" {
+
+int mrt_debug_build_hierarchy(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target,
+                              float* top_out, size_t top_cap, float* nodes_out, size_t nodes_cap,
+                              uint32_t* member_index_out, size_t member_cap, uint16_t* mfma_out, size_t mfma_cap,
+                              float mfma_origin_out[3], uint32_t info[10]) {
+    if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
+        return MRT_ERR_INVALID_ARG;
+    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+        centers[4 * i + 3] = 1.0f;
+        radii[i] = spheres[i].radius;
+    }
+    Hierarchy h;
+    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    std::vector<uint16_t> mf;
+    float origin[3];
+    double max_c2, med_r2;
+    size_t n_real;
+    build_top_mfma(h.top, mf, origin, &max_c2, &med_r2, &n_real);
+    info[0] = h.levels; info[1] = (uint32_t)h.top.size(); info[2] = (uint32_t)h.nodes.size(); info[3] = h.n_members;
+    info[4] = h.n_direct; info[5] = h.direct_first;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) info[6 + k] = h.level_base[k];
+    if ((top_out && top_cap < h.top.size()) || (nodes_out && nodes_cap < h.nodes.size()) ||
+        (member_index_out && member_cap < h.member_index.size()) || (mfma_out && mfma_cap < mf.size()))
+        return MRT_ERR_TOO_SMALL;
+    if (top_out) std::memcpy(top_out, h.top.data(), h.top.size() * sizeof(mrt::SphereRec));
+    if (nodes_out) std::memcpy(nodes_out, h.nodes.data(), h.nodes.size() * sizeof(mrt::SphereRec));
+    if (member_index_out) std::memcpy(member_index_out, h.member_index.data(), h.member_index.size() * sizeof(uint32_t));
+    if (mfma_out) std::memcpy(mfma_out, mf.data(), mf.size() * sizeof(uint16_t));
+    if (mfma_origin_out) for (int k = 0; k < 3; k++) mfma_origin_out[k] = origin[k];
+    return MRT_OK;
+}
+
+int mrt_debug_build_boxes_top_down(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, int open,
+                                   float* boxes_out, size_t boxes_cap, uint32_t info[5]) {
+    if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
+        return MRT_ERR_INVALID_ARG;
+    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+        centers[4 * i + 3] = 1.0f;
+        radii[i] = spheres[i].radius;
+    }
+    Hierarchy h;
+    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    std::vector<mrt::BoxFull> full;
+    std::vector<mrt::BoxRec> packed;
+    uint32_t cf = 0, cpf = 0;
+    boxes_top_down(h, open != 0, full, &cf, &cpf);
+    pack_boxes(full, packed);
+    // what the kernel reads, in the 8-float form of mrt_debug_build_boxes: centre, the extents WITH kpad folded in, the scene's kc, 0
+    std::vector<mrt::BoxFull> dev(full.size());
+    for (size_t i = 0; i < full.size(); i++)
+        dev[i] = mrt::BoxFull{packed[i].cx, packed[i].cy, packed[i].cz, packed[i].ex, packed[i].ey, packed[i].ez, full[i].ex >= 0.0f ? h.box_kc : 0.0f, 0.0f};
+    info[0] = h.levels; info[1] = (uint32_t)dev.size(); info[2] = (uint32_t)h.top.size(); info[3] = cf; info[4] = cpf;
+    if (boxes_out && boxes_cap < dev.size()) return MRT_ERR_TOO_SMALL;
+    if (boxes_out) std::memcpy(boxes_out, dev.data(), dev.size() * sizeof(mrt::BoxFull));
+    return MRT_OK;
+}
+
+int mrt_debug_build_boxes(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, float* boxes_out,
+                          size_t boxes_cap, uint32_t info[8]) {
+    if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
+        return MRT_ERR_INVALID_ARG;
+    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+        centers[4 * i + 3] = 1.0f;
+        radii[i] = spheres[i].radius;
+    }
+    Hierarchy h;
+    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    info[0] = h.levels; info[1] = (uint32_t)h.boxes.size(); info[2] = h.box_quad ? 1u : 0u;
+    for (uint32_t k = 0; k <= mrt::kMaxLevels; k++) info[3 + k] = h.box_base[k];
+    if (boxes_out && boxes_cap < h.boxes.size()) return MRT_ERR_TOO_SMALL;
+    if (boxes_out) std::memcpy(boxes_out, h.boxes.data(), h.boxes.size() * sizeof(mrt::BoxFull));
+    return MRT_OK;
+}
+
+int mrt_debug_mfma_scale(double reach, float scale_out[4], uint32_t* neg_k2_bf16_pair_out) {
+    if (!scale_out || !neg_k2_bf16_pair_out || !(reach >= 0.0) || !std::isfinite(reach)) return MRT_ERR_INVALID_ARG;
+    mfma_scales(reach, scale_out, neg_k2_bf16_pair_out);
+    return MRT_OK;
+}
+
+}  // extern "C"

@@ -172,11 +172,11 @@ __device__ __forceinline__ void test8(const Sph8& g, V3 o, V3 ds, uint32_t& bits
 // (necessary and sufficient for a line and a box; the parts of the line behind the origin are left to the sphere tests).
 // K = kc X + kpad, X = |p|^2 or |p|_1 (per scene), is the slack that makes it CONSERVATIVE against the reference's own
 // rounding: a member whose computed discriminant is >= 0 has the line within sqrt(r^2 + 14 eps |oc|^2 / a) of its centre,
-// i.e. up to min(14 eps |oc|^2 / (2 r), sqrt(14 eps) |oc|) beyond its surface, hence beyond its box; the host (api.cpp,
+// i.e. up to min(14 eps |oc|^2 / (2 r), sqrt(14 eps) |oc|) beyond its surface, hence beyond its box; the host (hierarchy.cpp,
 // build_boxes) sets kc per scene and kpad per box so that K covers 1.4143 x that for every member under the node, plus the
 // test's own rounding (4 eps |p|_1; the right-hand side's three roundings are in the extents).  The kernel reads kpad FOLDED
 // INTO THE EXTENTS (e + kpad: on the axis d x e_i that is a slack of kpad (|d_j| + |d_k|), which covers what "+ kpad" covered:
-// api.cpp, pack_boxes) and kc from its arguments, so a box is 24 bytes.  A never-hit box has extents
+// hierarchy.cpp, pack_boxes) and kc from its arguments, so a box is 24 bytes.  A never-hit box has extents
 // -3e38: some axis' right-hand side is then hugely negative (a unit direction has a component >= 0.57).
 // 24 VALU: 3 + 3 (X) + 1 (K) + 3 x 5 + 2.
 // (c, e): a BoxRec -- the centre and the half extents with kpad folded in (mrt_internal.h); kc: the scene's coefficient of X.
@@ -220,7 +220,7 @@ __device__ __forceinline__ bool box_may_touch(const V3 c, const V3 e, const floa
 // power of two changes no rounding.  What the split drops (C_lo v_lo and the remainders: 3 x 2^-18 of
 // every product) and the f32 accumulation err by at most 2.5e-5 o.o + 5e-5 C.C in S; the
 // test gives away 2^-13 = 1.2e-4 of o.o + C.C + R^2: o.o is scaled by 1 - 2^-13 (in mfma_scale[2]) and the host
-// lowers Ck by 2^-13 (C.C + R^2) (api.cpp, build_top_mfma).  o and C are taken relative to the centre of the
+// lowers Ck by 2^-13 (C.C + R^2) (hierarchy.cpp, build_top_mfma).  o and C are taken relative to the centre of the
 // records' bounding box (P.mfma_origin; the rounding of o - origin is relative to the difference), so the
 // slack does not depend on where the scene sits, only on its extent against R: the host selects this
 // variant only where it is small against R^2; elsewhere the SGPR-fed sweep above runs.
@@ -271,7 +271,7 @@ __device__ __forceinline__ MfmaRay mfma_ray_operands(V3 o, V3 dsk, float o2, flo
     return m;
 }
 // one tile of 32 records against the wave's 64 rays; `a` = this lane's 8 bf16 of the tile's A operand
-// (api.cpp, build_top_mfma).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
+// (hierarchy.cpp, build_top_mfma).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
 // lane's own ray.
 __device__ __forceinline__ uint32_t mfma_sweep_tile(const u32x4 a, const MfmaRay& m) {
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -407,7 +407,7 @@ constexpr uint32_t kWavesPerGroup = 4;
 // is ray number `texel` of P.dbg_rays, traced once; the winner goes to P.dbg_hit and every (ray, sphere) that
 // reaches the root tests is recorded in P.dbg_cand.  Nothing else of the kernel changes.
 // SC: the scene's layout -- 0 = SMALL (above), 1 / 2 = large, with the linear / the quadratic form of the box test's slack
-// (api.cpp build_boxes; a compile-time choice: as a run-time flag it was two branches in every box test).
+// (hierarchy.cpp build_boxes; a compile-time choice: as a run-time flag it was two branches in every box test).
 template <bool COUNT, bool PILOT, bool CTR, int SC, bool MFMA, bool DBG = false>
 // Registers: small scenes run 5 workgroups per CU (their LDS footprint, 31.5 KB at C3) = 5 waves per SIMD = 96 VGPRs; large
 // scenes (work queues of every level, u32 items: 33-36 KB per workgroup) fit 4 workgroups per CU whatever the kernel does, so
@@ -418,7 +418,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
     constexpr uint32_t kIdBits = Ent<SMALL>::id_bits;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    // small scenes always have one level (api.cpp)
+    // small scenes always have one level (hierarchy.cpp)
     const uint32_t levels = SMALL ? 1u : P.levels;
     // (small scenes: the member records, then their sphere indices as u16 -- what a root round reads per item; from L2 the
     // index was a dependent global load in the middle of every root round)
@@ -570,7 +570,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // o + t d of a finite ray and t < 1e4, and a hit point that is not finite makes the normal, hence the
             // scattered direction, NaN in the same iteration.
             // (matrix-core sweep: so does an origin further from the scene than the sweep's scaling admits -- 4 x the
-            // distance of the camera or of the farthest sphere surface, api.cpp: no ray of a frame, but a caller's ray
+            // distance of the camera or of the farthest sphere surface, world.cpp: no ray of a frame, but a caller's ray
             // under mrt_debug_world_hit may be)
             const V3 o_rel = MFMA ? v3(o.x - P.mfma_origin[0], o.y - P.mfma_origin[1], o.z - P.mfma_origin[2]) : o;
             const float o_rel2 = MFMA ? dot3(o_rel, o_rel) : 0.0f;
@@ -643,7 +643,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 asm volatile("" : "=s"(gb.lo), "=s"(gb.hi));   // defined (uniform) on every path to the block's final wait
                 uint32_t c = 0;
                 for (uint32_t i = blk; i < blk_end; i += kChunk, c++) {
-                    // (the record count is a multiple of 32 -- api.cpp pads the top level to whole matrix-core tiles --
+                    // (the record count is a multiple of 32 -- hierarchy.cpp pads the top level to whole matrix-core tiles --
                     // so every chunk is full and chunks come in pairs)
                     smem_wait_then_load8(ga, gb, sph_quads, i + 8u, bits);  test8(ga, o, ds, bits);
                     const uint32_t nxt = (i + kChunk < n_padded) ? i + kChunk : 0u;   // next chunk, or a harmless reload
@@ -1194,7 +1194,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     if (is_metal) { refl = reflect3(d, normal); fuzz = sh1.w; }     // :230, :232
                 } else if (m_ty == MRT_DIELECTRIC) {                        // extension, DESIGN.md §3
                     // The quantities that depend on the sphere alone come from its shading record, evaluated by
-                    // the host with the same f32 operations (api.cpp): 1/ior and ((1-ri)/(1+ri))^2 for ri = 1/ior
+                    // the host with the same f32 operations (world.cpp): 1/ior and ((1-ri)/(1+ri))^2 for ri = 1/ior
                     // (front face) and ri = ior (back face).  The attenuation of a Dielectric is (1,1,1).
                     const float ior = sh1.w;
                     const float ri = front_face ? sh1.x : ior;

@@ -1,5 +1,6 @@
-// Host-side state behind the opaque mrt_ctx of include/myraytracer_amd.h, shared by api.cpp (the frame loop)
-// and multi_gpu.cpp (the gather).  Internal: not installed.
+// Host-side state behind the opaque mrt_ctx of include/myraytracer_amd.h, and what the host files share: api.cpp (life cycle,
+// buffers, read-backs), world.cpp (the scene), frames.cpp (the frame loop), present.cpp, noise.cpp, denoise.cpp and multi_gpu.cpp
+// (the gather).  Internal: not installed.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -148,7 +149,7 @@ struct mrt_ctx {
     hipEvent_t ev_gather_root = nullptr;
     bool gather_per_band = false;              // mrt_debug_set_gather_per_band: the cross-device copy loop on one device
 
-    // present pass (mrt_present, api.cpp): a ring of images, each the present kernel's output on the device, its copy in pinned
+    // present pass (mrt_present, present.cpp): a ring of images, each the present kernel's output on the device, its copy in pinned
     // host memory and the event that says the copy has landed.  An entry is free, queued (presented, not acquired: its copy may
     // still be in flight) or held by the caller (mrt_present_acquire); entries are added, never freed before mrt_destroy.
     struct PresentEntry {
@@ -169,7 +170,7 @@ struct mrt_ctx {
     hipEvent_t ev_presented = nullptr;              // "the present kernel is done", on the ctx's stream (mode 0)
     float* d_present_tables = nullptr;              // present_thresholds() on the device
 
-    // noise estimate (mrt_set_noise_tracking / mrt_noise_query, api.cpp): S, updated by every blend while tracking is on; the
+    // noise estimate (mrt_set_noise_tracking / mrt_noise_query, noise.cpp): S, updated by every blend while tracking is on; the
     // reduction's scratch and tile map; a ring of reports, each the reduction's sums on the device, their copy in pinned host
     // memory and the event that says the copy has landed.  Entry seq % kNoiseRing holds query seq.
     static constexpr uint32_t kNoiseRing = 8;
@@ -190,7 +191,7 @@ struct mrt_ctx {
     uint64_t noise_first = 1;                       // the oldest query whose report may still be returned (mrt_reset)
     hipStream_t noise_stream = nullptr;             // mrt_read_noise_tiles' copy, created on first use
 
-    // denoiser (mrt_read_denoised / MRT_PRESENT_DENOISED, api.cpp; denoise.hip): the parameters, the first-hit guides of the
+    // denoiser (mrt_read_denoised / MRT_PRESENT_DENOISED, denoise.cpp; denoise.hip): the parameters, the first-hit guides of the
     // current camera and scene (width x height pixels, y * width + x; rebuilt on the ctx's stream at the next denoise after
     // mrt_set_camera / mrt_set_world* / mrt_set_shard mark them stale) and the filter's buffers, all allocated at the first use
     mrt_denoise_params denoise = mrt::denoise_defaults();
@@ -205,7 +206,7 @@ struct mrt_ctx {
     float* d_guides = nullptr;                      // 2 float4 per pixel
     float* d_den[3] = {nullptr, nullptr, nullptr};  // ping, pong, the denoised frame: a float4 per pixel
 
-    // adaptive sampling (mrt_render_tiles / mrt_render_adaptive, api.cpp; adaptive.hip): every tile's frame count n_t.  Until the
+    // adaptive sampling (mrt_render_tiles / mrt_render_adaptive, frames.cpp / noise.cpp; adaptive.hip): every tile's frame count n_t.  Until the
     // first subset frame every n_t is frames_done and nothing differs from a uniform accumulation.  From it on (tiles_diverged,
     // until mrt_reset) every blend is per tile (launch_tile_blend) and IN PLACE on d_fb[target ^ 1] (target no longer swaps), and
     // noise reports take K per tile from the tables K(n) = mrt_noise_factor(n, max_w), n < k_len, grown on demand.
@@ -247,6 +248,13 @@ int fail(mrt_ctx* ctx, int status, const char* fmt, ...) __attribute__((format(p
 
 inline uint32_t total_bands(uint32_t height) { return (height + kBandRows - 1) / kBandRows; }
 inline size_t local_texels(const mrt_ctx* c) { return (size_t)c->local_bands * kBandRows * c->args.width; }
+// ... at least 1: the size of an allocation that an empty shard makes all the same
+inline size_t local_texels_min1(const mrt_ctx* c) { return local_texels(c) ? local_texels(c) : 1; }
+inline uint32_t tiles_min1(const mrt_ctx* c) { return c->n_tiles ? c->n_tiles : 1; }
+
+// free device / pinned allocations (those there are) and forget them
+template <typename... T> void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+template <typename T> void free_pinned(T*& p) { if (p) (void)hipHostFree(p); p = nullptr; }
 
 // Bounded host waits (api.cpp): poll the event / stream until it is complete or the context's deadline has passed; `what`
 // names the wait in the error message.  Return an mrt_status.
@@ -254,6 +262,26 @@ int wait_event(mrt_ctx* c, hipEvent_t ev, const char* what);
 int wait_stream(mrt_ctx* c, hipStream_t s, const char* what);
 // everything this context has in flight: the side streams, then the caller's stream
 int wait_all(mrt_ctx* c, const char* what);
+
+// What one host file defines and another calls.  api.cpp: the current shard's buffers (re)allocated; the scene's arrays released;
+// a slot's first layer of colour sums, zeroed on the ctx's stream; the tail of a read-back of this shard's texels (`who`: the entry
+// point, for the messages) -- capacity check, the full bottom-up image when shard_world == 1 else the packed rows, bounded wait
+int alloc_frame_buffers(mrt_ctx* c);
+void free_world(mrt_ctx* c);
+int alloc_first_colour_sums(mrt_ctx* c, mrt_ctx::FrameSlot& S);
+int read_rows(mrt_ctx* c, const char* who, const void* src, void* out, size_t cap, size_t texel_bytes);
+// world.cpp: the scene / hierarchy / sweep-variant part of the kernel arguments
+void fill_scene_params(const mrt_ctx* c, KParams& p);
+// frames.cpp: the side stream of a frame slot and its events; adaptive sampling's per-tile state, released
+hipError_t create_slot_streams(mrt_ctx::FrameSlot& S);
+void free_tile_frames(mrt_ctx* c);
+// noise.cpp: noise tracking's per-texel buffers, sized like the framebuffers
+void free_noise_buffers(mrt_ctx* c);
+int alloc_noise_buffers(mrt_ctx* c);
+// denoise.cpp: the denoiser's buffers released; its part of mrt_present (present.cpp): the refusals; the denoise queued, *src = its output
+void free_denoise_buffers(mrt_ctx* c);
+int present_denoised_check(mrt_ctx* c);
+int present_denoised(mrt_ctx* c, const float** src);
 
 }  // namespace mrt
 

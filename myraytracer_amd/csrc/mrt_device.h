@@ -42,7 +42,7 @@ __device__ __forceinline__ float sqrt_unscaled(float x) {
     return s;
 }
 constexpr float kDivMinNum = 0x1p-90f, kDivMinDen = 0x1p-30f;       // the tested call sites' bounds (upper bounds: 2^30, from
-                                                                    // the ABI's |coordinate| <= 1e7, api.cpp)
+                                                                    // the ABI's |coordinate| <= 1e7, world.cpp)
 // The two call sites whose operands are TESTED (per wave: any lane failing sends its wave down the literal `/` and sqrtf()):
 // the hit normal (at - centre) / radius -- every component at least 2^-90 in magnitude (in particular not 0), |radius| >= 2^-30 --
 // and normalize(dir) = dir / sqrt(dot(dir, dir)) -- the same for the components, the squared length in [2^-60, 2^60).

@@ -1,5 +1,5 @@
 // Internal types shared by the HIP kernels (kernels.hip) and the host side of the C ABI
-// (api.cpp).  Not installed; the public contract is include/myraytracer_amd.h.
+// (api.cpp and the files beside it).  Not installed; the public contract is include/myraytracer_amd.h.
 #pragma once
 #include <stdint.h>
 #include "../../include/myraytracer_amd.h"
@@ -30,11 +30,11 @@ struct alignas(16) SphereRec { float cx, cy, cz, neg_r2; };
 
 // Axis-aligned box of the member spheres under a node of the hierarchy (large scenes: the walk's second, much tighter bound
 // -- a kd-built group of spheres on a plane fills its box, not its bounding sphere).
-// BoxFull: what the host derives per node (api.cpp, build_boxes) and the diagnostics report: centre, half extents (measured
+// BoxFull: what the host derives per node (hierarchy.cpp, build_boxes) and the diagnostics report: centre, half extents (measured
 // from the f32 centre, rounded up) and the two coefficients of the test's slack K = kc X + kpad (X = |p|^2 or |p|_1 of the ray
 // origin relative to the centre, per scene: KParams::box_quad); kc is ONE value per scene (KParams::box_kc).
 // BoxRec: what the kernel reads, 24 bytes: the centre and the half extents WITH kpad folded in (e + kpad, rounded up) -- on the
-// axis d x e_i the slack kpad (|d_j| + |d_k|) that gives covers what the "+ kpad" of the test covered (api.cpp, pack_boxes) --
+// axis d x e_i the slack kpad (|d_j| + |d_k|) that gives covers what the "+ kpad" of the test covered (hierarchy.cpp, pack_boxes) --
 // so an inner item's four children are 96 bytes instead of 128: a large scene's rounds wait for the vector-memory path's
 // 64 bytes per clock and CU.  A never-hit box has extents -3e38.
 struct BoxFull { float cx, cy, cz, ex, ey, ez, kc, kpad; };
@@ -53,7 +53,7 @@ struct KParams {
     uint32_t shard_rank, shard_world;
     uint32_t cus;               // compute units of the device (host-side launch sizing only)
     const SphereRec* spheres;   // n_spheres records in the reference's order (exact tests)
-    // Bounding-sphere hierarchy (api.cpp build_hierarchy): level 0 = the member spheres in cluster order
+    // Bounding-sphere hierarchy (hierarchy.cpp build_hierarchy): level 0 = the member spheres in cluster order
     // (4 per cluster, short clusters padded with never-hit records), level 1 = the clusters' bounds
     // (cx,cy,cz,-R^2), level k+1 = bounds of 4 consecutive level-k nodes; node j of level k has the
     // children 4j..4j+3 of level k-1.  The sweep runs over the TOP level (`levels`): `clusters`, n_padded
@@ -62,11 +62,11 @@ struct KParams {
     const SphereRec* clusters;
     // the same top-level records as the A operand of the matrix-core sweep (kernels.hip, mfma_sweep_tile):
     // per tile of 32 records 64 lanes x 8 bf16, record order within a tile permuted to the result layout;
-    // use_mfma selects that variant of the sweep (api.cpp decides per scene and camera)
+    // use_mfma selects that variant of the sweep (world.cpp decides per scene and camera)
     const uint16_t* top_mfma;
     uint32_t use_mfma;
     float mfma_origin[3];       // the records of top_mfma are relative to this point (centre of their bounding box)
-    // The ray-side factors of the matrix-core sweep (api.cpp, fill_scene_params): with K a power of two such that
+    // The ray-side factors of the matrix-core sweep (world.cpp, fill_scene_params): with K a power of two such that
     // |K oc.ds| <= 1/2 for every ray the sweep admits, {kBoundStretch K, 2 K^2, -(1 - 2^-13) K^2, the largest admitted
     // |o - mfma_origin|^2}, and -K^2 as a pair of bf16 (kernels.hip, mfma_ray_operands)
     float mfma_scale[4];
@@ -84,7 +84,7 @@ struct KParams {
     // the capacity of the wave's work stack.  Null / 0 for small scenes.
     const BoxRec* boxes;
     uint32_t box_cluster_first, box_cluster_parent_first, box_quad;
-    float box_kc;               // the slack's coefficient of X, one per scene (api.cpp, build_boxes)
+    float box_kc;               // the slack's coefficient of X, one per scene (hierarchy.cpp, build_boxes)
     // the first box_lds_count boxes of that numbering (the swept top, and the level below it where it fits) are copied into
     // the workgroup's LDS: what the owners' filter and the first inner rounds read (kernels.hip)
     uint32_t box_lds_count;
@@ -98,7 +98,7 @@ struct KParams {
     const float* f32_data;      // r_f32_data
     const int32_t* i32_data;    // r_i32_data
     // per sphere, in the reference's order: (cx, cy, cz, radius) (albedo r, g, b, fuzz | ior) -- copies of the
-    // entries of the three arrays above that shading the sphere reads (api.cpp)
+    // entries of the three arrays above that shading the sphere reads (world.cpp)
     const float* shade;
     const uint32_t* seeds;      // r_rands: local_rows x W x [u32;4]
     const float* prev;          // r_framebuffer: local_rows x W x rgba

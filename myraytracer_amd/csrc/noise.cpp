@@ -1,0 +1,304 @@
+// The noise estimate of include/myraytracer_amd.h: S and its reports, and adaptive sampling's selection from them.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include "mrt_ctx.h"
+
+using mrt::fail, mrt::local_texels, mrt::free_noise_buffers, mrt::alloc_noise_buffers;
+
+namespace mrt {
+
+// noise tracking's per-texel buffers, sized like the framebuffers (mrt_set_noise_tracking)
+void free_noise_buffers(mrt_ctx* c) { free_device(c->d_noise_s, c->d_noise_tiles, c->d_noise_partials); }
+
+int alloc_noise_buffers(mrt_ctx* c) {
+    free_noise_buffers(c);
+    const size_t n = local_texels_min1(c);
+    HIP_TRY(c, hipMalloc((void**)&c->d_noise_s, n * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(c->d_noise_s, 0, n * sizeof(float), c->stream));
+    const size_t map_floats = (size_t)mrt_ctx::kNoiseRing * tiles_min1(c);     // a tile map per report of the ring
+    HIP_TRY(c, hipMalloc((void**)&c->d_noise_tiles, map_floats * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(c->d_noise_tiles, 0, map_floats * sizeof(float), c->stream));
+    HIP_TRY(c, hipMalloc(&c->d_noise_partials, std::max<size_t>(mrt::noise_partials_bytes(c->args.width, c->local_bands), 64)));
+    c->noise_first = c->noise_seq + 1;          // (reports of the old geometry are discarded)
+    return MRT_OK;
+}
+
+}  // namespace mrt
+
+// ---- noise estimate (include/myraytracer_amd.h, "noise estimate") ----------------------------------------------------------
+// While tracking is on, every blend also updates S (finalize_tracked_kernel, kernels.hip) and the host follows c2 (noise_c2).
+// mrt_noise_query queues, on the ctx's stream right behind the most recent frame's blend, the reduction (noise.hip) into the
+// ring entry's device sums and the copy of those 48 bytes into pinned host memory, and records the entry's event; nothing
+// here waits for the frames in flight.  Ordering: S and the framebuffer the reduction reads are next written by blends queued
+// after it on the same stream; the scratch and the tile map are written only by reductions, in stream order.
+namespace {
+
+using NoiseEntry = mrt_ctx::NoiseEntry;
+constexpr uint32_t kNoiseRing = mrt_ctx::kNoiseRing;
+
+// the ring's pinned sums, device sums and events, kept from the first enable to mrt_destroy
+int ensure_noise_ring(mrt_ctx* c) {
+    if (!c->d_noise_sums) HIP_TRY(c, hipMalloc((void**)&c->d_noise_sums, kNoiseRing * sizeof(mrt::NoiseSums)));
+    if (!c->h_noise_sums) HIP_TRY(c, hipHostMalloc((void**)&c->h_noise_sums, kNoiseRing * sizeof(mrt::NoiseSums), hipHostMallocDefault));
+    for (auto& E : c->noise_ring)
+        if (!E.copied) HIP_TRY(c, hipEventCreateWithFlags(&E.copied, hipEventDisableTiming));
+    return MRT_OK;
+}
+
+// the report of the sums and what the host knew at query time; K = +inf is "no estimate yet" (every derived figure +inf,
+// without forming 0 * inf).  per_tile: reduced with K per tile (adaptive sampling), whose sum_s is sum_var already.
+void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s, bool per_tile = false) {
+    r->pixels = s.pixels; r->non_finite = s.non_finite; r->above = s.above;
+    r->sum_lum = s.sum_l;
+    if (std::isinf(r->noise_factor)) {
+        r->sum_var = r->rmse = r->rel_rmse = INFINITY;
+        r->max_se = INFINITY;
+        return;
+    }
+    r->sum_var = per_tile ? s.sum_s : s.sum_s * r->noise_factor;
+    r->max_se = s.max_se;
+    r->rmse = s.pixels ? std::sqrt(r->sum_var / (double)s.pixels) : 0.0;
+    r->rel_rmse = r->rmse > 0.0 ? r->rmse / (s.sum_l / (double)s.pixels) : 0.0;
+}
+
+bool noise_args_ok(float threshold, float floor_) { return std::isfinite(threshold) && std::isfinite(floor_) && floor_ >= 0.0f; }
+
+// Adaptive sampling: K(n) = mrt_noise_factor(n, max_w) for n < len on the device (as float and as double), grown by doubling.
+// The host table continues the c2 recursion of mrt_noise_factor; a larger device table replaces the old one after the ctx's
+// stream -- the only one whose reductions read it -- has drained (a handful of times per accumulation).
+int ensure_k_table(mrt_ctx* c, uint32_t len) {
+    if (len <= c->k_len) return MRT_OK;
+    uint32_t cap = std::max<uint32_t>(c->k_len ? c->k_len : 4096u, 4096u);
+    while (cap < len) cap = cap > 0x7FFFFFFFu ? 0xFFFFFFFFu : 2u * cap;
+    const float max_w = c->args.max_framebuffer_weight;
+    while (c->k_table.size() < cap) {
+        c->k_table.push_back(mrt::noise_factor_of(c->k_c2));     // K after k_table.size() frames
+        c->k_c2 = mrt::noise_c2_next(c->k_c2, mrt_frame_weight((uint32_t)(c->k_table.size() - 1), max_w));
+    }
+    std::vector<float> kf(c->k_table.begin(), c->k_table.end());
+    MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_noise_query: growing the K table"));
+    mrt::free_device(c->d_k_f32, c->d_k_f64);
+    c->k_len = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f32, (size_t)cap * sizeof(float)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f64, (size_t)cap * sizeof(double)));
+    HIP_TRY(c, hipMemcpy(c->d_k_f32, kf.data(), (size_t)cap * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_k_f64, c->k_table.data(), (size_t)cap * sizeof(double), hipMemcpyHostToDevice));
+    c->k_len = cap;
+    return MRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+double mrt_noise_factor(uint32_t frames_done, float max_w) {
+    double c2 = 1.0;
+    for (uint32_t k = 0; k < frames_done; k++) {
+        const float w = mrt_frame_weight(k, max_w);
+        const double next = mrt::noise_c2_next(c2, w);
+        // a saturated weight stays saturated (mrt_frame_weight is non-decreasing up to there): c2 is at its fixed point
+        if (k != 0 && w == max_w && max_w < 0.99999988f && next == c2) break;
+        c2 = next;
+    }
+    return mrt::noise_factor_of(c2);
+}
+
+int mrt_set_noise_tracking(mrt_ctx* c, int enabled) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (c->frames_done != 0) return fail(c, MRT_ERR_STATE, "mrt_set_noise_tracking: frames already rendered; call mrt_reset first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((enabled != 0) == c->noise_on) return MRT_OK;
+    MRT_TRY(mrt::wait_all(c, __func__));
+    if (enabled) {
+        MRT_TRY(ensure_noise_ring(c));
+        MRT_TRY(alloc_noise_buffers(c));
+        c->noise_on = true;
+    } else {
+        free_noise_buffers(c);
+        c->noise_on = false;
+        c->noise_first = c->noise_seq + 1;
+    }
+    return MRT_OK;
+}
+
+int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_noise_query: noise tracking is off (mrt_set_noise_tracking)");
+    if (!noise_args_ok(threshold, floor_))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t seq = c->noise_seq + 1;
+    const uint32_t i = (uint32_t)(seq % kNoiseRing);
+    NoiseEntry& E = c->noise_ring[i];
+    if (seq > kNoiseRing) {           // the ring is full when the entry's previous report is still in flight
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_noise_query: the ring is full (report %llu)", (unsigned long long)(seq - kNoiseRing));
+        MRT_TRY(mrt::wait_event(c, E.copied, what));
+    }
+    float* map = c->d_noise_tiles + (size_t)i * mrt::tiles_min1(c);
+    double K = mrt::noise_factor_of(c->noise_c2);
+    int e = 0;
+    if (!c->tiles_diverged) {
+        e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                     c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials, map,
+                                     c->d_noise_sums + i, c->stream);
+    } else {                        // adaptive sampling: K per tile; the report's K is the largest (the least-sampled tile's)
+        uint32_t most = 0;
+        for (uint32_t t : c->tile_frames) most = std::max(most, t);
+        MRT_TRY(ensure_k_table(c, most + 1u));
+        K = 0.0;
+        for (uint32_t t : c->tile_frames) K = std::max(K, c->k_table[t]);
+        e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                           c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials, map,
+                                           c->d_noise_sums + i, c->stream);
+    }
+    if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(c, hipMemcpyAsync(c->h_noise_sums + i, c->d_noise_sums + i, sizeof(mrt::NoiseSums), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipEventRecord(E.copied, c->stream));
+    E.report = mrt_noise_report{};
+    E.report.seq = seq;
+    E.report.frames_done = c->frames_done;
+    E.report.threshold = threshold; E.report.floor = floor_;
+    E.report.noise_factor = K;
+    E.per_tile = c->tiles_diverged;
+    c->noise_seq = seq;
+    return MRT_OK;
+}
+
+int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = mrt_noise_report{};
+    if (c->noise_seq < c->noise_first) return MRT_OK;                 // nothing queued (since the last reset)
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (wait) {
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_noise_result: report %llu", (unsigned long long)c->noise_seq);
+        MRT_TRY(mrt::wait_event(c, c->noise_ring[c->noise_seq % kNoiseRing].copied, what));
+    }
+    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    for (uint64_t seq = c->noise_seq; seq >= oldest; seq--) {        // the newest whose copy has landed (stream order)
+        const uint32_t i = (uint32_t)(seq % kNoiseRing);
+        const hipError_t q = hipEventQuery(c->noise_ring[i].copied);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+        if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_noise_result: %s", hipGetErrorString(q));
+        *out = c->noise_ring[i].report;
+        noise_fill(out, c->h_noise_sums[i], c->noise_ring[i].per_tile);
+        return MRT_OK;
+    }
+    return MRT_OK;
+}
+
+int mrt_read_noise(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_read_noise: noise tracking is off (mrt_set_noise_tracking)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return mrt::read_rows(c, __func__, c->d_noise_s, out, cap, sizeof(float));
+}
+
+int mrt_read_noise_tiles(mrt_ctx* c, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (tiles_x) *tiles_x = c->tiles_x;
+    if (tiles_rows) *tiles_rows = c->local_bands;
+    if (!c->noise_on || c->noise_seq < c->noise_first)
+        return fail(c, MRT_ERR_STATE, "mrt_read_noise_tiles: no noise query since tracking was enabled or the last reset");
+    if (!out) return MRT_ERR_INVALID_ARG;
+    const size_t n = c->n_tiles;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_noise_tiles: need %zu floats", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
+    // behind the latest query only: its copy's event, then the tile map on a stream of its own
+    HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[c->noise_seq % kNoiseRing].copied, 0));
+    const float* map = c->d_noise_tiles + (size_t)(c->noise_seq % kNoiseRing) * n;
+    if (n) HIP_TRY(c, hipMemcpyAsync(out, map, n * sizeof(float), hipMemcpyDeviceToHost, c->noise_stream));
+    return mrt::wait_stream(c, c->noise_stream, __func__);
+}
+
+// Adaptive sampling's selection: the tiles whose entry in report `report_seq`'s tile map is > its threshold (the tiles holding a
+// pixel counted in its `above`), from that report's own map (one per ring entry), then mrt_render_tiles.  Waits for that query only.
+int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64_t* used_seq, uint32_t* tiles_selected) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (used_seq) *used_seq = 0;
+    if (tiles_selected) *tiles_selected = 0;
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: noise tracking is off (mrt_set_noise_tracking)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    uint64_t seq = 0;
+    if (report_seq == 0) {                      // the newest finished report, without waiting; none: every tile
+        for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
+            const hipError_t q = hipEventQuery(c->noise_ring[k % kNoiseRing].copied);
+            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+            if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_render_adaptive: %s", hipGetErrorString(q));
+            seq = k;
+            break;
+        }
+    } else {
+        if (report_seq > c->noise_seq || report_seq < oldest)
+            return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: report %llu is not among the reports held (%llu .. %llu)",
+                        (unsigned long long)report_seq, (unsigned long long)oldest, (unsigned long long)c->noise_seq);
+        char what[96];
+        std::snprintf(what, sizeof what, "mrt_render_adaptive: report %llu", (unsigned long long)report_seq);
+        MRT_TRY(mrt::wait_event(c, c->noise_ring[report_seq % kNoiseRing].copied, what));
+        seq = report_seq;
+    }
+    const uint32_t nt = c->n_tiles;
+    c->selection.clear();
+    if (seq == 0) {
+        for (uint32_t t = 0; t < nt; t++) c->selection.push_back(t);
+    } else {
+        // the map was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
+        if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
+        c->h_select_map.resize(nt);
+        HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[seq % kNoiseRing].copied, 0));
+        HIP_TRY(c, hipMemcpyAsync(c->h_select_map.data(), c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float),
+                                  hipMemcpyDeviceToHost, c->noise_stream));
+        MRT_TRY(mrt::wait_stream(c, c->noise_stream, __func__));
+        const float threshold = c->noise_ring[seq % kNoiseRing].report.threshold;
+        for (uint32_t t = 0; t < nt; t++)
+            if (c->h_select_map[t] > threshold) c->selection.push_back(t);
+    }
+    if (used_seq) *used_seq = seq;
+    if (tiles_selected) *tiles_selected = (uint32_t)c->selection.size();
+    if (c->selection.empty()) return MRT_OK;              // converged at that threshold: nothing to render
+    return mrt_render_tiles(c, c->selection.data(), c->selection.size(), frames);
+}
+
+int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,
+                           float threshold, float floor_, mrt_noise_report* out, float* tiles_out) {
+    if (!c || !S || !rgba || !out || !width || !rows || (uint64_t)width * rows > (1ull << 28) || !noise_args_ok(threshold, floor_) ||
+        std::isnan(K) || K < 0.0)
+        return MRT_ERR_INVALID_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * rows;
+    const uint32_t bands = (rows + mrt::kBandRows - 1) / mrt::kBandRows, tx = (width + mrt::kTileW - 1) / mrt::kTileW;
+    const size_t tiles = (size_t)bands * tx;
+    float *d_s = nullptr, *d_rgba = nullptr, *d_tiles = nullptr;
+    void* d_part = nullptr;
+    mrt::NoiseSums* d_sums = nullptr;
+    mrt::NoiseSums h{};
+    hipError_t e = hipMalloc((void**)&d_s, n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_rgba, n * 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_tiles, tiles * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&d_part, mrt::noise_partials_bytes(width, bands));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, sizeof h);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = (hipError_t)mrt::launch_noise_reduce(d_s, d_rgba, width, bands, rows, 0, 1, (float)K, threshold, floor_, d_part, d_tiles,
+                                                 d_sums, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_sums, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && tiles_out) e = hipMemcpyAsync(tiles_out, d_tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    int ws = MRT_OK;
+    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_noise_reduce");
+    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
+    mrt::free_device(d_s, d_rgba, d_tiles, d_part, d_sums);
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_noise_reduce failed: %s", hipGetErrorString(e));
+    *out = mrt_noise_report{};
+    out->threshold = threshold; out->floor = floor_;
+    out->noise_factor = K;
+    noise_fill(out, h);
+    return MRT_OK;
+}
+
+}  // extern "C"

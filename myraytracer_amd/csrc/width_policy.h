@@ -1,4 +1,4 @@
-// The launch-width controller's POLICY, free of HIP and of the clock: what api.cpp's frame loop (redraw_frames) decides
+// The launch-width controller's POLICY, free of HIP and of the clock: what frames.cpp's frame loop (redraw_frames) decides
 // with, and what tests/test_width_policy.py drives with synthetic measurement windows on the CPU (through
 // mrt_debug_width_policy, include/myraytracer_amd_debug.h).  Scheduling only -- no decision here can change an image.
 //

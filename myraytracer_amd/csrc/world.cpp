@@ -1,0 +1,342 @@
+// The scene: mrt_set_world_raw / mrt_set_world (validation, the hierarchy of hierarchy.cpp, the uploads), the scene's part of
+// the kernel arguments, and the scene-related diagnostics.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "mrt_ctx.h"
+#include "hierarchy.h"
+
+using mrt::fail, mrt::free_world, mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::boxes_top_down, mrt::pack_boxes, mrt::kMfmaSlack, mrt::fill_scene_params;
+
+namespace {
+
+bool finite_in_range(float v, float lim) { return std::isfinite(v) && std::fabs(v) <= lim; }
+
+// matrix-core sweep or SGPR-fed VALU sweep for the next launch: forced by mrt_debug_set_sweep,
+// else the scene's verdict (mrt_set_world_raw) and the same test on the camera's distance from the origin
+bool use_matrix_core_sweep(const mrt_ctx* c) {
+    if (c->sweep_mode == 2) return true;
+    if (c->sweep_mode == 1 || !c->mfma_scene_ok) return false;
+    double o2 = 0.0;                              // squared distance of the camera from the GEMMs' origin
+    for (int k = 0; k < 3; k++) {
+        const double d = (c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k];
+        o2 += d * d;
+    }
+    return kMfmaSlack * o2 <= 0.1 * c->mfma_r2_ref;
+}
+
+}  // namespace
+
+namespace mrt {
+
+// the scene / hierarchy / sweep-variant part of the kernel arguments (everything that does not depend on the frame)
+void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
+    p.world = c->world;
+    p.cam = c->cam_raw;
+    p.n_spheres = c->n_spheres;
+    p.n_padded = c->n_padded;
+    { const uint32_t ch = (c->n_padded + mrt::kChunk - 1) / mrt::kChunk; p.mask_chunks = ch < 16u ? ch : 16u; }
+    {
+        p.use_mfma = use_matrix_core_sweep(c) ? 1u : 0u;
+        for (int k = 0; k < 3; k++) p.mfma_origin[k] = c->mfma_origin[k];
+        // The sweep squares K oc.ds through an instruction that saturates at 1 (kernels.hip, mfma_sweep_tile), K a power of
+        // two: rays start on the camera's lens or on a sphere, i.e. within `all` of mfma_origin; the sweep admits origins up
+        // to 4 x that (others take the literal loop), records lie within `all`, |ds| < 1.001: |K oc.ds| < 5.01 all K <= 1/2.
+        double cam_d2 = 0.0, lens = 0.0;
+        for (int k = 0; k < 3; k++) {
+            const double d = (c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k];
+            cam_d2 += d * d;
+        }
+        if (c->cam_raw.mode) {
+            double u2 = 0.0, v2 = 0.0;
+            for (int k = 0; k < 3; k++) { u2 += (double)c->cam_raw.ru[k] * c->cam_raw.ru[k]; v2 += (double)c->cam_raw.rv[k] * c->cam_raw.rv[k]; }
+            lens = std::sqrt(u2) + std::sqrt(v2);
+        }
+        mfma_scales(std::max(c->mfma_reach, std::sqrt(cam_d2) + lens), p.mfma_scale, &p.mfma_neg_k2_pair);
+    }
+    p.levels = c->levels; p.n_nodes = c->n_nodes; p.n_members = c->n_members;
+    // small scenes: the top queue holds a ray's candidates among ALL top records; large scenes: the wave's one work stack
+    p.box_lds_count = c->n_members <= 1024u ? 0u : mrt::large_scene_box_lds_count(c->n_padded, c->levels, p.mask_chunks, mrt::kBoxLdsCap);
+    p.gen_cap = c->n_members <= 1024u ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) p.level_base[k] = c->level_base[k];
+    // large scenes only (kernels.hip: !SMALL): every node's box, in the kernel's top-down numbering
+    p.boxes = c->boxes_mode == 0 ? c->d_boxes_open : c->d_boxes;
+    p.box_cluster_first = c->box_cluster_first; p.box_cluster_parent_first = c->box_cluster_parent_first;
+    p.box_quad = c->box_quad ? 1u : 0u;
+    p.box_kc = c->box_kc;
+    p.n_direct = c->n_direct; p.direct_first = c->direct_first;
+    for (uint32_t k = 0; k < mrt::kMaxDirect; k++) { p.direct[k] = c->direct[k]; p.direct_index[k] = c->direct_index[k]; }
+    p.cus = c->cus;
+    p.spheres = c->d_spheres; p.clusters = c->d_clusters; p.nodes = c->d_nodes; p.top_mfma = c->d_top_mfma; p.member_index = c->d_member_index; p.vec4_data = c->d_vec4; p.shade = c->d_shade; p.f32_data = c->d_f32; p.i32_data = c->d_i32;
+}
+
+}  // namespace mrt
+
+extern "C" {
+
+int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const float* vec4, size_t n_vec4,
+                      const float* f32, size_t n_f32, const int32_t* i32, size_t n_i32) {
+    if (!c || !world) return MRT_ERR_INVALID_ARG;
+    const auto t_begin = std::chrono::steady_clock::now();
+    // 64 bytes = the reference's raw::World (lib.rs:676-684) as it is; 80 = with the DielectricRange extension.
+    // Only world_bytes bytes of the caller's struct are read; a 64-byte World has no dielectrics.
+    if (world_bytes != MRT_WORLD_BYTES_REFERENCE && world_bytes != sizeof(mrt_world))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_world_raw: world_bytes %zu is neither %d (raw::World) nor %zu (mrt_world)",
+                    world_bytes, MRT_WORLD_BYTES_REFERENCE, sizeof(mrt_world));
+    mrt_world w_copy;
+    std::memset(&w_copy, 0, sizeof w_copy);
+    std::memcpy(&w_copy, world, world_bytes);
+    const mrt_world* const w = &w_copy;
+    if ((n_vec4 && !vec4) || (n_f32 && !f32) || (n_i32 && !i32)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_world_raw: null array");
+    const int64_t n = w->spheres.length;
+    if (n < 0 || n > (int64_t)mrt::kMaxSpheres) return fail(c, MRT_ERR_BAD_SCENE, "spheres.length %lld out of range [0, %u]", (long long)n, mrt::kMaxSpheres);
+    auto in_range = [](int64_t base, int64_t len, size_t cap) { return base >= 0 && len >= 0 && (uint64_t)(base + len) <= cap; };
+    if (!in_range(w->spheres.center_base_idx, n, n_vec4) || !in_range(w->spheres.radius_base_idx, n, n_f32) ||
+        !in_range(w->spheres.material_ty_base_idx, n, n_i32) || !in_range(w->spheres.material_idx_base_idx, n, n_i32) ||
+        !in_range(w->lambertians.albedo_base_idx, w->lambertians.length, n_vec4) ||
+        !in_range(w->metals.albedo_base_idx, w->metals.length, n_vec4) ||
+        !in_range(w->metals.fuzz_base_idx, w->metals.length, n_f32) ||
+        !in_range(w->dielectrics.ior_base_idx, w->dielectrics.length, n_f32))
+        return fail(c, MRT_ERR_BAD_SCENE, "a World range points outside its data array");
+    // geometry must be finite and moderate so that no discriminant can overflow to inf/NaN
+    const float kLim = 1.0e7f;
+    for (int64_t i = 0; i < n; i++) {
+        const float* ctr = vec4 + 4 * (w->spheres.center_base_idx + i);
+        const float r = f32[w->spheres.radius_base_idx + i];
+        if (!finite_in_range(ctr[0], kLim) || !finite_in_range(ctr[1], kLim) || !finite_in_range(ctr[2], kLim) ||
+            !finite_in_range(r, kLim))
+            return fail(c, MRT_ERR_BAD_SCENE, "sphere %lld: centre/radius not finite or |v| > 1e7", (long long)i);
+        const int32_t ty = i32[w->spheres.material_ty_base_idx + i];
+        const int32_t mi = i32[w->spheres.material_idx_base_idx + i];
+        const int32_t len = ty == MRT_LAMBERTIAN ? w->lambertians.length : ty == MRT_METAL ? w->metals.length
+                          : ty == MRT_DIELECTRIC ? w->dielectrics.length : INT32_MAX;   // unknown ty: absorbs, idx unused
+        if (mi < 0 || (ty >= MRT_LAMBERTIAN && ty <= MRT_DIELECTRIC && mi >= len))
+            return fail(c, MRT_ERR_BAD_SCENE, "sphere %lld: material index %d out of range for type %d", (long long)i, mi, ty);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, __func__));
+    free_world(c);
+
+    // exact-test records, in the reference's sphere order
+    std::vector<mrt::SphereRec> recs((size_t)n ? (size_t)n : 1);
+    for (int64_t i = 0; i < n; i++) {
+        const float* ctr = vec4 + 4 * (w->spheres.center_base_idx + i);
+        const float r = f32[w->spheres.radius_base_idx + i];
+        recs[(size_t)i] = mrt::SphereRec{ctr[0], ctr[1], ctr[2], -(r * r)};
+    }
+    // bounding-sphere hierarchy over spatially close spheres; the sweep tests its top level
+    Hierarchy hier;
+    build_hierarchy(vec4 + 4 * w->spheres.center_base_idx, f32 + w->spheres.radius_base_idx, (uint32_t)n,
+                    c->cluster_factor, c->max_levels, c->top_target, hier);
+    const uint32_t n_padded = (uint32_t)hier.top.size();
+    auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+        hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
+        if (e != hipSuccess || !bytes) return e;
+        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    };
+    HIP_TRY(c, upload((void**)&c->d_spheres, recs.data(), recs.size() * sizeof(mrt::SphereRec)));
+    HIP_TRY(c, upload((void**)&c->d_clusters, hier.top.data(), hier.top.size() * sizeof(mrt::SphereRec)));
+    HIP_TRY(c, upload((void**)&c->d_nodes, hier.nodes.data(), hier.nodes.size() * sizeof(mrt::SphereRec)));
+    if (hier.n_members > 1024u) {           // large scenes (the kernel's !SMALL layouts) walk the boxes
+        std::vector<mrt::BoxFull> full;
+        std::vector<mrt::BoxRec> dev;
+        boxes_top_down(hier, false, full, &c->box_cluster_first, &c->box_cluster_parent_first);
+        pack_boxes(full, dev);
+        HIP_TRY(c, upload((void**)&c->d_boxes, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
+        boxes_top_down(hier, true, full, &c->box_cluster_first, &c->box_cluster_parent_first);
+        pack_boxes(full, dev);
+        HIP_TRY(c, upload((void**)&c->d_boxes_open, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
+    }
+    c->box_quad = hier.box_quad;
+    c->box_kc = hier.box_kc;
+    {
+        std::vector<uint16_t> top_mfma;
+        double max_c2 = 0.0, med_r2 = 0.0;
+        size_t n_real = 0;
+        build_top_mfma(hier.top, top_mfma, c->mfma_origin, &max_c2, &med_r2, &n_real);
+        HIP_TRY(c, upload((void**)&c->d_top_mfma, top_mfma.data(), top_mfma.size() * sizeof(uint16_t)));
+        // The matrix-core sweep inflates R^2 by 2^-13 (o.o + C.C + R^2), o and C relative to mfma_origin; rays
+        // start in or around the scene.
+        // Selected where that stays below about a tenth of the typical R^2 (mrt_redraw checks the camera's
+        // own distance the same way) and there are enough records to fill most of a 32-record tile.
+        c->mfma_r2_ref = med_r2;
+        c->mfma_reach = 0.0;
+        for (int64_t i = 0; i < n; i++) {
+            const float* ctr = vec4 + 4 * (w->spheres.center_base_idx + i);
+            double d2 = 0.0;
+            for (int k = 0; k < 3; k++) { const double d = (double)ctr[k] - (double)c->mfma_origin[k]; d2 += d * d; }
+            c->mfma_reach = std::max(c->mfma_reach, std::sqrt(d2) + std::fabs((double)f32[w->spheres.radius_base_idx + i]));
+        }
+        c->mfma_scene_ok = n_real >= 24 && med_r2 > 0.0 && kMfmaSlack * 2.0 * max_c2 <= 0.1 * med_r2;
+    }
+    HIP_TRY(c, upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
+    // what shading a hit on sphere i reads, gathered per sphere (bit copies of the SoA entries)
+    std::vector<float> shade(8 * ((size_t)n ? (size_t)n : 1), 0.0f);
+    for (int64_t i = 0; i < n; i++) {
+        const float* ctr = vec4 + 4 * (w->spheres.center_base_idx + i);
+        float* sh = shade.data() + 8 * (size_t)i;
+        sh[0] = ctr[0]; sh[1] = ctr[1]; sh[2] = ctr[2];
+        sh[3] = f32[w->spheres.radius_base_idx + i];
+        const int32_t ty = i32[w->spheres.material_ty_base_idx + i];
+        const int32_t mi = i32[w->spheres.material_idx_base_idx + i];
+        sh[4] = sh[5] = sh[6] = 1.0f; sh[7] = 0.0f;
+        if (ty == MRT_LAMBERTIAN) {
+            std::memcpy(sh + 4, vec4 + 4 * (w->lambertians.albedo_base_idx + mi), 3 * sizeof(float));
+        } else if (ty == MRT_METAL) {
+            std::memcpy(sh + 4, vec4 + 4 * (w->metals.albedo_base_idx + mi), 3 * sizeof(float));
+            sh[7] = f32[w->metals.fuzz_base_idx + mi];
+        } else if (ty == MRT_DIELECTRIC) {
+            // A Dielectric attenuates by (1,1,1) (a constant in the kernel), so its colour slots carry what its
+            // scatter derives from the sphere alone, evaluated here with the same f32 operations in the same order
+            // (correctly rounded '/', no contraction): ri = 1/ior for a front-face hit, and the Schlick r0 =
+            // ((1-ri)/(1+ri))^2 for either face.  Bit-identical to evaluating them per hit.
+            const float ior = f32[w->dielectrics.ior_base_idx + mi];
+            auto schlick_r0 = [](float ri) { float r0 = (1.0f - ri) / (1.0f + ri); return r0 * r0; };
+            const float inv_ior = 1.0f / ior;
+            sh[4] = inv_ior; sh[5] = schlick_r0(inv_ior); sh[6] = schlick_r0(ior);
+            sh[7] = ior;
+        }
+    }
+    HIP_TRY(c, upload((void**)&c->d_shade, shade.data(), shade.size() * sizeof(float)));
+    HIP_TRY(c, upload((void**)&c->d_vec4, vec4, n_vec4 * 4 * sizeof(float)));
+    HIP_TRY(c, upload((void**)&c->d_f32, f32, n_f32 * sizeof(float)));
+    HIP_TRY(c, upload((void**)&c->d_i32, i32, n_i32 * sizeof(int32_t)));
+    for (auto& S : c->slot) S.cost_valid = false;
+    c->width.div = 0;                   // (the launch-width controller starts over with the new workload)
+    c->inputs_dirty = true;
+    c->world = *w;
+    c->n_spheres = (uint32_t)n;
+    c->n_padded = n_padded;
+    c->levels = hier.levels; c->n_nodes = (uint32_t)hier.nodes.size(); c->n_members = hier.n_members;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) c->level_base[k] = hier.level_base[k];
+    c->n_direct = hier.n_direct; c->direct_first = hier.direct_first;
+    for (uint32_t k = 0; k < mrt::kMaxDirect; k++) { c->direct[k] = hier.direct[k]; c->direct_index[k] = hier.direct_index[k]; }
+    c->have_world = true;
+    c->set_world_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return MRT_OK;
+}
+
+int mrt_debug_last_set_world_ms(mrt_ctx* c, float* ms) {
+    if (!c || !ms) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_last_set_world_ms: no scene");
+    *ms = c->set_world_ms;
+    return MRT_OK;
+}
+
+int mrt_set_world(mrt_ctx* c, const mrt_sphere* spheres, size_t n) {
+    if (!c || (!spheres && n)) return MRT_ERR_INVALID_ARG;
+    std::vector<float> vec4(8 * n + 4), f32(2 * n + 1);
+    std::vector<int32_t> i32(2 * n + 1);
+    mrt_world w;
+    size_t nv = 0, nf = 0, ni = 0;
+    int st = mrt_pack_world(spheres, n, &w, vec4.data(), 2 * n + 1, &nv, f32.data(), 2 * n + 1, &nf, i32.data(), 2 * n + 1, &ni);
+    if (st != MRT_OK) return fail(c, st, "mrt_set_world: packing failed (%s)", mrt_status_string(st));
+    return mrt_set_world_raw(c, &w, sizeof w, vec4.data(), nv, f32.data(), nf, i32.data(), ni);
+}
+
+// diagnostic / tuning: cluster growth factor used by the NEXT mrt_set_world* call
+int mrt_debug_set_cluster_factor(mrt_ctx* c, float factor) {
+    if (!c || !(factor >= 0.0f)) return MRT_ERR_INVALID_ARG;
+    c->cluster_factor = factor;
+    return MRT_OK;
+}
+
+int mrt_debug_set_sweep(mrt_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MRT_ERR_INVALID_ARG;
+    c->sweep_mode = mode;
+    return MRT_OK;
+}
+
+int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_out, uint32_t* cand_out, size_t cand_words) {
+    if (!c || !rays || !hit_out || n == 0) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_world_hit: no scene");
+    const size_t need_words = ((size_t)c->n_spheres + 31) / 32;
+    if (cand_out && cand_words < need_words) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_world_hit: need %zu bitmap words per ray", need_words);
+    if (n > (1u << 26)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_world_hit: too many rays");
+    for (size_t i = 0; i < 6 * n; i++)
+        if (!(std::fabs(rays[i]) <= 2.0e7f)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_world_hit: ray %zu is not finite or beyond 2e7", i / 6);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, __func__));
+    // rays become the texels of an 8-pixel-wide virtual image (one 8x8 tile per 64 rays), padded with copies of ray 0
+    const size_t n_pad = (n + 63) / 64 * 64;
+    const size_t words = need_words ? need_words : 1;
+    std::vector<float> host_rays(6 * n_pad);
+    std::memcpy(host_rays.data(), rays, 6 * n * sizeof(float));
+    for (size_t i = n; i < n_pad; i++) std::memcpy(host_rays.data() + 6 * i, rays, 6 * sizeof(float));
+    float* d_rays = nullptr; int32_t* d_hit = nullptr; uint32_t* d_cand = nullptr; uint32_t* d_queue = nullptr;
+    auto cleanup = [&]() { (void)hipFree(d_rays); (void)hipFree(d_hit); (void)hipFree(d_cand); (void)hipFree(d_queue); };
+    hipError_t e = hipMalloc((void**)&d_rays, host_rays.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_hit, n_pad * 2 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_cand, n_pad * words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_queue, 64);
+    if (e == hipSuccess) e = hipMemcpy(d_rays, host_rays.data(), host_rays.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_cand, 0, n_pad * words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(d_hit, 0xFF, n_pad * 2 * sizeof(int32_t));
+    if (e != hipSuccess) { cleanup(); return fail(c, MRT_ERR_HIP, "mrt_debug_world_hit: %s", hipGetErrorString(e)); }
+    mrt::KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.locals = c->locals;
+    p.locals.shape[0] = 8; p.locals.shape[1] = (uint32_t)(n_pad / 8);
+    p.locals.samples_per_frame = 1; p.locals.ray_depth = 1;
+    fill_scene_params(c, p);
+    p.shard_rank = 0; p.shard_world = 1;
+    p.tiles_x = 1; p.n_tiles = (uint32_t)(n_pad / 64);
+    p.tile_queue = d_queue;
+    p.n_blocks = 1; p.pix_stride = 0; p.queue_layers = 1; p.lane_frames = 1;
+    p.dbg_rays = d_rays; p.dbg_hit = d_hit; p.dbg_cand = d_cand; p.dbg_words = (uint32_t)words;
+    int le = mrt::launch_debug_world_hit(p, c->n_waves, c->stream);
+    int ws = MRT_OK;
+    if (le == 0) ws = mrt::wait_stream(c, c->stream, "mrt_debug_world_hit");
+    if (ws != MRT_OK) { cleanup(); return ws; }
+    if (le != 0 || e != hipSuccess) { cleanup(); return fail(c, MRT_ERR_HIP, "mrt_debug_world_hit: launch failed: %s", hipGetErrorString(le ? (hipError_t)le : e)); }
+    std::vector<int32_t> hits(n_pad * 2);
+    e = hipMemcpy(hits.data(), d_hit, hits.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) std::memcpy(hit_out, hits.data(), n * 2 * sizeof(int32_t));
+    if (e == hipSuccess && cand_out) {
+        std::vector<uint32_t> cand(n_pad * words);
+        e = hipMemcpy(cand.data(), d_cand, cand.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            for (size_t i = 0; i < n; i++) {
+                std::memset(cand_out + i * cand_words, 0, cand_words * sizeof(uint32_t));
+                std::memcpy(cand_out + i * cand_words, cand.data() + i * words, need_words * sizeof(uint32_t));
+            }
+    }
+    cleanup();
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_world_hit: read-back failed: %s", hipGetErrorString(e));
+    return MRT_OK;
+}
+
+int mrt_debug_set_boxes(mrt_ctx* c, int mode) {
+    if (!c || mode < 0 || mode > 2) return MRT_ERR_INVALID_ARG;
+    c->boxes_mode = mode;
+    return MRT_OK;
+}
+
+int mrt_debug_sweep_variant(mrt_ctx* c) {
+    if (!c || !c->have_world) return 0;
+    return use_matrix_core_sweep(c) ? 2 : 1;
+}
+
+int mrt_debug_set_hierarchy(mrt_ctx* c, uint32_t max_levels, uint32_t top_target) {
+    if (!c || max_levels < 1 || max_levels > mrt::kMaxLevels) return MRT_ERR_INVALID_ARG;      // top_target 0 = automatic
+    c->max_levels = max_levels;
+    c->top_target = top_target;
+    return MRT_OK;
+}
+
+int mrt_debug_lds_layout(uint32_t n_members, uint32_t n_nodes, uint32_t levels, uint32_t n_top_padded, uint32_t out[3]) {
+    if (!out || levels < 1 || levels > mrt::kMaxLevels) return MRT_ERR_INVALID_ARG;
+    mrt::KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.n_members = n_members; p.n_nodes = n_nodes; p.levels = levels; p.n_padded = n_top_padded;
+    { const uint32_t ch = (n_top_padded + mrt::kChunk - 1) / mrt::kChunk; p.mask_chunks = ch < 16u ? ch : 16u; }
+    p.box_lds_count = n_members <= 1024u ? 0u : mrt::large_scene_box_lds_count(n_top_padded, levels, p.mask_chunks, mrt::kBoxLdsCap);
+    p.gen_cap = n_members <= 1024u ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    uint32_t lay[2];
+    mrt::render_lds_layout(p, lay);
+    out[0] = lay[0]; out[1] = lay[1]; out[2] = p.gen_cap;
+    return MRT_OK;
+}
+
+}  // extern "C"

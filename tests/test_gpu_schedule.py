@@ -57,7 +57,7 @@ np.savez(sys.argv[2], seen=np.array(seen), got=got, serial=serial, counters=np.a
 def test_forced_schedule_transitions_mid_accumulation_are_bit_identical(mrt, oracle, tmp_path):
     """12 frames of the cover scene, the schedule changed under the accumulation: full width -> a quarter (4 frames in flight)
     -> an eighth (8, then 16 over-subscribed) -> a half (2) -> twice the frames at a half (4) -> back; every change waits for the frames under way and
-    re-allocates slots (api.cpp, set_frame_slots).  The accumulated image must be the one 12 serial frames give, and the oracle's.
+    re-allocates slots (frames.cpp, set_frame_slots).  The accumulated image must be the one 12 serial frames give, and the oracle's.
     Eight and sixteen frames in flight need as many hardware queues: the frames run in a fresh process with the package's own
     GPU_MAX_HW_QUEUES=20, whatever the caller's environment holds (HIP's default of 4 would hold every setting to 4 frames)."""
     out = str(tmp_path / "transitions.npz")

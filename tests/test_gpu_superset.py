@@ -158,7 +158,7 @@ def test_stress_scene_10k(mrt, oracle):
 
 @pytest.mark.parametrize("spread,rmin,rmax,quad", [(2000.0, 0.01, 0.05, False), (30.0, 0.05, 0.3, True)])
 def test_box_slack_forms_large_sparse_and_large_dense_scenes(mrt, oracle, spread, rmin, rmax, quad):
-    """The box test's slack has two forms, chosen per scene (api.cpp build_boxes): quadratic in the origin's distance where
+    """The box test's slack has two forms, chosen per scene (hierarchy.cpp build_boxes): quadratic in the origin's distance where
     the spheres are large against the scene's reach, linear where they are tiny against it (1,500 spheres of radius 0.01 - 0.05
     spread over 2,000 units: a grazing ray's discriminant error there is far more than a radius).  Both through the candidate-set
     test, grazing rays included."""
@@ -178,7 +178,7 @@ def test_box_slack_forms_large_sparse_and_large_dense_scenes(mrt, oracle, spread
 
 def test_origins_beyond_the_sweeps_scaling_take_the_literal_loop(mrt, oracle):
     """The matrix-core sweep scales its operands so that K oc.ds stays below 1/2 for origins within 4 x the scene's reach
-    (api.cpp, fill_scene_params); a caller's ray from farther away must still find the reference's winner (it takes the
+    (world.cpp, fill_scene_params); a caller's ray from farther away must still find the reference's winner (it takes the
     index-ordered loop over all spheres, which records no candidates)."""
     rng = np.random.default_rng(5)
     sc = _random_scene(mrt, rng, 300, ground=False)

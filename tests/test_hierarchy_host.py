@@ -1,5 +1,5 @@
 """Host-side invariants of the bounding-sphere hierarchy and of the matrix-core operand it is re-expressed in
-(api.cpp build_clusters / build_hierarchy / build_top_mfma), checked without a GPU through
+(hierarchy.cpp build_clusters / build_hierarchy / build_top_mfma), checked without a GPU through
 mrt_debug_build_hierarchy.  These are the facts the conservativeness argument of DESIGN.md §4 rests on."""
 import ctypes as C
 
@@ -9,7 +9,7 @@ import pytest
 from myraytracer_amd import _lib
 
 INFLATE = 1.015          # mrt_internal.h kBoundInflate
-SLACK = 2.0 ** -13       # api.cpp kMfmaSlack
+SLACK = 2.0 ** -13       # hierarchy.h kMfmaSlack
 
 
 def build(mrt, sc, max_levels=4, top_target=256):
@@ -218,7 +218,7 @@ def build_boxes(mrt, sc, max_levels=4, top_target=256):
 
 def test_every_box_encloses_the_spheres_under_it_and_its_slack_covers_the_discriminants_rounding(mrt):
     """The walk of large scenes tests the LINE of a ray against the axis-aligned box of the member spheres under a node, grown
-    by K = kc X + kpad (kernels.hip box_may_touch, api.cpp build_boxes).  Host-side facts the conservativeness rests on:
+    by K = kc X + kpad (kernels.hip box_may_touch, hierarchy.cpp build_boxes).  Host-side facts the conservativeness rests on:
     node j of level k covers the members [j 4^k, (j+1) 4^k); its box (f32 centre, extents measured from it) contains every
     member sphere; the boxes of a level line up with the level's records (same count, never-hit where the record is); and for
     ray origins at any distance the slack is at least 1.4143 x how far beyond a member's surface the line of a ray with a
@@ -285,11 +285,11 @@ def test_lds_footprint_keeps_the_residency_the_kernels_are_built_for(mrt):
 
 def test_the_kernels_top_down_numbering_of_the_boxes(mrt):
     """The large-scene walk addresses boxes by ONE rule -- the children of node g are 4 g + n_top .. + 3, whatever g's level
-    (kernels.hip) -- over the array api.cpp's boxes_top_down lays out.  Against the level-ordered boxes of
+    (kernels.hip) -- over the array hierarchy.cpp's boxes_top_down lays out.  Against the level-ordered boxes of
     mrt_debug_build_boxes: every node sits where the rule puts it (top record j at j; child q of the node at level k, index j,
     at 4 g + n_top + q), every other slot is a never-hit box, the cluster level and its parents start where the kernel is
     told, and the opened-wide copy differs only in the extents of real boxes.  The array is what the kernel reads (24 bytes a box:
-    centre + extents, reported here as 8 floats): the extents carry the level-ordered box's kpad (e + kpad, rounded up: api.cpp
+    centre + extents, reported here as 8 floats): the extents carry the level-ordered box's kpad (e + kpad, rounded up: hierarchy.cpp
     pack_boxes), kc is the scene's one value."""
     L = _lib.load()
     for name, sc in scenes(mrt):
