@@ -170,7 +170,10 @@ int mrt_set_wait_timeout(mrt_ctx* ctx, double seconds);
 
 /* Tile sharding for multi-GPU (no reference counterpart): this ctx renders the 8-row
  * bands b with b % world == rank.  Must be called before the first redraw.  Seeds are
- * keyed by global pixel index, so any sharding yields the same image. */
+ * keyed by global pixel index, so any sharding yields the same image.  Only while mrt_frames_done == 0 (after
+ * mrt_create or mrt_reset), else MRT_ERR_STATE.  The buffers are allocated anew for the shard's rows: the seed
+ * texture is filled again from mrt_create's seed (an earlier mrt_set_seeds is lost), presented images and unread
+ * noise reports are discarded; scene, camera, samples per frame, RNG mode and an overridden shuffle stay. */
 int mrt_set_shard(mrt_ctx* ctx, uint32_t rank, uint32_t world);
 /* hipStream_t to launch on (e.g. torch's current stream); NULL = the ctx's own stream. */
 int mrt_set_stream(mrt_ctx* ctx, void* hip_stream);
@@ -204,7 +207,9 @@ int mrt_camera_derive(const mrt_camera* cam, mrt_camera_raw* out);   /* host onl
 /* Replace the seed texture (Rgba32Uint W x H of lib.rs:397-415): seeds = W*H*4 u32,
  * row 0 = bottom.  Optional: mrt_create already fills it from `seed`. */
 int mrt_set_seeds(mrt_ctx* ctx, const uint32_t* seeds, size_t n_u32);
-int mrt_read_seeds(mrt_ctx* ctx, uint32_t* out, size_t cap_u32);    /* this shard's rows, packed */
+/* This shard's packed rows, local_rows (mrt_shard_info: a multiple of 8, also when world == 1) * W * 4 u32; what the rows
+ * >= height hold is unspecified. */
+int mrt_read_seeds(mrt_ctx* ctx, uint32_t* out, size_t cap_u32);
 
 /* ------------------------------------------------------------------ frame loop */
 
@@ -242,12 +247,16 @@ int mrt_set_schedule_hint(mrt_ctx* ctx, uint32_t div, uint32_t mult);
  * of them per frame in flight (two), e.g. 32 frames of 1920x1080 or 8 of 3840x2160; the buffers are kept until mrt_destroy. */
 int mrt_render(mrt_ctx* ctx, uint32_t frames);
 int mrt_sync(mrt_ctx* ctx);
-/* Restart accumulation: zero framebuffers, frame counter 0, weight 0, shuffle [0;4]. */
+/* Restart accumulation: zero framebuffers, frame counter 0, weight 0, shuffle [0;4] (an overridden shuffle is discarded), counters
+ * zero.  Scene, camera, seed texture, samples per frame, RNG mode, shard, noise tracking and the schedule stay; the numbering of
+ * presents and noise reports goes on (presented images and unread reports are discarded). */
 int mrt_reset(mrt_ctx* ctx);
 
 /* Current Locals (what the NEXT redraw will use) */
 int mrt_get_locals(mrt_ctx* ctx, mrt_locals* out);
-/* Override the next frame's rng_shuffle (the reference draws it from thread_rng, lib.rs:305) */
+/* Override the next frame's rng_shuffle (the reference draws it from thread_rng, lib.rs:305): the next frame of any kind -- a
+ * redraw, the first frame of mrt_render(k), a subset frame -- and that one only; the frames after it take
+ * mrt_frame_shuffle(seed, frames_done) as ever.  A refused call does not use it up. */
 int mrt_set_rng_shuffle(mrt_ctx* ctx, const uint32_t shuffle[4]);
 int mrt_set_samples_per_frame(mrt_ctx* ctx, uint32_t spp);
 int mrt_set_rng_mode(mrt_ctx* ctx, uint32_t mode);          /* MRT_RNG_*; takes effect at the next redraw */
@@ -318,7 +327,9 @@ int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
  * mrt_set_shard or mrt_destroy.  MRT_ACQUIRE_NEWEST (a viewer, mailbox): the most recent finished image; older finished ones are
  * skipped (info->dropped).  MRT_ACQUIRE_OLDEST (a capture, FIFO): the oldest; nothing is skipped while the caller keeps at most
  * depth - 1 presents outstanding.  wait == 0: returns MRT_OK with *pixels = NULL when none has finished; wait != 0: polls
- * (bounded) for one that is queued (*pixels = NULL only if none is).  MRT_ERR_STATE before the first present.  info may be
+ * (bounded) for one that is queued (*pixels = NULL only if none is; NEWEST with an older image
+ * finished returns that one at once, it does not wait for a newer one in flight).  MRT_ERR_STATE before the context's first present
+ * (numbering and this rule span mrt_reset: after a reset the call is MRT_OK with *pixels = NULL).  info may be
  * NULL.  Releases the image held before. */
 int mrt_present_acquire(mrt_ctx* ctx, int mode, int wait, const uint8_t** pixels, mrt_present_info* info);
 int mrt_present_release(mrt_ctx* ctx);            /* MRT_ERR_STATE if no image is held */
@@ -360,7 +371,7 @@ typedef struct {                 /* 96 bytes */
     uint32_t reserved2;
 } mrt_noise_report;
 /* Turns noise tracking on (allocates S, zeroed) or off (frees it).  Only while mrt_frames_done == 0 (after mrt_create or
- * mrt_reset), else MRT_ERR_STATE.  Tracking survives mrt_reset (S is zeroed with the framebuffers, unread reports are
+ * mrt_reset), else MRT_ERR_STATE; a call that changes nothing is MRT_OK, one that does discards the unread reports.  Tracking survives mrt_reset (S is zeroed with the framebuffers, unread reports are
  * discarded) and mrt_set_shard (S is reallocated for the new shard's rows, zeroed). */
 int mrt_set_noise_tracking(mrt_ctx* ctx, int enabled);
 /* Queues the noise report of the most recent frame on the ctx's stream, behind that frame's blend -- the reduction and a copy
@@ -399,7 +410,7 @@ double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
  *   Denoising after divergence (mrt_read_denoised, MRT_PRESENT_DENOISED) is refused with MRT_ERR_STATE; presents and read-backs
  *   work unchanged.  Shards (world > 1) are refused with MRT_ERR_STATE. */
 /* Queues `frames` consecutive subset frames over the n tiles of `tiles` (asynchronous, with mrt_render's back-pressure).
- * n == 0: MRT_OK, nothing queued.  An id >= the tile count, a duplicate id or tiles == NULL: MRT_ERR_INVALID_ARG; a shard:
+ * n == 0 or frames == 0: MRT_OK, nothing queued (before any other check).  An id >= the tile count, a duplicate id or tiles == NULL: MRT_ERR_INVALID_ARG; a shard:
  * MRT_ERR_STATE; no scene: MRT_ERR_NO_SCENE; counter-RNG mode with samples_per_frame > MRT_COUNTER_BLOCK: MRT_ERR_INVALID_ARG.
  * A list of every tile renders whole frames: while the accumulation is uniform, exactly mrt_render's. */
 int mrt_render_tiles(mrt_ctx* ctx, const uint32_t* tiles, size_t n, uint32_t frames);

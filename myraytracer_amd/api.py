@@ -351,6 +351,10 @@ class State:
                     "mrt_shard_info")
         return r.value, w.value, rows.value, width.value
 
+    def set_shard(self, rank: int, world: int):
+        """mrt_set_shard: this context renders the 8-row bands b with b % world == rank; only while frames_done == 0."""
+        self._check(self._L.mrt_set_shard(self._ctx, rank, world), "mrt_set_shard")
+
     def framebuffer_device_ptr(self) -> int:
         return int(self._L.mrt_framebuffer_device_ptr(self._ctx) or 0)
 

@@ -47,7 +47,16 @@ class Accum:
         self.S = np.zeros((height, width), np.float32)
         self.n = np.zeros(self.tr * self.tx, np.int64)
         self.frames_done = 0
+        self.diverged = False                      # a subset frame since the last reset: blends and reports are per tile
         self.tile = tile_of(height, width)
+
+    def reset(self):
+        """mrt_reset: framebuffer, S and every n_t zero, the accumulation uniform again."""
+        self.fb[:] = 0
+        self.S[:] = 0
+        self.n[:] = 0
+        self.frames_done = 0
+        self.diverged = False
 
     @property
     def n_tiles(self) -> int:
@@ -56,6 +65,7 @@ class Accum:
     def frame(self, mean: np.ndarray, tiles=None):
         """Blend one frame's mean (H, W, 4) into the listed tiles (None: every tile) at their own weights."""
         listed = np.ones(self.n_tiles, bool) if tiles is None else np.isin(np.arange(self.n_tiles), np.asarray(tiles, np.int64))
+        self.diverged = self.diverged or not listed.all()
         wt = np.array([frame_weight(int(k), self.max_w) for k in self.n], np.float32)
         for t in np.unique(wt[listed]):            # tiles that share a weight share one vectorised blend
             m = listed[self.tile] & (wt[self.tile] == t)

@@ -219,3 +219,34 @@ def centre_rays(width, height, cam_raw=None):
     for k in range(3):
         rays[..., 3 + k] = d[k] / length
     return rays
+
+
+def expected_guides(O, spheres, rays):
+    """orc_world_hit_batch's winners and t, orc_world_hit's normal and material per hit, the albedo from the packed materials."""
+    import ctypes as C
+
+    from common import to_oracle_spheres
+    packed = O.pack_world(to_oracle_spheres(O, spheres))
+    flat = rays.reshape(-1, 6)
+    hit, t, _, _ = O.world_hit_batch(packed, flat)
+    normal = np.zeros((len(flat), 3), np.float32)
+    albedo = np.ones((len(flat), 3), np.float32)
+    w = packed.world
+    L = O.lib()
+    for i in np.nonzero(hit >= 0)[0]:
+        h, which = O.Hit(), C.c_int32()
+        o = (C.c_float * 3)(*flat[i, :3]); d = (C.c_float * 3)(*flat[i, 3:])
+        assert L.orc_world_hit(C.byref(w), packed.vec4.ctypes.data, packed.f32.ctypes.data, packed.i32.ctypes.data, o, d,
+                               0.001, 1.0e4, C.byref(h), C.byref(which)) == 1 and which.value == hit[i]
+        normal[i] = np.array(h.normal[:], np.float32)
+        v4 = packed.vec4.reshape(-1, 4)
+        if h.ty == 1:
+            albedo[i] = v4[w.lambertians.albedo_base_idx + h.idx, :3]
+        elif h.ty == 2:
+            albedo[i] = v4[w.metals.albedo_base_idx + h.idx, :3]
+        elif h.ty != 3:
+            albedo[i] = 0.0
+    miss = hit < 0
+    normal[miss] = -flat[miss, 3:]
+    t = np.where(miss, np.float32(np.inf), t).astype(np.float32)
+    return hit, t, normal, albedo

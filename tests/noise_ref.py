@@ -86,12 +86,32 @@ def report(S: np.ndarray, rgba: np.ndarray, K: float, threshold: float = 0.02, f
     return out
 
 
-def tiles(S: np.ndarray, rgba: np.ndarray, K: float, threshold: float = 0.02, floor: float = 0.01) -> np.ndarray:
-    """Per-8x8-tile maximum of rel over finite pixels (0 for a tile without one; NaN rel ignored)."""
+def tiles(S: np.ndarray, rgba: np.ndarray, K: float, threshold: float = 0.02, floor: float = 0.01, valid=None) -> np.ndarray:
+    """Per-8x8-tile maximum of rel over finite pixels (0 for a tile without one; NaN rel ignored).  valid: a (rows,) mask of the
+    rows that are image rows -- a shard's packed rows end in padding, which the reduction skips (shard_rows)."""
     finite, se, L, rel, above = per_pixel(S, rgba, K, threshold, floor)
     rows, width = S.shape
+    if valid is not None:
+        finite = finite & np.asarray(valid, bool)[:, None]
     v = np.where(finite & ~np.isnan(rel), rel, np.float32(0)).astype(np.float32)
     tr, tx = -(-rows // 8), -(-width // 8)
     pad = np.zeros((tr * 8, tx * 8), np.float32)
     pad[:rows, :width] = v
     return pad.reshape(tr, 8, tx, 8).max(axis=(1, 3))
+
+
+def shard_rows(height: int, rank: int, world: int) -> np.ndarray:
+    """The image row of every packed local row of shard (rank, world) -- local row r is global row ((r / 8) world + rank) 8 + r % 8
+    (mrt_shard_global_row), ceil(ceil(height / 8) / world) bands on every rank -- or -1 where that is >= height (padding)."""
+    bands = -(-(-(-height // 8)) // world)
+    r = np.arange(bands * 8)
+    g = ((r // 8) * world + rank) * 8 + r % 8
+    return np.where(g < height, g, -1)
+
+
+def pack_rows(a: np.ndarray, rank: int, world: int) -> np.ndarray:
+    """A full bottom-up image (H, ...) -> shard (rank, world)'s packed rows, padding rows zero (what the read-backs of a shard give)."""
+    g = shard_rows(a.shape[0], rank, world)
+    out = np.zeros((len(g),) + a.shape[1:], a.dtype)
+    out[g >= 0] = a[g[g >= 0]]
+    return out

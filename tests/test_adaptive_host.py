@@ -122,3 +122,22 @@ def test_adaptive_symbols_are_bound(mrt):
         assert callable(getattr(st, meth))
     import inspect
     assert inspect.signature(st.render_until).parameters["adaptive"].default is False
+
+
+def test_reset_returns_to_the_uniform_state_and_divergence_is_tracked():
+    rng = np.random.default_rng(3)
+    a = adaptive_ref.Accum(19, 21, 0.75)
+    b = adaptive_ref.Accum(19, 21, 0.75)
+    means = [rng.random((19, 21, 4)).astype(np.float32) for _ in range(4)]
+    a.frame(means[0])
+    assert not a.diverged
+    a.frame(means[1], np.arange(a.n_tiles))            # every tile: still uniform
+    assert not a.diverged
+    a.frame(means[2], [0, 4])
+    assert a.diverged
+    a.reset()
+    assert not a.diverged and a.frames_done == 0 and not a.n.any() and not a.fb.any() and not a.S.any()
+    for m in means[:2]:
+        a.frame(m)
+        b.frame(m)
+    assert np.array_equal(a.fb.view(np.uint32), b.fb.view(np.uint32)) and np.array_equal(a.S.view(np.uint32), b.S.view(np.uint32))

@@ -1,13 +1,10 @@
 """The denoiser on the GPU (include/myraytracer_amd.h, "denoiser"): the first-hit guides against the oracle's world_hit and hit
 record, the a-trous filter bit for bit against its float32 restatement (tests/denoise_ref.py), the context's denoise and the
 DENOISED present against that restatement of the same frame, and the quality it buys on a cover scene."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from common import to_oracle_spheres
-from denoise_ref import centre_rays, denoise, random_case
+from denoise_ref import centre_rays, denoise, expected_guides, random_case
 from present_ref import encode_host
 
 pytestmark = pytest.mark.gpu
@@ -35,34 +32,6 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _expected_guides(O, spheres, rays):
-    """orc_world_hit_batch's winners and t, orc_world_hit's normal and material per hit, the albedo from the packed materials."""
-    packed = O.pack_world(to_oracle_spheres(O, spheres))
-    flat = rays.reshape(-1, 6)
-    hit, t, _, _ = O.world_hit_batch(packed, flat)
-    normal = np.zeros((len(flat), 3), np.float32)
-    albedo = np.ones((len(flat), 3), np.float32)
-    w = packed.world
-    L = O.lib()
-    for i in np.nonzero(hit >= 0)[0]:
-        h, which = O.Hit(), C.c_int32()
-        o = (C.c_float * 3)(*flat[i, :3]); d = (C.c_float * 3)(*flat[i, 3:])
-        assert L.orc_world_hit(C.byref(w), packed.vec4.ctypes.data, packed.f32.ctypes.data, packed.i32.ctypes.data, o, d,
-                               0.001, 1.0e4, C.byref(h), C.byref(which)) == 1 and which.value == hit[i]
-        normal[i] = np.array(h.normal[:], np.float32)
-        v4 = packed.vec4.reshape(-1, 4)
-        if h.ty == 1:
-            albedo[i] = v4[w.lambertians.albedo_base_idx + h.idx, :3]
-        elif h.ty == 2:
-            albedo[i] = v4[w.metals.albedo_base_idx + h.idx, :3]
-        elif h.ty != 3:
-            albedo[i] = 0.0
-    miss = hit < 0
-    normal[miss] = -flat[miss, 3:]
-    t = np.where(miss, np.float32(np.inf), t).astype(np.float32)
-    return hit, t, normal, albedo
-
-
 @pytest.mark.parametrize("name,w,h", [("default", 96, 54), ("cover-glass", 96, 54), ("stress", 64, 40)])
 def test_guides_equal_the_oracle(mrt, name, w, h):
     from oracle import pyoracle as O
@@ -71,7 +40,7 @@ def test_guides_equal_the_oracle(mrt, name, w, h):
         g = st.debug_read_guides()
     raw = mrt.camera_derive(cam) if cam is not None else None
     assert np.array_equal(_bits(g["rays"]), _bits(centre_rays(w, h, raw)))
-    hit, t, normal, albedo = _expected_guides(O, spheres, g["rays"])
+    hit, t, normal, albedo = expected_guides(O, spheres, g["rays"])
     assert np.array_equal(g["index"].ravel(), hit)
     assert (hit < 0).any() and (hit >= 0).any()
     assert np.array_equal(_bits(g["t"]).ravel(), _bits(t))

@@ -98,3 +98,29 @@ def test_noise_symbols_are_exported_and_bound(mrt):
     assert C.sizeof(_lib.MrtNoiseReport) == 96 and _lib.MrtNoiseReport.max_se.offset == 88
     for name in ("set_noise_tracking", "noise_query", "noise_result", "read_noise", "read_noise_tiles", "render_until"):
         assert callable(getattr(mrt.State, name))
+
+
+@pytest.mark.parametrize("height,world", [(1, 1), (27, 1), (27, 2), (43, 3), (60, 5), (9, 8)])
+def test_shard_rows_are_mrt_shard_global_row(mrt, height, world):
+    """The packing the shard references use is the library's own index math, and every image row lands in exactly one shard."""
+    seen = []
+    full = np.arange(height * 3, dtype=np.float32).reshape(height, 3)
+    for rank in range(world):
+        g = noise_ref.shard_rows(height, rank, world)
+        assert len(g) == mrt.shard_local_rows(height, world)
+        want = np.array([mrt.shard_global_row(r, rank, world) for r in range(len(g))])
+        assert np.array_equal(g, np.where(want < height, want, -1))
+        seen += g[g >= 0].tolist()
+        packed = noise_ref.pack_rows(full, rank, world)
+        assert np.array_equal(packed[g >= 0], full[g[g >= 0]]) and not packed[g < 0].any()
+    assert sorted(seen) == list(range(height))
+
+
+def test_tile_map_skips_rows_marked_invalid():
+    """K = +inf gives every finite pixel rel = +inf: a padding row must not put that into its tile."""
+    S = np.zeros((16, 10), np.float32)
+    rgba = np.ones((16, 10, 4), np.float32)
+    valid = np.arange(16) < 8
+    assert np.isinf(noise_ref.tiles(S, rgba, math.inf)).all()
+    m = noise_ref.tiles(S, rgba, math.inf, valid=valid)
+    assert np.isinf(m[0]).all() and (m[1] == 0).all()
