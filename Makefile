@@ -6,6 +6,9 @@ CSRC     := myraytracer_amd/csrc
 LIBDIR   := myraytracer_amd/lib
 LIB      := $(LIBDIR)/libmyraytracer_amd.so
 CLI      := $(LIBDIR)/native_runner
+# the failure-injecting build of the same sources (test infrastructure: tests/failinject/, tests/test_gpu_failure_paths.py)
+FI_DIR   := tests/failinject
+FI_LIB   := $(LIBDIR)/libmyraytracer_amd_failinject.so
 # -ffp-contract=off: fma only where the source says fma (MRT-F32 rules).
 # -fno-vectorize -fno-slp-vectorize: v_pk_* fp32 is not faster than scalar VALU on gfx950
 # and SLP packing spends s_mov on SGPR pairs (profiles/r01_ubench_sphere_loop_*.txt).
@@ -19,7 +22,7 @@ ifeq ($(strip $(SRCS)),)
 $(error scripts/source_hash.py --srcs printed no sources)
 endif
 
-all: $(LIB) $(CLI) oracle
+all: $(LIB) $(CLI) $(FI_LIB) oracle
 
 # one object per source (build/ is git-ignored), so that touching the host code does not recompile the kernels
 OBJDIR   := build/obj
@@ -43,6 +46,26 @@ $(OBJDIR)/build_id.cpp: $(SRCS) $(HDRS) Makefile scripts/source_hash.py
 $(LIB): $(OBJS) $(OBJDIR)/isa.ok $(OBJDIR)/build_id.cpp
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(OBJS) $(OBJDIR)/build_id.cpp -ldl
+
+# The failure-injecting library: the host .cpp files compiled once more with tests/failinject/mrt_failinject.h force-included
+# (their resource creators / releasers, copies and memsets go through the shim), the product's kernel objects as they are, and
+# the shim.  Selected at run time by MRT_LIB_OVERRIDE (bench.py refuses a headline from it); never the product.
+FI_OBJDIR := $(OBJDIR)/failinject
+FI_HOST   := $(filter %.cpp,$(SRCS))
+FI_OBJS   := $(patsubst $(CSRC)/%,$(FI_OBJDIR)/%.o,$(FI_HOST))
+KERNEL_OBJS := $(patsubst $(CSRC)/%,$(OBJDIR)/%.o,$(filter-out %.cpp,$(SRCS)))
+
+$(FI_OBJDIR)/%.o: $(CSRC)/% $(HDRS) $(FI_DIR)/mrt_failinject.h
+	@mkdir -p $(FI_OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -include $(FI_DIR)/mrt_failinject.h -x hip -c -o $@ $<
+
+$(FI_OBJDIR)/shim.o: $(FI_DIR)/mrt_failinject.cpp $(FI_DIR)/mrt_failinject.h
+	@mkdir -p $(FI_OBJDIR)
+	$(HIPCC) -O2 -std=c++17 -fPIC -Wall -Wextra -x hip --offload-arch=$(ARCH) -c -o $@ $<
+
+$(FI_LIB): $(FI_OBJS) $(FI_OBJDIR)/shim.o $(KERNEL_OBJS) $(OBJDIR)/isa.ok $(OBJDIR)/build_id.cpp
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -o $@ $(FI_OBJS) $(FI_OBJDIR)/shim.o $(KERNEL_OBJS) $(OBJDIR)/build_id.cpp -ldl
 
 $(CLI): $(CSRC)/native_runner.cpp $(LIB)
 	$(HIPCC) -O2 -std=c++17 -o $@ $(CSRC)/native_runner.cpp -L$(LIBDIR) -lmyraytracer_amd -Wl,-rpath,'$$ORIGIN'

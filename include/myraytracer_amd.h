@@ -47,7 +47,7 @@ typedef enum {
     MRT_OK = 0,
     MRT_ERR_INVALID_ARG = 1,   /* null pointer, zero size, bad enum */
     MRT_ERR_NO_DEVICE = 2,     /* no HIP device / wrong arch: the product never falls back to CPU */
-    MRT_ERR_HIP = 3,           /* a HIP runtime call failed; see mrt_last_error */
+    MRT_ERR_HIP = 3,           /* a HIP runtime call failed; see mrt_last_error, and "after MRT_ERR_HIP" below */
     MRT_ERR_NO_SCENE = 4,      /* redraw before set_world */
     MRT_ERR_BAD_SCENE = 5,     /* index out of range, non-finite or out-of-range geometry */
     MRT_ERR_TOO_SMALL = 6,     /* caller buffer too small */
@@ -56,6 +56,23 @@ typedef enum {
     MRT_ERR_STALLED = 9        /* a wait for the GPU passed its deadline (mrt_set_wait_timeout); mrt_last_error names the wait.
                                   The context stays failed: destroy it (mrt_destroy does not wait for a stalled context) */
 } mrt_status;
+
+/* ---- after MRT_ERR_HIP: what a caller may rely on when the runtime refuses a resource ----
+ * Device memory, pinned memory, streams and events are created by mrt_create and, on demand, by most later calls.  When a
+ * creation is refused (out of memory, out of handles):
+ *   C1  the call returns MRT_ERR_HIP and mrt_last_error(ctx) -- mrt_last_error(NULL) for mrt_create -- names the refused
+ *       runtime call ("hipMalloc(...) failed: ...");
+ *   C2  nothing leaks and nothing is released twice: after mrt_destroy the process holds what it held before mrt_create.  A
+ *       failed mrt_create leaves nothing behind and sets *out = NULL;
+ *   C3  the context stays sound: no call it accepts afterwards touches a buffer, stream or event that is not there.  A call
+ *       that replaces something keeps the old until the new exists (mrt_set_shard: the shard and its buffers are unchanged
+ *       after a failure) or the context knows what it lost (mrt_set_world*: no scene, MRT_ERR_NO_SCENE from the render
+ *       calls, until a mrt_set_world* succeeds);
+ *   C4  the call can be repeated: once the runtime has the resource to give, the same call succeeds, and every image,
+ *       counter and report from then on is bit-identical to a run in which nothing was ever refused (the schedule -- launch
+ *       widths, frames in flight -- may differ, as it may between any two runs).
+ * Failures of the calls that ENQUEUE work (copies, memsets, event records, launches) are reported as MRT_ERR_HIP too, but
+ * are outside this contract.  tests/test_gpu_failure_paths.py holds C1-C4 at every creation site by failure injection. */
 
 /* ---- raytracer::Args, lib.rs:18-37; flags of native-runner/src/main.rs:20-31 ---- */
 typedef struct {

@@ -167,6 +167,12 @@ int mrt_debug_wave_log_frame(mrt_ctx* ctx, uint32_t back, uint64_t* out, size_t 
 /* Host wall time (ms) the most recent mrt_set_world* call spent building and uploading the bounding-sphere
  * hierarchy (a one-off per scene, outside the per-frame metric). */
 int mrt_debug_last_set_world_ms(mrt_ctx* ctx, float* ms);
+/* Host only, launches nothing: walks the context and returns 0 if no call it would accept -- the next frame, query, present,
+ * denoise, gather or read-back -- could touch a buffer, stream or event that is not there; else 1, with the first finding in
+ * `why` (cap bytes).  A part the context knows it lacks and refuses the calls for (no scene: MRT_ERR_NO_SCENE) is sound.
+ * tests/test_gpu_failure_paths.py calls it after every refused resource creation, before anything else is launched; the
+ * state-machine sequences (tests/state_sequences.py) end with it. */
+int mrt_debug_check_context(mrt_ctx* ctx, char* why, size_t cap);
 
 #ifdef __cplusplus
 }

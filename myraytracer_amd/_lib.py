@@ -45,6 +45,7 @@ EXPORTS = [
     "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
     "mrt_debug_read_guides",
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
+    "mrt_debug_check_context",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -323,6 +324,7 @@ def load():
         "mrt_render_tiles": (i32, [vp, vp, sz, u32]),
         "mrt_render_adaptive": (i32, [vp, u32, C.c_uint64, P(C.c_uint64), P(u32)]),
         "mrt_read_tile_frames": (i32, [vp, vp, sz, P(u32), P(u32)]),
+        "mrt_debug_check_context": (i32, [vp, C.c_char_p, sz]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

@@ -444,6 +444,12 @@ class State:
         self._check(self._L.mrt_debug_stream_concurrency(self._ctx, streams, C.byref(out)), "mrt_debug_stream_concurrency")
         return float(out.value)
 
+    def debug_check_context(self) -> Optional[str]:
+        """Host only: None if no call the context accepts could touch a buffer, stream or event that is not there, else the
+        first finding (mrt_debug_check_context)."""
+        why = C.create_string_buffer(512)
+        return why.value.decode() if self._L.mrt_debug_check_context(self._ctx, why, len(why)) else None
+
     def debug_set_frames_in_flight(self, slots: int):
         """How many frames may be in flight, each on a side stream of its own (1..8; 0 = automatic)."""
         self._check(self._L.mrt_debug_set_frames_in_flight(self._ctx, slots), "mrt_debug_set_frames_in_flight")

@@ -122,30 +122,38 @@ int alloc_first_colour_sums(mrt_ctx* c, mrt_ctx::FrameSlot& S) {
     return MRT_OK;
 }
 
-// Subject::new + DoubleFramebuffers::new for the current shard (lib.rs:389-415, 514-538)
-int alloc_frame_buffers(mrt_ctx* c) {
-    free_frame_buffers(c);
-    const uint32_t nb = total_bands(c->args.height);
-    c->local_bands = (nb + c->shard_world - 1) / c->shard_world;   // same on every rank (gather-friendly)
-    const size_t n = local_texels(c);
-    HIP_TRY(c, hipMalloc(&c->d_seeds, n * 4 * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&c->d_fb[0], n * 4 * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->d_fb[1], n * 4 * sizeof(float)));
-    HIP_TRY(c, hipMemsetAsync(c->d_fb[0], 0, n * 4 * sizeof(float), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_fb[1], 0, n * 4 * sizeof(float), c->stream));
-    c->tiles_x = (c->args.width + mrt::kTileW - 1) / mrt::kTileW;
-    c->n_tiles = c->tiles_x * c->local_bands;
-    for (auto& S : c->slot) {
-        HIP_TRY(c, hipMalloc(&S.d_tile_cost, (size_t)tiles_min1(c) * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&S.d_tile_order, (size_t)tiles_min1(c) * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&S.d_sort_scratch, (1024 + 16) * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(S.d_sort_scratch, 0, (1024 + 16) * sizeof(uint32_t), c->stream));   // [1024] = the tile queue's counter
-        if (&S - c->slot >= 2) continue;        // further slots (pixel-starved shards only) get their colour sums on first use
-        MRT_TRY(alloc_first_colour_sums(c, S));
+// a shard's buffers while alloc_frame_buffers builds them: the context takes them over only when all of them exist
+struct ShardBuffers {
+    uint32_t* seeds = nullptr;
+    float* fb[2] = {nullptr, nullptr};
+    struct Slot { uint32_t *cost = nullptr, *order = nullptr, *scratch = nullptr; void* pix_acc = nullptr; } slot[mrt_ctx::kMaxFrameSlots];
+    float *noise_s = nullptr, *noise_tiles = nullptr;
+    void* noise_partials = nullptr;
+    uint32_t n_waves = 0, cus = 0;
+    void release() {
+        free_device(seeds, fb[0], fb[1], noise_s, noise_tiles, noise_partials);
+        for (auto& S : slot) free_device(S.cost, S.order, S.scratch, S.pix_acc);
     }
-    c->frame_slots = 2;
-    c->width.div = 0;
-    c->inputs_dirty = true;
+};
+
+static int build_shard_buffers(mrt_ctx* c, uint32_t rank, uint32_t world, uint32_t local_bands, ShardBuffers& B) {
+    const size_t n = (size_t)local_bands * kBandRows * c->args.width, n1 = n ? n : 1;
+    const uint32_t tiles_x = (c->args.width + mrt::kTileW - 1) / mrt::kTileW;
+    const size_t tiles1 = (size_t)tiles_x * local_bands ? (size_t)tiles_x * local_bands : 1;
+    HIP_TRY(c, hipMalloc(&B.seeds, n * 4 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&B.fb[0], n * 4 * sizeof(float)));
+    HIP_TRY(c, hipMalloc(&B.fb[1], n * 4 * sizeof(float)));
+    HIP_TRY(c, hipMemsetAsync(B.fb[0], 0, n * 4 * sizeof(float), c->stream));
+    HIP_TRY(c, hipMemsetAsync(B.fb[1], 0, n * 4 * sizeof(float), c->stream));
+    for (auto& S : B.slot) {
+        HIP_TRY(c, hipMalloc(&S.cost, tiles1 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMalloc(&S.order, tiles1 * sizeof(uint32_t)));
+        HIP_TRY(c, hipMalloc(&S.scratch, (1024 + 16) * sizeof(uint32_t)));
+        HIP_TRY(c, hipMemsetAsync(S.scratch, 0, (1024 + 16) * sizeof(uint32_t), c->stream));   // [1024] = the tile queue's counter
+        if (&S - B.slot >= 2) continue;        // further slots (pixel-starved shards only) get their colour sums on first use
+        HIP_TRY(c, hipMalloc(&S.pix_acc, n1 * 16));
+        HIP_TRY(c, hipMemsetAsync(S.pix_acc, 0, n1 * 16, c->stream));
+    }
     // as many persistent single-wave workgroups as the chip holds
     {
         hipDeviceProp_t prop;
@@ -153,14 +161,50 @@ int alloc_frame_buffers(mrt_ctx* c) {
         int wpc = 0;
         if (mrt::render_waves_per_cu(&wpc) != 0 || wpc <= 0) wpc = 16;
         if (c->waves_per_cu_override > 0) wpc = c->waves_per_cu_override;
-        c->n_waves = (uint32_t)prop.multiProcessorCount * (uint32_t)wpc;
-        c->cus = (uint32_t)prop.multiProcessorCount;
+        B.n_waves = (uint32_t)prop.multiProcessorCount * (uint32_t)wpc;
+        B.cus = (uint32_t)prop.multiProcessorCount;
     }
-    int e = mrt::launch_fill_seeds(c->d_seeds, c->seed, c->args.width, c->args.height, c->shard_rank,
-                                   c->shard_world, c->local_bands, c->stream);
+    int e = mrt::launch_fill_seeds(B.seeds, c->seed, c->args.width, c->args.height, rank, world, local_bands, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "fill_seeds launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (c->noise_on) MRT_TRY(alloc_noise_set(c, local_bands, &B.noise_s, &B.noise_tiles, &B.noise_partials));
+    return MRT_OK;
+}
+
+// Subject::new + DoubleFramebuffers::new for shard `rank` of `world` (lib.rs:389-415, 514-538).  The new buffers are all
+// allocated before the old ones are released, so a refused allocation leaves the context -- its shard, its buffers, its frame
+// slots -- exactly as it was and the call can simply be repeated; the price is both sets side by side for the moment of a call
+// that happens once per shard assignment.
+int alloc_frame_buffers(mrt_ctx* c, uint32_t rank, uint32_t world) {
+    const uint32_t nb = total_bands(c->args.height);
+    const uint32_t local_bands = (nb + world - 1) / world;   // same on every rank (gather-friendly)
+    ShardBuffers B;
+    const int st = build_shard_buffers(c, rank, world, local_bands, B);
+    if (st != MRT_OK) {
+        B.release();                             // (hipFree waits for the memsets queued on them)
+        return st;
+    }
+    free_frame_buffers(c);
+    c->shard_rank = rank; c->shard_world = world;
+    c->local_bands = local_bands;
+    c->d_seeds = B.seeds; c->d_fb[0] = B.fb[0]; c->d_fb[1] = B.fb[1];
+    c->tiles_x = (c->args.width + mrt::kTileW - 1) / mrt::kTileW;
+    c->n_tiles = c->tiles_x * c->local_bands;
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        mrt_ctx::FrameSlot& S = c->slot[i];
+        S.d_tile_cost = B.slot[i].cost; S.d_tile_order = B.slot[i].order; S.d_sort_scratch = B.slot[i].scratch;
+        S.d_pix_acc = B.slot[i].pix_acc;
+        S.pix_acc_layers = S.d_pix_acc ? 1 : 0;
+    }
+    c->frame_slots = 2;
+    c->last_slot = 0;               // (what mrt_debug_read_pixel_costs reads: a slot that has colour sums)
+    c->width.div = 0;
+    c->inputs_dirty = true;
+    c->n_waves = B.n_waves; c->cus = B.cus;
     c->target = 0;
-    if (c->noise_on) MRT_TRY(alloc_noise_buffers(c));
+    if (c->noise_on) {
+        c->d_noise_s = B.noise_s; c->d_noise_tiles = B.noise_tiles; c->d_noise_partials = B.noise_partials;
+        c->noise_first = c->noise_seq + 1;          // (reports of the old geometry are discarded)
+    }
     return MRT_OK;
 }
 
@@ -220,6 +264,18 @@ int read_rows(mrt_ctx* c, const char* who, const void* src, void* out, size_t ca
 }
 
 }  // namespace mrt
+
+// mrt_debug_check_context's finding: 1, with the reason in `why`
+static int check_finding(char* why, size_t cap, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+static int check_finding(char* why, size_t cap, const char* fmt, ...) {
+    if (why && cap) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(why, cap, fmt, ap);
+        va_end(ap);
+    }
+    return 1;
+}
 
 extern "C" {
 
@@ -397,21 +453,30 @@ int mrt_create(const mrt_args* args, uint64_t seed, int device, mrt_ctx** out) {
     }
     c->cam_raw.mode = 0;
     reset_locals(c);
-    auto bail = [&](int st) { g_err = c->err; mrt_destroy(c); return st; };
-    if (hipSetDevice(device) != hipSuccess) { c->err = "hipSetDevice failed"; return bail(MRT_ERR_HIP); }
-    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { c->err = "hipStreamCreate failed"; return bail(MRT_ERR_HIP); }
-    c->stream = c->own_stream;
-    // (slots 0 and 1 now; the further ones -- pixel-starved shards only -- when redraw_frames first needs them)
-    for (uint32_t i = 0; i < 2; i++)
-        if (mrt::create_slot_streams(c->slot[i]) != hipSuccess) { c->err = "side stream creation failed"; return bail(MRT_ERR_HIP); }
-    if (hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(MRT_ERR_HIP); }
-    for (uint32_t i = 0; i < mrt_ctx::kEventRing; i++)
-        if (hipEventCreate(&c->ev_start[i]) != hipSuccess || hipEventCreate(&c->ev_stop[i]) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(MRT_ERR_HIP); }
-    if (hipMalloc(&c->d_counters, 16 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream) != hipSuccess) { c->err = "counter allocation failed"; return bail(MRT_ERR_HIP); }
-    if (hipHostMalloc((void**)&c->h_stats, 5 * mrt_ctx::kMaxFrameSlots * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { c->err = "pinned allocation failed"; return bail(MRT_ERR_HIP); }
-    int st = alloc_frame_buffers(c);
-    if (st != MRT_OK) return bail(st);
+    // everything the context owns from the start; a failure names the refused call (mrt_last_error(NULL)) and mrt_destroy
+    // releases whatever the half-built context holds
+    auto init = [&]() -> int {
+        HIP_TRY(c, hipSetDevice(device));
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+        c->stream = c->own_stream;
+        // (slots 0 and 1 now; the further ones -- pixel-starved shards only -- when redraw_frames first needs them)
+        for (uint32_t i = 0; i < 2; i++) MRT_TRY(mrt::create_slot_streams(c, c->slot[i]));
+        HIP_TRY(c, hipEventCreateWithFlags(&c->ev_inputs, hipEventDisableTiming));
+        for (uint32_t i = 0; i < mrt_ctx::kEventRing; i++) {
+            HIP_TRY(c, hipEventCreate(&c->ev_start[i]));
+            HIP_TRY(c, hipEventCreate(&c->ev_stop[i]));
+        }
+        HIP_TRY(c, hipMalloc(&c->d_counters, 16 * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_stats, 5 * mrt_ctx::kMaxFrameSlots * sizeof(unsigned long long), hipHostMallocDefault));
+        return alloc_frame_buffers(c, 0, 1);
+    };
+    const int st = init();
+    if (st != MRT_OK) {
+        g_err = "mrt_create: " + c->err;
+        mrt_destroy(c);
+        return st;
+    }
     *out = c;
     return MRT_OK;
 }
@@ -466,8 +531,7 @@ int mrt_set_shard(mrt_ctx* c, uint32_t rank, uint32_t world) {
     MRT_TRY(mrt::wait_all(c, __func__));
     for (auto& E : c->present_ring) E.state = mrt_ctx::PresentEntry::kFree;      // (the presented images are discarded)
     c->present_dropped = 0;
-    c->shard_rank = rank; c->shard_world = world;
-    return alloc_frame_buffers(c);
+    return alloc_frame_buffers(c, rank, world);
 }
 
 int mrt_set_stream(mrt_ctx* c, void* s) {
@@ -558,7 +622,9 @@ int mrt_debug_arith_pairs(mrt_ctx* c, const float* x, const float* y, size_t n, 
     float* d_xy = nullptr;
     uint32_t* d_o = nullptr;
     HIP_TRY(c, hipMalloc((void**)&d_xy, 2 * n * sizeof(float)));
-    hipError_t e = hipMalloc((void**)&d_o, 6 * n * sizeof(uint32_t));
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_arith_pairs";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_o, 6 * n * sizeof(uint32_t)));
     if (e == hipSuccess) e = hipMemcpyAsync(d_xy, x, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_xy + n, y, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = (hipError_t)mrt::launch_arith_pairs(d_xy, d_xy + n, (uint32_t)n, d_o, c->stream);
@@ -568,7 +634,7 @@ int mrt_debug_arith_pairs(mrt_ctx* c, const float* x, const float* y, size_t n, 
     if (ws != MRT_OK) return ws;
     (void)hipFree(d_xy);
     if (d_o) (void)hipFree(d_o);
-    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_arith_pairs failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return MRT_OK;
 }
 
@@ -683,7 +749,9 @@ int mrt_debug_wave_log_frame(mrt_ctx* c, uint32_t back, uint64_t* out, size_t ca
         MRT_TRY(mrt::wait_all(c, __func__));
         free_device(c->d_wave_log);
         HIP_TRY(c, hipMalloc(&c->d_wave_log, mrt_ctx::kWaveLogFrames * n * 4 * sizeof(uint64_t)));
-        HIP_TRY(c, hipMemset(c->d_wave_log, 0, mrt_ctx::kWaveLogFrames * n * 4 * sizeof(uint64_t)));
+        // (on the ctx's stream and waited for: the side streams do not order themselves behind the null stream)
+        HIP_TRY(c, hipMemsetAsync(c->d_wave_log, 0, mrt_ctx::kWaveLogFrames * n * 4 * sizeof(uint64_t), c->stream));
+        MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
         c->wave_log_waves = n;
     }
     if (out) {
@@ -712,6 +780,69 @@ int mrt_kernel_ms_history(mrt_ctx* c, float* ms, size_t cap, size_t* n_out) {
     }
     *n_out = n;
     return MRT_OK;
+}
+
+// Host only: would a call this context ACCEPTS touch something that is not there?  Walks what the next frame, query, present,
+// denoise or gather reads and writes; a part the context knows it lacks and refuses the calls for (no scene: MRT_ERR_NO_SCENE)
+// is sound.  0 = sound; else 1 and the first finding in `why`.
+int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (why && cap) why[0] = 0;
+    if (!c->stream || !c->own_stream) return check_finding(why, cap, "the context has no stream");
+    if (!c->ev_inputs) return check_finding(why, cap, "ev_inputs is missing");
+    for (uint32_t i = 0; i < mrt_ctx::kEventRing; i++)
+        if (!c->ev_start[i] || !c->ev_stop[i]) return check_finding(why, cap, "timing event pair %u is missing", i);
+    if (!c->d_counters || !c->h_stats) return check_finding(why, cap, "the counters or their pinned copy are missing");
+    if (c->shard_world == 0 || c->shard_rank >= c->shard_world) return check_finding(why, cap, "shard %u of %u", c->shard_rank, c->shard_world);
+    if (c->local_bands != (total_bands(c->args.height) + c->shard_world - 1) / c->shard_world || c->tiles_x != (c->args.width + mrt::kTileW - 1) / mrt::kTileW ||
+        c->n_tiles != c->tiles_x * c->local_bands)
+        return check_finding(why, cap, "local_bands %u / tiles %u x %u do not belong to shard %u of %u", c->local_bands, c->tiles_x, c->n_tiles, c->shard_rank, c->shard_world);
+    if (local_texels(c) > 0 && (!c->d_fb[0] || !c->d_fb[1] || !c->d_seeds)) return check_finding(why, cap, "a framebuffer or the seeds are missing (%zu local texels)", local_texels(c));
+    if (c->target != 0 && c->target != 1) return check_finding(why, cap, "target %d", c->target);
+    if (c->n_waves == 0 || c->cus == 0) return check_finding(why, cap, "n_waves %u, cus %u", c->n_waves, c->cus);
+    if (c->frame_slots < 1 || c->frame_slots > mrt_ctx::kMaxFrameSlots) return check_finding(why, cap, "frame_slots %u", c->frame_slots);
+    if (c->last_slot >= mrt_ctx::kMaxFrameSlots) return check_finding(why, cap, "last_slot %u", c->last_slot);
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        const mrt_ctx::FrameSlot& S = c->slot[i];
+        if ((S.pix_acc_layers == 0) != (S.d_pix_acc == nullptr)) return check_finding(why, cap, "slot %u: %zu layers of colour sums at %p", i, S.pix_acc_layers, S.d_pix_acc);
+        if (S.d_pix_acc && (size_t)S.cost_first_layer + S.cost_layers > S.pix_acc_layers)
+            return check_finding(why, cap, "slot %u: cost layers %u + %u of %zu", i, S.cost_first_layer, S.cost_layers, S.pix_acc_layers);
+        if ((S.stats_pending || S.render_pending) && (!S.stream || !S.stats_ready || !S.render_done)) return check_finding(why, cap, "slot %u: a frame is pending without its stream or events", i);
+        if (i >= c->frame_slots && i != c->last_slot) continue;
+        if (!S.stream) return check_finding(why, cap, "slot %u of %u in use has no stream (its frames would run on the null stream)", i, c->frame_slots);
+        if (!S.render_done || !S.finalize_done || !S.stats_ready) return check_finding(why, cap, "slot %u of %u in use lacks an event", i, c->frame_slots);
+        if (!S.d_tile_cost || !S.d_tile_order || !S.d_sort_scratch) return check_finding(why, cap, "slot %u of %u in use lacks its tile cost / order / scratch buffers", i, c->frame_slots);
+        if (S.pix_acc_layers < 1) return check_finding(why, cap, "slot %u of %u in use has no colour sums", i, c->frame_slots);
+    }
+    if (c->have_world) {
+        if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
+            return check_finding(why, cap, "have_world without one of the scene's arrays");
+        if (c->n_members > 1024u && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
+    }
+    if (c->noise_on) {
+        if (!c->d_noise_s || !c->d_noise_tiles || !c->d_noise_partials) return check_finding(why, cap, "noise tracking is on without S, the tile maps or the scratch");
+        if (!c->d_noise_sums || !c->h_noise_sums) return check_finding(why, cap, "noise tracking is on without the ring's sums");
+        for (uint32_t i = 0; i < mrt_ctx::kNoiseRing; i++)
+            if (!c->noise_ring[i].copied) return check_finding(why, cap, "noise ring entry %u has no event", i);
+    } else if (c->d_noise_s) {
+        return check_finding(why, cap, "S exists while noise tracking is off (the blends would track)");
+    }
+    if (c->present_depth > c->present_ring.size()) return check_finding(why, cap, "present depth %u of %zu entries", c->present_depth, c->present_ring.size());
+    for (size_t i = 0; i < c->present_ring.size(); i++) {
+        const mrt_ctx::PresentEntry& E = c->present_ring[i];
+        if (!E.d_img || !E.h_img || !E.copied) return check_finding(why, cap, "present ring entry %zu lacks its device image, pinned image or event", i);
+    }
+    if (!c->present_ring.empty() && (c->present_entry_bytes == 0 || !c->d_present_tables)) return check_finding(why, cap, "a present ring without entry size or tables");
+    if (!c->guides_stale && (!c->d_guides || !c->d_guide_rays || !c->d_guide_hits || !c->d_guide_queue || !c->d_guide_cand || !c->d_den[0] || !c->d_den[1] || !c->d_den[2]))
+        return check_finding(why, cap, "the guides are marked current without the denoiser's buffers");
+    if (c->d_guide_cand == nullptr ? c->guide_cand_words != 0 : c->guide_cand_words == 0) return check_finding(why, cap, "guide bitmap %p of %zu words", (void*)c->d_guide_cand, c->guide_cand_words);
+    if (c->tiles_diverged) {
+        if (c->n_tiles && !c->d_tile_frames) return check_finding(why, cap, "the accumulation has diverged without the tile frame counts");
+        if (c->tile_frames.size() != c->n_tiles) return check_finding(why, cap, "%zu host tile frame counts for %u tiles", c->tile_frames.size(), c->n_tiles);
+    }
+    if (c->k_len != 0 && (!c->d_k_f32 || !c->d_k_f64 || c->k_table.size() < c->k_len)) return check_finding(why, cap, "a K table of %u entries without its buffers", c->k_len);
+    if (c->d_wave_log && c->wave_log_waves == 0) return check_finding(why, cap, "a wave log of no waves");
+    return 0;
 }
 
 int mrt_last_kernel_ms(mrt_ctx* c, float* ms) {

@@ -35,11 +35,12 @@ bool denoise_params_ok(const mrt_denoise_params* p) {
 
 int ensure_denoise_buffers(mrt_ctx* c) {
     const size_t n = (size_t)c->args.width * c->args.height;
-    if (!c->d_guides) {
-        HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
-        HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc((void**)&c->d_guide_queue, 64));
-        for (auto& d : c->d_den) HIP_TRY(c, hipMalloc((void**)&d, n * 16));
+    if (!c->d_guides) {         // (each of them unless an earlier, refused attempt already left it: d_guides is the last)
+        if (!c->d_guide_rays) HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
+        if (!c->d_guide_hits) HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
+        if (!c->d_guide_queue) HIP_TRY(c, hipMalloc((void**)&c->d_guide_queue, 64));
+        for (auto& d : c->d_den)
+            if (!d) HIP_TRY(c, hipMalloc((void**)&d, n * 16));
         HIP_TRY(c, hipMalloc((void**)&c->d_guides, n * 32));
         c->guides_stale = true;
     }
@@ -186,11 +187,12 @@ int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, c
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)width * rows;
     float *d_fb = nullptr, *d_s = nullptr, *d_g = nullptr, *d_b[3] = {nullptr, nullptr, nullptr};
-    hipError_t e = hipMalloc((void**)&d_fb, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_s, n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_g, n * 32);
-    for (auto& b : d_b)
-        if (e == hipSuccess) e = hipMalloc((void**)&b, n * 16);
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_denoise";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_fb, n * 16));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_s, n * sizeof(float)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_g, n * 32));
+    for (auto& b : d_b) HIP_CHAIN(e, what, hipMalloc((void**)&b, n * 16));
     if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
@@ -200,7 +202,7 @@ int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, c
     if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");
     if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
     mrt::free_device(d_fb, d_s, d_g, d_b[0], d_b[1], d_b[2]);
-    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_denoise failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return MRT_OK;
 }
 

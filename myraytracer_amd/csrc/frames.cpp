@@ -11,14 +11,13 @@ using mrt::fail, mrt::local_texels, mrt::create_slot_streams, mrt::fill_scene_pa
 
 namespace mrt {
 
-// the side stream of a frame slot and its two events
-hipError_t create_slot_streams(mrt_ctx::FrameSlot& S) {
-    hipError_t e = hipSuccess;
-    if (!S.stream) e = hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !S.render_done) e = hipEventCreateWithFlags(&S.render_done, hipEventDisableTiming);
-    if (e == hipSuccess && !S.finalize_done) e = hipEventCreateWithFlags(&S.finalize_done, hipEventDisableTiming);
-    if (e == hipSuccess && !S.stats_ready) e = hipEventCreateWithFlags(&S.stats_ready, hipEventDisableTiming);
-    return e;
+// the side stream of a frame slot and its three events (those it does not have yet)
+int create_slot_streams(mrt_ctx* c, mrt_ctx::FrameSlot& S) {
+    if (!S.stream) HIP_TRY(c, hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+    if (!S.render_done) HIP_TRY(c, hipEventCreateWithFlags(&S.render_done, hipEventDisableTiming));
+    if (!S.finalize_done) HIP_TRY(c, hipEventCreateWithFlags(&S.finalize_done, hipEventDisableTiming));
+    if (!S.stats_ready) HIP_TRY(c, hipEventCreateWithFlags(&S.stats_ready, hipEventDisableTiming));
+    return MRT_OK;
 }
 
 // adaptive sampling's per-tile state (mrt_render_tiles): back to a uniform accumulation
@@ -41,7 +40,7 @@ void free_tile_frames(mrt_ctx* c) {
 static int probe_stream_concurrency(mrt_ctx* c, uint32_t k, float* out) {
     if (k < 2u) k = 2u;
     if (k > mrt_ctx::kMaxFrameSlots) k = mrt_ctx::kMaxFrameSlots;
-    for (uint32_t i = 0; i < k; i++) HIP_TRY(c, create_slot_streams(c->slot[i]));
+    for (uint32_t i = 0; i < k; i++) MRT_TRY(create_slot_streams(c, c->slot[i]));
     MRT_TRY(mrt::wait_all(c, "probe_stream_concurrency"));
     unsigned long long* const stamps = c->h_stats + 3 * mrt_ctx::kMaxFrameSlots;      // pinned, device-visible: 2 per stream
     uint32_t best = 0;
@@ -248,16 +247,17 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
 static int set_frame_slots(mrt_ctx* c, uint32_t want) {
     if (want == c->frame_slots) return MRT_OK;
     MRT_TRY(mrt::wait_all(c, "mrt_redraw: change of the frames in flight"));
-    c->frame_slots = want;
     // the further slots' streams and colour sums now, in one go: allocated on first use each would wait for the frames in flight
+    // (frame_slots only once every slot below it is complete: if a creation fails, the next redraw comes back here)
     for (uint32_t i = 0; i < want; i++) {
         mrt_ctx::FrameSlot& T = c->slot[i];
-        HIP_TRY(c, create_slot_streams(T));
+        MRT_TRY(create_slot_streams(c, T));
         T.stats_pending = false;
         T.render_pending = false;
         if (T.pix_acc_layers != 0) continue;
         MRT_TRY(mrt::alloc_first_colour_sums(c, T));
     }
+    c->frame_slots = want;
     return MRT_OK;
 }
 
@@ -285,9 +285,10 @@ static int grow_colour_sums(mrt_ctx* c, mrt_ctx::FrameSlot& S, uint32_t layers, 
     if (S.pix_acc_layers >= layers) return MRT_OK;
     MRT_TRY(mrt::wait_stream(c, S.stream, side_wait));
     MRT_TRY(mrt::wait_stream(c, c->stream, ctx_wait));
+    void* grown = nullptr;          // (the larger sums first: if they cannot be had, the slot keeps the ones it has)
+    HIP_TRY(c, hipMalloc(&grown, (size_t)layers * mrt::local_texels_min1(c) * 16));
     mrt::free_device(S.d_pix_acc);
-    S.pix_acc_layers = 0;
-    HIP_TRY(c, hipMalloc(&S.d_pix_acc, (size_t)layers * mrt::local_texels_min1(c) * 16));
+    S.d_pix_acc = grown;
     S.pix_acc_layers = layers;
     return MRT_OK;
 }
@@ -685,11 +686,14 @@ int mrt_debug_set_schedule(mrt_ctx* c, uint32_t pilot_spp, int waves_per_cu) {
     if (!c) return MRT_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(mrt::wait_all(c, __func__));
+    if (c->frames_done != 0) return fail(c, MRT_ERR_STATE, "mrt_debug_set_schedule: frames already rendered");
+    const uint32_t old_pilot = c->pilot_spp;
+    const int old_waves = c->waves_per_cu_override;
     c->pilot_spp = pilot_spp ? pilot_spp : 1;
     c->waves_per_cu_override = waves_per_cu;
-    const uint32_t frames = c->frames_done;
-    if (frames != 0) return fail(c, MRT_ERR_STATE, "mrt_debug_set_schedule: frames already rendered");
-    return alloc_frame_buffers(c);
+    const int st = alloc_frame_buffers(c, c->shard_rank, c->shard_world);
+    if (st != MRT_OK) { c->pilot_spp = old_pilot; c->waves_per_cu_override = old_waves; }
+    return st;
 }
 
 int mrt_get_schedule(mrt_ctx* c, uint32_t out[6]) {

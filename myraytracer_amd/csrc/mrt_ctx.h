@@ -263,21 +263,24 @@ int wait_stream(mrt_ctx* c, hipStream_t s, const char* what);
 // everything this context has in flight: the side streams, then the caller's stream
 int wait_all(mrt_ctx* c, const char* what);
 
-// What one host file defines and another calls.  api.cpp: the current shard's buffers (re)allocated; the scene's arrays released;
+// What one host file defines and another calls.  api.cpp: the buffers of shard `rank` of `world` allocated and, only once all of
+// them exist, put in the place of the current shard's (a failure leaves the context as it was); the scene's arrays released;
 // a slot's first layer of colour sums, zeroed on the ctx's stream; the tail of a read-back of this shard's texels (`who`: the entry
 // point, for the messages) -- capacity check, the full bottom-up image when shard_world == 1 else the packed rows, bounded wait
-int alloc_frame_buffers(mrt_ctx* c);
+int alloc_frame_buffers(mrt_ctx* c, uint32_t rank, uint32_t world);
 void free_world(mrt_ctx* c);
 int alloc_first_colour_sums(mrt_ctx* c, mrt_ctx::FrameSlot& S);
 int read_rows(mrt_ctx* c, const char* who, const void* src, void* out, size_t cap, size_t texel_bytes);
 // world.cpp: the scene / hierarchy / sweep-variant part of the kernel arguments
 void fill_scene_params(const mrt_ctx* c, KParams& p);
 // frames.cpp: the side stream of a frame slot and its events; adaptive sampling's per-tile state, released
-hipError_t create_slot_streams(mrt_ctx::FrameSlot& S);
+int create_slot_streams(mrt_ctx* c, mrt_ctx::FrameSlot& S);
 void free_tile_frames(mrt_ctx* c);
-// noise.cpp: noise tracking's per-texel buffers, sized like the framebuffers
+// noise.cpp: noise tracking's per-texel buffers, sized like the framebuffers; the same three for a shard of `local_bands` bands
+// into the caller's pointers (all of them or, on a failure, none)
 void free_noise_buffers(mrt_ctx* c);
 int alloc_noise_buffers(mrt_ctx* c);
+int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, void** partials);
 // denoise.cpp: the denoiser's buffers released; its part of mrt_present (present.cpp): the refusals; the denoise queued, *src = its output
 void free_denoise_buffers(mrt_ctx* c);
 int present_denoised_check(mrt_ctx* c);
@@ -289,6 +292,16 @@ int present_denoised(mrt_ctx* c, const float** src);
     do {                                   \
         const int st_ = (expr);            \
         if (st_ != MRT_OK) return st_;     \
+    } while (0)
+
+// a chain of HIP calls that stops at the first failure (`e`) and remembers which call that was (`what`), for a function that
+// has scratch buffers to release before it reports: fail(ctx, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e))
+#define HIP_CHAIN(e, what, expr)                        \
+    do {                                                \
+        if ((e) == hipSuccess) {                        \
+            (e) = (expr);                               \
+            if ((e) != hipSuccess) (what) = #expr;      \
+        }                                               \
     } while (0)
 
 #define HIP_TRY(ctx, expr)                                                                     \

@@ -12,15 +12,25 @@ namespace mrt {
 // noise tracking's per-texel buffers, sized like the framebuffers (mrt_set_noise_tracking)
 void free_noise_buffers(mrt_ctx* c) { free_device(c->d_noise_s, c->d_noise_tiles, c->d_noise_partials); }
 
+int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, void** partials) {
+    const size_t texels = (size_t)local_bands * kBandRows * c->args.width, n = texels ? texels : 1;
+    const size_t n_tiles = (size_t)((c->args.width + kTileW - 1) / kTileW) * local_bands;
+    const size_t map_floats = (size_t)mrt_ctx::kNoiseRing * (n_tiles ? n_tiles : 1);     // a tile map per report of the ring
+    const int st = [&]() -> int {
+        HIP_TRY(c, hipMalloc((void**)s, n * sizeof(float)));
+        HIP_TRY(c, hipMemsetAsync(*s, 0, n * sizeof(float), c->stream));
+        HIP_TRY(c, hipMalloc((void**)tiles, map_floats * sizeof(float)));
+        HIP_TRY(c, hipMemsetAsync(*tiles, 0, map_floats * sizeof(float), c->stream));
+        HIP_TRY(c, hipMalloc(partials, std::max<size_t>(mrt::noise_partials_bytes(c->args.width, local_bands), 64)));
+        return MRT_OK;
+    }();
+    if (st != MRT_OK) free_device(*s, *tiles, *partials);      // (all three or none: S alone would switch the blends to tracking)
+    return st;
+}
+
 int alloc_noise_buffers(mrt_ctx* c) {
     free_noise_buffers(c);
-    const size_t n = local_texels_min1(c);
-    HIP_TRY(c, hipMalloc((void**)&c->d_noise_s, n * sizeof(float)));
-    HIP_TRY(c, hipMemsetAsync(c->d_noise_s, 0, n * sizeof(float), c->stream));
-    const size_t map_floats = (size_t)mrt_ctx::kNoiseRing * tiles_min1(c);     // a tile map per report of the ring
-    HIP_TRY(c, hipMalloc((void**)&c->d_noise_tiles, map_floats * sizeof(float)));
-    HIP_TRY(c, hipMemsetAsync(c->d_noise_tiles, 0, map_floats * sizeof(float), c->stream));
-    HIP_TRY(c, hipMalloc(&c->d_noise_partials, std::max<size_t>(mrt::noise_partials_bytes(c->args.width, c->local_bands), 64)));
+    MRT_TRY(alloc_noise_set(c, c->local_bands, &c->d_noise_s, &c->d_noise_tiles, &c->d_noise_partials));
     c->noise_first = c->noise_seq + 1;          // (reports of the old geometry are discarded)
     return MRT_OK;
 }
@@ -277,11 +287,13 @@ int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32
     void* d_part = nullptr;
     mrt::NoiseSums* d_sums = nullptr;
     mrt::NoiseSums h{};
-    hipError_t e = hipMalloc((void**)&d_s, n * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_rgba, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_tiles, tiles * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&d_part, mrt::noise_partials_bytes(width, bands));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_sums, sizeof h);
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_noise_reduce";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_s, n * sizeof(float)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_rgba, n * 16));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_tiles, tiles * sizeof(float)));
+    HIP_CHAIN(e, what, hipMalloc(&d_part, mrt::noise_partials_bytes(width, bands)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_sums, sizeof h));
     if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
@@ -293,7 +305,7 @@ int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32
     if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_noise_reduce");
     if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
     mrt::free_device(d_s, d_rgba, d_tiles, d_part, d_sums);
-    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_noise_reduce failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     *out = mrt_noise_report{};
     out->threshold = threshold; out->floor = floor_;
     out->noise_factor = K;

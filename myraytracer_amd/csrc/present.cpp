@@ -79,15 +79,17 @@ int present_ring_reserve(mrt_ctx* c, size_t bytes, uint32_t depth) {
     while (c->present_ring.size() < depth) {
         c->present_ring.emplace_back();
         PresentEntry& E = c->present_ring.back();
-        hipError_t e = hipMalloc((void**)&E.d_img, c->present_entry_bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&E.h_img, c->present_entry_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&E.copied, hipEventDisableTiming);
+        hipError_t e = hipSuccess;
+        const char* what = "";
+        HIP_CHAIN(e, what, hipMalloc((void**)&E.d_img, c->present_entry_bytes));
+        HIP_CHAIN(e, what, hipHostMalloc((void**)&E.h_img, c->present_entry_bytes, hipHostMallocDefault));
+        HIP_CHAIN(e, what, hipEventCreateWithFlags(&E.copied, hipEventDisableTiming));
         if (e != hipSuccess) {
             if (E.d_img) (void)hipFree(E.d_img);
             if (E.h_img) (void)hipHostFree(E.h_img);
             c->present_ring.pop_back();
-            return fail(c, MRT_ERR_HIP, "mrt_present: ring entry %zu (%zu bytes) allocation failed: %s", c->present_ring.size(),
-                        c->present_entry_bytes, hipGetErrorString(e));
+            return fail(c, MRT_ERR_HIP, "mrt_present: ring entry %zu (%zu bytes): %s failed: %s", c->present_ring.size(),
+                        c->present_entry_bytes, what, hipGetErrorString(e));
         }
     }
     c->present_depth = depth;
@@ -164,10 +166,9 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (e) return fail(c, MRT_ERR_HIP, "present launch failed: %s", hipGetErrorString((hipError_t)e));
     hipStream_t copy_stream = c->stream;
     if (c->present_copy_mode == 0) {
-        if (!c->present_stream) {
-            HIP_TRY(c, hipEventCreateWithFlags(&c->ev_presented, hipEventDisableTiming));
-            HIP_TRY(c, hipStreamCreateWithFlags(&c->present_stream, hipStreamNonBlocking));
-        }
+        // (each unless an earlier, refused attempt already left it)
+        if (!c->ev_presented) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_presented, hipEventDisableTiming));
+        if (!c->present_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->present_stream, hipStreamNonBlocking));
         HIP_TRY(c, hipEventRecord(c->ev_presented, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->present_stream, c->ev_presented, 0));
         copy_stream = c->present_stream;
@@ -266,7 +267,9 @@ int mrt_debug_present_encode(mrt_ctx* c, const float* rgba, uint32_t width, uint
     float* d_in = nullptr;
     uint8_t* d_out = nullptr;
     HIP_TRY(c, hipMalloc((void**)&d_in, n * 16));
-    hipError_t e = hipMalloc((void**)&d_out, n * 4);
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_present_encode";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_out, n * 4));
     if (e == hipSuccess) e = hipMemcpyAsync(d_in, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
         e = (hipError_t)mrt::launch_present(d_in, d_out, width, rows, (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u,
@@ -277,7 +280,7 @@ int mrt_debug_present_encode(mrt_ctx* c, const float* rgba, uint32_t width, uint
     if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
     (void)hipFree(d_in);
     if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_debug_present_encode failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     return MRT_OK;
 }
 

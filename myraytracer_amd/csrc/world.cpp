@@ -130,23 +130,23 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
     build_hierarchy(vec4 + 4 * w->spheres.center_base_idx, f32 + w->spheres.radius_base_idx, (uint32_t)n,
                     c->cluster_factor, c->max_levels, c->top_target, hier);
     const uint32_t n_padded = (uint32_t)hier.top.size();
-    auto upload = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
+        HIP_TRY(c, hipMalloc(dst, bytes ? bytes : 16));
+        if (bytes) HIP_TRY(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+        return MRT_OK;
     };
-    HIP_TRY(c, upload((void**)&c->d_spheres, recs.data(), recs.size() * sizeof(mrt::SphereRec)));
-    HIP_TRY(c, upload((void**)&c->d_clusters, hier.top.data(), hier.top.size() * sizeof(mrt::SphereRec)));
-    HIP_TRY(c, upload((void**)&c->d_nodes, hier.nodes.data(), hier.nodes.size() * sizeof(mrt::SphereRec)));
+    MRT_TRY(upload((void**)&c->d_spheres, recs.data(), recs.size() * sizeof(mrt::SphereRec)));
+    MRT_TRY(upload((void**)&c->d_clusters, hier.top.data(), hier.top.size() * sizeof(mrt::SphereRec)));
+    MRT_TRY(upload((void**)&c->d_nodes, hier.nodes.data(), hier.nodes.size() * sizeof(mrt::SphereRec)));
     if (hier.n_members > 1024u) {           // large scenes (the kernel's !SMALL layouts) walk the boxes
         std::vector<mrt::BoxFull> full;
         std::vector<mrt::BoxRec> dev;
         boxes_top_down(hier, false, full, &c->box_cluster_first, &c->box_cluster_parent_first);
         pack_boxes(full, dev);
-        HIP_TRY(c, upload((void**)&c->d_boxes, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
+        MRT_TRY(upload((void**)&c->d_boxes, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
         boxes_top_down(hier, true, full, &c->box_cluster_first, &c->box_cluster_parent_first);
         pack_boxes(full, dev);
-        HIP_TRY(c, upload((void**)&c->d_boxes_open, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
+        MRT_TRY(upload((void**)&c->d_boxes_open, dev.data(), dev.size() * sizeof(mrt::BoxRec)));
     }
     c->box_quad = hier.box_quad;
     c->box_kc = hier.box_kc;
@@ -155,7 +155,7 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         double max_c2 = 0.0, med_r2 = 0.0;
         size_t n_real = 0;
         build_top_mfma(hier.top, top_mfma, c->mfma_origin, &max_c2, &med_r2, &n_real);
-        HIP_TRY(c, upload((void**)&c->d_top_mfma, top_mfma.data(), top_mfma.size() * sizeof(uint16_t)));
+        MRT_TRY(upload((void**)&c->d_top_mfma, top_mfma.data(), top_mfma.size() * sizeof(uint16_t)));
         // The matrix-core sweep inflates R^2 by 2^-13 (o.o + C.C + R^2), o and C relative to mfma_origin; rays
         // start in or around the scene.
         // Selected where that stays below about a tenth of the typical R^2 (mrt_redraw checks the camera's
@@ -170,7 +170,7 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         }
         c->mfma_scene_ok = n_real >= 24 && med_r2 > 0.0 && kMfmaSlack * 2.0 * max_c2 <= 0.1 * med_r2;
     }
-    HIP_TRY(c, upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
+    MRT_TRY(upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
     // what shading a hit on sphere i reads, gathered per sphere (bit copies of the SoA entries)
     std::vector<float> shade(8 * ((size_t)n ? (size_t)n : 1), 0.0f);
     for (int64_t i = 0; i < n; i++) {
@@ -198,10 +198,10 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
             sh[7] = ior;
         }
     }
-    HIP_TRY(c, upload((void**)&c->d_shade, shade.data(), shade.size() * sizeof(float)));
-    HIP_TRY(c, upload((void**)&c->d_vec4, vec4, n_vec4 * 4 * sizeof(float)));
-    HIP_TRY(c, upload((void**)&c->d_f32, f32, n_f32 * sizeof(float)));
-    HIP_TRY(c, upload((void**)&c->d_i32, i32, n_i32 * sizeof(int32_t)));
+    MRT_TRY(upload((void**)&c->d_shade, shade.data(), shade.size() * sizeof(float)));
+    MRT_TRY(upload((void**)&c->d_vec4, vec4, n_vec4 * 4 * sizeof(float)));
+    MRT_TRY(upload((void**)&c->d_f32, f32, n_f32 * sizeof(float)));
+    MRT_TRY(upload((void**)&c->d_i32, i32, n_i32 * sizeof(int32_t)));
     for (auto& S : c->slot) S.cost_valid = false;
     c->width.div = 0;                   // (the launch-width controller starts over with the new workload)
     c->inputs_dirty = true;
@@ -266,14 +266,18 @@ int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_ou
     for (size_t i = n; i < n_pad; i++) std::memcpy(host_rays.data() + 6 * i, rays, 6 * sizeof(float));
     float* d_rays = nullptr; int32_t* d_hit = nullptr; uint32_t* d_cand = nullptr; uint32_t* d_queue = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_rays); (void)hipFree(d_hit); (void)hipFree(d_cand); (void)hipFree(d_queue); };
-    hipError_t e = hipMalloc((void**)&d_rays, host_rays.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_hit, n_pad * 2 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_cand, n_pad * words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_queue, 64);
+    hipError_t e = hipSuccess;
+    const char* what = "the upload";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_rays, host_rays.size() * sizeof(float)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_hit, n_pad * 2 * sizeof(int32_t)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_cand, n_pad * words * sizeof(uint32_t)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_queue, 64));
     if (e == hipSuccess) e = hipMemcpy(d_rays, host_rays.data(), host_rays.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cand, 0, n_pad * words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(d_hit, 0xFF, n_pad * 2 * sizeof(int32_t));
-    if (e != hipSuccess) { cleanup(); return fail(c, MRT_ERR_HIP, "mrt_debug_world_hit: %s", hipGetErrorString(e)); }
+    // (on the ctx's stream, which the launch follows: it is a non-blocking stream, so a memset on the null stream -- asynchronous
+    // for device memory -- could still be clearing these after the kernel has written them)
+    if (e == hipSuccess) e = hipMemsetAsync(d_cand, 0, n_pad * words * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_hit, 0xFF, n_pad * 2 * sizeof(int32_t), c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, MRT_ERR_HIP, "mrt_debug_world_hit: %s failed: %s", what, hipGetErrorString(e)); }
     mrt::KParams p;
     std::memset(&p, 0, sizeof p);
     p.locals = c->locals;

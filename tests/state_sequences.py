@@ -504,9 +504,22 @@ def _last_error(impl):
         return ""
 
 
+def check_context(label, impl):
+    """mrt_debug_check_context on a real State (host only): nothing a later call would touch is missing."""
+    L, ctx = getattr(impl, "_L", None), getattr(impl, "_ctx", None)
+    if L is None or not ctx or not hasattr(L, "mrt_debug_check_context"):
+        return          # (a model in the State's place: tests/test_state_model.py)
+    import ctypes
+    why = ctypes.create_string_buffer(512)
+    if L.mrt_debug_check_context(ctx, why, len(why)) != 0:
+        raise SequenceMismatch(f"{label}: the context is not sound after its sequence: {why.value.decode()}")
+
+
 def run(case, impl, model, stats=None, after=None):
-    """Applies case `case` to impl and model in lock step; raises SequenceMismatch at the first difference."""
+    """Applies case `case` to impl and model in lock step; raises SequenceMismatch at the first difference -- or if the
+    context is not sound after the last op."""
     run_ops(f"case {case}", sequence(case)[1], impl, model, stats, after)
+    check_context(f"case {case}", impl)
 
 
 def new_model(O, params, cls=None):

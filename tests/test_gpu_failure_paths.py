@@ -1,0 +1,97 @@
+"""The host library's resource-failure paths, by failure injection (include/myraytracer_amd.h, "after MRT_ERR_HIP": C1-C4).
+
+Each test starts ONE fresh child process (tests/failure_tour.py) against lib/libmyraytracer_amd_failinject.so -- the same
+sources with every creation / release of device memory, pinned memory, streams and events routed through a shim
+(tests/failinject/) -- with a time limit of its own.  The child walks N = 1 .. T once, refusing the N-th creation of a scripted
+tour that reaches every creation site, and logs one JSON line per case.  Nothing is provoked on the GPU: the shim says "no"
+without calling the runtime, and after a refusal mrt_debug_check_context (host only) must pass before anything is launched
+again.  If the child dies or runs into its limit the test fails with the last logged case; nothing is run a second time.
+
+The limits are three times what the walks took on an MI355X (profiles/failure_paths.txt)."""
+import json
+import os
+import subprocess
+import sys
+import time
+
+import pytest
+
+from failure_sites import ROOT
+
+pytestmark = pytest.mark.gpu
+
+TOUR = os.path.join(ROOT, "tests", "failure_tour.py")
+FI_LIB = os.path.join(ROOT, "myraytracer_amd", "lib", "libmyraytracer_amd_failinject.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "failure_sites.json")
+# 3 x what the child took on an MI355X, start-up included: about 4 s for the clean tour alone, + 24 s / + 49 s for the walks
+LIMIT_S = {"clean": 15, "destroy": 85, "continue": 160}
+
+
+def walk(mode, tmp_path):
+    assert os.path.exists(FI_LIB), "build the failure-injecting library first (make)"
+    log = tmp_path / f"{mode}.jsonl"
+    # the child alone loads the substituted library; twenty hardware queues, as the package asks for where the host sets none
+    env = dict(os.environ, MRT_LIB_OVERRIDE=FI_LIB, GPU_MAX_HW_QUEUES="20")
+
+    def records():
+        return [json.loads(line) for line in open(log)] if log.exists() else []
+
+    def last_case():
+        r = [x for x in records() if "n" in x]
+        return {k: v for k, v in r[-1].items() if k not in ("sites", "keys")} if r else "none"
+    t0 = time.time()
+    try:
+        p = subprocess.run([sys.executable, TOUR, "--mode", mode, "--log", str(log)], env=env, timeout=LIMIT_S[mode],
+                           capture_output=True, text=True, cwd=ROOT)
+    except subprocess.TimeoutExpired:
+        pytest.fail(f"the {mode} walk did not end within {LIMIT_S[mode]} s; last logged case: {last_case()} (find the cause there; not run again)")
+    print(f"{mode}: the child took {time.time() - t0:.1f} s of its {LIMIT_S[mode]} s")
+    recs = records()
+    if p.returncode not in (0, 1):
+        stopped = [r for r in recs if "stopped" in r]
+        pytest.fail(f"the {mode} walk's process ended with {p.returncode}; last logged case: {last_case()}; "
+                    f"{stopped[-1]['stopped'] if stopped else p.stderr[-2000:]}")
+    return recs
+
+
+def check(mode, recs):
+    clean = recs[0]
+    assert clean["mode"] == "clean" and clean["calls"] > 0
+    findings = [f"N={r.get('n', r.get('summary'))}: {f}" for r in recs for f in r.get("findings", [])]
+    assert not findings, f"{len(findings)} findings, the first of them:\n" + "\n".join(findings[:20])
+    golden = json.load(open(GOLDEN))["sites"]
+    assert clean["keys"] == sorted(golden), ("the clean tour's sites are not tests/golden/failure_sites.json: "
+                                             f"new {sorted(set(clean['keys']) - set(golden))}, gone {sorted(set(golden) - set(clean['keys']))}")
+    if mode == "clean":
+        return
+    T = clean["calls"]
+    cases = [r for r in recs if r.get("mode") == mode]
+    summary = [r for r in recs if r.get("summary") == mode]
+    assert [r["n"] for r in cases] == list(range(1, T + 1)), "the walk covers N = 1 .. T once, in order"
+    assert summary and summary[0]["first"] == 1 and summary[0]["last"] == T
+    reached = [r for r in cases if r["reached"]]
+    for r in cases:
+        if not r["reached"]:
+            print(f"N={r['n']}: not reached (the tour made {r['calls']} creator calls this time)")
+    # judged by sites: a refusal at every site of the clean run (the summary's findings, asserted above), most N reached
+    assert {r["site"] for r in reached} == set(clean["sites"])
+    assert len(reached) >= T - 64, f"only {len(reached)} of {T} cases reached their refusal"
+    print(f"{mode}: T = {T}, {len(clean['sites'])} sites, {len(reached)} refusals, clean tour {clean['seconds']} s, walk {summary[0]['seconds']} s")
+
+
+def test_clean_tour_reaches_the_recorded_sites_and_leaves_nothing(tmp_path):
+    """disarmed: every step succeeds, every creation site of tests/golden/failure_sites.json is seen, and after the last
+    mrt_destroy nothing is live and no release or copy was withheld (a leak on the SUCCESS path is caught here)"""
+    check("clean", walk("clean", tmp_path))
+
+
+def test_destroy_after_every_refusal_releases_everything(tmp_path):
+    """C1 and C2 for N = 1 .. T: the refused call returns MRT_ERR_HIP and names the runtime call; after mrt_destroy of every
+    context -- half-built ones of a failed mrt_create included -- the live counts are what they were, exactly"""
+    check("destroy", walk("destroy", tmp_path))
+
+
+def test_every_refused_call_can_be_repeated_and_nothing_differs_afterwards(tmp_path):
+    """C1-C4 for N = 1 .. T: sound after the refusal (mrt_debug_check_context), the same call succeeds when repeated, every
+    later observable is bit-identical to the clean run's, and nothing is live after the end"""
+    check("continue", walk("continue", tmp_path))
