@@ -93,6 +93,19 @@ int mrt_debug_build_boxes_top_down(const mrt_sphere* spheres, size_t n, uint32_t
  * -(1 - 2^-13) K^2, (4 reach)^2} with K the power of two for which |K oc.ds| <= 1/2 for every admitted ray, and
  * *neg_k2_bf16_pair_out = -K^2 as two bf16.  What mrt_redraw passes to the kernel (tests/test_host_logic.py). */
 int mrt_debug_mfma_scale(double reach, float scale_out[4], uint32_t* neg_k2_bf16_pair_out);
+/* Host-side diagnostic, no GPU needed: what mrt_set_world derives for the matrix-core sweep of a scene (default hierarchy
+ * parameters).  The sweep runs in the space x' = D (x - origin), D = diag(axis_out) with entries 1, 2 or 4 chosen from the
+ * spheres alone (force_axis != NULL: that D instead), so that flat clusters get small bounds.  records_out =
+ * n_top x (cx, cy, cz, -R^2): the bound of every top record in that space (never-hit: -R^2 = +inf); mfma_out: the A operand
+ * made from them, n_top / 32 x 512 bf16, laid out as mrt_debug_build_hierarchy describes -- for D = I the very operand that
+ * call returns; *reach_out = max over the spheres of |D (centre - origin)| + |radius| max D, the reach to pass to
+ * mrt_debug_mfma_scale.  Output pointers other than axis_out may be NULL; capacities in records / bf16 values. */
+int mrt_debug_build_sweep(const mrt_sphere* spheres, size_t n, const float* force_axis, float axis_out[3], float* records_out,
+                          size_t records_cap, uint16_t* mfma_out, size_t mfma_cap, float origin_out[3], double* reach_out);
+/* Diagnostic: the D of the NEXT mrt_set_world* call is axis[3] (entries 1, 2 or 4) instead of the scene's own choice; NULL
+ * returns to the choice.  mrt_debug_sweep_axes: the D of the current scene. */
+int mrt_debug_set_sweep_axes(mrt_ctx* ctx, const float* axis);
+int mrt_debug_sweep_axes(mrt_ctx* ctx, float axis_out[3]);
 /* Diagnostic: ONE world_hit (shader.wgsl:314-329, range [0.001, 1e4)) for each of n caller-supplied rays -- rays[6 i ..] =
  * origin xyz, direction xyz; directions of unit length to 1e-5, as every ray of the render loop is -- through the very sweep +
  * walk the render kernel runs (the same kernel, instantiated to take its rays from this array), with the current scene,

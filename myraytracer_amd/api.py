@@ -388,6 +388,18 @@ class State:
         """Tuning / test hook: 0 = automatic, 1 = SGPR-fed VALU sweep, 2 = matrix-core sweep (same image either way)."""
         self._check(self._L.mrt_debug_set_sweep(self._ctx, mode), "mrt_debug_set_sweep")
 
+    def debug_set_sweep_axes(self, axis=None):
+        """Tuning / test hook: the matrix-core sweep of the scene of the next set_world() runs in the space scaled by axis (three
+        of 1, 2, 4) instead of the one chosen for the scene; None returns to the choice.  Same image either way."""
+        arr = (C.c_float * 3)(*axis) if axis is not None else None
+        self._check(self._L.mrt_debug_set_sweep_axes(self._ctx, arr), "mrt_debug_set_sweep_axes")
+
+    def debug_sweep_axes(self):
+        """The axis scales of the space the current scene's matrix-core sweep runs in ((1, 1, 1): the world's)."""
+        arr = (C.c_float * 3)()
+        self._check(self._L.mrt_debug_sweep_axes(self._ctx, arr), "mrt_debug_sweep_axes")
+        return tuple(float(v) for v in arr)
+
     def debug_sweep_variant(self) -> int:
         """1 = SGPR-fed VALU sweep, 2 = matrix-core sweep, for the next redraw (0 before a scene is set)."""
         return int(self._L.mrt_debug_sweep_variant(self._ctx))

@@ -394,6 +394,18 @@ void build_hierarchy(const float* centers4, const float* radii, uint32_t n, floa
     build_boxes(centers4, radii, members, H);
 }
 
+// the GEMMs of the matrix-core sweep run in coordinates relative to the centre of the records' bounding box (the slack grows
+// with the squared distances from THAT point, wherever the scene sits); the kernel subtracts it from the ray origin
+static void sweep_origin(const std::vector<mrt::SphereRec>& top, float origin[3]) {
+    double lo[3] = {1e300, 1e300, 1e300}, hi3[3] = {-1e300, -1e300, -1e300};
+    for (const auto& r : top) {
+        if (!std::isfinite(r.neg_r2)) continue;
+        const double c[3] = {r.cx, r.cy, r.cz};
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], c[k]); hi3[k] = std::max(hi3[k], c[k]); }
+    }
+    for (int k = 0; k < 3; k++) origin[k] = lo[k] <= hi3[k] ? (float)(0.5 * (lo[k] + hi3[k])) : 0.0f;
+}
+
 // The top level once more, as the A operand of the matrix-core sweep (kernels.hip, mfma_sweep_tile): per
 // tile of 32 records 64 lanes x 8 bf16, lane l = row (l & 31), k = 8 (l >> 5) + j:
 //     k 0..2 C_hi, 3..5 C_hi, 6..8 C_lo, 9..11 (1,1,1), 12..14 Ck (hi, mid, lo), 15: 0
@@ -403,29 +415,18 @@ void build_hierarchy(const float* centers4, const float* radii, uint32_t n, floa
 // split drops.  A never-hit record gets Ck = 3e38 (finite: an infinity would turn the other
 // GEMM's 0 x Ck into NaN).  Also returns what set_world needs to decide whether the slack is negligible:
 // the largest C.C and the median R^2.
-void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t>& out, float origin[3], double* max_c2,
-                    double* med_r2, size_t* n_real) {
-    const size_t tiles = top.size() / 32;
+// `rel`: the records relative to the sweep's origin, in the top level's order (build_top_mfma, build_sweep_operand).
+static void pack_top_mfma(const std::vector<mrt::SphereRec>& rel, std::vector<uint16_t>& out, double* max_c2, double* med_r2, size_t* n_real) {
+    const size_t tiles = rel.size() / 32;
     out.assign(tiles * 512, 0);
     std::vector<double> r2s;
     *max_c2 = 0.0;
-    // the GEMMs run in coordinates relative to the centre of the records' bounding box (the slack grows with the
-    // squared distances from THAT point, wherever the scene sits); the kernel subtracts it from the ray origin
-    double lo[3] = {1e300, 1e300, 1e300}, hi3[3] = {-1e300, -1e300, -1e300};
-    for (const auto& r : top) {
-        if (!std::isfinite(r.neg_r2)) continue;
-        const double c[3] = {r.cx, r.cy, r.cz};
-        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], c[k]); hi3[k] = std::max(hi3[k], c[k]); }
-    }
-    for (int k = 0; k < 3; k++) origin[k] = lo[k] <= hi3[k] ? (float)(0.5 * (lo[k] + hi3[k])) : 0.0f;
     const uint16_t one = bf16_rne(1.0f);
     for (size_t t = 0; t < tiles; t++)
         for (uint32_t m = 0; m < 32; m++) {
-            const mrt::SphereRec& r = top[32 * t + 16 * ((m >> 2) & 1u) + 4 * (m >> 3) + (m & 3u)];
+            const mrt::SphereRec& r = rel[32 * t + 16 * ((m >> 2) & 1u) + 4 * (m >> 3) + (m & 3u)];
             float ck = 3.0e38f;
-            // centre relative to the origin: exact in double, then rounded to f32 -- the rounding moves the bound by
-            // at most 2 eps |c|, which its radius absorbs
-            const float c[3] = {(float)((double)r.cx - origin[0]), (float)((double)r.cy - origin[1]), (float)((double)r.cz - origin[2])};
+            const float c[3] = {r.cx, r.cy, r.cz};
             if (std::isfinite(r.neg_r2)) {
                 const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
                 const double R = std::sqrt(-(double)r.neg_r2) + 2.0 * 0x1p-24 * std::sqrt(c2), R2 = R * R;
@@ -449,6 +450,187 @@ void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t
     if (!r2s.empty()) { std::nth_element(r2s.begin(), r2s.begin() + r2s.size() / 2, r2s.end()); *med_r2 = r2s[r2s.size() / 2]; }
 }
 
+// the world-space top records relative to the origin: exact in double, then rounded to f32 -- the rounding moves a bound by at
+// most 2 eps |c|, which its radius absorbs (pack_top_mfma)
+static void relative_records(const std::vector<mrt::SphereRec>& top, const float origin[3], std::vector<mrt::SphereRec>& rel) {
+    rel.resize(top.size());
+    for (size_t i = 0; i < top.size(); i++) {
+        const mrt::SphereRec& r = top[i];
+        rel[i] = mrt::SphereRec{(float)((double)r.cx - origin[0]), (float)((double)r.cy - origin[1]), (float)((double)r.cz - origin[2]), r.neg_r2};
+    }
+}
+
+void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t>& out, float origin[3], double* max_c2,
+                    double* med_r2, size_t* n_real) {
+    sweep_origin(top, origin);
+    std::vector<mrt::SphereRec> rel;
+    relative_records(top, origin, rel);
+    pack_top_mfma(rel, out, max_c2, med_r2, n_real);
+}
+
+// The sweep's own space: x' = D (x - origin), D = diag(axis), every entry 1, 2 or 4.  A line that meets a
+// member sphere meets, in that space, the scaled member -- an ellipsoid with the semi-axes r D -- hence any sphere that
+// encloses the scaled members of its cluster, and flat clusters get much smaller spheres there.  rel[j] = such a sphere for
+// top record j, from the member spheres under it: centre = centre of the scaled members' common box, rounded to f32; radius =
+// kBoundInflate x the largest distance from THAT point to a point of a scaled member.  That distance, max |p + r D u| over
+// unit u, is the minimum over lambda > max (r D_k)^2 of lambda + sum_k p_k^2 lambda / (lambda - (r D_k)^2) (Lagrange
+// dual; EVERY lambda gives an upper bound, so the search below cannot make the result too small), never above the two
+// plain bounds |p| + r max D and |(|p_k| + r D_k)_k|.  Returns false where the proof of DESIGN.md §4 does not hold
+// for this D: a line that the reference's rounded discriminant accepts passes a member of radius r by up to 7 eps |oc|^2 / r, which
+// max D stretches; the direction's stretch pays for that only while max D E / r + (max D)^2 <= 36 (E the enclosing radius).
+constexpr double kScaledMarginBudget = 36.0;
+static bool scaled_top_records(const Hierarchy& H, const float axis[3], const float origin[3], std::vector<mrt::SphereRec>& rel) {
+    const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
+    const size_t span = (size_t)1 << (2 * H.levels), n_hier = std::min((size_t)H.direct_first, H.nodes.size());
+    const double D[3] = {axis[0], axis[1], axis[2]}, dmax = std::max(D[0], std::max(D[1], D[2]));
+    rel.assign(H.top.size(), never);
+    bool proven = true;
+    for (size_t j = 0; j < H.top.size(); j++) {
+        const size_t m0 = std::min(n_hier, j * span), m1 = std::min(n_hier, (j + 1) * span);
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, r_min = 1e300;
+        for (size_t m = m0; m < m1; m++) {
+            const mrt::SphereRec& s = H.nodes[m];
+            if (!std::isfinite(s.neg_r2)) continue;
+            const double r = std::sqrt(-(double)s.neg_r2) * (1.0 + 0x1p-22), c[3] = {s.cx, s.cy, s.cz};     // (-(r r) was rounded to f32)
+            for (int k = 0; k < 3; k++) {
+                const double ck = D[k] * (c[k] - origin[k]);
+                lo[k] = std::min(lo[k], ck - r * D[k]);
+                hi[k] = std::max(hi[k], ck + r * D[k]);
+            }
+            r_min = std::min(r_min, r);
+        }
+        if (!(lo[0] <= hi[0])) continue;
+        float ctr[3];
+        for (int k = 0; k < 3; k++) ctr[k] = (float)(0.5 * (lo[k] + hi[k]));
+        double E = 0.0;
+        for (size_t m = m0; m < m1; m++) {
+            const mrt::SphereRec& s = H.nodes[m];
+            if (!std::isfinite(s.neg_r2)) continue;
+            const double r = std::sqrt(-(double)s.neg_r2) * (1.0 + 0x1p-22), c[3] = {s.cx, s.cy, s.cz};
+            double p2[3], a2[3], pn = 0.0, box = 0.0, a2max = 0.0;
+            for (int k = 0; k < 3; k++) {
+                const double pk = D[k] * (c[k] - origin[k]) - (double)ctr[k], ak = r * D[k];
+                p2[k] = pk * pk; a2[k] = ak * ak;
+                pn += p2[k]; box += (std::fabs(pk) + ak) * (std::fabs(pk) + ak); a2max = std::max(a2max, a2[k]);
+            }
+            double best = std::min(std::sqrt(pn) + r * dmax, std::sqrt(box));
+            best *= best;
+            auto dual = [&](double x) {                   // lambda = a2max + x
+                const double l = a2max + x;
+                double v = l;
+                for (int k = 0; k < 3; k++) v += p2[k] * l / (l - a2[k]);
+                return v;
+            };
+            // convex in lambda: ternary search over x = lambda - a2max on a logarithmic axis
+            double xl = std::log(1e-9 * (a2max + pn) + 1e-300), xh = std::log(4.0 * (a2max + pn) + 1e-300);
+            for (int it = 0; it < 80; it++) {
+                const double x1 = xl + (xh - xl) / 3.0, x2 = xh - (xh - xl) / 3.0;
+                if (dual(std::exp(x1)) < dual(std::exp(x2))) xh = x2; else xl = x1;
+            }
+            const double v = dual(std::exp(0.5 * (xl + xh)));
+            if (std::isfinite(v) && v < best) best = v;
+            E = std::max(E, std::sqrt(best) * (1.0 + 1e-12));
+        }
+        if (!(r_min > 0.0) || dmax * E / r_min + dmax * dmax > kScaledMarginBudget) proven = false;
+        const float Rf = (float)(E * mrt::kBoundInflate) + 1e-30f;
+        rel[j] = mrt::SphereRec{ctr[0], ctr[1], ctr[2], -(Rf * Rf)};
+    }
+    return proven;
+}
+
+// D for a scene (mrt_set_world_raw): the candidates -- one axis scaled by 2 or by 4 -- are scored by how many bounds a fixed,
+// seeded set of lines through the box of the clustered spheres meets (half of them through two points of the box, which
+// favours the grazing directions a camera beside a flat scene produces; half through one point in a uniformly random
+// direction, as scattered rays run), against the world-space records' count.  The set only steers the choice: any D is
+// correct.  It depends on the spheres alone, never on the camera.  D = I unless the best candidate meets at least 5 % fewer
+// bounds, its proof holds (scaled_top_records) and the sweep's give-away stays as negligible in its space as the scene test of
+// mrt_set_world_raw demands.  One-level hierarchies only: the walk of larger scenes has its boxes.
+static void choose_sweep_axes(const Hierarchy& H, const float origin[3], float axis[3]) {
+    axis[0] = axis[1] = axis[2] = 1.0f;
+    if (H.levels != 1) return;
+    const size_t n_hier = std::min((size_t)H.direct_first, H.nodes.size());
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (size_t m = 0; m < n_hier; m++) {
+        const mrt::SphereRec& s = H.nodes[m];
+        if (!std::isfinite(s.neg_r2)) continue;
+        const double r = std::sqrt(-(double)s.neg_r2), c[3] = {s.cx, s.cy, s.cz};
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], c[k] - r); hi[k] = std::max(hi[k], c[k] + r); }
+    }
+    if (!(lo[0] <= hi[0])) return;
+    constexpr int kLines = 4096;
+    std::vector<double> lines(6 * kLines);
+    uint64_t state = 0x9E3779B97F4A7C15ull;
+    auto uniform = [&]() {                              // splitmix64 -> [0, 1)
+        uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return (double)((z ^ (z >> 31)) >> 11) * 0x1p-53;
+    };
+    for (int i = 0; i < kLines; i++) {
+        double* L = lines.data() + 6 * i;
+        for (int k = 0; k < 3; k++) L[k] = lo[k] + uniform() * (hi[k] - lo[k]);
+        if (i & 1) {
+            for (int k = 0; k < 3; k++) L[3 + k] = lo[k] + uniform() * (hi[k] - lo[k]) - L[k];
+        } else {
+            const double z = 2.0 * uniform() - 1.0, phi = 6.283185307179586 * uniform(), q = std::sqrt(1.0 - z * z);
+            L[3] = q * std::cos(phi); L[4] = q * std::sin(phi); L[5] = z;
+        }
+        if (L[3] * L[3] + L[4] * L[4] + L[5] * L[5] < 1e-300) L[3] = 1.0;
+    }
+    auto score = [&](const std::vector<mrt::SphereRec>& rel, const float ax[3]) {
+        size_t met = 0;
+        for (int i = 0; i < kLines; i++) {
+            const double* L = lines.data() + 6 * i;
+            double p[3], u[3], uu = 0.0;
+            for (int k = 0; k < 3; k++) { p[k] = ax[k] * (L[k] - origin[k]); u[k] = ax[k] * L[3 + k]; uu += u[k] * u[k]; }
+            for (const auto& r : rel) {
+                if (!std::isfinite(r.neg_r2)) continue;
+                const double w[3] = {p[0] - r.cx, p[1] - r.cy, p[2] - r.cz};
+                const double b = w[0] * u[0] + w[1] * u[1] + w[2] * u[2];
+                if (w[0] * w[0] + w[1] * w[1] + w[2] * w[2] - b * b / uu <= -(double)r.neg_r2) met++;
+            }
+        }
+        return met;
+    };
+    std::vector<mrt::SphereRec> rel;
+    relative_records(H.top, origin, rel);
+    const size_t base = score(rel, axis);
+    size_t best = base;
+    for (int k = 0; k < 3; k++)
+        for (float s : {2.0f, 4.0f}) {
+            float ax[3] = {1.0f, 1.0f, 1.0f};
+            ax[k] = s;
+            if (!scaled_top_records(H, ax, origin, rel)) continue;
+            double max_c2 = 0.0;
+            std::vector<double> r2s;
+            for (const auto& r : rel) {
+                if (!std::isfinite(r.neg_r2)) continue;
+                max_c2 = std::max(max_c2, (double)r.cx * r.cx + (double)r.cy * r.cy + (double)r.cz * r.cz);
+                r2s.push_back(-(double)r.neg_r2);
+            }
+            if (r2s.empty()) continue;
+            std::nth_element(r2s.begin(), r2s.begin() + r2s.size() / 2, r2s.end());
+            if (!(kMfmaSlack * 2.0 * max_c2 <= 0.1 * r2s[r2s.size() / 2])) continue;
+            const size_t met = score(rel, ax);
+            if (met < best) { best = met; for (int q = 0; q < 3; q++) axis[q] = ax[q]; }
+        }
+    if (!((double)best <= 0.95 * (double)base)) axis[0] = axis[1] = axis[2] = 1.0f;
+}
+
+// the sweep's A operand, origin and D for a scene (`force`: a caller's D instead of the choice; diagnostics): the world-space top
+// records for D = I (build_top_mfma, bit for bit), the records of scaled_top_records otherwise
+void build_sweep_operand(const Hierarchy& H, const float* force, float axis[3], std::vector<uint16_t>& out, float origin[3],
+                         double* max_c2, double* med_r2, size_t* n_real, std::vector<mrt::SphereRec>* rel_out) {
+    sweep_origin(H.top, origin);
+    if (force) for (int k = 0; k < 3; k++) axis[k] = force[k];
+    else choose_sweep_axes(H, origin, axis);
+    std::vector<mrt::SphereRec> rel;
+    if (axis[0] == 1.0f && axis[1] == 1.0f && axis[2] == 1.0f) relative_records(H.top, origin, rel);
+    else (void)scaled_top_records(H, axis, origin, rel);
+    pack_top_mfma(rel, out, max_c2, med_r2, n_real);
+    if (rel_out) rel_out->swap(rel);
+}
+
 // KParams::mfma_scale / mfma_neg_k2_pair for rays and records within `all` of the sweep's origin (mrt_debug_mfma_scale)
 void mfma_scales(double all, float scale[4], uint32_t* neg_k2_pair) {
     if (!(all > 1e-30)) all = 1.0;
@@ -463,9 +645,22 @@ void mfma_scales(double all, float scale[4], uint32_t* neg_k2_pair) {
     *neg_k2_pair = nk2 | (nk2 << 16);
 }
 
+// max over ALL spheres of |D (centre - origin)| + |radius| max D: no hit point lies further from the origin in the sweep's space
+double sweep_reach(const float* centers4, const float* radii, uint32_t n, const float origin[3], const float axis[3]) {
+    const double dmax = std::max(axis[0], std::max(axis[1], axis[2]));
+    double reach = 0.0;
+    for (uint32_t i = 0; i < n; i++) {
+        double d2 = 0.0;
+        for (int k = 0; k < 3; k++) { const double d = (double)axis[k] * ((double)centers4[4 * i + k] - (double)origin[k]); d2 += d * d; }
+        reach = std::max(reach, std::sqrt(d2) + std::fabs((double)radii[i]) * dmax);
+    }
+    return reach;
+}
+
+
 }  // namespace mrt
 
-using mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::boxes_top_down, mrt::pack_boxes, mrt::mfma_scales;
+using mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::build_sweep_operand, mrt::boxes_top_down, mrt::pack_boxes, mrt::mfma_scales;
 
 extern "C" {
 
@@ -499,6 +694,34 @@ int mrt_debug_build_hierarchy(const mrt_sphere* spheres, size_t n, uint32_t max_
     if (member_index_out) std::memcpy(member_index_out, h.member_index.data(), h.member_index.size() * sizeof(uint32_t));
     if (mfma_out) std::memcpy(mfma_out, mf.data(), mf.size() * sizeof(uint16_t));
     if (mfma_origin_out) for (int k = 0; k < 3; k++) mfma_origin_out[k] = origin[k];
+    return MRT_OK;
+}
+
+int mrt_debug_build_sweep(const mrt_sphere* spheres, size_t n, const float* force_axis, float axis_out[3], float* records_out,
+                          size_t records_cap, uint16_t* mfma_out, size_t mfma_cap, float origin_out[3], double* reach_out) {
+    if ((!spheres && n) || !axis_out || n > mrt::kMaxSpheres) return MRT_ERR_INVALID_ARG;
+    if (force_axis)
+        for (int k = 0; k < 3; k++)
+            if (force_axis[k] != 1.0f && force_axis[k] != 2.0f && force_axis[k] != 4.0f) return MRT_ERR_INVALID_ARG;
+    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+        centers[4 * i + 3] = 1.0f;
+        radii[i] = spheres[i].radius;
+    }
+    Hierarchy h;
+    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, mrt::kMaxLevels, 0, h);
+    std::vector<uint16_t> mf;
+    std::vector<mrt::SphereRec> rel;
+    float origin[3];
+    double max_c2, med_r2;
+    size_t n_real;
+    build_sweep_operand(h, force_axis, axis_out, mf, origin, &max_c2, &med_r2, &n_real, &rel);
+    if ((records_out && records_cap < rel.size()) || (mfma_out && mfma_cap < mf.size())) return MRT_ERR_TOO_SMALL;
+    if (records_out) std::memcpy(records_out, rel.data(), rel.size() * sizeof(mrt::SphereRec));
+    if (mfma_out) std::memcpy(mfma_out, mf.data(), mf.size() * sizeof(uint16_t));
+    if (origin_out) for (int k = 0; k < 3; k++) origin_out[k] = origin[k];
+    if (reach_out) *reach_out = mrt::sweep_reach(centers.data(), radii.data(), (uint32_t)n, origin, axis_out);
     return MRT_OK;
 }
 

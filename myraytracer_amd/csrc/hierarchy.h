@@ -41,5 +41,11 @@ void pack_boxes(const std::vector<BoxFull>& full, std::vector<BoxRec>& out);
 void build_top_mfma(const std::vector<SphereRec>& top, std::vector<uint16_t>& out, float origin[3], double* max_c2,
                     double* med_r2, size_t* n_real);
 void mfma_scales(double all, float scale[4], uint32_t* neg_k2_pair);
+// The space the matrix-core sweep of a scene runs in: x' = D (x - origin), D = diag(axis) with entries 1, 2 or 4 chosen from
+// the spheres alone (`force`: a caller's D instead), and the A operand of the top level's bounds in that space -- for D = I
+// exactly what build_top_mfma gives.  rel_out: those bounds as records.  sweep_reach: how far the spheres reach there.
+void build_sweep_operand(const Hierarchy& H, const float* force, float axis[3], std::vector<uint16_t>& out, float origin[3],
+                         double* max_c2, double* med_r2, size_t* n_real, std::vector<SphereRec>* rel_out);
+double sweep_reach(const float* centers4, const float* radii, uint32_t n, const float origin[3], const float axis[3]);
 
 }  // namespace mrt

@@ -572,12 +572,23 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // (matrix-core sweep: so does an origin further from the scene than the sweep's scaling admits -- 4 x the
             // distance of the camera or of the farthest sphere surface, world.cpp: no ray of a frame, but a caller's ray
             // under mrt_debug_world_hit may be)
-            const V3 o_rel = MFMA ? v3(o.x - P.mfma_origin[0], o.y - P.mfma_origin[1], o.z - P.mfma_origin[2]) : o;
+            // (a scene whose sweep runs in a scaled space, x' = D (x - origin) with D = diag(P.mfma_axis) of powers of two -- flat
+            // clusters get small bounds there, hierarchy.cpp -- hands the GEMMs the scaled ray: o' = D o_rel and D d, both exact,
+            // the latter brought back to unit length (one v_rsq_f32: to a few ulp, far inside the 1e-5 the test's proof asks of a
+            // direction) before the stretch; the admission test is on o'.o'.  The sign of the test and the order of the line's
+            // points do not change with the positive factor.  Wave-uniform: D = I scenes run none of it.)
+            V3 o_rel = MFMA ? v3(o.x - P.mfma_origin[0], o.y - P.mfma_origin[1], o.z - P.mfma_origin[2]) : o;
+            const float stretch = MFMA ? P.mfma_scale[0] : kBoundStretch;
+            V3 ds = v3(d.x * stretch, d.y * stretch, d.z * stretch);
+            if (MFMA && P.mfma_scaled != 0u) {
+                o_rel = v3(o_rel.x * P.mfma_axis[0], o_rel.y * P.mfma_axis[1], o_rel.z * P.mfma_axis[2]);
+                const V3 dd = v3(d.x * P.mfma_axis[0], d.y * P.mfma_axis[1], d.z * P.mfma_axis[2]);
+                const float unit = __builtin_amdgcn_rsqf(dot3(dd, dd)) * stretch;
+                ds = v3(dd.x * unit, dd.y * unit, dd.z * unit);
+            }
             const float o_rel2 = MFMA ? dot3(o_rel, o_rel) : 0.0f;
             const bool weird = !(a > 0.99999f && a < 1.00001f) || (MFMA && !(o_rel2 <= P.mfma_scale[3]));
             const bool usable = trace && !weird;
-            const float stretch = MFMA ? P.mfma_scale[0] : kBoundStretch;
-            const V3 ds = v3(d.x * stretch, d.y * stretch, d.z * stretch);
             // The few spheres far larger than the rest (a ground sphere) are outside the hierarchy: every ray does
             // sphere_hit (shader.wgsl:274-296) on them itself, record in SGPRs -- discriminant, and for lanes with
             // disc >= 0 (and the sphere not entirely behind the origin: see the node rounds) the roots and range tests

@@ -34,6 +34,11 @@ struct mrt_ctx {
     double mfma_r2_ref = 0.0;              // median R^2 of the top level (camera check at launch)
     float mfma_origin[3] = {0.0f, 0.0f, 0.0f};   // the matrix-core sweep works in coordinates relative to this point
     double mfma_reach = 0.0;                      // max over ALL spheres of |centre - mfma_origin| + |radius|: no hit point lies further out
+    // the sweep's space: x' = mfma_axis (x - mfma_origin) per component, entries 1, 2 or 4 (hierarchy.cpp, build_sweep_operand);
+    // mfma_r2_ref and mfma_reach are measured there.  force_axis: the next scene's D is the caller's (mrt_debug_set_sweep_axes)
+    float mfma_axis[3] = {1.0f, 1.0f, 1.0f};
+    float force_axis[3] = {1.0f, 1.0f, 1.0f};
+    bool have_force_axis = false;
     int sweep_mode = 0;                    // 0 automatic, 1 SGPR-fed VALU sweep, 2 matrix-core sweep (mrt_debug_set_sweep)
     float* d_shade = nullptr;              // 8 floats per sphere: centre, radius, material colour, fuzz | ior
     mrt::SphereRec* d_nodes = nullptr;     // hierarchy levels below the top: members (kClusterK per cluster), clusters, ...

@@ -71,6 +71,11 @@ struct KParams {
     // |o - mfma_origin|^2}, and -K^2 as a pair of bf16 (kernels.hip, mfma_ray_operands)
     float mfma_scale[4];
     uint32_t mfma_neg_k2_pair;
+    // The sweep's space: the GEMMs see x' = mfma_axis (x - mfma_origin) per component, entries 1, 2 or 4 chosen per scene so
+    // that flat clusters get small bounds (hierarchy.cpp, build_sweep_operand); top_mfma, mfma_scale and mfma_neg_k2_pair are
+    // made for that space.  mfma_scaled = some entry is not 1: only then the kernel scales its rays.
+    float mfma_axis[3];
+    uint32_t mfma_scaled;
     const SphereRec* nodes;
     const uint32_t* member_index;
     uint32_t levels, n_nodes, n_members, gen_cap;

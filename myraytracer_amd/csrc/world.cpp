@@ -7,7 +7,7 @@
 #include "mrt_ctx.h"
 #include "hierarchy.h"
 
-using mrt::fail, mrt::free_world, mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::boxes_top_down, mrt::pack_boxes, mrt::kMfmaSlack, mrt::fill_scene_params;
+using mrt::fail, mrt::free_world, mrt::Hierarchy, mrt::build_hierarchy, mrt::build_sweep_operand, mrt::boxes_top_down, mrt::pack_boxes, mrt::kMfmaSlack, mrt::fill_scene_params;
 
 namespace {
 
@@ -18,9 +18,9 @@ bool finite_in_range(float v, float lim) { return std::isfinite(v) && std::fabs(
 bool use_matrix_core_sweep(const mrt_ctx* c) {
     if (c->sweep_mode == 2) return true;
     if (c->sweep_mode == 1 || !c->mfma_scene_ok) return false;
-    double o2 = 0.0;                              // squared distance of the camera from the GEMMs' origin
+    double o2 = 0.0;                              // squared distance of the camera from the GEMMs' origin, in the sweep's space
     for (int k = 0; k < 3; k++) {
-        const double d = (c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k];
+        const double d = (double)c->mfma_axis[k] * ((c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k]);
         o2 += d * d;
     }
     return kMfmaSlack * o2 <= 0.1 * c->mfma_r2_ref;
@@ -43,14 +43,20 @@ void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
         // The sweep squares K oc.ds through an instruction that saturates at 1 (kernels.hip, mfma_sweep_tile), K a power of
         // two: rays start on the camera's lens or on a sphere, i.e. within `all` of mfma_origin; the sweep admits origins up
         // to 4 x that (others take the literal loop), records lie within `all`, |ds| < 1.001: |K oc.ds| < 5.01 all K <= 1/2.
+        // All of it in the sweep's space, x' = mfma_axis (x - mfma_origin): that is where the GEMMs run.
         double cam_d2 = 0.0, lens = 0.0;
         for (int k = 0; k < 3; k++) {
-            const double d = (c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k];
+            p.mfma_axis[k] = c->mfma_axis[k];
+            const double d = (double)c->mfma_axis[k] * ((c->cam_raw.mode ? (double)c->cam_raw.origin[k] : 0.0) - (double)c->mfma_origin[k]);
             cam_d2 += d * d;
         }
+        p.mfma_scaled = (c->mfma_axis[0] != 1.0f || c->mfma_axis[1] != 1.0f || c->mfma_axis[2] != 1.0f) ? 1u : 0u;
         if (c->cam_raw.mode) {
             double u2 = 0.0, v2 = 0.0;
-            for (int k = 0; k < 3; k++) { u2 += (double)c->cam_raw.ru[k] * c->cam_raw.ru[k]; v2 += (double)c->cam_raw.rv[k] * c->cam_raw.rv[k]; }
+            for (int k = 0; k < 3; k++) {
+                const double u = (double)c->mfma_axis[k] * c->cam_raw.ru[k], v = (double)c->mfma_axis[k] * c->cam_raw.rv[k];
+                u2 += u * u; v2 += v * v;
+            }
             lens = std::sqrt(u2) + std::sqrt(v2);
         }
         mfma_scales(std::max(c->mfma_reach, std::sqrt(cam_d2) + lens), p.mfma_scale, &p.mfma_neg_k2_pair);
@@ -154,20 +160,16 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         std::vector<uint16_t> top_mfma;
         double max_c2 = 0.0, med_r2 = 0.0;
         size_t n_real = 0;
-        build_top_mfma(hier.top, top_mfma, c->mfma_origin, &max_c2, &med_r2, &n_real);
+        build_sweep_operand(hier, c->have_force_axis ? c->force_axis : nullptr, c->mfma_axis, top_mfma, c->mfma_origin, &max_c2,
+                            &med_r2, &n_real, nullptr);
         MRT_TRY(upload((void**)&c->d_top_mfma, top_mfma.data(), top_mfma.size() * sizeof(uint16_t)));
-        // The matrix-core sweep inflates R^2 by 2^-13 (o.o + C.C + R^2), o and C relative to mfma_origin; rays
-        // start in or around the scene.
+        // The matrix-core sweep inflates R^2 by 2^-13 (o.o + C.C + R^2), o and C relative to mfma_origin in the sweep's
+        // space (x' = mfma_axis (x - mfma_origin)); rays start in or around the scene.
         // Selected where that stays below about a tenth of the typical R^2 (mrt_redraw checks the camera's
         // own distance the same way) and there are enough records to fill most of a 32-record tile.
         c->mfma_r2_ref = med_r2;
-        c->mfma_reach = 0.0;
-        for (int64_t i = 0; i < n; i++) {
-            const float* ctr = vec4 + 4 * (w->spheres.center_base_idx + i);
-            double d2 = 0.0;
-            for (int k = 0; k < 3; k++) { const double d = (double)ctr[k] - (double)c->mfma_origin[k]; d2 += d * d; }
-            c->mfma_reach = std::max(c->mfma_reach, std::sqrt(d2) + std::fabs((double)f32[w->spheres.radius_base_idx + i]));
-        }
+        c->mfma_reach = mrt::sweep_reach(vec4 + 4 * w->spheres.center_base_idx, f32 + w->spheres.radius_base_idx, (uint32_t)n,
+                                         c->mfma_origin, c->mfma_axis);
         c->mfma_scene_ok = n_real >= 24 && med_r2 > 0.0 && kMfmaSlack * 2.0 * max_c2 <= 0.1 * med_r2;
     }
     MRT_TRY(upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
@@ -239,6 +241,23 @@ int mrt_set_world(mrt_ctx* c, const mrt_sphere* spheres, size_t n) {
 int mrt_debug_set_cluster_factor(mrt_ctx* c, float factor) {
     if (!c || !(factor >= 0.0f)) return MRT_ERR_INVALID_ARG;
     c->cluster_factor = factor;
+    return MRT_OK;
+}
+
+int mrt_debug_set_sweep_axes(mrt_ctx* c, const float* axis) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (axis)
+        for (int k = 0; k < 3; k++)
+            if (axis[k] != 1.0f && axis[k] != 2.0f && axis[k] != 4.0f) return MRT_ERR_INVALID_ARG;
+    c->have_force_axis = axis != nullptr;
+    for (int k = 0; k < 3; k++) c->force_axis[k] = axis ? axis[k] : 1.0f;
+    return MRT_OK;
+}
+
+int mrt_debug_sweep_axes(mrt_ctx* c, float axis_out[3]) {
+    if (!c || !axis_out) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_sweep_axes: no scene");
+    for (int k = 0; k < 3; k++) axis_out[k] = c->mfma_axis[k];
     return MRT_OK;
 }
 
