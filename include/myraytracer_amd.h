@@ -39,8 +39,8 @@ extern "C" {
  * device-side present pass (mrt_present, mrt_present_acquire, mrt_present_release, mrt_set_present_ring, mrt_present_info);
  * the noise estimate (mrt_set_noise_tracking, mrt_noise_query, mrt_noise_result, mrt_read_noise, mrt_read_noise_tiles,
  * mrt_noise_factor, mrt_noise_report); the denoiser (mrt_denoise_params, mrt_denoise_params_default, mrt_set_denoise_params,
- * mrt_get_denoise_params, mrt_read_denoised, MRT_PRESENT_DENOISED); adaptive sampling (mrt_render_tiles, mrt_render_adaptive,
- * mrt_read_tile_frames). */
+ * mrt_get_denoise_params, mrt_set_denoise_variance, mrt_get_denoise_variance, mrt_read_denoised, MRT_PRESENT_DENOISED);
+ * adaptive sampling (mrt_render_tiles, mrt_render_adaptive, mrt_read_tile_frames). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -469,7 +469,29 @@ int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tile
  *     w          = ((((k_x * k_y) * w_lum) * w_normal) * w_depth) * w_albedo;  the centre tap: k_2 * k_2 = 9/64, no stops
  *     c'  = sum w c_q / sum w,   var' = sum (w * w) var_q / (sum w * sum w)     (sums in tap order, from 0)
  * Passed through unchanged (c and var): a texel that is not finite, and -- K finite only -- a texel whose var is 0.  K = +inf (fewer
- * than 2 frames) has no luminance stop and var = 0 for every finite S (no 0 * inf is formed).  Alpha is the framebuffer's. */
+ * than 2 frames) has no luminance stop and var = 0 for every finite S (no 0 * inf is formed).  Alpha is the framebuffer's.
+ *
+ * Variance modes (mrt_set_denoise_variance; the default, MRT_DENOISE_VAR_ACCUMULATED, is exactly the filter above).  A 2- to
+ * 4-frame variance estimate of ONE pixel is nearly worthless, and the luminance stop is scaled by it; both estimates below are
+ * float32 in the stated order with the same operations.
+ *   Prefilter (PREFILTERED and SPATIAL_EARLY; every iteration; only when a luminance stop exists).  For a texel p that is finite
+ *   in iteration i's input: taps q = p + (dx, dy), dy then dx from -1 to 1 -- distance 1 whatever the iteration's step -- with
+ *   k3 = {1/4, 1/2, 1/4}; a tap outside the image or whose c or var is not finite is skipped:
+ *     g_p   = (sum (k3[dx] * k3[dy]) * var_q) / (sum k3[dx] * k3[dy])                  (both sums in tap order, from 0)
+ *     w_lum = tukey(|L_p - L_q| * (1 / (sigma_l * sqrtf(g_p) + 1e-6f)))
+ *   g_p replaces var_p in the luminance stop and in the pass-through rule (a finite texel passes through when g_p == 0, not when
+ *   its own var is 0).  The propagated variance is unchanged: var' = sum (w * w) var_q / (sum w * sum w) over the unfiltered var_q.
+ *   With K = +inf there is no luminance stop and no prefilter: PREFILTERED is then bit for bit ACCUMULATED.
+ *   Spatial initial variance (SPATIAL_EARLY, while mrt_frames_done < spatial_frames; 1 frame, where K = +inf, included).  It
+ *   replaces S * K as iteration 0's variance, and the luminance stop is on.  For a texel p whose colour and S are finite: taps
+ *   q = p + (dx, dy), dy then dx from -3 to 3; a tap outside the image or whose colour or S is not finite is skipped; the weights
+ *   are the filter's own stops with the ctx's parameters, the centre tap's weight is 1:
+ *     w_q   = (w_normal * w_depth) * w_albedo
+ *     m0    = sum w_q;   m1 = sum w_q * L_q;   mean = m1 / m0
+ *     m2    = sum w_q * ((L_q - mean) * (L_q - mean))                                   (a second pass over the same taps)
+ *     var_p = m2 / m0
+ *   A texel with a finite S and a colour that is not finite gets var 0; a texel whose S is not finite keeps S as its var: both
+ *   pass through as above.  From frames_done >= spatial_frames on, SPATIAL_EARLY is PREFILTERED. */
 typedef struct {                 /* 48 bytes */
     uint32_t size;               /* sizeof(mrt_denoise_params): the version of this struct */
     uint32_t iterations;         /* 1 .. 8 (default 5: steps 1 .. 16) */
@@ -485,6 +507,16 @@ void mrt_denoise_params_default(mrt_denoise_params* out);
  * ctx NULL: checks the parameters only (host only). */
 int mrt_set_denoise_params(mrt_ctx* ctx, const mrt_denoise_params* params);
 int mrt_get_denoise_params(mrt_ctx* ctx, mrt_denoise_params* out);
+/* Where the luminance stop's variance comes from ("Variance modes" above). */
+enum { MRT_DENOISE_VAR_ACCUMULATED = 0,   /* default: var = S * K, the filter above exactly */
+       MRT_DENOISE_VAR_PREFILTERED = 1,
+       MRT_DENOISE_VAR_SPATIAL_EARLY = 2 };
+/* mode 0 .. 2; spatial_frames 1 .. 64 in every mode (default 3; only SPATIAL_EARLY reads it).  Anything else, or ctx NULL:
+ * MRT_ERR_INVALID_ARG, nothing changed.  The setting lives as long as the denoise parameters do (it survives mrt_reset,
+ * mrt_set_shard, mrt_set_world* and mrt_set_camera), takes effect at the next denoise and creates no resource.  Every refusal of
+ * a denoise holds in every mode. */
+int mrt_set_denoise_variance(mrt_ctx* ctx, uint32_t mode, uint32_t spatial_frames);
+int mrt_get_denoise_variance(mrt_ctx* ctx, uint32_t* mode, uint32_t* spatial_frames);   /* either pointer may be NULL */
 /* Denoises the most recent frame (queued on the ctx's stream behind its blend) and reads it back: height * width * 4 floats,
  * row 0 = bottom, as mrt_read_framebuffer; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE with tracking off or on a
  * shard, MRT_ERR_NO_SCENE without a scene. */

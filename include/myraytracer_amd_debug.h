@@ -37,6 +37,10 @@ int mrt_debug_noise_reduce(mrt_ctx* ctx, const float* S, const float* rgba, uint
  * {normal x, y, z, t, albedo r, g, b, sphere index as int32 bits}; out = rows x width RGBA32F.  params NULL: the ctx's. */
 int mrt_debug_denoise(mrt_ctx* ctx, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,
                       const mrt_denoise_params* params, float* out);
+/* Diagnostic: mrt_debug_denoise with a variance estimate ("Variance modes"): 0 accumulated (mrt_debug_denoise itself), 1
+ * prefiltered, 2 prefiltered with the spatial initial variance (K is ignored); anything else: MRT_ERR_INVALID_ARG. */
+int mrt_debug_denoise_variance(mrt_ctx* ctx, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
+                               uint32_t rows, const mrt_denoise_params* params, uint32_t variance, float* out);
 /* Diagnostic: the ctx's guides (rebuilt first if stale), height x width pixels, row 0 = bottom: rays 6 floats (origin,
  * direction), index 1 int32, t 1 float, normal 3 floats, albedo 3 floats per pixel; any pointer may be NULL.  cap_pixels >=
  * width * height.  Synchronous.  MRT_ERR_STATE on a shard, MRT_ERR_NO_SCENE without a scene. */

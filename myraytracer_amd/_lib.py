@@ -43,7 +43,7 @@ EXPORTS = [
     "mrt_set_noise_tracking", "mrt_noise_query", "mrt_noise_result", "mrt_read_noise", "mrt_read_noise_tiles", "mrt_noise_factor",
     "mrt_debug_noise_reduce",
     "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
-    "mrt_debug_read_guides",
+    "mrt_debug_read_guides", "mrt_set_denoise_variance", "mrt_get_denoise_variance", "mrt_debug_denoise_variance",
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
     "mrt_debug_check_context",
 ]
@@ -52,6 +52,8 @@ EXPORTS = [
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
 PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED = 1, 2, 8
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
+# the denoiser's variance modes (mrt_set_denoise_variance)
+DENOISE_VAR_ACCUMULATED, DENOISE_VAR_PREFILTERED, DENOISE_VAR_SPATIAL_EARLY = 0, 1, 2
 
 
 class MrtArgs(C.Structure):
@@ -323,6 +325,9 @@ def load():
         "mrt_get_denoise_params": (i32, [vp, P(MrtDenoiseParams)]),
         "mrt_read_denoised": (i32, [vp, vp, sz]),
         "mrt_debug_denoise": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), vp]),
+        "mrt_set_denoise_variance": (i32, [vp, u32, u32]),
+        "mrt_get_denoise_variance": (i32, [vp, P(u32), P(u32)]),
+        "mrt_debug_denoise_variance": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), u32, vp]),
         "mrt_debug_read_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
         "mrt_render_tiles": (i32, [vp, vp, sz, u32]),
         "mrt_render_adaptive": (i32, [vp, u32, C.c_uint64, P(C.c_uint64), P(u32)]),

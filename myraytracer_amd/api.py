@@ -698,6 +698,21 @@ class State:
         self._check(self._L.mrt_get_denoise_params(self._ctx, C.byref(p)), "mrt_get_denoise_params")
         return denoise_params_dict(p)
 
+    def set_denoise_variance(self, mode, spatial_frames: int = 3):
+        """Where the luminance stop's variance comes from: "accumulated" (0, the default: S * K of the one pixel), "prefiltered"
+        (1: its 3 x 3 mean) or "spatial-early" (2: a spatial estimate while frames_done < spatial_frames, prefiltered from then on)."""
+        if isinstance(mode, str):
+            if mode not in DENOISE_VARIANCE_MODES:
+                raise ValueError(f"set_denoise_variance: unknown mode {mode!r} ({', '.join(DENOISE_VARIANCE_MODES)})")
+            mode = DENOISE_VARIANCE_MODES.index(mode)
+        self._check(self._L.mrt_set_denoise_variance(self._ctx, mode, spatial_frames), "mrt_set_denoise_variance")
+
+    def denoise_variance(self) -> tuple:
+        """(mode name, spatial_frames)."""
+        mode, frames = C.c_uint32(), C.c_uint32()
+        self._check(self._L.mrt_get_denoise_variance(self._ctx, C.byref(mode), C.byref(frames)), "mrt_get_denoise_variance")
+        return DENOISE_VARIANCE_MODES[mode.value], int(frames.value)
+
     def read_denoised(self) -> np.ndarray:
         """The most recent frame, denoised: (H, W, 4) f32, row 0 = bottom.  Needs noise tracking and world == 1; waits for the
         frames in flight, as read_framebuffer does."""
@@ -715,9 +730,11 @@ class State:
                                                   g["normal"].ctypes.data, g["albedo"].ctypes.data, h * w), "mrt_debug_read_guides")
         return g
 
-    def debug_denoise(self, rgba: np.ndarray, S: np.ndarray, K: float, guides: dict, params: Optional[dict] = None) -> np.ndarray:
+    def debug_denoise(self, rgba: np.ndarray, S: np.ndarray, K: float, guides: dict, params: Optional[dict] = None,
+                      variance: int = 0) -> np.ndarray:
         """The filter on caller-supplied buffers, synchronously: rgba (rows, W, 4) f32, S (rows, W) f32, guides as
-        debug_read_guides returns them (index, t, normal, albedo); params: fields over the State's parameters."""
+        debug_read_guides returns them (index, t, normal, albedo); params: fields over the State's parameters; variance: 0
+        accumulated (mrt_debug_denoise), 1 prefiltered, 2 prefiltered with the spatial initial variance (K ignored)."""
         rgba = np.ascontiguousarray(rgba, np.float32)
         S = np.ascontiguousarray(S, np.float32)
         rows, width = S.shape
@@ -729,12 +746,17 @@ class State:
         for k, v in (params or {}).items():
             setattr(p, k, v)
         out = np.empty_like(rgba)
-        self._check(self._L.mrt_debug_denoise(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows, C.byref(p),
-                                              out.ctypes.data), "mrt_debug_denoise")
+        if variance == 0:
+            self._check(self._L.mrt_debug_denoise(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows, C.byref(p),
+                                                  out.ctypes.data), "mrt_debug_denoise")
+        else:
+            self._check(self._L.mrt_debug_denoise_variance(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows,
+                                                           C.byref(p), variance, out.ctypes.data), "mrt_debug_denoise_variance")
         return out
 
 
 DENOISE_FIELDS = ("iterations", "sigma_l", "normal_exp", "sigma_z", "sigma_a")
+DENOISE_VARIANCE_MODES = ("accumulated", "prefiltered", "spatial-early")          # MRT_DENOISE_VAR_*
 
 
 def denoise_params_dict(p) -> dict:

@@ -102,12 +102,20 @@ int ensure_guides(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// launch_denoise's variance of a frame count in a mode: SPATIAL_EARLY is the spatial estimate while the history is short and
+// PREFILTERED from then on
+uint32_t variance_of(uint32_t mode, uint32_t frames_done, uint32_t spatial_frames) {
+    if (mode == MRT_DENOISE_VAR_SPATIAL_EARLY) return frames_done < spatial_frames ? 2u : 1u;
+    return mode == MRT_DENOISE_VAR_PREFILTERED ? 1u : 0u;
+}
+
 // the most recent frame, denoised into d_den[2] (after denoise_check)
 int queue_denoise(mrt_ctx* c) {
     MRT_TRY(ensure_guides(c));
     const float K = (float)mrt::noise_factor_of(c->noise_c2);
+    const uint32_t variance = variance_of(c->denoise_var_mode, c->frames_done, c->denoise_spatial_frames);
     const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, K, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
-                                      c->args.width, c->args.height, c->denoise, c->stream);
+                                      c->args.width, c->args.height, c->denoise, variance, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
@@ -146,6 +154,22 @@ int mrt_get_denoise_params(mrt_ctx* c, mrt_denoise_params* out) {
     return MRT_OK;
 }
 
+int mrt_set_denoise_variance(mrt_ctx* c, uint32_t mode, uint32_t spatial_frames) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (mode > MRT_DENOISE_VAR_SPATIAL_EARLY || spatial_frames < 1 || spatial_frames > 64)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_denoise_variance: mode %u (0..2), spatial_frames %u (1..64)", mode, spatial_frames);
+    c->denoise_var_mode = mode;
+    c->denoise_spatial_frames = spatial_frames;
+    return MRT_OK;
+}
+
+int mrt_get_denoise_variance(mrt_ctx* c, uint32_t* mode, uint32_t* spatial_frames) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (mode) *mode = c->denoise_var_mode;
+    if (spatial_frames) *spatial_frames = c->denoise_spatial_frames;
+    return MRT_OK;
+}
+
 int mrt_read_denoised(mrt_ctx* c, float* out, size_t cap) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
     MRT_TRY(denoise_check(c, "mrt_read_denoised", true));
@@ -180,8 +204,15 @@ int mrt_debug_read_guides(mrt_ctx* c, float* rays, int32_t* index, float* t, flo
 
 int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,
                       const mrt_denoise_params* params, float* out) {
-    if (!c || !rgba || !S || !guides || !out || !width || !rows || (uint64_t)width * rows > (1ull << 26) || std::isnan(K) || K < 0.0)
+    return mrt_debug_denoise_variance(c, rgba, S, K, guides, width, rows, params, 0, out);
+}
+
+int mrt_debug_denoise_variance(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
+                               uint32_t rows, const mrt_denoise_params* params, uint32_t variance, float* out) {
+    if (!c || !rgba || !S || !guides || !out || !width || !rows || (uint64_t)width * rows > (1ull << 26) || variance > 2)
         return MRT_ERR_INVALID_ARG;
+    if (variance == 2) K = 0.0;             // (the spatial initial variance: K is not read)
+    if (std::isnan(K) || K < 0.0) return MRT_ERR_INVALID_ARG;
     const mrt_denoise_params prm = params ? *params : c->denoise;
     if (!denoise_params_ok(&prm)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_denoise: bad parameters");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -196,7 +227,7 @@ int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, c
     if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(d_fb, d_s, (float)K, d_g, d_b[0], d_b[1], d_b[2], width, rows, prm, c->stream);
+    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(d_fb, d_s, (float)K, d_g, d_b[0], d_b[1], d_b[2], width, rows, prm, variance, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_b[2], n * 16, hipMemcpyDeviceToHost, c->stream);
     int ws = MRT_OK;
     if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");

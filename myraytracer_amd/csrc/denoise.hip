@@ -5,7 +5,8 @@
 // Guides (once per camera / scene): guide_rays_kernel writes one ray per pixel through the mean of the render's sample
 // positions; the closest hits come from the DBG instantiation of render_kernel (launch_debug_world_hit, no candidate bitmap);
 // guide_fill_kernel turns them into the per-texel record the filter reads.
-// Filter: atrous_kernel, one launch per iteration, colour and variance ping-ponged as one float4.  Only + - * /, sqrtf, fminf,
+// Filter: atrous_kernel, one launch per iteration, colour and variance ping-ponged as one float4; with a variance mode
+// (mrt_set_denoise_variance) atrous_prefilter_kernel instead, behind spatial_variance_kernel while the history is short.  Only + - * /, sqrtf, fminf,
 // fmaxf in a fixed order (-ffp-contract=off; hipcc's `/` and sqrtf are correctly rounded), so tests/denoise_ref.py restates it
 // bit for bit in float32 numpy.
 #include <hip/hip_runtime.h>
@@ -108,6 +109,33 @@ __device__ __forceinline__ float4 load_cv(const AtrousArgs& A, size_t i) {
     return make_float4(c.x, c.y, c.z, var);
 }
 
+// g_p of a finite texel p: the {1/4, 1/2, 1/4}^2 mean of var over the 3 x 3 texels around it, rows then columns in increasing
+// order, a tap outside the image or not finite skipped (p itself never is).
+template <bool FIRST>
+__device__ __forceinline__ float prefiltered_var(const AtrousArgs& A, uint32_t x, uint32_t y, float4 cp) {
+    const float k3[3] = {0.25f, 0.5f, 0.25f};
+    float num = 0.0f, den = 0.0f;
+#pragma unroll
+    for (int ty = 0; ty < 3; ty++) {
+        const int yq = (int)y + (ty - 1);
+        if (yq < 0 || yq >= (int)A.height) continue;
+#pragma unroll
+        for (int tx = 0; tx < 3; tx++) {
+            const int xq = (int)x + (tx - 1);
+            if (xq < 0 || xq >= (int)A.width) continue;
+            const float kxy = k3[tx] * k3[ty];
+            float4 cq = cp;
+            if (!(tx == 1 && ty == 1)) {
+                cq = load_cv<FIRST>(A, (size_t)yq * A.width + (uint32_t)xq);
+                if (!finite4(cq)) continue;
+            }
+            num = num + kxy * cq.w;
+            den = den + kxy;
+        }
+    }
+    return num / den;
+}
+
 // grid (ceil(W / 32), ceil(H / 8)), 32 x 8 threads; one pixel per thread.  Taps at offsets {-2..2} x step, rows then columns in
 // increasing order, B3-spline weights {1/16, 1/4, 3/8, 1/4, 1/16}; outside the image or not finite: skipped.  The centre tap
 // weighs (3/8)^2 without stops; any other tap k_x k_y w_lum w_normal w_depth w_albedo, multiplied in that order.
@@ -172,6 +200,158 @@ __global__ void __launch_bounds__(kTileX * kTileY) atrous_kernel(const AtrousArg
     A.out[i] = res;
 }
 
+// The edge stops of a tap q of p, as atrous_kernel forms them (for the kernels of the variance modes below; atrous_kernel keeps
+// its own text, so that the default mode's four instantiations stay the same instructions).
+__device__ __forceinline__ float stop_normal(const AtrousArgs& A, float4 gp0, float4 gq0) {
+    float wn = fmaxf(0.0f, (gp0.x * gq0.x + gp0.y * gq0.y) + gp0.z * gq0.z);
+    for (uint32_t e = 0; e < A.normal_exp; e++) wn = wn * wn;
+    return wn;
+}
+__device__ __forceinline__ float stop_depth(float4 gp0, float4 gq0, bool miss_p, bool miss_q, float inv_z) {
+    return miss_p != miss_q ? 0.0f : miss_p ? 1.0f : tukey(fabsf(gp0.w - gq0.w) * inv_z);
+}
+__device__ __forceinline__ float stop_albedo(const AtrousArgs& A, float4 gp1, float4 gq1) {
+    const float da = fmaxf(fmaxf(fabsf(gp1.x - gq1.x), fabsf(gp1.y - gq1.y)), fabsf(gp1.z - gq1.z));
+    return tukey(da * A.inv_sigma_a);
+}
+
+// The prefiltering a-trous iteration (PREFILTERED, SPATIAL_EARLY; launched only with a luminance stop): atrous_kernel, except
+// that the luminance stop and the pass-through rule read g_p (prefiltered_var: 9 more loads, for the centre texel only).  The
+// propagated variance still sums the unfiltered var_q.
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_prefilter_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = load_cv<FIRST>(A, i);
+    float4 res = cp;
+    const float gv = finite4(cp) ? prefiltered_var<FIRST>(A, x, y, cp) : 0.0f;
+    // passed through: not finite, or a prefiltered variance of 0
+    if (finite4(cp) && gv != 0.0f) {
+        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+        const bool miss_p = __float_as_int(gp1.w) < 0;
+        const float lp = lumf(cp.x, cp.y, cp.z);
+        const float inv_l = 1.0f / (A.sigma_l * sqrtf(gv) + 1.0e-6f);
+        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+        const float kern[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+        float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+        const int step = (int)A.step;
+#pragma unroll
+        for (int ty = 0; ty < 5; ty++) {
+            const int yq = (int)y + (ty - 2) * step;
+            if (yq < 0 || yq >= (int)A.height) continue;
+#pragma unroll
+            for (int tx = 0; tx < 5; tx++) {
+                const int xq = (int)x + (tx - 2) * step;
+                if (xq < 0 || xq >= (int)A.width) continue;
+                float w = kern[tx] * kern[ty];
+                float4 cq = cp;
+                if (!(tx == 2 && ty == 2)) {
+                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                    cq = load_cv<FIRST>(A, q);
+                    if (!finite4(cq)) continue;
+                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                    const bool miss_q = __float_as_int(gq1.w) < 0;
+                    w = w * tukey(fabsf(lp - lumf(cq.x, cq.y, cq.z)) * inv_l);
+                    w = w * stop_normal(A, gp0, gq0);
+                    w = w * stop_depth(gp0, gq0, miss_p, miss_q, inv_z);
+                    w = w * stop_albedo(A, gp1, gq1);
+                }
+                sw = sw + w;
+                sr = sr + w * cq.x;
+                sg = sg + w * cq.y;
+                sb = sb + w * cq.z;
+                sv = sv + (w * w) * cq.w;
+            }
+        }
+        res = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+    }
+    if (LAST) res.w = A.fb[i].w;
+    A.out[i] = res;
+}
+
+// The spatial initial variance (SPATIAL_EARLY while the history is short): per texel the weighted variance of the luminance over
+// the 7 x 7 window, the weights the filter's own normal, depth and albedo stops (the centre's 1); out = (r, g, b, var), which the
+// first a-trous iteration then reads as a non-first one.  Same grid and block as atrous_kernel.  Two passes over the taps (the
+// mean, then the squares about it): the 49 weights and luminances of the first stay in registers (the loops are fully unrolled,
+// every index a constant), so the second pass loads nothing -- recomputing them would cost 49 x 52 more bytes of loads and the
+// stops' arithmetic per pixel.  132 VGPRs, no scratch: 3 waves per SIMD.
+__global__ void __launch_bounds__(kTileX * kTileY) spatial_variance_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = A.fb[i];
+    const float sp = A.S[i];
+    float var = sp;                             // S not finite: kept (the texel passes through)
+    if (__builtin_isfinite(sp)) {
+        var = 0.0f;                             // a colour that is not finite: passes through as well
+        if (__builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
+            const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+            const bool miss_p = __float_as_int(gp1.w) < 0;
+            const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+            float w[49], l[49];
+            uint64_t used = 0;
+            float m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+            for (int ty = 0; ty < 7; ty++) {
+#pragma unroll
+                for (int tx = 0; tx < 7; tx++) {
+                    const int t = ty * 7 + tx;
+                    w[t] = 0.0f;
+                    l[t] = 0.0f;
+                    const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
+                    if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
+                    float wq, lq;
+                    if (tx == 3 && ty == 3) {
+                        wq = 1.0f;
+                        lq = lumf(cp.x, cp.y, cp.z);
+                    } else {
+                        const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                        const float4 cq = A.fb[q];
+                        const float sq = A.S[q];
+                        if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && __builtin_isfinite(sq)))
+                            continue;
+                        const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                        const bool miss_q = __float_as_int(gq1.w) < 0;
+                        wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
+                        lq = lumf(cq.x, cq.y, cq.z);
+                    }
+                    w[t] = wq;
+                    l[t] = lq;
+                    used |= 1ull << t;
+                    m0 = m0 + wq;
+                    m1 = m1 + wq * lq;
+                }
+            }
+            const float mean = m1 / m0;
+            float m2 = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 49; t++) {
+                if (!(used >> t & 1ull)) continue;
+                const float d = l[t] - mean;
+                m2 = m2 + w[t] * (d * d);
+            }
+            var = m2 / m0;
+        }
+    }
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
+}
+
+template <bool PF>
+void launch_atrous(bool first, bool last, dim3 grid, dim3 block, hipStream_t st, const AtrousArgs& A) {
+    if (PF) {
+        if (first && last) hipLaunchKernelGGL((atrous_prefilter_kernel<true, true>), grid, block, 0, st, A);
+        else if (first) hipLaunchKernelGGL((atrous_prefilter_kernel<true, false>), grid, block, 0, st, A);
+        else if (last) hipLaunchKernelGGL((atrous_prefilter_kernel<false, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((atrous_prefilter_kernel<false, false>), grid, block, 0, st, A);
+    } else {
+        if (first && last) hipLaunchKernelGGL((atrous_kernel<true, true>), grid, block, 0, st, A);
+        else if (first) hipLaunchKernelGGL((atrous_kernel<true, false>), grid, block, 0, st, A);
+        else if (last) hipLaunchKernelGGL((atrous_kernel<false, true>), grid, block, 0, st, A);
+        else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, st, A);
+    }
+}
+
 }  // namespace
 
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream) {
@@ -190,31 +370,37 @@ int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade
 }
 
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, void* stream) {
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream) {
     if (width == 0 || height == 0) return 0;
+    const bool spatial = variance == 2;
     AtrousArgs A;
     A.fb = reinterpret_cast<const float4*>(fb);
     A.S = S;
+    A.in = nullptr;
     A.guides = reinterpret_cast<const float4*>(guides);
-    A.width = width; A.height = height;
-    A.K = K;
-    A.lum_stop = __builtin_isinf(K) ? 0u : 1u;
+    A.width = width; A.height = height; A.step = 1;
+    A.K = spatial ? 0.0f : K;
+    A.lum_stop = spatial || !__builtin_isinf(K) ? 1u : 0u;
     A.sigma_l = prm.sigma_l; A.sigma_z = prm.sigma_z;
     A.inv_sigma_a = 1.0f / prm.sigma_a;
     A.normal_exp = prm.normal_exp;
     const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
     hipStream_t st = (hipStream_t)stream;
     float4* buf[2] = {reinterpret_cast<float4*>(ping), reinterpret_cast<float4*>(pong)};
+    // without a luminance stop there is nothing to prefilter: today's kernels
+    const bool prefilter = variance != 0 && A.lum_stop;
+    if (spatial) {          // into pong, where iteration 0 reads it as "the previous iteration's" (and iteration 1 writes pong after it)
+        A.out = buf[1];
+        hipLaunchKernelGGL(spatial_variance_kernel, grid, block, 0, st, A);
+    }
     const uint32_t n = prm.iterations;
     for (uint32_t it = 0; it < n; it++) {
-        const bool first = it == 0, last = it + 1 == n;
+        const bool first = it == 0 && !spatial, last = it + 1 == n;
         A.step = 1u << it;
-        A.in = first ? nullptr : buf[(it - 1) & 1u];
+        A.in = first ? nullptr : buf[(it + 1) & 1u];
         A.out = last ? reinterpret_cast<float4*>(out) : buf[it & 1u];
-        if (first && last) hipLaunchKernelGGL((atrous_kernel<true, true>), grid, block, 0, st, A);
-        else if (first) hipLaunchKernelGGL((atrous_kernel<true, false>), grid, block, 0, st, A);
-        else if (last) hipLaunchKernelGGL((atrous_kernel<false, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, st, A);
+        if (prefilter) launch_atrous<true>(first, last, grid, block, st, A);
+        else launch_atrous<false>(first, last, grid, block, st, A);
     }
     return (int)hipGetLastError();
 }

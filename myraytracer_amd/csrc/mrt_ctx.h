@@ -200,6 +200,8 @@ struct mrt_ctx {
     // current camera and scene (width x height pixels, y * width + x; rebuilt on the ctx's stream at the next denoise after
     // mrt_set_camera / mrt_set_world* / mrt_set_shard mark them stale) and the filter's buffers, all allocated at the first use
     mrt_denoise_params denoise = mrt::denoise_defaults();
+    uint32_t denoise_var_mode = MRT_DENOISE_VAR_ACCUMULATED;   // mrt_set_denoise_variance: where the luminance stop's variance comes from
+    uint32_t denoise_spatial_frames = 3;                       // SPATIAL_EARLY: the spatial estimate while frames_done < this
     bool guides_stale = true;
     float* d_guide_rays = nullptr;                  // 6 floats per pixel
     int32_t* d_guide_hits = nullptr;                // {sphere | -1, bits of t} per pixel (the DBG render kernel's output)

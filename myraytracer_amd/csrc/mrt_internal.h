@@ -228,12 +228,14 @@ int launch_tile_blend(const TileBlendArgs& a, void* stream);
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
 // pixel (launch_debug_world_hit) -> 2 float4 per pixel {normal, t} {albedo, bits of the index}; shade / mat_ty: KParams' shade and
 // the spheres' material types (i32_data + material_ty_base_idx).  launch_denoise: prm.iterations launches; ping / pong: scratch of
-// width x height float4 each (unused for 1 iteration / ping only for 2); out: width x height RGBA32F.
+// width x height float4 each (unused for 1 iteration / ping only for 2); out: width x height RGBA32F.  variance: 0 var = S * K,
+// today's four kernels; 1 the prefiltered luminance stop (with K = +inf exactly 0); 2 the spatial initial variance into pong (one
+// more launch; K is not read) and every iteration prefiltered.
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream);
 int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade, const int32_t* mat_ty, float* guides,
                       uint32_t width, uint32_t height, void* stream);
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, void* stream);
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream);
 inline mrt_denoise_params denoise_defaults() {
     mrt_denoise_params p{};
     p.size = sizeof(mrt_denoise_params);

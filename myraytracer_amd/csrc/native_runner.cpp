@@ -25,13 +25,16 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive]] [--denoise-out FILE]\n"
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive]]\n"
+        "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]]]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
         "                      check earlier finds noisy, and the loop also stops when no pixel is above rel 0.02; prints frames,\n"
         "                      samples and tiles selected per check\n"
-        "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png; one GPU)\n");
+        "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png; one GPU)\n"
+        "  --denoise-variance: the luminance stop's variance (mrt_set_denoise_variance): the pixel's own accumulated estimate\n"
+        "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n");
 }
 
 int main(int argc, char** argv) {
@@ -42,7 +45,7 @@ int main(int argc, char** argv) {
     mrt_args args;
     mrt_args_default(&args);
     uint32_t frames = 1, warmup = 0, rng_mode = MRT_RNG_PIXEL_STREAM; uint64_t seed = 1; int device = 0;
-    uint32_t hint_div = 0, hint_mult = 0, check_every = 16;
+    uint32_t hint_div = 0, hint_mult = 0, check_every = 16, denoise_var = MRT_DENOISE_VAR_ACCUMULATED, spatial_frames = 3;
     double target_noise = -1.0;
     bool adaptive = false;
     std::string scene = "default", scene_file, save_scene, out, denoise_out;
@@ -75,6 +78,18 @@ int main(int argc, char** argv) {
         }
         else if (a == "--out") out = v;
         else if (a == "--denoise-out") denoise_out = v;
+        else if (a == "--denoise-variance") {
+            const size_t colon = v.find(':');
+            const std::string m = v.substr(0, colon);
+            if (m == "accumulated") denoise_var = MRT_DENOISE_VAR_ACCUMULATED;
+            else if (m == "prefiltered") denoise_var = MRT_DENOISE_VAR_PREFILTERED;
+            else if (m == "spatial-early") denoise_var = MRT_DENOISE_VAR_SPATIAL_EARLY;
+            else { std::fprintf(stderr, "unknown --denoise-variance %s\n", v.c_str()); return 2; }
+            if (colon != std::string::npos) {
+                if (denoise_var != MRT_DENOISE_VAR_SPATIAL_EARLY) { std::fprintf(stderr, "--denoise-variance: only spatial-early takes :N\n"); return 2; }
+                spatial_frames = (uint32_t)std::strtoul(v.c_str() + colon + 1, nullptr, 10);
+            }
+        }
         else if (a == "--device") device = std::atoi(v.c_str());
         else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
         else if (a == "--check-every") check_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
@@ -127,6 +142,7 @@ int main(int argc, char** argv) {
         if (rng_mode != MRT_RNG_PIXEL_STREAM) TRY(ctxs[i], mrt_set_rng_mode(ctxs[i], rng_mode));
         if (hint_div) TRY(ctxs[i], mrt_set_schedule_hint(ctxs[i], hint_div, hint_mult));
         if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
+        TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
     }
     if (!denoise_out.empty() && n_gpus > 1) { std::fprintf(stderr, "--denoise-out wants one GPU (a shard has no neighbours)\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
