@@ -152,6 +152,26 @@ int mrt_debug_sweep_variant(mrt_ctx* ctx);
 int mrt_debug_set_frame_batching(mrt_ctx* ctx, int enabled);
 /* Diagnostic A/B switch: 0 queues tiles in index order instead of heaviest-first. */
 int mrt_debug_set_tile_sort(mrt_ctx* ctx, int enabled);
+/* Diagnostic: the tile-queue sort a frame runs, on caller-supplied costs, synchronously (it waits for the frames in flight
+ * first).  cost = n_cost u32, 1 <= n_cost <= the context's tile count (pick the image size for the count wanted).  list NULL:
+ * the whole-frame sort of tiles 0 .. n_cost - 1 (n must equal n_cost); else the list sort of a subset frame over the n <=
+ * n_cost tile ids of list[], each < n_cost.  order_out gets the n entries of the queue, heaviest first (ties in any order).
+ * Staged through the buffers of the slot of the most recent frame: afterwards that slot's cost estimate is marked invalid, so
+ * the caller's costs never order a real frame (the next one gets a pilot launch or index order), and
+ * mrt_debug_read_tile_schedule reports MRT_TILE_ORDER_NONE until the slot's next frame.  MRT_ERR_NO_SCENE without a scene. */
+int mrt_debug_sort_tiles(mrt_ctx* ctx, const uint32_t* cost, size_t n_cost, const uint32_t* list, size_t n, uint32_t* order_out);
+/* Diagnostic: the scheduling state of the slot of the most recent frame, after waiting for the frames in flight.  cost_out
+ * (may be NULL): the per-tile costs as that slot's last finalize or per-tile blend left them, *n_out = the context's tile
+ * count of them.  order_out (may be NULL): the queue order the slot's most recent render launch was given, info_out[1]
+ * entries.  cap >= the tile count holds for both.  info_out[4] = {how the order came about (MRT_TILE_ORDER_*), its entries,
+ * 1 if a cost-estimating pilot launch preceded the launch, the slot}.  MRT_ERR_NO_SCENE without a scene. */
+#define MRT_TILE_ORDER_NONE 0u        /* no render launch on this slot yet (or mrt_debug_sort_tiles since) */
+#define MRT_TILE_ORDER_INDEX 1u       /* whole frame, no sort: tiles 0 .. n - 1 */
+#define MRT_TILE_ORDER_SORTED 2u      /* whole frame, heaviest first by the slot's costs */
+#define MRT_TILE_ORDER_SORTED_LIST 3u /* subset frame, its list heaviest first by the slot's costs */
+#define MRT_TILE_ORDER_LIST 4u        /* subset frame, its list as the caller gave it */
+int mrt_debug_read_tile_schedule(mrt_ctx* ctx, uint32_t* cost_out, uint32_t* order_out, size_t cap, uint32_t* n_out,
+                                 uint32_t info_out[4]);
 /* Diagnostic / tuning: pilot samples per pixel, waves per CU (0 = automatic).  Before the first
  * redraw only. */
 int mrt_debug_set_schedule(mrt_ctx* ctx, uint32_t pilot_spp, int waves_per_cu);

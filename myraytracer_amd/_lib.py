@@ -45,13 +45,15 @@ EXPORTS = [
     "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
     "mrt_debug_read_guides", "mrt_set_denoise_variance", "mrt_get_denoise_variance", "mrt_debug_denoise_variance",
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
-    "mrt_debug_check_context",
+    "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule",
 ]
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
 PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED = 1, 2, 8
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
+# how a slot's tile queue was ordered (mrt_debug_read_tile_schedule, MRT_TILE_ORDER_*)
+TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
 # the denoiser's variance modes (mrt_set_denoise_variance)
 DENOISE_VAR_ACCUMULATED, DENOISE_VAR_PREFILTERED, DENOISE_VAR_SPATIAL_EARLY = 0, 1, 2
 
@@ -333,6 +335,8 @@ def load():
         "mrt_render_adaptive": (i32, [vp, u32, C.c_uint64, P(C.c_uint64), P(u32)]),
         "mrt_read_tile_frames": (i32, [vp, vp, sz, P(u32), P(u32)]),
         "mrt_debug_check_context": (i32, [vp, C.c_char_p, sz]),
+        "mrt_debug_sort_tiles": (i32, [vp, vp, sz, vp, sz, vp]),
+        "mrt_debug_read_tile_schedule": (i32, [vp, vp, vp, sz, P(u32), P(u32)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

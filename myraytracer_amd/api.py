@@ -470,6 +470,36 @@ class State:
         """Before the first redraw: samples per pixel of the pilot launch, persistent waves per CU (0 = automatic)."""
         self._check(self._L.mrt_debug_set_schedule(self._ctx, pilot_spp, waves_per_cu), "mrt_debug_set_schedule")
 
+    def debug_sort_tiles(self, cost, tiles=None) -> np.ndarray:
+        """The tile-queue sort a frame runs, on caller-supplied costs (u32, at most the context's tile count of them): the whole
+        range (tiles None) or the listed tile ids, as a subset frame's list.  Returns the queue, heaviest first.  Synchronous;
+        the slot's own estimate is invalid afterwards (mrt_debug_sort_tiles)."""
+        cost = np.ascontiguousarray(cost, np.uint32).ravel()
+        lst = None if tiles is None else np.ascontiguousarray(tiles, np.uint32).ravel()
+        n = len(cost) if lst is None else len(lst)
+        out = np.empty(n, np.uint32)
+        self._check(self._L.mrt_debug_sort_tiles(self._ctx, cost.ctypes.data, len(cost), None if lst is None else lst.ctypes.data, n,
+                                                 out.ctypes.data), "mrt_debug_sort_tiles")
+        return out
+
+    def debug_read_tile_schedule(self):
+        """(costs (n_tiles,) u32 as the last slot's finalize or per-tile blend left them, the queue order (entries,) u32 its most
+        recent render launch was given, {"kind": one of _lib.TILE_ORDER_KINDS, "entries", "pilot", "slot"}).  Waits for the
+        frames in flight."""
+        _, _, rows, width = self.shard_info()
+        tiles = ((width + 7) // 8) * (rows // 8)
+        n, info = C.c_uint32(), (C.c_uint32 * 4)()
+        cost, order = np.empty(tiles, np.uint32), np.empty(tiles, np.uint32)
+        self._check(self._L.mrt_debug_read_tile_schedule(self._ctx, cost.ctypes.data, order.ctypes.data, tiles, C.byref(n), info),
+                    "mrt_debug_read_tile_schedule")
+        assert n.value == tiles
+        return cost, order[:info[1]].copy(), {"kind": _lib.TILE_ORDER_KINDS[info[0]], "entries": int(info[1]), "pilot": bool(info[2]),
+                                              "slot": int(info[3])}
+
+    def debug_set_tile_sort(self, enabled: bool):
+        """A/B switch: False queues tiles in index order instead of heaviest-first (same image)."""
+        self._check(self._L.mrt_debug_set_tile_sort(self._ctx, int(enabled)), "mrt_debug_set_tile_sort")
+
     def debug_set_boxes(self, mode):
         """A/B switch (large scenes, whose walk tests every node's axis-aligned box): 0 / False = the boxes are opened wide and
         never reject, 1 / 2 / True = the real boxes (default); the image is the same."""

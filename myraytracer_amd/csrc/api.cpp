@@ -52,6 +52,7 @@ void free_frame_buffers(mrt_ctx* c) {
         free_pinned(S.h_tile_list);
         S.pix_acc_layers = 0; S.cost_first_layer = 0; S.cost_layers = 1;
         S.cost_valid = false;
+        S.order_kind = 0; S.order_n = 0; S.order_pilot = false;
     }
 }
 

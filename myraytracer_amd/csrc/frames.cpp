@@ -441,11 +441,13 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
         c->last_frames_running = frames_running;
         launch_waves = std::max(whole / c->last_launch_div, 1u);
     }
+    bool piloted = false;
     if (c->lpt_enabled && c->n_tiles > launch_waves && chain_spp >= 4u) {
         if (!S.cost_valid && c->locals.samples_per_frame >= 8u * c->pilot_spp) {
             int pe = mrt::launch_render(p, true, launch_waves, S.stream, &c->last_launch[1]);
             if (pe) return fail(c, MRT_ERR_HIP, "pilot launch failed: %s", hipGetErrorString((hipError_t)pe));
             S.cost_valid = true;
+            piloted = true;
         }
         if (S.cost_valid) {
             int se = mrt::launch_sort_tiles(S.d_tile_cost, S.d_tile_order, S.d_sort_scratch, c->n_tiles, S.stream);
@@ -458,6 +460,9 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
         HIP_TRY(c, hipMemsetAsync(p.wave_log, 0, c->wave_log_waves * 4 * sizeof(unsigned long long), S.stream));
     }
     MRT_TRY(launch_frame(c, S, p, launch_waves));
+    S.order_kind = p.tile_order ? MRT_TILE_ORDER_SORTED : MRT_TILE_ORDER_INDEX;     // (mrt_debug_read_tile_schedule)
+    S.order_n = c->n_tiles;
+    S.order_pilot = piloted;
     // (on the slot's stream right behind render_done, as ever: the ctx's stream waits for that event, already recorded)
     if (adaptive) {         // the launch-width controller's sample: cumulative world_hit calls and lane slots after this kernel
         // (counters 1 .. 3 in ONE copy: world_hit calls and lane slots of the same instant)
@@ -547,6 +552,13 @@ static int begin_tile_frames(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// the slot's tile list on the device and its pinned staging copy, on first use
+static int alloc_tile_list(mrt_ctx* c, mrt_ctx::FrameSlot& S) {
+    if (!S.d_tile_list) HIP_TRY(c, hipMalloc((void**)&S.d_tile_list, (size_t)c->n_tiles * sizeof(uint32_t)));
+    if (!S.h_tile_list) HIP_TRY(c, hipHostMalloc((void**)&S.h_tile_list, (size_t)c->n_tiles * sizeof(uint32_t), hipHostMallocDefault));
+    return MRT_OK;
+}
+
 // `batch` consecutive subset frames over the n tiles of `tiles` in ONE render launch (batch > 1: the in-lane form only)
 static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t batch) {
     c->last_slot = (uint32_t)(c->frame_seq % c->frame_slots);
@@ -560,8 +572,7 @@ static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t
         if (S.render_pending) MRT_TRY(mrt::wait_event(c, S.render_done, what));
         S.render_pending = false;
     }
-    if (!S.d_tile_list) HIP_TRY(c, hipMalloc((void**)&S.d_tile_list, (size_t)c->n_tiles * sizeof(uint32_t)));
-    if (!S.h_tile_list) HIP_TRY(c, hipHostMalloc((void**)&S.h_tile_list, (size_t)c->n_tiles * sizeof(uint32_t), hipHostMallocDefault));
+    MRT_TRY(alloc_tile_list(c, S));
     std::memcpy(S.h_tile_list, tiles, (size_t)n * sizeof(uint32_t));
     const size_t texels = mrt::local_texels_min1(c);
     MRT_TRY(grow_colour_sums(c, S, batch, "mrt_render_tiles: regrowing a slot's colour sums (its side stream)", __func__));
@@ -589,6 +600,9 @@ static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t
         p.tile_order = S.d_tile_order;
     }
     MRT_TRY(launch_frame(c, S, p, launch_waves));
+    S.order_kind = p.tile_order == S.d_tile_order ? MRT_TILE_ORDER_SORTED_LIST : MRT_TILE_ORDER_LIST;     // (mrt_debug_read_tile_schedule)
+    S.order_n = n;
+    S.order_pilot = false;
     for (uint32_t b = 0; b < batch; b++) {
         p.pix_acc = (char*)S.d_pix_acc + (size_t)b * texels * 16;
         p.n_blocks = 1;
@@ -664,6 +678,53 @@ int mrt_debug_read_pixel_costs(mrt_ctx* c, uint32_t* out, size_t cap) {
     }
     for (size_t i = 0; i < n; i++) out[i] = tmp[4 * i + 3];
     return MRT_OK;
+}
+
+// diagnostic: the very sort a frame's queue gets, on caller-supplied costs, staged through the last slot's own buffers
+int mrt_debug_sort_tiles(mrt_ctx* c, const uint32_t* cost, size_t n_cost, const uint32_t* list, size_t n, uint32_t* order_out) {
+    if (!c || !cost || !order_out) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_sort_tiles: no scene (call mrt_set_world first)");
+    if (n_cost == 0 || n_cost > c->n_tiles) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_sort_tiles: %zu costs, the context has %u tiles", n_cost, c->n_tiles);
+    if (list ? (n == 0 || n > n_cost) : n != n_cost) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_sort_tiles: %zu entries of %zu costs", n, n_cost);
+    for (size_t i = 0; list && i < n; i++)
+        if (list[i] >= n_cost) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_sort_tiles: tile %u of %zu", list[i], n_cost);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, __func__));
+    mrt_ctx::FrameSlot& S = c->slot[c->last_slot];
+    if (list) MRT_TRY(alloc_tile_list(c, S));
+    // whatever comes next, the slot's costs are no estimate of a frame any more and its recorded order is gone
+    S.cost_valid = false;
+    S.order_kind = MRT_TILE_ORDER_NONE; S.order_n = 0; S.order_pilot = false;
+    HIP_TRY(c, hipMemcpyAsync(S.d_tile_cost, cost, n_cost * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    if (list) HIP_TRY(c, hipMemcpyAsync(S.d_tile_list, list, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    const int se = list ? mrt::launch_sort_tile_list(S.d_tile_cost, S.d_tile_list, S.d_tile_order, S.d_sort_scratch, (uint32_t)n, c->stream)
+                        : mrt::launch_sort_tiles(S.d_tile_cost, S.d_tile_order, S.d_sort_scratch, (uint32_t)n, c->stream);
+    if (se) return fail(c, MRT_ERR_HIP, "mrt_debug_sort_tiles: sort launch failed: %s", hipGetErrorString((hipError_t)se));
+    HIP_TRY(c, hipMemcpyAsync(order_out, S.d_tile_order, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+// diagnostic: the last slot's tile costs as its last finalize / blend left them, and the queue order of its most recent launch
+int mrt_debug_read_tile_schedule(mrt_ctx* c, uint32_t* cost_out, uint32_t* order_out, size_t cap, uint32_t* n_out, uint32_t info_out[4]) {
+    if (!c || !n_out || !info_out) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_read_tile_schedule: no scene (call mrt_set_world first)");
+    const size_t n = c->n_tiles;
+    *n_out = c->n_tiles;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_tile_schedule: need %zu values", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, __func__));
+    const mrt_ctx::FrameSlot& S = c->slot[c->last_slot];
+    info_out[0] = S.order_kind; info_out[1] = S.order_n; info_out[2] = S.order_pilot ? 1u : 0u; info_out[3] = c->last_slot;
+    if (cost_out && n) HIP_TRY(c, hipMemcpyAsync(cost_out, S.d_tile_cost, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (order_out && S.order_n) {
+        if (S.order_kind == MRT_TILE_ORDER_INDEX) {
+            for (uint32_t i = 0; i < S.order_n; i++) order_out[i] = i;           // (tile_order null: the kernel takes the queue position)
+        } else {
+            const uint32_t* src = S.order_kind == MRT_TILE_ORDER_LIST ? S.d_tile_list : S.d_tile_order;
+            HIP_TRY(c, hipMemcpyAsync(order_out, src, (size_t)S.order_n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    return mrt::wait_stream(c, c->stream, __func__);
 }
 
 int mrt_debug_last_launch(mrt_ctx* c, uint32_t out[2]) {

@@ -106,6 +106,10 @@ struct mrt_ctx {
         // before the render (the host rewrites it only after the slot's previous render kernel has completed)
         uint32_t* h_tile_list = nullptr;
         uint32_t* d_tile_list = nullptr;
+        // mrt_debug_read_tile_schedule: how the queue of the slot's most recent render launch was ordered (MRT_TILE_ORDER_*),
+        // its length, and whether a pilot launch preceded it.  Written by the launch functions, read by the diagnostic alone.
+        uint32_t order_kind = 0, order_n = 0;
+        bool order_pilot = false;
     } slot[kMaxFrameSlots];
     // Launch width (redraw_frames; the policy itself: width_policy.h): a frame is launched on 1 / width.div of the persistent
     // waves the chip holds and max(2, width.div) x width.mult frames are in flight, so that the chip stays full.  Narrow launches

@@ -148,6 +148,7 @@ def lib(path=None):
                                       C.c_void_p, C.POINTER(CameraRaw), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
                                       C.POINTER(Counters)]
+        L.orc_render_rect_trips.argtypes = L.orc_render_rect.argtypes + [C.c_void_p]
         L.orc_world_hit_batch.argtypes = [C.POINTER(World), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.orc_max_threads.restype = C.c_int
@@ -232,9 +233,10 @@ def lookat_camera(lookfrom, lookat, vup, vfov, defocus_angle, focus_dist):
 
 
 def render_frame(width, height, spp, depth, packed, cam, seeds, shuffle=(0, 0, 0, 0), weight=0.0,
-                 prev=None, rows=None, nthreads=0, counters=None, rng_mode=0, cols=None):
+                 prev=None, rows=None, nthreads=0, counters=None, rng_mode=0, cols=None, trips=None):
     """One pass of fs_main (shader.wgsl:371-386) over rows [rows[0], rows[1]) (and columns [cols[0], cols[1]))
-    -> (H,W,4) f32, row 0 = bottom; texels outside the rectangle stay 0."""
+    -> (H,W,4) f32, row 0 = bottom; texels outside the rectangle stay 0.  trips: an (H,W) uint32 array that gets every
+    rendered pixel's world_hit calls (its bounce-loop trips when depth > 0)."""
     L = Locals()
     L.shape[0], L.shape[1] = width, height
     L.samples_per_frame, L.ray_depth = spp, depth
@@ -250,9 +252,12 @@ def render_frame(width, height, spp, depth, packed, cam, seeds, shuffle=(0, 0, 0
     y0, y1 = (0, height) if rows is None else rows
     raw = camera_derive(cam) if isinstance(cam, Camera) else cam
     x0, x1 = (0, width) if cols is None else cols
-    lib().orc_render_rect(C.byref(L), C.byref(packed.world), _ptr(packed.vec4), _ptr(packed.f32),
-                          _ptr(packed.i32), C.byref(raw), _ptr(seeds), _ptr(prev), _ptr(out),
-                          x0, x1, y0, y1, nthreads, C.byref(counters) if counters is not None else None)
+    if trips is not None:
+        assert trips.shape == (height, width) and trips.dtype == np.uint32 and trips.flags.c_contiguous
+    lib().orc_render_rect_trips(C.byref(L), C.byref(packed.world), _ptr(packed.vec4), _ptr(packed.f32),
+                                _ptr(packed.i32), C.byref(raw), _ptr(seeds), _ptr(prev), _ptr(out),
+                                x0, x1, y0, y1, nthreads, C.byref(counters) if counters is not None else None,
+                                _ptr(trips) if trips is not None else None)
     return out
 
 

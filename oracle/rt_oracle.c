@@ -455,11 +455,12 @@ int orc_max_threads(void) {
 #endif
 }
 
-void orc_render_rect(const orc_locals* locals, const orc_world* world,
-                     const float* vec4, const float* f32, const int32_t* i32,
-                     const orc_camera_raw* cam, const uint32_t* seeds,
-                     const float* prev, float* out,
-                     uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, int nthreads, orc_counters* counters) {
+void orc_render_rect_trips(const orc_locals* locals, const orc_world* world,
+                           const float* vec4, const float* f32, const int32_t* i32,
+                           const orc_camera_raw* cam, const uint32_t* seeds,
+                           const float* prev, float* out,
+                           uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, int nthreads, orc_counters* counters,
+                           uint32_t* trips) {
     scene_t s = {world, vec4, f32, i32};
     orc_counters total; memset(&total, 0, sizeof total);
     if (x1 <= x0 || y1 <= y0) return;
@@ -475,14 +476,26 @@ void orc_render_rect(const orc_locals* locals, const orc_world* world,
 #ifdef _OPENMP
 #pragma omp for schedule(dynamic, 16)
 #endif
-        for (int64_t k = 0; k < n; k++)
-            shade_pixel(locals, &s, cam, seeds, prev, out, x0 + (uint32_t)(k % rw), y0 + (uint32_t)(k / rw), &local);
+        for (int64_t k = 0; k < n; k++) {
+            const uint32_t px = x0 + (uint32_t)(k % rw), py = y0 + (uint32_t)(k / rw);
+            const uint64_t before = local.world_hit_calls;
+            shade_pixel(locals, &s, cam, seeds, prev, out, px, py, &local);
+            if (trips) trips[(size_t)py * locals->shape[0] + px] = (uint32_t)(local.world_hit_calls - before);
+        }
 #ifdef _OPENMP
 #pragma omp critical
 #endif
         counters_add(&total, &local);
     }
     if (counters) counters_add(counters, &total);
+}
+
+void orc_render_rect(const orc_locals* locals, const orc_world* world,
+                     const float* vec4, const float* f32, const int32_t* i32,
+                     const orc_camera_raw* cam, const uint32_t* seeds,
+                     const float* prev, float* out,
+                     uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, int nthreads, orc_counters* counters) {
+    orc_render_rect_trips(locals, world, vec4, f32, i32, cam, seeds, prev, out, x0, x1, y0, y1, nthreads, counters, NULL);
 }
 
 void orc_render_rows(const orc_locals* locals, const orc_world* world,

@@ -144,6 +144,15 @@ void orc_render_rect(const orc_locals* locals, const orc_world* world,
                      const float* prev, float* out,
                      uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, int nthreads, orc_counters* counters);
 
+/* orc_render_rect with one more output: trips (may be NULL; W*H u32, row 0 = bottom) gets, for every pixel of the rectangle,
+ * the world_hit calls of that pixel's samples -- its share of counters->world_hit_calls; other entries are left untouched */
+void orc_render_rect_trips(const orc_locals* locals, const orc_world* world,
+                           const float* vec4, const float* f32, const int32_t* i32,
+                           const orc_camera_raw* cam, const uint32_t* seeds,
+                           const float* prev, float* out,
+                           uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1, int nthreads, orc_counters* counters,
+                           uint32_t* trips);
+
 int orc_max_threads(void);
 
 #ifdef __cplusplus
