@@ -1,29 +1,24 @@
 // Adaptive sampling (mrt_render_tiles / mrt_render_adaptive, include/myraytracer_amd.h "adaptive sampling"): the blend of a frame
 // whose tiles each have their own frame count n_t.  Once a subset frame has been blended, the framebuffer is blended in place
 // (frames.cpp): a subset frame then costs its listed tiles, not the image, and the unlisted tiles keep their texels and S bit for bit.
-// A translation unit of its own, so that kernels.hip -- render_kernel and finalize_kernel / finalize_tracked_kernel -- is unchanged.
+// The steps of the blend are blend.h's, the ones finalize_kernel / finalize_tracked_kernel (kernels.hip) are built from.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
+#include "blend.h"
 
 namespace mrt {
 namespace {
 
-struct alignas(16) PixAcc { float r, g, b; uint32_t cost; };      // kernels.hip's colour sum + cost of one texel
-
-__device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
-__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// one wave per listed tile.  The blend and S update are finalize_kernel<false>'s / finalize_tracked_kernel's, operation for
-// operation (-ffp-contract=off), at the weight mrt_frame_weight(n_t, max_w) computes on the host: so a tile's texels are exactly
-// what a uniform accumulation of its n_t + 1 frames gives.  In place: every texel is read and then written by its own lane.
+// one wave per listed tile.  The same blend and S update as a whole frame's (blend.h), at the weight mrt_frame_weight(n_t, max_w)
+// computes on the host: so a tile's texels are exactly what a uniform accumulation of its n_t + 1 frames gives.  In place:
+// every texel is read and then written by its own lane.
 template <bool TRACKED>
 __global__ void __launch_bounds__(64) tile_blend_kernel(const TileBlendArgs A) {
     const uint32_t lane = threadIdx.x;
     const uint32_t tile = A.list ? A.list[blockIdx.x] : blockIdx.x;
-    const uint32_t tile_x = tile % A.tiles_x, band = tile / A.tiles_x;
-    const uint32_t px = tile_x * kTileW + (lane & 7u);
-    const uint32_t py = band * kBandRows + (lane >> 3);
-    const size_t texel = (size_t)py * A.width + px;
+    uint32_t px, py;
+    size_t texel;
+    blend_locate(lane, tile, A.tiles_x, 1u, 0u, A.width, px, py, texel);      // one context of world 1: local rows are image rows
     const uint32_t nt = A.tile_frames[tile];
     float w = 0.0f;                                                   // mrt_frame_weight (lib.rs:301-304, :424)
     if (nt != 0u) {
@@ -31,36 +26,16 @@ __global__ void __launch_bounds__(64) tile_blend_kernel(const TileBlendArgs A) {
         w = A.max_w < w ? A.max_w : w;
     }
     uint32_t cost = 0;
+    float4* const fb = reinterpret_cast<float4*>(A.fb);
     if (px < A.width && py < A.height) {
-        const PixAcc* acc = reinterpret_cast<const PixAcc*>(A.pix_acc);
-        PixAcc sa = acc[texel];
-        for (uint32_t b = 1; b < A.n_blocks; b++) {
-            const PixAcc sb = acc[(size_t)b * A.pix_stride + texel];
-            sa.r += sb.r; sa.g += sb.g; sa.b += sb.b; sa.cost += sb.cost;
-        }
+        const PixAcc sa = blend_sum_layers(reinterpret_cast<const PixAcc*>(A.pix_acc), texel, A.n_blocks, A.pix_stride);
         cost = sa.cost;
-        const float n = (float)A.spp;
-        const float mr = sa.r / n, mg = sa.g / n, mb = sa.b / n;
-        float4* fb = reinterpret_cast<float4*>(A.fb);
-        const float4 prev = fb[texel];
-        float4 res;
-        res.x = mixf(mr, prev.x, w);
-        res.y = mixf(mg, prev.y, w);
-        res.z = mixf(mb, prev.z, w);
-        res.w = mixf(1.0f, prev.w, w);
-        fb[texel] = res;
-        if (TRACKED) {
-            const float d = lumf(mr, mg, mb) - lumf(prev.x, prev.y, prev.z);
-            const float s = A.noise_s[texel];
-            A.noise_s[texel] = w == 0.0f ? 0.0f : w * (s + (1.0f - w) * (d * d));
-        }
+        blend_texel<TRACKED>(sa, A.spp, w, fb, fb, A.noise_s, texel);
     } else if (px < A.width) {
-        reinterpret_cast<float4*>(A.fb)[texel] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // the last band's rows below the image
-        if (TRACKED) A.noise_s[texel] = 0.0f;
+        blend_padding<TRACKED>(fb, A.noise_s, texel);                 // the last band's rows below the image
     }
-    // the tile's heaviest pixel (finalize_kernel's cost), for the slot's next queue order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const uint32_t o2 = __shfl_xor(cost, off); cost = cost > o2 ? cost : o2; }
+    // the tile's heaviest pixel, for the slot's next queue order
+    cost = blend_max_cost(cost);
     if (lane == 0) {
         A.tile_cost[tile] = cost;
         A.tile_frames[tile] = nt == 0xFFFFFFFFu ? nt : nt + 1u;       // saturating, as frames_done

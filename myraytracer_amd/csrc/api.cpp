@@ -818,7 +818,7 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
     if (c->have_world) {
         if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
             return check_finding(why, cap, "have_world without one of the scene's arrays");
-        if (c->n_members > 1024u && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
+        if (!mrt::scene_is_small(c->n_members) && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
     }
     if (c->noise_on) {
         if (!c->d_noise_s || !c->d_noise_tiles || !c->d_noise_partials) return check_finding(why, cap, "noise tracking is on without S, the tile maps or the scratch");

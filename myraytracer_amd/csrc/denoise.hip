@@ -11,13 +11,13 @@
 // bit for bit in float32 numpy.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
+#include "rt_math.h"
 
 namespace mrt {
 namespace {
 
 constexpr uint32_t kTileX = 32, kTileY = 8;          // one workgroup: 32 x 8 pixels (4 waves of 32 x 2)
 
-__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 // Tukey's biweight: compact support, no transcendental
 __device__ __forceinline__ float tukey(float x) {
     const float u = 1.0f - x * x;

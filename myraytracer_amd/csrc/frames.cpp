@@ -117,7 +117,7 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
             mrt::width_policy_start(c->width, w);
             // a setting this context has already settled at for the same workload returns without trials
             for (const auto& m : c->width_memo)
-                if (m.n_tiles == w.n_tiles && m.spp == w.spp && m.large == (w.n_members > 1024u ? 1u : 0u) && m.counter == w.counter &&
+                if (m.n_tiles == w.n_tiles && m.spp == w.spp && m.large == (mrt::scene_is_small(w.n_members) ? 0u : 1u) && m.counter == w.counter &&
                     m.n_spheres == c->n_spheres) { c->width.div = m.div; c->width.mult = m.mult; c->width.settled = 1u; }
         }
         width_restart_measurement(c);
@@ -216,7 +216,7 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
         mrt::width_policy_step(c->width, w, m);
         if (c->width.settled) {
             if (trace) std::fprintf(stderr, "mrt width: settled at div %u x %u\n", c->width.div, c->width.mult);
-            const mrt_ctx::WidthMemo memo{w.n_tiles, w.spp, w.n_members > 1024u ? 1u : 0u, w.counter, c->n_spheres, c->width.div, c->width.mult};
+            const mrt_ctx::WidthMemo memo{w.n_tiles, w.spp, mrt::scene_is_small(w.n_members) ? 0u : 1u, w.counter, c->n_spheres, c->width.div, c->width.mult};
             bool known = false;
             for (auto& m : c->width_memo)
                 if (m.n_tiles == memo.n_tiles && m.spp == memo.spp && m.large == memo.large && m.counter == memo.counter && m.n_spheres == memo.n_spheres) {

@@ -188,7 +188,7 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
     }
 }
 
-// The boxes of every node (levels 1 .. top), for the walk of large scenes (kernels.hip, box_may_touch).  Node j of level k
+// The boxes of every node (levels 1 .. top), for the walk of large scenes (sweep.h, box_may_touch).  Node j of level k
 // covers the members [j 4^k, (j+1) 4^k) of the hierarchy part of level 0.  The test is "the LINE of the ray passes the box
 // grown by K on every side", three separating axes d x e_i; it must hold whenever the reference's discriminant of a member
 // under the node is computed >= 0, i.e. whenever the line passes within h of the member's centre,
@@ -346,7 +346,7 @@ void build_hierarchy(const float* centers4, const float* radii, uint32_t n, floa
     H.level_base[0] = 0;
     // scenes whose members fit 10-bit ids (the kernel's SMALL variant) keep one level: with <= 256 clusters
     // the sweep is cheap and the bounds of 16 spheres are loose (C3: a ray touches 10 of 38 such bounds)
-    if (H.n_members <= 1024u) max_levels = 1;      // (same test as scene_is_small() in kernels.hip)
+    if (scene_is_small(H.n_members)) max_levels = 1;
     // top_target 0 = automatic: levels are added while the top has more than 256 records -- 128 where the walk tests boxes
     // below the top, which make a smaller top cheaper (round 3: 4,901 spheres 34.1 -> 33.3 ms per 64-spp frame, 10,001 spheres
     // 48.2 -> 47.3; without boxes 1,297 / 2,501 spheres lose 20 % with a top of <= 64)
@@ -406,7 +406,7 @@ static void sweep_origin(const std::vector<mrt::SphereRec>& top, float origin[3]
     for (int k = 0; k < 3; k++) origin[k] = lo[k] <= hi3[k] ? (float)(0.5 * (lo[k] + hi3[k])) : 0.0f;
 }
 
-// The top level once more, as the A operand of the matrix-core sweep (kernels.hip, mfma_sweep_tile): per
+// The top level once more, as the A operand of the matrix-core sweep (sweep.h, mfma_sweep_tile): per
 // tile of 32 records 64 lanes x 8 bf16, lane l = row (l & 31), k = 8 (l >> 5) + j:
 //     k 0..2 C_hi, 3..5 C_hi, 6..8 C_lo, 9..11 (1,1,1), 12..14 Ck (hi, mid, lo), 15: 0
 // where row m of tile t is record 32 t + 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3) -- the order in which the

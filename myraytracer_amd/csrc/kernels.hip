@@ -28,6 +28,8 @@
 //     sample's camera ray for the lanes that need one, sharing the scatter's normalize;
 //   * finalize_kernel turns the per-pixel colour sums into the framebuffer: one coalesced
 //     RGBA32F store per pixel per frame, whole 128-byte lines per 8x8 tile.
+// This file holds render_kernel, the finalize entry points, fill_seeds_kernel, the LDS layout and the launchers; the vector
+// arithmetic and the RNG are rt_math.h, the sweep (both variants) and the box test sweep.h, the steps of the blend blend.h.
 //
 // Arithmetic follows the "MRT-F32" rules: fma only where written, no
 // contraction (-ffp-contract=off), correctly rounded sqrt and divide (hipcc's default expansions, or those
@@ -38,74 +40,28 @@
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
 #include "mrt_device.h"
+#include "sweep.h"
+#include "blend.h"
 
 #include <type_traits>
 
 namespace mrt {
 namespace {
 
-struct V3 { float x, y, z; };
-
-__device__ __forceinline__ V3 v3(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, V3 b) { return v3(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ V3 operator-(V3 a) { return v3(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ V3 operator/(V3 a, float s) { return v3(a.x / s, a.y / s, a.z / s); }
-
-// WGSL dot(): x*x first, then fma in y, then fma in z
-__device__ __forceinline__ float dot3(V3 a, V3 b) {
-    return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));
-}
-// WGSL normalize(e) = e / length(e)
-__device__ __forceinline__ V3 normalize3(V3 v) { return v / __builtin_sqrtf(dot3(v, v)); }
-// WGSL reflect(e1, e2) = e1 - 2*dot(e2, e1)*e2  (shader.wgsl:230)
-__device__ __forceinline__ V3 reflect3(V3 d, V3 n) {
-    float k = 2.0f * dot3(n, d);
-    return v3(d.x - k * n.x, d.y - k * n.y, d.z - k * n.z);
-}
-// WGSL mix(e1, e2, e3) = e1*(1-e3) + e2*e3
-__device__ __forceinline__ float mixf(float a, float b, float t) { return a * (1.0f - t) + b * t; }
-// luminance as noise tracking defines it (finalize_tracked_kernel; noise.hip has the same)
-__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// ---- Xoshiro128+ (shader.wgsl:36-94) -------------------------------------------------
-struct Rng { uint32_t s0, s1, s2, s3; uint32_t draws; };
-
-__device__ __forceinline__ uint32_t rng_next(Rng& r) {          // shader.wgsl:49-64
-    uint32_t result = r.s0 + r.s3;
-    uint32_t t = r.s1 << 9;
-    r.s2 ^= r.s0;
-    r.s3 ^= r.s1;
-    r.s1 ^= r.s2;
-    r.s0 ^= r.s3;
-    r.s2 ^= t;
-    r.s3 = (r.s3 << 11) | (r.s3 >> 21);                          // rotl_u32(.., 11), :36-38
-    return result;
-}
-__device__ __forceinline__ float rng_f32(Rng& r) {               // shader.wgsl:66-69
-    r.draws++;
-    return (float)rng_next(r) * 0x1p-32f;                        // == f32(i) / 4294967296.0
-}
-__device__ __forceinline__ uint32_t fmix32(uint32_t z) {         // MurmurHash3 finaliser (counter mode)
-    z ^= z >> 16; z *= 0x85EBCA6Bu; z ^= z >> 13; z *= 0xC2B2AE35u; z ^= z >> 16;
-    return z;
-}
-// 2.0 * random_f32() - 1.0 (shader.wgsl:86) in one rounding: f32(i) * 2^-32 and the doubling are exact
-// (powers of two, no underflow), so the reference's value is fl(f32(i) * 2^-31 - 1) = this fma, bit for bit
-__device__ __forceinline__ float rng_pm1(Rng& r) {
-    r.draws++;
-    return __builtin_fmaf((float)rng_next(r), 0x1p-31f, -1.0f);
+// The reference's quadratic for the ray (o, d), a = dot(d, d), against the sphere (cx, cy, cz, -(r*r)), sphere_hit
+// shader.wgsl:274-282: b = dot(oc, d), c = |oc|^2 - r^2, and the discriminant b*b - a*c, which is returned.
+__device__ __forceinline__ float sphere_quadratic(float cx, float cy, float cz, float neg_r2, V3 o, V3 d, float a, float& b, float& c) {
+    const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;
+    b = __builtin_fmaf(ocz, d.z, __builtin_fmaf(ocy, d.y, ocx * d.x));
+    c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocx, ocx, neg_r2)));
+    return __builtin_fmaf(b, b, -(a * c));
 }
 // The reference's literal acceptance test, for the index-ordered loop over ALL spheres that rays
 // with a non-finite or non-unit direction take: NaN compares false, so a NaN root is accepted.
 __device__ __forceinline__ void literal_test(const SphereRec s, uint32_t idx, V3 o, V3 d, float a,
                                              float& t_sup, int32_t& best) {
-    V3 oc = v3(o.x - s.cx, o.y - s.cy, o.z - s.cz);
-    float b = dot3(oc, d);
-    float c = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, __builtin_fmaf(oc.x, oc.x, s.neg_r2)));
-    float disc = __builtin_fmaf(b, b, -(a * c));
+    float b, c;
+    const float disc = sphere_quadratic(s.cx, s.cy, s.cz, s.neg_r2, o, d, a, b, c);
     if (!(disc < 0.0f)) {
         float d_sqrt = __builtin_sqrtf(disc);
         const float t_min = 0.001f;
@@ -113,192 +69,6 @@ __device__ __forceinline__ void literal_test(const SphereRec s, uint32_t idx, V3
         if (t < t_min || t_sup <= t) t = (-b + d_sqrt) / a;
         if (!(t < t_min || t_sup <= t)) { t_sup = t; best = (int32_t)idx; }
     }
-}
-
-// ---- the discriminant sweep over wave-uniform sphere records --------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// four SphereRec = 16 dwords = one s_load_dwordx16 from the constant address space
-typedef const f32x16 __attribute__((address_space(4)))* SphQuadPtr;
-struct Sph8 { f32x16 lo, hi; };
-
-// Scalar loads are issued and waited for by hand (inline asm): hipcc schedules every
-// s_load of an unrolled body first and then spills the SGPRs, and its waitcnt pass can only
-// emit lgkmcnt(0) -- scalar loads return out of order -- which would also wait for a
-// prefetch.  An asm load is invisible to that pass, so each group is tied to its own wait:
-// smem_wait() "redefines" the group, and every use of the group therefore follows the wait.
-__device__ __forceinline__ void smem_load8(Sph8& g, SphQuadPtr quads, uint32_t first_sphere) {
-    const SphQuadPtr p = quads + first_sphere / 4u;
-    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40"
-                 : "=&s"(g.lo), "=&s"(g.hi) : "s"(p));
-}
-// One statement = "group `cur` has landed; start fetching group `nxt`".  `bits` (produced by
-// the previous group's tests) rides along so that those tests are scheduled BEFORE this
-// point and the tests of `cur` after it, i.e. while the loads of `nxt` are in flight.
-__device__ __forceinline__ void smem_wait_then_load8(Sph8& cur, Sph8& nxt, SphQuadPtr quads, uint32_t first_sphere,
-                                                     uint32_t& bits) {
-    const SphQuadPtr p = quads + first_sphere / 4u;
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %2, %5, 0x0\n\ts_load_dwordx16 %3, %5, 0x40"
-                 : "+s"(cur.lo), "+s"(cur.hi), "=&s"(nxt.lo), "=&s"(nxt.hi), "+v"(bits) : "s"(p));
-}
-// The sweep's CONSERVATIVE line-vs-bounding-sphere test (10 fp32 VALU + 1 v_alignbit): with `ds` the
-// ray direction stretched by kBoundStretch (1 + 1e-4), S = (oc.ds)^2 - (oc.oc - R^2) is >= 0 whenever the
-// reference's discriminant b*b - a*c (shader.wgsl:277-282) of ANY sphere inside the bound is >= 0:
-// the stretch adds >= 1.9e-4*|oc|^2 of slack against <= 1.2e-4*|oc|^2 of accumulated rounding error
-// and R is 1.5 % larger than the enclosing radius (proof sketch: DESIGN.md §4).  False positives only
-// cost a discriminant evaluation; a false negative cannot happen.  sign(S) is shifted into `bits`.
-__device__ __forceinline__ void test1(float cx, float cy, float cz, float neg_R2, V3 o, V3 ds, uint32_t& bits) {
-    const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;
-    const float b = __builtin_fmaf(ocz, ds.z, __builtin_fmaf(ocy, ds.y, ocx * ds.x));
-    const float c = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocx, ocx, neg_R2)));
-    const float S = __builtin_fmaf(b, b, -c);
-    bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(S), 31);       // oldest record ends in the top bit
-}
-__device__ __forceinline__ void test4(const f32x16 q, V3 o, V3 ds, uint32_t& bits) {
-    test1(q[0], q[1], q[2], q[3], o, ds, bits);
-    test1(q[4], q[5], q[6], q[7], o, ds, bits);
-    test1(q[8], q[9], q[10], q[11], o, ds, bits);
-    test1(q[12], q[13], q[14], q[15], o, ds, bits);
-}
-__device__ __forceinline__ void test8(const Sph8& g, V3 o, V3 ds, uint32_t& bits) {
-    test4(g.lo, o, ds, bits);
-    test4(g.hi, o, ds, bits);
-}
-
-// ---- the walk's second bound for large scenes: the axis-aligned box of the member spheres under a node -----------------
-// A kd-built group of spheres on a plane fills its box, not its bounding sphere: over C5's 100 x 100 grid a ray's LINE touches
-// 7.2 + 7.4 + 1.4 bounding spheres of the three levels but 1.9 + 1.9 + 0.9 boxes (experiments/bound_stats.py).  The test is the
-// line against the box grown by K on every side, through the three separating axes d x e_i:
-//     |p_j d_k - p_k d_j| <= e_j |d_k| + e_k |d_j| + K        p = o - centre, (i, j, k) cyclic
-// (necessary and sufficient for a line and a box; the parts of the line behind the origin are left to the sphere tests).
-// K = kc X + kpad, X = |p|^2 or |p|_1 (per scene), is the slack that makes it CONSERVATIVE against the reference's own
-// rounding: a member whose computed discriminant is >= 0 has the line within sqrt(r^2 + 14 eps |oc|^2 / a) of its centre,
-// i.e. up to min(14 eps |oc|^2 / (2 r), sqrt(14 eps) |oc|) beyond its surface, hence beyond its box; the host (hierarchy.cpp,
-// build_boxes) sets kc per scene and kpad per box so that K covers 1.4143 x that for every member under the node, plus the
-// test's own rounding (4 eps |p|_1; the right-hand side's three roundings are in the extents).  The kernel reads kpad FOLDED
-// INTO THE EXTENTS (e + kpad: on the axis d x e_i that is a slack of kpad (|d_j| + |d_k|), which covers what "+ kpad" covered:
-// hierarchy.cpp, pack_boxes) and kc from its arguments, so a box is 24 bytes.  A never-hit box has extents
-// -3e38: some axis' right-hand side is then hugely negative (a unit direction has a component >= 0.57).
-// 24 VALU: 3 + 3 (X) + 1 (K) + 3 x 5 + 2.
-// (c, e): a BoxRec -- the centre and the half extents with kpad folded in (mrt_internal.h); kc: the scene's coefficient of X.
-template <bool QUAD>
-__device__ __forceinline__ uint32_t box_separated_bits(const V3 c, const V3 e, const float kc, V3 o, V3 d) {
-    const float px = o.x - c.x, py = o.y - c.y, pz = o.z - c.z;
-    const float X = QUAD ? __builtin_fmaf(pz, pz, __builtin_fmaf(py, py, px * px))
-                         : (__builtin_fabsf(px) + __builtin_fabsf(py)) + __builtin_fabsf(pz);
-    const float K = kc * X;
-    const float ex = e.x, ey = e.y, ez = e.z;
-    const float adx = __builtin_fabsf(d.x), ady = __builtin_fabsf(d.y), adz = __builtin_fabsf(d.z);
-    const float sx = __builtin_fmaf(ey, adz, __builtin_fmaf(ez, ady, K)) - __builtin_fabsf(__builtin_fmaf(-pz, d.y, py * d.z));
-    const float sy = __builtin_fmaf(ez, adx, __builtin_fmaf(ex, adz, K)) - __builtin_fabsf(__builtin_fmaf(-px, d.z, pz * d.x));
-    const float sz = __builtin_fmaf(ex, ady, __builtin_fmaf(ey, adx, K)) - __builtin_fabsf(__builtin_fmaf(-py, d.x, px * d.y));
-    // separated on some axis <=> some difference is negative (finite operands: never NaN): the sign bit of the result
-    return __float_as_uint(sx) | __float_as_uint(sy) | __float_as_uint(sz);
-}
-template <bool QUAD>
-__device__ __forceinline__ bool box_may_touch(const V3 c, const V3 e, const float kc, V3 o, V3 d) {
-    return (int32_t)box_separated_bits<QUAD>(c, e, kc, o, d) >= 0;
-}
-
-// ---- the same conservative test on the matrix cores -------------------------------------------------
-// Expanding S = (oc.ds)^2 - (oc.oc - R^2) with oc = o - C turns its two dot products into products of a
-// per-record vector with a per-ray vector:
-//     -(oc.ds) = C.ds - o.ds                 S = (oc.ds)^2 - o.o - U
-//     U        = -2 o.C + (C.C - R^2)
-// i.e. two [32 records] x [32 rays] GEMMs per tile.  The f32 MFMA runs on the vector FMA units (measured:
-// no overlap with VALU work), so the GEMMs run in bf16 on the matrix cores proper, with every f32 factor
-// split into bf16 pieces x = hi + lo (+ mid) and the cross products laid out along K = 16:
-//     k  0..2   C_hi (x,y,z)     . v_hi        v = K ds for the first GEMM, 2 K^2 o for the second
-//     k  3..5   C_hi             . v_lo
-//     k  6..8   C_lo             . v_hi
-//     k  9..11  (1, 1, 1)        . (-K o.ds | -K^2 o.o (minus its slack)), each as hi, mid, lo
-//     k 12..14  Ck (hi, mid, lo) . (0, 0, 0 | -K^2 x (1, 1, 1))       Ck = C.C - R^2 (minus its slack)
-// so ONE A operand per tile serves both; the first GEMM's result g = -K oc.ds, squared where it is positive (the
-// record's centre ahead of the origin), is the C input of the second, which therefore delivers
-// K^2 (max(-oc.ds, 0)^2 - U - o.o) -- K^2 S for a centre ahead, K^2 (R^2 - |oc|^2) otherwise, which drops the bounds
-// that lie entirely behind the origin: one multiply and one alignbit per (ray, record).  K, a power of two chosen by
-// the host so that |g| <= 1/2 (KParams::mfma_scale), only makes the multiply's clamp to [0, 1] act as max(g, 0)^2; a
-// power of two changes no rounding.  What the split drops (C_lo v_lo and the remainders: 3 x 2^-18 of
-// every product) and the f32 accumulation err by at most 2.5e-5 o.o + 5e-5 C.C in S; the
-// test gives away 2^-13 = 1.2e-4 of o.o + C.C + R^2: o.o is scaled by 1 - 2^-13 (in mfma_scale[2]) and the host
-// lowers Ck by 2^-13 (C.C + R^2) (hierarchy.cpp, build_top_mfma).  o and C are taken relative to the centre of the
-// records' bounding box (P.mfma_origin; the rounding of o - origin is relative to the difference), so the
-// slack does not depend on where the scene sits, only on its extent against R: the host selects this
-// variant only where it is small against R^2; elsewhere the SGPR-fed sweep above runs.
-// Operand layout (lane l, r = l & 31, h = l >> 5): A[record r][k = 8h + j], B[k = 8h + j][ray r], j = 0..7;
-// result register i of lane l is record (i&3) + 8(i>>2) + 4h for ray r.  v_permlane32_swap(a, b) =
-// {(a.lo, b.lo), (a.hi, b.hi)} builds the B operands of both 32-ray halves from a lane's own k 0..7 and
-// k 8..15 words and, applied to the two halves' sign words, hands every lane the signs of its OWN ray:
-// r[0] = the records with (row & 4) == 0, r[1] = the others.  The host stores the records of a tile in that
-// order, so r[0] / r[1] are the masks of chunks 2t / 2t+1.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct MfmaRay { u32x4 bp[2], bu[2]; };
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {          // two round-to-nearest conversions
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float bf16_round(float x) { return (float)(__bf16)x; }
-__device__ __forceinline__ void swap32(uint32_t a, uint32_t b, uint32_t& r0, uint32_t& r1) {
-    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    r0 = r[0];
-    r1 = r[1];
-}
-__device__ __forceinline__ void mfma_pack_ray(V3 v, float w0, float w1, float w2, uint32_t y2, uint32_t y3, u32x4 out[2]) {
-    const V3 h = v3(bf16_round(v.x), bf16_round(v.y), bf16_round(v.z));
-    const V3 l = v3(v.x - h.x, v.y - h.y, v.z - h.z);           // exact; rounded to bf16 by the packing below
-    const uint32_t x0 = pk_bf16(h.x, h.y), x1 = pk_bf16(h.z, l.x), x2 = pk_bf16(l.y, l.z);      // k 0..5, 6..7 = x0
-    const uint32_t y0 = pk_bf16(h.z, w0), y1 = pk_bf16(w1, w2);                                   // k 8..11
-    uint32_t a0, a1, a2, a3, b0, b1, b2, b3;
-    swap32(x0, y0, a0, b0);
-    swap32(x1, y1, a1, b1);
-    swap32(x2, y2, a2, b2);
-    swap32(x0, y3, a3, b3);
-    out[0] = u32x4{a0, a1, a2, a3};
-    out[1] = u32x4{b0, b1, b2, b3};
-}
-// `dsk` = K x the stretched direction, o2 = o.o, s2k2 = 2 K^2, nsk2 = -(1 - 2^-13) K^2, nk2 = -K^2 as a bf16 pair, K the
-// power of two of KParams::mfma_scale: the first GEMM comes out as K (C.ds - o.ds) = -K oc.ds, the second as
-// -K^2 (U + o.o) with o.o lowered by its slack.  Scaling by a power of two changes no rounding.
-__device__ __forceinline__ MfmaRay mfma_ray_operands(V3 o, V3 dsk, float o2, float s2k2, float nsk2, uint32_t nk2) {
-    MfmaRay m;
-    const float nk0 = -dot3(o, dsk);
-    const float n0 = bf16_round(nk0), n1 = bf16_round(nk0 - n0), n2 = (nk0 - n0) - n1;    // hi + mid + lo, each difference exact
-    mfma_pack_ray(dsk, n0, n1, n2, 0u, 0u, m.bp);
-    const float k1p = o2 * nsk2;
-    const float q0 = bf16_round(k1p), q1 = bf16_round(k1p - q0), q2 = (k1p - q0) - q1;
-    mfma_pack_ray(v3(s2k2 * o.x, s2k2 * o.y, s2k2 * o.z), q0, q1, q2, nk2, nk2 & 0xFFFFu, m.bu);     // k 12..14: -K^2, k 15: 0
-    return m;
-}
-// one tile of 32 records against the wave's 64 rays; `a` = this lane's 8 bf16 of the tile's A operand
-// (hierarchy.cpp, build_top_mfma).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
-// lane's own ray.
-__device__ __forceinline__ uint32_t mfma_sweep_tile(const u32x4 a, const MfmaRay& m) {
-    const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bf16x8 av = __builtin_bit_cast(bf16x8, a);
-    uint32_t hb[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        // The first GEMM gives g = -K oc.ds: positive where the record's centre lies AHEAD of the origin.  Its square
-        // becomes the C input of the second GEMM -- but only where g > 0: x |x| clamped to [0, 1] (the output modifier
-        // of the same multiply; |g| <= 1/2 by the choice of K) is max(g, 0)^2 -- which then delivers
-        // K^2 (max(-oc.ds, 0)^2 - U - o.o) in the same 16 registers.  For a centre ahead that is K^2 S, the stretched
-        // discriminant, positive for a true candidate by the margin of the slack; for a centre not ahead it is
-        // -K^2 c, c = |oc|^2 - R^2 (inflated, minus the slack): positive only if the origin lies inside the bound.
-        // A bound with its centre not ahead and the origin outside lies entirely behind the origin -- no root of
-        // anything inside it is positive (see the node rounds) -- and is no candidate: candidate = sign bit clear.
-        // (A g that is not > 0 only through rounding has g^2 far below the slack.)
-        f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, m.bp[h]), zero, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 16; i++) acc[i] = __builtin_amdgcn_fmed3f(acc[i] * __builtin_fabsf(acc[i]), 0.0f, 1.0f);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, m.bu[h]), acc, 0, 0, 0);
-        uint32_t bb = 0;
-#pragma unroll
-        for (int i = 0; i < 16; i++) bb = __builtin_amdgcn_alignbit(bb, __float_as_uint(acc[i]), 31);
-        hb[h] = bb;
-    }
-    const auto r = __builtin_amdgcn_permlane32_swap(hb[0], hb[1], false, false);
-    return ~((r[0] << 16) | (r[1] & 0xFFFFu));         // record i of the tile at bit 31 - i
 }
 
 // Candidate masks: per wave kBlockChunks / 2 x 64 lanes of u32 (one sign mask per 32 records -- two chunks, one
@@ -335,6 +105,22 @@ constexpr uint32_t kBlockChunks = 16;     // 16 chunks x 16 clusters x 4 = 1024 
 // (kStackReserve, mrt_internal.h)
 constexpr unsigned long long kNoHitKey = 0x461C4000FFFFFFFFull;   // (bits(1e4f) << 32) | -1
 
+// The owners' side of the walk reads a lane's candidates off its masks one bit at a time.  wm: the 32-record mask word being
+// unpacked, refilled from the block's next non-empty word (a bit of nz) when it has run out; ebase: `owner_bits` | first record id
+// of that word (the block starts at record `first`); the next candidate is wm's highest bit (clz = record within the word).
+__device__ __forceinline__ void refill_mask_word(uint32_t& nz, uint32_t& wm, const uint32_t* masks, uint32_t& ebase,
+                                                 uint32_t owner_bits, uint32_t first) {
+    const uint32_t cc = (uint32_t)__builtin_ctz(nz);
+    nz &= nz - 1u;
+    wm = masks[cc * 64u];
+    ebase = owner_bits | (first + cc * 2u * kChunk);
+}
+__device__ __forceinline__ uint32_t take_mask_bit(uint32_t& wm, uint32_t ebase) {      // wm != 0: owner bits | record id
+    const uint32_t j = (uint32_t)__builtin_clz(wm);
+    wm ^= 0x80000000u >> j;
+    return ebase + j;
+}
+
 template <int N> struct IC { static constexpr int value = N; };
 template <bool SMALL> struct Ent;
 template <> struct Ent<true>  { typedef uint16_t type; static constexpr uint32_t id_bits = 10u; };
@@ -370,10 +156,6 @@ __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }  
 __device__ __forceinline__ uint32_t rank_in(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
-
-// What render_kernel leaves per pixel for finalize_kernel: the colour sum of the frame's samples
-// and the pixel's cost (trips of the bounce loop).
-struct alignas(16) PixAcc { float r, g, b; uint32_t cost; };
 
 // Persistent waves and a global heaviest-first tile queue:
 //  * the grid is as many single-wave workgroups as the chip holds; every wave starts at t = 0
@@ -603,10 +385,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 for (uint32_t j = 0; j < n_direct; j++) {
                     const float cx = C->direct[j].cx, cy = C->direct[j].cy, cz = C->direct[j].cz, nr2 = C->direct[j].neg_r2;
                     const uint32_t sidx = C->direct_index[j];
-                    const float ocx = o.x - cx, ocy = o.y - cy, ocz = o.z - cz;
-                    const float bq = __builtin_fmaf(ocz, d.z, __builtin_fmaf(ocy, d.y, ocx * d.x));
-                    const float cq = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocx, ocx, nr2)));
-                    const float disc = __builtin_fmaf(bq, bq, -(a * cq));
+                    float bq, cq;
+                    const float disc = sphere_quadratic(cx, cy, cz, nr2, o, d, a, bq, cq);
                     const bool cand = !(disc < 0.0f), ahead = (int32_t)(__float_as_uint(bq) | __float_as_uint(cq)) < 0;
                     const bool hq = usable && cand && ahead;
                     const float d_sqrt = sqrt_unscaled(disc);                     // :286
@@ -680,43 +460,28 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 uint32_t wm = 0, ebase = 0;               // owner side: see the unpacking loop
                 uint32_t incl = wave_incl_scan(rem);
                 uint32_t total_rem = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                // owners unpack their masks into `n_new` (owner, top record) items at their scanned positions behind dst[0];
-                // wm: the 32-record mask word being unpacked (clz = record within the word); ebase: owner bits | first record
-                // id of that word.  `room` >= n_new entries are free behind dst.
+                // owners unpack their masks into `n_new` (owner, top record) items at their scanned positions behind dst[0].
+                // `room` >= n_new entries are free behind dst.
                 auto unpack = [&](auto* const dst, const uint32_t room, const uint32_t owner_shift) -> uint32_t {
                     typedef typename std::remove_pointer<decltype(dst)>::type item_t;
                     const uint32_t excl = incl - rem;
                     const uint32_t n_new = total_rem < room ? total_rem : room;
                     item_t* wp = dst + excl;
-                    auto refill = [&]() {
-                        const uint32_t cc = (uint32_t)__builtin_ctz(nz);
-                        nz &= nz - 1u;
-                        wm = masks[cc * 64u];
-                        ebase = (lane << owner_shift) | (blk + cc * 2u * kChunk);
-                    };
                     if (total_rem <= room) {             // the usual case: everything fits, no bound to watch
                         while ((nz | wm) != 0u) {
-                            if (wm == 0u) refill();
-                            const uint32_t j = (uint32_t)__builtin_clz(wm);
-                            wm ^= 0x80000000u >> j;
-                            *wp++ = (item_t)(ebase + j);
+                            if (wm == 0u) refill_mask_word(nz, wm, masks, ebase, lane << owner_shift, blk);
+                            *wp++ = (item_t)take_mask_bit(wm, ebase);
                             // further records of the same word in the same trip: fewer trips, i.e. fewer taken branches
 #pragma unroll
                             for (int more = 0; more < kUnpackMore; more++) {
-                                if (wm != 0u) {
-                                    const uint32_t j2 = (uint32_t)__builtin_clz(wm);
-                                    wm ^= 0x80000000u >> j2;
-                                    *wp++ = (item_t)(ebase + j2);
-                                }
+                                if (wm != 0u) *wp++ = (item_t)take_mask_bit(wm, ebase);
                             }
                         }
                     } else {
                         item_t* const wend = dst + n_new;
                         while ((nz | wm) != 0u && wp < wend) {
-                            if (wm == 0u) refill();
-                            const uint32_t j = (uint32_t)__builtin_clz(wm);
-                            wm ^= 0x80000000u >> j;
-                            *wp++ = (item_t)(ebase + j);
+                            if (wm == 0u) refill_mask_word(nz, wm, masks, ebase, lane << owner_shift, blk);
+                            *wp++ = (item_t)take_mask_bit(wm, ebase);
                         }
                     }
                     rem -= (uint32_t)(wp - (dst + excl));
@@ -725,6 +490,12 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     lds_order();
                     MRT_STAMP(6);
                     return n_new;
+                };
+                // the ray of the lane that owns a work item, from where every lane left its own
+                auto fetch_ray = [&](const uint32_t owner, V3& ro, V3& rd) {
+                    const float4 r0 = rays[2u * owner];
+                    const float2 r1 = *reinterpret_cast<const float2*>(rays + 2u * owner + 1u);
+                    ro = v3(r0.x, r0.y, r0.z), rd = v3(r0.w, r1.x, r1.y);
                 };
                 // root round: the reference's sqrt / divide / range tests (shader.wgsl:286-296) for up to 64 (owner, member)
                 // items.  Each member's root goes into its owner's slot by a 64-bit unsigned minimum of
@@ -736,16 +507,13 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     const bool act = lane < take;
                     const uint32_t it = src[act ? start + lane : 0u];
                     const uint32_t owner = it >> kIdBits, node = it & ((1u << kIdBits) - 1u);
-                    const float4 r0 = rays[2u * owner];
-                    const float2 r1 = *reinterpret_cast<const float2*>(rays + 2u * owner + 1u);
-                    const V3 ro = v3(r0.x, r0.y, r0.z), rd = v3(r0.w, r1.x, r1.y);
+                    V3 ro, rd;
+                    fetch_ray(owner, ro, rd);
                     const float ra = dot3(rd, rd);                      // the owner's `a`, same expression
                     const SphereRec sm = nodes[node];
                     const uint32_t sidx = SMALL ? (uint32_t)index_lds[node] : member_index[node];
-                    const float ocx = ro.x - sm.cx, ocy = ro.y - sm.cy, ocz = ro.z - sm.cz;
-                    const float bq = __builtin_fmaf(ocz, rd.z, __builtin_fmaf(ocy, rd.y, ocx * rd.x));
-                    const float cq = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocx, ocx, sm.neg_r2)));
-                    const float disc = __builtin_fmaf(bq, bq, -(ra * cq));
+                    float bq, cq;
+                    const float disc = sphere_quadratic(sm.cx, sm.cy, sm.cz, sm.neg_r2, ro, rd, ra, bq, cq);
                     // sqrt and the two divisions by `ra` without operand scaling: ra is within 1e-5 of 1 (`weird` rays
                     // own no items), so scaling could only act on a numerator below 2^-102 or above 2^95 -- roots that
                     // fail the range test below whatever their last bits -- and on disc < 2^-96, a d_sqrt below 2^-47
@@ -787,10 +555,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     unsigned long long hm[4];
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
-                        const float ocx = ro.x - sr[q].cx, ocy = ro.y - sr[q].cy, ocz = ro.z - sr[q].cz;
-                        const float bq = __builtin_fmaf(ocz, rd.z, __builtin_fmaf(ocy, rd.y, ocx * rd.x));
-                        const float cq = __builtin_fmaf(ocz, ocz, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocx, ocx, sr[q].neg_r2)));
-                        const float disc = __builtin_fmaf(bq, bq, -(ra * cq));
+                        float bq, cq;
+                        const float disc = sphere_quadratic(sr[q].cx, sr[q].cy, sr[q].cz, sr[q].neg_r2, ro, rd, ra, bq, cq);
                         h[q] = (int32_t)((__float_as_uint(bq) | __float_as_uint(cq)) & ~__float_as_uint(disc)) < 0;
                         hm[q] = __builtin_amdgcn_ballot_w64(h[q]);
                     }
@@ -835,9 +601,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         const bool act = lane < take;
                         const uint32_t it = q1[act ? start + lane : 0u];
                         const uint32_t owner = it >> kIdBits, node = it & ((1u << kIdBits) - 1u);
-                        const float4 r0 = rays[2u * owner];
-                        const float2 r1 = *reinterpret_cast<const float2*>(rays + 2u * owner + 1u);
-                        const V3 ro = v3(r0.x, r0.y, r0.z), rd = v3(r0.w, r1.x, r1.y);
+                        V3 ro, rd;
+                        fetch_ray(owner, ro, rd);
                         qn0 += members_round(nodes + 4u * node, ro, rd, dot3(rd, rd), act, (owner << kIdBits) | (4u * node), q0 + qn0);
                         qn1 = start;
                         if (!PILOT) mtests += kClusterK * take;
@@ -897,15 +662,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                                 auto next_candidate = [&]() -> uint32_t {
                                     uint32_t code = 0u;
                                     if ((nz | wm) != 0u) {
-                                        if (wm == 0u) {
-                                            const uint32_t cc = (uint32_t)__builtin_ctz(nz);
-                                            nz &= nz - 1u;
-                                            wm = masks[cc * 64u];
-                                            ebase = blk + cc * 2u * kChunk;
-                                        }
-                                        const uint32_t j = (uint32_t)__builtin_clz(wm);
-                                        wm ^= 0x80000000u >> j;
-                                        code = 0x80000000u | (ebase + j);
+                                        if (wm == 0u) refill_mask_word(nz, wm, masks, ebase, 0u, blk);
+                                        code = 0x80000000u | take_mask_bit(wm, ebase);
                                     }
                                     return code;
                                 };
@@ -964,9 +722,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         const bool act = lane < take;
                         const uint32_t it = (k == 1 ? clusterq : stack)[act ? start + lane : 0u];
                         const uint32_t owner = it >> 26, g = act ? it & kIndexMask : 0u;
-                        const float4 r0 = rays[2u * owner];
-                        const float2 r1 = *reinterpret_cast<const float2*>(rays + 2u * owner + 1u);
-                        const V3 ro = v3(r0.x, r0.y, r0.z), rd = v3(r0.w, r1.x, r1.y);
+                        V3 ro, rd;
+                        fetch_ray(owner, ro, rd);
                         if (k == 1) {
                             const uint32_t m4 = act ? 4u * (g - P.box_cluster_first) : 0u;
                             rn += members_round(nodes + m4, ro, rd, dot3(rd, rd), act, (owner << 26) | m4, rootq + rn);
@@ -1319,92 +1076,36 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
 
 // After render_kernel: per 8x8 tile, one coalesced pass over the parked colour sums --
 // colour / spp blended with the previous framebuffer (shader.wgsl:383-385), whole 128-byte lines --
-// and the tile's cost (sum of its pixels' bounce-loop trips) for the next frame's queue order.
-template <bool PILOT>
-__global__ void __launch_bounds__(64) finalize_kernel(const KParams P) {
+// and the tile's cost (its heaviest pixel's bounce-loop trips) for the next frame's queue order.  The steps are blend.h's.
+// PILOT: the cost only.  TRACKED (mrt_set_noise_tracking): the blend also updates the per-texel luminance variance S
+// (noise_s, the framebuffer's texel index; shard padding rows stay 0).
+template <bool PILOT, bool TRACKED>
+__device__ __forceinline__ void finalize_body(const KParams& P, float* __restrict__ noise_s) {
     const uint32_t lane = threadIdx.x, tile = blockIdx.x;
     const uint32_t W = P.locals.shape[0], H = P.locals.shape[1];
-    const uint32_t tile_x = tile % P.tiles_x, band = tile / P.tiles_x;
-    const uint32_t px = tile_x * kTileW + (lane & 7u);
-    const uint32_t py = (band * P.shard_world + P.shard_rank) * kBandRows + (lane >> 3);
-    const size_t texel = (size_t)(band * kBandRows + (lane >> 3)) * W + px;
+    uint32_t px, py;
+    size_t texel;
+    blend_locate(lane, tile, P.tiles_x, P.shard_world, P.shard_rank, W, px, py, texel);
     uint32_t cost = 0;
     if (px < W && py < H) {
-        PixAcc sa = reinterpret_cast<const PixAcc*>(P.pix_acc)[texel];
-        // counter-RNG mode: the pixel's blocks of 64 samples were summed separately (possibly by different lanes);
-        // their sums are added in block order -- ((S0 + S1) + S2) ... -- which is how the mode defines the colour
-        for (uint32_t b = 1; b < (PILOT ? 1u : P.n_blocks); b++) {
-            const PixAcc sb = reinterpret_cast<const PixAcc*>(P.pix_acc)[(size_t)b * P.pix_stride + texel];
-            sa.r += sb.r; sa.g += sb.g; sa.b += sb.b; sa.cost += sb.cost;
-        }
+        const PixAcc sa = blend_sum_layers(reinterpret_cast<const PixAcc*>(P.pix_acc), texel, PILOT ? 1u : P.n_blocks, P.pix_stride);
         cost = sa.cost;
-        if (!PILOT) {
-            const float n = (float)P.locals.samples_per_frame;
-            const V3 mean = v3(sa.r / n, sa.g / n, sa.b / n);                       // :383
-            const float w = P.locals.framebuffer_weight;
-            const float4 prev = reinterpret_cast<const float4*>(P.prev)[texel];        // framebuffer_load :366-369
-            float4 res;
-            res.x = mixf(mean.x, prev.x, w);                                        // :385
-            res.y = mixf(mean.y, prev.y, w);
-            res.z = mixf(mean.z, prev.z, w);
-            res.w = mixf(1.0f, prev.w, w);
-            reinterpret_cast<float4*>(P.out)[texel] = res;
-        }
+        if (!PILOT)
+            blend_texel<TRACKED>(sa, P.locals.samples_per_frame, P.locals.framebuffer_weight, reinterpret_cast<const float4*>(P.prev),
+                                 reinterpret_cast<float4*>(P.out), noise_s, texel);
     } else if (!PILOT && px < W) {
-        reinterpret_cast<float4*>(P.out)[texel] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // shard padding rows
+        blend_padding<TRACKED>(reinterpret_cast<float4*>(P.out), noise_s, texel);
     }
-    // A pixel's samples form one sequential chain, so the frame's critical path is its longest
-    // pixel: tiles are ranked by their HEAVIEST pixel, not by their sum.
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const uint32_t o2 = __shfl_xor(cost, off); cost = cost > o2 ? cost : o2; }
+    cost = blend_max_cost(cost);
     if (lane == 0 && P.tile_cost) P.tile_cost[tile] = cost;
     // the slot's tile queue is empty again for its next render launch (which follows this pass: finalize_done)
     if (lane == 0 && tile == 0) *P.tile_queue = 0u;
 }
-
-// finalize_kernel<false> with noise tracking (mrt_set_noise_tracking): the same blend, which also updates the per-texel
-// luminance variance S (noise_s, the framebuffer's texel index; shard padding rows stay 0) by West's weighted recursion with
-// the blend's own weights:
-//   lum(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b,   d = lum(mean) - lum(prev.rgb),
-//   S' = (w == 0.0f) ? 0.0f : w * (S + (1.0f - w) * (d * d))
-// (a select at w == 0: NaN / Inf from before a reset does not survive it).  A kernel of its own rather than a template
-// argument of finalize_kernel, whose arguments and code (byte-identical) are thereby left as they were.
+// the entry points: their names and arguments are what the launchers and the profiles know
+template <bool PILOT>
+__global__ void __launch_bounds__(64) finalize_kernel(const KParams P) { finalize_body<PILOT, false>(P, nullptr); }
 __global__ void __launch_bounds__(64) finalize_tracked_kernel(const KParams P, float* __restrict__ noise_s) {
-    const uint32_t lane = threadIdx.x, tile = blockIdx.x;
-    const uint32_t W = P.locals.shape[0], H = P.locals.shape[1];
-    const uint32_t tile_x = tile % P.tiles_x, band = tile / P.tiles_x;
-    const uint32_t px = tile_x * kTileW + (lane & 7u);
-    const uint32_t py = (band * P.shard_world + P.shard_rank) * kBandRows + (lane >> 3);
-    const size_t texel = (size_t)(band * kBandRows + (lane >> 3)) * W + px;
-    uint32_t cost = 0;
-    if (px < W && py < H) {
-        PixAcc sa = reinterpret_cast<const PixAcc*>(P.pix_acc)[texel];
-        for (uint32_t b = 1; b < P.n_blocks; b++) {
-            const PixAcc sb = reinterpret_cast<const PixAcc*>(P.pix_acc)[(size_t)b * P.pix_stride + texel];
-            sa.r += sb.r; sa.g += sb.g; sa.b += sb.b; sa.cost += sb.cost;
-        }
-        cost = sa.cost;
-        const float n = (float)P.locals.samples_per_frame;
-        const V3 mean = v3(sa.r / n, sa.g / n, sa.b / n);
-        const float w = P.locals.framebuffer_weight;
-        const float4 prev = reinterpret_cast<const float4*>(P.prev)[texel];
-        float4 res;
-        res.x = mixf(mean.x, prev.x, w);
-        res.y = mixf(mean.y, prev.y, w);
-        res.z = mixf(mean.z, prev.z, w);
-        res.w = mixf(1.0f, prev.w, w);
-        reinterpret_cast<float4*>(P.out)[texel] = res;
-        const float d = lumf(mean.x, mean.y, mean.z) - lumf(prev.x, prev.y, prev.z);
-        const float s = noise_s[texel];
-        noise_s[texel] = w == 0.0f ? 0.0f : w * (s + (1.0f - w) * (d * d));
-    } else if (px < W) {
-        reinterpret_cast<float4*>(P.out)[texel] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // shard padding rows
-        noise_s[texel] = 0.0f;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const uint32_t o2 = __shfl_xor(cost, off); cost = cost > o2 ? cost : o2; }
-    if (lane == 0 && P.tile_cost) P.tile_cost[tile] = cost;
-    if (lane == 0 && tile == 0) *P.tile_queue = 0u;
+    finalize_body<false, true>(P, noise_s);
 }
 
 // Seed texture (Subject::new, lib.rs:389-415) generated on the device: SplitMix64 (mrt_device.h) used as a
@@ -1429,8 +1130,6 @@ __global__ void __launch_bounds__(256) fill_seeds_kernel(uint32_t* seeds, uint64
 
 }  // namespace
 
-// SMALL scenes (every node id < 1024): member records live in LDS and work items are u16
-static bool scene_is_small(const KParams& p) { return p.n_members <= 1024u; }
 static uint32_t group_lds_bytes(const KParams& p, bool small) {
     return (small ? p.n_nodes * (uint32_t)sizeof(SphereRec) + lds_index_bytes(p.n_members) : p.box_lds_count * (uint32_t)sizeof(BoxRec)) +
            kWavesPerGroup * lds_wave_bytes(small, p.levels, p.gen_cap, p.mask_chunks);
@@ -1439,7 +1138,7 @@ static uint32_t group_lds_bytes(const KParams& p, bool small) {
 // host: LDS bytes of one workgroup and how many of them one CU holds, for this scene's layout (launch sizing; pinned by
 // tests/test_hierarchy_host.py so that a change of the layout cannot drop residency unnoticed)
 void render_lds_layout(const KParams& p, uint32_t out[2]) {
-    const bool small = scene_is_small(p);
+    const bool small = scene_is_small(p.n_members);
     const uint32_t lds = group_lds_bytes(p, small);
     uint32_t per_cu = (160u * 1024u) / lds;
     if (!small && per_cu > 4u) per_cu = 4u;         // the large-scene kernels are built for 4 waves per SIMD (render_kernel)
@@ -1470,49 +1169,58 @@ uint32_t large_scene_stack_cap(uint32_t mask_chunks, uint32_t box_lds_count) {
     return (((group - shared) / kWavesPerGroup - fixed) / 4u) & ~3u;
 }
 
+// The persistent grid of a launch of at most n_waves waves (from the register-limited occupancy): as many workgroups as are
+// resident with the scene's LDS footprint, and no more waves than tiles.  *lds: the workgroup's dynamic LDS bytes.
+static dim3 persistent_grid(const KParams& p, uint32_t n_waves, uint32_t* lds) {
+    uint32_t lay[2];
+    render_lds_layout(p, lay);
+    *lds = lay[0];
+    const uint32_t cap = p.cus * lay[1] * kWavesPerGroup;
+    if (cap < n_waves) n_waves = cap;
+    const uint32_t want = n_waves < p.n_tiles ? n_waves : p.n_tiles;
+    return dim3((want + kWavesPerGroup - 1) / kWavesPerGroup);
+}
+// The scene's layout and sweep are template arguments of render_kernel: (small / linear / quadratic box slack) x (SGPR-fed /
+// matrix-core sweep), chosen here at run time for the given compile-time COUNT, PILOT, CTR, DBG
+template <bool COUNT, bool PILOT, bool CTR, bool DBG>
+static void launch_render_kernel(const KParams& p, uint32_t n_waves, hipStream_t st) {
+    uint32_t lds;
+    const dim3 grid = persistent_grid(p, n_waves, &lds), block(64 * kWavesPerGroup);
+    auto with_sweep = [&](auto sc) {
+        auto go = [&](auto mfma) {
+            hipLaunchKernelGGL((render_kernel<COUNT, PILOT, CTR, decltype(sc)::value, decltype(mfma)::value != 0, DBG>), grid, block, lds, st, p);
+        };
+        if (p.use_mfma != 0) go(IC<1>{}); else go(IC<0>{});
+    };
+    if (scene_is_small(p.n_members)) with_sweep(IC<0>{});
+    else if (p.box_quad != 0) with_sweep(IC<2>{});
+    else with_sweep(IC<1>{});
+}
+
 // the persistent render waves (pilot: + its cost-only finalize) on `stream`
 int launch_render(const KParams& p, bool pilot, uint32_t n_waves, void* stream, uint32_t* which) {
     if (which) *which = 0xFFFFFFFFu;
     if (p.n_tiles == 0 || n_waves == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     // (the queue counter is zero: reset at allocation and by every finalize pass of the slot)
-    const bool small = scene_is_small(p);
-    // persistent grid: as many workgroups as are resident with this launch's LDS footprint
-    // (n_waves comes from the register-limited occupancy)
-    uint32_t lay[2];
-    render_lds_layout(p, lay);
-    const uint32_t lds = lay[0];
-    {
-        const uint32_t cap = p.cus * lay[1] * kWavesPerGroup;
-        if (cap < n_waves) n_waves = cap;
-    }
-    const uint32_t want = n_waves < p.n_tiles ? n_waves : p.n_tiles;
-    dim3 grid((want + kWavesPerGroup - 1) / kWavesPerGroup), block(64 * kWavesPerGroup);
+    const bool small = scene_is_small(p.n_members);
     const bool ctr = p.locals.rng_mode == MRT_RNG_COUNTER;
     const bool mfma = p.use_mfma != 0, quad = p.box_quad != 0;
-#define MRT_LAUNCH(C_, P_, R_)                                                                                      \
-    do {                                                                                                            \
-        if (small && mfma) hipLaunchKernelGGL((render_kernel<C_, P_, R_, 0, true>), grid, block, lds, st, p);       \
-        else if (small) hipLaunchKernelGGL((render_kernel<C_, P_, R_, 0, false>), grid, block, lds, st, p);         \
-        else if (quad && mfma) hipLaunchKernelGGL((render_kernel<C_, P_, R_, 2, true>), grid, block, lds, st, p);   \
-        else if (quad) hipLaunchKernelGGL((render_kernel<C_, P_, R_, 2, false>), grid, block, lds, st, p);          \
-        else if (mfma) hipLaunchKernelGGL((render_kernel<C_, P_, R_, 1, true>), grid, block, lds, st, p);           \
-        else hipLaunchKernelGGL((render_kernel<C_, P_, R_, 1, false>), grid, block, lds, st, p);                    \
-    } while (0)
     // which instantiation this is, for mrt_debug_last_launch: bit 0 COUNT, 1 PILOT, 2 CTR, 3 SMALL, 4 MFMA, 5 quadratic box slack
     if (which) *which = ((!pilot && p.count_draws) ? 1u : 0u) | (pilot ? 2u : 0u) | (ctr ? 4u : 0u) | (small ? 8u : 0u) | (mfma ? 16u : 0u) |
                         ((!small && quad) ? 32u : 0u);
     if (pilot) {
-        if (ctr) MRT_LAUNCH(false, true, true); else MRT_LAUNCH(false, true, false);
+        if (ctr) launch_render_kernel<false, true, true, false>(p, n_waves, st);
+        else launch_render_kernel<false, true, false, false>(p, n_waves, st);
         hipLaunchKernelGGL((finalize_kernel<true>), dim3(p.n_tiles), dim3(64), 0, st, p);
     } else if (ctr) {
-        if (p.count_draws) MRT_LAUNCH(true, false, true); else MRT_LAUNCH(false, false, true);
+        if (p.count_draws) launch_render_kernel<true, false, true, false>(p, n_waves, st);
+        else launch_render_kernel<false, false, true, false>(p, n_waves, st);
     } else if (p.count_draws) {
-        MRT_LAUNCH(true, false, false);
+        launch_render_kernel<true, false, false, false>(p, n_waves, st);
     } else {
-        MRT_LAUNCH(false, false, false);
+        launch_render_kernel<false, false, false, false>(p, n_waves, st);
     }
-#undef MRT_LAUNCH
     return (int)hipGetLastError();
 }
 
@@ -1522,22 +1230,7 @@ int launch_debug_world_hit(const KParams& p, uint32_t n_waves, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(p.tile_queue, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return (int)e;
-    const bool small = scene_is_small(p);
-    uint32_t lay[2];
-    render_lds_layout(p, lay);
-    const uint32_t lds = lay[0];
-    const uint32_t cap = p.cus * lay[1] * kWavesPerGroup;
-    if (cap < n_waves) n_waves = cap;
-    const uint32_t want = n_waves < p.n_tiles ? n_waves : p.n_tiles;
-    dim3 grid((want + kWavesPerGroup - 1) / kWavesPerGroup), block(64 * kWavesPerGroup);
-    const bool mfma = p.use_mfma != 0;
-    const bool quad = p.box_quad != 0;
-    if (small && mfma) hipLaunchKernelGGL((render_kernel<false, false, false, 0, true, true>), grid, block, lds, st, p);
-    else if (small) hipLaunchKernelGGL((render_kernel<false, false, false, 0, false, true>), grid, block, lds, st, p);
-    else if (quad && mfma) hipLaunchKernelGGL((render_kernel<false, false, false, 2, true, true>), grid, block, lds, st, p);
-    else if (quad) hipLaunchKernelGGL((render_kernel<false, false, false, 2, false, true>), grid, block, lds, st, p);
-    else if (mfma) hipLaunchKernelGGL((render_kernel<false, false, false, 1, true, true>), grid, block, lds, st, p);
-    else hipLaunchKernelGGL((render_kernel<false, false, false, 1, false, true>), grid, block, lds, st, p);
+    launch_render_kernel<false, false, false, true>(p, n_waves, st);
     return (int)hipGetLastError();
 }
 

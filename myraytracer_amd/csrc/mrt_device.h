@@ -1,4 +1,4 @@
-// Device-side helpers shared by kernels.hip (the render path) and debug_kernels.hip (the diagnostic kernels that test
+// Device-side arithmetic helpers (rt_math.h has the vectors and the RNG) shared by kernels.hip (the render path) and debug_kernels.hip (the diagnostic kernels that test
 // them): the correctly rounded division / square root without their operand-scaling steps, the per-wave operand tests
 // of their two tested call sites, and the counter-based SplitMix64 of the seed texture.  Internal: not installed.
 #pragma once

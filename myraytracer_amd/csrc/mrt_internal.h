@@ -1,4 +1,4 @@
-// Internal types shared by the HIP kernels (kernels.hip) and the host side of the C ABI
+// Internal types shared by the HIP kernels (kernels.hip and the files beside it) and the host side of the C ABI
 // (api.cpp and the files beside it).  Not installed; the public contract is include/myraytracer_amd.h.
 #pragma once
 #include <stdint.h>
@@ -22,6 +22,9 @@ constexpr uint32_t kMaxFrameBatch = 32;   // frames one render launch may cover 
 constexpr uint32_t kQueueCap = 320;      // a work queue of the walk: < 64 left over + 4 x 64 pushed by one round
 constexpr uint32_t kStackReserve = 16;   // large scenes' work stack: entries beyond its capacity a one-item round may use (3 per level)
 constexpr uint32_t kMaxDirect = 4;       // very large spheres tested by every ray directly, outside the hierarchy
+// SMALL scenes (render_kernel's SC == 0): every node id of the hierarchy's n_members member slots fits 10 bits, so the hierarchy
+// has one level, the member records live in LDS and the walk's work items are u16; larger scenes walk the boxes
+inline bool scene_is_small(uint32_t n_members) { return n_members <= 1024u; }
 
 // (cx, cy, cz, -(r*r)): the only per-sphere data the discriminant loop reads.  Derived on
 // the host from the reference's SoA arrays (centres: vec4_f32_data, radii: f32_data;
@@ -60,7 +63,7 @@ struct KParams {
     // records (multiple of kGroup, padded with never-hit entries).  `nodes` holds levels 0..levels-1,
     // level k at level_base[k]; member_index[] is each member's index in the reference's sphere order.
     const SphereRec* clusters;
-    // the same top-level records as the A operand of the matrix-core sweep (kernels.hip, mfma_sweep_tile):
+    // the same top-level records as the A operand of the matrix-core sweep (sweep.h, mfma_sweep_tile):
     // per tile of 32 records 64 lanes x 8 bf16, record order within a tile permuted to the result layout;
     // use_mfma selects that variant of the sweep (world.cpp decides per scene and camera)
     const uint16_t* top_mfma;
@@ -68,7 +71,7 @@ struct KParams {
     float mfma_origin[3];       // the records of top_mfma are relative to this point (centre of their bounding box)
     // The ray-side factors of the matrix-core sweep (world.cpp, fill_scene_params): with K a power of two such that
     // |K oc.ds| <= 1/2 for every ray the sweep admits, {kBoundStretch K, 2 K^2, -(1 - 2^-13) K^2, the largest admitted
-    // |o - mfma_origin|^2}, and -K^2 as a pair of bf16 (kernels.hip, mfma_ray_operands)
+    // |o - mfma_origin|^2}, and -K^2 as a pair of bf16 (sweep.h, mfma_ray_operands)
     float mfma_scale[4];
     uint32_t mfma_neg_k2_pair;
     // The sweep's space: the GEMMs see x' = mfma_axis (x - mfma_origin) per component, entries 1, 2 or 4 chosen per scene so
@@ -207,11 +210,11 @@ int launch_noise_reduce_tiles(const float* S, const float* rgba, uint32_t width,
 
 // adaptive.hip (include/myraytracer_amd.h, "adaptive sampling"): the per-tile blend of a frame whose tiles have their own frame
 // counts.  One wave per tile of `list` (null: every tile 0 .. n - 1), in place on `fb` (and S with noise_s): w =
-// mrt_frame_weight(tile_frames[t], max_w) as the same float expression, the blend and S update of finalize_kernel<false> /
-// finalize_tracked_kernel, then tile_frames[t] += 1 (saturating) and tile_cost[t]; the first wave zeroes *tile_queue.  One
+// mrt_frame_weight(tile_frames[t], max_w) as the same float expression, the blend and S update finalize_kernel<false> /
+// finalize_tracked_kernel are built from (blend.h), then tile_frames[t] += 1 (saturating) and tile_cost[t]; the first wave zeroes *tile_queue.  One
 // context of world 1: local rows are image rows.
 struct TileBlendArgs {
-    const void* pix_acc;        // PixAcc per texel and layer (kernels.hip): n_blocks layers pix_stride apart, added in order
+    const void* pix_acc;        // PixAcc per texel and layer (blend.h): n_blocks layers pix_stride apart, added in order
     uint32_t pix_stride, n_blocks;
     float* fb;                  // RGBA32F, width x (8 x bands) texels, blended in place
     float* noise_s;             // S per texel, or null (tracking off)

@@ -4,9 +4,10 @@
 //   var_p = S_p * (float)K,  se_p = sqrtf(var_p),  L_p = lum(fb_p),  rel_p = se_p / fmaxf(L_p, floor),  above = rel_p > threshold
 // with K = +inf ("no estimate yet") giving se_p = +inf without forming 0 * inf.  A pixel whose S or L is not finite counts in
 // non_finite only.  Deterministic: every block writes its partial sums, a single-block pass adds them in block order; no
-// float atomics.  A translation unit of its own, outside the render path's (kernels.hip).  Memory-bound: 20 B per pixel.
+// float atomics.  lum() is rt_math.h's, the one the blend's S update uses (blend.h).  Memory-bound: 20 B per pixel.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
+#include "rt_math.h"
 
 namespace mrt {
 namespace {
@@ -20,8 +21,6 @@ struct NoisePartial {                                // 32 B, one per block
     uint32_t pixels, non_finite, above;
     float max_se;
 };
-
-__device__ __forceinline__ float lumf(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

@@ -9,6 +9,7 @@
 // the measured lane utilisation is low, and kept only if the measured frame rate rises by 3 %.
 #pragma once
 #include <stdint.h>
+#include "mrt_internal.h"
 
 namespace mrt {
 
@@ -18,7 +19,7 @@ struct WidthWorkload {
     uint32_t max_slots;     // most frames that can be in flight (mrt_ctx::kMaxFrameSlots, capped by the hardware queues)
                             // (a launch is never narrower than 1 / kMaxWidthDiv, whatever max_slots)
     uint32_t spp;           // samples per pixel and frame
-    uint32_t n_members;     // member slots of the scene's hierarchy (> 1,024: the large-scene kernels)
+    uint32_t n_members;     // member slots of the scene's hierarchy (!scene_is_small: the large-scene kernels)
     uint32_t counter;       // counter-RNG mode
 };
 
@@ -72,7 +73,7 @@ inline void width_policy_start(WidthState& s, const WidthWorkload& w) {
     s = WidthState();
     // (... a quarter for large scenes, whose pixels' chains differ 10 x: C5's 1/2 share 4,121 Msamples/s at a half x 2, 4,447 at a
     // quarter x 2; C5 and scenes of 1,297 to 4,901 spheres the same within 1 % either way: profiles/r05_schedule_sweep.txt)
-    const uint32_t spare = (w.n_members > 1024u && slots >= 8u) ? 4u : 2u;
+    const uint32_t spare = (!scene_is_small(w.n_members) && slots >= 8u) ? 4u : 2u;
     s.div = starved ? narrowest : short_chains ? width_min_u32(4u, slots) : (!w.counter && w.n_tiles >= 3u * w.n_waves) ? spare : 1u;
     if (!short_chains) s.mult = width_mult_for(s.div, slots);
 }

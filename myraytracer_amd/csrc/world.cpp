@@ -40,7 +40,7 @@ void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
     {
         p.use_mfma = use_matrix_core_sweep(c) ? 1u : 0u;
         for (int k = 0; k < 3; k++) p.mfma_origin[k] = c->mfma_origin[k];
-        // The sweep squares K oc.ds through an instruction that saturates at 1 (kernels.hip, mfma_sweep_tile), K a power of
+        // The sweep squares K oc.ds through an instruction that saturates at 1 (sweep.h, mfma_sweep_tile), K a power of
         // two: rays start on the camera's lens or on a sphere, i.e. within `all` of mfma_origin; the sweep admits origins up
         // to 4 x that (others take the literal loop), records lie within `all`, |ds| < 1.001: |K oc.ds| < 5.01 all K <= 1/2.
         // All of it in the sweep's space, x' = mfma_axis (x - mfma_origin): that is where the GEMMs run.
@@ -63,8 +63,8 @@ void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
     }
     p.levels = c->levels; p.n_nodes = c->n_nodes; p.n_members = c->n_members;
     // small scenes: the top queue holds a ray's candidates among ALL top records; large scenes: the wave's one work stack
-    p.box_lds_count = c->n_members <= 1024u ? 0u : mrt::large_scene_box_lds_count(c->n_padded, c->levels, p.mask_chunks, mrt::kBoxLdsCap);
-    p.gen_cap = c->n_members <= 1024u ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    p.box_lds_count = mrt::scene_is_small(c->n_members) ? 0u : mrt::large_scene_box_lds_count(c->n_padded, c->levels, p.mask_chunks, mrt::kBoxLdsCap);
+    p.gen_cap = mrt::scene_is_small(c->n_members) ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
     for (uint32_t k = 0; k < mrt::kMaxLevels; k++) p.level_base[k] = c->level_base[k];
     // large scenes only (kernels.hip: !SMALL): every node's box, in the kernel's top-down numbering
     p.boxes = c->boxes_mode == 0 ? c->d_boxes_open : c->d_boxes;
@@ -144,7 +144,7 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
     MRT_TRY(upload((void**)&c->d_spheres, recs.data(), recs.size() * sizeof(mrt::SphereRec)));
     MRT_TRY(upload((void**)&c->d_clusters, hier.top.data(), hier.top.size() * sizeof(mrt::SphereRec)));
     MRT_TRY(upload((void**)&c->d_nodes, hier.nodes.data(), hier.nodes.size() * sizeof(mrt::SphereRec)));
-    if (hier.n_members > 1024u) {           // large scenes (the kernel's !SMALL layouts) walk the boxes
+    if (!mrt::scene_is_small(hier.n_members)) {           // large scenes (the kernel's !SMALL layouts) walk the boxes
         std::vector<mrt::BoxFull> full;
         std::vector<mrt::BoxRec> dev;
         boxes_top_down(hier, false, full, &c->box_cluster_first, &c->box_cluster_parent_first);
@@ -354,8 +354,8 @@ int mrt_debug_lds_layout(uint32_t n_members, uint32_t n_nodes, uint32_t levels, 
     std::memset(&p, 0, sizeof p);
     p.n_members = n_members; p.n_nodes = n_nodes; p.levels = levels; p.n_padded = n_top_padded;
     { const uint32_t ch = (n_top_padded + mrt::kChunk - 1) / mrt::kChunk; p.mask_chunks = ch < 16u ? ch : 16u; }
-    p.box_lds_count = n_members <= 1024u ? 0u : mrt::large_scene_box_lds_count(n_top_padded, levels, p.mask_chunks, mrt::kBoxLdsCap);
-    p.gen_cap = n_members <= 1024u ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    p.box_lds_count = mrt::scene_is_small(n_members) ? 0u : mrt::large_scene_box_lds_count(n_top_padded, levels, p.mask_chunks, mrt::kBoxLdsCap);
+    p.gen_cap = mrt::scene_is_small(n_members) ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
     uint32_t lay[2];
     mrt::render_lds_layout(p, lay);
     out[0] = lay[0]; out[1] = lay[1]; out[2] = p.gen_cap;

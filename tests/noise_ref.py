@@ -14,7 +14,7 @@ def lum(rgb: np.ndarray) -> np.ndarray:
 
 
 def blend(mean: np.ndarray, prev: np.ndarray, w: float) -> np.ndarray:
-    """mixf(mean, prev, w) per channel, alpha from 1 (kernels.hip, finalize_kernel)."""
+    """mixf(mean, prev, w) per channel, alpha from 1 (blend.h, blend_texel)."""
     w = F(w)
     out = np.empty_like(prev)
     out[..., :3] = mean[..., :3] * (F(1) - w) + prev[..., :3] * w

@@ -131,7 +131,7 @@ def fma32(a, b, c):
 
 
 def dot32(a, b):
-    """kernels.hip dot3"""
+    """rt_math.h dot3"""
     return fma32(a[..., 2], b[..., 2], fma32(a[..., 1], b[..., 1], f32(a[..., 0] * b[..., 0])))
 
 

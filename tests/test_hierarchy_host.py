@@ -122,7 +122,7 @@ def test_matrix_core_operand_restates_the_top_level_with_its_slack(mrt):
 
 
 def bf16_round(x):
-    """round-to-nearest-even of float32 values to bf16, returned as float32 (kernels.hip bf16_round)"""
+    """round-to-nearest-even of float32 values to bf16, returned as float32 (sweep.h bf16_round)"""
     u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
     u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
     return u.astype(np.uint32).view(np.float32)
@@ -136,7 +136,7 @@ def split3(x):
 
 
 def test_matrix_core_sweep_algebra_is_conservative_and_drops_only_what_lies_behind(mrt):
-    """The sweep's two GEMMs (kernels.hip mfma_ray_operands / mfma_sweep_tile) restated in numpy from the very A operand the
+    """The sweep's two GEMMs (sweep.h mfma_ray_operands / mfma_sweep_tile) restated in numpy from the very A operand the
     host uploads and the scale factors it passes (mrt_debug_mfma_scale): g = A.B1 = -K oc.ds, C = clamp(g |g|) = max(g, 0)^2,
     result = A.B2 + C = K^2 (max(-oc.ds, 0)^2 - U - o.o), candidate = result not < 0.  Products of bf16 pieces are exact in
     float64 here (the hardware accumulates in f32; that error is what the 2^-13 slack is for).  Every top-level bound whose
@@ -218,7 +218,7 @@ def build_boxes(mrt, sc, max_levels=4, top_target=256):
 
 def test_every_box_encloses_the_spheres_under_it_and_its_slack_covers_the_discriminants_rounding(mrt):
     """The walk of large scenes tests the LINE of a ray against the axis-aligned box of the member spheres under a node, grown
-    by K = kc X + kpad (kernels.hip box_may_touch, hierarchy.cpp build_boxes).  Host-side facts the conservativeness rests on:
+    by K = kc X + kpad (sweep.h box_may_touch, hierarchy.cpp build_boxes).  Host-side facts the conservativeness rests on:
     node j of level k covers the members [j 4^k, (j+1) 4^k); its box (f32 centre, extents measured from it) contains every
     member sphere; the boxes of a level line up with the level's records (same count, never-hit where the record is); and for
     ray origins at any distance the slack is at least 1.4143 x how far beyond a member's surface the line of a ray with a

@@ -225,7 +225,7 @@ def test_scene_file_errors_name_the_line(mrt, tmp_path):
 
 
 def test_matrix_core_sweep_scale_keeps_the_clamp_from_saturating(mrt):
-    """hierarchy.cpp mfma_scales: the sweep squares g = K oc.ds with an instruction that clamps to [0, 1] (kernels.hip,
+    """hierarchy.cpp mfma_scales: the sweep squares g = K oc.ds with an instruction that clamps to [0, 1] (sweep.h,
     mfma_sweep_tile), so K must be a power of two (no rounding changes) with |g| <= 1/2 for every admitted ray: origins up
     to 4 x reach, records within reach, |ds| < 1.001."""
     import ctypes as C
