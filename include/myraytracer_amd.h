@@ -210,6 +210,25 @@ int mrt_set_world_raw(mrt_ctx* ctx, const void* world, size_t world_bytes,
                       const int32_t* i32_data, size_t n_i32);
 /* api::World { spheres } (lib.rs:611-639) -> packs with mrt_pack_world, then uploads */
 int mrt_set_world(mrt_ctx* ctx, const mrt_sphere* spheres, size_t n);
+/* New centres and radii for spheres [first, first + count) of the current scene; xyzr = count x (cx, cy, cz, radius).
+ * Materials, the sphere count and the hierarchy's grouping stay: the host does O(count) work, and everything derived from the
+ * spheres (member records, every level's bounds, the boxes of large scenes, the matrix-core sweep's operand) is recomputed by
+ * kernels queued on the ctx's stream.  No buffer is freed or allocated and nothing is built on the host.
+ *   Refusals, each before anything is changed or queued: MRT_ERR_NO_SCENE without a scene; MRT_ERR_INVALID_ARG if first + count
+ *     exceeds the sphere count or xyzr is NULL with count > 0; MRT_ERR_BAD_SCENE for a value that is not finite or beyond 1e7 in
+ *     magnitude (the rule of mrt_set_world_raw).  count == 0: MRT_OK, nothing queued.
+ *   Negative radii stay legal (hollow glass): bounds use |r|, the stored radius and -(r r) are the caller's value.
+ *   Ordering: frames queued before the call render the old geometry, frames queued after it the new one.  The call does not
+ *     wait on the host for the frames in flight; xyzr may be reused as soon as it returns.
+ *   The accumulation is not restarted (only mrt_reset does that, as for mrt_set_world); the denoiser's guides are marked stale.
+ *   The launch schedule is not restarted and the tile costs stay valid: a caller that updates every frame still reaches a
+ *     settled schedule (mrt_get_schedule), and a pinned hint stays as it is.
+ *   Regrouping: the bounds only get looser as spheres leave the groups they were built in.  The image never changes, only the
+ *     speed; mrt_read_counters' member_tests per world_hit_calls is the signal to watch, and mrt_set_world* regroups.
+ *   The matrix-core sweep runs in the world's own space (no per-scene axis scale) after an update; the scaled space comes back
+ *     with the next mrt_set_world*.
+ *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as a failed mrt_set_world* does. */
+int mrt_update_spheres(mrt_ctx* ctx, uint32_t first, uint32_t count, const float* xyzr);
 /* The AoS -> SoA packing of lib.rs:722-799 (host only, no GPU needed).  Capacities are
  * in elements (vec4: 4 floats each); returns MRT_ERR_TOO_SMALL if any is short.
  * Needs at most 2n vec4, 2n f32, 2n i32. */

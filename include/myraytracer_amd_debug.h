@@ -210,6 +210,17 @@ int mrt_debug_last_set_world_ms(mrt_ctx* ctx, float* ms);
  * tests/test_gpu_failure_paths.py calls it after every refused resource creation, before anything else is launched; the
  * state-machine sequences (tests/state_sequences.py) end with it. */
 int mrt_debug_check_context(mrt_ctx* ctx, char* why, size_t cap);
+/* Diagnostic: the scene's hierarchy as the device holds it, read back behind the ctx's stream (after every mrt_update_spheres
+ * queued so far).  info[16] = {levels, top records, nodes, member slots, direct spheres, direct_first, level_base[4], boxes (0 for
+ * a small scene), box_quad, spheres, box_cluster_first, box_cluster_parent_first, the build's matrix-core verdict}; a first call
+ * with every array NULL gives the sizes.  scalars[8] = {box_kc, the sweep's origin xyz, its axes xyz, its reach}; direct_out =
+ * 4 x 4 floats, direct_index_out = 4: the direct spheres' records as the kernel arguments carry them.  Arrays (each may be
+ * NULL): top 4 floats a record; nodes 4 floats; member_index; boxes and boxes_open 6 floats a box in the kernel's top-down
+ * numbering; the A operand 512 u16 per tile of 32 top records; and the four copies of the spheres' geometry -- spheres (4
+ * floats), shade (8 floats), the SoA's centres (4 floats) and radii.  MRT_ERR_NO_SCENE without a scene. */
+int mrt_debug_read_hierarchy(mrt_ctx* ctx, uint32_t info[16], double scalars[8], float* direct_out, uint32_t* direct_index_out,
+                             float* top_out, float* nodes_out, uint32_t* member_index_out, float* boxes_out, float* boxes_open_out,
+                             uint16_t* mfma_out, float* spheres_out, float* shade_out, float* centres_out, float* radii_out);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ LIB_PATH = os.environ.get("MRT_LIB_OVERRIDE") or os.path.join(_HERE, "lib", "lib
 # declare (tests/test_abi.py checks this list against both headers and against the loaded library)
 EXPORTS = [
     "mrt_args_default", "mrt_args_resolve_size", "mrt_create", "mrt_destroy", "mrt_set_shard",
-    "mrt_set_stream", "mrt_set_world_raw", "mrt_set_world", "mrt_pack_world", "mrt_set_camera",
+    "mrt_set_stream", "mrt_set_world_raw", "mrt_set_world", "mrt_update_spheres", "mrt_pack_world", "mrt_set_camera",
     "mrt_camera_derive", "mrt_set_seeds", "mrt_read_seeds", "mrt_redraw", "mrt_render", "mrt_sync",
     "mrt_reset", "mrt_get_locals", "mrt_set_rng_shuffle", "mrt_set_samples_per_frame", "mrt_set_rng_mode",
     "mrt_frames_done", "mrt_frame_weight", "mrt_frame_shuffle", "mrt_pixel_seed", "mrt_shard_info",
@@ -45,7 +45,7 @@ EXPORTS = [
     "mrt_denoise_params_default", "mrt_set_denoise_params", "mrt_get_denoise_params", "mrt_read_denoised", "mrt_debug_denoise",
     "mrt_debug_read_guides", "mrt_set_denoise_variance", "mrt_get_denoise_variance", "mrt_debug_denoise_variance",
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
-    "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule",
+    "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule", "mrt_debug_read_hierarchy",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -232,6 +232,7 @@ def load():
         "mrt_set_stream": (i32, [vp, vp]),
         "mrt_set_world_raw": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, sz]),
         "mrt_set_world": (i32, [vp, vp, sz]),
+        "mrt_update_spheres": (i32, [vp, u32, u32, vp]),
         "mrt_pack_world": (i32, [vp, sz, P(MrtWorld), vp, sz, P(sz), vp, sz, P(sz), vp, sz, P(sz)]),
         "mrt_set_camera": (i32, [vp, P(MrtCamera)]),
         "mrt_camera_derive": (i32, [P(MrtCamera), P(MrtCameraRaw)]),
@@ -337,6 +338,7 @@ def load():
         "mrt_debug_check_context": (i32, [vp, C.c_char_p, sz]),
         "mrt_debug_sort_tiles": (i32, [vp, vp, sz, vp, sz, vp]),
         "mrt_debug_read_tile_schedule": (i32, [vp, vp, vp, sz, P(u32), P(u32)]),
+        "mrt_debug_read_hierarchy": (i32, [vp] * 15),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

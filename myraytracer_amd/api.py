@@ -294,6 +294,43 @@ class State:
         self._check(self._L.mrt_set_world_raw(self._ctx, wbuf, len(wbuf), vec4.ctypes.data, len(vec4), f32.ctypes.data,
                                               len(f32), i32.ctypes.data, len(i32)), "mrt_set_world_raw")
 
+    def update_spheres(self, first: int, xyzr):
+        """mrt_update_spheres: new (cx, cy, cz, radius) for spheres first .. first + len(xyzr) - 1 of the current scene -- any
+        (count, 4) array; materials and the hierarchy's grouping stay, the derived arrays are refitted on the device in stream
+        order and nothing waits for the frames in flight."""
+        arr = np.ascontiguousarray(xyzr, np.float32)
+        if arr.ndim != 2 or arr.shape[1] != 4:
+            raise ValueError(f"update_spheres: xyzr must be (count, 4), got {arr.shape}")
+        self._check(self._L.mrt_update_spheres(self._ctx, first, len(arr), arr.ctypes.data if len(arr) else None), "mrt_update_spheres")
+
+    def debug_read_hierarchy(self) -> dict:
+        """The scene's hierarchy and the four copies of the spheres' geometry as the device holds them, plus the host-side
+        scalars the kernels get as arguments (mrt_debug_read_hierarchy)."""
+        info = (C.c_uint32 * 16)()
+        scal = (C.c_double * 8)()
+        direct = np.zeros((4, 4), np.float32)
+        direct_index = np.zeros(4, np.uint32)
+        nul = [None] * 10
+        self._check(self._L.mrt_debug_read_hierarchy(self._ctx, info, scal, direct.ctypes.data, direct_index.ctypes.data, *nul),
+                    "mrt_debug_read_hierarchy")
+        levels, n_top, n_nodes, n_members, n_direct, direct_first = (int(v) for v in info[:6])
+        n_boxes, n = int(info[10]), int(info[12])
+        top, nodes = np.zeros((n_top, 4), np.float32), np.zeros((n_nodes, 4), np.float32)
+        midx = np.zeros(n_members, np.uint32)
+        boxes, boxes_open = np.zeros((n_boxes, 6), np.float32), np.zeros((n_boxes, 6), np.float32)
+        mfma = np.zeros(n_top // 32 * 512, np.uint16)
+        spheres, shade = np.zeros((n, 4), np.float32), np.zeros((n, 8), np.float32)
+        centres, radii = np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+        arrays = [top, nodes, midx, boxes, boxes_open, mfma, spheres, shade, centres, radii]
+        self._check(self._L.mrt_debug_read_hierarchy(self._ctx, info, scal, direct.ctypes.data, direct_index.ctypes.data,
+                                                     *[a.ctypes.data if a.size else None for a in arrays]), "mrt_debug_read_hierarchy")
+        return dict(levels=levels, top=top, nodes=nodes, midx=midx, mfma=mfma, n_direct=n_direct, direct_first=direct_first,
+                    level_base=[int(info[6 + k]) for k in range(4)], n_members=n_members, boxes=boxes, boxes_open=boxes_open,
+                    box_quad=bool(info[11]), box_kc=np.float32(scal[0]), origin=np.array(scal[1:4], np.float64),
+                    axes=tuple(float(v) for v in scal[4:7]), reach=float(scal[7]), direct=direct, direct_index=direct_index,
+                    box_cluster_first=int(info[13]), box_cluster_parent_first=int(info[14]), mfma_scene_ok=bool(info[15]),
+                    spheres=spheres, shade=shade, centres=centres, radii=radii)
+
     def set_camera(self, cam: Camera):
         self._check(self._L.mrt_set_camera(self._ctx, C.byref(cam._c())), "mrt_set_camera")
 

@@ -227,6 +227,40 @@ struct TileBlendArgs {
 };
 int launch_tile_blend(const TileBlendArgs& a, void* stream);
 
+// refit.hip (include/myraytracer_amd.h, mrt_update_spheres): the device side of a geometry update whose grouping stays.
+// launch_refit_scatter: `count` <= kRefitBatch spheres (cx, cy, cz, radius), passed BY VALUE in the kernel arguments (no staging
+// buffer, no copy for the runtime to order), into the four device copies of spheres [first, first + count): spheres, floats 0..3
+// of shade, and the reference's SoA -- centres = vec4_data + 4 center_base_idx, radii = f32_data + radius_base_idx.
+// launch_refit: everything derived from them, as hierarchy.cpp derives it: the member records (level 0 of nodes), every level's
+// bounding spheres (nodes / clusters), with boxes != null the boxes and their opened-wide copies in the top-down numbering for
+// box_quad / box_kc, and the A operand for D = I relative to origin.  n_hier: the member slots the hierarchy covers (direct_first).
+constexpr uint32_t kRefitBatch = 192;    // 3 KB of the 4 KB a launch's arguments may take
+struct RefitScatterArgs {
+    SphereRec* spheres;
+    float* shade;
+    float* centres;
+    float* radii;
+    uint32_t first, count;
+    float xyzr[4 * kRefitBatch];
+};
+struct RefitArgs {
+    const SphereRec* spheres;
+    const float* shade;
+    const uint32_t* member_index;
+    SphereRec* nodes;
+    SphereRec* clusters;
+    BoxRec* boxes;
+    BoxRec* boxes_open;
+    uint16_t* top_mfma;
+    uint32_t n_members, n_hier, levels, n_nodes, n_padded;
+    uint32_t level_base[kMaxLevels];
+    uint32_t box_quad;
+    float box_kc;
+    float origin[3];
+};
+int launch_refit_scatter(const RefitScatterArgs& a, void* stream);
+int launch_refit(const RefitArgs& a, void* stream);
+
 // denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
 // pixel (launch_debug_world_hit) -> 2 float4 per pixel {normal, t} {albedo, bits of the index}; shade / mat_ty: KParams' shade and

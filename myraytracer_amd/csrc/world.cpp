@@ -237,6 +237,126 @@ int mrt_set_world(mrt_ctx* c, const mrt_sphere* spheres, size_t n) {
     return mrt_set_world_raw(c, &w, sizeof w, vec4.data(), nv, f32.data(), nf, i32.data(), ni);
 }
 
+// New geometry for spheres whose grouping stays (include/myraytracer_amd.h): O(count) work here, everything derived from the
+// spheres recomputed by refit.hip in stream order.  Nothing waits on the host: the ctx's stream is made to wait for the render
+// kernels in flight (they read the arrays about to change), and every later frame's side stream waits for ev_inputs, recorded
+// on the ctx's stream behind the refit (frames.cpp, enter_slot).  The updates travel in kernel arguments, kRefitBatch spheres a
+// launch: a hipMemcpyAsync from the caller's pageable memory would have the runtime stage the data and order the copy itself --
+// it may hold the calling thread until the stream has drained -- and needs a staging buffer of ours to be safe from the caller
+// reusing xyzr; arguments are copied at the launch call and need neither.
+int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* xyzr) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_update_spheres: no scene");
+    if ((uint64_t)first + count > c->n_spheres)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_update_spheres: spheres [%u, %llu) of a scene of %u", first, (unsigned long long)first + count, c->n_spheres);
+    if (count && !xyzr) return fail(c, MRT_ERR_INVALID_ARG, "mrt_update_spheres: null array");
+    for (size_t i = 0; i < 4 * (size_t)count; i++)
+        if (!finite_in_range(xyzr[i], 1.0e7f))
+            return fail(c, MRT_ERR_BAD_SCENE, "mrt_update_spheres: sphere %zu: centre/radius not finite or |v| > 1e7", first + i / 4);
+    if (count == 0) return MRT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // from here on a failure leaves the device arrays between two scenes: the context then has no scene until the next mrt_set_world*
+    auto lost = [&](int st) { c->have_world = false; return st; };
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        mrt_ctx::FrameSlot& S = c->slot[i];
+        if (!S.render_pending) continue;
+        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
+        if (e != hipSuccess) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: hipStreamWaitEvent failed: %s", hipGetErrorString(e)));
+    }
+    c->inputs_dirty = true;
+    c->guides_stale = true;
+    const bool boxed = !mrt::scene_is_small(c->n_members);
+    double reach = c->mfma_reach;
+    float kc = c->box_kc;
+    for (uint32_t b = 0; b < count; b += mrt::kRefitBatch) {
+        mrt::RefitScatterArgs s;
+        s.spheres = c->d_spheres; s.shade = c->d_shade;
+        s.centres = c->d_vec4 + 4 * (size_t)c->world.spheres.center_base_idx;
+        s.radii = c->d_f32 + c->world.spheres.radius_base_idx;
+        s.first = first + b; s.count = std::min(mrt::kRefitBatch, count - b);
+        std::memcpy(s.xyzr, xyzr + 4 * (size_t)b, 16 * (size_t)s.count);
+        const int le = mrt::launch_refit_scatter(s, c->stream);
+        if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
+        // The scene-level kernel arguments, kept valid monotonically from the updated spheres alone: the sweep's reach (D = I
+        // from here on; a reach measured in a scaled space only overstates it), the direct spheres' records, and the box slack's
+        // kc >= 1.3e-6 / the smallest clustered radius (the quadratic form; both forms are valid bounds, so the form stays).
+        for (uint32_t i = 0; i < s.count; i++) {
+            const float* v = s.xyzr + 4 * i;
+            const uint32_t idx = s.first + i;
+            double d2 = 0.0;
+            for (int k = 0; k < 3; k++) { const double d = (double)v[k] - (double)c->mfma_origin[k]; d2 += d * d; }
+            reach = std::max(reach, std::sqrt(d2) + std::fabs((double)v[3]));
+            bool direct = false;
+            for (uint32_t k = 0; k < c->n_direct; k++)
+                if (c->direct_index[k] == idx) { c->direct[k] = mrt::SphereRec{v[0], v[1], v[2], -(v[3] * v[3])}; direct = true; }
+            if (boxed && c->box_quad && !direct) {
+                const double need = 1.3e-6 / std::max(std::fabs((double)v[3]), 1e-30);
+                float f = (float)need;
+                if ((double)f < need) f = std::nextafterf(f, INFINITY);
+                kc = std::max(kc, f);
+            }
+        }
+    }
+    c->mfma_reach = reach;
+    c->box_kc = kc;
+    // The scaled sweep space's proof (hierarchy.cpp, scaled_top_records) needs scene statistics only the device now has: D = I
+    // until the next mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack
+    // is small against R^2, a speed rule -- the sweep is conservative wherever it runs.
+    c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
+    mrt::RefitArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.spheres = c->d_spheres; a.shade = c->d_shade; a.member_index = c->d_member_index;
+    a.nodes = c->d_nodes; a.clusters = c->d_clusters;
+    a.boxes = boxed ? c->d_boxes : nullptr; a.boxes_open = boxed ? c->d_boxes_open : nullptr;
+    a.top_mfma = c->d_top_mfma;
+    a.n_members = c->n_members; a.n_hier = c->direct_first; a.levels = c->levels; a.n_nodes = c->n_nodes; a.n_padded = c->n_padded;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) a.level_base[k] = c->level_base[k];
+    a.box_quad = c->box_quad ? 1u : 0u; a.box_kc = c->box_kc;
+    for (int k = 0; k < 3; k++) a.origin[k] = c->mfma_origin[k];
+    const int le = mrt::launch_refit(a, c->stream);
+    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
+    return MRT_OK;
+}
+
+int mrt_debug_read_hierarchy(mrt_ctx* c, uint32_t info[16], double scalars[8], float* direct_out, uint32_t* direct_index_out,
+                             float* top_out, float* nodes_out, uint32_t* member_index_out, float* boxes_out, float* boxes_open_out,
+                             uint16_t* mfma_out, float* spheres_out, float* shade_out, float* centres_out, float* radii_out) {
+    if (!c || !info) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_read_hierarchy: no scene");
+    const bool boxed = !mrt::scene_is_small(c->n_members);
+    size_t n_boxes = 0;
+    if (boxed) for (uint32_t t = 0; t < c->levels; t++) n_boxes += (size_t)c->n_padded << (2 * t);
+    info[0] = c->levels; info[1] = c->n_padded; info[2] = c->n_nodes; info[3] = c->n_members; info[4] = c->n_direct; info[5] = c->direct_first;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) info[6 + k] = c->level_base[k];
+    info[10] = (uint32_t)n_boxes; info[11] = c->box_quad ? 1u : 0u; info[12] = c->n_spheres; info[13] = c->box_cluster_first;
+    info[14] = c->box_cluster_parent_first; info[15] = c->mfma_scene_ok ? 1u : 0u;
+    if (scalars) {
+        scalars[0] = (double)c->box_kc;
+        for (int k = 0; k < 3; k++) { scalars[1 + k] = (double)c->mfma_origin[k]; scalars[4 + k] = (double)c->mfma_axis[k]; }
+        scalars[7] = c->mfma_reach;
+    }
+    if (direct_out) std::memcpy(direct_out, c->direct, sizeof c->direct);
+    if (direct_index_out) std::memcpy(direct_index_out, c->direct_index, sizeof c->direct_index);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_debug_read_hierarchy"));
+    auto read = [&](void* dst, const void* src, size_t bytes) -> int {
+        if (dst && bytes) HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        return MRT_OK;
+    };
+    const size_t n = c->n_spheres;
+    MRT_TRY(read(top_out, c->d_clusters, (size_t)c->n_padded * sizeof(mrt::SphereRec)));
+    MRT_TRY(read(nodes_out, c->d_nodes, (size_t)c->n_nodes * sizeof(mrt::SphereRec)));
+    MRT_TRY(read(member_index_out, c->d_member_index, (size_t)c->n_members * sizeof(uint32_t)));
+    MRT_TRY(read(boxes_out, c->d_boxes, n_boxes * sizeof(mrt::BoxRec)));
+    MRT_TRY(read(boxes_open_out, c->d_boxes_open, n_boxes * sizeof(mrt::BoxRec)));
+    MRT_TRY(read(mfma_out, c->d_top_mfma, (size_t)c->n_padded / 32 * 512 * sizeof(uint16_t)));
+    MRT_TRY(read(spheres_out, c->d_spheres, n * sizeof(mrt::SphereRec)));
+    MRT_TRY(read(shade_out, c->d_shade, n * 8 * sizeof(float)));
+    MRT_TRY(read(centres_out, c->d_vec4 + 4 * (size_t)c->world.spheres.center_base_idx, n * 4 * sizeof(float)));
+    MRT_TRY(read(radii_out, c->d_f32 + c->world.spheres.radius_base_idx, n * sizeof(float)));
+    return MRT_OK;
+}
+
 // diagnostic / tuning: cluster growth factor used by the NEXT mrt_set_world* call
 int mrt_debug_set_cluster_factor(mrt_ctx* c, float factor) {
     if (!c || !(factor >= 0.0f)) return MRT_ERR_INVALID_ARG;

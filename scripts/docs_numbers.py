@@ -34,6 +34,14 @@ def _phase(name, pattern):
     raise KeyError(pattern)
 
 
+def _anim(scene, way, pattern):
+    """a figure of the line of profiles/animation_rates.txt for `scene` ("C3" / "C5") rendered through `way` ("set_world" / "update")"""
+    for line in open(os.path.join(ROOT, "profiles", "animation_rates.txt")):
+        if re.match(rf"\s+{scene} \S.* {way}\s", line):
+            return float(re.search(pattern, line).group(1))
+    raise KeyError((scene, way))
+
+
 # token -> (how to get the value, format)
 TOKENS = {
     "C3_VALUE": (lambda: _json(f"{R}_bench_n1.json")["value"], ",.0f"),
@@ -75,6 +83,16 @@ TOKENS = {
     "SHARD4_VALUE": (lambda: _shard(r"^stress 1920x1080x4096 shard 0/4 rng_mode 0")[0], ",.0f"),
     "SHARD2_VALUE": (lambda: _shard(r"^stress 1920x1080x4096 shard 0/2 rng_mode 0")[0], ",.0f"),
     "C4SHARD_VALUE": (lambda: _shard(r"^cover-glass 3840x2160x1024 shard 0/8 rng_mode 0")[0], ",.0f"),
+    "ANIM_C3_SET_RATE": (lambda: _anim("C3", "set_world", r"([\d.]+) steps/s"), ",.0f"),
+    "ANIM_C3_UPD_RATE": (lambda: _anim("C3", "update", r"([\d.]+) steps/s"), ",.0f"),
+    "ANIM_C5_SET_RATE": (lambda: _anim("C5", "set_world", r"([\d.]+) steps/s"), ",.0f"),
+    "ANIM_C5_UPD_RATE": (lambda: _anim("C5", "update", r"([\d.]+) steps/s"), ",.0f"),
+    "ANIM_C3_SET_MS": (lambda: _anim("C3", "set_world", r"median\s+([\d.]+) ms"), ".2f"),
+    "ANIM_C5_SET_MS": (lambda: _anim("C5", "set_world", r"median\s+([\d.]+) ms"), ".1f"),
+    "ANIM_C3_UPD_MS": (lambda: _anim("C3", "update", r"median\s+([\d.]+) ms"), ".3f"),
+    "ANIM_C5_UPD_MS": (lambda: _anim("C5", "update", r"median\s+([\d.]+) ms"), ".3f"),
+    "ANIM_C3_REFIT_MS": (lambda: _anim("C3", "update", r"events\): median ([\d.]+) ms"), ".3f"),
+    "ANIM_C5_REFIT_MS": (lambda: _anim("C5", "update", r"events\): median ([\d.]+) ms"), ".3f"),
     "C5_NODE_ROUNDS": (lambda: _phase("c5", r"node rounds/sweep ([\d.]+)"), ".1f"),
     "C5_ROUND_ITEMS": (lambda: _phase("c5", r"node rounds/sweep [\d.]+ \(items/round ([\d.]+)\)"), ".0f"),
 }
