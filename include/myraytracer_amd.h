@@ -224,11 +224,28 @@ int mrt_set_world(mrt_ctx* ctx, const mrt_sphere* spheres, size_t n);
  *   The launch schedule is not restarted and the tile costs stay valid: a caller that updates every frame still reaches a
  *     settled schedule (mrt_get_schedule), and a pinned hint stays as it is.
  *   Regrouping: the bounds only get looser as spheres leave the groups they were built in.  The image never changes, only the
- *     speed; mrt_read_counters' member_tests per world_hit_calls is the signal to watch, and mrt_set_world* regroups.
+ *     speed; mrt_read_counters' member_tests per world_hit_calls is the signal to watch, and mrt_regroup_spheres regroups.
  *   The matrix-core sweep runs in the world's own space (no per-scene axis scale) after an update; the scaled space comes back
  *     with the next mrt_set_world*.
  *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as a failed mrt_set_world* does. */
 int mrt_update_spheres(mrt_ctx* ctx, uint32_t first, uint32_t count, const float* xyzr);
+/* The hierarchy's grouping made anew, on the device, from the spheres as they are now: the spheres that share clusters (all but
+ * the few far larger than the rest) are permuted over the member slots they occupy -- a kd ordering whose cuts fall on
+ * power-of-two blocks of clusters, so that every level's nodes are compact -- and everything derived from the grouping is refitted
+ * as after an update.  The sphere count, the slot pattern, every buffer and the host builder's work stay: no buffer is freed or
+ * allocated, nothing is built on the host.  The result depends on the geometry and the build's slot pattern alone, not on earlier
+ * regroups: a second call changes nothing.
+ *   Refusals, each before anything is queued: MRT_ERR_INVALID_ARG for NULL, MRT_ERR_NO_SCENE without a scene.  A scene whose
+ *     spheres share at most one cluster (or that was built without clustering): MRT_OK, nothing queued.
+ *   Ordering: as mrt_update_spheres -- frames queued before the call render with the old grouping, frames queued after it with
+ *     the new one, and the call does not wait on the host for the frames in flight.
+ *   The image never depends on the grouping: the framebuffer, the accumulation and the counters samples / world_hit_calls /
+ *     rng_draws of every frame are what they would be without the call; node_tests and member_tests are what it lowers.
+ *   The tile costs, the launch schedule and a pinned hint stay, and the denoiser's guides stay current (no geometry changed).
+ *   The matrix-core sweep runs in the world's own space afterwards, as after an update: a small flat scene loses its per-scene
+ *     axis scale until the next mrt_set_world*.
+ *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as for mrt_update_spheres. */
+int mrt_regroup_spheres(mrt_ctx* ctx);
 /* The AoS -> SoA packing of lib.rs:722-799 (host only, no GPU needed).  Capacities are
  * in elements (vec4: 4 floats each); returns MRT_ERR_TOO_SMALL if any is short.
  * Needs at most 2n vec4, 2n f32, 2n i32. */

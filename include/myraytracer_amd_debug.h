@@ -221,6 +221,15 @@ int mrt_debug_check_context(mrt_ctx* ctx, char* why, size_t cap);
 int mrt_debug_read_hierarchy(mrt_ctx* ctx, uint32_t info[16], double scalars[8], float* direct_out, uint32_t* direct_index_out,
                              float* top_out, float* nodes_out, uint32_t* member_index_out, float* boxes_out, float* boxes_open_out,
                              uint16_t* mfma_out, float* spheres_out, float* shade_out, float* centres_out, float* radii_out);
+/* Diagnostics of mrt_regroup_spheres.  mrt_debug_regroup_info: out[4] = {the clusters the builder made from the spheres that may
+ * share one (the regroup permutes over their slots), the block capacity in force (clusters a workgroup of the block kernel
+ * takes), the depths the last regroup ran over global memory, the depths it ran in LDS}; the last two are 0 before the first
+ * regroup of a scene.  mrt_debug_set_regroup_block: the block capacity of the next regroups, a power of two from 4 to the
+ * built-in 512, 0 = the default -- lets tiny scenes drive the global depths.  mrt_debug_pool_clusters (host only): the first of
+ * those numbers for the hierarchy mrt_debug_build_hierarchy builds. */
+int mrt_debug_regroup_info(mrt_ctx* ctx, uint32_t out[4]);
+int mrt_debug_set_regroup_block(mrt_ctx* ctx, uint32_t clusters);
+int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, uint32_t* n_pool);
 
 #ifdef __cplusplus
 }

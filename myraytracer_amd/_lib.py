@@ -46,6 +46,7 @@ EXPORTS = [
     "mrt_debug_read_guides", "mrt_set_denoise_variance", "mrt_get_denoise_variance", "mrt_debug_denoise_variance",
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
     "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule", "mrt_debug_read_hierarchy",
+    "mrt_regroup_spheres", "mrt_debug_regroup_info", "mrt_debug_set_regroup_block", "mrt_debug_pool_clusters",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -233,6 +234,10 @@ def load():
         "mrt_set_world_raw": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, sz]),
         "mrt_set_world": (i32, [vp, vp, sz]),
         "mrt_update_spheres": (i32, [vp, u32, u32, vp]),
+        "mrt_regroup_spheres": (i32, [vp]),
+        "mrt_debug_regroup_info": (i32, [vp, vp]),
+        "mrt_debug_set_regroup_block": (i32, [vp, u32]),
+        "mrt_debug_pool_clusters": (i32, [vp, sz, u32, u32, vp]),
         "mrt_pack_world": (i32, [vp, sz, P(MrtWorld), vp, sz, P(sz), vp, sz, P(sz), vp, sz, P(sz)]),
         "mrt_set_camera": (i32, [vp, P(MrtCamera)]),
         "mrt_camera_derive": (i32, [P(MrtCamera), P(MrtCameraRaw)]),

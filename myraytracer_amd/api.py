@@ -303,6 +303,20 @@ class State:
             raise ValueError(f"update_spheres: xyzr must be (count, 4), got {arr.shape}")
         self._check(self._L.mrt_update_spheres(self._ctx, first, len(arr), arr.ctypes.data if len(arr) else None), "mrt_update_spheres")
 
+    def regroup_spheres(self):
+        """mrt_regroup_spheres: the hierarchy's grouping made anew on the device from the spheres as they are now (after
+        update_spheres calls have moved them), refitted in stream order; images do not change, member_tests do."""
+        self._check(self._L.mrt_regroup_spheres(self._ctx), "mrt_regroup_spheres")
+
+    def debug_regroup_info(self) -> dict:
+        """n_pool, the block capacity in force, and the global / in-LDS depths of the last regroup (mrt_debug_regroup_info)"""
+        out = (C.c_uint32 * 4)()
+        self._check(self._L.mrt_debug_regroup_info(self._ctx, out), "mrt_debug_regroup_info")
+        return dict(n_pool=int(out[0]), block=int(out[1]), global_depths=int(out[2]), lds_depths=int(out[3]))
+
+    def debug_set_regroup_block(self, clusters: int):
+        self._check(self._L.mrt_debug_set_regroup_block(self._ctx, clusters), "mrt_debug_set_regroup_block")
+
     def debug_read_hierarchy(self) -> dict:
         """The scene's hierarchy and the four copies of the spheres' geometry as the device holds them, plus the host-side
         scalars the kernels get as arguments (mrt_debug_read_hierarchy)."""

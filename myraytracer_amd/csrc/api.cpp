@@ -111,7 +111,7 @@ void set_global_error(const char* msg) { g_err = msg ? msg : ""; }
 
 void free_world(mrt_ctx* c) {
     free_device(c->d_spheres, c->d_clusters, c->d_nodes, c->d_boxes, c->d_boxes_open, c->d_shade, c->d_top_mfma, c->d_member_index,
-                c->d_vec4, c->d_f32, c->d_i32);
+                c->d_regroup, c->d_vec4, c->d_f32, c->d_i32);
     c->have_world = false;
     c->guides_stale = true;
 }
@@ -816,7 +816,7 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
         if (S.pix_acc_layers < 1) return check_finding(why, cap, "slot %u of %u in use has no colour sums", i, c->frame_slots);
     }
     if (c->have_world) {
-        if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
+        if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_regroup || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
             return check_finding(why, cap, "have_world without one of the scene's arrays");
         if (!mrt::scene_is_small(c->n_members) && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
     }

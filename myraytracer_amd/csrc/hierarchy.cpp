@@ -26,7 +26,7 @@ namespace {
 // discriminant of -inf).
 void build_clusters(const float* centers4, const float* radii, uint32_t n, float factor,
                     std::vector<mrt::SphereRec>& clusters, std::vector<mrt::SphereRec>& members,
-                    std::vector<uint32_t>& member_index, std::vector<uint32_t>& direct) {
+                    std::vector<uint32_t>& member_index, std::vector<uint32_t>& direct, uint32_t* n_pool) {
     clusters.clear(); members.clear(); member_index.clear(); direct.clear();
     const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
     std::vector<double> rs(n);
@@ -158,6 +158,7 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
             if (!improved) break;
         }
     }
+    *n_pool = (uint32_t)groups.size();               // the clusters made from `pool` come first (regroup.hip permutes over them)
     // the largest of the big spheres are tested by every ray directly (KParams::direct); the others get a
     // cluster of their own
     std::stable_sort(alone.begin(), alone.end(), [&](uint32_t x, uint32_t y) { return rs[x] > rs[y]; });
@@ -323,7 +324,7 @@ void build_hierarchy(const float* centers4, const float* radii, uint32_t n, floa
     const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
     std::vector<mrt::SphereRec> members, cur;
     std::vector<uint32_t> direct;
-    build_clusters(centers4, radii, n, factor, cur, members, H.member_index, direct);
+    build_clusters(centers4, radii, n, factor, cur, members, H.member_index, direct, &H.n_pool);
     H.nodes = members;
     // the direct spheres follow the clusters' members in level 0 (no cluster, no bound above them)
     H.n_direct = (uint32_t)direct.size();
@@ -768,6 +769,20 @@ int mrt_debug_build_boxes(const mrt_sphere* spheres, size_t n, uint32_t max_leve
     for (uint32_t k = 0; k <= mrt::kMaxLevels; k++) info[3 + k] = h.box_base[k];
     if (boxes_out && boxes_cap < h.boxes.size()) return MRT_ERR_TOO_SMALL;
     if (boxes_out) std::memcpy(boxes_out, h.boxes.data(), h.boxes.size() * sizeof(mrt::BoxFull));
+    return MRT_OK;
+}
+
+int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, uint32_t* n_pool) {
+    if ((!spheres && n) || !n_pool || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres) return MRT_ERR_INVALID_ARG;
+    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+        centers[4 * i + 3] = 1.0f;
+        radii[i] = spheres[i].radius;
+    }
+    Hierarchy h;
+    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    *n_pool = h.n_pool;
     return MRT_OK;
 }
 

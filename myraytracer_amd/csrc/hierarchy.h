@@ -24,6 +24,7 @@ struct Hierarchy {
     uint32_t levels = 1, n_members = 0;       // n_members: level 0 including the direct spheres
     uint32_t level_base[mrt::kMaxLevels] = {0, 0, 0, 0};
     uint32_t n_direct = 0, direct_first = 0;
+    uint32_t n_pool = 0;                      // the clusters [0, n_pool) are those build_clusters made from its pool (regroup.hip)
     mrt::SphereRec direct[mrt::kMaxDirect] = {};
     uint32_t direct_index[mrt::kMaxDirect] = {};
 };

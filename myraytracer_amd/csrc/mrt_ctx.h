@@ -43,6 +43,12 @@ struct mrt_ctx {
     float* d_shade = nullptr;              // 8 floats per sphere: centre, radius, material colour, fuzz | ior
     mrt::SphereRec* d_nodes = nullptr;     // hierarchy levels below the top: members (kClusterK per cluster), clusters, ...
     uint32_t* d_member_index = nullptr;    // their indices in the reference's sphere order
+    // mrt_regroup_spheres (regroup.hip): the scene's regroup scratch (regroup_layout: the pool list, rank -> cluster, pref, two
+    // orders, the segments' boxes, the sort's keys), the clusters made from the builder's pool and the spheres in them; the block
+    // the next regroup uses (mrt_debug_set_regroup_block; 0 = kRegroupBlock) and what the last one did (mrt_debug_regroup_info)
+    uint32_t* d_regroup = nullptr;
+    uint32_t n_pool = 0, n_pooled = 0;
+    uint32_t regroup_block = 0, regroup_last[3] = {0, 0, 0};
     // large scenes' walk: the axis-aligned boxes of the hierarchy's nodes in the kernel's top-down numbering (KParams::boxes),
     // and the same array with every real box opened wide (a box test that never rejects: mrt_debug_set_boxes(0))
     mrt::BoxRec* d_boxes = nullptr;

@@ -261,6 +261,48 @@ struct RefitArgs {
 int launch_refit_scatter(const RefitScatterArgs& a, void* stream);
 int launch_refit(const RefitArgs& a, void* stream);
 
+// regroup.hip (include/myraytracer_amd.h, mrt_regroup_spheres): the pooled spheres -- those of the clusters [0, n_pool) that
+// build_clusters made from its pool -- permuted over the member slots they occupy, by the ordering of tests/regroup_ref.py: a kd
+// split whose cuts fall on power-of-two blocks of clusters.  Only member_index is written (and the scratch); launch_refit follows.
+// The scratch is one scene buffer of u32 words, made by mrt_set_world_raw (world.cpp) and laid out by regroup_layout:
+//   pool   the pooled spheres' indices, ascending: the order every regroup starts from          (host, read only)
+//   clus   the cluster whose slots rank i of an order falls into                                 (host, read only)
+//   pref   pref[k] = real member slots of the clusters [0, k), n_pool + 1 entries                (host, read only)
+//   ord    two orders of the pool, written in turn by the depths whose segments are wider than a block
+//   box    6 words per segment of such a depth: min x, y, z and max x, y, z of the centres in key form
+//   keys   n_sort u64 composite keys (segment, key along the segment's axis, rank), sorted in place
+constexpr uint32_t kRegroupBlock = 512;      // clusters per workgroup of the block kernel: at most 2,048 spheres in LDS
+constexpr uint32_t kRegroupChunk = 4 * kRegroupBlock;
+constexpr uint32_t kRegroupMaxSegments = 4096;   // 12 bits of a composite key; 32 for the key, 20 for the rank (kMaxSpheres)
+struct RegroupLayout { size_t pool, clus, pref, ord[2], box, keys, words; uint32_t n_sort; };
+inline RegroupLayout regroup_layout(uint32_t n_pool, uint32_t pooled) {
+    RegroupLayout l{};
+    l.n_sort = kRegroupChunk;
+    while (l.n_sort < pooled) l.n_sort <<= 1;
+    size_t at = 0;
+    l.pool = at; at += pooled;
+    l.clus = at; at += pooled;
+    l.pref = at; at += (size_t)n_pool + 1;
+    l.ord[0] = at; at += pooled;
+    l.ord[1] = at; at += pooled;
+    l.box = at; at += 6 * ((size_t)n_pool / 8 + 2);      // the narrowest such depth has segments of 8 clusters (a block of 4)
+    at += at & 1;                                        // (the keys are 8 bytes each)
+    l.keys = at; at += 2 * (size_t)l.n_sort;
+    l.words = at;
+    return l;
+}
+struct RegroupArgs {
+    const SphereRec* spheres;
+    uint32_t* member_index;
+    uint32_t* scratch;
+    uint32_t n_pool, pooled;
+    uint32_t block;             // clusters per workgroup of the block kernel: a power of two, 4 .. kRegroupBlock
+};
+// the block in force for n_pool clusters (raised while a depth above it would have more than kRegroupMaxSegments segments), and
+// the depths above it / within it: host only
+void regroup_plan(uint32_t n_pool, uint32_t block, uint32_t out[3]);
+int launch_regroup(const RegroupArgs& a, void* stream);
+
 // denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
 // pixel (launch_debug_world_hit) -> 2 float4 per pixel {normal, t} {albedo, bits of the index}; shade / mat_ty: KParams' shade and

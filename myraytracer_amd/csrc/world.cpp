@@ -26,6 +26,22 @@ bool use_matrix_core_sweep(const mrt_ctx* c) {
     return kMfmaSlack * o2 <= 0.1 * c->mfma_r2_ref;
 }
 
+// launch_refit's arguments for the scene as the context holds it (mrt_update_spheres, mrt_regroup_spheres)
+mrt::RefitArgs refit_args(const mrt_ctx* c) {
+    const bool boxed = !mrt::scene_is_small(c->n_members);
+    mrt::RefitArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.spheres = c->d_spheres; a.shade = c->d_shade; a.member_index = c->d_member_index;
+    a.nodes = c->d_nodes; a.clusters = c->d_clusters;
+    a.boxes = boxed ? c->d_boxes : nullptr; a.boxes_open = boxed ? c->d_boxes_open : nullptr;
+    a.top_mfma = c->d_top_mfma;
+    a.n_members = c->n_members; a.n_hier = c->direct_first; a.levels = c->levels; a.n_nodes = c->n_nodes; a.n_padded = c->n_padded;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) a.level_base[k] = c->level_base[k];
+    a.box_quad = c->box_quad ? 1u : 0u; a.box_kc = c->box_kc;
+    for (int k = 0; k < 3; k++) a.origin[k] = c->mfma_origin[k];
+    return a;
+}
+
 }  // namespace
 
 namespace mrt {
@@ -173,6 +189,35 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         c->mfma_scene_ok = n_real >= 24 && med_r2 > 0.0 && kMfmaSlack * 2.0 * max_c2 <= 0.1 * med_r2;
     }
     MRT_TRY(upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
+    {
+        // The regroup scratch (mrt_regroup_spheres; mrt_internal.h, regroup_layout): what a regroup reads of the build -- the pool's
+        // sphere indices ascending, the cluster of every rank, pref -- and the room it works in: 16 bytes a pooled sphere for the
+        // lists and orders, 7 a cluster for pref and the boxes, 8 a key of the sort (a power of two of at least 2,048, below twice
+        // the pool): under 64 bytes a pooled sphere beyond the smallest scenes.  A scene without a pool gets the 16-byte stub.
+        uint32_t pooled = 0;
+        std::vector<uint32_t> pref((size_t)hier.n_pool + 1, 0u);
+        for (uint32_t k = 0; k < hier.n_pool; k++) {
+            for (uint32_t m = 0; m < mrt::kClusterK; m++) pooled += std::isfinite(hier.nodes[(size_t)mrt::kClusterK * k + m].neg_r2) ? 1u : 0u;
+            pref[k + 1] = pooled;
+        }
+        std::vector<uint32_t> scratch;
+        if (hier.n_pool > 1) {
+            const mrt::RegroupLayout L = mrt::regroup_layout(hier.n_pool, pooled);
+            scratch.assign(L.words, 0u);
+            for (uint32_t k = 0, at = 0; k < hier.n_pool; k++)
+                for (uint32_t m = 0; m < mrt::kClusterK; m++)
+                    if (std::isfinite(hier.nodes[(size_t)mrt::kClusterK * k + m].neg_r2)) {
+                        scratch[L.pool + at] = hier.member_index[(size_t)mrt::kClusterK * k + m];
+                        scratch[L.clus + at] = k;
+                        at++;
+                    }
+            std::sort(scratch.begin() + (long)L.pool, scratch.begin() + (long)(L.pool + pooled));
+            std::copy(pref.begin(), pref.end(), scratch.begin() + (long)L.pref);
+        }
+        MRT_TRY(upload((void**)&c->d_regroup, scratch.data(), scratch.size() * sizeof(uint32_t)));
+        c->n_pool = hier.n_pool; c->n_pooled = pooled;
+        c->regroup_last[0] = c->regroup_last[1] = c->regroup_last[2] = 0;
+    }
     // what shading a hit on sphere i reads, gathered per sphere (bit copies of the SoA entries)
     std::vector<float> shade(8 * ((size_t)n ? (size_t)n : 1), 0.0f);
     for (int64_t i = 0; i < n; i++) {
@@ -303,18 +348,53 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
     // until the next mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack
     // is small against R^2, a speed rule -- the sweep is conservative wherever it runs.
     c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
-    mrt::RefitArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.spheres = c->d_spheres; a.shade = c->d_shade; a.member_index = c->d_member_index;
-    a.nodes = c->d_nodes; a.clusters = c->d_clusters;
-    a.boxes = boxed ? c->d_boxes : nullptr; a.boxes_open = boxed ? c->d_boxes_open : nullptr;
-    a.top_mfma = c->d_top_mfma;
-    a.n_members = c->n_members; a.n_hier = c->direct_first; a.levels = c->levels; a.n_nodes = c->n_nodes; a.n_padded = c->n_padded;
-    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) a.level_base[k] = c->level_base[k];
-    a.box_quad = c->box_quad ? 1u : 0u; a.box_kc = c->box_kc;
-    for (int k = 0; k < 3; k++) a.origin[k] = c->mfma_origin[k];
+    const mrt::RefitArgs a = refit_args(c);
     const int le = mrt::launch_refit(a, c->stream);
     if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
+    return MRT_OK;
+}
+
+// The grouping made anew from the spheres as the device holds them (include/myraytracer_amd.h): regroup.hip permutes the pooled
+// spheres over their member slots, refit.hip derives everything from the new order.  Ordered like an update: the ctx's stream
+// waits for the render kernels in flight, later frames wait for ev_inputs; nothing waits on the host.
+int mrt_regroup_spheres(mrt_ctx* c) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_regroup_spheres: no scene");
+    if (c->n_pool <= 1) return MRT_OK;                  // no clustering, or nothing to trade between clusters
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto lost = [&](int st) { c->have_world = false; return st; };
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        mrt_ctx::FrameSlot& S = c->slot[i];
+        if (!S.render_pending) continue;
+        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
+        if (e != hipSuccess) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: hipStreamWaitEvent failed: %s", hipGetErrorString(e)));
+    }
+    c->inputs_dirty = true;                             // (the guides stay current: the geometry did not change)
+    mrt::RegroupArgs g;
+    g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
+    g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
+    mrt::regroup_plan(g.n_pool, g.block, c->regroup_last);
+    int le = mrt::launch_regroup(g, c->stream);
+    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
+    // the refit's operand is the one for D = I, as after an update: a scaled sweep space comes back with the next mrt_set_world*
+    c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
+    le = mrt::launch_refit(refit_args(c), c->stream);
+    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
+    return MRT_OK;
+}
+
+int mrt_debug_regroup_info(mrt_ctx* c, uint32_t out[4]) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_regroup_info: no scene");
+    uint32_t plan[3];
+    mrt::regroup_plan(c->n_pool, c->regroup_block ? c->regroup_block : mrt::kRegroupBlock, plan);
+    out[0] = c->n_pool; out[1] = plan[0]; out[2] = c->regroup_last[1]; out[3] = c->regroup_last[2];
+    return MRT_OK;
+}
+
+int mrt_debug_set_regroup_block(mrt_ctx* c, uint32_t clusters) {
+    if (!c || (clusters != 0 && (clusters < 4 || clusters > mrt::kRegroupBlock || (clusters & (clusters - 1))))) return MRT_ERR_INVALID_ARG;
+    c->regroup_block = clusters;
     return MRT_OK;
 }
 

@@ -7,7 +7,12 @@
    recorded on the context's stream before and after the call (the scatter + refit kernels); how often the call returned while
    the previous frame was still unfinished (an event recorded behind that frame, queried when the call returns); and the member
    tests per world_hit call over the first and the last quarter of the run (what the kept grouping costs as the spheres drift).
-   python scripts/animation_rates.py [w h] [--steps 200] [--walk 0.0005] [--depth 50]"""
+   python scripts/animation_rates.py [w h] [--steps 200] [--walk 0.0005] [--depth 50]
+   --regroup-every N prints the section "regroup" instead (mrt_regroup_spheres): (1) the cost of one regroup at C3
+   and C5 -- host time of the call, device time between HIP events on the context's stream around it -- next to the same
+   process's mrt_set_world call; (2) the animated C5 three ways in one process -- the refit alone, a regroup every N steps, a
+   rebuild (mrt_set_world) every N steps -- with the member tests per world_hit by quarter; (3) the static C5 and C3 as built and
+   after one regroup with no motion: the render kernel's time (mrt_kernel_ms_history) and member tests per world_hit."""
 import argparse
 import os
 import sys
@@ -24,6 +29,7 @@ ap.add_argument("size", nargs="*", type=int, default=[1920, 1080])
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--walk", type=float, default=0.0005)
 ap.add_argument("--depth", type=int, default=50)
+ap.add_argument("--regroup-every", type=int, default=0)
 a = ap.parse_args()
 W, H = a.size
 
@@ -40,9 +46,12 @@ def walk(spheres, steps, rng):
     return out
 
 
-def run(name, spheres, cam, way, path):
+def run(name, spheres, cam, way, path, every=0):
+    """way: set_world | update | regroup (update, and mrt_regroup_spheres every `every` steps) | rebuild (update, but mrt_set_world
+    every `every` steps); with `every` the member tests are reported for each quarter of the run"""
     stream = torch.cuda.Stream()
     quarter = max(1, len(path) // 4)
+    bounds = (quarter, 2 * quarter, 3 * quarter) if every else (quarter, len(path) - quarter)
     with M.State(M.Args(W, H, 1, a.depth, 1.0), seed=1, stream=stream.cuda_stream) as st:
         st.set_world(spheres)
         st.set_camera(cam)
@@ -54,12 +63,12 @@ def run(name, spheres, cam, way, path):
         st.sync()
         t0 = time.perf_counter()
         for i, xyzr in enumerate(path):
-            if i in (quarter, len(path) - quarter):
+            if i in bounds:
                 st.sync()
                 marks.append(st.read_counters())
             if i == 0:
                 marks.append(st.read_counters())
-            if way == "update":
+            if way != "set_world" and not (way == "rebuild" and i and i % every == 0):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(stream)
                 c0 = time.perf_counter()
@@ -67,6 +76,8 @@ def run(name, spheres, cam, way, path):
                 host.append(time.perf_counter() - c0)
                 e1.record(stream)
                 pairs.append((e0, e1))
+                if way == "regroup" and i and i % every == 0:
+                    st.regroup_spheres()
             else:
                 sc["center"] = xyzr[:, :3]
                 c0 = time.perf_counter()
@@ -90,12 +101,97 @@ def run(name, spheres, cam, way, path):
     if pairs:
         dev = np.array([p[0].elapsed_time(p[1]) for p in pairs])
         line += f"  refit on the device (events): median {np.median(dev):.4f} ms, max {dev.max():.4f}"
-    line += (f"  returned before the previous frame had ended: {early} of {len(path) - 1} calls"
-             f"  member tests / world_hit: first quarter {tests_per_hit(marks[0], marks[1]):.2f}, last quarter {tests_per_hit(marks[2], marks[3]):.2f}"
-             f"  schedule at the end: div {sch['div']} x {sch['mult']}, settled {sch['settled']}")
+    line += f"  returned before the previous frame had ended: {early} of {len(path) - 1} calls"
+    if every:
+        line += "  member tests / world_hit by quarter: " + ", ".join(f"{tests_per_hit(marks[q], marks[q + 1]):.2f}" for q in range(4))
+    else:
+        line += f"  member tests / world_hit: first quarter {tests_per_hit(marks[0], marks[1]):.2f}, last quarter {tests_per_hit(marks[2], marks[3]):.2f}"
+    line += (f"  schedule at the end: div {sch['div']} x {sch['mult']}, settled {sch['settled']}")
     print(line, flush=True)
     return len(path) / sec
 
+
+def regroup_cost(name, spheres, cam, path):
+    """(1): one regroup of the scene moved to the end of the walk, against the same context's mrt_set_world of it"""
+    stream = torch.cuda.Stream()
+    with M.State(M.Args(W, H, 1, a.depth, 1.0), seed=1, stream=stream.cuda_stream) as st:
+        st.set_world(spheres)
+        st.set_camera(cam)
+        st.render(4)
+        st.update_spheres(0, path[-1])
+        st.sync()
+        host, dev = [], []
+        for _ in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            c0 = time.perf_counter()
+            st.regroup_spheres()
+            host.append((time.perf_counter() - c0) * 1e3)
+            e1.record(stream)
+            st.sync()
+            dev.append(e0.elapsed_time(e1))
+        info = st.debug_regroup_info()
+        sc = spheres.copy()
+        sc["center"] = path[-1][:, :3]
+        built = []
+        for _ in range(5):
+            c0 = time.perf_counter()
+            st.set_world(sc)
+            built.append((time.perf_counter() - c0) * 1e3)
+    print(f"  {name}: mrt_regroup_spheres ({info['n_pool']} pool clusters, {info['global_depths']} depths over global memory, {info['lds_depths']} in LDS): "
+          f"host median {np.median(host):.3f} ms, max {max(host):.3f}; device (events) median {np.median(dev):.4f} ms, max {max(dev):.4f};  "
+          f"mrt_set_world of the same spheres: host median {np.median(built):.3f} ms;  regroup host + device = "
+          f"{(np.median(host) + np.median(dev)) / np.median(built):.4f} x the rebuild's host time", flush=True)
+
+
+def static_cost(name, spheres, cam):
+    """(3): the scene as built and after one regroup with no motion, 64 frames each, twice in turn in one context (as built,
+    regrouped, built again, regrouped again), so that a drift of the machine shows as a difference between the rounds"""
+    out = []
+    with M.State(M.Args(W, H, 1, a.depth, 1.0), seed=1) as st:
+        st.set_camera(cam)
+        for rnd in range(2):
+            for regroup in (False, True):
+                if regroup:
+                    st.regroup_spheres()
+                else:
+                    st.set_world(spheres)
+                st.reset()
+                for _ in range(16):
+                    st.redraw()
+                st.sync()
+                c0 = st.read_counters()
+                for _ in range(64):
+                    st.redraw()
+                st.sync()
+                c1 = st.read_counters()
+                ms = np.array(st.kernel_ms_history(64))
+                out.append((np.median(ms), ms.min(), (c1["member_tests"] - c0["member_tests"]) / max(1, c1["world_hit_calls"] - c0["world_hit_calls"])))
+                print(f"  {name} static, round {rnd + 1}, {'regrouped' if regroup else 'as built '}: render kernel median {out[-1][0]:.4f} ms, min {out[-1][1]:.4f} "
+                      f"(64 frames); member tests / world_hit {out[-1][2]:.2f}; sweep variant {st.debug_sweep_variant()}, "
+                      f"sweep axes {st.debug_read_hierarchy()['axes']}", flush=True)
+    for rnd in range(2):
+        b, r = out[2 * rnd], out[2 * rnd + 1]
+        print(f"  {name} static, round {rnd + 1}: regrouped / as built = {r[0] / b[0]:.4f} x the kernel's median time ({r[1] / b[1]:.4f} x its minimum), "
+              f"{r[2] / b[2]:.4f} x the member tests", flush=True)
+
+
+if a.regroup_every:
+    N = a.regroup_every
+    print(f"regroup: {W}x{H} x 1 spp, depth {a.depth}; the walk of {a.walk} x the scene's size a step; build {M._lib.load().mrt_build_id().decode()}", flush=True)
+    scenes = (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100)))
+    paths = {name: walk(spheres, a.steps, np.random.default_rng(1)) for name, (spheres, cam) in scenes}
+    print(f"(1) one regroup of the scene after {a.steps} steps, 20 calls", flush=True)
+    for name, (spheres, cam) in scenes:
+        regroup_cost(name, spheres, cam, paths[name])
+    name, (spheres, cam) = scenes[1]
+    print(f"(2) {name}, {a.steps} steps, one frame a step: the refit alone, a regroup every {N} steps, a rebuild every {N} steps", flush=True)
+    for way in ("update", "regroup", "rebuild"):
+        run(name, spheres, cam, way, paths[name], every=N)
+    print("(3) no motion: as built against one regroup", flush=True)
+    for name, (spheres, cam) in scenes[::-1]:
+        static_cost(name, spheres, cam)
+    sys.exit(0)
 
 print(f"{W}x{H} x 1 spp, depth {a.depth}; {a.steps} steps of a random walk ({a.walk} x the scene's size a step), one frame a step", flush=True)
 for name, (spheres, cam) in (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100))):
