@@ -40,7 +40,9 @@ extern "C" {
  * the noise estimate (mrt_set_noise_tracking, mrt_noise_query, mrt_noise_result, mrt_read_noise, mrt_read_noise_tiles,
  * mrt_noise_factor, mrt_noise_report); the denoiser (mrt_denoise_params, mrt_denoise_params_default, mrt_set_denoise_params,
  * mrt_get_denoise_params, mrt_set_denoise_variance, mrt_get_denoise_variance, mrt_read_denoised, MRT_PRESENT_DENOISED);
- * adaptive sampling (mrt_render_tiles, mrt_render_adaptive, mrt_read_tile_frames). */
+ * adaptive sampling (mrt_render_tiles, mrt_render_adaptive, mrt_read_tile_frames); temporal reprojection (mrt_temporal_params,
+ * mrt_temporal_params_default, mrt_set_temporal, mrt_get_temporal, mrt_temporal_step, mrt_temporal_reset, mrt_read_temporal,
+ * MRT_PRESENT_TEMPORAL). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -190,7 +192,8 @@ int mrt_set_wait_timeout(mrt_ctx* ctx, double seconds);
  * keyed by global pixel index, so any sharding yields the same image.  Only while mrt_frames_done == 0 (after
  * mrt_create or mrt_reset), else MRT_ERR_STATE.  The buffers are allocated anew for the shard's rows: the seed
  * texture is filled again from mrt_create's seed (an earlier mrt_set_seeds is lost), presented images and unread
- * noise reports are discarded; scene, camera, samples per frame, RNG mode and an overridden shuffle stay. */
+ * noise reports are discarded; scene, camera, samples per frame, RNG mode and an overridden shuffle stay.  With temporal
+ * reprojection on, world > 1 is MRT_ERR_STATE and the history is dropped otherwise. */
 int mrt_set_shard(mrt_ctx* ctx, uint32_t rank, uint32_t world);
 /* hipStream_t to launch on (e.g. torch's current stream); NULL = the ctx's own stream. */
 int mrt_set_stream(mrt_ctx* ctx, void* hip_stream);
@@ -359,6 +362,8 @@ enum {
 };
 /* the denoised frame (mrt_read_denoised's image; "denoiser" below), not the framebuffer itself */
 #define MRT_PRESENT_DENOISED 8u
+/* the temporal image (mrt_read_temporal's; "temporal reprojection" below), not the framebuffer itself */
+#define MRT_PRESENT_TEMPORAL 16u
 enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
 typedef struct {               /* 40 bytes */
     uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
@@ -370,11 +375,12 @@ typedef struct {               /* 40 bytes */
 } mrt_present_info;
 /* Queues the present of the most recent frame (after mrt_render(k): its last frame) on the ctx's stream, behind that frame's
  * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB; flags: MRT_PRESENT_FLIP_Y |
- * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
+ * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
  * local rows in mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full
  * frame (MRT_ERR_STATE before the first gather); DENOISED, the `height` rows of the denoised frame, queued on the same stream
  * right before the encode (the guide rebuild if the guides are stale, then the filter; refusals as mrt_read_denoised's, and
- * DENOISED | GATHERED: MRT_ERR_INVALID_ARG).  Must not be called while the ctx's stream is being captured into a graph. */
+ * DENOISED | GATHERED: MRT_ERR_INVALID_ARG); TEMPORAL, the `height` rows of the temporal image, queued the same way (refusals as
+ * mrt_read_temporal's; TEMPORAL | DENOISED and TEMPORAL | GATHERED: MRT_ERR_INVALID_ARG).  Must not be called while the ctx's stream is being captured into a graph. */
 int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
 /* A finished image: *pixels = rows x row_bytes bytes, valid until mrt_present_release, the next acquire, mrt_reset,
  * mrt_set_shard or mrt_destroy.  MRT_ACQUIRE_NEWEST (a viewer, mailbox): the most recent finished image; older finished ones are
@@ -479,8 +485,8 @@ int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tile
 
 /* ------------------------------------------------------------------ denoiser (no reference counterpart)
  *
- * A variance-guided edge-aware a-trous filter (the spatial filter of SVGF; the accumulation is its temporal part) over the most
- * recent frame, for a preview of a progressive render.  It needs noise tracking (mrt_set_noise_tracking: var = S * K below) and an
+ * A variance-guided edge-aware a-trous filter (the spatial filter of SVGF; for a static picture the accumulation is its temporal
+ * part, for a moving one "temporal reprojection" below is) over the most recent frame, for a preview of a progressive render.  It needs noise tracking (mrt_set_noise_tracking: var = S * K below) and an
  * unsharded context (world == 1: a shard's rows are interleaved bands without spatial neighbours); else MRT_ERR_STATE.
  *
  * Guides, per pixel, from ONE ray through the mean of the render's sample positions: the camera ray of u = v = 0.5
@@ -557,6 +563,84 @@ int mrt_get_denoise_variance(mrt_ctx* ctx, uint32_t* mode, uint32_t* spatial_fra
  * row 0 = bottom, as mrt_read_framebuffer; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE with tracking off or on a
  * shard, MRT_ERR_NO_SCENE without a scene. */
 int mrt_read_denoised(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
+
+/* ------------------------------------------------------------------ temporal reprojection (no reference counterpart)
+ *
+ * The accumulation assumes a static picture: after mrt_update_spheres or mrt_set_camera it blends two pictures, and a caller who
+ * resets every step looks at raw noise.  With temporal reprojection on, the context keeps a per-pixel HISTORY that follows the
+ * spheres' and the camera's motion (SVGF's temporal part): mrt_temporal_step reprojects it, blends the newest frame into it and
+ * keeps luminance moments; mrt_read_temporal / MRT_PRESENT_TEMPORAL hand the history, with a variance, to the denoiser's a-trous
+ * iterations.  A hit point rides its sphere, so the motion vector is analytic: the guides hold the first-hit sphere index and
+ * distance per pixel, the device the spheres as they are and -- a copy made by every step -- as they were.
+ *
+ * The intended loop: a context with max_framebuffer_weight = 0 (every blend weight is then 0: the framebuffer is the newest frame
+ * alone); per animation step mrt_update_spheres and / or mrt_set_camera, mrt_redraw, mrt_temporal_step, mrt_present(fmt,
+ * MRT_PRESENT_TEMPORAL | ...).  The step's input is the current framebuffer, whatever it holds: a caller who resets and renders k
+ * frames per step gives it those k frames' mean, which is why mrt_reset does not touch the history.
+ *
+ * Contract.  Everything is queued on the ctx's stream behind the newest blend; nothing waits on the host (mrt_read_temporal, a
+ * read-back, aside); none of these calls may be made while the ctx's stream is being captured into a graph.
+ *   Enabling (mrt_set_temporal): MRT_ERR_STATE on a shard (world > 1); MRT_ERR_INVALID_ARG for a parameter out of range, a wrong
+ *     size or a reserved word that is not 0, nothing changed.  It needs no noise tracking (the history keeps its own moments) and
+ *     creates nothing: the four image-sized history buffers (16 bytes a pixel each) come with the denoiser's at the first step.
+ *     Disabling frees them (after a bounded wait for the ctx's stream).  mrt_set_shard to world > 1 while enabled: MRT_ERR_STATE,
+ *     nothing changed.  New parameters apply from the next step / read on; the history stays.
+ *   mrt_temporal_step: MRT_ERR_STATE if disabled, on a shard, or before the first frame since mrt_create / mrt_reset;
+ *     MRT_ERR_NO_SCENE without a scene.  It rebuilds the guides if they are stale, runs the reprojection, and then snapshots
+ *     "previous" as the state at THIS step: the spheres' (cx, cy, cz, r) into a device copy, the derived camera on the host, and
+ *     the history's two buffer pairs swap.  It advances the history exactly once.  An adaptive accumulation (mrt_render_tiles)
+ *     is no obstacle: only the framebuffer is read.
+ *   Invalidation: mrt_set_world* changes what the sphere indices mean and mrt_set_shard the buffers: both drop the history, as
+ *     mrt_temporal_reset does (every length 0, nothing freed by the reset itself; the next step starts every pixel anew).
+ *     mrt_update_spheres, mrt_regroup_spheres, mrt_set_camera and mrt_reset do not.
+ *   mrt_read_temporal / MRT_PRESENT_TEMPORAL change no state: two calls without a step between them return identical bits.
+ *     MRT_ERR_STATE before the first step since enabling or since the history was dropped.  The filter's parameters are the
+ *     ctx's mrt_denoise_params; alpha is the framebuffer's.
+ *
+ * Definition (float32 in this order; only + - * /, sqrtf, floorf, fminf, fmaxf and comparisons; no fma).  History per texel:
+ * H0 = (r, g, b, len), H1 = (m1, m2, t, bits of the sphere index).  For pixel p: cur = the framebuffer texel; (o, d) the guide ray;
+ * (t, s) the guides' distance and sphere index (-1: a miss); (c1, r1) sphere s as it is, (c0, r0) as it was at the previous step;
+ * o' the previous camera's origin and M the inverse of the 3 x 3 matrix with the columns su, sv, -fw of the previous derived
+ * camera -- mode 0: su = x, sv = y, fw = +z, o' = 0 -- computed on the host in double by cofactors (M = adj / det, det =
+ * (A00 C00 + A01 C01) + A02 C02, every cofactor one difference of two products) and rounded to float.  At the first step after the
+ * history was dropped no tap counts, whatever "previous" holds.
+ *   1 Previous position.  A hit: X = o + t * d (per component), k = r0 / r1, Xp = c0 + (X - c1) * k.  A miss: Xp = o' + d.
+ *   2 Previous pixel.  v = Xp - o';  a = (M00 v.x + M01 v.y) + M02 v.z, b and l from rows 1 and 2 alike.  Unless l > 0: no
+ *     history.  fx = (a / l) * (0.5f * H) + (0.5f * W - 1.0f), fy = (b / l) * (0.5f * H) + (0.5f * H - 1.0f) -- the inverse of the
+ *     guide rays' vx = (x + 1 - W / 2) * 2 / H.  te = sqrtf((v.x v.x + v.y v.y) + v.z v.z).
+ *   3 Taps.  x0 = floorf(fx), wx = fx - x0, y alike; the four taps (x0 + i, y0 + j), j then i, weigh bw = (i ? wx : 1 - wx) *
+ *     (j ? wy : 1 - wy).  A tap q counts only if it lies inside the image, bw > 0, len_q >= 1, H0_q's r, g, b are finite, the
+ *     index bits of H1_q equal s and -- for a hit -- fabsf(t_q - te) <= depth_tol * te.  In tap order, from 0: sw += bw,
+ *     sc += bw * c_q, s1 += bw * m1_q, s2 += bw * m2_q; lmin = the smallest len_q.
+ *   4 Blend.  Lc = lum(cur) (the noise estimate's lum).  With history (sw > 0): cp = sc / sw, m1p = s1 / sw, m2p = s2 / sw,
+ *     N = fminf(lmin + 1, max_history), alpha = 1 / N, c' = cp + alpha * (cur - cp), m1' = m1p + alpha * (Lc - m1p), m2' = m2p +
+ *     alpha * (Lc * Lc - m2p).  Without: c' = cur, m1' = Lc, m2' = Lc * Lc, N = 1.  Stored: H0' = (c', N), H1' = (m1', m2', t, s).
+ *     A cur whose r, g or b is not finite stores H0' = (cur, 0), H1' = (0, 0, t, s): never a tap, passed through by the filter.
+ *   5 Variance (at read / present time; the filter's input is (r, g, b, var)).  N >= max(2, spatial_len): var = fmaxf(0, m2' -
+ *     m1' * m1') / (N - 1).  Otherwise, for a texel with N >= 1 and a finite colour, the denoiser's spatial initial variance:
+ *     the same 7 x 7 taps, w_q = (w_normal * w_depth) * w_albedo with the ctx's denoise parameters, two passes, over L(c'), with
+ *     "S finite" read as len >= 1.  Any other texel: var = 0.
+ *   6 Filter.  The denoiser's prefiltering iterations (as SPATIAL_EARLY runs them behind its spatial estimate: luminance stop on,
+ *     every iteration prefiltered) over that field. */
+typedef struct {            /* 32 bytes */
+    uint32_t size;          /* sizeof(mrt_temporal_params): the version of this struct */
+    uint32_t max_history;   /* 1 .. 256 (default 32): the history length at which the blend becomes an EMA of weight 1 / max_history */
+    uint32_t spatial_len;   /* 1 .. 16 (default 4): shorter histories take the spatial variance */
+    float    depth_tol;     /* finite, > 0 (default 0.05): relative distance tolerance of a history tap */
+    uint32_t reserved[4];   /* 0 */
+} mrt_temporal_params;
+/* Host only: the defaults. */
+void mrt_temporal_params_default(mrt_temporal_params* out);
+/* Turns temporal reprojection on or off; params NULL: the current ones (the defaults at first).  ctx NULL: checks the parameters
+ * only (host only; MRT_ERR_INVALID_ARG with params NULL too). */
+int mrt_set_temporal(mrt_ctx* ctx, int enabled, const mrt_temporal_params* params);
+int mrt_get_temporal(mrt_ctx* ctx, int* enabled, mrt_temporal_params* out);   /* either pointer may be NULL */
+/* Integrates the newest frame into the history; advances it exactly once. */
+int mrt_temporal_step(mrt_ctx* ctx);
+/* Every history length 0; nothing freed.  MRT_ERR_STATE if disabled. */
+int mrt_temporal_reset(mrt_ctx* ctx);
+/* The temporal image: height * width * 4 floats, row 0 = bottom, as mrt_read_framebuffer; synchronises as it does. */
+int mrt_read_temporal(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

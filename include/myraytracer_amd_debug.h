@@ -230,6 +230,15 @@ int mrt_debug_read_hierarchy(mrt_ctx* ctx, uint32_t info[16], double scalars[8],
 int mrt_debug_regroup_info(mrt_ctx* ctx, uint32_t out[4]);
 int mrt_debug_set_regroup_block(mrt_ctx* ctx, uint32_t clusters);
 int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, uint32_t* n_pool);
+/* Diagnostics of temporal reprojection: the context's OWN history (the pair the next step reads: h0 = (r, g, b, len), h1 = (m1,
+ * m2, t, index bits), 4 floats a pixel each, y * width + x), its previous spheres (4 floats each) and, for the load, its previous
+ * derived camera, read / overwritten behind the ctx's stream, so that a test can start a step from a synthetic history.  They
+ * allocate nothing: MRT_ERR_STATE while temporal reprojection is off or before the first step has brought the buffers.  read: cap
+ * in pixels (and at least the sphere count when prev_xyzr is given); any array may be NULL.  load: n_spheres must be the scene's
+ * when prev_xyzr is given; prev_cam NULL keeps the camera; a loaded history counts as stepped (mrt_read_temporal reads it). */
+int mrt_debug_read_temporal(mrt_ctx* ctx, float* h0, float* h1, float* prev_xyzr, size_t cap);
+int mrt_debug_load_temporal(mrt_ctx* ctx, const float* h0, const float* h1, const float* prev_xyzr, size_t n_spheres,
+                            const mrt_camera_raw* prev_cam);
 
 #ifdef __cplusplus
 }

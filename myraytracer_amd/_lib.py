@@ -47,11 +47,13 @@ EXPORTS = [
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
     "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule", "mrt_debug_read_hierarchy",
     "mrt_regroup_spheres", "mrt_debug_regroup_info", "mrt_debug_set_regroup_block", "mrt_debug_pool_clusters",
+    "mrt_temporal_params_default", "mrt_set_temporal", "mrt_get_temporal", "mrt_temporal_step", "mrt_temporal_reset",
+    "mrt_read_temporal", "mrt_debug_read_temporal", "mrt_debug_load_temporal",
 ]
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
-PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED = 1, 2, 8
+PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED, PRESENT_TEMPORAL = 1, 2, 8, 16
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 # how a slot's tile queue was ordered (mrt_debug_read_tile_schedule, MRT_TILE_ORDER_*)
 TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
@@ -110,6 +112,11 @@ class MrtNoiseReport(C.Structure):
 class MrtDenoiseParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_l", C.c_float), ("normal_exp", C.c_uint32),
                 ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class MrtTemporalParams(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("max_history", C.c_uint32), ("spatial_len", C.c_uint32), ("depth_tol", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class MrtSphere(C.Structure):
@@ -344,6 +351,14 @@ def load():
         "mrt_debug_sort_tiles": (i32, [vp, vp, sz, vp, sz, vp]),
         "mrt_debug_read_tile_schedule": (i32, [vp, vp, vp, sz, P(u32), P(u32)]),
         "mrt_debug_read_hierarchy": (i32, [vp] * 15),
+        "mrt_temporal_params_default": (None, [P(MrtTemporalParams)]),
+        "mrt_set_temporal": (i32, [vp, i32, P(MrtTemporalParams)]),
+        "mrt_get_temporal": (i32, [vp, P(i32), P(MrtTemporalParams)]),
+        "mrt_temporal_step": (i32, [vp]),
+        "mrt_temporal_reset": (i32, [vp]),
+        "mrt_read_temporal": (i32, [vp, vp, sz]),
+        "mrt_debug_read_temporal": (i32, [vp, vp, vp, vp, sz]),
+        "mrt_debug_load_temporal": (i32, [vp, vp, vp, vp, sz, P(MrtCameraRaw)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

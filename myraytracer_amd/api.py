@@ -605,13 +605,14 @@ class State:
     #    waiting for the frames in flight
     _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB}
 
-    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False):
+    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False, temporal: bool = False):
         """mrt_present: queue the most recent frame's 8-bit sRGB image ("rgba8" / "bgra8"; flip = rows top-down; gathered = the
-        root's full frame of the last gather; denoise = the denoised frame, read_denoised's image).  Asynchronous."""
+        root's full frame of the last gather; denoise = the denoised frame, read_denoised's image; temporal = the temporal image,
+        read_temporal's).  Asynchronous."""
         if fmt not in self._PRESENT_FORMATS:
             raise ValueError(f"present: format {fmt!r} (rgba8, bgra8)")
         flags = ((_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0) |
-                 (_lib.PRESENT_DENOISED if denoise else 0))
+                 (_lib.PRESENT_DENOISED if denoise else 0) | (_lib.PRESENT_TEMPORAL if temporal else 0))
         self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
 
     def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):
@@ -834,6 +835,72 @@ class State:
             self._check(self._L.mrt_debug_denoise_variance(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows,
                                                            C.byref(p), variance, out.ctypes.data), "mrt_debug_denoise_variance")
         return out
+
+    # -- temporal reprojection (include/myraytracer_amd.h, "temporal reprojection"): a per-pixel history that follows the spheres'
+    #    and the camera's motion, for a moving scene rendered with max_framebuffer_weight 0
+    def set_temporal(self, enabled: bool, **params):
+        """Turn temporal reprojection on / off; params: max_history, spatial_len, depth_tol over the current ones."""
+        p = _lib.MrtTemporalParams()
+        self._check(self._L.mrt_get_temporal(self._ctx, None, C.byref(p)), "mrt_get_temporal")
+        for k, v in params.items():
+            if k not in TEMPORAL_FIELDS:
+                raise ValueError(f"set_temporal: unknown field {k!r} ({', '.join(TEMPORAL_FIELDS)})")
+            setattr(p, k, v)
+        self._check(self._L.mrt_set_temporal(self._ctx, int(enabled), C.byref(p)), "mrt_set_temporal")
+
+    def temporal(self) -> Tuple[bool, dict]:
+        """(enabled, parameters)."""
+        on, p = C.c_int(), _lib.MrtTemporalParams()
+        self._check(self._L.mrt_get_temporal(self._ctx, C.byref(on), C.byref(p)), "mrt_get_temporal")
+        return bool(on.value), temporal_params_dict(p)
+
+    def temporal_step(self):
+        """Integrate the newest frame into the history (asynchronous)."""
+        self._check(self._L.mrt_temporal_step(self._ctx), "mrt_temporal_step")
+
+    def temporal_reset(self):
+        self._check(self._L.mrt_temporal_reset(self._ctx), "mrt_temporal_reset")
+
+    def read_temporal(self) -> np.ndarray:
+        """The temporal image: (H, W, 4) f32, row 0 = bottom; waits for the frames in flight, as read_framebuffer does."""
+        out = np.empty((self.args.height, self.args.width, 4), np.float32)
+        self._check(self._L.mrt_read_temporal(self._ctx, out.ctypes.data, out.size), "mrt_read_temporal")
+        return out
+
+    def debug_read_temporal(self, n_spheres: int) -> dict:
+        """The history the next step reads: h0 (H, W, 4) = (r, g, b, len), h1 (H, W, 4) = (m1, m2, t, index bits), and the
+        previous spheres prev_xyzr (n_spheres, 4)."""
+        h, w = self.args.height, self.args.width
+        d = {"h0": np.empty((h, w, 4), np.float32), "h1": np.empty((h, w, 4), np.float32),
+             "prev_xyzr": np.empty((n_spheres, 4), np.float32)}
+        self._check(self._L.mrt_debug_read_temporal(self._ctx, d["h0"].ctypes.data, d["h1"].ctypes.data, d["prev_xyzr"].ctypes.data,
+                                                    max(h * w, n_spheres)), "mrt_debug_read_temporal")
+        return d
+
+    def debug_load_temporal(self, h0=None, h1=None, prev_xyzr=None, prev_cam: Optional[MrtCameraRaw] = None):
+        """Overwrite the history the next step reads, the previous spheres and / or the previous derived camera."""
+        h0 = None if h0 is None else np.ascontiguousarray(h0, np.float32)
+        h1 = None if h1 is None else np.ascontiguousarray(h1, np.float32)
+        px = None if prev_xyzr is None else np.ascontiguousarray(prev_xyzr, np.float32).reshape(-1, 4)
+        for a in (h0, h1):
+            assert a is None or a.shape == (self.args.height, self.args.width, 4)
+        self._check(self._L.mrt_debug_load_temporal(self._ctx, None if h0 is None else h0.ctypes.data, None if h1 is None else h1.ctypes.data,
+                                                    None if px is None else px.ctypes.data, 0 if px is None else len(px),
+                                                    None if prev_cam is None else C.byref(prev_cam)), "mrt_debug_load_temporal")
+
+
+TEMPORAL_FIELDS = ("max_history", "spatial_len", "depth_tol")
+
+
+def temporal_params_dict(p) -> dict:
+    return {k: (float(getattr(p, k)) if k == "depth_tol" else int(getattr(p, k))) for k in TEMPORAL_FIELDS}
+
+
+def temporal_params_default() -> dict:
+    """mrt_temporal_params_default as a dict (host only)."""
+    p = _lib.MrtTemporalParams()
+    _lib.load().mrt_temporal_params_default(C.byref(p))
+    return temporal_params_dict(p)
 
 
 DENOISE_FIELDS = ("iterations", "sigma_l", "normal_exp", "sigma_z", "sigma_a")

@@ -111,9 +111,10 @@ void set_global_error(const char* msg) { g_err = msg ? msg : ""; }
 
 void free_world(mrt_ctx* c) {
     free_device(c->d_spheres, c->d_clusters, c->d_nodes, c->d_boxes, c->d_boxes_open, c->d_shade, c->d_top_mfma, c->d_member_index,
-                c->d_regroup, c->d_vec4, c->d_f32, c->d_i32);
+                c->d_regroup, c->d_prev_xyzr, c->d_vec4, c->d_f32, c->d_i32);
     c->have_world = false;
     c->guides_stale = true;
+    drop_temporal_history(c);           // (the sphere indices it holds belong to the scene that goes)
 }
 
 int alloc_first_colour_sums(mrt_ctx* c, mrt_ctx::FrameSlot& S) {
@@ -528,6 +529,7 @@ int mrt_set_shard(mrt_ctx* c, uint32_t rank, uint32_t world) {
     if (!c) return MRT_ERR_INVALID_ARG;
     if (world == 0 || rank >= world) return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_shard: rank %u of %u", rank, world);
     if (c->frames_done != 0) return fail(c, MRT_ERR_STATE, "mrt_set_shard: frames already rendered; call mrt_reset first");
+    if (c->temporal_on && world > 1) return fail(c, MRT_ERR_STATE, "mrt_set_shard: temporal reprojection is on (a shard has no history; mrt_set_temporal)");
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(mrt::wait_all(c, __func__));
     for (auto& E : c->present_ring) E.state = mrt_ctx::PresentEntry::kFree;      // (the presented images are discarded)
@@ -816,7 +818,7 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
         if (S.pix_acc_layers < 1) return check_finding(why, cap, "slot %u of %u in use has no colour sums", i, c->frame_slots);
     }
     if (c->have_world) {
-        if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_regroup || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
+        if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_regroup || !c->d_prev_xyzr || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
             return check_finding(why, cap, "have_world without one of the scene's arrays");
         if (!mrt::scene_is_small(c->n_members) && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
     }
@@ -836,6 +838,12 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
     if (!c->present_ring.empty() && (c->present_entry_bytes == 0 || !c->d_present_tables)) return check_finding(why, cap, "a present ring without entry size or tables");
     if (!c->guides_stale && (!c->d_guides || !c->d_guide_rays || !c->d_guide_hits || !c->d_guide_queue || !c->d_guide_cand || !c->d_den[0] || !c->d_den[1] || !c->d_den[2]))
         return check_finding(why, cap, "the guides are marked current without the denoiser's buffers");
+    if (c->temporal_on && c->shard_world != 1) return check_finding(why, cap, "temporal reprojection is on on shard %u of %u", c->shard_rank, c->shard_world);
+    if (c->temporal_cur > 1) return check_finding(why, cap, "temporal history pair %u", c->temporal_cur);
+    if (c->temporal_stepped && (!c->temporal_on || c->temporal_clear || !c->have_world || !c->d_guides || !c->d_den[0] || !c->d_den[1] || !c->d_den[2] ||
+                                !c->d_den[3] || !c->d_den[4] || !c->d_den[5] || !c->d_den[6]))
+        return check_finding(why, cap, "a temporal history is marked readable without temporal reprojection, a scene, the guides or its buffers");
+    if (!c->temporal_on && (c->d_den[3] || c->d_den[4] || c->d_den[5] || c->d_den[6])) return check_finding(why, cap, "history buffers exist while temporal reprojection is off");
     if (c->d_guide_cand == nullptr ? c->guide_cand_words != 0 : c->guide_cand_words == 0) return check_finding(why, cap, "guide bitmap %p of %zu words", (void*)c->d_guide_cand, c->guide_cand_words);
     if (c->tiles_diverged) {
         if (c->n_tiles && !c->d_tile_frames) return check_finding(why, cap, "the accumulation has diverged without the tile frame counts");

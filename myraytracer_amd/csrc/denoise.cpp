@@ -11,8 +11,15 @@ namespace mrt {
 // the denoiser's guides and buffers (sized for the image; allocated at the first denoise, ensure_denoise_buffers)
 void free_denoise_buffers(mrt_ctx* c) {
     free_device(c->d_guide_rays, c->d_guide_hits, c->d_guide_cand, c->d_guide_queue, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2]);
+    free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6]);
     c->guide_cand_words = 0;
     c->guides_stale = true;
+    drop_temporal_history(c);
+}
+
+void drop_temporal_history(mrt_ctx* c) {
+    c->temporal_clear = true;
+    c->temporal_stepped = false;
 }
 
 }  // namespace mrt
@@ -35,14 +42,20 @@ bool denoise_params_ok(const mrt_denoise_params* p) {
 
 int ensure_denoise_buffers(mrt_ctx* c) {
     const size_t n = (size_t)c->args.width * c->args.height;
-    if (!c->d_guides) {         // (each of them unless an earlier, refused attempt already left it: d_guides is the last)
+    // the filter's three buffers; with temporal reprojection on -- and only then -- the history's four behind them
+    const size_t n_den = c->temporal_on ? 7 : 3;
+    if (!c->d_guides || !c->d_den[n_den - 1]) {     // (each of them unless it is there already, an earlier, refused attempt's included)
         if (!c->d_guide_rays) HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
         if (!c->d_guide_hits) HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
         if (!c->d_guide_queue) HIP_TRY(c, hipMalloc((void**)&c->d_guide_queue, 64));
-        for (auto& d : c->d_den)
+        for (auto& d : c->d_den) {
+            if ((size_t)(&d - c->d_den) >= n_den) break;
             if (!d) HIP_TRY(c, hipMalloc((void**)&d, n * 16));
-        HIP_TRY(c, hipMalloc((void**)&c->d_guides, n * 32));
-        c->guides_stale = true;
+        }
+        if (!c->d_guides) {
+            HIP_TRY(c, hipMalloc((void**)&c->d_guides, n * 32));
+            c->guides_stale = true;
+        }
     }
     const size_t words = n + ((size_t)c->n_spheres + 31) / 32 + 1;
     if (c->guide_cand_words < words) {
@@ -120,9 +133,64 @@ int queue_denoise(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// ---- temporal reprojection (include/myraytracer_amd.h, "temporal reprojection") ----------------------------------------------
+bool temporal_params_ok(const mrt_temporal_params* p) {
+    if (p->size != sizeof(mrt_temporal_params) || p->max_history < 1 || p->max_history > 256 || p->spatial_len < 1 || p->spatial_len > 16)
+        return false;
+    if (!(std::isfinite(p->depth_tol) && p->depth_tol > 0.0f)) return false;
+    for (uint32_t r : p->reserved)
+        if (r != 0) return false;
+    return true;
+}
+
+// the refusals of a step, a read and a present of the temporal image; `stepped`: the reads' (they need a history)
+int temporal_check(mrt_ctx* c, const char* who, bool stepped) {
+    if (!c->temporal_on) return fail(c, MRT_ERR_STATE, "%s: temporal reprojection is off (mrt_set_temporal)", who);
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) has no temporal history", who, c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
+    if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
+    if (stepped && !c->temporal_stepped) return fail(c, MRT_ERR_STATE, "%s: no mrt_temporal_step since the history was last empty", who);
+    return MRT_OK;
+}
+
+// The inverse of the matrix with the columns su, sv, -fw of a derived camera (mode 0: x, y, -z) by cofactors, in double, rounded
+// to float, row-major; and the camera's origin.
+void temporal_camera(const mrt_camera_raw& cam, float M[9], float o[3]) {
+    double A[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, -1.0}};
+    for (int k = 0; k < 3; k++) {
+        o[k] = cam.mode != 0 ? cam.origin[k] : 0.0f;
+        if (cam.mode != 0) { A[k][0] = (double)cam.su[k]; A[k][1] = (double)cam.sv[k]; A[k][2] = -(double)cam.fw[k]; }
+    }
+    double C[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            C[i][j] = A[i1][j1] * A[i2][j2] - A[i1][j2] * A[i2][j1];
+        }
+    const double det = (A[0][0] * C[0][0] + A[0][1] * C[0][1]) + A[0][2] * C[0][2];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) M[3 * i + j] = (float)(C[j][i] / det);
+}
+
+// the temporal image into d_den[2]: the history's field (its variance made first), then the filter's iterations
+int queue_temporal_image(mrt_ctx* c) {
+    const uint32_t cur = c->temporal_cur;
+    const mrt::TemporalField field{c->d_den[3 + 2 * cur], c->d_den[4 + 2 * cur], c->temporal.spatial_len};
+    const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], nullptr, 0.0f, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
+                                      c->args.width, c->args.height, c->denoise, 3, c->stream, &field);
+    if (e) return fail(c, MRT_ERR_HIP, "temporal image launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
 }  // namespace
 
 namespace mrt {
+int present_temporal_check(mrt_ctx* c) { return temporal_check(c, "mrt_present", true); }
+int present_temporal(mrt_ctx* c, const float** src) {
+    MRT_TRY(queue_temporal_image(c));
+    *src = c->d_den[2];
+    return MRT_OK;
+}
 // mrt_present's part (present.cpp): checks, then queues the denoise; *src = the denoised frame
 int present_denoised(mrt_ctx* c, const float** src) {
     MRT_TRY(queue_denoise(c));
@@ -179,6 +247,127 @@ int mrt_read_denoised(mrt_ctx* c, float* out, size_t cap) {
     MRT_TRY(queue_denoise(c));
     HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return mrt::wait_stream(c, c->stream, __func__);
+}
+
+void mrt_temporal_params_default(mrt_temporal_params* out) {
+    if (out) *out = mrt::temporal_defaults();
+}
+
+int mrt_set_temporal(mrt_ctx* c, int enabled, const mrt_temporal_params* params) {
+    if (!c && !params) return MRT_ERR_INVALID_ARG;
+    if (params && !temporal_params_ok(params))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_temporal: size %u (%zu), max_history %u (1..256), spatial_len %u (1..16), "
+                    "depth_tol %g (finite, > 0), reserved 0", params->size, sizeof(mrt_temporal_params), params->max_history,
+                    params->spatial_len, params->depth_tol);
+    if (!c) return MRT_OK;              // (ctx NULL: a check of the parameters alone)
+    if (enabled && c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_set_temporal: a shard (world %u) has no temporal history", c->shard_world);
+    if (!enabled && c->temporal_on) {   // the history goes; queued steps and reads may still use it
+        HIP_TRY(c, hipSetDevice(c->device));
+        MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_set_temporal: releasing the history"));
+        mrt::free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6]);
+        mrt::drop_temporal_history(c);
+    }
+    if (params) c->temporal = *params;
+    c->temporal_on = enabled != 0;
+    return MRT_OK;
+}
+
+int mrt_get_temporal(mrt_ctx* c, int* enabled, mrt_temporal_params* out) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (enabled) *enabled = c->temporal_on ? 1 : 0;
+    if (out) *out = c->temporal;
+    return MRT_OK;
+}
+
+int mrt_temporal_step(mrt_ctx* c) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_temporal_step", false));
+    if (c->frames_done == 0) return fail(c, MRT_ERR_STATE, "mrt_temporal_step: no frame since mrt_create / mrt_reset");
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(ensure_guides(c));
+    const size_t n = (size_t)c->args.width * c->args.height;
+    const uint32_t cur = c->temporal_cur;
+    if (c->temporal_clear) {            // every length 0: no tap of this step counts
+        HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
+        c->temporal_prev_cam = c->cam_raw;
+        c->temporal_clear = false;
+    }
+    mrt::TemporalArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.fb = c->d_fb[c->target ^ 1];
+    a.rays = c->d_guide_rays; a.guides = c->d_guides; a.shade = c->d_shade; a.prev_xyzr = c->d_prev_xyzr;
+    a.h0_in = c->d_den[3 + 2 * cur]; a.h1_in = c->d_den[4 + 2 * cur];
+    a.h0_out = c->d_den[3 + 2 * (cur ^ 1)]; a.h1_out = c->d_den[4 + 2 * (cur ^ 1)];
+    a.width = c->args.width; a.height = c->args.height; a.n_spheres = c->n_spheres;
+    temporal_camera(c->temporal_prev_cam, a.M, a.o_prev);
+    a.max_history = (float)c->temporal.max_history; a.depth_tol = c->temporal.depth_tol;
+    int e = mrt::launch_temporal_reproject(a, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+    // "previous" from here on: the state at this step
+    e = mrt::launch_temporal_snapshot(c->d_shade, c->d_prev_xyzr, c->n_spheres, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "temporal snapshot launch failed: %s", hipGetErrorString((hipError_t)e));
+    c->temporal_prev_cam = c->cam_raw;
+    c->temporal_cur = cur ^ 1;
+    c->temporal_stepped = true;
+    return MRT_OK;
+}
+
+int mrt_temporal_reset(mrt_ctx* c) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (!c->temporal_on) return fail(c, MRT_ERR_STATE, "mrt_temporal_reset: temporal reprojection is off (mrt_set_temporal)");
+    mrt::drop_temporal_history(c);      // (the next step zeroes the lengths it reads, on the stream, before it reads them)
+    return MRT_OK;
+}
+
+int mrt_read_temporal(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_read_temporal", true));
+    const size_t n = (size_t)c->args.width * c->args.height * 4;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_temporal: need %zu floats", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(queue_temporal_image(c));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+int mrt_debug_read_temporal(mrt_ctx* c, float* h0, float* h1, float* prev_xyzr, size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_debug_read_temporal", false));
+    if (!c->d_den[6]) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal: no history buffers yet (mrt_temporal_step)");
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (cap < n || (prev_xyzr && cap < c->n_spheres)) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_temporal: need %zu pixels, %u spheres", n, c->n_spheres);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t cur = c->temporal_cur;
+    if (c->temporal_clear) {            // (a dropped history reads as what the next step will see)
+        HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
+        c->temporal_prev_cam = c->cam_raw;
+        c->temporal_clear = false;
+    }
+    if (h0) HIP_TRY(c, hipMemcpyAsync(h0, c->d_den[3 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (h1) HIP_TRY(c, hipMemcpyAsync(h1, c->d_den[4 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(prev_xyzr, c->d_prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+int mrt_debug_load_temporal(mrt_ctx* c, const float* h0, const float* h1, const float* prev_xyzr, size_t n_spheres,
+                            const mrt_camera_raw* prev_cam) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_debug_load_temporal", false));
+    if (!c->d_den[6]) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal: no history buffers yet (mrt_temporal_step)");
+    if (prev_xyzr && n_spheres != c->n_spheres) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_load_temporal: %zu spheres for a scene of %u", n_spheres, c->n_spheres);
+    const size_t n = (size_t)c->args.width * c->args.height;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t cur = c->temporal_cur;
+    if (c->temporal_clear && !h0) HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
+    if (c->temporal_clear && !prev_cam) c->temporal_prev_cam = c->cam_raw;
+    c->temporal_clear = false;
+    if (h0) HIP_TRY(c, hipMemcpyAsync(c->d_den[3 + 2 * cur], h0, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (h1) HIP_TRY(c, hipMemcpyAsync(c->d_den[4 + 2 * cur], h1, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(c->d_prev_xyzr, prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyHostToDevice, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));      // (the caller's arrays are pageable: theirs again on return)
+    if (prev_cam) c->temporal_prev_cam = *prev_cam;
+    c->temporal_stepped = true;
+    return MRT_OK;
 }
 
 int mrt_debug_read_guides(mrt_ctx* c, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap) {

@@ -1,6 +1,6 @@
 // The denoiser (include/myraytracer_amd.h, "denoiser"): first-hit guide buffers and a variance-guided,
 // edge-aware a-trous filter over the framebuffer (the spatial filter of SVGF without its temporal part: the accumulation is
-// the temporal part).  A translation unit of its own, outside the render path's (kernels.hip).
+// the temporal part; a moving scene's is temporal.hip, whose history the same iterations filter).  A translation unit of its own, outside the render path's (kernels.hip).
 //
 // Guides (once per camera / scene): guide_rays_kernel writes one ray per pixel through the mean of the render's sample
 // positions; the closest hits come from the DBG instantiation of render_kernel (launch_debug_world_hit, no candidate bitmap);
@@ -352,6 +352,73 @@ void launch_atrous(bool first, bool last, dim3 grid, dim3 block, hipStream_t st,
     }
 }
 
+// The temporal image's field (variance 3; include/myraytracer_amd.h, "temporal reprojection", 5): A.fb is the history's H0 =
+// (r, g, b, len), h1 its H1 = (m1, m2, t, index); out = (r, g, b, var).  A history of len >= max(2, spatial_len) takes the variance
+// of its own luminance moments.  A shorter one -- a disocclusion, the first frames -- takes spatial_variance_kernel's estimate
+// over L of the history's colours, "S finite" read as len >= 1: 49 taps for those pixels alone, so the kernel is divergent by
+// design, and the pixels that pay are the few that just restarted.  Any other texel -- len < 1, or short with a colour that is
+// not finite -- gets var 0.
+__global__ void __launch_bounds__(kTileX * kTileY) temporal_variance_kernel(const AtrousArgs A, const float4* __restrict__ h1,
+                                                                            float min_len) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = A.fb[i];
+    const float N = cp.w;
+    float var = 0.0f;
+    if (N >= min_len) {
+        const float4 mp = h1[i];
+        var = fmaxf(0.0f, mp.y - mp.x * mp.x) / (N - 1.0f);
+    } else if (N >= 1.0f && __builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
+        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+        const bool miss_p = __float_as_int(gp1.w) < 0;
+        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+        float w[49], l[49];
+        uint64_t used = 0;
+        float m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+        for (int ty = 0; ty < 7; ty++) {
+#pragma unroll
+            for (int tx = 0; tx < 7; tx++) {
+                const int t = ty * 7 + tx;
+                w[t] = 0.0f;
+                l[t] = 0.0f;
+                const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
+                if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
+                float wq, lq;
+                if (tx == 3 && ty == 3) {
+                    wq = 1.0f;
+                    lq = lumf(cp.x, cp.y, cp.z);
+                } else {
+                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                    const float4 cq = A.fb[q];
+                    if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && cq.w >= 1.0f))
+                        continue;
+                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                    const bool miss_q = __float_as_int(gq1.w) < 0;
+                    wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
+                    lq = lumf(cq.x, cq.y, cq.z);
+                }
+                w[t] = wq;
+                l[t] = lq;
+                used |= 1ull << t;
+                m0 = m0 + wq;
+                m1 = m1 + wq * lq;
+            }
+        }
+        const float mean = m1 / m0;
+        float m2 = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 49; t++) {
+            if (!(used >> t & 1ull)) continue;
+            const float d = l[t] - mean;
+            m2 = m2 + w[t] * (d * d);
+        }
+        var = m2 / m0;
+    }
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
+}
+
 }  // namespace
 
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream) {
@@ -370,9 +437,11 @@ int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade
 }
 
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream) {
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
+                   const TemporalField* temporal) {
     if (width == 0 || height == 0) return 0;
-    const bool spatial = variance == 2;
+    if ((variance == 3) != (temporal != nullptr)) return (int)hipErrorInvalidValue;
+    const bool spatial = variance >= 2;         // (iteration 0 reads a field made before it: the spatial estimate's, the history's)
     AtrousArgs A;
     A.fb = reinterpret_cast<const float4*>(fb);
     A.S = S;
@@ -391,7 +460,14 @@ int launch_denoise(const float* fb, const float* S, float K, const float* guides
     const bool prefilter = variance != 0 && A.lum_stop;
     if (spatial) {          // into pong, where iteration 0 reads it as "the previous iteration's" (and iteration 1 writes pong after it)
         A.out = buf[1];
-        hipLaunchKernelGGL(spatial_variance_kernel, grid, block, 0, st, A);
+        if (temporal) {
+            const uint32_t min_len = temporal->spatial_len > 2u ? temporal->spatial_len : 2u;
+            A.fb = reinterpret_cast<const float4*>(temporal->h0);
+            hipLaunchKernelGGL(temporal_variance_kernel, grid, block, 0, st, A, reinterpret_cast<const float4*>(temporal->h1), (float)min_len);
+            A.fb = reinterpret_cast<const float4*>(fb);
+        } else {
+            hipLaunchKernelGGL(spatial_variance_kernel, grid, block, 0, st, A);
+        }
     }
     const uint32_t n = prm.iterations;
     for (uint32_t it = 0; it < n; it++) {

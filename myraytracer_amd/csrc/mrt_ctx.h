@@ -221,7 +221,21 @@ struct mrt_ctx {
     size_t guide_cand_words = 0;
     uint32_t* d_guide_queue = nullptr;              // the DBG launch's tile queue counter
     float* d_guides = nullptr;                      // 2 float4 per pixel
-    float* d_den[3] = {nullptr, nullptr, nullptr};  // ping, pong, the denoised frame: a float4 per pixel
+    // ping, pong, the denoised frame; with temporal reprojection on also the history, H0 and H1 of pair 0 and of pair 1: a float4
+    // per pixel each
+    float* d_den[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+
+    // temporal reprojection (mrt_set_temporal / mrt_temporal_step / mrt_read_temporal, denoise.cpp; temporal.hip): the history
+    // the next step reads is pair temporal_cur (d_den[3 + 2 cur] = H0, d_den[4 + 2 cur] = H1), the step writes the other pair and
+    // swaps.  temporal_clear: the pair to read holds nothing valid (just allocated, or the history was dropped): the next step
+    // zeroes its H0 first.  temporal_stepped: a step since then (what the reads need).  "Previous": the spheres' (cx, cy, cz, r)
+    // at the last step, a scene buffer (mrt_set_world_raw makes it, free_world frees it), and the derived camera.
+    bool temporal_on = false;
+    mrt_temporal_params temporal = mrt::temporal_defaults();
+    uint32_t temporal_cur = 0;
+    bool temporal_clear = true, temporal_stepped = false;
+    float* d_prev_xyzr = nullptr;
+    mrt_camera_raw temporal_prev_cam{};
 
     // adaptive sampling (mrt_render_tiles / mrt_render_adaptive, frames.cpp / noise.cpp; adaptive.hip): every tile's frame count n_t.  Until the
     // first subset frame every n_t is frames_done and nothing differs from a uniform accumulation.  From it on (tiles_diverged,
@@ -302,6 +316,10 @@ int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, 
 void free_denoise_buffers(mrt_ctx* c);
 int present_denoised_check(mrt_ctx* c);
 int present_denoised(mrt_ctx* c, const float** src);
+// ... the same two for the temporal image, and the history dropped (mrt_set_world*, mrt_set_shard: nothing queued, nothing freed)
+int present_temporal_check(mrt_ctx* c);
+int present_temporal(mrt_ctx* c, const float** src);
+void drop_temporal_history(mrt_ctx* c);
 
 }  // namespace mrt
 

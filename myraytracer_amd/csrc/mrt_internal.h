@@ -313,12 +313,45 @@ int launch_regroup(const RegroupArgs& a, void* stream);
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream);
 int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade, const int32_t* mat_ty, float* guides,
                       uint32_t width, uint32_t height, void* stream);
+// variance 3 (the temporal image, mrt_read_temporal): the field is the history's -- colour and length from h0, the luminance
+// moments from h1, var as "temporal reprojection" defines it (temporal_variance_kernel, into pong as variance 2's) -- and every
+// iteration prefiltered; S and K are not read, fb gives the alpha.
+struct TemporalField { const float* h0; const float* h1; uint32_t spatial_len; };
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream);
+                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
+                   const TemporalField* temporal = nullptr);
 inline mrt_denoise_params denoise_defaults() {
     mrt_denoise_params p{};
     p.size = sizeof(mrt_denoise_params);
     p.iterations = 5; p.sigma_l = 8.0f; p.normal_exp = 7; p.sigma_z = 0.05f; p.sigma_a = 0.1f;   // tuned: profiles/denoise_quality.txt
+    return p;
+}
+
+
+// temporal.hip (include/myraytracer_amd.h, "temporal reprojection"): one step of the history.  fb: the newest frame; rays / guides:
+// the first-hit guides of the current camera and scene; shade: the spheres as they are; prev_xyzr: (cx, cy, cz, r) per sphere as
+// they were at the previous step; h0 / h1: the history, float4 per texel, in -> out (different buffers); M: the inverse of the
+// previous camera's (su, sv, -fw) as rows, o_prev its origin.  launch_temporal_snapshot: floats 0..3 of shade -> prev_xyzr.
+struct TemporalArgs {
+    const float* fb;
+    const float* rays;
+    const float* guides;
+    const float* shade;
+    const float* prev_xyzr;
+    const float* h0_in;
+    const float* h1_in;
+    float* h0_out;
+    float* h1_out;
+    uint32_t width, height, n_spheres;
+    float M[9], o_prev[3];
+    float max_history, depth_tol;
+};
+int launch_temporal_reproject(const TemporalArgs& a, void* stream);
+int launch_temporal_snapshot(const float* shade, float* prev_xyzr, uint32_t n_spheres, void* stream);
+inline mrt_temporal_params temporal_defaults() {
+    mrt_temporal_params p{};
+    p.size = sizeof(mrt_temporal_params);
+    p.max_history = 32; p.spatial_len = 4; p.depth_tol = 0.05f;
     return p;
 }
 

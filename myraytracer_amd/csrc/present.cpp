@@ -127,15 +127,19 @@ extern "C" {
 int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (!c) return MRT_ERR_INVALID_ARG;
     if (!present_format_ok(format)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: format %d", format);
-    if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED))
+    if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
     const bool gathered = (flags & MRT_PRESENT_GATHERED) != 0, denoised = (flags & MRT_PRESENT_DENOISED) != 0;
+    const bool temporal = (flags & MRT_PRESENT_TEMPORAL) != 0;
     if (gathered && denoised) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the gathered frame cannot be denoised (it has no S)");
+    if (temporal && (gathered || denoised))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the temporal image is neither the gathered nor the denoised frame (flags 0x%x)", flags);
     if (denoised) MRT_TRY(mrt::present_denoised_check(c));
+    if (temporal) MRT_TRY(mrt::present_temporal_check(c));
     const uint32_t width = c->args.width;
     const float* src;
     uint32_t rows;
-    if (denoised) {
+    if (denoised || temporal) {
         src = nullptr;              // (queued below, right before the encode)
         rows = c->args.height;
     } else if (gathered) {
@@ -161,6 +165,7 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     PresentEntry& E = c->present_ring[i];
     E.state = PresentEntry::kFree;
     if (denoised) MRT_TRY(mrt::present_denoised(c, &src));
+    if (temporal) MRT_TRY(mrt::present_temporal(c, &src));
     const int e = mrt::launch_present(src, E.d_img, width, rows, (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u,
                                       format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u, c->d_present_tables, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "present launch failed: %s", hipGetErrorString((hipError_t)e));

@@ -246,6 +246,12 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         }
     }
     MRT_TRY(upload((void**)&c->d_shade, shade.data(), shade.size() * sizeof(float)));
+    {
+        // temporal reprojection's "previous" spheres (mrt_temporal_step snapshots into it): (cx, cy, cz, r) each, the scene's own to begin with
+        std::vector<float> xyzr(4 * ((size_t)n ? (size_t)n : 1), 0.0f);
+        for (int64_t i = 0; i < n; i++) std::memcpy(xyzr.data() + 4 * (size_t)i, shade.data() + 8 * (size_t)i, 4 * sizeof(float));
+        MRT_TRY(upload((void**)&c->d_prev_xyzr, xyzr.data(), xyzr.size() * sizeof(float)));
+    }
     MRT_TRY(upload((void**)&c->d_vec4, vec4, n_vec4 * 4 * sizeof(float)));
     MRT_TRY(upload((void**)&c->d_f32, f32, n_f32 * sizeof(float)));
     MRT_TRY(upload((void**)&c->d_i32, i32, n_i32 * sizeof(int32_t)));

@@ -12,7 +12,12 @@
    and C5 -- host time of the call, device time between HIP events on the context's stream around it -- next to the same
    process's mrt_set_world call; (2) the animated C5 three ways in one process -- the refit alone, a regroup every N steps, a
    rebuild (mrt_set_world) every N steps -- with the member tests per world_hit by quarter; (3) the static C5 and C3 as built and
-   after one regroup with no motion: the render kernel's time (mrt_kernel_ms_history) and member tests per world_hit."""
+   after one regroup with no motion: the render kernel's time (mrt_kernel_ms_history) and member tests per world_hit.
+   --temporal prints the section "temporal" instead (mrt_temporal_step): the animated C3 and C5 through
+   mrt_update_spheres at max_framebuffer_weight 0, one frame a step, two ways in one process -- the frame and a present of the
+   framebuffer; the frame, mrt_temporal_step and a present of the temporal image -- with the steps per second and the time between
+   HIP events on the context's stream around the step (guide rebuild + reprojection + snapshot) and around the temporal present
+   (variance + a-trous iterations + encode)."""
 import argparse
 import os
 import sys
@@ -30,6 +35,7 @@ ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--walk", type=float, default=0.0005)
 ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--regroup-every", type=int, default=0)
+ap.add_argument("--temporal", action="store_true")
 a = ap.parse_args()
 W, H = a.size
 
@@ -175,6 +181,54 @@ def static_cost(name, spheres, cam):
         print(f"  {name} static, round {rnd + 1}: regrouped / as built = {r[0] / b[0]:.4f} x the kernel's median time ({r[1] / b[1]:.4f} x its minimum), "
               f"{r[2] / b[2]:.4f} x the member tests", flush=True)
 
+
+def temporal_cost(name, spheres, cam, path):
+    rates = {}
+    for temporal in (False, True):
+        stream = torch.cuda.Stream()
+        with M.State(M.Args(W, H, 1, a.depth, 0.0), seed=1, stream=stream.cuda_stream) as st:
+            st.set_world(spheres)
+            st.set_camera(cam)
+            st.set_temporal(temporal)
+            st.set_present_ring(4)
+            for _ in range(8):                      # (the schedule's trials, the first step's allocations and the ring)
+                st.redraw()
+                if temporal:
+                    st.temporal_step()
+                st.present("rgba8", temporal=temporal)
+            st.sync()
+            steps, presents = [], []
+            t0 = time.perf_counter()
+            for xyzr in path:
+                st.update_spheres(0, xyzr)
+                st.redraw()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                ev[0].record(stream)
+                if temporal:
+                    st.temporal_step()
+                ev[1].record(stream)
+                ev[2].record(stream)
+                st.present("rgba8", temporal=temporal)
+                ev[3].record(stream)
+                steps.append(ev[:2])
+                presents.append(ev[2:])
+            st.sync()
+            sec = time.perf_counter() - t0
+        rates[temporal] = len(path) / sec
+        step_ms = np.array([e0.elapsed_time(e1) for e0, e1 in steps])
+        pres_ms = np.array([e0.elapsed_time(e1) for e0, e1 in presents])
+        print(f"  {name} {'frame + step + temporal present' if temporal else 'frame + present               '} {rates[temporal]:8.1f} steps/s"
+              + (f"  mrt_temporal_step on the device (events): median {np.median(step_ms):.4f} ms, max {step_ms.max():.4f};" if temporal else "")
+              + f"  present (kernels + copy, events): median {np.median(pres_ms):.4f} ms, max {pres_ms.max():.4f}", flush=True)
+    print(f"  {name}: with the temporal step and present / without = {rates[True] / rates[False]:.3f} x the steps per second", flush=True)
+
+
+if a.temporal:
+    print(f"temporal: {W}x{H} x 1 spp, depth {a.depth}, max_framebuffer_weight 0; {a.steps} steps of a random walk ({a.walk} x the scene's size a "
+          f"step), one frame a step; build {M._lib.load().mrt_build_id().decode()}", flush=True)
+    for name, (spheres, cam) in (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100))):
+        temporal_cost(name, spheres, cam, walk(spheres, a.steps, np.random.default_rng(1)))
+    sys.exit(0)
 
 if a.regroup_every:
     N = a.regroup_every

@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """Dev helper: registers / scratch / LDS of every render_kernel instantiation, from the ISA hipcc emits for gfx950
 (the same compile scripts/check_isa.py does).  A non-zero scratch size = spilled registers.
-    python scripts/kernel_resources.py [--all]"""
+    python scripts/kernel_resources.py [--all] [file.hip]
+   With a file (e.g. myraytracer_amd/csrc/temporal.hip, denoise.hip): every kernel of that translation unit instead."""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 from check_isa import DEFAULT_FLAGS, SRC
+other = [x for x in sys.argv[1:] if x.endswith(".hip")]
+if other:
+    SRC = other[0] if os.path.exists(other[0]) else os.path.join(ROOT, "myraytracer_amd", "csrc", other[0])
+    sys.argv.append("--all")
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "k.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + DEFAULT_FLAGS.split() + ["--cuda-device-only", "-S", "-o", out, SRC])
