@@ -42,7 +42,8 @@ extern "C" {
  * mrt_get_denoise_params, mrt_set_denoise_variance, mrt_get_denoise_variance, mrt_read_denoised, MRT_PRESENT_DENOISED);
  * adaptive sampling (mrt_render_tiles, mrt_render_adaptive, mrt_read_tile_frames); temporal reprojection (mrt_temporal_params,
  * mrt_temporal_params_default, mrt_set_temporal, mrt_get_temporal, mrt_temporal_step, mrt_temporal_reset, mrt_read_temporal,
- * MRT_PRESENT_TEMPORAL). */
+ * MRT_PRESENT_TEMPORAL); the temporal response (mrt_temporal_response, mrt_temporal_response_default,
+ * mrt_set_temporal_response, mrt_get_temporal_response). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -641,6 +642,55 @@ int mrt_temporal_step(mrt_ctx* ctx);
 int mrt_temporal_reset(mrt_ctx* ctx);
 /* The temporal image: height * width * 4 floats, row 0 = bottom, as mrt_read_framebuffer; synchronises as it does. */
 int mrt_read_temporal(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
+
+/* The temporal RESPONSE: a fast-history clamp and an anti-lag rule for what the index and depth tests of step 3 let through.
+ * A reflection or a refraction moves with the spheres BEHIND the first hit, which the motion vector does not know: a pixel on a
+ * mirror keeps its full history while what it shows changes, and at max_history 32 the stale colour decays by 1 / 32 a step.
+ * With the response on the history carries a third texel, H2 = (fr, fg, fb, valid): a FAST history of the same taps whose length
+ * stops at fast_history.  After every step the long history's colour is clamped to the local statistics of the fast one, and
+ * where the clamp had to act the long history's length is pulled towards the fast length (the fast-history clamping of real-time
+ * denoisers).  Off -- the default -- every bit, buffer and launch of mrt_temporal_step is what it is without it.
+ *
+ * Contract.  The setting lives as long as the temporal parameters do: mrt_reset, mrt_set_world*, mrt_set_camera and mrt_set_shard
+ * keep it.  It may be set whether or not temporal reprojection is enabled, and setting it creates nothing.  A call that changes
+ * `enabled` drops the history, as mrt_temporal_reset does (mrt_read_temporal / MRT_PRESENT_TEMPORAL: MRT_ERR_STATE until the next
+ * step); a call that changes only the three numbers keeps it and applies from the next step on.  With `enabled` on, the first
+ * mrt_temporal_step brings two more image-sized buffers, the H2 pair (16 bytes a pixel each), with the history's and by the same
+ * means; they swap with the other two pairs, are freed when temporal reprojection is disabled or the ctx destroyed (not when
+ * the response alone is turned off), and a dropped history zeroes the H2 the next step reads.  MRT_ERR_INVALID_ARG, nothing
+ * changed: a wrong size, enabled above 1, fast_history outside 1 .. 16, a clamp_sigma that is not finite and > 0, an antilag
+ * outside 0 .. 1 (a NaN included), a reserved word that is not 0, a NULL argument.  Every refusal of the step, the read and the
+ * present is what it was; mrt_read_temporal and MRT_PRESENT_TEMPORAL read H0 and H1 as before.
+ *
+ * Definition (float32 in this order; only + - * /, sqrtf, floorf, fminf, fmaxf, fabsf and comparisons; no fma).  Steps 1 to 3 are
+ * the ones above: the same taps count, with the same weights.
+ *   3 also, for every counted tap, in tap order, from 0: sf += bw * H2_q.rgb (whatever H2_q's valid says).
+ *   4 also.  With history: fp = sf / sw, Nf = fminf(N, fast_history), f' = fp + (1 / Nf) * (cur - fp).  Without: f' = cur.
+ *     Stored: H2' = (f', 1).  A cur whose r, g or b is not finite stores H2' = (cur, 0).
+ *   4b Clamp, after step 4 of EVERY pixel, for a pixel whose H0'.w >= 2 (one that found history).  Window: the 5 x 5 pixels around
+ *     it, dy then dx from -2 to 2, the centre included.  A window tap q counts if it lies inside the image, H2'_q.w == 1, H2'_q's
+ *     r, g, b are finite and the index bits of H1'_q equal the pixel's own.  Per channel, in tap order, from 0: s1 += f_q,
+ *     s2 += f_q * f_q; n += 1 (a float).  Fewer than 2 counted taps: the pixel stays as step 4 left it.  Otherwise per channel
+ *     mean = s1 / n, sd = sqrtf(fmaxf(0, s2 / n - mean * mean)), e = clamp_sigma * sd, c'' = fminf(fmaxf(c', mean - e), mean + e).
+ *   4c Anti-lag.  d = fmaxf(fmaxf(fabsf(c''.r - c'.r), fabsf(c''.g - c'.g)), fabsf(c''.b - c'.b)), emax = fmaxf(fmaxf(e.r, e.g),
+ *     e.b), r = fminf(1, d / (emax + 1e-6f)), N'' = N + (antilag * r) * (fminf(N, fast_history) - N).
+ *     Stored: H0' = (c'', N'').  m1', m2' and H1' are step 4's.
+ * The stored length may therefore be fractional (step 3's lmin and step 5's N take it as the float it is).  The luminance
+ * moments are not clamped: a pixel that was clamped reads a wide variance for a few steps and the filter blurs it more -- a short
+ * history wants more spatial support. */
+typedef struct {            /* 32 bytes */
+    uint32_t size;          /* sizeof(mrt_temporal_response): the version of this struct */
+    uint32_t enabled;       /* 0 (default): mrt_temporal_step is exactly what it is without the response; 1: on */
+    uint32_t fast_history;  /* 1 .. 16 (default 4): the length at which the fast history becomes an EMA */
+    float    clamp_sigma;   /* finite, > 0 (default 2): half-width of the clamp box in standard deviations */
+    float    antilag;       /* 0 .. 1 (default 1): how far a fully clamped pixel's length is pulled to the fast length */
+    uint32_t reserved[3];   /* 0 */
+} mrt_temporal_response;
+/* Host only: the defaults (enabled = 0). */
+void mrt_temporal_response_default(mrt_temporal_response* out);
+/* ctx NULL: checks the setting only (host only). */
+int mrt_set_temporal_response(mrt_ctx* ctx, const mrt_temporal_response* response);
+int mrt_get_temporal_response(mrt_ctx* ctx, mrt_temporal_response* out);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

@@ -49,6 +49,8 @@ EXPORTS = [
     "mrt_regroup_spheres", "mrt_debug_regroup_info", "mrt_debug_set_regroup_block", "mrt_debug_pool_clusters",
     "mrt_temporal_params_default", "mrt_set_temporal", "mrt_get_temporal", "mrt_temporal_step", "mrt_temporal_reset",
     "mrt_read_temporal", "mrt_debug_read_temporal", "mrt_debug_load_temporal",
+    "mrt_temporal_response_default", "mrt_set_temporal_response", "mrt_get_temporal_response",
+    "mrt_debug_read_temporal_fast", "mrt_debug_load_temporal_fast",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -117,6 +119,11 @@ class MrtDenoiseParams(C.Structure):
 class MrtTemporalParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("max_history", C.c_uint32), ("spatial_len", C.c_uint32), ("depth_tol", C.c_float),
                 ("reserved", C.c_uint32 * 4)]
+
+
+class MrtTemporalResponse(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("enabled", C.c_uint32), ("fast_history", C.c_uint32), ("clamp_sigma", C.c_float),
+                ("antilag", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
 class MrtSphere(C.Structure):
@@ -359,6 +366,11 @@ def load():
         "mrt_read_temporal": (i32, [vp, vp, sz]),
         "mrt_debug_read_temporal": (i32, [vp, vp, vp, vp, sz]),
         "mrt_debug_load_temporal": (i32, [vp, vp, vp, vp, sz, P(MrtCameraRaw)]),
+        "mrt_temporal_response_default": (None, [P(MrtTemporalResponse)]),
+        "mrt_set_temporal_response": (i32, [vp, P(MrtTemporalResponse)]),
+        "mrt_get_temporal_response": (i32, [vp, P(MrtTemporalResponse)]),
+        "mrt_debug_read_temporal_fast": (i32, [vp, vp, sz]),
+        "mrt_debug_load_temporal_fast": (i32, [vp, vp]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

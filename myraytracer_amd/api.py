@@ -888,8 +888,41 @@ class State:
                                                     None if px is None else px.ctypes.data, 0 if px is None else len(px),
                                                     None if prev_cam is None else C.byref(prev_cam)), "mrt_debug_load_temporal")
 
+    # -- the temporal response ("temporal reprojection", steps 4b and 4c): a fast-history clamp and an anti-lag rule for what moves
+    #    behind the first hit
+    def set_temporal_response(self, enabled: bool, **numbers):
+        """Turn the response on / off; numbers: fast_history, clamp_sigma, antilag over the current ones.  A change of `enabled`
+        drops the history."""
+        p = _lib.MrtTemporalResponse()
+        self._check(self._L.mrt_get_temporal_response(self._ctx, C.byref(p)), "mrt_get_temporal_response")
+        for k, v in numbers.items():
+            if k not in RESPONSE_FIELDS:
+                raise ValueError(f"set_temporal_response: unknown field {k!r} ({', '.join(RESPONSE_FIELDS)})")
+            setattr(p, k, v)
+        p.enabled = int(bool(enabled))
+        self._check(self._L.mrt_set_temporal_response(self._ctx, C.byref(p)), "mrt_set_temporal_response")
+
+    def temporal_response(self) -> Tuple[bool, dict]:
+        """(enabled, numbers)."""
+        p = _lib.MrtTemporalResponse()
+        self._check(self._L.mrt_get_temporal_response(self._ctx, C.byref(p)), "mrt_get_temporal_response")
+        return bool(p.enabled), temporal_response_dict(p)
+
+    def debug_read_temporal_fast(self) -> np.ndarray:
+        """The fast history the next step reads: h2 (H, W, 4) = (fr, fg, fb, valid)."""
+        out = np.empty((self.args.height, self.args.width, 4), np.float32)
+        self._check(self._L.mrt_debug_read_temporal_fast(self._ctx, out.ctypes.data, out.shape[0] * out.shape[1]), "mrt_debug_read_temporal_fast")
+        return out
+
+    def debug_load_temporal_fast(self, h2):
+        """Overwrite the fast history the next step reads."""
+        h2 = np.ascontiguousarray(h2, np.float32)
+        assert h2.shape == (self.args.height, self.args.width, 4)
+        self._check(self._L.mrt_debug_load_temporal_fast(self._ctx, h2.ctypes.data), "mrt_debug_load_temporal_fast")
+
 
 TEMPORAL_FIELDS = ("max_history", "spatial_len", "depth_tol")
+RESPONSE_FIELDS = ("fast_history", "clamp_sigma", "antilag")
 
 
 def temporal_params_dict(p) -> dict:
@@ -980,3 +1013,14 @@ def unshard_rows(gathered: np.ndarray, height: int) -> np.ndarray:
     if st:
         raise MrtError(st, "mrt_unshard_rows")
     return out
+
+
+def temporal_response_dict(p) -> dict:
+    return {k: (int(getattr(p, k)) if k == "fast_history" else float(getattr(p, k))) for k in RESPONSE_FIELDS}
+
+
+def temporal_response_default() -> dict:
+    """mrt_temporal_response_default's numbers as a dict (host only; enabled is 0)."""
+    p = _lib.MrtTemporalResponse()
+    _lib.load().mrt_temporal_response_default(C.byref(p))
+    return temporal_response_dict(p)

@@ -844,6 +844,11 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
                                 !c->d_den[3] || !c->d_den[4] || !c->d_den[5] || !c->d_den[6]))
         return check_finding(why, cap, "a temporal history is marked readable without temporal reprojection, a scene, the guides or its buffers");
     if (!c->temporal_on && (c->d_den[3] || c->d_den[4] || c->d_den[5] || c->d_den[6])) return check_finding(why, cap, "history buffers exist while temporal reprojection is off");
+    if (c->temporal_stepped && c->temporal_response.enabled && (!c->d_den[7] || !c->d_den[8]))
+        return check_finding(why, cap, "a temporal history with the response on is marked readable without the fast history's buffers");
+    if (!c->temporal_on && (c->d_den[7] || c->d_den[8])) return check_finding(why, cap, "fast history buffers exist while temporal reprojection is off");
+    if (c->temporal_response.enabled > 1 || c->temporal_response.size != sizeof(mrt_temporal_response))
+        return check_finding(why, cap, "temporal response enabled %u, size %u", c->temporal_response.enabled, c->temporal_response.size);
     if (c->d_guide_cand == nullptr ? c->guide_cand_words != 0 : c->guide_cand_words == 0) return check_finding(why, cap, "guide bitmap %p of %zu words", (void*)c->d_guide_cand, c->guide_cand_words);
     if (c->tiles_diverged) {
         if (c->n_tiles && !c->d_tile_frames) return check_finding(why, cap, "the accumulation has diverged without the tile frame counts");

@@ -11,7 +11,7 @@ namespace mrt {
 // the denoiser's guides and buffers (sized for the image; allocated at the first denoise, ensure_denoise_buffers)
 void free_denoise_buffers(mrt_ctx* c) {
     free_device(c->d_guide_rays, c->d_guide_hits, c->d_guide_cand, c->d_guide_queue, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2]);
-    free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6]);
+    free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6], c->d_den[7], c->d_den[8]);
     c->guide_cand_words = 0;
     c->guides_stale = true;
     drop_temporal_history(c);
@@ -42,8 +42,9 @@ bool denoise_params_ok(const mrt_denoise_params* p) {
 
 int ensure_denoise_buffers(mrt_ctx* c) {
     const size_t n = (size_t)c->args.width * c->args.height;
-    // the filter's three buffers; with temporal reprojection on -- and only then -- the history's four behind them
-    const size_t n_den = c->temporal_on ? 7 : 3;
+    // the filter's three buffers; with temporal reprojection on -- and only then -- the history's four behind them, and with its
+    // response on as well the fast history's two behind those
+    const size_t n_den = !c->temporal_on ? 3 : c->temporal_response.enabled ? 9 : 7;
     if (!c->d_guides || !c->d_den[n_den - 1]) {     // (each of them unless it is there already, an earlier, refused attempt's included)
         if (!c->d_guide_rays) HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
         if (!c->d_guide_hits) HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
@@ -172,6 +173,29 @@ void temporal_camera(const mrt_camera_raw& cam, float M[9], float o[3]) {
         for (int j = 0; j < 3; j++) M[3 * i + j] = (float)(C[j][i] / det);
 }
 
+bool temporal_response_ok(const mrt_temporal_response* p) {
+    if (p->size != sizeof(mrt_temporal_response) || p->enabled > 1 || p->fast_history < 1 || p->fast_history > 16) return false;
+    if (!(std::isfinite(p->clamp_sigma) && p->clamp_sigma > 0.0f) || !(p->antilag >= 0.0f && p->antilag <= 1.0f)) return false;
+    for (uint32_t r : p->reserved)
+        if (r != 0) return false;
+    return true;
+}
+
+// the history's buffers are there: the four, and with the response on the fast history's two
+bool have_history_buffers(const mrt_ctx* c) { return c->d_den[6] && (!c->temporal_response.enabled || c->d_den[8]); }
+
+// A dropped history, made what the next step reads: every length 0 (no tap counts), the fast history zeroed with it, "previous"
+// camera the current one.  Queued on the ctx's stream.
+int clear_history(mrt_ctx* c) {
+    const size_t n = (size_t)c->args.width * c->args.height;
+    const uint32_t cur = c->temporal_cur;
+    HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
+    if (c->temporal_response.enabled && c->d_den[7 + cur]) HIP_TRY(c, hipMemsetAsync(c->d_den[7 + cur], 0, n * 16, c->stream));
+    c->temporal_prev_cam = c->cam_raw;
+    c->temporal_clear = false;
+    return MRT_OK;
+}
+
 // the temporal image into d_den[2]: the history's field (its variance made first), then the filter's iterations
 int queue_temporal_image(mrt_ctx* c) {
     const uint32_t cur = c->temporal_cur;
@@ -264,7 +288,7 @@ int mrt_set_temporal(mrt_ctx* c, int enabled, const mrt_temporal_params* params)
     if (!enabled && c->temporal_on) {   // the history goes; queued steps and reads may still use it
         HIP_TRY(c, hipSetDevice(c->device));
         MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_set_temporal: releasing the history"));
-        mrt::free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6]);
+        mrt::free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6], c->d_den[7], c->d_den[8]);
         mrt::drop_temporal_history(c);
     }
     if (params) c->temporal = *params;
@@ -279,19 +303,39 @@ int mrt_get_temporal(mrt_ctx* c, int* enabled, mrt_temporal_params* out) {
     return MRT_OK;
 }
 
+void mrt_temporal_response_default(mrt_temporal_response* out) {
+    if (out) *out = mrt::temporal_response_defaults();
+}
+
+int mrt_set_temporal_response(mrt_ctx* c, const mrt_temporal_response* r) {
+    if (!r) return MRT_ERR_INVALID_ARG;
+    if (!temporal_response_ok(r))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_temporal_response: size %u (%zu), enabled %u (0, 1), fast_history %u (1..16), "
+                    "clamp_sigma %g (finite, > 0), antilag %g (0..1), reserved 0", r->size, sizeof(mrt_temporal_response), r->enabled,
+                    r->fast_history, r->clamp_sigma, r->antilag);
+    if (!c) return MRT_OK;              // (ctx NULL: a check of the setting alone)
+    // another kind of history from the next step on: what is there goes (nothing queued, nothing freed; the H2 pair comes with
+    // the first step that needs it)
+    if (r->enabled != c->temporal_response.enabled) mrt::drop_temporal_history(c);
+    c->temporal_response = *r;
+    return MRT_OK;
+}
+
+int mrt_get_temporal_response(mrt_ctx* c, mrt_temporal_response* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = c->temporal_response;
+    return MRT_OK;
+}
+
 int mrt_temporal_step(mrt_ctx* c) {
     if (!c) return MRT_ERR_INVALID_ARG;
     MRT_TRY(temporal_check(c, "mrt_temporal_step", false));
     if (c->frames_done == 0) return fail(c, MRT_ERR_STATE, "mrt_temporal_step: no frame since mrt_create / mrt_reset");
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(ensure_guides(c));
-    const size_t n = (size_t)c->args.width * c->args.height;
     const uint32_t cur = c->temporal_cur;
-    if (c->temporal_clear) {            // every length 0: no tap of this step counts
-        HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
-        c->temporal_prev_cam = c->cam_raw;
-        c->temporal_clear = false;
-    }
+    const mrt_temporal_response& resp = c->temporal_response;
+    if (c->temporal_clear) MRT_TRY(clear_history(c));       // every length 0: no tap of this step counts
     mrt::TemporalArgs a;
     std::memset(&a, 0, sizeof a);
     a.fb = c->d_fb[c->target ^ 1];
@@ -301,8 +345,18 @@ int mrt_temporal_step(mrt_ctx* c) {
     a.width = c->args.width; a.height = c->args.height; a.n_spheres = c->n_spheres;
     temporal_camera(c->temporal_prev_cam, a.M, a.o_prev);
     a.max_history = (float)c->temporal.max_history; a.depth_tol = c->temporal.depth_tol;
-    int e = mrt::launch_temporal_reproject(a, c->stream);
-    if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+    int e;
+    if (resp.enabled) {                 // the same step with the fast history, then the clamp in place on its output
+        const mrt::TemporalFastArgs f{c->d_den[7 + cur], c->d_den[7 + (cur ^ 1)], (float)resp.fast_history};
+        e = mrt::launch_temporal_reproject_fast(a, f, c->stream);
+        if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+        const mrt::TemporalClampArgs k{a.h0_out, a.h1_out, f.h2_out, a.width, a.height, f.fast_history, resp.clamp_sigma, resp.antilag};
+        e = mrt::launch_temporal_clamp(k, c->stream);
+        if (e) return fail(c, MRT_ERR_HIP, "temporal clamp launch failed: %s", hipGetErrorString((hipError_t)e));
+    } else {
+        e = mrt::launch_temporal_reproject(a, c->stream);
+        if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
     // "previous" from here on: the state at this step
     e = mrt::launch_temporal_snapshot(c->d_shade, c->d_prev_xyzr, c->n_spheres, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "temporal snapshot launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -333,16 +387,12 @@ int mrt_read_temporal(mrt_ctx* c, float* out, size_t cap) {
 int mrt_debug_read_temporal(mrt_ctx* c, float* h0, float* h1, float* prev_xyzr, size_t cap) {
     if (!c) return MRT_ERR_INVALID_ARG;
     MRT_TRY(temporal_check(c, "mrt_debug_read_temporal", false));
-    if (!c->d_den[6]) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal: no history buffers yet (mrt_temporal_step)");
+    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal: no history buffers yet (mrt_temporal_step)");
     const size_t n = (size_t)c->args.width * c->args.height;
     if (cap < n || (prev_xyzr && cap < c->n_spheres)) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_temporal: need %zu pixels, %u spheres", n, c->n_spheres);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t cur = c->temporal_cur;
-    if (c->temporal_clear) {            // (a dropped history reads as what the next step will see)
-        HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
-        c->temporal_prev_cam = c->cam_raw;
-        c->temporal_clear = false;
-    }
+    if (c->temporal_clear) MRT_TRY(clear_history(c));       // (a dropped history reads as what the next step will see)
     if (h0) HIP_TRY(c, hipMemcpyAsync(h0, c->d_den[3 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
     if (h1) HIP_TRY(c, hipMemcpyAsync(h1, c->d_den[4 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
     if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(prev_xyzr, c->d_prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyDeviceToHost, c->stream));
@@ -353,12 +403,13 @@ int mrt_debug_load_temporal(mrt_ctx* c, const float* h0, const float* h1, const 
                             const mrt_camera_raw* prev_cam) {
     if (!c) return MRT_ERR_INVALID_ARG;
     MRT_TRY(temporal_check(c, "mrt_debug_load_temporal", false));
-    if (!c->d_den[6]) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal: no history buffers yet (mrt_temporal_step)");
+    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal: no history buffers yet (mrt_temporal_step)");
     if (prev_xyzr && n_spheres != c->n_spheres) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_load_temporal: %zu spheres for a scene of %u", n_spheres, c->n_spheres);
     const size_t n = (size_t)c->args.width * c->args.height;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t cur = c->temporal_cur;
     if (c->temporal_clear && !h0) HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
+    if (c->temporal_clear && c->temporal_response.enabled) HIP_TRY(c, hipMemsetAsync(c->d_den[7 + cur], 0, n * 16, c->stream));
     if (c->temporal_clear && !prev_cam) c->temporal_prev_cam = c->cam_raw;
     c->temporal_clear = false;
     if (h0) HIP_TRY(c, hipMemcpyAsync(c->d_den[3 + 2 * cur], h0, n * 16, hipMemcpyHostToDevice, c->stream));
@@ -366,6 +417,33 @@ int mrt_debug_load_temporal(mrt_ctx* c, const float* h0, const float* h1, const 
     if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(c->d_prev_xyzr, prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyHostToDevice, c->stream));
     MRT_TRY(mrt::wait_stream(c, c->stream, __func__));      // (the caller's arrays are pageable: theirs again on return)
     if (prev_cam) c->temporal_prev_cam = *prev_cam;
+    c->temporal_stepped = true;
+    return MRT_OK;
+}
+
+int mrt_debug_read_temporal_fast(mrt_ctx* c, float* h2, size_t cap) {
+    if (!c || !h2) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_debug_read_temporal_fast", false));
+    if (!c->temporal_response.enabled) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal_fast: the response is off (mrt_set_temporal_response)");
+    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal_fast: no history buffers yet (mrt_temporal_step)");
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_temporal_fast: need %zu pixels", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->temporal_clear) MRT_TRY(clear_history(c));
+    HIP_TRY(c, hipMemcpyAsync(h2, c->d_den[7 + c->temporal_cur], n * 16, hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+int mrt_debug_load_temporal_fast(mrt_ctx* c, const float* h2) {
+    if (!c || !h2) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(temporal_check(c, "mrt_debug_load_temporal_fast", false));
+    if (!c->temporal_response.enabled) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal_fast: the response is off (mrt_set_temporal_response)");
+    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal_fast: no history buffers yet (mrt_temporal_step)");
+    const size_t n = (size_t)c->args.width * c->args.height;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->temporal_clear) MRT_TRY(clear_history(c));
+    HIP_TRY(c, hipMemcpyAsync(c->d_den[7 + c->temporal_cur], h2, n * 16, hipMemcpyHostToDevice, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));      // (the caller's array is pageable: theirs again on return)
     c->temporal_stepped = true;
     return MRT_OK;
 }

@@ -221,9 +221,9 @@ struct mrt_ctx {
     size_t guide_cand_words = 0;
     uint32_t* d_guide_queue = nullptr;              // the DBG launch's tile queue counter
     float* d_guides = nullptr;                      // 2 float4 per pixel
-    // ping, pong, the denoised frame; with temporal reprojection on also the history, H0 and H1 of pair 0 and of pair 1: a float4
-    // per pixel each
-    float* d_den[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // ping, pong, the denoised frame; with temporal reprojection on also the history, H0 and H1 of pair 0 and of pair 1, and with
+    // its response on as well H2 of pair 0 and of pair 1: a float4 per pixel each
+    float* d_den[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
     // temporal reprojection (mrt_set_temporal / mrt_temporal_step / mrt_read_temporal, denoise.cpp; temporal.hip): the history
     // the next step reads is pair temporal_cur (d_den[3 + 2 cur] = H0, d_den[4 + 2 cur] = H1), the step writes the other pair and
@@ -236,6 +236,9 @@ struct mrt_ctx {
     bool temporal_clear = true, temporal_stepped = false;
     float* d_prev_xyzr = nullptr;
     mrt_camera_raw temporal_prev_cam{};
+    // the response (mrt_set_temporal_response): the fast history H2 of pair p is d_den[7 + p]; zeroed with H0 where the history
+    // was dropped
+    mrt_temporal_response temporal_response = mrt::temporal_response_defaults();
 
     // adaptive sampling (mrt_render_tiles / mrt_render_adaptive, frames.cpp / noise.cpp; adaptive.hip): every tile's frame count n_t.  Until the
     // first subset frame every n_t is frames_done and nothing differs from a uniform accumulation.  From it on (tiles_diverged,

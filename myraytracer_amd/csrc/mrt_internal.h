@@ -348,10 +348,34 @@ struct TemporalArgs {
 };
 int launch_temporal_reproject(const TemporalArgs& a, void* stream);
 int launch_temporal_snapshot(const float* shade, float* prev_xyzr, uint32_t n_spheres, void* stream);
+// The response ("temporal reprojection", steps 4b and 4c): a third history texel H2 = (fr, fg, fb, valid), in -> out with the
+// other two pairs.  launch_temporal_reproject_fast: the same step with the fast colour carried along (h2_in / h2_out;
+// fast_history as a float); launch_temporal_clamp, queued behind it: h0 the step's output, clamped IN PLACE (every thread reads
+// and writes its own texel of h0 alone), h1 / h2 the step's outputs, read only.
+struct TemporalFastArgs {
+    const float* h2_in;
+    float* h2_out;
+    float fast_history;
+};
+struct TemporalClampArgs {
+    float* h0;
+    const float* h1;
+    const float* h2;
+    uint32_t width, height;
+    float fast_history, clamp_sigma, antilag;
+};
+int launch_temporal_reproject_fast(const TemporalArgs& a, const TemporalFastArgs& f, void* stream);
+int launch_temporal_clamp(const TemporalClampArgs& a, void* stream);
 inline mrt_temporal_params temporal_defaults() {
     mrt_temporal_params p{};
     p.size = sizeof(mrt_temporal_params);
     p.max_history = 32; p.spatial_len = 4; p.depth_tol = 0.05f;
+    return p;
+}
+inline mrt_temporal_response temporal_response_defaults() {
+    mrt_temporal_response p{};
+    p.size = sizeof(mrt_temporal_response);
+    p.enabled = 0; p.fast_history = 4; p.clamp_sigma = 2.0f; p.antilag = 1.0f;      // the grid: profiles/temporal_response_quality.txt
     return p;
 }
 

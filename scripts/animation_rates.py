@@ -17,7 +17,11 @@
    mrt_update_spheres at max_framebuffer_weight 0, one frame a step, two ways in one process -- the frame and a present of the
    framebuffer; the frame, mrt_temporal_step and a present of the temporal image -- with the steps per second and the time between
    HIP events on the context's stream around the step (guide rebuild + reprojection + snapshot) and around the temporal present
-   (variance + a-trous iterations + encode)."""
+   (variance + a-trous iterations + encode).
+   --response (with or without --temporal) prints that section with a third way, the temporal response on (mrt_set_temporal_response,
+   DESIGN.md 7h: the reprojection with the fast history, then the clamp), and the ways alternate over `--rounds` rounds in the one
+   process: the response's cost is its step's device time against the response-off step's of the same round, and the difference
+   between the rounds is the spread to read it against."""
 import argparse
 import os
 import sys
@@ -36,6 +40,8 @@ ap.add_argument("--walk", type=float, default=0.0005)
 ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--regroup-every", type=int, default=0)
 ap.add_argument("--temporal", action="store_true")
+ap.add_argument("--response", action="store_true")
+ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 W, H = a.size
 
@@ -182,52 +188,68 @@ def static_cost(name, spheres, cam):
               f"{r[2] / b[2]:.4f} x the member tests", flush=True)
 
 
-def temporal_cost(name, spheres, cam, path):
-    rates = {}
-    for temporal in (False, True):
-        stream = torch.cuda.Stream()
-        with M.State(M.Args(W, H, 1, a.depth, 0.0), seed=1, stream=stream.cuda_stream) as st:
-            st.set_world(spheres)
-            st.set_camera(cam)
-            st.set_temporal(temporal)
-            st.set_present_ring(4)
-            for _ in range(8):                      # (the schedule's trials, the first step's allocations and the ring)
-                st.redraw()
-                if temporal:
-                    st.temporal_step()
-                st.present("rgba8", temporal=temporal)
-            st.sync()
-            steps, presents = [], []
-            t0 = time.perf_counter()
-            for xyzr in path:
-                st.update_spheres(0, xyzr)
-                st.redraw()
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-                ev[0].record(stream)
-                if temporal:
-                    st.temporal_step()
-                ev[1].record(stream)
-                ev[2].record(stream)
-                st.present("rgba8", temporal=temporal)
-                ev[3].record(stream)
-                steps.append(ev[:2])
-                presents.append(ev[2:])
-            st.sync()
-            sec = time.perf_counter() - t0
-        rates[temporal] = len(path) / sec
-        step_ms = np.array([e0.elapsed_time(e1) for e0, e1 in steps])
-        pres_ms = np.array([e0.elapsed_time(e1) for e0, e1 in presents])
-        print(f"  {name} {'frame + step + temporal present' if temporal else 'frame + present               '} {rates[temporal]:8.1f} steps/s"
-              + (f"  mrt_temporal_step on the device (events): median {np.median(step_ms):.4f} ms, max {step_ms.max():.4f};" if temporal else "")
-              + f"  present (kernels + copy, events): median {np.median(pres_ms):.4f} ms, max {pres_ms.max():.4f}", flush=True)
-    print(f"  {name}: with the temporal step and present / without = {rates[True] / rates[False]:.3f} x the steps per second", flush=True)
+def temporal_cost(name, spheres, cam, path, response=False, rounds=1):
+    ways = (False, True, "response") if response else (False, True)
+    label = {False: "frame + present               ", True: "frame + step + temporal present", "response": "the same with the response on  "}
+    step_med = {w: [] for w in ways}
+    for rnd in range(rounds):
+        rates = {}
+        for way in ways:
+            temporal = way is not False
+            stream = torch.cuda.Stream()
+            with M.State(M.Args(W, H, 1, a.depth, 0.0), seed=1, stream=stream.cuda_stream) as st:
+                st.set_world(spheres)
+                st.set_camera(cam)
+                st.set_temporal(temporal)
+                if way == "response":
+                    st.set_temporal_response(True)
+                st.set_present_ring(4)
+                for _ in range(8):                      # (the schedule's trials, the first step's allocations and the ring)
+                    st.redraw()
+                    if temporal:
+                        st.temporal_step()
+                    st.present("rgba8", temporal=temporal)
+                st.sync()
+                steps, presents = [], []
+                t0 = time.perf_counter()
+                for xyzr in path:
+                    st.update_spheres(0, xyzr)
+                    st.redraw()
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+                    ev[0].record(stream)
+                    if temporal:
+                        st.temporal_step()
+                    ev[1].record(stream)
+                    ev[2].record(stream)
+                    st.present("rgba8", temporal=temporal)
+                    ev[3].record(stream)
+                    steps.append(ev[:2])
+                    presents.append(ev[2:])
+                st.sync()
+                sec = time.perf_counter() - t0
+            rates[way] = len(path) / sec
+            step_ms = np.array([e0.elapsed_time(e1) for e0, e1 in steps])
+            pres_ms = np.array([e0.elapsed_time(e1) for e0, e1 in presents])
+            step_med[way].append(float(np.median(step_ms)))
+            q1, q3 = np.percentile(step_ms, [25, 75])
+            print(f"  {name} {label[way]} {rates[way]:8.1f} steps/s"
+                  + (f"  mrt_temporal_step on the device (events): median {np.median(step_ms):.4f} ms, quartiles {q1:.4f} .. {q3:.4f}, max {step_ms.max():.4f};" if temporal else "")
+                  + f"  present (kernels + copy, events): median {np.median(pres_ms):.4f} ms, max {pres_ms.max():.4f}"
+                  + (f"  (round {rnd + 1})" if rounds > 1 else ""), flush=True)
+        print(f"  {name}: with the temporal step and present / without = {rates[True] / rates[False]:.3f} x the steps per second"
+              + (f"; with the response on {rates['response'] / rates[False]:.3f} x" if response else ""), flush=True)
+    if response:
+        on, off = np.array(step_med["response"]), np.array(step_med[True])
+        print(f"  {name}: the response's cost, step on - step off by round: " + ", ".join(f"{d:+.4f} ms" for d in on - off)
+              + f" ({', '.join(f'{r:.3f}' for r in on / off)} x the step); the step's median between the rounds: off "
+              + " / ".join(f"{v:.4f}" for v in off) + ", on " + " / ".join(f"{v:.4f}" for v in on), flush=True)
 
 
-if a.temporal:
-    print(f"temporal: {W}x{H} x 1 spp, depth {a.depth}, max_framebuffer_weight 0; {a.steps} steps of a random walk ({a.walk} x the scene's size a "
+if a.temporal or a.response:
+    print(f"temporal{' + response' if a.response else ''}: {W}x{H} x 1 spp, depth {a.depth}, max_framebuffer_weight 0; {a.steps} steps of a random walk ({a.walk} x the scene's size a "
           f"step), one frame a step; build {M._lib.load().mrt_build_id().decode()}", flush=True)
     for name, (spheres, cam) in (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100))):
-        temporal_cost(name, spheres, cam, walk(spheres, a.steps, np.random.default_rng(1)))
+        temporal_cost(name, spheres, cam, walk(spheres, a.steps, np.random.default_rng(1)), a.response, a.rounds if a.response else 1)
     sys.exit(0)
 
 if a.regroup_every:
