@@ -230,6 +230,15 @@ int mrt_debug_read_hierarchy(mrt_ctx* ctx, uint32_t info[16], double scalars[8],
 int mrt_debug_regroup_info(mrt_ctx* ctx, uint32_t out[4]);
 int mrt_debug_set_regroup_block(mrt_ctx* ctx, uint32_t clusters);
 int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, uint32_t* n_pool);
+/* Camera-ray cluster masks (small scenes of at most 128 top records): mrt_debug_set_camera_masks switches them
+ * off / on for the launches that follow (an A/B switch: images and the counters samples / world_hit_calls / rng_draws do not
+ * depend on it, member_tests do).  mrt_debug_read_camera_masks: info[4] = {entries the table holds for the current shard (0: the
+ * masks do not apply -- a large scene, more than 128 top records, a shard that outgrew the table), words per entry (4), whether the
+ * most recent render launch ran with them, whether the table is built for the current scene / camera / shard}; with `out` (cap_words
+ * >= entries x 4) the table itself, entry e = texels 8 e .. 8 e + 7 of the shard's row-major order, top record 32 w + i at bit
+ * 31 - i of word w.  MRT_ERR_NO_SCENE without a scene, MRT_ERR_TOO_SMALL for a short buffer. */
+int mrt_debug_set_camera_masks(mrt_ctx* ctx, int on);
+int mrt_debug_read_camera_masks(mrt_ctx* ctx, uint32_t info[4], uint32_t* out, size_t cap_words);
 /* Diagnostics of temporal reprojection: the context's OWN history (the pair the next step reads: h0 = (r, g, b, len), h1 = (m1,
  * m2, t, index bits), 4 floats a pixel each, y * width + x), its previous spheres (4 floats each) and, for the load, its previous
  * derived camera, read / overwritten behind the ctx's stream, so that a test can start a step from a synthetic history.  They

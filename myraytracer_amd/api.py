@@ -314,6 +314,22 @@ class State:
         self._check(self._L.mrt_debug_regroup_info(self._ctx, out), "mrt_debug_regroup_info")
         return dict(n_pool=int(out[0]), block=int(out[1]), global_depths=int(out[2]), lds_depths=int(out[3]))
 
+    def debug_set_camera_masks(self, on: bool):
+        """the camera-ray cluster masks off / on for the launches that follow (mrt_debug_set_camera_masks); images do not change"""
+        self._check(self._L.mrt_debug_set_camera_masks(self._ctx, 1 if on else 0), "mrt_debug_set_camera_masks")
+
+    def debug_read_camera_masks(self, table: bool = True) -> dict:
+        """entries, words per entry, whether the last launch ran with the masks and whether the table is built for the current
+        scene / camera / shard; with `table` the (entries, 4) uint32 array itself (mrt_debug_read_camera_masks)"""
+        info = (C.c_uint32 * 4)()
+        self._check(self._L.mrt_debug_read_camera_masks(self._ctx, info, None, 0), "mrt_debug_read_camera_masks")
+        out = dict(entries=int(info[0]), words=int(info[1]), in_force=bool(info[2]), built=bool(info[3]), masks=None)
+        if table and out["entries"]:
+            m = np.zeros((out["entries"], 4), np.uint32)
+            self._check(self._L.mrt_debug_read_camera_masks(self._ctx, info, m.ctypes.data, m.size), "mrt_debug_read_camera_masks")
+            out["masks"] = m
+        return out
+
     def debug_set_regroup_block(self, clusters: int):
         self._check(self._L.mrt_debug_set_regroup_block(self._ctx, clusters), "mrt_debug_set_regroup_block")
 

@@ -111,7 +111,11 @@ void set_global_error(const char* msg) { g_err = msg ? msg : ""; }
 
 void free_world(mrt_ctx* c) {
     free_device(c->d_spheres, c->d_clusters, c->d_nodes, c->d_boxes, c->d_boxes_open, c->d_shade, c->d_top_mfma, c->d_member_index,
-                c->d_regroup, c->d_prev_xyzr, c->d_vec4, c->d_f32, c->d_i32);
+                c->d_regroup, c->d_prev_xyzr, c->d_vec4, c->d_f32, c->d_i32, c->d_cam_masks);
+    c->cam_mask_entries = 0;
+    c->cam_mask_built = 0;
+    c->cam_masks_in_force = false;
+    c->cam_mask_gen++;
     c->have_world = false;
     c->guides_stale = true;
     drop_temporal_history(c);           // (the sphere indices it holds belong to the scene that goes)
@@ -188,6 +192,7 @@ int alloc_frame_buffers(mrt_ctx* c, uint32_t rank, uint32_t world) {
     free_frame_buffers(c);
     c->shard_rank = rank; c->shard_world = world;
     c->local_bands = local_bands;
+    c->cam_mask_gen++;                  // (the camera masks are per texel of the shard)
     c->d_seeds = B.seeds; c->d_fb[0] = B.fb[0]; c->d_fb[1] = B.fb[1];
     c->tiles_x = (c->args.width + mrt::kTileW - 1) / mrt::kTileW;
     c->n_tiles = c->tiles_x * c->local_bands;
@@ -556,6 +561,7 @@ int mrt_set_camera(mrt_ctx* c, const mrt_camera* cam) {
         if (raw.mode != 0 && !(std::fabs(raw.origin[k]) <= 1.0e7f && std::fabs(raw.ru[k]) <= 1.0e7f && std::fabs(raw.rv[k]) <= 1.0e7f))
             return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_camera: |lookfrom| or the lens radius exceeds 1e7");
     c->cam_raw = raw;
+    c->cam_mask_gen++;
     c->guides_stale = true;
     for (auto& S : c->slot) S.cost_valid = false;
     c->width.div = 0;                   // (the launch-width controller starts over with the new workload)
@@ -821,7 +827,12 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
         if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_regroup || !c->d_prev_xyzr || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
             return check_finding(why, cap, "have_world without one of the scene's arrays");
         if (!mrt::scene_is_small(c->n_members) && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
+        if (mrt::scene_is_small(c->n_members) && c->n_padded <= mrt::kCamMaskRecords && (!c->d_cam_masks || c->cam_mask_entries == 0))
+            return check_finding(why, cap, "a small scene of %u top records without its camera masks", c->n_padded);
     }
+    if ((c->d_cam_masks == nullptr) != (c->cam_mask_entries == 0)) return check_finding(why, cap, "camera masks %p of %zu entries", (void*)c->d_cam_masks, c->cam_mask_entries);
+    if (c->cam_mask_built > c->cam_mask_gen || (c->cam_mask_built != 0 && !c->d_cam_masks)) return check_finding(why, cap, "camera masks built for generation %llu of %llu without a table", (unsigned long long)c->cam_mask_built, (unsigned long long)c->cam_mask_gen);
+    if (c->cam_masks_in_force && (!c->d_cam_masks || !c->have_world)) return check_finding(why, cap, "camera masks in force without a table or a scene");
     if (c->noise_on) {
         if (!c->d_noise_s || !c->d_noise_tiles || !c->d_noise_partials) return check_finding(why, cap, "noise tracking is on without S, the tile maps or the scratch");
         if (!c->d_noise_sums || !c->h_noise_sums) return check_finding(why, cap, "noise tracking is on without the ring's sums");

@@ -301,6 +301,51 @@ static void batch_shuffles(const mrt_ctx* c, uint32_t batch, mrt::KParams& p) {
     }
 }
 
+// Camera-ray cluster masks (cam_mask.hip): p.cam_masks for this launch, the table rebuilt first when it is stale and a build
+// pays: always from kCamMaskAlwaysSpp samples per pixel and launch on, otherwise once the generation has survived a frame (a
+// viewer that moves its camera every frame below that never pays a build).  The threshold is the measured build time over the
+// measured saving per sample (profiles/cam_mask_rates.txt: 3.2 ms at 1080p against 5.7 - 6.6 us per sample per pixel; both
+// scale with the pixel count): a lone frame breaks even at about 512 samples per pixel.  The masks apply to a small scene of at
+// most kCamMaskRecords top records whose table holds the shard, and to launches whose `texel` is the pixel's own: the stream
+// mode's queue layers add a layer offset to it and run without masks.
+// The build runs on the frame's own side stream, behind enter_slot (the scene's uploads and refits are visible there) and ahead
+// of the render launch, and every slot builds for itself before its first frame of a generation (they write the same words; a
+// slot of a generation that some slot has built follows at once): a frame reads what its own stream has written, no stream
+// waits for another one's build -- a wait would start the waiting frames as a convoy -- and no frame in flight is held back.
+// Only a build for a NEW generation waits, for the other slots' frames that may still be reading the previous one.  Which
+// launches run with masks depends on the calls alone, never on timing.
+static constexpr uint32_t kCamMaskAlwaysSpp = 512;
+static int camera_masks(mrt_ctx* c, mrt_ctx::FrameSlot& S, mrt::KParams& p) {
+    p.cam_masks = nullptr;
+    c->cam_masks_in_force = false;
+    if (!S.render_pending) { S.cam_used_gen = 0; S.cam_stale_reader = false; }
+    const uint64_t gen = c->cam_mask_gen;
+    const bool survived = c->cam_mask_seen == gen;
+    c->cam_mask_seen = gen;
+    const size_t need = (local_texels(c) + 7) / 8;
+    const bool own_texel = p.queue_layers == 1u || c->locals.rng_mode == MRT_RNG_COUNTER;
+    if (!c->cam_masks_on || !c->d_cam_masks || !mrt::scene_is_small(c->n_members) || c->n_padded > mrt::kCamMaskRecords || need == 0 ||
+        need > c->cam_mask_entries || !own_texel)
+        return MRT_OK;
+    if (S.cam_built != gen) {
+        if (c->cam_mask_built != gen && !survived && (uint64_t)c->locals.samples_per_frame * p.lane_frames < kCamMaskAlwaysSpp) return MRT_OK;
+        for (mrt_ctx::FrameSlot& T : c->slot)
+            if (&T != &S && T.render_pending && (T.cam_stale_reader || (T.cam_used_gen != 0 && T.cam_used_gen != gen)))
+                HIP_TRY(c, hipStreamWaitEvent(S.stream, T.render_done, 0));
+        mrt::KParams b = p;             // (a subset frame's p.n_tiles is its list's length: the masks cover the shard)
+        b.tiles_x = c->tiles_x; b.n_tiles = c->n_tiles;
+        const int e = mrt::launch_cam_masks(b, c->d_cam_masks, (uint32_t)need, S.stream);
+        if (e) return fail(c, MRT_ERR_HIP, "camera mask launch failed: %s", hipGetErrorString((hipError_t)e));
+        S.cam_built = gen;
+        c->cam_mask_built = gen;
+    }
+    if (S.cam_used_gen != 0 && S.cam_used_gen != gen) S.cam_stale_reader = true;      // (an earlier frame of this slot, still pending)
+    S.cam_used_gen = gen;
+    p.cam_masks = c->d_cam_masks;
+    c->cam_masks_in_force = true;
+    return MRT_OK;
+}
+
 // side stream: wait for the scene / seeds uploads and for this slot's previous frame (n-2) to
 // have been finalized (its colour sums and tile costs are about to be overwritten / used)
 static int enter_slot(mrt_ctx* c, mrt_ctx::FrameSlot& S, const mrt::KParams& p) {
@@ -423,6 +468,7 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
     }
     p.pix_acc = S.d_pix_acc;
     MRT_TRY(enter_slot(c, S, p));
+    MRT_TRY(camera_masks(c, S, p));
     // The tile queue is ordered by the per-tile cost this slot measured two frames ago, heaviest
     // first; before the slot's first frame of a scene a small pilot launch (no output) provides
     // the estimate when the frame is long enough to pay for it.  Without an estimate: index order.
@@ -585,6 +631,7 @@ static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t
     batch_shuffles(c, batch, p);
     p.pix_acc = S.d_pix_acc;
     MRT_TRY(enter_slot(c, S, p));
+    MRT_TRY(camera_masks(c, S, p));
     HIP_TRY(c, hipMemcpyAsync(S.d_tile_list, S.h_tile_list, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, S.stream));
     // launch width: the setting in force (the controller's last launch), and round 3's 8 waves per CU for chains of a few bounces
     const uint32_t chain_spp = c->locals.samples_per_frame * batch;

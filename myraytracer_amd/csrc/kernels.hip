@@ -343,6 +343,28 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
         int32_t best = -1;
         if (__any(trace)) {
             const float a = dot3(d, d);                                     // sphere_hit :277 (same for every sphere)
+            // Camera-ray cluster masks (cam_mask.hip): a camera ray -- the only kind whose geometry is known before the frame --
+            // can only touch the clusters set in its texel's entry, so the entry is ANDed onto the sweep's candidate words.
+            // The entry is requested here, where the direct spheres and the operand packing cover its latency, and parked in
+            // the lane's own mask words in LDS right before the sweep (every other ray parks all ones): nothing of it is live
+            // in registers during the sweep.  Wave-uniform on the pointer (null: today's instructions).  Small scenes of at
+            // most kCamMaskRecords records (one block, at most 4 words), never the caller's rays (DBG).
+            constexpr bool CAM = SMALL && !DBG;
+            bool cam_on = false;
+            uint4 cam_entry = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+            if constexpr (CAM) {
+                const KArgPtr C = cold_args();
+                const uint32_t* const cam_masks = C->cam_masks;
+                cam_on = cam_masks != nullptr;
+                if (cam_on && trace && depth_left == C->locals.ray_depth) cam_entry = reinterpret_cast<const uint4*>(cam_masks)[texel >> 3];
+            }
+            // What the lane's parked entry allows of the sweep's word w: read at the top of a tile's tests, under the wave-uniform
+            // branch, so that the LDS round trip runs under the tile's arithmetic; all ones while the masks are off
+            auto cam_allow = [&](const uint32_t w) -> uint32_t {
+                uint32_t allow = 0xFFFFFFFFu;
+                if constexpr (CAM) { if (cam_on) allow = masks[w * 64u]; }
+                return allow;
+            };
             // A ray with a non-finite component makes every discriminant NaN, which the
             // reference treats as "not < 0".  Such lanes take the literal loop below.
             // So does a direction that is not (nearly) unit length -- normalize() of an overflowed or
@@ -414,6 +436,13 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // MFMA variant of the sweep: per-ray operands of the two GEMMs, rays x records (see mfma_sweep_tile)
             MfmaRay mr;
             if (MFMA) mr = mfma_ray_operands(o_rel, ds, o_rel2, P.mfma_scale[1], P.mfma_scale[2], P.mfma_neg_k2_pair);
+            if (CAM && cam_on) {        // (the block's words only: n_padded / 32 of them)
+                masks[0] = cam_entry.x;
+                if (n_padded > 32u) masks[64] = cam_entry.y;
+                if (n_padded > 64u) masks[128] = cam_entry.z;
+                if (n_padded > 96u) masks[192] = cam_entry.w;
+                lds_order();
+            }
             for (uint32_t blk = 0; blk < n_padded; blk += kBlockChunks * kChunk) {
                 const uint32_t blk_end = (blk + kBlockChunks * kChunk < n_padded) ? blk + kBlockChunks * kChunk : n_padded;
                 uint32_t nz = 0;                                        // bit w: records 32 w .. 32 w + 31 of this block hold a candidate
@@ -422,7 +451,9 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     // 32 records per tile = one mask word per lane and ray
                     uint32_t w = 0;
                     for (uint32_t i = blk; i < blk_end; i += 2u * kChunk, w++) {
-                        const uint32_t m = mfma_sweep_tile(reinterpret_cast<const u32x4*>(P.top_mfma)[(size_t)(i / 32u) * 64u + lane], mr);
+                        const uint32_t allow = cam_allow(w);
+                        uint32_t m = mfma_sweep_tile(reinterpret_cast<const u32x4*>(P.top_mfma)[(size_t)(i / 32u) * 64u + lane], mr);
+                        if constexpr (CAM) m &= allow;
                         masks[w * 64u] = m;
                         nz |= (m < 1u ? m : 1u) << w;
                         rem += (uint32_t)__builtin_popcount(m);
@@ -436,13 +467,15 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 for (uint32_t i = blk; i < blk_end; i += kChunk, c++) {
                     // (the record count is a multiple of 32 -- hierarchy.cpp pads the top level to whole matrix-core tiles --
                     // so every chunk is full and chunks come in pairs)
+                    const uint32_t allow = cam_allow(c >> 1);
                     smem_wait_then_load8(ga, gb, sph_quads, i + 8u, bits);  test8(ga, o, ds, bits);
                     const uint32_t nxt = (i + kChunk < n_padded) ? i + kChunk : 0u;   // next chunk, or a harmless reload
                     smem_wait_then_load8(gb, ga, sph_quads, nxt, bits);
                     test8(gb, o, ds, bits);
                     if (c & 1u) {
                         // 32 signs, record i - 16 (the even chunk's first) at bit 31; candidate = S >= 0
-                        const uint32_t m = ~bits;
+                        uint32_t m = ~bits;
+                        if constexpr (CAM) m &= allow;
                         masks[(c >> 1) * 64u] = m;
                         nz |= (m < 1u ? m : 1u) << (c >> 1);
                         rem += (uint32_t)__builtin_popcount(m);

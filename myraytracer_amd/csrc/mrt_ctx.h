@@ -49,6 +49,20 @@ struct mrt_ctx {
     uint32_t* d_regroup = nullptr;
     uint32_t n_pool = 0, n_pooled = 0;
     uint32_t regroup_block = 0, regroup_last[3] = {0, 0, 0};
+    // Camera-ray cluster masks (cam_mask.hip; frames.cpp, camera_masks): a scene buffer (mrt_set_world_raw makes it for a small
+    // scene of at most kCamMaskRecords top records, all ones, sized for the shard as it is then; free_world frees it) of
+    // cam_mask_entries entries of 4 words.  ONE staleness generation, bumped by everything the masks depend on (scene, camera,
+    // geometry updates, regroups, image shape and shard); cam_mask_built: the generation the table holds (0: none yet),
+    // cam_mask_seen: the generation the previous frame was launched under (a generation that survives a frame is worth a
+    // build).  cam_masks_on: mrt_debug_set_camera_masks; cam_masks_in_force: the most recent render launch got the table.
+    uint32_t* d_cam_masks = nullptr;
+    size_t cam_mask_entries = 0;
+    uint64_t cam_mask_gen = 1, cam_mask_built = 0, cam_mask_seen = 0;
+    bool cam_masks_on = true, cam_masks_in_force = false;
+    // The build runs on the side stream of the frame that needs it, and EVERY frame slot builds the table on its own stream before
+    // its first frame of a generation (FrameSlot::cam_built): a slot's frames follow that slot's build in stream order, no stream
+    // ever waits for another one's build, and the frames in flight are not held back.  The builds of one generation write the
+    // same words.  cam_mask_built is the generation some slot has built.
     // large scenes' walk: the axis-aligned boxes of the hierarchy's nodes in the kernel's top-down numbering (KParams::boxes),
     // and the same array with every real box opened wide (a box test that never rejects: mrt_debug_set_boxes(0))
     mrt::BoxRec* d_boxes = nullptr;
@@ -107,6 +121,11 @@ struct mrt_ctx {
         uint64_t stats_seq = 0;
         bool stats_pending = false;
         bool render_pending = false;           // a render kernel of this slot has been launched and not yet been seen complete
+        // camera masks: the generation this slot's stream has built the table for; the generation the slot's most recent frame
+        // reads it under (0: none), and whether an earlier frame of the slot that may still run reads an older one -- a build
+        // for a new generation on another slot's stream waits for such frames first
+        uint64_t cam_built = 0, cam_used_gen = 0;
+        bool cam_stale_reader = false;
         uint64_t render_seq = 0;               // its frame (diagnostics of a stalled wait)
         // adaptive sampling: a subset frame's tile list, written by the host into pinned memory and copied on the slot's stream
         // before the render (the host rewrites it only after the slot's previous render kernel has completed)

@@ -22,6 +22,7 @@ constexpr uint32_t kMaxFrameBatch = 32;   // frames one render launch may cover 
 constexpr uint32_t kQueueCap = 320;      // a work queue of the walk: < 64 left over + 4 x 64 pushed by one round
 constexpr uint32_t kStackReserve = 16;   // large scenes' work stack: entries beyond its capacity a one-item round may use (3 per level)
 constexpr uint32_t kMaxDirect = 4;       // very large spheres tested by every ray directly, outside the hierarchy
+constexpr uint32_t kCamMaskRecords = 128; // camera-ray cluster masks (cam_mask.hip): one 128-bit entry covers at most this many top records
 // SMALL scenes (render_kernel's SC == 0): every node id of the hierarchy's n_members member slots fits 10 bits, so the hierarchy
 // has one level, the member records live in LDS and the walk's work items are u16; larger scenes walk the boxes
 inline bool scene_is_small(uint32_t n_members) { return n_members <= 1024u; }
@@ -136,6 +137,10 @@ struct KParams {
     int32_t* dbg_hit;
     uint32_t* dbg_cand;
     uint32_t dbg_words;         // bitmap words per ray
+    // Camera-ray cluster masks (cam_mask.hip; small scenes of at most kCamMaskRecords top records): 4 words per 8 consecutive texels
+    // of the shard, entry texel >> 3, in the sweep's bit layout; the sweep ANDs them onto the candidate words of camera rays.
+    // Null = off (today's instructions).  LAST, so that no other argument's offset moves.
+    const uint32_t* cam_masks;
 };
 
 // api.cpp: message behind mrt_last_error(NULL), for failures of entry points that have no context
@@ -258,6 +263,9 @@ struct RefitArgs {
     float box_kc;
     float origin[3];
 };
+// cam_mask.hip: the camera-ray cluster masks of p's scene (level 0 of p.nodes), camera, image shape and shard into `masks`,
+// `entries` entries of 4 words (entry e: texels 8 e .. 8 e + 7 of the shard's row-major order)
+int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t entries, void* stream);
 int launch_refit_scatter(const RefitScatterArgs& a, void* stream);
 int launch_refit(const RefitArgs& a, void* stream);
 

@@ -189,6 +189,14 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         c->mfma_scene_ok = n_real >= 24 && med_r2 > 0.0 && kMfmaSlack * 2.0 * max_c2 <= 0.1 * med_r2;
     }
     MRT_TRY(upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
+    if (mrt::scene_is_small(hier.n_members) && n_padded <= mrt::kCamMaskRecords) {
+        // the camera-ray cluster masks (cam_mask.hip; frames.cpp builds them before a frame when it pays): an entry of 4 words per
+        // 8 texels of the shard as it is now, all ones until built.  A shard that outgrows it renders without masks.
+        const size_t entries = std::max<size_t>((mrt::local_texels(c) + 7) / 8, 1);
+        const std::vector<uint32_t> ones(4 * entries, 0xFFFFFFFFu);
+        MRT_TRY(upload((void**)&c->d_cam_masks, ones.data(), ones.size() * sizeof(uint32_t)));
+        c->cam_mask_entries = entries;
+    }
     {
         // The regroup scratch (mrt_regroup_spheres; mrt_internal.h, regroup_layout): what a regroup reads of the build -- the pool's
         // sphere indices ascending, the cluster of every rank, pref -- and the room it works in: 16 bytes a pooled sphere for the
@@ -316,6 +324,7 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
     }
     c->inputs_dirty = true;
     c->guides_stale = true;
+    c->cam_mask_gen++;
     const bool boxed = !mrt::scene_is_small(c->n_members);
     double reach = c->mfma_reach;
     float kc = c->box_kc;
@@ -376,6 +385,7 @@ int mrt_regroup_spheres(mrt_ctx* c) {
         if (e != hipSuccess) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: hipStreamWaitEvent failed: %s", hipGetErrorString(e)));
     }
     c->inputs_dirty = true;                             // (the guides stay current: the geometry did not change)
+    c->cam_mask_gen++;                                  // (the camera masks are per cluster slot)
     mrt::RegroupArgs g;
     g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
     g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
@@ -457,6 +467,29 @@ int mrt_debug_set_sweep_axes(mrt_ctx* c, const float* axis) {
             if (axis[k] != 1.0f && axis[k] != 2.0f && axis[k] != 4.0f) return MRT_ERR_INVALID_ARG;
     c->have_force_axis = axis != nullptr;
     for (int k = 0; k < 3; k++) c->force_axis[k] = axis ? axis[k] : 1.0f;
+    return MRT_OK;
+}
+
+int mrt_debug_set_camera_masks(mrt_ctx* c, int on) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    c->cam_masks_on = on != 0;
+    return MRT_OK;
+}
+
+int mrt_debug_read_camera_masks(mrt_ctx* c, uint32_t info[4], uint32_t* out, size_t cap_words) {
+    if (!c || !info) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_read_camera_masks: no scene");
+    const size_t need = (mrt::local_texels(c) + 7) / 8;
+    const bool fits = c->d_cam_masks && need != 0 && need <= c->cam_mask_entries;
+    info[0] = fits ? (uint32_t)need : 0u;
+    info[1] = 4u;
+    info[2] = c->cam_masks_in_force ? 1u : 0u;
+    info[3] = fits && c->cam_mask_built == c->cam_mask_gen ? 1u : 0u;
+    if (!out || !fits) return MRT_OK;
+    if (cap_words < 4 * need) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_camera_masks: need %zu words", 4 * need);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, "mrt_debug_read_camera_masks"));             // (the build runs on a frame's side stream)
+    HIP_TRY(c, hipMemcpy(out, c->d_cam_masks, 4 * need * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MRT_OK;
 }
 
