@@ -8,7 +8,7 @@
 // The bundle of one texel: a ray runs from O + off, |off| <= rho in the lens plane, through O + p, with p in the texel's patch
 // around pc, |p - pc| <= h; at the affine parameter s >= 0 its point O + off + s (p - off) lies within |1 - s| rho + s h of the
 // axis point O + s pc.  Every member sphere is tested against that widening axis in double, its radius inflated for the
-// reference's own rounding (hierarchy.cpp, build_boxes: the line of a ray whose computed discriminant is >= 0 passes within
+// reference's own rounding (bounds.h, box_kpad: the line of a ray whose computed discriminant is >= 0 passes within
 // sqrt(r^2 + 14 eps |oc|^2 / a) of the centre; twice that here) and rho, h and the positions widened by 1e-5 relative.
 // The kernel reads the device's own member records (level 0 of `nodes`, members 4 m .. 4 m + 3 of cluster m), so it is right after
 // mrt_update_spheres and mrt_regroup_spheres; it creates nothing and runs in stream order.

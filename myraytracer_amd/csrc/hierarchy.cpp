@@ -20,15 +20,14 @@ namespace {
 // centres, at a multiple of kClusterK near the median) down to groups of <= 8, and such a group is cut
 // into 4 + rest by trying every choice.  Spheres far larger than the median (a ground sphere) stay alone;
 // factor == 0 (diagnostic) gives every sphere a cluster of its own.  Consecutive clusters are kd siblings, which is what
-// the upper levels (build_hierarchy) group.  R is 1.5 % above the enclosing radius measured from the
-// f32-rounded centre: part of the conservativeness argument in DESIGN.md §4.  Clusters are padded to
+// the upper levels (build_hierarchy) group.  The bounds are bounds.h's (Span, bound_record).  Clusters are padded to
 // kClusterK members and the list to a multiple of kGroup with never-hit records (-r^2 = +inf gives a
 // discriminant of -inf).
 void build_clusters(const float* centers4, const float* radii, uint32_t n, float factor,
                     std::vector<mrt::SphereRec>& clusters, std::vector<mrt::SphereRec>& members,
                     std::vector<uint32_t>& member_index, std::vector<uint32_t>& direct, uint32_t* n_pool) {
     clusters.clear(); members.clear(); member_index.clear(); direct.clear();
-    const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
+    const mrt::SphereRec never = never_hit_record();
     std::vector<double> rs(n);
     for (uint32_t i = 0; i < n; i++) rs[i] = std::fabs((double)radii[i]);
     double big = 1e300;
@@ -37,22 +36,13 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
         std::nth_element(sorted.begin(), sorted.begin() + n / 2, sorted.end());
         big = 8.0 * sorted[n / 2];
     }
-    // enclosing sphere of a set: centre of the members' common bounding box, R = max(|c_m - centre| + r_m)
-    auto enclose = [&](const uint32_t* idx, uint32_t cnt, double ctr[3]) -> double {
-        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-        for (uint32_t m = 0; m < cnt; m++)
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::min(lo[k], (double)centers4[4 * idx[m] + k] - rs[idx[m]]);
-                hi[k] = std::max(hi[k], (double)centers4[4 * idx[m] + k] + rs[idx[m]]);
-            }
-        // the record stores the centre as f32: measure R from the ROUNDED centre so that it stays an enclosure
-        for (int k = 0; k < 3; k++) ctr[k] = (double)(float)(0.5 * (lo[k] + hi[k]));
+    // enclosing sphere of a set (bounds.h, Span): R, and the f32-rounded centre it is measured from
+    auto enclose = [&](const uint32_t* idx, uint32_t cnt, float ctr[3]) -> double {
+        Span s;
+        for (uint32_t m = 0; m < cnt; m++) s.add(centers4 + 4 * idx[m], rs[idx[m]]);
+        s.centre(ctr);
         double R = 0;
-        for (uint32_t m = 0; m < cnt; m++) {
-            double d2 = 0;
-            for (int k = 0; k < 3; k++) { const double d = (double)centers4[4 * idx[m] + k] - ctr[k]; d2 += d * d; }
-            R = std::max(R, std::sqrt(d2) + rs[idx[m]]);
-        }
+        for (uint32_t m = 0; m < cnt; m++) R = std::max(R, reach_from(ctr, centers4 + 4 * idx[m], rs[idx[m]]));
         return R;
     };
     std::vector<std::vector<uint32_t>> groups;
@@ -95,7 +85,7 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
             if (!(mask & 1u) || __builtin_popcount(mask) != (int)mrt::kClusterK) continue;
             uint32_t A[8], B[8], na = 0, nb = 0;
             for (uint32_t q = 0; q < m; q++) ((mask >> q) & 1u ? A[na++] : B[nb++]) = pool[lo + q];
-            double ctr[3];
+            float ctr[3];
             const double ra = enclose(A, na, ctr), rb = enclose(B, nb, ctr);
             if (ra * ra + rb * rb < best) { best = ra * ra + rb * rb; bestmask = mask; }
         }
@@ -111,7 +101,7 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
         const size_t ng = groups.size();
         std::vector<double> gr(ng);
         std::vector<std::array<double, 3>> gc(ng);
-        auto refresh = [&](size_t g) { double c3[3]; gr[g] = enclose(groups[g].data(), (uint32_t)groups[g].size(), c3); gc[g] = {c3[0], c3[1], c3[2]}; };
+        auto refresh = [&](size_t g) { float c3[3]; gr[g] = enclose(groups[g].data(), (uint32_t)groups[g].size(), c3); gc[g] = {c3[0], c3[1], c3[2]}; };
         for (size_t g = 0; g < ng; g++) refresh(g);
         const size_t window = ng <= 4096 ? ng : 32;
         for (int pass = 0; pass < (ng <= 4096 ? 4 : 2); pass++) {
@@ -125,7 +115,7 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
                     double best = base - 1e-12 * base;
                     std::vector<uint32_t> bestA, bestB;
                     std::vector<uint32_t> A, B;
-                    double c3[3];
+                    float c3[3];
                     auto consider = [&]() {
                         const double ra = enclose(A.data(), (uint32_t)A.size(), c3), rb = enclose(B.data(), (uint32_t)B.size(), c3);
                         if (ra * ra + rb * rb < best) { best = ra * ra + rb * rb; bestA = A; bestB = B; }
@@ -168,10 +158,9 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
     }
     for (auto& g : groups) {
         std::sort(g.begin(), g.end());
-        double ctr[3];
+        float ctr[3];
         const double R = enclose(g.data(), (uint32_t)g.size(), ctr);
-        const float Rf = (float)(R * mrt::kBoundInflate) + 1e-30f;     // rounding R to f32 moves it by 6e-8 R, the 1.5 % is for the proof
-        clusters.push_back(mrt::SphereRec{(float)ctr[0], (float)ctr[1], (float)ctr[2], -(Rf * Rf)});
+        clusters.push_back(bound_record(ctr, R));
         for (uint32_t m = 0; m < mrt::kClusterK; m++) {
             if (m < g.size()) {
                 const float r = radii[g[m]];
@@ -189,117 +178,68 @@ void build_clusters(const float* centers4, const float* radii, uint32_t n, float
     }
 }
 
-// The boxes of every node (levels 1 .. top), for the walk of large scenes (sweep.h, box_may_touch).  Node j of level k
-// covers the members [j 4^k, (j+1) 4^k) of the hierarchy part of level 0.  The test is "the LINE of the ray passes the box
-// grown by K on every side", three separating axes d x e_i; it must hold whenever the reference's discriminant of a member
-// under the node is computed >= 0, i.e. whenever the line passes within h of the member's centre,
-// h^2 <= r^2 + E, E = 14 eps |oc|^2 / a: h - r <= E / (2 r) (the quadratic form) and <= sqrt(E) (the linear form).  With
-// |oc| <= |p| + |e| (p: origin - box centre, e: half extents) and |d_j| + |d_k| <= 1.4143:
-//     quadratic   K = kc |p|^2 + kpad,  kc = 1.3e-6 / r_min,  kpad = kc |e|^2 + 4.4e-14 / kc
-//     linear      K = kc |p|_1 + kpad,  kc = 1.5e-3,          kpad = kc |e|_1
-// (each with >= 9 % to spare over 1.4143 x the bound; the 4.4e-14 / kc makes the quadratic form cover the test's own
-// rounding, 4 eps |p|_1, by the inequality of the means).  The quadratic form is far smaller at moderate distances, the
-// linear one at large distances from tiny spheres; the scene takes the one that is smaller at its own reach.
-// kc is ONE value per scene (round 5; r_min = the scene's smallest radius, which only makes K larger for the other boxes): the
-// kernel takes it from its arguments, and kpad -- the only other per-box part of K -- is folded into the extents the kernel
-// reads (pack_boxes), so a box is 24 bytes on the device.
+// The spheres in the member slots [j span, (j+1) span) of the hierarchy part of level 0 -- what node j of a level bounds:
+// f(centre, |radius|) for each.  Never-hit padding slots are skipped.
+template <class F>
+void for_members_under(const float* centers4, const float* radii, const std::vector<mrt::SphereRec>& members,
+                       const std::vector<uint32_t>& member_index, size_t j, size_t span, F&& f) {
+    for (size_t m = j * span, m1 = std::min(members.size(), (j + 1) * span); m < m1; m++)
+        if (std::isfinite(members[m].neg_r2)) f(centers4 + 4 * member_index[m], std::fabs((double)radii[member_index[m]]));
+}
+
+// The boxes of every node (levels 1 .. top), for the walk of large scenes (sweep.h, box_may_touch): node j of level k covers the
+// members [j 4^k, (j+1) 4^k).  The extents, the two forms of the slack K and their constants are bounds.h's (box_extents,
+// box_kpad); here the scene takes the form that is smaller at its own reach, and its one kc.
 void build_boxes(const float* centers4, const float* radii, const std::vector<mrt::SphereRec>& members, Hierarchy& H) {
-    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, -3.0e38f, -3.0e38f, -3.0e38f, 0.0f, 0.0f};
+    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, kBoxNeverExtent, kBoxNeverExtent, kBoxNeverExtent, 0.0f, 0.0f};
     H.boxes.clear();
-    // the scene's reach and median radius decide the form of the slack
-    double lo_all[3] = {1e300, 1e300, 1e300}, hi_all[3] = {-1e300, -1e300, -1e300};
-    std::vector<double> rr;
-    for (size_t m = 0; m < members.size(); m++) {
-        if (!std::isfinite(members[m].neg_r2)) continue;
-        const uint32_t i = H.member_index[m];
-        rr.push_back(std::fabs((double)radii[i]));
-        for (int k = 0; k < 3; k++) {
-            lo_all[k] = std::min(lo_all[k], (double)centers4[4 * i + k]);
-            hi_all[k] = std::max(hi_all[k], (double)centers4[4 * i + k]);
-        }
-    }
-    double reach = 0.0, r_small = 1e300;
-    if (!rr.empty()) {
+    // the scene's reach and smallest radius decide the form of the slack
+    double lo_all[3] = {1e300, 1e300, 1e300}, hi_all[3] = {-1e300, -1e300, -1e300}, r_small = 1e300;
+    for_members_under(centers4, radii, members, H.member_index, 0, members.size(), [&](const float* c, double r) {
+        r_small = std::min(r_small, r);
+        for (int k = 0; k < 3; k++) { lo_all[k] = std::min(lo_all[k], (double)c[k]); hi_all[k] = std::max(hi_all[k], (double)c[k]); }
+    });
+    double reach = 0.0;
+    if (lo_all[0] <= hi_all[0]) {
         for (int k = 0; k < 3; k++) reach += (hi_all[k] - lo_all[k]) * (hi_all[k] - lo_all[k]);
         reach = std::sqrt(reach);
-        r_small = *std::min_element(rr.begin(), rr.end());
     }
     // (by the scene's SMALLEST radius, since kc is one value per scene: a scene with a few tiny spheres takes the linear form)
-    H.box_quad = 1.3e-6 / std::max(r_small, 1e-300) * reach < 1.5e-3 * 2.0;      // quadratic slack at the reach < 2 x the linear one
-    const double kc_scene = H.box_quad ? 1.3e-6 / std::max(r_small, 1e-30) : 1.5e-3;
-    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
+    H.box_quad = kBoxQuadKc / std::max(r_small, 1e-300) * reach < kBoxLinKc * 2.0;      // quadratic slack at the reach < 2 x the linear one
+    const double kc_scene = H.box_quad ? quad_kc_for_radius(r_small) : kBoxLinKc;
+    H.box_kc = H.box_quad ? round_up_f32(kc_scene) : (float)kBoxLinKc;
     for (uint32_t k = 1; k <= H.levels; k++) {
         H.box_base[k] = (uint32_t)H.boxes.size();
         const size_t n_k = k == H.levels ? H.top.size() : (size_t)((k + 1 < H.levels ? H.level_base[k + 1] : (uint32_t)H.nodes.size()) - H.level_base[k]);
-        const size_t span = (size_t)1 << (2 * k);
         for (size_t j = 0; j < n_k; j++) {
-            const size_t m0 = j * span, m1 = std::min(members.size(), (j + 1) * span);
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            bool any = false;
-            for (size_t m = m0; m < m1; m++) {
-                if (!std::isfinite(members[m].neg_r2)) continue;
-                const uint32_t i = H.member_index[m];
-                const double r = std::fabs((double)radii[i]);
-                for (int q = 0; q < 3; q++) {
-                    lo[q] = std::min(lo[q], (double)centers4[4 * i + q] - r);
-                    hi[q] = std::max(hi[q], (double)centers4[4 * i + q] + r);
-                }
-                any = true;
-            }
-            if (!any) { H.boxes.push_back(never_box); continue; }
-            mrt::BoxFull b;
-            float c[3], e[3];
-            double e1 = 0.0, e2 = 0.0;
-            for (int q = 0; q < 3; q++) {
-                c[q] = (float)(0.5 * (lo[q] + hi[q]));
-                const double ext = std::max(hi[q] - (double)c[q], (double)c[q] - lo[q]) * (1.0 + 1e-6) + 1e-37;   // (the 1e-6: the three roundings of the test's right-hand side)
-                e[q] = up(ext);
-                e1 += (double)e[q];
-                e2 += (double)e[q] * (double)e[q];
-            }
-            b.cx = c[0]; b.cy = c[1]; b.cz = c[2]; b.ex = e[0]; b.ey = e[1]; b.ez = e[2];
-            b.kc = H.box_quad ? up(kc_scene) : 1.5e-3f;
-            b.kpad = H.box_quad ? up((double)b.kc * e2 + 4.4e-14 / kc_scene) : up(1.5e-3 * e1);
-            H.boxes.push_back(b);
+            Span s;
+            for_members_under(centers4, radii, members, H.member_index, j, (size_t)1 << (2 * k), [&](const float* c, double r) { s.add(c, r); });
+            if (s.empty()) { H.boxes.push_back(never_box); continue; }
+            const BoxExtents b = box_extents(s);
+            H.boxes.push_back(mrt::BoxFull{b.c[0], b.c[1], b.c[2], b.e[0], b.e[1], b.e[2], H.box_kc, box_kpad(H.box_quad, (double)H.box_kc, kc_scene, b.e1, b.e2)});
         }
     }
-    H.box_kc = H.box_quad ? up(kc_scene) : 1.5e-3f;
 }
-
-uint16_t bf16_rne(float x) {
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);      // NaN stays NaN
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-float bf16_value(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; }
 
 }  // namespace
 
-// What the kernel reads of a box (mrt_internal.h, BoxRec): the centre and the extents with kpad folded in, e' = e + kpad rounded
-// up.  The test on the axis d x e_i then has the slack kc X + kpad (|d_j| + |d_k|) instead of kc X + kpad; what is needed there is
-// rho |d x e_i| + (the test's rounding) (|d_j| + |d_k|), rho the distance beyond the box the line of a candidate can pass, and
-// |d x e_i| <= s = |d_j| + |d_k| <= 1.4143: both sides are linear in s on [0, 1] and on [1, 1.4143], at s = 0 the left side is
-// kc X >= 0, and at s = 1 and s = 1.4143 the inequality is the one build_boxes provides (kc X + kpad >= 1.4143 rho + the
-// rounding: tests/test_hierarchy_host.py checks it box by box).
+// What the kernel reads of a box (mrt_internal.h, BoxRec): the centre and the extents with kpad folded in (bounds.h, fold_kpad)
 void pack_boxes(const std::vector<mrt::BoxFull>& full, std::vector<mrt::BoxRec>& out) {
-    auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return f; };
     out.resize(full.size());
     for (size_t i = 0; i < full.size(); i++) {
         const mrt::BoxFull& b = full[i];
-        const bool real = b.ex >= 0.0f && b.ex < 1.0e37f;           // (never-hit: -3e38; opened wide: 3e37)
-        out[i] = mrt::BoxRec{b.cx, b.cy, b.cz, real ? up((double)b.ex + (double)b.kpad) : b.ex, real ? up((double)b.ey + (double)b.kpad) : b.ey,
-                             real ? up((double)b.ez + (double)b.kpad) : b.ez};
+        const bool real = b.ex >= 0.0f && b.ex < 1.0e37f;           // (never-hit: kBoxNeverExtent; opened wide: kBoxOpenExtent)
+        out[i] = real ? mrt::BoxRec{b.cx, b.cy, b.cz, fold_kpad(b.ex, b.kpad), fold_kpad(b.ey, b.kpad), fold_kpad(b.ez, b.kpad)}
+                      : mrt::BoxRec{b.cx, b.cy, b.cz, b.ex, b.ey, b.ez};
     }
 }
 
 // The boxes in the order the kernel walks them (KParams::boxes): depth t of the hierarchy (0 = the swept top = level
 // `levels`, levels - 1 = the clusters = level 1) at o_t = n_top (4^t - 1) / 3, n_top = the padded top: the children of node g
 // are 4 g + n_top .. + 3 whatever its depth, so a work item needs no level.  Slots without a node hold never-hit boxes.
-// `open`: every real box opened wide (extents 3e37: the test never rejects) -- the A/B form of mrt_debug_set_boxes(0).
+// `open`: every real box opened wide (kBoxOpenExtent: the test never rejects) -- the A/B form of mrt_debug_set_boxes(0).
 void boxes_top_down(const Hierarchy& H, bool open, std::vector<mrt::BoxFull>& out, uint32_t* cluster_first, uint32_t* cluster_parent_first) {
-    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, -3.0e38f, -3.0e38f, -3.0e38f, 0.0f, 0.0f};
+    const mrt::BoxFull never_box{0.0f, 0.0f, 0.0f, kBoxNeverExtent, kBoxNeverExtent, kBoxNeverExtent, 0.0f, 0.0f};
     const size_t n_top = H.top.size();
     size_t o[mrt::kMaxLevels + 1];
     o[0] = 0;
@@ -310,7 +250,7 @@ void boxes_top_down(const Hierarchy& H, bool open, std::vector<mrt::BoxFull>& ou
         const size_t first = H.box_base[k], last = k < H.levels ? H.box_base[k + 1] : H.boxes.size();
         for (size_t j = 0; j < last - first && j < (n_top << (2 * t)); j++) {
             mrt::BoxFull b = H.boxes[first + j];
-            if (open && b.ex >= 0.0f) b.ex = b.ey = b.ez = 3.0e37f;
+            if (open && b.ex >= 0.0f) b.ex = b.ey = b.ez = kBoxOpenExtent;
             out[o[t] + j] = b;
         }
     }
@@ -321,7 +261,7 @@ void boxes_top_down(const Hierarchy& H, bool open, std::vector<mrt::BoxFull>& ou
 constexpr uint32_t kBoxMinMembers = 4096;     // member slots from which the walk tests boxes by default (fill_scene_params)
 void build_hierarchy(const float* centers4, const float* radii, uint32_t n, float factor, uint32_t max_levels,
                      uint32_t top_target, Hierarchy& H) {
-    const mrt::SphereRec never{0.0f, 0.0f, 0.0f, INFINITY};
+    const mrt::SphereRec never = never_hit_record();
     std::vector<mrt::SphereRec> members, cur;
     std::vector<uint32_t> direct;
     build_clusters(centers4, radii, n, factor, cur, members, H.member_index, direct, &H.n_pool);
@@ -358,31 +298,14 @@ void build_hierarchy(const float* centers4, const float* radii, uint32_t n, floa
         std::vector<mrt::SphereRec> par;
         par.reserve(n_par + mrt::kGroup);
         for (size_t j = 0; j < n_par; j++) {
-            const size_t m0 = j * span, m1 = std::min(members.size(), (j + 1) * span);
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            bool any = false;
-            for (size_t m = m0; m < m1; m++) {
-                if (!std::isfinite(members[m].neg_r2)) continue;
-                const uint32_t i = H.member_index[m];
-                const double r = std::fabs((double)radii[i]);
-                for (int k = 0; k < 3; k++) {
-                    lo[k] = std::min(lo[k], (double)centers4[4 * i + k] - r);
-                    hi[k] = std::max(hi[k], (double)centers4[4 * i + k] + r);
-                }
-                any = true;
-            }
-            if (!any) { par.push_back(never); continue; }
-            double ctr[3], R = 0;
-            for (int k = 0; k < 3; k++) ctr[k] = (double)(float)(0.5 * (lo[k] + hi[k]));
-            for (size_t m = m0; m < m1; m++) {
-                if (!std::isfinite(members[m].neg_r2)) continue;
-                const uint32_t i = H.member_index[m];
-                double d2 = 0;
-                for (int k = 0; k < 3; k++) { const double d = (double)centers4[4 * i + k] - ctr[k]; d2 += d * d; }
-                R = std::max(R, std::sqrt(d2) + std::fabs((double)radii[i]));
-            }
-            const float Rf = (float)(R * mrt::kBoundInflate) + 1e-30f;
-            par.push_back(mrt::SphereRec{(float)ctr[0], (float)ctr[1], (float)ctr[2], -(Rf * Rf)});
+            Span s;
+            for_members_under(centers4, radii, members, H.member_index, j, span, [&](const float* c, double r) { s.add(c, r); });
+            if (s.empty()) { par.push_back(never); continue; }
+            float ctr[3];
+            s.centre(ctr);
+            double R = 0;
+            for_members_under(centers4, radii, members, H.member_index, j, span, [&](const float* c, double r) { R = std::max(R, reach_from(ctr, c, r)); });
+            par.push_back(bound_record(ctr, R));
         }
         while (cur.size() % 4 != 0) cur.push_back(never);
         H.level_base[H.levels] = (uint32_t)H.nodes.size();
@@ -407,58 +330,35 @@ static void sweep_origin(const std::vector<mrt::SphereRec>& top, float origin[3]
     for (int k = 0; k < 3; k++) origin[k] = lo[k] <= hi3[k] ? (float)(0.5 * (lo[k] + hi3[k])) : 0.0f;
 }
 
-// The top level once more, as the A operand of the matrix-core sweep (sweep.h, mfma_sweep_tile): per
-// tile of 32 records 64 lanes x 8 bf16, lane l = row (l & 31), k = 8 (l >> 5) + j:
-//     k 0..2 C_hi, 3..5 C_hi, 6..8 C_lo, 9..11 (1,1,1), 12..14 Ck (hi, mid, lo), 15: 0
-// where row m of tile t is record 32 t + 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3) -- the order in which the
-// MFMA result registers come out, so that the two 16-bit sign words per tile are the masks of chunks 2t and
-// 2t + 1.  Ck = C.C - R^2 - 2^-13 (C.C + R^2): the record's share of the slack that covers what the bf16
-// split drops.  A never-hit record gets Ck = 3e38 (finite: an infinity would turn the other
-// GEMM's 0 x Ck into NaN).  Also returns what set_world needs to decide whether the slack is negligible:
-// the largest C.C and the median R^2.
+// The top level once more, as the A operand of the matrix-core sweep: the rows and their placement are bounds.h's (mfma_row).
+// Also returns what set_world needs to decide whether the slack is negligible: the largest C.C and the median R^2.
 // `rel`: the records relative to the sweep's origin, in the top level's order (build_top_mfma, build_sweep_operand).
 static void pack_top_mfma(const std::vector<mrt::SphereRec>& rel, std::vector<uint16_t>& out, double* max_c2, double* med_r2, size_t* n_real) {
     const size_t tiles = rel.size() / 32;
     out.assign(tiles * 512, 0);
     std::vector<double> r2s;
     *max_c2 = 0.0;
-    const uint16_t one = bf16_rne(1.0f);
     for (size_t t = 0; t < tiles; t++)
         for (uint32_t m = 0; m < 32; m++) {
-            const mrt::SphereRec& r = rel[32 * t + 16 * ((m >> 2) & 1u) + 4 * (m >> 3) + (m & 3u)];
-            float ck = 3.0e38f;
-            const float c[3] = {r.cx, r.cy, r.cz};
+            const mrt::SphereRec& r = rel[mfma_source_record((uint32_t)t, m)];
             if (std::isfinite(r.neg_r2)) {
-                const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-                const double R = std::sqrt(-(double)r.neg_r2) + 2.0 * 0x1p-24 * std::sqrt(c2), R2 = R * R;
-                const double v = c2 - R2 - kMfmaSlack * (c2 + R2);
-                ck = (float)v;
-                if ((double)ck > v) ck = std::nextafterf(ck, -INFINITY);
-                *max_c2 = std::max(*max_c2, c2);
-                r2s.push_back(R2);
+                const MfmaTerms terms = mfma_terms(r);
+                *max_c2 = std::max(*max_c2, terms.c2);
+                r2s.push_back(terms.R2);
             }
-            uint16_t hi[3], lo16[3];
-            for (int k = 0; k < 3; k++) { hi[k] = bf16_rne(c[k]); lo16[k] = bf16_rne(c[k] - bf16_value(hi[k])); }
-            const uint16_t k0 = bf16_rne(ck);
-            const float ck1 = ck - bf16_value(k0);
-            const uint16_t k1 = bf16_rne(ck1), k2 = bf16_rne(ck1 - bf16_value(k1));
-            const uint16_t kvals[16] = {hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo16[0], lo16[1], lo16[2], one, one, one, k0, k1, k2, 0};
-            uint16_t* o = out.data() + t * 512;
-            for (int k = 0; k < 16; k++) o[((k >> 3) * 32 + m) * 8 + (k & 7)] = kvals[k];
+            uint16_t row[16];
+            mfma_row(r, row);
+            for (uint32_t q = 0; q < 16; q++) out[t * 512 + mfma_slot(m, q)] = row[q];
         }
     *n_real = r2s.size();
     *med_r2 = 0.0;
     if (!r2s.empty()) { std::nth_element(r2s.begin(), r2s.begin() + r2s.size() / 2, r2s.end()); *med_r2 = r2s[r2s.size() / 2]; }
 }
 
-// the world-space top records relative to the origin: exact in double, then rounded to f32 -- the rounding moves a bound by at
-// most 2 eps |c|, which its radius absorbs (pack_top_mfma)
+// the world-space top records relative to the origin (bounds.h, relative_record)
 static void relative_records(const std::vector<mrt::SphereRec>& top, const float origin[3], std::vector<mrt::SphereRec>& rel) {
     rel.resize(top.size());
-    for (size_t i = 0; i < top.size(); i++) {
-        const mrt::SphereRec& r = top[i];
-        rel[i] = mrt::SphereRec{(float)((double)r.cx - origin[0]), (float)((double)r.cy - origin[1]), (float)((double)r.cz - origin[2]), r.neg_r2};
-    }
+    for (size_t i = 0; i < top.size(); i++) rel[i] = relative_record(top[i], origin);
 }
 
 void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t>& out, float origin[3], double* max_c2,
@@ -473,7 +373,7 @@ void build_top_mfma(const std::vector<mrt::SphereRec>& top, std::vector<uint16_t
 // member sphere meets, in that space, the scaled member -- an ellipsoid with the semi-axes r D -- hence any sphere that
 // encloses the scaled members of its cluster, and flat clusters get much smaller spheres there.  rel[j] = such a sphere for
 // top record j, from the member spheres under it: centre = centre of the scaled members' common box, rounded to f32; radius =
-// kBoundInflate x the largest distance from THAT point to a point of a scaled member.  That distance, max |p + r D u| over
+// bound_record of the largest distance from THAT point to a point of a scaled member.  That distance, max |p + r D u| over
 // unit u, is the minimum over lambda > max (r D_k)^2 of lambda + sum_k p_k^2 lambda / (lambda - (r D_k)^2) (Lagrange
 // dual; EVERY lambda gives an upper bound, so the search below cannot make the result too small), never above the two
 // plain bounds |p| + r max D and |(|p_k| + r D_k)_k|.  Returns false where the proof of DESIGN.md §4 does not hold
@@ -533,8 +433,7 @@ static bool scaled_top_records(const Hierarchy& H, const float axis[3], const fl
             E = std::max(E, std::sqrt(best) * (1.0 + 1e-12));
         }
         if (!(r_min > 0.0) || dmax * E / r_min + dmax * dmax > kScaledMarginBudget) proven = false;
-        const float Rf = (float)(E * mrt::kBoundInflate) + 1e-30f;
-        rel[j] = mrt::SphereRec{ctr[0], ctr[1], ctr[2], -(Rf * Rf)};
+        rel[j] = bound_record(ctr, E);
     }
     return proven;
 }
@@ -663,6 +562,22 @@ double sweep_reach(const float* centers4, const float* radii, uint32_t n, const 
 
 using mrt::Hierarchy, mrt::build_hierarchy, mrt::build_top_mfma, mrt::build_sweep_operand, mrt::boxes_top_down, mrt::pack_boxes, mrt::mfma_scales;
 
+namespace {
+// what every mrt_debug_build_* entry point starts from: the caller's spheres as the builder takes them, and their hierarchy
+struct BuiltScene {
+    std::vector<float> centers, radii;
+    Hierarchy h;
+    BuiltScene(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target) : centers(4 * (n ? n : 1)), radii(n ? n : 1) {
+        for (size_t i = 0; i < n; i++) {
+            for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
+            centers[4 * i + 3] = 1.0f;
+            radii[i] = spheres[i].radius;
+        }
+        build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int mrt_debug_build_hierarchy(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target,
@@ -671,14 +586,8 @@ int mrt_debug_build_hierarchy(const mrt_sphere* spheres, size_t n, uint32_t max_
                               float mfma_origin_out[3], uint32_t info[10]) {
     if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
         return MRT_ERR_INVALID_ARG;
-    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
-    for (size_t i = 0; i < n; i++) {
-        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
-        centers[4 * i + 3] = 1.0f;
-        radii[i] = spheres[i].radius;
-    }
-    Hierarchy h;
-    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    const BuiltScene b(spheres, n, max_levels, top_target);
+    const Hierarchy& h = b.h;
     std::vector<uint16_t> mf;
     float origin[3];
     double max_c2, med_r2;
@@ -704,14 +613,8 @@ int mrt_debug_build_sweep(const mrt_sphere* spheres, size_t n, const float* forc
     if (force_axis)
         for (int k = 0; k < 3; k++)
             if (force_axis[k] != 1.0f && force_axis[k] != 2.0f && force_axis[k] != 4.0f) return MRT_ERR_INVALID_ARG;
-    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
-    for (size_t i = 0; i < n; i++) {
-        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
-        centers[4 * i + 3] = 1.0f;
-        radii[i] = spheres[i].radius;
-    }
-    Hierarchy h;
-    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, mrt::kMaxLevels, 0, h);
+    const BuiltScene b(spheres, n, mrt::kMaxLevels, 0);
+    const Hierarchy& h = b.h;
     std::vector<uint16_t> mf;
     std::vector<mrt::SphereRec> rel;
     float origin[3];
@@ -722,7 +625,7 @@ int mrt_debug_build_sweep(const mrt_sphere* spheres, size_t n, const float* forc
     if (records_out) std::memcpy(records_out, rel.data(), rel.size() * sizeof(mrt::SphereRec));
     if (mfma_out) std::memcpy(mfma_out, mf.data(), mf.size() * sizeof(uint16_t));
     if (origin_out) for (int k = 0; k < 3; k++) origin_out[k] = origin[k];
-    if (reach_out) *reach_out = mrt::sweep_reach(centers.data(), radii.data(), (uint32_t)n, origin, axis_out);
+    if (reach_out) *reach_out = mrt::sweep_reach(b.centers.data(), b.radii.data(), (uint32_t)n, origin, axis_out);
     return MRT_OK;
 }
 
@@ -730,14 +633,8 @@ int mrt_debug_build_boxes_top_down(const mrt_sphere* spheres, size_t n, uint32_t
                                    float* boxes_out, size_t boxes_cap, uint32_t info[5]) {
     if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
         return MRT_ERR_INVALID_ARG;
-    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
-    for (size_t i = 0; i < n; i++) {
-        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
-        centers[4 * i + 3] = 1.0f;
-        radii[i] = spheres[i].radius;
-    }
-    Hierarchy h;
-    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    const BuiltScene b(spheres, n, max_levels, top_target);
+    const Hierarchy& h = b.h;
     std::vector<mrt::BoxFull> full;
     std::vector<mrt::BoxRec> packed;
     uint32_t cf = 0, cpf = 0;
@@ -757,14 +654,8 @@ int mrt_debug_build_boxes(const mrt_sphere* spheres, size_t n, uint32_t max_leve
                           size_t boxes_cap, uint32_t info[8]) {
     if ((!spheres && n) || !info || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres)
         return MRT_ERR_INVALID_ARG;
-    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
-    for (size_t i = 0; i < n; i++) {
-        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
-        centers[4 * i + 3] = 1.0f;
-        radii[i] = spheres[i].radius;
-    }
-    Hierarchy h;
-    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    const BuiltScene b(spheres, n, max_levels, top_target);
+    const Hierarchy& h = b.h;
     info[0] = h.levels; info[1] = (uint32_t)h.boxes.size(); info[2] = h.box_quad ? 1u : 0u;
     for (uint32_t k = 0; k <= mrt::kMaxLevels; k++) info[3 + k] = h.box_base[k];
     if (boxes_out && boxes_cap < h.boxes.size()) return MRT_ERR_TOO_SMALL;
@@ -774,14 +665,8 @@ int mrt_debug_build_boxes(const mrt_sphere* spheres, size_t n, uint32_t max_leve
 
 int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_levels, uint32_t top_target, uint32_t* n_pool) {
     if ((!spheres && n) || !n_pool || max_levels < 1 || max_levels > mrt::kMaxLevels || n > mrt::kMaxSpheres) return MRT_ERR_INVALID_ARG;
-    std::vector<float> centers(4 * (n ? n : 1)), radii(n ? n : 1);
-    for (size_t i = 0; i < n; i++) {
-        for (int k = 0; k < 3; k++) centers[4 * i + k] = spheres[i].center[k];
-        centers[4 * i + 3] = 1.0f;
-        radii[i] = spheres[i].radius;
-    }
-    Hierarchy h;
-    build_hierarchy(centers.data(), radii.data(), (uint32_t)n, 8.0f, max_levels, top_target, h);
+    const BuiltScene b(spheres, n, max_levels, top_target);
+    const Hierarchy& h = b.h;
     *n_pool = h.n_pool;
     return MRT_OK;
 }

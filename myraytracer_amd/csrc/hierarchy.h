@@ -3,7 +3,7 @@
 #pragma once
 #include <vector>
 
-#include "mrt_internal.h"
+#include "bounds.h"
 
 namespace mrt {
 
@@ -28,9 +28,6 @@ struct Hierarchy {
     mrt::SphereRec direct[mrt::kMaxDirect] = {};
     uint32_t direct_index[mrt::kMaxDirect] = {};
 };
-
-// the matrix-core sweep inflates R^2 by this share of o.o + C.C + R^2 (build_top_mfma)
-constexpr double kMfmaSlack = 0x1p-13;
 
 // the hierarchy of n spheres (centers4: 4 floats each); its boxes in the kernel's top-down numbering (KParams::boxes) and in the form
 // the kernel reads; its top level as the matrix-core sweep's A operand; KParams::mfma_scale / mfma_neg_k2_pair for rays and

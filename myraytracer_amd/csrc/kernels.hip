@@ -189,7 +189,7 @@ constexpr uint32_t kWavesPerGroup = 4;
 // is ray number `texel` of P.dbg_rays, traced once; the winner goes to P.dbg_hit and every (ray, sphere) that
 // reaches the root tests is recorded in P.dbg_cand.  Nothing else of the kernel changes.
 // SC: the scene's layout -- 0 = SMALL (above), 1 / 2 = large, with the linear / the quadratic form of the box test's slack
-// (hierarchy.cpp build_boxes; a compile-time choice: as a run-time flag it was two branches in every box test).
+// (hierarchy.cpp build_boxes, bounds.h box_kpad; a compile-time choice: as a run-time flag it was two branches in every box test).
 template <bool COUNT, bool PILOT, bool CTR, int SC, bool MFMA, bool DBG = false>
 // Registers: small scenes run 5 workgroups per CU (their LDS footprint, 31.5 KB at C3) = 5 waves per SIMD = 96 VGPRs; large
 // scenes (work queues of every level, u32 items: 33-36 KB per workgroup) fit 4 workgroups per CU whatever the kernel does, so

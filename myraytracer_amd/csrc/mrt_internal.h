@@ -15,7 +15,7 @@ constexpr uint32_t kClusterK = 4;        // spheres per sweep record (cluster)
 constexpr uint32_t kMaxSpheres = 1u << 20;
 constexpr uint32_t kMaxLevels = 4;       // levels of bounding spheres above the member spheres
 // Conservativeness of a bounding-sphere test: the ray direction is stretched by kBoundStretch
-// in the test and the stored radius is kBoundInflate x the enclosing radius.
+// in the test and the stored radius is kBoundInflate x the enclosing radius (bounds.h, bound_record).
 constexpr float kBoundStretch = 1.0001f;
 constexpr double kBoundInflate = 1.015;
 constexpr uint32_t kMaxFrameBatch = 32;   // frames one render launch may cover (stream mode, mrt_render)
@@ -34,11 +34,11 @@ struct alignas(16) SphereRec { float cx, cy, cz, neg_r2; };
 
 // Axis-aligned box of the member spheres under a node of the hierarchy (large scenes: the walk's second, much tighter bound
 // -- a kd-built group of spheres on a plane fills its box, not its bounding sphere).
-// BoxFull: what the host derives per node (hierarchy.cpp, build_boxes) and the diagnostics report: centre, half extents (measured
+// BoxFull: what the host derives per node (hierarchy.cpp, build_boxes, by the formulas of bounds.h) and the diagnostics report: centre, half extents (measured
 // from the f32 centre, rounded up) and the two coefficients of the test's slack K = kc X + kpad (X = |p|^2 or |p|_1 of the ray
 // origin relative to the centre, per scene: KParams::box_quad); kc is ONE value per scene (KParams::box_kc).
 // BoxRec: what the kernel reads, 24 bytes: the centre and the half extents WITH kpad folded in (e + kpad, rounded up) -- on the
-// axis d x e_i the slack kpad (|d_j| + |d_k|) that gives covers what the "+ kpad" of the test covered (hierarchy.cpp, pack_boxes) --
+// axis d x e_i the slack kpad (|d_j| + |d_k|) that gives covers what the "+ kpad" of the test covered (bounds.h, fold_kpad) --
 // so an inner item's four children are 96 bytes instead of 128: a large scene's rounds wait for the vector-memory path's
 // 64 bytes per clock and CU.  A never-hit box has extents -3e38.
 struct BoxFull { float cx, cy, cz, ex, ey, ez, kc, kpad; };
@@ -93,7 +93,7 @@ struct KParams {
     // the capacity of the wave's work stack.  Null / 0 for small scenes.
     const BoxRec* boxes;
     uint32_t box_cluster_first, box_cluster_parent_first, box_quad;
-    float box_kc;               // the slack's coefficient of X, one per scene (hierarchy.cpp, build_boxes)
+    float box_kc;               // the slack's coefficient of X, one per scene (bounds.h, box_kpad)
     // the first box_lds_count boxes of that numbering (the swept top, and the level below it where it fits) are copied into
     // the workgroup's LDS: what the owners' filter and the first inner rounds read (kernels.hip)
     uint32_t box_lds_count;
@@ -236,7 +236,7 @@ int launch_tile_blend(const TileBlendArgs& a, void* stream);
 // launch_refit_scatter: `count` <= kRefitBatch spheres (cx, cy, cz, radius), passed BY VALUE in the kernel arguments (no staging
 // buffer, no copy for the runtime to order), into the four device copies of spheres [first, first + count): spheres, floats 0..3
 // of shade, and the reference's SoA -- centres = vec4_data + 4 center_base_idx, radii = f32_data + radius_base_idx.
-// launch_refit: everything derived from them, as hierarchy.cpp derives it: the member records (level 0 of nodes), every level's
+// launch_refit: everything derived from them, by the functions hierarchy.cpp derives it with (bounds.h): the member records (level 0 of nodes), every level's
 // bounding spheres (nodes / clusters), with boxes != null the boxes and their opened-wide copies in the top-down numbering for
 // box_quad / box_kc, and the A operand for D = I relative to origin.  n_hier: the member slots the hierarchy covers (direct_first).
 constexpr uint32_t kRefitBatch = 192;    // 3 KB of the 4 KB a launch's arguments may take

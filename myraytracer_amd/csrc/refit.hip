@@ -1,23 +1,19 @@
 // The refit behind mrt_update_spheres (world.cpp; include/myraytracer_amd.h "scene"): new centres and radii for spheres whose
 // grouping stays.  Everything hierarchy.cpp derives from the spheres' geometry -- member records, the bounding spheres of the
 // clusters / inner levels / top, the boxes of large scenes in the kernel's top-down numbering, the matrix-core sweep's A operand
-// for D = I -- recomputed on the device with hierarchy.cpp's formulas, in double, queued in stream order.  Node j of level k
-// covers the member slots [j 4^k, (j+1) 4^k) of the hierarchy part of level 0, so every bound is a segmented reduction over the
-// members themselves and the levels do not depend on one another.  The outputs are held to the builder's invariants
-// (tests/refit_ref.py), not to bit identity with it.  (The build's -ffp-contract=off holds here too: no fused rounding.)
+// for D = I -- recomputed on the device by the functions of bounds.h, which the builder calls too, in double, queued in stream
+// order.  Node j of level k covers the member slots [j 4^k, (j+1) 4^k) of the hierarchy part of level 0, so every bound is a
+// segmented reduction over the members themselves and the levels do not depend on one another.  What is the device's own here:
+// which lane takes which member, the shuffles, the top-down slot of a box, the launches.  The outputs are held to the builder's
+// invariants (tests/refit_ref.py) and to their recorded bits (tests/golden/hierarchy_hashes.json), not to bit identity with the
+// builder: box_kpad (bounds.h) says where the two differ.  (The build's -ffp-contract=off holds here too: no fused rounding.)
 #include <hip/hip_runtime.h>
-#include "mrt_internal.h"
+#include "bounds.h"
 
 namespace mrt {
 namespace {
 
 constexpr uint32_t kRefitBlock = 256;
-
-__device__ __forceinline__ float round_up_f32(double v) {
-    float f = (float)v;
-    if ((double)f < v) f = nextafterf(f, INFINITY);
-    return f;
-}
 
 // One lane per updated sphere of the batch: the four device copies of a sphere's geometry.  The batch rides in the kernel
 // arguments, so the host stages nothing.
@@ -54,108 +50,63 @@ template <uint32_t L> __device__ __forceinline__ double group_max(double v) {
 }
 
 // Level k (1 .. levels; the top is level `levels`): L = min(4^k, 64) lanes per node, each taking every L-th member slot of the
-// node's span -- a lane per member up to level 3, a whole wave with four slots a lane at level 4.  Two passes over the members,
-// as enclose / build_hierarchy make them: their common box (-> the f32 centre), then R = max(|c_m - centre| + |r_m|) measured
-// from the ROUNDED centre.  The node's box (large scenes) comes from the first pass: build_boxes' extents, pack_boxes' 24 bytes.
+// node's span -- a lane per member up to level 3, a whole wave with four slots a lane at level 4.  Two passes over the members:
+// their common box (bounds.h, Span: -> the f32 centre), then R measured from that centre.  The node's box (large scenes) comes
+// from the first pass.
 template <uint32_t L>
 __global__ void __launch_bounds__(kRefitBlock) refit_level_kernel(const RefitArgs a, const uint32_t k) {
     const uint32_t g = blockIdx.x * kRefitBlock + threadIdx.x, j = g / L, sub = g % L;
     const uint32_t n_k = k == a.levels ? a.n_padded : (k + 1 < a.levels ? a.level_base[k + 1] : a.n_nodes) - a.level_base[k];
     const uint64_t span = 1ull << (2 * k);
     const uint64_t m0 = min((uint64_t)a.n_hier, (uint64_t)j * span), m1 = min((uint64_t)a.n_hier, ((uint64_t)j + 1) * span);
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    Span s;
     for (uint64_t m = m0 + sub; m < m1; m += L) {
-        const SphereRec s = a.nodes[m];
-        if (s.neg_r2 == INFINITY) continue;
-        const double r = fabs((double)a.shade[8 * (size_t)a.member_index[m] + 3]);
-        const double c[3] = {s.cx, s.cy, s.cz};
-#pragma unroll
-        for (int q = 0; q < 3; q++) { lo[q] = fmin(lo[q], c[q] - r); hi[q] = fmax(hi[q], c[q] + r); }
+        const SphereRec rec = a.nodes[m];
+        if (rec.neg_r2 == INFINITY) continue;
+        s.add(&rec.cx, fabs((double)a.shade[8 * (size_t)a.member_index[m] + 3]));
     }
 #pragma unroll
-    for (int q = 0; q < 3; q++) { lo[q] = group_min<L>(lo[q]); hi[q] = group_max<L>(hi[q]); }
-    const bool any = lo[0] <= hi[0];
-    double ctr[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) ctr[q] = (double)(float)(0.5 * (lo[q] + hi[q]));
+    for (int q = 0; q < 3; q++) { s.lo[q] = group_min<L>(s.lo[q]); s.hi[q] = group_max<L>(s.hi[q]); }
+    float ctr[3];
+    s.centre(ctr);
     double R = 0.0;
     for (uint64_t m = m0 + sub; m < m1; m += L) {
-        const SphereRec s = a.nodes[m];
-        if (s.neg_r2 == INFINITY) continue;
-        const double r = fabs((double)a.shade[8 * (size_t)a.member_index[m] + 3]);
-        const double dx = (double)s.cx - ctr[0], dy = (double)s.cy - ctr[1], dz = (double)s.cz - ctr[2];
-        R = fmax(R, sqrt(dx * dx + dy * dy + dz * dz) + r);
+        const SphereRec rec = a.nodes[m];
+        if (rec.neg_r2 == INFINITY) continue;
+        R = fmax(R, reach_from(ctr, &rec.cx, fabs((double)a.shade[8 * (size_t)a.member_index[m] + 3])));
     }
     R = group_max<L>(R);
     if (sub != 0 || j >= n_k) return;
     SphereRec* const out = k == a.levels ? a.clusters : a.nodes + a.level_base[k];
-    if (any) {
-        const float Rf = (float)(R * kBoundInflate) + 1e-30f;
-        out[j] = SphereRec{(float)ctr[0], (float)ctr[1], (float)ctr[2], -(Rf * Rf)};
-    } else {
-        out[j] = SphereRec{0.0f, 0.0f, 0.0f, INFINITY};
-    }
+    if (s.empty()) out[j] = never_hit_record();
+    else out[j] = bound_record(ctr, R);
     if (!a.boxes) return;
     // depth t = levels - k of the top-down numbering starts at n_padded (4^t - 1) / 3 and has n_padded 4^t slots
     const uint32_t t = a.levels - k;
     const uint64_t width = (uint64_t)a.n_padded << (2 * t), at = (width - a.n_padded) / 3 + j;
     if (j >= width) return;
-    if (!any) {
-        a.boxes[at] = a.boxes_open[at] = BoxRec{0.0f, 0.0f, 0.0f, -3.0e38f, -3.0e38f, -3.0e38f};
+    if (s.empty()) {
+        a.boxes[at] = a.boxes_open[at] = never_hit_box();
         return;
     }
-    float c[3], e[3];
-    double e1 = 0.0, e2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        c[q] = (float)(0.5 * (lo[q] + hi[q]));
-        e[q] = round_up_f32(fmax(hi[q] - (double)c[q], (double)c[q] - lo[q]) * (1.0 + 1e-6) + 1e-37);
-        e1 += (double)e[q];
-        e2 += (double)e[q] * (double)e[q];
-    }
-    // kpad for the kc of THIS call (the host keeps kc >= 1.3e-6 / the smallest radius: world.cpp), folded into the extents
-    const double kc = (double)a.box_kc;
-    const float kpad = a.box_quad ? round_up_f32(kc * e2 + 4.4e-14 / kc) : round_up_f32(1.5e-3 * e1);
-    a.boxes[at] = BoxRec{c[0], c[1], c[2], round_up_f32((double)e[0] + (double)kpad), round_up_f32((double)e[1] + (double)kpad),
-                         round_up_f32((double)e[2] + (double)kpad)};
-    a.boxes_open[at] = BoxRec{c[0], c[1], c[2], 3.0e37f, 3.0e37f, 3.0e37f};
+    // kpad for the kc of THIS call (the host keeps kc >= quad_kc_for_radius of every clustered sphere: world.cpp)
+    const BoxExtents b = box_extents(s);
+    const float kpad = box_kpad(a.box_quad, (double)a.box_kc, (double)a.box_kc, b.e1, b.e2);
+    a.boxes[at] = BoxRec{b.c[0], b.c[1], b.c[2], fold_kpad(b.e[0], kpad), fold_kpad(b.e[1], kpad), fold_kpad(b.e[2], kpad)};
+    a.boxes_open[at] = BoxRec{b.c[0], b.c[1], b.c[2], kBoxOpenExtent, kBoxOpenExtent, kBoxOpenExtent};
 }
 
-__device__ __forceinline__ uint16_t bf16_rne(float x) {
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf16_value(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-// The top records as the matrix-core sweep's A operand for D = I, relative to the kept origin: pack_top_mfma's layout, bf16
-// splits and round-down of Ck, one lane per row (record) of a tile.  After the top level's kernel in stream order.
+// The top records as the matrix-core sweep's A operand for D = I, relative to the kept origin (bounds.h, mfma_row): one lane per
+// row (record) of a tile.  After the top level's kernel in stream order.
 __global__ void __launch_bounds__(kRefitBlock) refit_mfma_kernel(const RefitArgs a) {
     const uint32_t g = blockIdx.x * kRefitBlock + threadIdx.x;
     if (g >= a.n_padded) return;
     const uint32_t t = g / 32u, m = g % 32u;
-    const SphereRec rec = a.clusters[32u * t + 16u * ((m >> 2) & 1u) + 4u * (m >> 3) + (m & 3u)];
-    const float c[3] = {(float)((double)rec.cx - (double)a.origin[0]), (float)((double)rec.cy - (double)a.origin[1]),
-                        (float)((double)rec.cz - (double)a.origin[2])};
-    float ck = 3.0e38f;
-    if (rec.neg_r2 != INFINITY) {
-        const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-        const double R = sqrt(-(double)rec.neg_r2) + 2.0 * 0x1p-24 * sqrt(c2), R2 = R * R;
-        const double v = c2 - R2 - 0x1p-13 * (c2 + R2);
-        ck = (float)v;
-        if ((double)ck > v) ck = nextafterf(ck, -INFINITY);
-    }
-    uint16_t hi[3], lo16[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) { hi[q] = bf16_rne(c[q]); lo16[q] = bf16_rne(c[q] - bf16_value(hi[q])); }
-    const uint16_t k0 = bf16_rne(ck);
-    const float ck1 = ck - bf16_value(k0);
-    const uint16_t k1 = bf16_rne(ck1), k2 = bf16_rne(ck1 - bf16_value(k1)), one = bf16_rne(1.0f);
-    const uint16_t kvals[16] = {hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo16[0], lo16[1], lo16[2], one, one, one, k0, k1, k2, 0};
+    uint16_t row[16];
+    mfma_row(relative_record(a.clusters[mfma_source_record(t, m)], a.origin), row);
     uint16_t* const o = a.top_mfma + (size_t)t * 512;
 #pragma unroll
-    for (int q = 0; q < 16; q++) o[((q >> 3) * 32 + m) * 8 + (q & 7)] = kvals[q];
+    for (uint32_t q = 0; q < 16; q++) o[mfma_slot(m, q)] = row[q];
 }
 
 template <uint32_t L> void launch_level(const RefitArgs& a, uint32_t k, uint32_t n_k, hipStream_t st) {

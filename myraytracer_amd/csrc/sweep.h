@@ -63,11 +63,11 @@ __device__ __forceinline__ void test8(const Sph8& g, V3 o, V3 ds, uint32_t& bits
 // (necessary and sufficient for a line and a box; the parts of the line behind the origin are left to the sphere tests).
 // K = kc X + kpad, X = |p|^2 or |p|_1 (per scene), is the slack that makes it CONSERVATIVE against the reference's own
 // rounding: a member whose computed discriminant is >= 0 has the line within sqrt(r^2 + 14 eps |oc|^2 / a) of its centre,
-// i.e. up to min(14 eps |oc|^2 / (2 r), sqrt(14 eps) |oc|) beyond its surface, hence beyond its box; the host (hierarchy.cpp,
-// build_boxes) sets kc per scene and kpad per box so that K covers 1.4143 x that for every member under the node, plus the
+// i.e. up to min(14 eps |oc|^2 / (2 r), sqrt(14 eps) |oc|) beyond its surface, hence beyond its box; the host (bounds.h,
+// box_kpad) sets kc per scene and kpad per box so that K covers 1.4143 x that for every member under the node, plus the
 // test's own rounding (4 eps |p|_1; the right-hand side's three roundings are in the extents).  The kernel reads kpad FOLDED
 // INTO THE EXTENTS (e + kpad: on the axis d x e_i that is a slack of kpad (|d_j| + |d_k|), which covers what "+ kpad" covered:
-// hierarchy.cpp, pack_boxes) and kc from its arguments, so a box is 24 bytes.  A never-hit box has extents
+// bounds.h, fold_kpad) and kc from its arguments, so a box is 24 bytes.  A never-hit box has extents
 // -3e38: some axis' right-hand side is then hugely negative (a unit direction has a component >= 0.57).
 // 24 VALU: 3 + 3 (X) + 1 (K) + 3 x 5 + 2.
 // (c, e): a BoxRec -- the centre and the half extents with kpad folded in (mrt_internal.h); kc: the scene's coefficient of X.
@@ -111,7 +111,7 @@ __device__ __forceinline__ bool box_may_touch(const V3 c, const V3 e, const floa
 // power of two changes no rounding.  What the split drops (C_lo v_lo and the remainders: 3 x 2^-18 of
 // every product) and the f32 accumulation err by at most 2.5e-5 o.o + 5e-5 C.C in S; the
 // test gives away 2^-13 = 1.2e-4 of o.o + C.C + R^2: o.o is scaled by 1 - 2^-13 (in mfma_scale[2]) and the host
-// lowers Ck by 2^-13 (C.C + R^2) (hierarchy.cpp, build_top_mfma).  o and C are taken relative to the centre of the
+// lowers Ck by 2^-13 (C.C + R^2) (bounds.h, mfma_row).  o and C are taken relative to the centre of the
 // records' bounding box (P.mfma_origin; the rounding of o - origin is relative to the difference), so the
 // slack does not depend on where the scene sits, only on its extent against R: the host selects this
 // variant only where it is small against R^2; elsewhere the SGPR-fed sweep above runs.
@@ -162,7 +162,7 @@ __device__ __forceinline__ MfmaRay mfma_ray_operands(V3 o, V3 dsk, float o2, flo
     return m;
 }
 // one tile of 32 records against the wave's 64 rays; `a` = this lane's 8 bf16 of the tile's A operand
-// (hierarchy.cpp, build_top_mfma).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
+// (bounds.h, mfma_row).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
 // lane's own ray.
 __device__ __forceinline__ uint32_t mfma_sweep_tile(const u32x4 a, const MfmaRay& m) {
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

@@ -42,6 +42,32 @@ mrt::RefitArgs refit_args(const mrt_ctx* c) {
     return a;
 }
 
+// The device arrays of the scene change (mrt_update_spheres, mrt_regroup_spheres; `who` for the messages): the ctx's stream waits
+// for the render kernels in flight, which read them; later frames wait for ev_inputs (inputs_dirty); the camera masks, which are
+// per cluster slot, are built anew; `change` queues what the call is about (-> 0 or a HIP error) and refit.hip derives
+// everything else behind it, in stream order.  Nothing waits on the host.  The refit's operand is the one for D = I: the scaled
+// sweep space's proof (hierarchy.cpp, scaled_top_records) needs scene statistics only the device now has, so D = I until the next
+// mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack is small against
+// R^2, a speed rule -- the sweep is conservative wherever it runs.  A failure leaves the device arrays between
+// two scenes: the context then has no scene until the next mrt_set_world*.
+template <class F> int change_scene(mrt_ctx* c, const char* who, F&& change) {
+    auto lost = [&](const char* what, hipError_t e) { c->have_world = false; return fail(c, MRT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e)); };
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        mrt_ctx::FrameSlot& S = c->slot[i];
+        if (!S.render_pending) continue;
+        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
+        if (e != hipSuccess) return lost("hipStreamWaitEvent", e);
+    }
+    c->inputs_dirty = true;
+    c->cam_mask_gen++;
+    int le = change();
+    if (le) return lost("launch", (hipError_t)le);
+    c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
+    le = mrt::launch_refit(refit_args(c), c->stream);
+    if (le) return lost("launch", (hipError_t)le);
+    return MRT_OK;
+}
+
 }  // namespace
 
 namespace mrt {
@@ -314,59 +340,39 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
             return fail(c, MRT_ERR_BAD_SCENE, "mrt_update_spheres: sphere %zu: centre/radius not finite or |v| > 1e7", first + i / 4);
     if (count == 0) return MRT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    // from here on a failure leaves the device arrays between two scenes: the context then has no scene until the next mrt_set_world*
-    auto lost = [&](int st) { c->have_world = false; return st; };
-    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
-        mrt_ctx::FrameSlot& S = c->slot[i];
-        if (!S.render_pending) continue;
-        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
-        if (e != hipSuccess) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: hipStreamWaitEvent failed: %s", hipGetErrorString(e)));
-    }
-    c->inputs_dirty = true;
-    c->guides_stale = true;
-    c->cam_mask_gen++;
-    const bool boxed = !mrt::scene_is_small(c->n_members);
-    double reach = c->mfma_reach;
-    float kc = c->box_kc;
-    for (uint32_t b = 0; b < count; b += mrt::kRefitBatch) {
-        mrt::RefitScatterArgs s;
-        s.spheres = c->d_spheres; s.shade = c->d_shade;
-        s.centres = c->d_vec4 + 4 * (size_t)c->world.spheres.center_base_idx;
-        s.radii = c->d_f32 + c->world.spheres.radius_base_idx;
-        s.first = first + b; s.count = std::min(mrt::kRefitBatch, count - b);
-        std::memcpy(s.xyzr, xyzr + 4 * (size_t)b, 16 * (size_t)s.count);
-        const int le = mrt::launch_refit_scatter(s, c->stream);
-        if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
-        // The scene-level kernel arguments, kept valid monotonically from the updated spheres alone: the sweep's reach (D = I
-        // from here on; a reach measured in a scaled space only overstates it), the direct spheres' records, and the box slack's
-        // kc >= 1.3e-6 / the smallest clustered radius (the quadratic form; both forms are valid bounds, so the form stays).
-        for (uint32_t i = 0; i < s.count; i++) {
-            const float* v = s.xyzr + 4 * i;
-            const uint32_t idx = s.first + i;
-            double d2 = 0.0;
-            for (int k = 0; k < 3; k++) { const double d = (double)v[k] - (double)c->mfma_origin[k]; d2 += d * d; }
-            reach = std::max(reach, std::sqrt(d2) + std::fabs((double)v[3]));
-            bool direct = false;
-            for (uint32_t k = 0; k < c->n_direct; k++)
-                if (c->direct_index[k] == idx) { c->direct[k] = mrt::SphereRec{v[0], v[1], v[2], -(v[3] * v[3])}; direct = true; }
-            if (boxed && c->box_quad && !direct) {
-                const double need = 1.3e-6 / std::max(std::fabs((double)v[3]), 1e-30);
-                float f = (float)need;
-                if ((double)f < need) f = std::nextafterf(f, INFINITY);
-                kc = std::max(kc, f);
+    return change_scene(c, "mrt_update_spheres", [&]() -> int {
+        c->guides_stale = true;
+        const bool boxed = !mrt::scene_is_small(c->n_members);
+        double reach = c->mfma_reach;
+        float kc = c->box_kc;
+        for (uint32_t b = 0; b < count; b += mrt::kRefitBatch) {
+            mrt::RefitScatterArgs s;
+            s.spheres = c->d_spheres; s.shade = c->d_shade;
+            s.centres = c->d_vec4 + 4 * (size_t)c->world.spheres.center_base_idx;
+            s.radii = c->d_f32 + c->world.spheres.radius_base_idx;
+            s.first = first + b; s.count = std::min(mrt::kRefitBatch, count - b);
+            std::memcpy(s.xyzr, xyzr + 4 * (size_t)b, 16 * (size_t)s.count);
+            const int le = mrt::launch_refit_scatter(s, c->stream);
+            if (le) return le;
+            // The scene-level kernel arguments, kept valid monotonically from the updated spheres alone: the sweep's reach (D = I
+            // from here on; a reach measured in a scaled space only overstates it), the direct spheres' records, and the box slack's
+            // kc >= quad_kc_for_radius of every clustered sphere (the quadratic form; both forms are valid bounds, so the form stays).
+            for (uint32_t i = 0; i < s.count; i++) {
+                const float* v = s.xyzr + 4 * i;
+                const uint32_t idx = s.first + i;
+                double d2 = 0.0;
+                for (int k = 0; k < 3; k++) { const double d = (double)v[k] - (double)c->mfma_origin[k]; d2 += d * d; }
+                reach = std::max(reach, std::sqrt(d2) + std::fabs((double)v[3]));
+                bool direct = false;
+                for (uint32_t k = 0; k < c->n_direct; k++)
+                    if (c->direct_index[k] == idx) { c->direct[k] = mrt::SphereRec{v[0], v[1], v[2], -(v[3] * v[3])}; direct = true; }
+                if (boxed && c->box_quad && !direct) kc = std::max(kc, mrt::round_up_f32(mrt::quad_kc_for_radius(std::fabs((double)v[3]))));
             }
         }
-    }
-    c->mfma_reach = reach;
-    c->box_kc = kc;
-    // The scaled sweep space's proof (hierarchy.cpp, scaled_top_records) needs scene statistics only the device now has: D = I
-    // until the next mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack
-    // is small against R^2, a speed rule -- the sweep is conservative wherever it runs.
-    c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
-    const mrt::RefitArgs a = refit_args(c);
-    const int le = mrt::launch_refit(a, c->stream);
-    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_update_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
-    return MRT_OK;
+        c->mfma_reach = reach;
+        c->box_kc = kc;
+        return 0;
+    });
 }
 
 // The grouping made anew from the spheres as the device holds them (include/myraytracer_amd.h): regroup.hip permutes the pooled
@@ -377,26 +383,13 @@ int mrt_regroup_spheres(mrt_ctx* c) {
     if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_regroup_spheres: no scene");
     if (c->n_pool <= 1) return MRT_OK;                  // no clustering, or nothing to trade between clusters
     HIP_TRY(c, hipSetDevice(c->device));
-    auto lost = [&](int st) { c->have_world = false; return st; };
-    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
-        mrt_ctx::FrameSlot& S = c->slot[i];
-        if (!S.render_pending) continue;
-        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
-        if (e != hipSuccess) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: hipStreamWaitEvent failed: %s", hipGetErrorString(e)));
-    }
-    c->inputs_dirty = true;                             // (the guides stay current: the geometry did not change)
-    c->cam_mask_gen++;                                  // (the camera masks are per cluster slot)
-    mrt::RegroupArgs g;
-    g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
-    g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
-    mrt::regroup_plan(g.n_pool, g.block, c->regroup_last);
-    int le = mrt::launch_regroup(g, c->stream);
-    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
-    // the refit's operand is the one for D = I, as after an update: a scaled sweep space comes back with the next mrt_set_world*
-    c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
-    le = mrt::launch_refit(refit_args(c), c->stream);
-    if (le) return lost(fail(c, MRT_ERR_HIP, "mrt_regroup_spheres: launch failed: %s", hipGetErrorString((hipError_t)le)));
-    return MRT_OK;
+    return change_scene(c, "mrt_regroup_spheres", [&]() -> int {          // (the guides stay current: the geometry did not change)
+        mrt::RegroupArgs g;
+        g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
+        g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
+        mrt::regroup_plan(g.n_pool, g.block, c->regroup_last);
+        return mrt::launch_regroup(g, c->stream);
+    });
 }
 
 int mrt_debug_regroup_info(mrt_ctx* c, uint32_t out[4]) {

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "myraytracer_amd", "csrc")
 # the host files (scripts/source_hash.py's compiled .cpp files and the headers they share)
 HOST_FILES = ("api.cpp", "frames.cpp", "world.cpp", "noise.cpp", "present.cpp", "denoise.cpp", "multi_gpu.cpp", "hierarchy.cpp",
-              "scenes.cpp", "image_io.cpp", "mrt_ctx.h", "mrt_internal.h", "hierarchy.h", "width_policy.h")
+              "scenes.cpp", "image_io.cpp", "mrt_ctx.h", "mrt_internal.h", "hierarchy.h", "bounds.h", "width_policy.h")
 CREATORS = ("hipMalloc", "hipHostMalloc", "hipStreamCreate", "hipStreamCreateWithFlags", "hipEventCreate", "hipEventCreateWithFlags")
 _CALL = re.compile(r"\b(" + "|".join(sorted(CREATORS, key=len, reverse=True)) + r")\s*\(")
 

@@ -10,8 +10,13 @@ Layouts (the last sphere is a radius-1000 ground, which the builder keeps out of
   small      201 spheres: one level, two tiles of top records, the sweep space the builder chooses for a flat scene
   large-quad 1,100 spheres of one radius, hierarchy forced to (4, 32): three levels, boxes with the quadratic slack
   large-lin  the same with one sphere of radius 1e-4: the linear slack
-  boxes-4200 4,200 spheres: the depth rule's own hierarchy, boxes in use by default"""
+  boxes-4200 4,200 spheres: the depth rule's own hierarchy, boxes in use by default
+  deep-4200  (the hash test only) the same spheres forced to (4, 8): four levels of 1,050, 263, 66 and 17 nodes, the one layout in
+             which the refit's 64-lane kernel takes several member slots a lane"""
 import ctypes as C
+import json
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -23,6 +28,9 @@ from myraytracer_amd import _lib
 from test_gpu_superset import _rays_for
 from test_refit_host import host_hierarchy
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts"))
+from record_hierarchy_hashes import FIXTURE, device_hashes  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 W, H, SPP, DEPTH, SEED = 20, 12, 2, 8, 7
@@ -30,6 +38,9 @@ KEYS = ("samples", "world_hit_calls", "rng_draws")
 MRT_ERR_INVALID_ARG, MRT_ERR_NO_SCENE, MRT_ERR_BAD_SCENE = 1, 4, 5
 LAYOUTS = {"small": (201, None), "large-quad": (1100, (4, 32)), "large-lin": (1100, (4, 32)), "boxes-4200": (4200, None)}
 MOTIONS = ("jitter", "scatter", "radii", "partial", "ground", "around-camera")
+# tests/golden/hierarchy_hashes.json, "device": layout -> (its scene, the forced hierarchy); the cases as (layout, motion)
+HASH_LAYOUTS = {"small": ("small", None), "large-quad": ("large-quad", (4, 32)), "large-lin": ("large-lin", (4, 32)), "deep-4200": ("boxes-4200", (4, 8))}
+HASH_CASES = [(name, which) for name in HASH_LAYOUTS for which in ("jitter", "radii", "ground")] + [("large-quad", "scatter+regroup")]
 
 
 def camera(mrt):
@@ -110,6 +121,25 @@ def state(mrt, name, sc, rng_mode=0, **kw):
     if rng_mode:
         st.set_rng_mode(rng_mode)
     return st
+
+
+def refitted_hierarchy(mrt, name, which):
+    """mrt_debug_read_hierarchy after the motion `which` of the hash layout `name` ("+regroup": and mrt_regroup_spheres)"""
+    base, forced = HASH_LAYOUTS[name]
+    sc = scene(mrt, base)
+    first, upd, sc_new = motion(mrt, sc, which.split("+")[0])
+    with mrt.State(mrt.Args(W, H, SPP, DEPTH, 1.0), seed=SEED) as st:
+        if forced:
+            st.debug_set_hierarchy(*forced)
+        st.set_world(sc)
+        st.update_spheres(first, upd)
+        if which.endswith("+regroup"):
+            st.regroup_spheres()
+        h = st.debug_read_hierarchy()
+    if name == "deep-4200":
+        assert h["levels"] == 4
+        R.check(h, R.xyzr_of(sc_new))
+    return h
 
 
 _oracle_cache = {}
@@ -193,6 +223,18 @@ def test_a_motion_refits_the_hierarchy_and_renders_the_updated_scene(mrt, oracle
         got, counters = st.read_framebuffer(), st.read_counters()
     ref, ref_counters = oracle_frames(oracle, mrt, (name, which), [sc_new], rng_mode)
     assert_same(got, counters, ref, ref_counters, f"{name}, {which}")   # the oracle second
+
+
+@pytest.mark.parametrize("name,which", HASH_CASES, ids=[f"{n}-{w}" for n, w in HASH_CASES])
+def test_the_refitted_arrays_hash_to_the_recorded_ones(mrt, name, which):
+    """every array and scalar the device holds after the call, bit for bit, against the build the fixture was recorded from
+    (scripts/record_hierarchy_hashes.py): a change that means to leave the refit's arithmetic alone did.  deep-4200 also passes
+    the float64 checker."""
+    want = json.load(open(FIXTURE))["device"]["hashes"][f"{name}|{which}"]
+    got = device_hashes(refitted_hierarchy(mrt, name, which))
+    assert got.keys() == want.keys()
+    differ = sorted(k for k in got if got[k] != want[k])
+    assert not differ, f"{name}, {which}: {differ} differ from the recorded build"
 
 
 @pytest.mark.parametrize("sweep", [1, 2], ids=["valu-sweep", "matrix-core-sweep"])
