@@ -43,7 +43,8 @@ extern "C" {
  * adaptive sampling (mrt_render_tiles, mrt_render_adaptive, mrt_read_tile_frames); temporal reprojection (mrt_temporal_params,
  * mrt_temporal_params_default, mrt_set_temporal, mrt_get_temporal, mrt_temporal_step, mrt_temporal_reset, mrt_read_temporal,
  * MRT_PRESENT_TEMPORAL); the temporal response (mrt_temporal_response, mrt_temporal_response_default,
- * mrt_set_temporal_response, mrt_get_temporal_response). */
+ * mrt_set_temporal_response, mrt_get_temporal_response); the noise estimate across shards and the gathered frame's denoise
+ * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -365,6 +366,8 @@ enum {
 #define MRT_PRESENT_DENOISED 8u
 /* the temporal image (mrt_read_temporal's; "temporal reprojection" below), not the framebuffer itself */
 #define MRT_PRESENT_TEMPORAL 16u
+/* the latest gathered frame, denoised on the root (mrt_read_gathered_denoised's image; "multi-GPU" below) */
+#define MRT_PRESENT_GATHERED_DENOISED 32u
 enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
 typedef struct {               /* 40 bytes */
     uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
@@ -376,12 +379,15 @@ typedef struct {               /* 40 bytes */
 } mrt_present_info;
 /* Queues the present of the most recent frame (after mrt_render(k): its last frame) on the ctx's stream, behind that frame's
  * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB; flags: MRT_PRESENT_FLIP_Y |
- * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
+ * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL | MRT_PRESENT_GATHERED_DENOISED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
  * local rows in mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full
  * frame (MRT_ERR_STATE before the first gather); DENOISED, the `height` rows of the denoised frame, queued on the same stream
  * right before the encode (the guide rebuild if the guides are stale, then the filter; refusals as mrt_read_denoised's, and
  * DENOISED | GATHERED: MRT_ERR_INVALID_ARG); TEMPORAL, the `height` rows of the temporal image, queued the same way (refusals as
- * mrt_read_temporal's; TEMPORAL | DENOISED and TEMPORAL | GATHERED: MRT_ERR_INVALID_ARG).  Must not be called while the ctx's stream is being captured into a graph. */
+ * mrt_read_temporal's; TEMPORAL | DENOISED and TEMPORAL | GATHERED: MRT_ERR_INVALID_ARG); GATHERED_DENOISED, the `height` rows of
+ * the latest gathered frame denoised on the root, queued the same way (refusals as mrt_read_gathered_denoised's; with FLIP_Y only:
+ * together with GATHERED, DENOISED or TEMPORAL it is MRT_ERR_INVALID_ARG; mrt_present_info::frames_done is then the gather's).
+ * Must not be called while the ctx's stream is being captured into a graph. */
 int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
 /* A finished image: *pixels = rows x row_bytes bytes, valid until mrt_present_release, the next acquire, mrt_reset,
  * mrt_set_shard or mrt_destroy.  MRT_ACQUIRE_NEWEST (a viewer, mailbox): the most recent finished image; older finished ones are
@@ -714,6 +720,43 @@ int mrt_gather_rccl(mrt_ctx* ctx, void* nccl_comm, uint32_t root);
  * everything queued on the root's stream before it, so an asynchronous reader queued there is never overtaken). */
 void* mrt_gathered_device_ptr(mrt_ctx* root_ctx);
 int mrt_read_gathered(mrt_ctx* root_ctx, float* rgba_out, size_t cap_floats);   /* synchronises */
+
+/* ---- the noise estimate across shards: a denoised preview of the gathered frame ----
+ * A shard tracks S for its own rows (mrt_set_noise_tracking), bit for bit the unsharded context's; every shard holds the same
+ * scene and camera.  With this setting on, a gather also assembles the full-frame S on the root, and the root can build the
+ * guides of the full image and run the denoiser on (gathered colour, gathered S, K, guides) -- the layout of world == 1.  The
+ * shards' own mrt_read_denoised / MRT_PRESENT_DENOISED stay refused (MRT_ERR_STATE), and MRT_PRESENT_DENOISED |
+ * MRT_PRESENT_GATHERED stays MRT_ERR_INVALID_ARG.
+ *
+ * mrt_set_gather_noise(ctx, enabled): default 0, and with 0 both gathers queue exactly the calls and bytes they always have.
+ * Creates nothing; takes effect at the next gather; a CHANGE of the setting drops the gathered S until then (the reads below:
+ * MRT_ERR_STATE), as mrt_set_shard does, and the first gather after a change allocates the gathered frame anew, S included or
+ * not (it waits for the root's stream first; mrt_gathered_device_ptr changes).  ctx NULL: MRT_ERR_INVALID_ARG.  mrt_gather reads the ROOT's setting.
+ * mrt_gather_rccl reads each rank's own, and all ranks must agree: a disagreement is the caller's error, like a disagreeing
+ * `root` (the messages no longer match; nothing in this library can detect it).
+ *   With the setting on, mrt_gather also copies every shard's S bands into their places of a full-frame S on the root (in the
+ * allocation of the gathered colour, behind it: mrt_gathered_device_ptr means what it meant), on the same streams, behind the
+ * same events and under the same write-after-read rule as the colour.  Refused with MRT_ERR_STATE on the root, before anything
+ * is queued and with a message that names the context: a context with noise tracking off, one whose accumulation is adaptive
+ * (mrt_render_tiles since its last reset), one whose mrt_frames_done or max_framebuffer_weight differs from the root's (ONE K
+ * turns the frame's S into a variance).  mrt_gather_rccl: a non-root rank sends S as a second message in the same call; the
+ * root receives both in its one group and un-permutes both (a rank with noise tracking off: MRT_ERR_STATE on that rank).
+ *   The snapshot: at such a gather the root records K = mrt_noise_factor of ITS accumulation and its mrt_frames_done.  The
+ * gathered frame is denoised with that snapshot, whatever the root renders between the gather and the denoise.
+ *
+ * mrt_read_gathered_noise: the gathered S, height * width floats, row 0 = bottom; synchronises as mrt_read_gathered does.
+ * MRT_ERR_STATE before the first gather and when the latest gather carried no S; MRT_ERR_TOO_SMALL.
+ * mrt_read_gathered_denoised: the latest gathered frame, denoised: height * width * 4 floats, row 0 = bottom.  Queues, on the
+ * root's stream behind the gather's waits, the guide rebuild if the guides are stale (the root's CURRENT camera and scene over
+ * the full image; mrt_set_camera, mrt_set_world*, mrt_update_spheres and mrt_set_shard mark them stale, as for
+ * mrt_read_denoised) and the filter with the root's mrt_denoise_params and variance mode -- MRT_DENOISE_VAR_SPATIAL_EARLY
+ * compares the SNAPSHOT's frame count with spatial_frames; the read-back is the only host wait.  Refusals: MRT_ERR_STATE as
+ * mrt_read_gathered_noise's, MRT_ERR_NO_SCENE without a scene, MRT_ERR_TOO_SMALL.  The denoiser's buffers are allocated on the
+ * root at the first use, full-image sized, as mrt_read_denoised's are.  Works for world == 1 too (a gather of one): the image
+ * is then mrt_read_denoised's, bit for bit -- as it is for any world, since the shards' rows and S are the unsharded ones. */
+int mrt_set_gather_noise(mrt_ctx* ctx, int enabled);
+int mrt_read_gathered_noise(mrt_ctx* root_ctx, float* s_out, size_t cap_floats);              /* synchronises */
+int mrt_read_gathered_denoised(mrt_ctx* root_ctx, float* rgba_out, size_t cap_floats);        /* synchronises */
 /* host-only index math of the interleave: local row r of shard (rank, world) is this global row; rows per
  * shard; and the un-permute of a rank-major [world][local_rows][width][4] array into [height][width][4] */
 uint32_t mrt_shard_global_row(uint32_t local_row, uint32_t rank, uint32_t world);

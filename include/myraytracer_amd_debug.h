@@ -45,6 +45,10 @@ int mrt_debug_denoise_variance(mrt_ctx* ctx, const float* rgba, const float* S, 
  * direction), index 1 int32, t 1 float, normal 3 floats, albedo 3 floats per pixel; any pointer may be NULL.  cap_pixels >=
  * width * height.  Synchronous.  MRT_ERR_STATE on a shard, MRT_ERR_NO_SCENE without a scene. */
 int mrt_debug_read_guides(mrt_ctx* ctx, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap_pixels);
+/* Diagnostic: the same records of the guides mrt_read_gathered_denoised filters with -- the root's current camera and scene over
+ * the FULL image, on a root that is a shard too (where mrt_debug_read_guides stays refused).  Its checks are
+ * mrt_read_gathered_denoised's without the need for a gathered S: MRT_ERR_NO_SCENE without a scene, MRT_ERR_TOO_SMALL. */
+int mrt_debug_read_gathered_guides(mrt_ctx* root_ctx, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap_pixels);
 
 /* Diagnostic: make mrt_gather on this root use the cross-device form of the copy (one hipMemcpyPeerAsync per
  * band) even when a shard shares the root's device, so that its indexing runs on a one-GPU box. */

@@ -52,11 +52,12 @@ EXPORTS = [
     "mrt_read_temporal", "mrt_debug_read_temporal", "mrt_debug_load_temporal",
     "mrt_temporal_response_default", "mrt_set_temporal_response", "mrt_get_temporal_response",
     "mrt_debug_read_temporal_fast", "mrt_debug_load_temporal_fast",
+    "mrt_set_gather_noise", "mrt_read_gathered_noise", "mrt_read_gathered_denoised", "mrt_debug_read_gathered_guides",
 ]
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
-PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED, PRESENT_TEMPORAL = 1, 2, 8, 16
+PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED, PRESENT_TEMPORAL, PRESENT_GATHERED_DENOISED = 1, 2, 8, 16, 32
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 # how a slot's tile queue was ordered (mrt_debug_read_tile_schedule, MRT_TILE_ORDER_*)
 TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
@@ -374,6 +375,10 @@ def load():
         "mrt_get_temporal_response": (i32, [vp, P(MrtTemporalResponse)]),
         "mrt_debug_read_temporal_fast": (i32, [vp, vp, sz]),
         "mrt_debug_load_temporal_fast": (i32, [vp, vp]),
+        "mrt_set_gather_noise": (i32, [vp, i32]),
+        "mrt_read_gathered_noise": (i32, [vp, vp, sz]),
+        "mrt_read_gathered_denoised": (i32, [vp, vp, sz]),
+        "mrt_debug_read_gathered_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

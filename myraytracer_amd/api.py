@@ -617,18 +617,52 @@ class State:
         self._check(self._L.mrt_read_gathered(self._ctx, out.ctypes.data, out.size), "mrt_read_gathered")
         return out
 
+    # -- the noise estimate across shards (include/myraytracer_amd.h, "the noise estimate across shards"): S travels with the
+    #    gather and the root denoises the gathered frame
+    def set_gather_noise(self, enabled: bool):
+        """mrt_set_gather_noise: from the next gather on, S travels with the colour (gather(): the root's setting decides;
+        gather_rccl(): every rank's own, and all must agree).  A change drops the gathered S until the next gather."""
+        self._check(self._L.mrt_set_gather_noise(self._ctx, int(enabled)), "mrt_set_gather_noise")
+
+    def read_gathered_noise(self) -> np.ndarray:
+        """(H, W) f32, row 0 = bottom: the full-frame S assembled on this (root) State by the last gather."""
+        out = np.empty((self.args.height, self.args.width), np.float32)
+        self._check(self._L.mrt_read_gathered_noise(self._ctx, out.ctypes.data, out.size), "mrt_read_gathered_noise")
+        return out
+
+    def read_gathered_denoised(self) -> np.ndarray:
+        """(H, W, 4) f32, row 0 = bottom: the last gathered frame, denoised on this (root) State with the gather's snapshot of
+        K and the frame count and the guides of this State's current camera and scene."""
+        out = np.empty((self.args.height, self.args.width, 4), np.float32)
+        self._check(self._L.mrt_read_gathered_denoised(self._ctx, out.ctypes.data, out.size), "mrt_read_gathered_denoised")
+        return out
+
+    def debug_read_gathered_guides(self) -> dict:
+        """debug_read_guides' dict of the guides read_gathered_denoised filters with: the full image's, on a root that is a
+        shard too."""
+        h, w = self.args.height, self.args.width
+        g = {"rays": np.empty((h, w, 6), np.float32), "index": np.empty((h, w), np.int32), "t": np.empty((h, w), np.float32),
+             "normal": np.empty((h, w, 3), np.float32), "albedo": np.empty((h, w, 3), np.float32)}
+        self._check(self._L.mrt_debug_read_gathered_guides(self._ctx, g["rays"].ctypes.data, g["index"].ctypes.data, g["t"].ctypes.data,
+                                                           g["normal"].ctypes.data, g["albedo"].ctypes.data, h * w),
+                    "mrt_debug_read_gathered_guides")
+        return g
+
     # -- present pass (the reference's pass 2, lib.rs:270-297 / sample_framebuffer.wgsl): 8-bit sRGB images, read back without
     #    waiting for the frames in flight
     _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB}
 
-    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False, temporal: bool = False):
+    def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False, temporal: bool = False,
+                gathered_denoised: bool = False):
         """mrt_present: queue the most recent frame's 8-bit sRGB image ("rgba8" / "bgra8"; flip = rows top-down; gathered = the
         root's full frame of the last gather; denoise = the denoised frame, read_denoised's image; temporal = the temporal image,
-        read_temporal's).  Asynchronous."""
+        read_temporal's; gathered_denoised = the last gathered frame denoised on the root, read_gathered_denoised's image, a
+        source of its own: with flip only).  Asynchronous."""
         if fmt not in self._PRESENT_FORMATS:
             raise ValueError(f"present: format {fmt!r} (rgba8, bgra8)")
         flags = ((_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0) |
-                 (_lib.PRESENT_DENOISED if denoise else 0) | (_lib.PRESENT_TEMPORAL if temporal else 0))
+                 (_lib.PRESENT_DENOISED if denoise else 0) | (_lib.PRESENT_TEMPORAL if temporal else 0) |
+                 (_lib.PRESENT_GATHERED_DENOISED if gathered_denoised else 0))
         self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
 
     def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):

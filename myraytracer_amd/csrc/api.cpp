@@ -190,6 +190,7 @@ int alloc_frame_buffers(mrt_ctx* c, uint32_t rank, uint32_t world) {
         return st;
     }
     free_frame_buffers(c);
+    c->gather_has_s = false;            // (a gathered S was another shard layout's; the gathered colour stays readable, as before)
     c->shard_rank = rank; c->shard_world = world;
     c->local_bands = local_bands;
     c->cam_mask_gen++;                  // (the camera masks are per texel of the shard)
@@ -849,6 +850,8 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
     if (!c->present_ring.empty() && (c->present_entry_bytes == 0 || !c->d_present_tables)) return check_finding(why, cap, "a present ring without entry size or tables");
     if (!c->guides_stale && (!c->d_guides || !c->d_guide_rays || !c->d_guide_hits || !c->d_guide_queue || !c->d_guide_cand || !c->d_den[0] || !c->d_den[1] || !c->d_den[2]))
         return check_finding(why, cap, "the guides are marked current without the denoiser's buffers");
+    if (c->gather_has_s && (!c->d_gather || c->gather_bytes < mrt::gathered_colour_bytes(c) + mrt::gathered_colour_bytes(c) / 4))
+        return check_finding(why, cap, "a gathered S is marked readable in a gathered frame of %zu bytes (%zu of colour)", c->gather_bytes, mrt::gathered_colour_bytes(c));
     if (c->temporal_on && c->shard_world != 1) return check_finding(why, cap, "temporal reprojection is on on shard %u of %u", c->shard_rank, c->shard_world);
     if (c->temporal_cur > 1) return check_finding(why, cap, "temporal history pair %u", c->temporal_cur);
     if (c->temporal_stepped && (!c->temporal_on || c->temporal_clear || !c->have_world || !c->d_guides || !c->d_den[0] || !c->d_den[1] || !c->d_den[2] ||

@@ -71,7 +71,11 @@ int ensure_denoise_buffers(mrt_ctx* c) {
     return MRT_OK;
 }
 
-// the guides of the current camera and scene, queued on the ctx's stream
+// The guides of the current camera and scene, queued on the ctx's stream: always over the FULL image.  On a shard (the root of
+// a gather, mrt_read_gathered_denoised) the ctx's own tile count and seed texture are its bands' alone, so the pass gets the full
+// image's tile count and, for the seed texel the kernel loads for every pixel it acquires (and, in this instantiation, never
+// uses), the filter's ping buffer: width x height 16-byte texels, idle here -- the filter that writes it is queued behind this
+// pass on the same stream, and the previous one before it.
 int rebuild_guides(mrt_ctx* c) {
     const uint32_t W = c->args.width, H = c->args.height;
     int e = mrt::launch_guide_rays(c->d_guide_rays, W, H, c->cam_raw, c->stream);
@@ -84,8 +88,9 @@ int rebuild_guides(mrt_ctx* c) {
     p.locals.samples_per_frame = 1; p.locals.ray_depth = 1;
     fill_scene_params(c, p);
     p.shard_rank = 0; p.shard_world = 1;
-    p.seeds = c->d_seeds;
-    p.tiles_x = c->tiles_x; p.n_tiles = c->n_tiles;
+    const bool shard = c->shard_world != 1;
+    p.seeds = shard ? reinterpret_cast<const uint32_t*>(c->d_den[0]) : c->d_seeds;
+    p.tiles_x = c->tiles_x; p.n_tiles = shard ? c->tiles_x * mrt::total_bands(H) : c->n_tiles;
     p.tile_queue = c->d_guide_queue;
     p.n_blocks = 1; p.pix_stride = 0; p.queue_layers = 1; p.lane_frames = 1;
     p.dbg_rays = c->d_guide_rays; p.dbg_hit = c->d_guide_hits;
@@ -123,6 +128,25 @@ uint32_t variance_of(uint32_t mode, uint32_t frames_done, uint32_t spatial_frame
     return mode == MRT_DENOISE_VAR_PREFILTERED ? 1u : 0u;
 }
 
+// The refusals of the gathered frame's guides and denoise: denoise_check's for a frame that lives on a shard's root (`tracking`:
+// the filter's -- a gathered S; the guides alone need none).
+int gathered_denoise_check(mrt_ctx* c, const char* who, bool tracking) {
+    if (tracking) MRT_TRY(mrt::gathered_noise_check(c, who));
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
+    if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
+    return MRT_OK;
+}
+
+// the latest gathered frame, denoised into d_den[2] with the gather's snapshot of K and the frame count (after gathered_denoise_check)
+int queue_gathered_denoise(mrt_ctx* c) {
+    MRT_TRY(ensure_guides(c));
+    const uint32_t variance = variance_of(c->denoise_var_mode, c->gather_frames, c->denoise_spatial_frames);
+    const int e = mrt::launch_denoise(c->d_gather, mrt::gathered_noise(c), (float)c->gather_k, c->d_guides, c->d_den[0], c->d_den[1],
+                                      c->d_den[2], c->args.width, c->args.height, c->denoise, variance, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
 // the most recent frame, denoised into d_den[2] (after denoise_check)
 int queue_denoise(mrt_ctx* c) {
     MRT_TRY(ensure_guides(c));
@@ -131,6 +155,26 @@ int queue_denoise(mrt_ctx* c) {
     const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, K, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
                                       c->args.width, c->args.height, c->denoise, variance, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
+// the guides (rebuilt first if stale) read back and split into their fields, after the caller's checks
+int read_guides(mrt_ctx* c, const char* who, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap) {
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "%s: need %zu pixels", who, n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(ensure_guides(c));
+    std::vector<float> g(n * 8);
+    if (rays) HIP_TRY(c, hipMemcpyAsync(rays, c->d_guide_rays, n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(g.data(), c->d_guides, n * 32, hipMemcpyDeviceToHost, c->stream));
+    MRT_TRY(mrt::wait_stream(c, c->stream, who));
+    for (size_t i = 0; i < n; i++) {
+        const float* r = g.data() + 8 * i;
+        if (index) std::memcpy(index + i, r + 7, 4);
+        if (t) t[i] = r[3];
+        if (normal) std::memcpy(normal + 3 * i, r, 12);
+        if (albedo) std::memcpy(albedo + 3 * i, r + 4, 12);
+    }
     return MRT_OK;
 }
 
@@ -222,6 +266,12 @@ int present_denoised(mrt_ctx* c, const float** src) {
     return MRT_OK;
 }
 int present_denoised_check(mrt_ctx* c) { return denoise_check(c, "mrt_present", true); }
+int present_gathered_denoised_check(mrt_ctx* c) { return gathered_denoise_check(c, "mrt_present", true); }
+int present_gathered_denoised(mrt_ctx* c, const float** src) {
+    MRT_TRY(queue_gathered_denoise(c));
+    *src = c->d_den[2];
+    return MRT_OK;
+}
 }  // namespace mrt
 
 extern "C" {
@@ -269,6 +319,17 @@ int mrt_read_denoised(mrt_ctx* c, float* out, size_t cap) {
     if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_denoised: need %zu floats", n);
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(queue_denoise(c));
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, __func__);
+}
+
+int mrt_read_gathered_denoised(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(gathered_denoise_check(c, "mrt_read_gathered_denoised", true));
+    const size_t n = (size_t)c->args.width * c->args.height * 4;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_gathered_denoised: need %zu floats", n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(queue_gathered_denoise(c));
     HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return mrt::wait_stream(c, c->stream, __func__);
 }
@@ -451,22 +512,13 @@ int mrt_debug_load_temporal_fast(mrt_ctx* c, const float* h2) {
 int mrt_debug_read_guides(mrt_ctx* c, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap) {
     if (!c) return MRT_ERR_INVALID_ARG;
     MRT_TRY(denoise_check(c, "mrt_debug_read_guides", false));
-    const size_t n = (size_t)c->args.width * c->args.height;
-    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_guides: need %zu pixels", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    MRT_TRY(ensure_guides(c));
-    std::vector<float> g(n * 8);
-    if (rays) HIP_TRY(c, hipMemcpyAsync(rays, c->d_guide_rays, n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(g.data(), c->d_guides, n * 32, hipMemcpyDeviceToHost, c->stream));
-    MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
-    for (size_t i = 0; i < n; i++) {
-        const float* r = g.data() + 8 * i;
-        if (index) std::memcpy(index + i, r + 7, 4);
-        if (t) t[i] = r[3];
-        if (normal) std::memcpy(normal + 3 * i, r, 12);
-        if (albedo) std::memcpy(albedo + 3 * i, r + 4, 12);
-    }
-    return MRT_OK;
+    return read_guides(c, "mrt_debug_read_guides", rays, index, t, normal, albedo, cap);
+}
+
+int mrt_debug_read_gathered_guides(mrt_ctx* c, float* rays, int32_t* index, float* t, float* normal, float* albedo, size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(gathered_denoise_check(c, "mrt_debug_read_gathered_guides", false));
+    return read_guides(c, "mrt_debug_read_gathered_guides", rays, index, t, normal, albedo, cap);
 }
 
 int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,

@@ -182,6 +182,13 @@ struct mrt_ctx {
     // d_gather among it -- which every shard's stream waits for before it overwrites d_gather (write-after-read)
     hipEvent_t ev_gather_root = nullptr;
     bool gather_per_band = false;              // mrt_debug_set_gather_per_band: the cross-device copy loop on one device
+    // the noise estimate across shards (mrt_set_gather_noise): with the setting on a gather also assembles the full-frame S,
+    // height x width floats in the SAME allocation right behind the colour (gathered_noise()), and records the root's K and
+    // frame count as they are then -- what mrt_read_gathered_denoised filters with, whatever the root renders afterwards.
+    // gather_has_s: the latest gather carried S and nothing since (mrt_set_shard, a toggle of the setting) took it away.
+    bool gather_noise = false, gather_has_s = false;
+    double gather_k = 0.0;
+    uint32_t gather_frames = 0;
 
     // present pass (mrt_present, present.cpp): a ring of images, each the present kernel's output on the device, its copy in pinned
     // host memory and the event that says the copy has landed.  An entry is free, queued (presented, not acquired: its copy may
@@ -304,6 +311,9 @@ inline size_t local_texels(const mrt_ctx* c) { return (size_t)c->local_bands * k
 // ... at least 1: the size of an allocation that an empty shard makes all the same
 inline size_t local_texels_min1(const mrt_ctx* c) { return local_texels(c) ? local_texels(c) : 1; }
 inline uint32_t tiles_min1(const mrt_ctx* c) { return c->n_tiles ? c->n_tiles : 1; }
+// the root's gathered frame (multi_gpu.cpp): the colour's bytes -- every shard's bands, padding included -- and S behind them
+inline size_t gathered_colour_bytes(const mrt_ctx* c) { return local_texels(c) * c->shard_world * 4 * sizeof(float); }
+inline float* gathered_noise(const mrt_ctx* c) { return c->d_gather + gathered_colour_bytes(c) / sizeof(float); }
 
 // free device / pinned allocations (those there are) and forget them
 template <typename... T> void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
@@ -342,6 +352,11 @@ int present_denoised(mrt_ctx* c, const float** src);
 int present_temporal_check(mrt_ctx* c);
 int present_temporal(mrt_ctx* c, const float** src);
 void drop_temporal_history(mrt_ctx* c);
+// ... and for the gathered frame's denoise (mrt_read_gathered_denoised's refusals; the guides over the full image, then the filter)
+// (multi_gpu.cpp: is there a gathered S -- MRT_ERR_STATE before the first gather and when the latest carried none)
+int gathered_noise_check(mrt_ctx* R, const char* who);
+int present_gathered_denoised_check(mrt_ctx* c);
+int present_gathered_denoised(mrt_ctx* c, const float** src);
 
 }  // namespace mrt
 

@@ -27,9 +27,12 @@ namespace {
 
 size_t band_bytes(const mrt_ctx* c) { return (size_t)mrt::kBandRows * c->args.width * 4 * sizeof(float); }
 
-// the root's full-frame buffer: local_bands * world bands (the tail beyond `height` rows is shard padding)
+// the root's full-frame buffer: local_bands * world bands (the tail beyond `height` rows is shard padding); with
+// mrt_set_gather_noise on, the same bands of S -- a float per texel, a quarter of the colour's bytes -- behind the colour in the
+// same allocation (mrt::gathered_noise)
 int ensure_gather_buffer(mrt_ctx* R) {
-    const size_t need = band_bytes(R) * R->local_bands * R->shard_world;
+    const size_t colour = band_bytes(R) * R->local_bands * R->shard_world;
+    const size_t need = colour + (R->gather_noise ? colour / 4 : 0);
     if (R->d_gather && R->gather_bytes == need) return MRT_OK;
     HIP_TRY(R, hipSetDevice(R->device));
     if (R->d_gather) { MRT_TRY(mrt::wait_stream(R, R->stream, __func__)); (void)hipFree(R->d_gather); R->d_gather = nullptr; }
@@ -103,7 +106,25 @@ const Rccl& rccl() {
     return r;
 }
 
+// the root's K and frame count as they are at a gather that carried S: what the gathered frame is denoised with
+void snapshot_noise(mrt_ctx* R) {
+    R->gather_k = mrt::noise_factor_of(R->noise_c2);
+    R->gather_frames = R->frames_done;
+    R->gather_has_s = true;
+}
+
 }  // namespace
+
+namespace mrt {
+// the refusals of every read of the gathered S
+int gathered_noise_check(mrt_ctx* R, const char* who) {
+    if (!R->d_gather) return fail(R, MRT_ERR_STATE, "%s: nothing gathered yet (mrt_gather / mrt_gather_rccl on the root)", who);
+    if (!R->gather_has_s)
+        return fail(R, MRT_ERR_STATE, "%s: the latest gather carried no S (mrt_set_gather_noise before the gather; mrt_set_shard and a "
+                    "change of the setting drop it)", who);
+    return MRT_OK;
+}
+}  // namespace mrt
 
 extern "C" {
 
@@ -143,6 +164,23 @@ int mrt_gather(mrt_ctx* const* ctxs, uint32_t n, uint32_t root) {
             return fail(R, MRT_ERR_STATE, "mrt_gather: ctxs[%u] renders %ux%u, the root %ux%u", i, c->args.width, c->args.height,
                         R->args.width, R->args.height);
     }
+    // S travels with the colour (the root's setting decides): every shard must have one, of the same accumulation as the root's,
+    // since the ONE K of the root's snapshot turns all of it into a variance
+    const bool with_s = R->gather_noise;
+    for (uint32_t i = 0; with_s && i < n; i++) {
+        const mrt_ctx* c = ctxs[i];
+        if (!c->noise_on || !c->d_noise_s)
+            return fail(R, MRT_ERR_STATE, "mrt_gather: ctxs[%u] has noise tracking off (mrt_set_noise_tracking), mrt_set_gather_noise is on", i);
+        if (c->tiles_diverged)
+            return fail(R, MRT_ERR_STATE, "mrt_gather: ctxs[%u]'s accumulation is adaptive (one K per tile), mrt_set_gather_noise is on", i);
+        if (c->frames_done != R->frames_done)
+            return fail(R, MRT_ERR_STATE, "mrt_gather: ctxs[%u] has %u frames done, the root %u (mrt_set_gather_noise: one K for the frame)", i,
+                        c->frames_done, R->frames_done);
+        if (c->args.max_framebuffer_weight != R->args.max_framebuffer_weight)
+            return fail(R, MRT_ERR_STATE, "mrt_gather: ctxs[%u] has max_framebuffer_weight %g, the root %g (mrt_set_gather_noise: one K for the frame)",
+                        i, (double)c->args.max_framebuffer_weight, (double)R->args.max_framebuffer_weight);
+    }
+    R->gather_has_s = false;
     int st = ensure_gather_buffer(R);
     if (st != MRT_OK) return st;
     const size_t bb = band_bytes(R);
@@ -165,11 +203,15 @@ int mrt_gather(mrt_ctx* const* ctxs, uint32_t n, uint32_t root) {
         // on the SOURCE's stream, i.e. after its finalize pass; the root's stream then waits for every shard
         const float* src = c->d_fb[c->target ^ 1];
         HIP_TRY(R, scatter_bands(R->d_gather, R->device, src, c->device, i, n, c->local_bands, bb, c->stream, R->gather_per_band));
+        if (with_s)     // (S is updated in place by the shard's blends, on this very stream: the copy sits between two of them)
+            HIP_TRY(R, scatter_bands(mrt::gathered_noise(R), R->device, c->d_noise_s, c->device, i, n, c->local_bands, bb / 4, c->stream,
+                                     R->gather_per_band));
         HIP_TRY(R, hipEventRecord(c->ev_gather, c->stream));
     }
     HIP_TRY(R, hipSetDevice(R->device));
     for (uint32_t i = 0; i < n; i++)
         if (ctxs[i] != R) HIP_TRY(R, hipStreamWaitEvent(R->stream, ctxs[i]->ev_gather, 0));
+    if (with_s) snapshot_noise(R);
     return MRT_OK;
 }
 
@@ -183,8 +225,13 @@ int mrt_gather_rccl(mrt_ctx* c, void* nccl_comm, uint32_t root) {
     if (N.comm_rank(nccl_comm, &crank) != 0 || N.comm_count(nccl_comm, &ccount) != 0 || crank != (int)rank || ccount != (int)world)
         return fail(c, MRT_ERR_STATE, "mrt_gather_rccl: communicator is rank %d of %d, the context is shard %u of %u", crank, ccount,
                     rank, world);
+    const bool with_s = c->gather_noise;        // (this rank's own setting: all ranks must agree, as on `root`)
+    if (with_s && (!c->noise_on || !c->d_noise_s))
+        return fail(c, MRT_ERR_STATE, "mrt_gather_rccl: shard %u has noise tracking off (mrt_set_noise_tracking), mrt_set_gather_noise is on", rank);
+    if (with_s && c->tiles_diverged)
+        return fail(c, MRT_ERR_STATE, "mrt_gather_rccl: shard %u's accumulation is adaptive (one K per tile), mrt_set_gather_noise is on", rank);
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t local_floats = mrt::local_texels(c) * 4;
+    const size_t local_floats = mrt::local_texels(c) * 4, local_s = mrt::local_texels(c);
     const float* src = c->d_fb[c->target ^ 1];
     auto nccl_try = [&](int r, const char* what) -> int {
         if (r == 0) return MRT_OK;
@@ -193,10 +240,18 @@ int mrt_gather_rccl(mrt_ctx* c, void* nccl_comm, uint32_t root) {
     int st;
     if (rank != root) {
         // one message straight to the root over this GPU's own xGMI link
-        return nccl_try(N.send(const_cast<float*>(src), local_floats, kNcclFloat, (int)root, nccl_comm, c->stream), "ncclSend");
+        if (!with_s) return nccl_try(N.send(const_cast<float*>(src), local_floats, kNcclFloat, (int)root, nccl_comm, c->stream), "ncclSend");
+        // ... and S as a second one behind it, in the order the root posts its receives
+        if ((st = nccl_try(N.group_start(), "ncclGroupStart")) != MRT_OK) return st;
+        st = nccl_try(N.send(const_cast<float*>(src), local_floats, kNcclFloat, (int)root, nccl_comm, c->stream), "ncclSend");
+        if (st == MRT_OK) st = nccl_try(N.send(c->d_noise_s, local_s, kNcclFloat, (int)root, nccl_comm, c->stream), "ncclSend");
+        if (st != MRT_OK) { (void)N.group_end(); return st; }
+        return nccl_try(N.group_end(), "ncclGroupEnd");
     }
+    c->gather_has_s = false;
     if ((st = ensure_gather_buffer(c)) != MRT_OK) return st;
-    const size_t stage_need = local_floats * sizeof(float) * world;
+    // rank-major: every rank's colour, then (with S) every rank's S
+    const size_t stage_need = (local_floats + (with_s ? local_s : 0)) * sizeof(float) * world;
     if (!c->d_gather_stage || c->gather_stage_bytes != stage_need) {
         if (c->d_gather_stage) { MRT_TRY(mrt::wait_stream(c, c->stream, __func__)); (void)hipFree(c->d_gather_stage); c->d_gather_stage = nullptr; }
         HIP_TRY(c, hipMalloc((void**)&c->d_gather_stage, stage_need ? stage_need : 16));
@@ -204,10 +259,13 @@ int mrt_gather_rccl(mrt_ctx* c, void* nccl_comm, uint32_t root) {
     }
     // (no write-after-read hazard here: the receives into the staging buffer and the un-permute into d_gather are all on the
     // context's own stream, i.e. behind whatever the caller queued there to read the previous frame)
+    float* const stage_s = c->d_gather_stage + (size_t)world * local_floats;
     if ((st = nccl_try(N.group_start(), "ncclGroupStart")) != MRT_OK) return st;
     for (uint32_t r = 0; r < world; r++) {
         if (r == root) continue;
         st = nccl_try(N.recv(c->d_gather_stage + (size_t)r * local_floats, local_floats, kNcclFloat, (int)r, nccl_comm, c->stream), "ncclRecv");
+        if (st == MRT_OK && with_s)
+            st = nccl_try(N.recv(stage_s + (size_t)r * local_s, local_s, kNcclFloat, (int)r, nccl_comm, c->stream), "ncclRecv");
         if (st != MRT_OK) { (void)N.group_end(); return st; }
     }
     if ((st = nccl_try(N.group_end(), "ncclGroupEnd")) != MRT_OK) return st;
@@ -215,7 +273,18 @@ int mrt_gather_rccl(mrt_ctx* c, void* nccl_comm, uint32_t root) {
     for (uint32_t r = 0; r < world; r++) {
         const float* from = r == root ? src : c->d_gather_stage + (size_t)r * local_floats;
         HIP_TRY(c, scatter_bands(c->d_gather, c->device, from, c->device, r, world, c->local_bands, bb, c->stream));
+        if (!with_s) continue;
+        const float* from_s = r == root ? c->d_noise_s : stage_s + (size_t)r * local_s;
+        HIP_TRY(c, scatter_bands(mrt::gathered_noise(c), c->device, from_s, c->device, r, world, c->local_bands, bb / 4, c->stream));
     }
+    if (with_s) snapshot_noise(c);
+    return MRT_OK;
+}
+
+int mrt_set_gather_noise(mrt_ctx* c, int enabled) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if ((enabled != 0) != c->gather_noise) c->gather_has_s = false;     // (the gathered S is the other setting's until the next gather)
+    c->gather_noise = enabled != 0;
     return MRT_OK;
 }
 
@@ -234,6 +303,17 @@ int mrt_read_gathered(mrt_ctx* R, float* out, size_t cap) {
     if (cap < n) return fail(R, MRT_ERR_TOO_SMALL, "mrt_read_gathered: need %zu floats", n);
     HIP_TRY(R, hipSetDevice(R->device));
     HIP_TRY(R, hipMemcpyAsync(out, R->d_gather, n * sizeof(float), hipMemcpyDeviceToHost, R->stream));
+    MRT_TRY(mrt::wait_stream(R, R->stream, __func__));
+    return MRT_OK;
+}
+
+int mrt_read_gathered_noise(mrt_ctx* R, float* out, size_t cap) {
+    if (!R || !out) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(mrt::gathered_noise_check(R, "mrt_read_gathered_noise"));
+    const size_t n = (size_t)R->args.width * R->args.height;
+    if (cap < n) return fail(R, MRT_ERR_TOO_SMALL, "mrt_read_gathered_noise: need %zu floats", n);
+    HIP_TRY(R, hipSetDevice(R->device));
+    HIP_TRY(R, hipMemcpyAsync(out, mrt::gathered_noise(R), n * sizeof(float), hipMemcpyDeviceToHost, R->stream));
     MRT_TRY(mrt::wait_stream(R, R->stream, __func__));
     return MRT_OK;
 }

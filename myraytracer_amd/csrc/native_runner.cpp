@@ -32,7 +32,8 @@ static void usage() {
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
         "                      check earlier finds noisy, and the loop also stops when no pixel is above rel 0.02; prints frames,\n"
         "                      samples and tiles selected per check\n"
-        "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png; one GPU)\n"
+        "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png); with several GPUs the\n"
+        "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame\n"
         "  --denoise-variance: the luminance stop's variance (mrt_set_denoise_variance): the pixel's own accumulated estimate\n"
         "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n");
 }
@@ -144,7 +145,8 @@ int main(int argc, char** argv) {
         if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
         TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
     }
-    if (!denoise_out.empty() && n_gpus > 1) { std::fprintf(stderr, "--denoise-out wants one GPU (a shard has no neighbours)\n"); destroy_all(); return 2; }
+    // several GPUs: the noise estimate travels with the gather, and the first GPU denoises the gathered frame
+    if (!denoise_out.empty() && n_gpus > 1) TRY(ctxs[0], mrt_set_gather_noise(ctxs[0], 1));
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
@@ -261,7 +263,8 @@ int main(int argc, char** argv) {
     }
     if (!denoise_out.empty()) {
         std::vector<float> fb((size_t)args.width * args.height * 4);
-        TRY(ctxs[0], mrt_read_denoised(ctxs[0], fb.data(), fb.size()));
+        if (n_gpus > 1) TRY(ctxs[0], mrt_read_gathered_denoised(ctxs[0], fb.data(), fb.size()));
+        else TRY(ctxs[0], mrt_read_denoised(ctxs[0], fb.data(), fb.size()));
         if (write_image(denoise_out, fb)) { destroy_all(); return 1; }
     }
     destroy_all();

@@ -127,19 +127,23 @@ extern "C" {
 int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (!c) return MRT_ERR_INVALID_ARG;
     if (!present_format_ok(format)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: format %d", format);
-    if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL))
+    if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL | MRT_PRESENT_GATHERED_DENOISED))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
     const bool gathered = (flags & MRT_PRESENT_GATHERED) != 0, denoised = (flags & MRT_PRESENT_DENOISED) != 0;
     const bool temporal = (flags & MRT_PRESENT_TEMPORAL) != 0;
     if (gathered && denoised) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the gathered frame cannot be denoised (it has no S)");
     if (temporal && (gathered || denoised))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the temporal image is neither the gathered nor the denoised frame (flags 0x%x)", flags);
+    const bool gathered_denoised = (flags & MRT_PRESENT_GATHERED_DENOISED) != 0;
+    if (gathered_denoised && (gathered || denoised || temporal))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the denoised gathered frame is a source of its own (flags 0x%x: with FLIP_Y only)", flags);
     if (denoised) MRT_TRY(mrt::present_denoised_check(c));
+    if (gathered_denoised) MRT_TRY(mrt::present_gathered_denoised_check(c));
     if (temporal) MRT_TRY(mrt::present_temporal_check(c));
     const uint32_t width = c->args.width;
     const float* src;
     uint32_t rows;
-    if (denoised || temporal) {
+    if (denoised || temporal || gathered_denoised) {
         src = nullptr;              // (queued below, right before the encode)
         rows = c->args.height;
     } else if (gathered) {
@@ -166,6 +170,7 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     E.state = PresentEntry::kFree;
     if (denoised) MRT_TRY(mrt::present_denoised(c, &src));
     if (temporal) MRT_TRY(mrt::present_temporal(c, &src));
+    if (gathered_denoised) MRT_TRY(mrt::present_gathered_denoised(c, &src));
     const int e = mrt::launch_present(src, E.d_img, width, rows, (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u,
                                       format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u, c->d_present_tables, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "present launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -182,7 +187,7 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     HIP_TRY(c, hipEventRecord(E.copied, copy_stream));
     E.info = mrt_present_info{};
     E.info.seq = ++c->present_seq;
-    E.info.frames_done = c->frames_done;
+    E.info.frames_done = gathered_denoised ? c->gather_frames : c->frames_done;      // (the gather's snapshot: what the image shows)
     E.info.width = width; E.info.rows = rows; E.info.row_bytes = width * 4;
     E.info.format = (uint32_t)format; E.info.flags = flags;
     E.state = PresentEntry::kQueued;
