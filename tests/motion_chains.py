@@ -1,0 +1,894 @@
+"""Chains of calls on a scene that moves: mrt_update_spheres, mrt_regroup_spheres, mrt_set_camera, frames and mrt_temporal_step, many
+in a row, checked against a host model.
+
+Every single-step test of these calls starts from a freshly built scene.  What only a chain reaches: the host scalars that
+mrt_update_spheres keeps valid monotonically (the sweep's reach, the quadratic box slack's kc, the direct records) and the sweep's
+origin, frozen at the build, after a scene has drifted fifty scene sizes, shrunk three times or taken a radius of 0; a partial
+update through a member_index that regroups have permuted; the camera masks' generations with 4 to 8 frames in flight; a temporal
+history across updates, regroups, resets and a mrt_set_world to another sphere count.
+
+chain(case) draws (params, ops) from np.random.default_rng(case); ops are plain tuples:
+  ("set_world", layout)            tests/test_gpu_update_spheres.py's scenes, with the forced hierarchy of its HASH_LAYOUTS
+  ("update", kind, seed[, k])      UPDATE_KINDS; "drift" moves k scene sizes in ONE mrt_update_spheres (see drift below) and takes
+                                   the camera along; "tiny" is two one-sphere updates
+  ("regroup",) ("set_regroup_block", 4 | 0) ("set_camera", angle, distance, height)
+  ("render", k) ("reset",) ("set_frames_in_flight", n) ("set_frame_batching", 0) ("set_sweep", m) ("set_camera_masks", on)
+  ("set_temporal", on) ("temporal_step",) ("temporal_reset",)
+  ("refused", kind, seed)          one call the header refuses, REFUSALS
+  ("check",)
+Shadow turns an op into calls -- it follows the geometry and the camera the way the generator did when it drew the op, without
+an oracle -- and Run applies every call to the implementation and to the model and compares statuses; a check compares what the
+model can say (frames_done, framebuffer, counters, guides, the temporal history and image) bit for bit and, on a real context,
+the hierarchy (tests/refit_ref.py), member_index (tests/regroup_ref.py), the candidate sets under both sweeps, the camera masks
+(tests/camera_mask_ref.py) and mrt_debug_check_context.
+
+Drift: a drift op carries the number of scene sizes it moves in ONE mrt_update_spheres.  Chain 8 is the long one: fifty-two drifts of
+one scene size each, with frames and checks at the positions between, about 120 ops.  The other chains are kept to forty ops;
+their drifts jump 1 .. 16 sizes a call, and the host scalars see the same maxima as after that many single steps.
+
+Checks: every chain ends with one, one follows every third update, and one follows every regroup before the grouping changes
+again.  In seg_two_regroups it comes straight behind the regroup, so that the regrouped hierarchy is checked before a refit
+rewrites it; in seg_regroup_then_partial and seg_masks updates, camera changes and frames come first on purpose -- they are queued
+behind the regroup without a wait, which a check would be -- and the check then sees the hierarchy after the later refit
+(member_index is held to the ordering computed at the regroup either way).
+
+A HIP error or a stalled wait from ANY call the runner makes on a real context -- the ops' own (Run._both), the read-backs and
+diagnostics of a check and of the steps (Run._dev), the creation of the context (new_state) -- is ChainStopped, which the GPU tests
+turn into pytest.exit: nothing more is started on the GPU.
+
+Imports: the module needs no device, but it imports the package (which loads the host library) and, for the scenes and ray
+batches the issue tells it to share, the gpu-marked modules tests/test_gpu_update_spheres.py and tests/test_gpu_superset.py; those
+must stay importable on a machine without a GPU (they are: their imports touch no device), or tests/test_motion_chains_host.py fails.
+
+The model is host only.  It holds the spheres, the camera, the (scene, camera) of every frame queued since the last reset, the
+guides' staleness, and the temporal state (h0, h1, previous spheres, previous derived camera, dropped / stepped); frames and
+counters are the oracle's, guides denoise_ref's, a step and the image temporal_ref's.  Nothing is read back from the library."""
+import math
+
+import numpy as np
+
+import camera_mask_ref as CM
+import denoise_ref
+import myraytracer_amd as M
+import refit_ref as R
+import regroup_ref as G
+import temporal_ref as T
+from common import mismatch_report, to_oracle_spheres
+from test_gpu_superset import _rays_for
+from test_gpu_update_spheres import DEPTH, H, HASH_LAYOUTS, KEYS, SEED, SPP, W, scene
+
+OK, INVALID_ARG, HIP, NO_SCENE, BAD_SCENE, STATE, STALLED = 0, 1, 3, 4, 5, 7, 9
+SUITE_CASES = tuple(range(12))
+UPDATE_KINDS = ("jitter", "scatter", "drift", "shrink", "grow", "flip", "tiny", "partial", "ground")
+REFUSALS = ("step-after-reset", "step-while-off", "range-past-the-end", "coordinate-too-large", "radius-nan")
+VOCABULARY = ("set_world", "update", "regroup", "set_regroup_block", "set_camera", "render", "reset", "set_frames_in_flight",
+              "set_frame_batching", "set_sweep", "set_camera_masks", "set_temporal", "temporal_step", "temporal_reset", "refused", "check")
+LIMIT = 1.0e7                                  # mrt_update_spheres: |coordinate|, |radius| <= 1e7
+DRIFT_DIR = np.array([0.6, 0.1, 0.79]) / np.linalg.norm([0.6, 0.1, 0.79])
+GENERATION_CALLS = ("set_world", "update_spheres", "regroup_spheres", "set_camera")
+# case -> (layout, flavour).  masks: frame batching off, 4 or 8 frames in flight, generation changes with two frames between them
+# and with none; temporal: max_framebuffer_weight 0, a step per frame; world: mrt_set_world to another sphere count while temporal
+# reprojection is on; drift: ends fifty scene sizes away, in a few jumps; long drift: the one chain beyond forty ops, fifty-two drifts of
+# ONE scene size each with frames and checks at the positions between; shrink: three shrinks in a row and the tiny radii
+PLAN = {0: ("small", "masks"), 1: ("small", "masks"), 2: ("small", "masks drift"), 3: ("small", "masks shrink"),
+        4: ("small", "temporal"), 5: ("small", "temporal world"), 6: ("large-quad", "shrink"), 7: ("large-quad", "temporal world"),
+        8: ("large-quad", "long drift"), 9: ("large-lin", "temporal world"), 10: ("large-lin", "shrink drift"), 11: ("deep-4200", "mixed")}
+DRIFT_STEPS = (1, 3, 8, 8, 16, 16)             # 52 scene sizes
+
+
+class Refused(Exception):
+    def __init__(self, status, where):
+        super().__init__(f"{where}: status {status}")
+        self.status = status
+
+
+class ChainMismatch(AssertionError):
+    pass
+
+
+class ChainStopped(RuntimeError):
+    """A status that is no comparison failure (a HIP error, a stalled wait): nothing more may run on the GPU."""
+
+
+# ------------------------------------------------------------------ the geometry an op names
+
+def layout_scene(layout):
+    return scene(M, HASH_LAYOUTS[layout][0])
+
+
+class Shadow:
+    """The spheres and the camera as the calls so far have left them (no oracle, no device): what an op means."""
+
+    def __init__(self):
+        self.layout = self.sc = self.cam = None
+        self.grown = 0
+
+    @property
+    def n(self):
+        return len(self.sc)
+
+    def xyzr(self):
+        return R.xyzr_of(self.sc)
+
+    def centroid(self):
+        return self.sc["center"][:self.n - 1].astype(np.float64).mean(0)
+
+    def ground_top(self):
+        return float(self.sc["center"][self.n - 1, 1]) + abs(float(self.sc["radius"][self.n - 1]))
+
+    def load(self, layout):
+        self.layout, self.sc, self.grown = layout, layout_scene(layout), 0
+        c = self.sc["center"][:self.n - 1].astype(np.float64)
+        self.ext0 = c.max(0) - c.min(0)
+        self.size = float(self.ext0.max())
+        self.origin0 = self.centroid()
+        self.rmin0 = float(np.abs(self.sc["radius"][:self.n - 1]).min())
+
+    def camera_at(self, angle, distance, height):
+        """a look-at camera `height` above the higher of the centroid and the ground's top, looking at the centroid"""
+        c = self.centroid()
+        f32 = lambda v: tuple(float(np.float32(x)) for x in v)
+        return (f32((c[0] + distance * math.sin(angle), max(c[1], self.ground_top()) + height, c[2] + distance * math.cos(angle))), f32(c))
+
+    def camera_stale(self):
+        """the camera no longer stands a unit above the ground, or looks more than a quarter of a scene size past the centroid"""
+        frm, at = self.cam
+        return frm[1] < self.ground_top() + 1.0 or float(np.linalg.norm(np.asarray(at) - self.centroid())) > 0.25 * self.size
+
+    def drifted(self):
+        """the centroid's distance from the one the scene was built around, in scene sizes"""
+        return float(np.linalg.norm(self.centroid() - self.origin0)) / self.size
+
+    def smallest_clustered_radius(self):
+        return float(np.abs(self.sc["radius"][:self.n - 1]).min())
+
+    def motion(self, kind, seed, k=1):
+        """-> [(first, (count, 4) float32)]: the updates of ("update", kind, seed, k) from the spheres as they are"""
+        rng = np.random.default_rng(seed)
+        n, x = self.n, self.xyzr()
+        third = (n - 1) // 3
+        size = np.float32(self.size)
+        if kind == "jitter":                    # 1 % of the scene's size, the ground included
+            x[:, :3] += rng.uniform(-0.01, 0.01, (n, 3)).astype(np.float32) * size
+            return [(0, x)]
+        if kind == "scatter":                   # anywhere in a box twice the build's size around the middle: the groups stop meaning anything
+            c = x[:n - 1, :3].astype(np.float64)
+            mid = 0.5 * (c.min(0) + c.max(0))
+            x[:n - 1, :3] = rng.uniform(mid - self.ext0, mid + self.ext0, (n - 1, 3)).astype(np.float32)
+            top = rng.uniform(mid - self.ext0, mid + self.ext0 * [1.0, 0.0, 1.0])      # (the ground's top: the box's lower half)
+            x[n - 1, :3] = (top - [0.0, abs(float(x[n - 1, 3])), 0.0]).astype(np.float32)
+            return [(0, x)]
+        if kind == "drift":
+            x[:, :3] = (x[:, :3].astype(np.float64) + k * self.size * DRIFT_DIR).astype(np.float32)
+            return [(0, x)]
+        if kind == "shrink":                    # always the first third: three in a row reach 1e-3 of the build's radii
+            x[:third, 3] *= np.float32(0.1)
+            return [(0, x[:third].copy())]
+        if kind == "grow":
+            x[third:2 * third, 3] *= np.float32(3.0)
+            return [(third, x[third:2 * third].copy())]
+        if kind == "flip":
+            glass = np.nonzero(self.sc["material_ty"][:n - 1] == 3)[0]
+            i = int(glass[rng.integers(0, len(glass))])
+            x[i, 3] = -x[i, 3]
+            return [(i, x[i:i + 1].copy())]
+        if kind == "tiny":                      # legal radii that quad_kc_for_radius clamps; two one-sphere updates
+            i, j = (int(v) for v in 2 * third + rng.choice(n - 1 - 2 * third, 2, replace=False))
+            x[i, 3], x[j, 3] = 0.0, 1e-30
+            return [(i, x[i:i + 1].copy()), (j, x[j:j + 1].copy())]
+        if kind == "partial":
+            form = seed % 3                     # 0: ends at the last sphere, 1: one sphere, 2: anywhere
+            count = 1 if form == 1 else int(rng.integers(2, max(3, n // 2)))
+            first = n - count if form == 0 else int(rng.integers(0, n - count))
+            x[first:first + count, :3] += rng.uniform(-0.05, 0.05, (count, 3)).astype(np.float32) * size
+            return [(first, x[first:first + count].copy())]
+        if kind == "ground":                    # the direct sphere: a step aside, a little down or up, the radius 1000 <-> 1001 under the same top
+            r = abs(float(x[n - 1, 3]))
+            r2 = 1001.0 if r == 1000.0 else 1000.0
+            step = rng.uniform([-1.0, -0.3, -1.0], [1.0, 0.1, 1.0])
+            x[n - 1, :3] = (x[n - 1, :3].astype(np.float64) + step - [0.0, r2 - r, 0.0]).astype(np.float32)
+            x[n - 1, 3] = r2
+            return [(n - 1, x[n - 1:n].copy())]
+        raise KeyError(kind)
+
+    def apply_update(self, first, arr):
+        self.sc["center"][first:first + len(arr)] = arr[:, :3]
+        self.sc["radius"][first:first + len(arr)] = arr[:, 3]
+
+    def camera_call(self):
+        frm, at = self.cam
+        return ("set_camera", (M.Camera(1, frm, at, (0.0, 1.0, 0.0), 40.0, 0.0, 10.0),))
+
+    def calls(self, op):
+        """the op as [(method, args)] of State / Model, the shadow moved on by what the legal ones do"""
+        name, a = op[0], op[1:]
+        if name == "set_world":
+            self.load(a[0])
+            self.cam = self.camera_at(0.0, 13.0, 2.5)
+            return [("debug_set_hierarchy", HASH_LAYOUTS[a[0]][1] or (4, 0)), ("set_world", (self.sc.copy(),)), self.camera_call()]
+        if name == "update":
+            out = []
+            for first, arr in self.motion(*a):
+                self.apply_update(first, arr)
+                out.append(("update_spheres", (first, arr)))
+            if a[0] == "grow":
+                self.grown += 1
+            if a[0] == "drift":
+                shift = a[2] * self.size * DRIFT_DIR
+                frm, at = self.cam
+                f32 = lambda v: tuple(float(np.float32(x)) for x in v)
+                self.cam = (f32(np.asarray(frm) + shift), f32(np.asarray(at) + shift))
+                out.append(self.camera_call())
+            return out
+        if name == "set_camera":
+            self.cam = self.camera_at(*a)
+            return [self.camera_call()]
+        if name == "refused":
+            kind, seed = a
+            x = self.xyzr()
+            if kind in ("step-after-reset", "step-while-off"):
+                return [("temporal_step", ())]
+            if kind == "range-past-the-end":
+                return [("update_spheres", (self.n - 2, x[:4].copy()))]
+            bad = x[5:9].copy()
+            if kind == "coordinate-too-large":
+                bad[2, seed % 3] = 1.5e7
+            else:
+                bad[1, 3] = np.nan
+            return [("update_spheres", (5, bad))]
+        simple = {"regroup": "regroup_spheres", "set_regroup_block": "debug_set_regroup_block", "render": "render", "reset": "reset",
+                  "set_frames_in_flight": "debug_set_frames_in_flight", "set_frame_batching": "debug_set_frame_batching",
+                  "set_sweep": "debug_set_sweep", "set_camera_masks": "debug_set_camera_masks", "set_temporal": "set_temporal",
+                  "temporal_step": "temporal_step", "temporal_reset": "temporal_reset"}
+        return [(simple[name], a)] if name != "check" else []
+
+
+# ------------------------------------------------------------------ the generator
+
+def chain(case: int):
+    """-> (params, ops): params = dict(layout, flavour, max_w); ops = the case's list of tuples"""
+    rng = np.random.default_rng(case)
+    layout, flavour = PLAN[case % len(PLAN)]
+    temporal, masks = "temporal" in flavour, "masks" in flavour
+    p = dict(layout=layout, flavour=flavour, max_w=0.0 if temporal else 1.0)
+    sh = Shadow()
+    ops = []
+    g = dict(frames=0, temporal=False, updates=0, owed=False)
+    chance = lambda q: bool(rng.random() < q)
+    seed = lambda: int(rng.integers(0, 2 ** 31))
+
+    def emit(*op):
+        if op[0] in ("regroup", "set_world") and g["owed"]:
+            emit("check")                       # a check follows every regroup before the grouping changes again
+        if op == ("check",) and ops[-1] == op:
+            return
+        ops.append(op)
+        sh.calls(op)
+        assert sh.sc is None or max(float(np.abs(sh.xyzr()).max()), float(np.abs(sh.cam[0]).max())) <= 0.5 * LIMIT     # the 1e7 rule
+        if op[0] == "check":
+            g.update(updates=0, owed=False)
+        elif op[0] == "regroup":
+            g["owed"] = True
+        elif op[0] == "render":
+            g["frames"] += op[1]
+        elif op[0] == "reset":
+            g["frames"] = 0
+        elif op[0] == "set_temporal":
+            g["temporal"] = op[1]
+        elif op[0] == "update":
+            g["updates"] += 1
+            if sh.camera_stale():
+                emit("set_camera", float(rng.uniform(-0.5, 0.5)), float(rng.uniform(11.0, 15.0)), float(rng.uniform(2.0, 3.0)))
+            if g["updates"] >= 3:
+                emit("check")                   # ... and every third update
+
+    def update(kind, k=None):
+        if kind == "grow" and sh.grown >= 1:    # (once a scene: a second x 3 would hide the sky)
+            kind = "jitter"
+        emit("update", kind, seed(), *(() if k is None else (k,)))
+
+    def frame(k=1):
+        if g["temporal"] and g["frames"] and chance(0.2):
+            emit("reset")                       # (a caller who resets before every step's frames: the history stays)
+        emit("render", k)
+        if g["temporal"]:
+            emit("temporal_step")
+
+    def animate(kinds):
+        for kind in kinds:
+            update(kind)
+            frame(int(rng.integers(1, 4)) if not g["temporal"] else 1)
+
+    # -- the segments a flavour is made of
+    def seg_regroup_then_partial():             # a partial update through a permuted member_index, queued right behind the regroup
+        update("scatter" if chance(0.6) else "jitter")
+        emit("regroup")
+        update("partial")
+        emit("check")
+        frame()
+
+    def seg_two_regroups():                     # update, regroup, update, regroup
+        update(str(rng.choice(["scatter", "jitter", "partial"])))
+        emit("regroup")
+        emit("check")                           # the regrouped hierarchy itself, before a refit rewrites it
+        update(str(rng.choice(["scatter", "partial", "flip"])))
+        emit("regroup")
+        emit("check")
+        frame()
+
+    def seg_masks():                            # generation changes of all three kinds, two frames between some and none between others
+        if g["updates"]:
+            emit("check")                       # (so that no check of the every-third-update rule drains the frames in flight below)
+        emit("set_frames_in_flight", int(rng.choice([4, 8])))
+        kinds = ["update", "regroup", "camera", "update"]
+        rng.shuffle(kinds)
+        for i, kind in enumerate(kinds):
+            if kind == "update":
+                update(str(rng.choice(["jitter", "partial", "flip"])))
+            elif kind == "regroup":
+                emit("regroup")
+            else:
+                emit("set_camera", float(rng.uniform(-0.4, 0.4)), float(rng.uniform(11.0, 15.0)), float(rng.uniform(2.0, 3.0)))
+            if i % 2 == 0 or i == len(kinds) - 1:
+                emit("render", 2 if chance(0.5) else 3)
+            elif chance(0.5):
+                emit("render", 1)
+        if chance(0.5):                         # a built table left unused for a launch, then used again
+            emit("set_camera_masks", False)
+            emit("render", 1)
+            emit("set_camera_masks", True)
+            emit("render", 1)
+        emit("check")
+
+    def seg_drift(steps):
+        for i, k in enumerate(steps):
+            update("drift", int(k))
+            if i % 2 == 0 or g["temporal"]:
+                frame()
+
+    def seg_shrink():
+        for _ in range(3):
+            update("shrink")
+            if chance(0.5):
+                frame()
+        update("tiny")
+        frame()
+        emit("check")
+
+    def seg_other_world():                      # another sphere count; with temporal reprojection on this re-creates "previous"
+        other = [l for l in ("small", "large-quad", "large-lin") if len(layout_scene(l)) != sh.n]
+        emit("set_world", str(rng.choice(other)))
+        frame()
+        animate(["jitter"])
+        emit("check")
+
+    def seg_switches():                         # (by case number: every value turns up somewhere in the suite)
+        emit("set_sweep", case % 3)
+        if case % 3 != 2 and not masks:         # (the mask chains switch them off for a launch or two, seg_masks)
+            emit("set_camera_masks", bool(case % 2))
+        if not masks:
+            emit("set_frames_in_flight", (0, 1, 4, 8)[case % 4])
+        emit("set_regroup_block", (4, 0)[(case // 2) % 2])
+
+    def seg_reset():
+        emit("reset")
+        if chance(0.5):
+            emit("check")
+        frame(int(rng.integers(1, 3)) if not g["temporal"] else 1)
+
+    def seg_refusal():
+        kinds = [k for k in REFUSALS if k != "step-after-reset" or g["temporal"]]
+        kinds = [k for k in kinds if k != "step-while-off" or not g["temporal"]]
+        kind = kinds[case % len(kinds)]
+        if kind == "step-after-reset":
+            emit("reset")
+        emit("refused", kind, seed())
+        emit("check")                           # the refused call changed nothing
+        if kind == "step-after-reset":
+            frame()
+
+    def seg_temporal_toggles():
+        which = case % 3
+        if which == 0:
+            emit("temporal_reset")
+            emit("check")                       # dropped: the read refuses
+        elif which == 1:
+            emit("set_temporal", False)
+            emit("set_temporal", True)
+        else:
+            emit("temporal_reset")
+        frame()
+        animate(["ground"] if chance(0.5) else ["jitter"])
+
+    def seg_pan():                              # the camera turns a little between two steps: "previous camera" is the last step's
+        frm, at = sh.cam
+        angle = math.atan2(frm[0] - at[0], frm[2] - at[2]) + float(rng.uniform(-0.06, 0.06))
+        emit("set_camera", angle, float(np.hypot(frm[0] - at[0], frm[2] - at[2])), 2.5)
+        frame()
+        animate(["jitter"])
+        emit("check")
+
+    emit("set_world", layout)
+    if masks:
+        emit("set_frame_batching", 0)
+    if temporal:
+        emit("set_temporal", True)
+    frame(1 if temporal else 2)
+    seg_switches()                              # (first: they hold for the chain)
+    body = [seg_refusal]
+    if masks:
+        body += [seg_masks, seg_masks] if flavour == "masks" else [seg_masks]
+    if temporal:
+        body += [seg_pan, seg_temporal_toggles, seg_regroup_then_partial]
+        if flavour == "temporal":
+            body.append(lambda: seg_drift([2]))
+    if flavour == "long drift":
+        body += [lambda: seg_drift([1] * 26), lambda: seg_drift([1] * 26)]
+    elif "drift" in flavour:
+        steps = list(DRIFT_STEPS)
+        rng.shuffle(steps)
+        body += [lambda: seg_drift(steps[:3]), lambda: seg_drift(steps[3:])]
+    if "shrink" in flavour:
+        body.append(seg_shrink)
+    if flavour in ("shrink", "long drift", "mixed", "masks"):
+        body += [seg_two_regroups] if masks else [seg_two_regroups, seg_reset]
+    if flavour in ("shrink", "mixed", "masks drift", "shrink drift"):
+        body.append(seg_regroup_then_partial)
+    if flavour in ("mixed", "long drift", "masks shrink"):
+        body.append(lambda: animate(["grow", "scatter", "ground"]))
+    body = [body[int(i)] for i in rng.permutation(len(body))]
+    if "world" in flavour:                      # (in the later half: both scenes get their share of the chain)
+        body.insert(int(rng.integers(len(body) // 2 + 1, len(body) + 1)), seg_other_world)
+    for seg in body:
+        seg()
+    if ops[-1] != ("check",):
+        emit("check")
+    return p, ops
+
+
+# ------------------------------------------------------------------ the model
+
+_FRAMES, _GUIDES, _HITS = {}, {}, {}
+
+
+def _key(a) -> int:
+    return hash(np.ascontiguousarray(a).tobytes())
+
+
+def _cached(cache, key, make, limit=4000):
+    if key not in cache:
+        if len(cache) > limit:
+            cache.clear()
+        cache[key] = make()
+    return cache[key]
+
+
+class Model:
+    """State's method names for the chain vocabulary; a call the header refuses raises Refused(status).  The methods the seeded
+    defects of tests/test_motion_chains_host.py override are the ones with a leading underscore."""
+
+    def __init__(self, O, max_w):
+        self.O, self.max_w = O, max_w
+        self.spheres = None
+        self.set_camera(None)
+        self.seeds = O.fill_seeds(SEED, W, H)
+        self.frames, self.done = [], []         # per frame queued since the reset: (spheres, cam_raw, key); (fb, counters) after it
+        self.guides_built = None                # the (scene, camera) the guides were last rebuilt for
+        self.guides_stale = True
+        self.temporal_on, self.stepped, self.cleared = False, False, True
+        self.h0 = self.h1 = self.prev_xyzr = self.prev_cam = None
+        self.found = []                         # per step: (first since a drop, pixels that found history, pixels)
+
+    # ---- what the seeded defects change
+    def _after_update(self):
+        self.guides_stale = True
+
+    def _after_set_world(self):
+        self._drop_history()
+
+    def _after_reset(self):
+        pass
+
+    def _refused_update(self, first, arr):
+        pass
+
+    def _queue_frame(self):
+        self.frames.append((self.spheres, self.cam_raw, (_key(self.spheres), self.cam_key)))
+
+    # ---- helpers
+    def xyzr(self):
+        return R.xyzr_of(self.spheres)
+
+    def _drop_history(self):
+        self.stepped, self.cleared = False, True
+
+    def _evaluate(self):
+        O = self.O
+        for f in range(len(self.done), len(self.frames)):
+            spheres, cam_raw, key = self.frames[f]
+            fb, cnt = self.done[f - 1] if f else (np.zeros((H, W, 4), np.float32), (0, 0, 0))
+
+            def make():
+                c = O.Counters()
+                out = O.render_frame(W, H, SPP, DEPTH, O.pack_world(to_oracle_spheres(O, spheres)), cam_raw, self.seeds,
+                                     O.frame_shuffle(SEED, f), O.frame_weight(f, self.max_w), fb, counters=c)
+                return out, tuple(int(c.as_dict()[k]) for k in KEYS)
+            out, add = _cached(_FRAMES, (key, f, self.max_w, _key(fb)), make)
+            self.done.append((out, tuple(a + b for a, b in zip(cnt, add))))
+
+    def _guides(self, key):
+        spheres, cam_raw = key[2], key[3]
+
+        def make():
+            rays = denoise_ref.centre_rays(W, H, cam_raw)
+            hit, t, normal, albedo = denoise_ref.expected_guides(self.O, spheres, rays)
+            return {"rays": rays, "index": hit.reshape(H, W).astype(np.int32), "t": t.reshape(H, W), "normal": normal.reshape(H, W, 3),
+                    "albedo": albedo.reshape(H, W, 3)}
+        return _cached(_GUIDES, key[:2], make, 400)
+
+    def _ensure_guides(self):
+        if self.guides_stale or self.guides_built is None:
+            self.guides_built = (_key(self.spheres), self.cam_key, self.spheres, self.cam_raw)
+            self.guides_stale = False
+        return self._guides(self.guides_built)
+
+    # ---- scene
+    def debug_set_hierarchy(self, levels, target):
+        pass
+
+    def set_world(self, spheres):
+        self.spheres = np.array(spheres, copy=True)
+        self.guides_stale = True
+        self.prev_xyzr = self.xyzr()            # "previous" is created anew: the scene's own to begin with
+        self._after_set_world()
+
+    def update_spheres(self, first, xyzr):
+        arr = np.ascontiguousarray(xyzr, np.float32).reshape(-1, 4)
+        if self.spheres is None:
+            raise Refused(NO_SCENE, "update_spheres")
+        status = OK
+        if first + len(arr) > len(self.spheres):
+            status = INVALID_ARG
+        elif not (np.isfinite(arr) & (np.abs(arr) <= LIMIT)).all():
+            status = BAD_SCENE
+        if status:
+            self._refused_update(first, arr)
+            raise Refused(status, "update_spheres")
+        if len(arr) == 0:
+            return
+        self._write(first, arr)
+        self._after_update()
+
+    def _write(self, first, arr):
+        sc = self.spheres.copy()
+        sc["center"][first:first + len(arr)] = arr[:, :3]
+        sc["radius"][first:first + len(arr)] = arr[:, 3]
+        self.spheres = sc
+
+    def regroup_spheres(self):
+        if self.spheres is None:
+            raise Refused(NO_SCENE, "regroup_spheres")
+
+    def set_camera(self, cam):
+        O = self.O
+        self.cam = O.pinhole_camera() if cam is None else O.lookat_camera(cam.lookfrom, cam.lookat, cam.vup, cam.vfov_deg,
+                                                                            cam.defocus_angle_deg, cam.focus_dist)
+        self.cam_raw = O.camera_derive(self.cam)
+        self.cam_key = hash(bytes(self.cam_raw))
+        self.guides_stale = True
+
+    # ---- frames
+    def render(self, frames=1):
+        for _ in range(frames):
+            if self.spheres is None:
+                raise Refused(NO_SCENE, "render")
+            self._queue_frame()
+
+    def reset(self):
+        self.frames, self.done = [], []
+        self._after_reset()
+
+    @property
+    def frames_done(self):
+        return len(self.frames)
+
+    def read_framebuffer(self):
+        self._evaluate()
+        return self.done[-1][0].copy() if self.done else np.zeros((H, W, 4), np.float32)
+
+    def read_counters(self):
+        self._evaluate()
+        return dict(zip(KEYS, self.done[-1][1] if self.done else (0, 0, 0)))
+
+    def debug_read_guides(self):
+        if self.spheres is None:
+            raise Refused(NO_SCENE, "debug_read_guides")
+        return {k: v.copy() for k, v in self._ensure_guides().items()}
+
+    # ---- switches that change no output
+    def debug_set_frames_in_flight(self, slots):
+        pass
+
+    def debug_set_frame_batching(self, enabled):
+        pass
+
+    def debug_set_sweep(self, mode):
+        pass
+
+    def debug_set_camera_masks(self, on):
+        pass
+
+    def debug_set_regroup_block(self, clusters):
+        pass
+
+    # ---- temporal reprojection
+    def set_temporal(self, enabled):
+        if not enabled and self.temporal_on:
+            self._drop_history()
+        self.temporal_on = bool(enabled)
+
+    def _temporal_check(self, where, stepped):
+        if not self.temporal_on:
+            raise Refused(STATE, where)
+        if self.spheres is None:
+            raise Refused(NO_SCENE, where)
+        if stepped and not self.stepped:
+            raise Refused(STATE, where)
+
+    def temporal_step(self):
+        self._temporal_check("temporal_step", False)
+        if self.frames_done == 0:
+            raise Refused(STATE, "temporal_step")
+        g = self._ensure_guides()
+        first = self.cleared
+        if self.cleared:                        # every length 0: no tap of this step counts, whatever "previous" holds
+            self.h0 = np.zeros((H, W, 4), np.float32)
+            self.h1 = np.zeros((H, W, 4), np.float32)
+            self.prev_cam = self.cam_raw
+            self.cleared = False
+        Mx, o = T.camera_matrix(self.prev_cam)
+        now = self.xyzr()
+        self.h0, self.h1, info = T.step(self.read_framebuffer(), g["rays"], g["index"], g["t"], now, self.prev_xyzr, Mx, o, self.h0, self.h1)
+        self.prev_xyzr, self.prev_cam, self.stepped = now, self.cam_raw, True
+        self.found.append((first, int(info["found"].sum()), info["found"].size))
+
+    def temporal_reset(self):
+        if not self.temporal_on:
+            raise Refused(STATE, "temporal_reset")
+        self._drop_history()
+
+    def read_temporal(self):
+        self._temporal_check("read_temporal", True)
+        return T.image(self.h0, self.h1, self.read_framebuffer()[..., 3], self._guides(self.guides_built))
+
+    def debug_read_temporal(self, n_spheres):
+        self._temporal_check("debug_read_temporal", True)
+        return {"h0": self.h0.copy(), "h1": self.h1.copy(), "prev_xyzr": self.prev_xyzr.copy()}
+
+
+def new_model(O, params, cls=None):
+    return (cls or Model)(O, params["max_w"])
+
+
+def new_state(params):
+    """a context for a chain; a HIP error or a stalled wait while it is made is ChainStopped, as in the runner"""
+    try:
+        st = M.State(M.Args(W, H, SPP, DEPTH, params["max_w"]), seed=SEED)
+        st.set_wait_timeout(60.0)               # (a stalled wait stops the case with the wait's name long before the suite's own limit)
+        st.debug_set_boxes(2)                   # the walk's box tests on (large scenes), as tests/test_gpu_update_spheres.py has them
+    except M.MrtError as e:
+        if e.status in (HIP, STALLED):
+            raise ChainStopped(f"creating a context: {e}")
+        raise
+    return st
+
+
+# ------------------------------------------------------------------ applying and comparing
+
+def _call(obj, name, args):
+    try:
+        v = getattr(obj, name)
+        return OK, (v(*args) if callable(v) else v)
+    except (Refused, M.MrtError) as e:
+        return e.status, None
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype == np.float32:                   # bit for bit; a NaN equals a NaN
+        return bool(((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))).all())
+    return bool(np.array_equal(a, b))
+
+
+def _describe(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return f"shape / type {a.shape} {a.dtype} against {b.shape} {b.dtype}"
+    if a.dtype == np.float32 and a.ndim == 3 and a.shape[-1] == 4:
+        return mismatch_report(a, b)
+    neq = np.argwhere(~((a == b) | ((a != a) & (b != b))))
+    return f"{len(neq)} of {a.size} differ; first at {tuple(neq[0])}: {a[tuple(neq[0])]!r} against {b[tuple(neq[0])]!r}"
+
+
+def _last_error(impl):
+    try:
+        return impl._L.mrt_last_error(impl._ctx).decode()
+    except Exception:
+        return ""
+
+
+def check_rays(spheres, cam_raw):
+    """the rays of a check: about 2,000 random, grazing and on-surface rays around the spheres as they are, and the camera's own
+    (every texel's four corner jitters and six random ones, as tests/camera_mask_cases.py samples them); -> (rays, index of the first camera ray, the camera rays' texels)"""
+    rays = _rays_for(np.random.default_rng(7), spheres, 500, 900, 600)
+    n_tex = CM.local_texels(W, H)
+    px, py = CM.texel_pixels(n_tex, W)
+    tex = np.nonzero(py < H)[0]
+    cam_rays, ray_tex = CM.camera_rays(cam_raw, W, H, tex, px[tex], py[tex], np.random.default_rng(17), 6)
+    return np.concatenate([rays, cam_rays], 0), len(rays), ray_tex
+
+
+def reference_hits(O, spheres, rays):
+    """oracle.world_hit_batch of the rays against the spheres: (winner, t, discriminant >= 0, required)"""
+    return _cached(_HITS, (_key(spheres), _key(rays)),
+                   lambda: O.world_hit_batch(O.pack_world(to_oracle_spheres(O, spheres)), rays), 200)
+
+
+class Run:
+    """One chain on one implementation and one model, op by op.  after(i, op, run): called behind every op that compared equal."""
+
+    def __init__(self, label, params, impl, model, O, stats=None, after=None, device_checks=True):
+        self.label, self.p, self.impl, self.model, self.O = label, params, impl, model, O
+        self.device_checks = device_checks      # (off: what the model can say alone -- the liveness test's view of a real context)
+        self.stats, self.after = stats if stats is not None else {}, after
+        self.sh = Shadow()
+        self.device = getattr(impl, "_ctx", None) is not None
+        self.sweep, self.fif, self.gen = 0, 0, 0
+        self.midx = self.real = self.n_pool = None
+        self.ops = []
+
+    def _bump(self, k, by=1):
+        k = (self.sh.layout, k)                 # (per layout: a chain may change its scene)
+        self.stats[k] = self.stats.get(k, 0) + by
+
+    def _fail(self, what):
+        raise ChainMismatch(f"{self.label}, op {len(self.ops) - 1} {self.ops[-1]!r}: {what}\nops so far: {self.ops!r}")
+
+    def _dev(self, name, *args, **kw):
+        """a call on the real context alone (the read-backs and diagnostics of a check): its value.  EVERY call this runner makes
+        on an implementation goes through here or through _both: MRT_ERR_HIP or MRT_ERR_STALLED from any of them is ChainStopped,
+        never a comparison failure; any other refusal of a diagnostic is a mismatch."""
+        try:
+            return getattr(self.impl, name)(*args, **kw)
+        except M.MrtError as e:
+            where = f"{self.label}, op {len(self.ops) - 1} {self.ops[-1]!r}: {name}: status {e.status}: {_last_error(self.impl)}"
+            if e.status in (HIP, STALLED):
+                raise ChainStopped(f"{where}\nops so far: {self.ops!r}")
+            self._fail(f"{name} refused: status {e.status} ({_last_error(self.impl)})")
+
+    def _both(self, name, args=()):
+        """the call on both; -> (status, the implementation's value, the model's)"""
+        si, got = _call(self.impl, name, args)
+        sm, want = _call(self.model, name, args)
+        if si in (HIP, STALLED):
+            raise ChainStopped(f"{self.label}, op {len(self.ops) - 1} {self.ops[-1]!r}: {name}: status {si}: {_last_error(self.impl)}\n"
+                               f"ops so far: {self.ops!r}")
+        if si != sm:
+            self._fail(f"{name}: status {si} against the model's {sm} ({_last_error(self.impl)})")
+        return si, got, want
+
+    def step(self, op):
+        self.ops.append(op)
+        for name, args in self.sh.calls(op):
+            status, _, _ = self._both(name, args)
+            if status == OK and name in GENERATION_CALLS and not (name == "update_spheres" and len(args[1]) == 0):
+                self.gen += 1
+                self._bump("generation changes")
+            if status == OK and name == "set_world" and self.device:
+                h = self._dev("debug_read_hierarchy")
+                self.midx, self.real, self.n_pool = h["midx"], G.real_slots(h), self._dev("debug_regroup_info")["n_pool"]
+            if status == OK and name == "regroup_spheres":
+                self._bump("regroups")
+                if self.device:                 # the ordering tests/regroup_ref.py gives for the geometry at this regroup
+                    self.midx = G.regroup(self.midx, self.real, self.n_pool, self.model.xyzr()[:, :3])
+            if name == "debug_set_sweep":
+                self.sweep = args[0]
+            if name == "debug_set_frames_in_flight":
+                self.fif = args[0]
+            if status == OK and name == "render" and self.device and self.sh.layout == "small":
+                info = self._dev("debug_read_camera_masks", table=False)       # (host only: no wait)
+                self.stats.setdefault("mask launches", []).append((self.gen, info["in_force"], self.fif))
+        if op[0] == "check":
+            self.check()
+            self._bump("checks")
+        self._bump("ops")
+        self.stats["largest drift"] = max(self.stats.get("largest drift", 0.0), self.sh.drifted())
+        self.stats["smallest radius"] = min(self.stats.get("smallest radius", math.inf), self.sh.smallest_clustered_radius())
+        if self.after is not None:
+            self.after(len(self.ops) - 1, op, self)
+
+    def check(self):
+        m = self.model
+        for name in ("frames_done", "read_framebuffer", "read_counters"):
+            _, got, want = self._both(name)
+            if name == "read_counters":
+                got, want = {k: got[k] for k in KEYS}, {k: want[k] for k in KEYS}
+                if got != want:
+                    self._fail(f"counters {got} against {want}")
+            elif name == "frames_done":
+                if got != want:
+                    self._fail(f"frames_done {got} against {want}")
+            elif not _same(got, want):
+                self._fail("framebuffer: " + _describe(got, want))
+        _, got, want = self._both("debug_read_guides")
+        for k in ("rays", "index", "t", "normal", "albedo"):
+            if not _same(got[k], want[k]):
+                self._fail(f"guide {k}: " + _describe(got[k], want[k]))
+        if m.temporal_on:
+            status, got, want = self._both("read_temporal")         # dropped: both refuse with MRT_ERR_STATE
+            if status == OK:
+                if not _same(got, want):
+                    self._fail("temporal image: " + _describe(got, want))
+                _, got, want = self._both("debug_read_temporal", (len(m.spheres),))
+                for k in ("h0", "h1", "prev_xyzr"):
+                    if not _same(got[k], want[k]):
+                        self._fail(f"temporal {k}: " + _describe(got[k], want[k]))
+        if self.device and self.device_checks:
+            self.check_device()
+
+    def check_device(self):
+        m, O = self.model, self.O
+        xyzr = m.xyzr()
+        h = self._dev("debug_read_hierarchy")
+        full = dict(h)
+        if h["axes"] != (1.0, 1.0, 1.0):        # (the checker's operand and reach are statements about D = I)
+            del h["mfma"], h["reach"]
+        try:
+            R.check(h, xyzr)
+        except AssertionError as e:
+            self._fail(f"hierarchy: {e}")
+        bad = np.nonzero(h["midx"] != self.midx)[0]
+        if len(bad):
+            self._fail(f"member_index: {len(bad)} slots differ from the reference's grouping; first: slot {bad[0]} holds {h['midx'][bad[0]]}, want {self.midx[bad[0]]}")
+        rays, first_cam, ray_tex = check_rays(m.spheres, m.cam_raw)
+        a2 = (rays[:, 3:].astype(np.float64) ** 2).sum(1)
+        if not (np.abs(a2 - 1.0) < 5e-6).all():
+            self._fail(f"{int((np.abs(a2 - 1.0) >= 5e-6).sum())} rays are not of unit length")
+        ref_hit, ref_t, ref_set, required = reference_hits(O, m.spheres, rays)
+        for sweep in (1, 2):
+            self._dev("debug_set_sweep", sweep)
+            hit, t, cand = self._dev("debug_world_hit", rays, len(m.spheres))
+            missing, extra = required & ~cand, cand & ~ref_set
+            if missing.any():
+                self._fail(f"sweep {sweep}: {int(missing.sum())} (ray, sphere) pairs with a discriminant >= 0 never reached the root tests; "
+                           f"first ray {int(np.nonzero(missing.any(1))[0][0])}, sphere {int(np.nonzero(missing.any(0))[0][0])}")
+            if extra.any():
+                self._fail(f"sweep {sweep}: {int(extra.sum())} pairs reached the root tests with a negative discriminant")
+            if not np.array_equal(hit, ref_hit):
+                self._fail(f"sweep {sweep}: winners differ on {int((hit != ref_hit).sum())} rays")
+            if not np.array_equal(t.view(np.uint32)[hit >= 0], ref_t.view(np.uint32)[hit >= 0]):
+                self._fail(f"sweep {sweep}: t differs")
+        self._dev("debug_set_sweep", self.sweep)
+        if self.sh.layout == "small":
+            info = self._dev("debug_read_camera_masks")
+            if info["built"]:                   # built for the current generation: it covers what the current camera's rays require
+                cluster_of = CM.cluster_of_sphere(full["midx"], len(full["top"]), full["direct_first"], full["nodes"][:full["n_members"]],
+                                                  len(m.spheres))
+                ri, si = CM.missing_pairs(info["masks"], ray_tex, required[first_cam:], cluster_of)
+                self._bump("mask tables checked")
+                if len(ri):
+                    self._fail(f"camera masks: {len(ri)} required (ray, sphere) pairs lie in a cluster the table's entry does not set")
+        why = self._dev("debug_check_context")
+        if why is not None:
+            self._fail(f"the context is not sound: {why}")
+
+
+def run(case, impl, model, O, stats=None, after=None, device_checks=True):
+    """Applies chain `case` to impl and model in lock step; raises ChainMismatch at the first difference."""
+    p, ops = chain(case)
+    r = Run(f"chain {case}", p, impl, model, O, stats, after, device_checks)
+    for op in ops:
+        r.step(op)
+    return r
