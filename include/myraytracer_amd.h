@@ -44,7 +44,8 @@ extern "C" {
  * mrt_temporal_params_default, mrt_set_temporal, mrt_get_temporal, mrt_temporal_step, mrt_temporal_reset, mrt_read_temporal,
  * MRT_PRESENT_TEMPORAL); the temporal response (mrt_temporal_response, mrt_temporal_response_default,
  * mrt_set_temporal_response, mrt_get_temporal_response); the noise estimate across shards and the gathered frame's denoise
- * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED). */
+ * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED); the denoise of
+ * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -473,8 +474,9 @@ double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
  *   Noise reports after divergence: per finite pixel var_p = S_p * (float)K(n_t), K(n) = mrt_noise_factor(n, max_w) (K = +inf:
  *     se_p = +inf); se, rel, above and the tile map follow as before; sum_var = sum of S_p * K(n_t) in double; noise_factor = the
  *     largest K over the tiles (the least-sampled tile's).  Before divergence reports are unchanged.
- *   Denoising after divergence (mrt_read_denoised, MRT_PRESENT_DENOISED) is refused with MRT_ERR_STATE; presents and read-backs
- *   work unchanged.  Shards (world > 1) are refused with MRT_ERR_STATE. */
+ *   Denoising after divergence (mrt_read_denoised, MRT_PRESENT_DENOISED) is refused with MRT_ERR_STATE unless
+ *   mrt_set_denoise_adaptive has turned the per-tile filter on ("denoiser" below, "Adaptive accumulations"); presents and
+ *   read-backs work unchanged.  Shards (world > 1) are refused with MRT_ERR_STATE. */
 /* Queues `frames` consecutive subset frames over the n tiles of `tiles` (asynchronous, with mrt_render's back-pressure).
  * n == 0 or frames == 0: MRT_OK, nothing queued (before any other check).  An id >= the tile count, a duplicate id or tiles == NULL: MRT_ERR_INVALID_ARG; a shard:
  * MRT_ERR_STATE; no scene: MRT_ERR_NO_SCENE; counter-RNG mode with samples_per_frame > MRT_COUNTER_BLOCK: MRT_ERR_INVALID_ARG.
@@ -540,7 +542,28 @@ int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tile
  *     m2    = sum w_q * ((L_q - mean) * (L_q - mean))                                   (a second pass over the same taps)
  *     var_p = m2 / m0
  *   A texel with a finite S and a colour that is not finite gets var 0; a texel whose S is not finite keeps S as its var: both
- *   pass through as above.  From frames_done >= spatial_frames on, SPATIAL_EARLY is PREFILTERED. */
+ *   pass through as above.  From frames_done >= spatial_frames on, SPATIAL_EARLY is PREFILTERED.
+ *
+ * Adaptive accumulations (mrt_set_denoise_adaptive; off by default, and then a denoise after divergence is refused).  After the
+ * first subset frame every tile has its own n_t, hence its own K.  With the setting on the filter is defined per pixel, float32
+ * in the stated order with the same operations.  For pixel p = (x, y) of tile t = (y / 8) * tiles_x + x / 8:
+ *     n_p       = n_t
+ *     K_p       = (float)mrt_noise_factor(n_p, max_framebuffer_weight), as the per-tile noise report takes it (+inf for n_p < 2)
+ *     spatial_p = the mode is SPATIAL_EARLY and n_p < spatial_frames           (n_p in the place of mrt_frames_done)
+ *     stop_p    = spatial_p, or K_p finite                                      (constant over the iterations)
+ *   Iteration 0's variance: with spatial_p the spatial initial variance above, unchanged -- its taps need a finite colour and S,
+ *   whatever their own tile's count; otherwise S_p * K_p for a finite K_p; otherwise 0 for a finite S_p and S_p itself if it is
+ *   not finite (no 0 * inf is formed).
+ *   Every iteration, for the centre p: without stop_p, w_lum = 1 for all its taps, no prefilter, and a variance of 0 does not pass
+ *   through (only a texel that is not finite does); with stop_p, the luminance stop and the pass-through rule above, and in
+ *   PREFILTERED / SPATIAL_EARLY g_p -- over the 3 x 3 finite taps var_q, whatever their tiles' stop -- replaces var_p in both.  A
+ *   tap's own stop is never read: the centre decides.  The propagated variance, the centre tap, skipped taps and alpha are as
+ *   above.
+ *   A tile with n_t = 0 (black, S = 0, no stop) is therefore not left black: its neighbours' colour is filtered into it through
+ *   the edge stops alone, as far as the taps reach (in SPATIAL_EARLY it is in its spatial phase and has a stop: its estimate is 0
+ *   over a black tile, so its interior passes through until its border has been filled).  When every n_t equals n, the image is bit for bit the uniform filter's for n frames in the same mode.
+ *   The first such denoise, and the first after a tile has passed the K table's length, may wait once (bounded) for the ctx's
+ *   stream while the device's table of K(n) is made (the table of the per-tile noise report; nothing else is created). */
 typedef struct {                 /* 48 bytes */
     uint32_t size;               /* sizeof(mrt_denoise_params): the version of this struct */
     uint32_t iterations;         /* 1 .. 8 (default 5: steps 1 .. 16) */
@@ -566,9 +589,17 @@ enum { MRT_DENOISE_VAR_ACCUMULATED = 0,   /* default: var = S * K, the filter ab
  * a denoise holds in every mode. */
 int mrt_set_denoise_variance(mrt_ctx* ctx, uint32_t mode, uint32_t spatial_frames);
 int mrt_get_denoise_variance(mrt_ctx* ctx, uint32_t* mode, uint32_t* spatial_frames);   /* either pointer may be NULL */
+/* Whether an adaptive accumulation is denoised ("Adaptive accumulations" above) or refused; off by default.  On, mrt_read_denoised
+ * and MRT_PRESENT_DENOISED of a diverged accumulation run the per-tile filter instead of returning MRT_ERR_STATE; every other
+ * refusal stays (tracking off, a shard, no scene, DENOISED | GATHERED, the gathers' refusal of an adaptive accumulation,
+ * everything temporal), and an accumulation that has not diverged is denoised exactly as with the setting off: the same launches,
+ * the same bits.  The setting creates nothing, lives as long as the denoise parameters do (it survives mrt_reset, mrt_set_shard,
+ * mrt_set_world* and mrt_set_camera) and takes effect at the next denoise.  ctx NULL, or enabled NULL: MRT_ERR_INVALID_ARG. */
+int mrt_set_denoise_adaptive(mrt_ctx* ctx, int enabled);
+int mrt_get_denoise_adaptive(mrt_ctx* ctx, int* enabled);
 /* Denoises the most recent frame (queued on the ctx's stream behind its blend) and reads it back: height * width * 4 floats,
  * row 0 = bottom, as mrt_read_framebuffer; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE with tracking off or on a
- * shard, MRT_ERR_NO_SCENE without a scene. */
+ * shard, or after divergence without mrt_set_denoise_adaptive; MRT_ERR_NO_SCENE without a scene. */
 int mrt_read_denoised(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
 
 /* ------------------------------------------------------------------ temporal reprojection (no reference counterpart)

@@ -257,6 +257,15 @@ int mrt_debug_load_temporal(mrt_ctx* ctx, const float* h0, const float* h1, cons
  * read: cap in pixels.  load: everything else as mrt_debug_load_temporal with every array NULL leaves it. */
 int mrt_debug_read_temporal_fast(mrt_ctx* ctx, float* h2, size_t cap);
 int mrt_debug_load_temporal_fast(mrt_ctx* ctx, const float* h2);
+/* Diagnostic of the denoiser and adaptive sampling: an accumulation of the caller's in the place of the context's own, so that a
+ * test can put non-finite texels, tiles of 0 or 1 frames and any map of n_t in front of the product's denoise and noise report.
+ * World 1 only (a shard: MRT_ERR_STATE).  Waits (bounded) for the frames in flight, then overwrites what mrt_read_framebuffer
+ * (rgba: height * width * 4 floats, row 0 = bottom), mrt_read_noise (S: height * width floats; MRT_ERR_STATE with tracking off)
+ * and mrt_read_tile_frames (tile_frames: one count per tile, each < 2^20, else MRT_ERR_INVALID_ARG and nothing changed) read;
+ * any pointer may be NULL and leaves that part as it is.  tile_frames makes the accumulation adaptive if it is not yet -- as
+ * the first subset frame of mrt_render_tiles would, with the one allocation of that step -- and sets the device's and the host's
+ * copy of the map; nothing else is allocated.  mrt_frames_done is untouched; mrt_reset returns to the uniform state. */
+int mrt_debug_load_accumulation(mrt_ctx* ctx, const float* rgba, const float* S, const uint32_t* tile_frames);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,7 @@ EXPORTS = [
     "mrt_temporal_response_default", "mrt_set_temporal_response", "mrt_get_temporal_response",
     "mrt_debug_read_temporal_fast", "mrt_debug_load_temporal_fast",
     "mrt_set_gather_noise", "mrt_read_gathered_noise", "mrt_read_gathered_denoised", "mrt_debug_read_gathered_guides",
+    "mrt_set_denoise_adaptive", "mrt_get_denoise_adaptive", "mrt_debug_load_accumulation",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -353,6 +354,9 @@ def load():
         "mrt_debug_denoise": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), vp]),
         "mrt_set_denoise_variance": (i32, [vp, u32, u32]),
         "mrt_get_denoise_variance": (i32, [vp, P(u32), P(u32)]),
+        "mrt_set_denoise_adaptive": (i32, [vp, C.c_int]),
+        "mrt_get_denoise_adaptive": (i32, [vp, P(C.c_int)]),
+        "mrt_debug_load_accumulation": (i32, [vp, vp, vp, vp]),
         "mrt_debug_denoise_variance": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), u32, vp]),
         "mrt_debug_read_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
         "mrt_render_tiles": (i32, [vp, vp, sz, u32]),

@@ -845,6 +845,30 @@ class State:
         self._check(self._L.mrt_get_denoise_variance(self._ctx, C.byref(mode), C.byref(frames)), "mrt_get_denoise_variance")
         return DENOISE_VARIANCE_MODES[mode.value], int(frames.value)
 
+    def set_denoise_adaptive(self, enabled: bool):
+        """Whether an adaptive accumulation (render_tiles / render_adaptive since the last reset) is denoised, with K and the
+        variance estimate chosen per tile, or refused (the default)."""
+        self._check(self._L.mrt_set_denoise_adaptive(self._ctx, int(bool(enabled))), "mrt_set_denoise_adaptive")
+
+    def denoise_adaptive(self) -> bool:
+        on = C.c_int()
+        self._check(self._L.mrt_get_denoise_adaptive(self._ctx, C.byref(on)), "mrt_get_denoise_adaptive")
+        return bool(on.value)
+
+    def debug_load_accumulation(self, rgba=None, S=None, tile_frames=None):
+        """Overwrite what read_framebuffer (rgba (H, W, 4) f32), read_noise (S (H, W) f32) and tile_frames (one u32 per tile;
+        makes the accumulation adaptive) read; None leaves a part as it is.  World 1 only."""
+        h, w = self.args.height, self.args.width
+        rgba = None if rgba is None else np.ascontiguousarray(rgba, np.float32)
+        S = None if S is None else np.ascontiguousarray(S, np.float32)
+        tf = None if tile_frames is None else np.ascontiguousarray(tile_frames, np.uint32).reshape(-1)
+        assert rgba is None or rgba.shape == (h, w, 4)
+        assert S is None or S.shape == (h, w)
+        assert tf is None or tf.size == ((w + 7) // 8) * ((h + 7) // 8)
+        self._check(self._L.mrt_debug_load_accumulation(self._ctx, None if rgba is None else rgba.ctypes.data,
+                                                        None if S is None else S.ctypes.data, None if tf is None else tf.ctypes.data),
+                    "mrt_debug_load_accumulation")
+
     def read_denoised(self) -> np.ndarray:
         """The most recent frame, denoised: (H, W, 4) f32, row 0 = bottom.  Needs noise tracking and world == 1; waits for the
         frames in flight, as read_framebuffer does."""

@@ -1,4 +1,5 @@
 // The denoiser of include/myraytracer_amd.h: the first-hit guides and the filter (denoise.hip).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -110,7 +111,7 @@ int denoise_check(mrt_ctx* c, const char* who, bool tracking) {
     if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) cannot be denoised", who, c->shard_world);
     if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
     if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
-    if (c->tiles_diverged)          // (K differs per tile: the filter has no definition for that yet)
+    if (c->tiles_diverged && !c->denoise_adaptive)      // (K differs per tile: the per-tile filter is opt-in, mrt_set_denoise_adaptive)
         return fail(c, MRT_ERR_STATE, "%s: the accumulation is adaptive (mrt_render_tiles since the last reset)", who);
     return MRT_OK;
 }
@@ -149,6 +150,18 @@ int queue_gathered_denoise(mrt_ctx* c) {
 
 // the most recent frame, denoised into d_den[2] (after denoise_check)
 int queue_denoise(mrt_ctx* c) {
+    if (c->denoise_adaptive && c->tiles_diverged) {
+        // K per tile: the device table covers every count of the host's map, which is the device's at this point of the stream
+        uint32_t most = 0;
+        for (uint32_t t : c->tile_frames) most = std::max(most, t);
+        MRT_TRY(mrt::ensure_k_table(c, most + 1u));
+        MRT_TRY(ensure_guides(c));
+        const mrt::TileField tiles{c->d_tile_frames, c->d_k_f32, c->tiles_x, c->denoise_var_mode, c->denoise_spatial_frames};
+        const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, 0.0f, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
+                                          c->args.width, c->args.height, c->denoise, 0, c->stream, nullptr, &tiles);
+        if (e) return fail(c, MRT_ERR_HIP, "per-tile denoise launch failed: %s", hipGetErrorString((hipError_t)e));
+        return MRT_OK;
+    }
     MRT_TRY(ensure_guides(c));
     const float K = (float)mrt::noise_factor_of(c->noise_c2);
     const uint32_t variance = variance_of(c->denoise_var_mode, c->frames_done, c->denoise_spatial_frames);
@@ -309,6 +322,18 @@ int mrt_get_denoise_variance(mrt_ctx* c, uint32_t* mode, uint32_t* spatial_frame
     if (!c) return MRT_ERR_INVALID_ARG;
     if (mode) *mode = c->denoise_var_mode;
     if (spatial_frames) *spatial_frames = c->denoise_spatial_frames;
+    return MRT_OK;
+}
+
+int mrt_set_denoise_adaptive(mrt_ctx* c, int enabled) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    c->denoise_adaptive = enabled != 0;
+    return MRT_OK;
+}
+
+int mrt_get_denoise_adaptive(mrt_ctx* c, int* enabled) {
+    if (!c || !enabled) return MRT_ERR_INVALID_ARG;
+    *enabled = c->denoise_adaptive ? 1 : 0;
     return MRT_OK;
 }
 

@@ -419,6 +419,154 @@ __global__ void __launch_bounds__(kTileX * kTileY) temporal_variance_kernel(cons
     A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
 }
 
+// ---- the filter of an adaptive accumulation (include/myraytracer_amd.h, "Adaptive accumulations") ----------------------------
+// Every 8 x 8 tile has its own frame count n_t, hence its own K and its own choice between the spatial estimate and S * K.  The
+// per-pixel state is read from tile_frames and the K table by every kernel below; it is uniform over a tile, so a wave (32 x 2
+// pixels: four tiles) splits at 8-lane granularity at worst.  Kernels of their own: the uniform path's keep their text.
+struct TilePixel {
+    bool spatial;               // SPATIAL_EARLY and n_p < spatial_frames: iteration 0's variance is the spatial estimate
+    bool stop;                  // spatial, or K_p finite: the centre has a luminance stop (constant over the iterations)
+    float K;
+};
+__device__ __forceinline__ TilePixel tile_pixel(const TileField& T, uint32_t x, uint32_t y) {
+    const uint32_t n = T.tile_frames[(size_t)(y / kBandRows) * T.tiles_x + x / kTileW];
+    TilePixel s;
+    s.K = T.Kf[n];
+    s.spatial = T.mode == MRT_DENOISE_VAR_SPATIAL_EARLY && n < T.spatial_frames;
+    s.stop = s.spatial || !__builtin_isinf(s.K);
+    return s;
+}
+
+// The field iteration 0 reads "as the previous iteration's": out = (r, g, b, var0).  A pixel of a tile that is still in its
+// spatial phase takes spatial_variance_kernel's estimate (its taps need a finite colour and S, whatever their own tile's count):
+// 49 taps for those pixels alone, divergent by design, as temporal_variance_kernel is.  Any other pixel: S * K_p, or without an
+// estimate (K_p = +inf) 0 for a finite S and S itself otherwise.
+__global__ void __launch_bounds__(kTileX * kTileY) tile_variance_kernel(const AtrousArgs A, const TileField T) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const TilePixel tp = tile_pixel(T, x, y);
+    const float4 cp = A.fb[i];
+    const float sp = A.S[i];
+    float var;
+    if (!tp.spatial) {
+        var = !__builtin_isinf(tp.K) ? sp * tp.K : (__builtin_isfinite(sp) ? 0.0f : sp);
+    } else {
+        var = sp;                               // S not finite: kept (the texel passes through)
+        if (__builtin_isfinite(sp)) {
+            var = 0.0f;                         // a colour that is not finite: passes through as well
+            if (__builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
+                const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+                const bool miss_p = __float_as_int(gp1.w) < 0;
+                const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+                float w[49], l[49];
+                uint64_t used = 0;
+                float m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+                for (int ty = 0; ty < 7; ty++) {
+#pragma unroll
+                    for (int tx = 0; tx < 7; tx++) {
+                        const int t = ty * 7 + tx;
+                        w[t] = 0.0f;
+                        l[t] = 0.0f;
+                        const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
+                        if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
+                        float wq, lq;
+                        if (tx == 3 && ty == 3) {
+                            wq = 1.0f;
+                            lq = lumf(cp.x, cp.y, cp.z);
+                        } else {
+                            const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                            const float4 cq = A.fb[q];
+                            const float sq = A.S[q];
+                            if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && __builtin_isfinite(sq)))
+                                continue;
+                            const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                            const bool miss_q = __float_as_int(gq1.w) < 0;
+                            wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
+                            lq = lumf(cq.x, cq.y, cq.z);
+                        }
+                        w[t] = wq;
+                        l[t] = lq;
+                        used |= 1ull << t;
+                        m0 = m0 + wq;
+                        m1 = m1 + wq * lq;
+                    }
+                }
+                const float mean = m1 / m0;
+                float m2 = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 49; t++) {
+                    if (!(used >> t & 1ull)) continue;
+                    const float d = l[t] - mean;
+                    m2 = m2 + w[t] * (d * d);
+                }
+                var = m2 / m0;
+            }
+        }
+    }
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
+}
+
+// An a-trous iteration whose CENTRE decides (a tap's own stop is never read).  A centre with a stop: atrous_kernel's luminance
+// stop and pass-through rule, with PF (PREFILTERED / SPATIAL_EARLY) on g_p as in atrous_prefilter_kernel.  A centre without
+// one: w_lum = 1 for all its taps, no prefilter, and a variance of 0 does not pass through.  Never the first reader of the
+// framebuffer: A.in is tile_variance_kernel's field or the previous iteration's output.
+template <bool PF, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const AtrousArgs A, const TileField T) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const bool stop = tile_pixel(T, x, y).stop;
+    const float4 cp = A.in[i];
+    float4 res = cp;
+    const bool fin = finite4(cp);
+    float gv = cp.w;
+    if (PF && stop && fin) gv = prefiltered_var<false>(A, x, y, cp);
+    // passed through: not finite, or (with a luminance stop) a (prefiltered) variance of 0
+    if (fin && !(stop && gv == 0.0f)) {
+        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+        const bool miss_p = __float_as_int(gp1.w) < 0;
+        const float lp = lumf(cp.x, cp.y, cp.z);
+        const float inv_l = stop ? 1.0f / (A.sigma_l * sqrtf(gv) + 1.0e-6f) : 0.0f;
+        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+        const float kern[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+        float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
+        const int step = (int)A.step;
+#pragma unroll
+        for (int ty = 0; ty < 5; ty++) {
+            const int yq = (int)y + (ty - 2) * step;
+            if (yq < 0 || yq >= (int)A.height) continue;
+#pragma unroll
+            for (int tx = 0; tx < 5; tx++) {
+                const int xq = (int)x + (tx - 2) * step;
+                if (xq < 0 || xq >= (int)A.width) continue;
+                float w = kern[tx] * kern[ty];
+                float4 cq = cp;
+                if (!(tx == 2 && ty == 2)) {
+                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                    cq = A.in[q];
+                    if (!finite4(cq)) continue;
+                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                    const bool miss_q = __float_as_int(gq1.w) < 0;
+                    w = w * (stop ? tukey(fabsf(lp - lumf(cq.x, cq.y, cq.z)) * inv_l) : 1.0f);
+                    w = w * stop_normal(A, gp0, gq0);
+                    w = w * stop_depth(gp0, gq0, miss_p, miss_q, inv_z);
+                    w = w * stop_albedo(A, gp1, gq1);
+                }
+                sw = sw + w;
+                sr = sr + w * cq.x;
+                sg = sg + w * cq.y;
+                sb = sb + w * cq.z;
+                sv = sv + (w * w) * cq.w;
+            }
+        }
+        res = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+    }
+    if (LAST) res.w = A.fb[i].w;
+    A.out[i] = res;
+}
+
 }  // namespace
 
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream) {
@@ -438,9 +586,9 @@ int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade
 
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
                    uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
-                   const TemporalField* temporal) {
+                   const TemporalField* temporal, const TileField* tiles) {
     if (width == 0 || height == 0) return 0;
-    if ((variance == 3) != (temporal != nullptr)) return (int)hipErrorInvalidValue;
+    if ((variance == 3) != (temporal != nullptr) || (tiles && temporal)) return (int)hipErrorInvalidValue;
     const bool spatial = variance >= 2;         // (iteration 0 reads a field made before it: the spatial estimate's, the history's)
     AtrousArgs A;
     A.fb = reinterpret_cast<const float4*>(fb);
@@ -456,6 +604,26 @@ int launch_denoise(const float* fb, const float* S, float K, const float* guides
     const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
     hipStream_t st = (hipStream_t)stream;
     float4* buf[2] = {reinterpret_cast<float4*>(ping), reinterpret_cast<float4*>(pong)};
+    if (tiles) {            // an adaptive accumulation: the per-pixel field into pong, then iterations whose centre decides
+        if (tiles->mode > MRT_DENOISE_VAR_SPATIAL_EARLY || !tiles->tile_frames || !tiles->Kf ||
+            tiles->tiles_x != (width + kTileW - 1) / kTileW)
+            return (int)hipErrorInvalidValue;
+        A.K = 0.0f; A.lum_stop = 0u;            // (not read: K and the stop are per pixel)
+        A.out = buf[1];
+        hipLaunchKernelGGL(tile_variance_kernel, grid, block, 0, st, A, *tiles);
+        const bool pf = tiles->mode != MRT_DENOISE_VAR_ACCUMULATED;
+        for (uint32_t it = 0; it < prm.iterations; it++) {
+            const bool last = it + 1 == prm.iterations;
+            A.step = 1u << it;
+            A.in = buf[(it + 1) & 1u];
+            A.out = last ? reinterpret_cast<float4*>(out) : buf[it & 1u];
+            if (pf && last) hipLaunchKernelGGL((atrous_tiles_kernel<true, true>), grid, block, 0, st, A, *tiles);
+            else if (pf) hipLaunchKernelGGL((atrous_tiles_kernel<true, false>), grid, block, 0, st, A, *tiles);
+            else if (last) hipLaunchKernelGGL((atrous_tiles_kernel<false, true>), grid, block, 0, st, A, *tiles);
+            else hipLaunchKernelGGL((atrous_tiles_kernel<false, false>), grid, block, 0, st, A, *tiles);
+        }
+        return (int)hipGetLastError();
+    }
     // without a luminance stop there is nothing to prefilter: today's kernels
     const bool prefilter = variance != 0 && A.lum_stop;
     if (spatial) {          // into pong, where iteration 0 reads it as "the previous iteration's" (and iteration 1 writes pong after it)

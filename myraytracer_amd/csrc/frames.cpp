@@ -598,6 +598,9 @@ static int begin_tile_frames(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// mrt_debug_load_accumulation's bound on a loaded n_t: the K tables have an entry per count (12 bytes each on the device)
+static constexpr uint32_t kMaxLoadedTileFrames = 1u << 20;
+
 // the slot's tile list on the device and its pinned staging copy, on first use
 static int alloc_tile_list(mrt_ctx* c, mrt_ctx::FrameSlot& S) {
     if (!S.d_tile_list) HIP_TRY(c, hipMalloc((void**)&S.d_tile_list, (size_t)c->n_tiles * sizeof(uint32_t)));
@@ -868,6 +871,28 @@ int mrt_read_tile_frames(mrt_ctx* c, uint32_t* out, size_t cap, uint32_t* tiles_
     MRT_TRY(mrt::wait_stream(c, c->stream, __func__));
     if (!c->tiles_diverged) std::fill(out, out + n, c->frames_done);
     return MRT_OK;
+}
+
+// diagnostic: an accumulation of the caller's in the place of the context's own (world 1; allocates nothing beyond what the first
+// subset frame would)
+int mrt_debug_load_accumulation(mrt_ctx* c, const float* rgba, const float* S, const uint32_t* tile_frames) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_debug_load_accumulation: a shard (world %u)", c->shard_world);
+    if (S && !c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_debug_load_accumulation: S without noise tracking (mrt_set_noise_tracking)");
+    for (uint32_t t = 0; tile_frames && t < c->n_tiles; t++)
+        if (tile_frames[t] >= kMaxLoadedTileFrames)
+            return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_load_accumulation: tile %u at %u frames (< %u)", t, tile_frames[t], kMaxLoadedTileFrames);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, __func__));
+    const size_t n = (size_t)c->args.width * c->args.height;
+    if (rgba && n) HIP_TRY(c, hipMemcpyAsync(c->d_fb[c->target ^ 1], rgba, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (S && n) HIP_TRY(c, hipMemcpyAsync(c->d_noise_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (tile_frames && c->n_tiles) {
+        MRT_TRY(begin_tile_frames(c));
+        HIP_TRY(c, hipMemcpyAsync(c->d_tile_frames, tile_frames, (size_t)c->n_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        c->tile_frames.assign(tile_frames, tile_frames + c->n_tiles);
+    }
+    return mrt::wait_stream(c, c->stream, __func__);        // (the caller's arrays are pageable: theirs again on return)
 }
 
 }  // extern "C"

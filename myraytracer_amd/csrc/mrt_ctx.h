@@ -238,6 +238,7 @@ struct mrt_ctx {
     mrt_denoise_params denoise = mrt::denoise_defaults();
     uint32_t denoise_var_mode = MRT_DENOISE_VAR_ACCUMULATED;   // mrt_set_denoise_variance: where the luminance stop's variance comes from
     uint32_t denoise_spatial_frames = 3;                       // SPATIAL_EARLY: the spatial estimate while frames_done < this
+    bool denoise_adaptive = false;                  // mrt_set_denoise_adaptive: a diverged accumulation is filtered per tile, not refused
     bool guides_stale = true;
     float* d_guide_rays = nullptr;                  // 6 floats per pixel
     int32_t* d_guide_hits = nullptr;                // {sphere | -1, bits of t} per pixel (the DBG render kernel's output)
@@ -344,6 +345,9 @@ void free_tile_frames(mrt_ctx* c);
 void free_noise_buffers(mrt_ctx* c);
 int alloc_noise_buffers(mrt_ctx* c);
 int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, void** partials);
+// ... and adaptive sampling's device tables K(n), n < k_len, grown to at least `len` entries (a per-tile noise report's and a
+// per-tile denoise's: both read d_k_f32 on the ctx's stream, which is drained once before a larger table replaces the old one)
+int ensure_k_table(mrt_ctx* c, uint32_t len);
 // denoise.cpp: the denoiser's buffers released; its part of mrt_present (present.cpp): the refusals; the denoise queued, *src = its output
 void free_denoise_buffers(mrt_ctx* c);
 int present_denoised_check(mrt_ctx* c);

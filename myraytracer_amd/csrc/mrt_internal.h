@@ -325,9 +325,14 @@ int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade
 // moments from h1, var as "temporal reprojection" defines it (temporal_variance_kernel, into pong as variance 2's) -- and every
 // iteration prefiltered; S and K are not read, fb gives the alpha.
 struct TemporalField { const float* h0; const float* h1; uint32_t spatial_len; };
+// `tiles` (an adaptive accumulation, "Adaptive accumulations" of the header's denoiser section; not with `temporal`): K and
+// `variance` are not read.  Pixel p of tile (y / 8) * tiles_x + x / 8 has n_p = tile_frames[tile], K_p = Kf[n_p] (Kf: K(n) as
+// float for every n the map holds) and mode / spatial_frames choose its variance and stop: one launch for the field (into pong,
+// as variance 2's) and prm.iterations launches whose centre pixel decides on the luminance stop.  ping and pong are both used.
+struct TileField { const uint32_t* tile_frames; const float* Kf; uint32_t tiles_x, mode, spatial_frames; };
 int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
                    uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
-                   const TemporalField* temporal = nullptr);
+                   const TemporalField* temporal = nullptr, const TileField* tiles = nullptr);
 inline mrt_denoise_params denoise_defaults() {
     mrt_denoise_params p{};
     p.size = sizeof(mrt_denoise_params);

@@ -33,7 +33,8 @@ static void usage() {
         "                      check earlier finds noisy, and the loop also stops when no pixel is above rel 0.02; prints frames,\n"
         "                      samples and tiles selected per check\n"
         "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png); with several GPUs the\n"
-        "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame\n"
+        "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame; with\n"
+        "                      --adaptive the per-tile filter of an adaptive accumulation is turned on (mrt_set_denoise_adaptive)\n"
         "  --denoise-variance: the luminance stop's variance (mrt_set_denoise_variance): the pixel's own accumulated estimate\n"
         "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n");
 }
@@ -144,6 +145,8 @@ int main(int argc, char** argv) {
         if (hint_div) TRY(ctxs[i], mrt_set_schedule_hint(ctxs[i], hint_div, hint_mult));
         if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
         TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
+        // an adaptive run's tiles end at their own frame counts: its denoise is the per-tile filter (one GPU: checked below)
+        if (adaptive && !denoise_out.empty()) TRY(ctxs[i], mrt_set_denoise_adaptive(ctxs[i], 1));
     }
     // several GPUs: the noise estimate travels with the gather, and the first GPU denoises the gathered frame
     if (!denoise_out.empty() && n_gpus > 1) TRY(ctxs[0], mrt_set_gather_noise(ctxs[0], 1));

@@ -35,6 +35,30 @@ int alloc_noise_buffers(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// Adaptive sampling: K(n) = mrt_noise_factor(n, max_w) for n < len on the device (as float and as double), grown by doubling.
+// The host table continues the c2 recursion of mrt_noise_factor; a larger device table replaces the old one after the ctx's
+// stream -- the only one whose reductions read it -- has drained (a handful of times per accumulation).
+int ensure_k_table(mrt_ctx* c, uint32_t len) {
+    if (len <= c->k_len) return MRT_OK;
+    uint32_t cap = std::max<uint32_t>(c->k_len ? c->k_len : 4096u, 4096u);
+    while (cap < len) cap = cap > 0x7FFFFFFFu ? 0xFFFFFFFFu : 2u * cap;
+    const float max_w = c->args.max_framebuffer_weight;
+    while (c->k_table.size() < cap) {
+        c->k_table.push_back(mrt::noise_factor_of(c->k_c2));     // K after k_table.size() frames
+        c->k_c2 = mrt::noise_c2_next(c->k_c2, mrt_frame_weight((uint32_t)(c->k_table.size() - 1), max_w));
+    }
+    std::vector<float> kf(c->k_table.begin(), c->k_table.end());
+    MRT_TRY(mrt::wait_stream(c, c->stream, "growing the K table"));
+    mrt::free_device(c->d_k_f32, c->d_k_f64);
+    c->k_len = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f32, (size_t)cap * sizeof(float)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_k_f64, (size_t)cap * sizeof(double)));
+    HIP_TRY(c, hipMemcpy(c->d_k_f32, kf.data(), (size_t)cap * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_k_f64, c->k_table.data(), (size_t)cap * sizeof(double), hipMemcpyHostToDevice));
+    c->k_len = cap;
+    return MRT_OK;
+}
+
 }  // namespace mrt
 
 // ---- noise estimate (include/myraytracer_amd.h, "noise estimate") ----------------------------------------------------------
@@ -74,30 +98,6 @@ void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s, bool per_tile = fa
 }
 
 bool noise_args_ok(float threshold, float floor_) { return std::isfinite(threshold) && std::isfinite(floor_) && floor_ >= 0.0f; }
-
-// Adaptive sampling: K(n) = mrt_noise_factor(n, max_w) for n < len on the device (as float and as double), grown by doubling.
-// The host table continues the c2 recursion of mrt_noise_factor; a larger device table replaces the old one after the ctx's
-// stream -- the only one whose reductions read it -- has drained (a handful of times per accumulation).
-int ensure_k_table(mrt_ctx* c, uint32_t len) {
-    if (len <= c->k_len) return MRT_OK;
-    uint32_t cap = std::max<uint32_t>(c->k_len ? c->k_len : 4096u, 4096u);
-    while (cap < len) cap = cap > 0x7FFFFFFFu ? 0xFFFFFFFFu : 2u * cap;
-    const float max_w = c->args.max_framebuffer_weight;
-    while (c->k_table.size() < cap) {
-        c->k_table.push_back(mrt::noise_factor_of(c->k_c2));     // K after k_table.size() frames
-        c->k_c2 = mrt::noise_c2_next(c->k_c2, mrt_frame_weight((uint32_t)(c->k_table.size() - 1), max_w));
-    }
-    std::vector<float> kf(c->k_table.begin(), c->k_table.end());
-    MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_noise_query: growing the K table"));
-    mrt::free_device(c->d_k_f32, c->d_k_f64);
-    c->k_len = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_k_f32, (size_t)cap * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_k_f64, (size_t)cap * sizeof(double)));
-    HIP_TRY(c, hipMemcpy(c->d_k_f32, kf.data(), (size_t)cap * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_k_f64, c->k_table.data(), (size_t)cap * sizeof(double), hipMemcpyHostToDevice));
-    c->k_len = cap;
-    return MRT_OK;
-}
 
 }  // namespace
 
@@ -157,7 +157,7 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
     } else {                        // adaptive sampling: K per tile; the report's K is the largest (the least-sampled tile's)
         uint32_t most = 0;
         for (uint32_t t : c->tile_frames) most = std::max(most, t);
-        MRT_TRY(ensure_k_table(c, most + 1u));
+        MRT_TRY(mrt::ensure_k_table(c, most + 1u));
         K = 0.0;
         for (uint32_t t : c->tile_frames) K = std::max(K, c->k_table[t]);
         e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
