@@ -240,9 +240,17 @@ int mrt_debug_pool_clusters(const mrt_sphere* spheres, size_t n, uint32_t max_le
  * masks do not apply -- a large scene, more than 128 top records, a shard that outgrew the table), words per entry (4), whether the
  * most recent render launch ran with them, whether the table is built for the current scene / camera / shard}; with `out` (cap_words
  * >= entries x 4) the table itself, entry e = texels 8 e .. 8 e + 7 of the shard's row-major order, top record 32 w + i at bit
- * 31 - i of word w.  MRT_ERR_NO_SCENE without a scene, MRT_ERR_TOO_SMALL for a short buffer. */
+ * 31 - i of word w.  MRT_ERR_NO_SCENE without a scene, MRT_ERR_TOO_SMALL for a short buffer.
+ * Camera-ray sphere lists: built with the masks and switched with them.  A launch with enough pixels to be bound by throughput gets
+ * the lists instead of the masks -- its camera rays are resolved in the lane against their entry's member slots -- and info[2] is 2
+ * after it (1: the masks).  mrt_debug_set_camera_masks(ctx, 2) gives every launch the tables apply to the lists, 3 the masks (1: the
+ * library's rule).  mrt_debug_read_camera_lists: the same info[4], and with
+ * `out` the lists' table, 4 words per entry of the same indexing: word 0 = the number of level-0 member slots a camera ray of the
+ * entry's texels can touch, at most 8, or 0xFFFFFFFF for an entry with more (its rays take world_hit; so does every entry before
+ * the first build); words 1 .. 3 = the slot ids in ascending order, 10 bits each, id k at bits 10 k .. 10 k + 9 of the 96 bits. */
 int mrt_debug_set_camera_masks(mrt_ctx* ctx, int on);
 int mrt_debug_read_camera_masks(mrt_ctx* ctx, uint32_t info[4], uint32_t* out, size_t cap_words);
+int mrt_debug_read_camera_lists(mrt_ctx* ctx, uint32_t info[4], uint32_t* out, size_t cap_words);
 /* Diagnostics of temporal reprojection: the context's OWN history (the pair the next step reads: h0 = (r, g, b, len), h1 = (m1,
  * m2, t, index bits), 4 floats a pixel each, y * width + x), its previous spheres (4 floats each) and, for the load, its previous
  * derived camera, read / overwritten behind the ctx's stream, so that a test can start a step from a synthetic history.  They

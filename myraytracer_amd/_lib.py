@@ -47,7 +47,7 @@ EXPORTS = [
     "mrt_render_tiles", "mrt_render_adaptive", "mrt_read_tile_frames",
     "mrt_debug_check_context", "mrt_debug_sort_tiles", "mrt_debug_read_tile_schedule", "mrt_debug_read_hierarchy",
     "mrt_regroup_spheres", "mrt_debug_regroup_info", "mrt_debug_set_regroup_block", "mrt_debug_pool_clusters",
-    "mrt_debug_set_camera_masks", "mrt_debug_read_camera_masks",
+    "mrt_debug_set_camera_masks", "mrt_debug_read_camera_masks", "mrt_debug_read_camera_lists",
     "mrt_temporal_params_default", "mrt_set_temporal", "mrt_get_temporal", "mrt_temporal_step", "mrt_temporal_reset",
     "mrt_read_temporal", "mrt_debug_read_temporal", "mrt_debug_load_temporal",
     "mrt_temporal_response_default", "mrt_set_temporal_response", "mrt_get_temporal_response",
@@ -256,6 +256,7 @@ def load():
         "mrt_debug_set_regroup_block": (i32, [vp, u32]),
         "mrt_debug_set_camera_masks": (i32, [vp, i32]),
         "mrt_debug_read_camera_masks": (i32, [vp, vp, vp, sz]),
+        "mrt_debug_read_camera_lists": (i32, [vp, vp, vp, sz]),
         "mrt_debug_pool_clusters": (i32, [vp, sz, u32, u32, vp]),
         "mrt_pack_world": (i32, [vp, sz, P(MrtWorld), vp, sz, P(sz), vp, sz, P(sz), vp, sz, P(sz)]),
         "mrt_set_camera": (i32, [vp, P(MrtCamera)]),

@@ -315,20 +315,31 @@ class State:
         return dict(n_pool=int(out[0]), block=int(out[1]), global_depths=int(out[2]), lds_depths=int(out[3]))
 
     def debug_set_camera_masks(self, on: bool):
-        """the camera-ray cluster masks off / on for the launches that follow (mrt_debug_set_camera_masks); images do not change"""
-        self._check(self._L.mrt_debug_set_camera_masks(self._ctx, 1 if on else 0), "mrt_debug_set_camera_masks")
+        """the camera-ray cluster masks and sphere lists off / on for the launches that follow (mrt_debug_set_camera_masks); 2: the lists
+        wherever the tables apply, 3: the masks; images do not change"""
+        self._check(self._L.mrt_debug_set_camera_masks(self._ctx, int(on)), "mrt_debug_set_camera_masks")
 
     def debug_read_camera_masks(self, table: bool = True) -> dict:
         """entries, words per entry, whether the last launch ran with the masks and whether the table is built for the current
         scene / camera / shard; with `table` the (entries, 4) uint32 array itself (mrt_debug_read_camera_masks)"""
         info = (C.c_uint32 * 4)()
         self._check(self._L.mrt_debug_read_camera_masks(self._ctx, info, None, 0), "mrt_debug_read_camera_masks")
-        out = dict(entries=int(info[0]), words=int(info[1]), in_force=bool(info[2]), built=bool(info[3]), masks=None)
+        out = dict(entries=int(info[0]), words=int(info[1]), in_force=bool(info[2]), built=bool(info[3]), masks=None, lists=info[2] == 2)
         if table and out["entries"]:
             m = np.zeros((out["entries"], 4), np.uint32)
             self._check(self._L.mrt_debug_read_camera_masks(self._ctx, info, m.ctypes.data, m.size), "mrt_debug_read_camera_masks")
             out["masks"] = m
         return out
+
+    def debug_read_camera_lists(self) -> np.ndarray:
+        """the camera-ray sphere lists built with the masks: (entries, 4) uint32, word 0 the count (0xFFFFFFFF: overflowed), words
+        1 .. 3 the member slots, 10 bits each (mrt_debug_read_camera_lists); no entries where the masks do not apply"""
+        info = (C.c_uint32 * 4)()
+        self._check(self._L.mrt_debug_read_camera_lists(self._ctx, info, None, 0), "mrt_debug_read_camera_lists")
+        m = np.zeros((int(info[0]), 4), np.uint32)
+        if len(m):
+            self._check(self._L.mrt_debug_read_camera_lists(self._ctx, info, m.ctypes.data, m.size), "mrt_debug_read_camera_lists")
+        return m
 
     def debug_set_regroup_block(self, clusters: int):
         self._check(self._L.mrt_debug_set_regroup_block(self._ctx, clusters), "mrt_debug_set_regroup_block")

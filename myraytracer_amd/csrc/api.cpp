@@ -115,6 +115,7 @@ void free_world(mrt_ctx* c) {
     c->cam_mask_entries = 0;
     c->cam_mask_built = 0;
     c->cam_masks_in_force = false;
+    c->cam_lists_in_force = false;
     c->cam_mask_gen++;
     c->have_world = false;
     c->guides_stale = true;

@@ -12,6 +12,13 @@
 // sqrt(r^2 + 14 eps |oc|^2 / a) of the centre; twice that here) and rho, h and the positions widened by 1e-5 relative.
 // The kernel reads the device's own member records (level 0 of `nodes`, members 4 m .. 4 m + 3 of cluster m), so it is right after
 // mrt_update_spheres and mrt_regroup_spheres; it creates nothing and runs in stream order.
+//
+// Camera-ray sphere lists: the same launch and the same member loop also keep the per-member answer the cluster bit is the OR of.
+// List entry e (the masks' indexing) is 4 words: x = the number of level-0 member slots whose bundle test passes for any valid
+// texel of the entry, at most kCamListCap, or kCamListOverflow when there are more; y, z, w = their slot ids in ascending order,
+// 10 bits each (a small scene's slots are below 1,024), id k at bits 10 k .. 10 k + 9 of the 96-bit word w:z:y.  The render
+// kernel resolves the camera ray of a texel against its entry's slots in the lane (kernels.hip, primary hit); an overflowed
+// entry's camera rays take world_hit.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"
 
@@ -42,7 +49,8 @@ __device__ __forceinline__ bool bundle_touches(double qx, double qy, double qz, 
 }
 
 // One thread per entry.  The workgroup first leaves every member's (O - centre, inflated radius) in LDS.
-__global__ void __launch_bounds__(kCamMaskBlock) cam_mask_kernel(const KParams P, uint32_t* __restrict__ out, uint32_t entries) {
+__global__ void __launch_bounds__(kCamMaskBlock) cam_mask_kernel(const KParams P, uint32_t* __restrict__ out, uint32_t* __restrict__ lists,
+                                                                  uint32_t entries) {
     __shared__ double mem[kCamMaskMembers][4];
     const uint32_t W = P.locals.shape[0], H = P.locals.shape[1];
     const uint32_t local_rows = P.tiles_x ? (P.n_tiles / P.tiles_x) * kBandRows : 0u;
@@ -103,28 +111,42 @@ __global__ void __launch_bounds__(kCamMaskBlock) cam_mask_kernel(const KParams P
         valid |= 1u << t;
     }
     uint32_t words[4] = {0u, 0u, 0u, 0u};
+    uint32_t count = 0;
+    uint64_t ids_lo = 0, ids_hi = 0;                                // the list's 96 bits: ids 0 .. 5 and a part of 6 | the rest
     for (uint32_t c = 0; c < n_top; c++) {
         bool set = false;
-        for (uint32_t k = 0; k < kClusterK && !set; k++) {
-            const double qx = mem[kClusterK * c + k][0], qy = mem[kClusterK * c + k][1], qz = mem[kClusterK * c + k][2];
-            const double R = mem[kClusterK * c + k][3];
+        for (uint32_t k = 0; k < kClusterK; k++) {
+            const uint32_t slot = kClusterK * c + k;
+            const double qx = mem[slot][0], qy = mem[slot][1], qz = mem[slot][2];
+            const double R = mem[slot][3];
             if (!(R >= 0.0)) continue;
             const double Q2 = qx * qx + qy * qy + qz * qz;
+            bool touched = false;
 #pragma unroll
             for (uint32_t t = 0; t < 8; t++)
-                if (!set && (valid >> t & 1u) != 0u) set = bundle_touches(qx, qy, qz, Q2, R, pcx[t], pcy[t], pcz[t], P2[t], hp[t], rho);
+                if (!touched && (valid >> t & 1u) != 0u) touched = bundle_touches(qx, qy, qz, Q2, R, pcx[t], pcy[t], pcz[t], P2[t], hp[t], rho);
+            if (!touched) continue;
+            set = true;
+            if (count < kCamListCap) {
+                const uint32_t pos = 10u * count;
+                if (pos < 64u) ids_lo |= (uint64_t)slot << pos;
+                if (pos + 10u > 64u) ids_hi |= pos >= 64u ? (uint64_t)slot << (pos - 64u) : (uint64_t)slot >> (64u - pos);
+            }
+            count++;
         }
         if (set) words[c >> 5] |= 0x80000000u >> (c & 31u);
     }
     reinterpret_cast<uint4*>(out)[e] = make_uint4(words[0], words[1], words[2], words[3]);
+    reinterpret_cast<uint4*>(lists)[e] = count <= kCamListCap ? make_uint4(count, (uint32_t)ids_lo, (uint32_t)(ids_lo >> 32), (uint32_t)ids_hi)
+                                                               : make_uint4(kCamListOverflow, 0u, 0u, 0u);
 }
 
 }  // namespace
 
-int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t entries, void* stream) {
+int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t* lists, uint32_t entries, void* stream) {
     if (entries == 0) return 0;
     hipLaunchKernelGGL(cam_mask_kernel, dim3((entries + kCamMaskBlock - 1) / kCamMaskBlock), dim3(kCamMaskBlock), 0, (hipStream_t)stream,
-                       p, masks, entries);
+                       p, masks, lists, entries);
     return (int)hipGetLastError();
 }
 

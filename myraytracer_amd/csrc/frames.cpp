@@ -301,23 +301,37 @@ static void batch_shuffles(const mrt_ctx* c, uint32_t batch, mrt::KParams& p) {
     }
 }
 
-// Camera-ray cluster masks (cam_mask.hip): p.cam_masks for this launch, the table rebuilt first when it is stale and a build
-// pays: always from kCamMaskAlwaysSpp samples per pixel and launch on, otherwise once the generation has survived a frame (a
-// viewer that moves its camera every frame below that never pays a build).  The threshold is the measured build time over the
-// measured saving per sample (profiles/cam_mask_rates.txt: 3.2 ms at 1080p against 5.7 - 6.6 us per sample per pixel; both
-// scale with the pixel count): a lone frame breaks even at about 512 samples per pixel.  The masks apply to a small scene of at
-// most kCamMaskRecords top records whose table holds the shard, and to launches whose `texel` is the pixel's own: the stream
-// mode's queue layers add a layer offset to it and run without masks.
+// Camera-ray cluster masks and sphere lists (cam_mask.hip, one table of each from one build): which of the two this launch gets,
+// the tables rebuilt first when they are stale and a build pays.
+// The tables apply to a small scene of at most kCamMaskRecords top records whose table holds the shard, and to launches whose
+// `texel` is the pixel's own: the stream mode's queue layers add a layer offset to it and run without them.
+// A launch they apply to gets ONE of the two.  The lists (its camera rays are resolved in the lane: the SC = 3 instantiations of
+// render_kernel) take a third of the wave iterations away and make each about a sixth longer: that pays where the launch is
+// bound by throughput, and costs where it is bound by its longest pixel chains, whose many bounces per sample lose one slot in
+// ten and pay the longer iteration on every one (C2, 2.5 pixels per resident lane: a quarter less work for the same frame time).  So a launch
+// with fewer than kCamListMinPixelsPerLane pixels (tiles x queue layers x 64) per lane the chip holds gets the masks and runs
+// the kernel it ran before the lists existed.  Measured on C3's scene at 64 spp (profiles/cam_list_rates.txt, "shapes around
+// the rule"): up to 4.4 pixels per lane the frame takes the 8 ms of its longest chains whatever its size and the lists run 0.99 -
+// 1.03 x the masks' time; at 5.3 they run 0.86 x, at 6.3 (1080p) 0.83 x.  The rule reads the calls and the device alone.
+// mrt_debug_set_camera_masks can force either table.
+// A stale table is rebuilt always from a threshold of samples per pixel and launch on, otherwise once the generation has survived a
+// frame (a viewer that moves its camera every frame below that never pays a build).  The threshold is the measured build time over
+// the measured saving per sample, both proportional to the pixel count: kCamListAlwaysSpp for a launch that gets the lists (2.4 -
+// 2.9 ms at 1080p against 26 - 38 us per sample per pixel: a lone frame breaks even at about 96; profiles/cam_list_rates.txt),
+// kCamMaskAlwaysSpp for one that gets the masks (3.2 ms against 5.7 - 6.6 us; profiles/cam_mask_rates.txt).
 // The build runs on the frame's own side stream, behind enter_slot (the scene's uploads and refits are visible there) and ahead
 // of the render launch, and every slot builds for itself before its first frame of a generation (they write the same words; a
 // slot of a generation that some slot has built follows at once): a frame reads what its own stream has written, no stream
 // waits for another one's build -- a wait would start the waiting frames as a convoy -- and no frame in flight is held back.
 // Only a build for a NEW generation waits, for the other slots' frames that may still be reading the previous one.  Which
-// launches run with masks depends on the calls alone, never on timing.
-static constexpr uint32_t kCamMaskAlwaysSpp = 512;
+// launches run with the tables depends on the calls alone, never on timing.
+static constexpr uint32_t kCamListAlwaysSpp = 96, kCamMaskAlwaysSpp = 512;
+static constexpr uint64_t kCamListMinPixelsPerLane = 5;
 static int camera_masks(mrt_ctx* c, mrt_ctx::FrameSlot& S, mrt::KParams& p) {
     p.cam_masks = nullptr;
+    p.cam_lists = nullptr;
     c->cam_masks_in_force = false;
+    c->cam_lists_in_force = false;
     if (!S.render_pending) { S.cam_used_gen = 0; S.cam_stale_reader = false; }
     const uint64_t gen = c->cam_mask_gen;
     const bool survived = c->cam_mask_seen == gen;
@@ -327,21 +341,27 @@ static int camera_masks(mrt_ctx* c, mrt_ctx::FrameSlot& S, mrt::KParams& p) {
     if (!c->cam_masks_on || !c->d_cam_masks || !mrt::scene_is_small(c->n_members) || c->n_padded > mrt::kCamMaskRecords || need == 0 ||
         need > c->cam_mask_entries || !own_texel)
         return MRT_OK;
+    const bool lists = c->cam_prefer == 1u ||
+                       (c->cam_prefer == 0u && (uint64_t)p.n_tiles * p.queue_layers * 64u >= kCamListMinPixelsPerLane * c->n_waves * 64u);
     if (S.cam_built != gen) {
-        if (c->cam_mask_built != gen && !survived && (uint64_t)c->locals.samples_per_frame * p.lane_frames < kCamMaskAlwaysSpp) return MRT_OK;
+        if (c->cam_mask_built != gen && !survived &&
+            (uint64_t)c->locals.samples_per_frame * p.lane_frames < (lists ? kCamListAlwaysSpp : kCamMaskAlwaysSpp))
+            return MRT_OK;
         for (mrt_ctx::FrameSlot& T : c->slot)
             if (&T != &S && T.render_pending && (T.cam_stale_reader || (T.cam_used_gen != 0 && T.cam_used_gen != gen)))
                 HIP_TRY(c, hipStreamWaitEvent(S.stream, T.render_done, 0));
         mrt::KParams b = p;             // (a subset frame's p.n_tiles is its list's length: the masks cover the shard)
         b.tiles_x = c->tiles_x; b.n_tiles = c->n_tiles;
-        const int e = mrt::launch_cam_masks(b, c->d_cam_masks, (uint32_t)need, S.stream);
+        const int e = mrt::launch_cam_masks(b, c->d_cam_masks, c->cam_lists(), (uint32_t)need, S.stream);
         if (e) return fail(c, MRT_ERR_HIP, "camera mask launch failed: %s", hipGetErrorString((hipError_t)e));
         S.cam_built = gen;
         c->cam_mask_built = gen;
     }
     if (S.cam_used_gen != 0 && S.cam_used_gen != gen) S.cam_stale_reader = true;      // (an earlier frame of this slot, still pending)
     S.cam_used_gen = gen;
-    p.cam_masks = c->d_cam_masks;
+    if (lists) p.cam_lists = c->cam_lists();
+    else p.cam_masks = c->d_cam_masks;
+    c->cam_lists_in_force = lists;
     c->cam_masks_in_force = true;
     return MRT_OK;
 }

@@ -180,6 +180,38 @@ __device__ __forceinline__ KArgPtr cold_args() {
     return p;
 }
 
+// sphere_hit (shader.wgsl:274-296) of the ray (o, d), a = dot(d, d), by_a = divisor_of(a), on ONE sphere in the lane: the
+// discriminant, and for disc >= 0 (and the sphere not entirely behind the origin: see the node rounds) the roots and range tests
+// exactly as a root round does them, sqrt and quotients by `a` in their unscaled forms for the same reason.  `usable`: the lane's
+// ray is this one and admits the unscaled forms.  Returns (bits(t) << 32 | sidx) of the root the reference would take, kNoHitKey
+// without one: the minimum of the keys is the walk's 64-bit LDS minimum.  hq: the sphere's roots were tested.
+// For the direct spheres of world_hit and for the camera rays resolved in the lane (render_kernel, primary hit).
+__device__ __forceinline__ unsigned long long sphere_root_key(const float cx, const float cy, const float cz, const float nr2, const uint32_t sidx,
+                                                              const V3 o, const V3 d, const float a, const Divisor by_a, const bool usable, bool& hq) {
+    float bq, cq;
+    const float disc = sphere_quadratic(cx, cy, cz, nr2, o, d, a, bq, cq);
+    const bool cand = !(disc < 0.0f), ahead = (int32_t)(__float_as_uint(bq) | __float_as_uint(cq)) < 0;
+    hq = usable && cand && ahead;
+    const float d_sqrt = sqrt_unscaled(disc);                     // :286
+    const float t_min = 0.001f;                                   // :340
+    const float t_near = div_unscaled(-bq - d_sqrt, by_a);        // :290
+    const float t_far = div_unscaled(-bq + d_sqrt, by_a);         // :292
+    const bool ok_near = !(t_near < t_min) && t_near < 1.0e4f;
+    const bool ok_far = !(t_far < t_min) && t_far < 1.0e4f;
+    const float t = ok_near ? t_near : t_far;
+    return (hq && (ok_near || ok_far)) ? (((unsigned long long)__float_as_uint(t) << 32) | sidx) : kNoHitKey;
+}
+// normalize() of a new sample's camera ray where it is finished ahead of the tail's shared normalize (render_kernel, primary hit),
+// the same two forms: the literal expression if any lane has a component that is 0 or below 2^-90, or a squared length outside
+// [2^-60, 2^60).  (The tail keeps its own copy: as a call it changed the register allocation of every large-scene instantiation.)
+__device__ __forceinline__ V3 unit_direction(const V3 ndir) {
+    const float dd = dot3(ndir, ndir);
+    const float nd_min = __builtin_fminf(__builtin_fminf(__builtin_fabsf(ndir.x), __builtin_fabsf(ndir.y)), __builtin_fabsf(ndir.z));
+    if (__builtin_expect(__any(!normalize_unscaled_ok(dd, nd_min)), 0)) return normalize3(ndir);
+    const Divisor by_len = divisor_of(sqrt_unscaled(dd));
+    return v3(div_unscaled(ndir.x, by_len), div_unscaled(ndir.y, by_len), div_unscaled(ndir.z, by_len));
+}
+
 // A workgroup is kWavesPerGroup INDEPENDENT waves (each with its own FIFO, masks, queues); they share
 // one thing: when the scene is small enough (SMALL), a read-only LDS copy of the member records that
 // the walk gathers per item -- an L1 round trip per candidate cluster otherwise.  SMALL also means
@@ -190,12 +222,15 @@ constexpr uint32_t kWavesPerGroup = 4;
 // reaches the root tests is recorded in P.dbg_cand.  Nothing else of the kernel changes.
 // SC: the scene's layout -- 0 = SMALL (above), 1 / 2 = large, with the linear / the quadratic form of the box test's slack
 // (hierarchy.cpp build_boxes, bounds.h box_kpad; a compile-time choice: as a run-time flag it was two branches in every box test).
+// SC = 3: the small layout with the camera-ray sphere lists (cam_mask.hip) in force -- P.cam_lists is the table -- whose lanes resolve a
+// new sample's camera ray in the tail ("primary hit" below).  Instantiations of their own, so that every launch without the lists
+// runs the machine code it ran before they existed (scripts/isa_diff.py); never DBG.
 template <bool COUNT, bool PILOT, bool CTR, int SC, bool MFMA, bool DBG = false>
 // Registers: small scenes run 5 workgroups per CU (their LDS footprint, 31.5 KB at C3) = 5 waves per SIMD = 96 VGPRs; large
 // scenes (work queues of every level, u32 items: 33-36 KB per workgroup) fit 4 workgroups per CU whatever the kernel does, so
 // they may use the 128 VGPRs of 4 waves per SIMD instead of spilling at 96.
-__global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_waves_per_eu(SC == 0 ? 5 : 4, 8))) render_kernel(const KParams P) {
-    constexpr bool SMALL = SC == 0, QUAD = SC == 2;
+__global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_waves_per_eu(SC == 0 || SC == 3 ? 5 : 4, 8))) render_kernel(const KParams P) {
+    constexpr bool SMALL = SC == 0 || SC == 3, QUAD = SC == 2, LISTS = SC == 3;
     typedef typename Ent<SMALL>::type entry_t;
     constexpr uint32_t kIdBits = Ent<SMALL>::id_bits;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -274,6 +309,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
     uint32_t depth_left = 0, trips = 0;
     unsigned long long started = 0, bounces = 0;     // wave totals, counted by ballot where the control flow is uniform
     unsigned long long mtests = 0;       // wave-uniform
+    unsigned long long prim_slots = 0;   // wave total: camera rays resolved in the lane (the tail's primary hit), a lane slot each
 
 #ifdef MRT_STAMPS
     uint64_t phase_[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -349,7 +385,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // the lane's own mask words in LDS right before the sweep (every other ray parks all ones): nothing of it is live
             // in registers during the sweep.  Wave-uniform on the pointer (null: today's instructions).  Small scenes of at
             // most kCamMaskRecords records (one block, at most 4 words), never the caller's rays (DBG).
-            constexpr bool CAM = SMALL && !DBG;
+            constexpr bool CAM = SMALL && !DBG && !LISTS;       // (a launch with the lists has no masks)
             bool cam_on = false;
             uint4 cam_entry = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
             if constexpr (CAM) {
@@ -394,9 +430,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             const bool weird = !(a > 0.99999f && a < 1.00001f) || (MFMA && !(o_rel2 <= P.mfma_scale[3]));
             const bool usable = trace && !weird;
             // The few spheres far larger than the rest (a ground sphere) are outside the hierarchy: every ray does
-            // sphere_hit (shader.wgsl:274-296) on them itself, record in SGPRs -- discriminant, and for lanes with
-            // disc >= 0 (and the sphere not entirely behind the origin: see the node rounds) the roots and range tests
-            // exactly as a root round would, sqrt and quotients by `a` in their unscaled forms for the same reason.
+            // sphere_hit on them itself, record in SGPRs (sphere_root_key).
             // Their closest root is what the lane's hit slot starts from: a ground sphere is a candidate for most rays,
             // and as work items these were more than half of the root rounds' load.
             unsigned long long key0 = kNoHitKey;
@@ -407,18 +441,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 for (uint32_t j = 0; j < n_direct; j++) {
                     const float cx = C->direct[j].cx, cy = C->direct[j].cy, cz = C->direct[j].cz, nr2 = C->direct[j].neg_r2;
                     const uint32_t sidx = C->direct_index[j];
-                    float bq, cq;
-                    const float disc = sphere_quadratic(cx, cy, cz, nr2, o, d, a, bq, cq);
-                    const bool cand = !(disc < 0.0f), ahead = (int32_t)(__float_as_uint(bq) | __float_as_uint(cq)) < 0;
-                    const bool hq = usable && cand && ahead;
-                    const float d_sqrt = sqrt_unscaled(disc);                     // :286
-                    const float t_min = 0.001f;                                   // :340
-                    const float t_near = div_unscaled(-bq - d_sqrt, by_a);        // :290
-                    const float t_far = div_unscaled(-bq + d_sqrt, by_a);         // :292
-                    const bool ok_near = !(t_near < t_min) && t_near < 1.0e4f;
-                    const bool ok_far = !(t_far < t_min) && t_far < 1.0e4f;
-                    const float t = ok_near ? t_near : t_far;
-                    const unsigned long long key = (hq && (ok_near || ok_far)) ? (((unsigned long long)__float_as_uint(t) << 32) | sidx) : kNoHitKey;
+                    bool hq;
+                    const unsigned long long key = sphere_root_key(cx, cy, cz, nr2, sidx, o, d, a, by_a, usable, hq);
                     key0 = key < key0 ? key : key0;
                     if (DBG && hq) atomicOr(P.dbg_cand + (size_t)texel * P.dbg_words + (sidx >> 5), 1u << (sidx & 31u));
                 }
@@ -836,7 +860,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
         // their camera-ray draws share the rejection loop below with the hit lanes' unit-ball draws.
         bool start_sample = false;
         V3 ndir = d;
-        const bool hit = !DBG && live && depth_left != 0u && best >= 0;
+        bool hit = !DBG && live && depth_left != 0u && best >= 0;      // (+ below: a camera ray's hit resolved in the lane)
         if (!DBG && live && !hit) {
             if (depth_left != 0u) {
                 // color_sky, shader.wgsl:331-334, 343-345
@@ -958,7 +982,79 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // -- (a) lanes starting a sample: jitter and camera point (shader.wgsl:378-381); the lens-disk draws follow below
             V3 cam_p = v3(0.0f, 0.0f, 0.0f);
             bool need_lens = false;
-            if (start_sample) need_lens = new_sample_head(ndir, cam_p);
+            // Camera-ray sphere lists (cam_mask.hip): with them the lanes starting a sample FINISH their camera ray here -- a lens
+            // disk loop of their own, the normalize -- and resolve it in the lane: the direct spheres, then sphere_hit on the
+            // member slots of the texel's list entry (a handful: every member any camera ray of the texel can touch), records
+            // from the group's LDS copy, with the node rounds' "entirely behind" drop and the root rounds' tests, the (t, index)
+            // minimum in registers -- the winner and the tie rule of the walk's 64-bit LDS minimum.  A hit joins the bounce hits
+            // below (shading, the one unit-ball loop, the scatter, the final normalize) and the lane enters the next world_hit
+            // with its first bounce ray; a miss takes the sky's colour here and the lane idles one iteration, where the sample is
+            // accounted with the paths that end without a scatter.  The camera ray never rides the sweep and the walk.  It counts
+            // as one trip of the pixel, one world_hit call, one lane slot and its member tests.  An overflowed entry, a
+            // direction that is not unit length (world_hit's `weird`) and a ray depth of 0 leave the finished ray to the next
+            // iteration's world_hit as before.  Compiled into the SC = 3 instantiations alone.
+            bool own_ray = false;                   // this lane's camera ray was normalized here (not below)
+            if constexpr (LISTS) {
+                if (__any(start_sample)) {
+                    uint4 ent = make_uint4(kCamListOverflow, 0u, 0u, 0u);
+                    if (start_sample) {
+                        ent = reinterpret_cast<const uint4*>(cold_args()->cam_lists)[texel >> 3];
+                        if (new_sample_head(ndir, cam_p)) {
+                            float lx, ly;
+                            do { lx = rng_pm1(rng); ly = rng_pm1(rng); } while (__builtin_fmaf(ly, ly, lx * lx) > 1.0f);
+                            new_sample_lens(ndir, cam_p, lx, ly);
+                        }
+                        d = unit_direction(ndir);                           // :381
+                        ndir = d;
+                        own_ray = true;
+                    }
+                    const float a = dot3(d, d);
+                    const bool prim = start_sample && depth_left != 0u && ent.x != kCamListOverflow && a > 0.99999f && a < 1.00001f;
+                    const unsigned long long prim_mask = __builtin_amdgcn_ballot_w64(prim);
+                    const KArgPtr C = cold_args();
+                    const uint32_t n_direct = C->n_direct;
+                    const Divisor by_a = divisor_of(a);
+                    unsigned long long key = kNoHitKey;
+                    bool hq;
+                    for (uint32_t j = 0; j < n_direct; j++) {
+                        const unsigned long long kk = sphere_root_key(C->direct[j].cx, C->direct[j].cy, C->direct[j].cz, C->direct[j].neg_r2,
+                                                                      C->direct_index[j], o, d, a, by_a, prim, hq);
+                        key = kk < key ? kk : key;
+                    }
+                    if (!PILOT) mtests += (unsigned long long)n_direct * (uint32_t)__popcll(prim_mask);
+                    const uint32_t cnt = prim ? ent.x : 0u;
+                    uint32_t w0 = ent.y, w1 = ent.z, w2 = ent.w;            // the ids left, the next one lowest
+                    for (uint32_t k = 0;; k++) {
+                        const bool on = k < cnt;
+                        const unsigned long long on_mask = __builtin_amdgcn_ballot_w64(on);
+                        if (on_mask == 0ull) break;
+                        const uint32_t slot = on ? w0 & 1023u : 0u;
+                        w0 = __builtin_amdgcn_alignbit(w1, w0, 10u); w1 = __builtin_amdgcn_alignbit(w2, w1, 10u); w2 >>= 10u;
+                        const SphereRec sm = nodes[slot];
+                        const unsigned long long kk = sphere_root_key(sm.cx, sm.cy, sm.cz, sm.neg_r2, (uint32_t)index_lds[slot], o, d, a, by_a, on, hq);
+                        key = kk < key ? kk : key;
+                        if (!PILOT) mtests += (uint32_t)__popcll(on_mask);
+                    }
+                    if (!PILOT) {
+                        bounces += (uint32_t)__popcll(prim_mask);
+                        prim_slots += (uint32_t)__popcll(prim_mask);
+                    }
+                    if (prim) {
+                        pix_trips++;
+                        if ((int32_t)(uint32_t)key >= 0) {
+                            t_sup = __uint_as_float((uint32_t)(key >> 32));
+                            best = (int32_t)(uint32_t)key;
+                            hit = true;
+                            own_ray = false;                                // (the scattered direction is normalized below)
+                        } else {
+                            // color_sky, shader.wgsl:331-334, 343-345, as above; the sample is accounted one iteration on
+                            float t = 0.5f * d.y + 0.5f;
+                            color = color + att * v3(mixf(1.0f, 0.5f, t), mixf(1.0f, 0.7f, t), mixf(1.0f, 1.0f, t));     // :381
+                            depth_left = 0u;
+                        }
+                    }
+                }
+            } else if (start_sample) need_lens = new_sample_head(ndir, cam_p);
             // -- (b) lanes with a hit: the rest of sphere_hit for the winning sphere (:298-309) and the material's own part
             // (centre, radius) and (material colour, fuzz | ior) of sphere `best` come packed in two 16-byte records built
             // at upload from the reference's SoA arrays (sphere_load_* :254-268, albedo / fuzz loads :205, :232-240): the
@@ -1058,7 +1154,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             }
             // normalize() of the scattered direction (:354) and of the new sample's camera ray (:381), one code
             // path for the lanes of either kind
-            if (has_task && !task_done) {
+            // (with the camera-ray lists a new sample's ray has had its normalize above)
+            if (has_task && !task_done && !own_ray) {
                 // d = ndir / sqrt(dot(ndir, ndir)); as for the normal: the literal expression if any lane has a component
                 // that is 0 or below 2^-90, or a squared length outside [2^-60, 2^60)
                 const float dd = dot3(ndir, ndir);
@@ -1089,7 +1186,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             atomicAdd(P.counters + 0, c0);
             atomicAdd(P.counters + 1, c1);
             atomicAdd(P.counters + 2, c2);
-            atomicAdd(P.counters + 3, 64ull * trips);
+            atomicAdd(P.counters + 3, 64ull * trips + (LISTS ? prim_slots : 0ull));
             atomicAdd(P.counters + 4, (unsigned long long)mtests);     // wave-uniform
 #ifdef MRT_STAMPS
             for (int k = 0; k < 6; k++) atomicAdd(P.counters + 6 + k, (unsigned long long)phase_[k]);
@@ -1225,7 +1322,11 @@ static void launch_render_kernel(const KParams& p, uint32_t n_waves, hipStream_t
         };
         if (p.use_mfma != 0) go(IC<1>{}); else go(IC<0>{});
     };
-    if (scene_is_small(p.n_members)) with_sweep(IC<0>{});
+    if (scene_is_small(p.n_members)) {
+        // (a launch that got the camera-ray lists -- frames.cpp, camera_masks -- runs the instantiation that reads them)
+        if constexpr (!DBG) { if (p.cam_lists != nullptr) { with_sweep(IC<3>{}); return; } }
+        with_sweep(IC<0>{});
+    }
     else if (p.box_quad != 0) with_sweep(IC<2>{});
     else with_sweep(IC<1>{});
 }

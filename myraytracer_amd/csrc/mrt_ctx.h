@@ -55,10 +55,19 @@ struct mrt_ctx {
     // geometry updates, regroups, image shape and shard); cam_mask_built: the generation the table holds (0: none yet),
     // cam_mask_seen: the generation the previous frame was launched under (a generation that survives a frame is worth a
     // build).  cam_masks_on: mrt_debug_set_camera_masks; cam_masks_in_force: the most recent render launch got the table.
+    // The camera-ray sphere lists (4 words an entry, the same entries) are the second half of the same buffer -- cam_lists() --
+    // written by the same build: one allocation, one generation, one switch.  A launch the tables apply to gets one of the two
+    // (cam_prefer below).
     uint32_t* d_cam_masks = nullptr;
     size_t cam_mask_entries = 0;
+    uint32_t* cam_lists() const { return d_cam_masks ? d_cam_masks + 4 * cam_mask_entries : nullptr; }
     uint64_t cam_mask_gen = 1, cam_mask_built = 0, cam_mask_seen = 0;
     bool cam_masks_on = true, cam_masks_in_force = false;
+    // which of the two tables a launch gets (frames.cpp, camera_masks): cam_prefer 0 = the library's rule (the lists where the
+    // launch has the pixels to be bound by throughput, the masks where it is bound by its longest pixel chains), 1 = the lists,
+    // 2 = the masks (mrt_debug_set_camera_masks 1 / 2 / 3); cam_lists_in_force: the most recent render launch got the lists.
+    uint32_t cam_prefer = 0;
+    bool cam_lists_in_force = false;
     // The build runs on the side stream of the frame that needs it, and EVERY frame slot builds the table on its own stream before
     // its first frame of a generation (FrameSlot::cam_built): a slot's frames follow that slot's build in stream order, no stream
     // ever waits for another one's build, and the frames in flight are not held back.  The builds of one generation write the

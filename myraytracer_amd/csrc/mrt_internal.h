@@ -23,6 +23,8 @@ constexpr uint32_t kQueueCap = 320;      // a work queue of the walk: < 64 left 
 constexpr uint32_t kStackReserve = 16;   // large scenes' work stack: entries beyond its capacity a one-item round may use (3 per level)
 constexpr uint32_t kMaxDirect = 4;       // very large spheres tested by every ray directly, outside the hierarchy
 constexpr uint32_t kCamMaskRecords = 128; // camera-ray cluster masks (cam_mask.hip): one 128-bit entry covers at most this many top records
+constexpr uint32_t kCamListCap = 8;       // camera-ray sphere lists (cam_mask.hip): member slots one entry holds; more: kCamListOverflow
+constexpr uint32_t kCamListOverflow = 0xFFFFFFFFu;      // (an unbuilt table is all ones: every entry overflowed)
 // SMALL scenes (render_kernel's SC == 0): every node id of the hierarchy's n_members member slots fits 10 bits, so the hierarchy
 // has one level, the member records live in LDS and the walk's work items are u16; larger scenes walk the boxes
 inline bool scene_is_small(uint32_t n_members) { return n_members <= 1024u; }
@@ -141,6 +143,12 @@ struct KParams {
     // of the shard, entry texel >> 3, in the sweep's bit layout; the sweep ANDs them onto the candidate words of camera rays.
     // Null = off (today's instructions).  LAST, so that no other argument's offset moves.
     const uint32_t* cam_masks;
+    // Camera-ray sphere lists (cam_mask.hip, the same launch; the masks' indexing): 4 words per entry, the level-0 member slots a
+    // camera ray of the entry's texels can touch; the render kernel resolves such a ray in the lane, at the tail of the iteration
+    // that starts its sample (kernels.hip, primary hit).  Non-null selects the instantiations that read it (SC = 3, launch_render):
+    // a launch without it runs the kernels of before.  While they are in force cam_masks is null.  Appended behind cam_masks for
+    // the same reason.
+    const uint32_t* cam_lists;
 };
 
 // api.cpp: message behind mrt_last_error(NULL), for failures of entry points that have no context
@@ -264,8 +272,9 @@ struct RefitArgs {
     float origin[3];
 };
 // cam_mask.hip: the camera-ray cluster masks of p's scene (level 0 of p.nodes), camera, image shape and shard into `masks`,
-// `entries` entries of 4 words (entry e: texels 8 e .. 8 e + 7 of the shard's row-major order)
-int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t entries, void* stream);
+// `entries` entries of 4 words (entry e: texels 8 e .. 8 e + 7 of the shard's row-major order), and the camera-ray sphere lists
+// of the same entries into `lists`, 4 words each
+int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t* lists, uint32_t entries, void* stream);
 int launch_refit_scatter(const RefitScatterArgs& a, void* stream);
 int launch_refit(const RefitArgs& a, void* stream);
 

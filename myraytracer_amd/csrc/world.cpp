@@ -217,9 +217,11 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
     MRT_TRY(upload((void**)&c->d_member_index, hier.member_index.data(), hier.member_index.size() * sizeof(uint32_t)));
     if (mrt::scene_is_small(hier.n_members) && n_padded <= mrt::kCamMaskRecords) {
         // the camera-ray cluster masks (cam_mask.hip; frames.cpp builds them before a frame when it pays): an entry of 4 words per
-        // 8 texels of the shard as it is now, all ones until built.  A shard that outgrows it renders without masks.
+        // 8 texels of the shard as it is now, all ones until built.  A shard that outgrows it renders without masks.  Behind
+        // them, in the same buffer, the camera-ray sphere lists of the same entries (mrt_ctx::cam_lists), 4 words each: all
+        // ones is "overflowed" there.
         const size_t entries = std::max<size_t>((mrt::local_texels(c) + 7) / 8, 1);
-        const std::vector<uint32_t> ones(4 * entries, 0xFFFFFFFFu);
+        const std::vector<uint32_t> ones(8 * entries, 0xFFFFFFFFu);
         MRT_TRY(upload((void**)&c->d_cam_masks, ones.data(), ones.size() * sizeof(uint32_t)));
         c->cam_mask_entries = entries;
     }
@@ -465,7 +467,9 @@ int mrt_debug_set_sweep_axes(mrt_ctx* c, const float* axis) {
 
 int mrt_debug_set_camera_masks(mrt_ctx* c, int on) {
     if (!c) return MRT_ERR_INVALID_ARG;
+    if (on < 0 || on > 3) return MRT_ERR_INVALID_ARG;
     c->cam_masks_on = on != 0;
+    c->cam_prefer = on >= 2 ? (uint32_t)on - 1u : 0u;
     return MRT_OK;
 }
 
@@ -476,13 +480,25 @@ int mrt_debug_read_camera_masks(mrt_ctx* c, uint32_t info[4], uint32_t* out, siz
     const bool fits = c->d_cam_masks && need != 0 && need <= c->cam_mask_entries;
     info[0] = fits ? (uint32_t)need : 0u;
     info[1] = 4u;
-    info[2] = c->cam_masks_in_force ? 1u : 0u;
+    info[2] = c->cam_masks_in_force ? (c->cam_lists_in_force ? 2u : 1u) : 0u;
     info[3] = fits && c->cam_mask_built == c->cam_mask_gen ? 1u : 0u;
     if (!out || !fits) return MRT_OK;
     if (cap_words < 4 * need) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_camera_masks: need %zu words", 4 * need);
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(mrt::wait_all(c, "mrt_debug_read_camera_masks"));             // (the build runs on a frame's side stream)
     HIP_TRY(c, hipMemcpy(out, c->d_cam_masks, 4 * need * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MRT_OK;
+}
+
+int mrt_debug_read_camera_lists(mrt_ctx* c, uint32_t info[4], uint32_t* out, size_t cap_words) {
+    if (!c || !info) return MRT_ERR_INVALID_ARG;
+    MRT_TRY(mrt_debug_read_camera_masks(c, info, nullptr, 0));
+    const size_t need = info[0];
+    if (!out || need == 0) return MRT_OK;
+    if (cap_words < 4 * need) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_camera_lists: need %zu words", 4 * need);
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_all(c, "mrt_debug_read_camera_lists"));
+    HIP_TRY(c, hipMemcpy(out, c->cam_lists(), 4 * need * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MRT_OK;
 }
 
