@@ -124,9 +124,22 @@ int ensure_guides(mrt_ctx* c) {
 
 // launch_denoise's variance of a frame count in a mode: SPATIAL_EARLY is the spatial estimate while the history is short and
 // PREFILTERED from then on
-uint32_t variance_of(uint32_t mode, uint32_t frames_done, uint32_t spatial_frames) {
-    if (mode == MRT_DENOISE_VAR_SPATIAL_EARLY) return frames_done < spatial_frames ? 2u : 1u;
-    return mode == MRT_DENOISE_VAR_PREFILTERED ? 1u : 0u;
+mrt::UniformVariance variance_of(uint32_t mode, uint32_t frames_done, uint32_t spatial_frames) {
+    using V = mrt::UniformVariance;
+    if (mode == MRT_DENOISE_VAR_SPATIAL_EARLY) return frames_done < spatial_frames ? V::Spatial : V::Prefiltered;
+    return mode == MRT_DENOISE_VAR_PREFILTERED ? V::Prefiltered : V::Accumulated;
+}
+
+// what every denoise of the context shares: frame `fb` through the context's guides, scratch and parameters into d_den[2]
+mrt::DenoiseJob denoise_job(const mrt_ctx* c, const float* fb, mrt::DenoiseSource source) {
+    mrt::DenoiseJob j{};
+    j.fb = fb;
+    j.guides = c->d_guides;
+    j.ping = c->d_den[0]; j.pong = c->d_den[1]; j.out = c->d_den[2];
+    j.width = c->args.width; j.height = c->args.height;
+    j.prm = c->denoise;
+    j.source = source;
+    return j;
 }
 
 // The refusals of the gathered frame's guides and denoise: denoise_check's for a frame that lives on a shard's root (`tracking`:
@@ -141,9 +154,10 @@ int gathered_denoise_check(mrt_ctx* c, const char* who, bool tracking) {
 // the latest gathered frame, denoised into d_den[2] with the gather's snapshot of K and the frame count (after gathered_denoise_check)
 int queue_gathered_denoise(mrt_ctx* c) {
     MRT_TRY(ensure_guides(c));
-    const uint32_t variance = variance_of(c->denoise_var_mode, c->gather_frames, c->denoise_spatial_frames);
-    const int e = mrt::launch_denoise(c->d_gather, mrt::gathered_noise(c), (float)c->gather_k, c->d_guides, c->d_den[0], c->d_den[1],
-                                      c->d_den[2], c->args.width, c->args.height, c->denoise, variance, c->stream);
+    mrt::DenoiseJob job = denoise_job(c, c->d_gather, mrt::DenoiseSource::Uniform);
+    job.S = mrt::gathered_noise(c);
+    job.uniform = {(float)c->gather_k, variance_of(c->denoise_var_mode, c->gather_frames, c->denoise_spatial_frames)};
+    const int e = mrt::launch_denoise(job, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
@@ -156,17 +170,18 @@ int queue_denoise(mrt_ctx* c) {
         for (uint32_t t : c->tile_frames) most = std::max(most, t);
         MRT_TRY(mrt::ensure_k_table(c, most + 1u));
         MRT_TRY(ensure_guides(c));
-        const mrt::TileField tiles{c->d_tile_frames, c->d_k_f32, c->tiles_x, c->denoise_var_mode, c->denoise_spatial_frames};
-        const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, 0.0f, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
-                                          c->args.width, c->args.height, c->denoise, 0, c->stream, nullptr, &tiles);
+        mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Tiles);
+        job.S = c->d_noise_s;
+        job.tiles = {c->d_tile_frames, c->d_k_f32, c->tiles_x, c->denoise_var_mode, c->denoise_spatial_frames};
+        const int e = mrt::launch_denoise(job, c->stream);
         if (e) return fail(c, MRT_ERR_HIP, "per-tile denoise launch failed: %s", hipGetErrorString((hipError_t)e));
         return MRT_OK;
     }
     MRT_TRY(ensure_guides(c));
-    const float K = (float)mrt::noise_factor_of(c->noise_c2);
-    const uint32_t variance = variance_of(c->denoise_var_mode, c->frames_done, c->denoise_spatial_frames);
-    const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], c->d_noise_s, K, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
-                                      c->args.width, c->args.height, c->denoise, variance, c->stream);
+    mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Uniform);
+    job.S = c->d_noise_s;
+    job.uniform = {(float)mrt::noise_factor_of(c->noise_c2), variance_of(c->denoise_var_mode, c->frames_done, c->denoise_spatial_frames)};
+    const int e = mrt::launch_denoise(job, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
@@ -256,9 +271,9 @@ int clear_history(mrt_ctx* c) {
 // the temporal image into d_den[2]: the history's field (its variance made first), then the filter's iterations
 int queue_temporal_image(mrt_ctx* c) {
     const uint32_t cur = c->temporal_cur;
-    const mrt::TemporalField field{c->d_den[3 + 2 * cur], c->d_den[4 + 2 * cur], c->temporal.spatial_len};
-    const int e = mrt::launch_denoise(c->d_fb[c->target ^ 1], nullptr, 0.0f, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2],
-                                      c->args.width, c->args.height, c->denoise, 3, c->stream, &field);
+    mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Temporal);
+    job.temporal = {c->d_den[3 + 2 * cur], c->d_den[4 + 2 * cur], c->temporal.spatial_len};
+    const int e = mrt::launch_denoise(job, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "temporal image launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
@@ -571,7 +586,14 @@ int mrt_debug_denoise_variance(mrt_ctx* c, const float* rgba, const float* S, do
     if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(d_fb, d_s, (float)K, d_g, d_b[0], d_b[1], d_b[2], width, rows, prm, variance, c->stream);
+    mrt::DenoiseJob job{};
+    job.fb = d_fb; job.S = d_s; job.guides = d_g;
+    job.ping = d_b[0]; job.pong = d_b[1]; job.out = d_b[2];
+    job.width = width; job.height = rows;
+    job.prm = prm;
+    job.source = mrt::DenoiseSource::Uniform;
+    job.uniform = {(float)K, (mrt::UniformVariance)variance};
+    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(job, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_b[2], n * 16, hipMemcpyDeviceToHost, c->stream);
     int ws = MRT_OK;
     if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");

@@ -5,11 +5,17 @@
 // Guides (once per camera / scene): guide_rays_kernel writes one ray per pixel through the mean of the render's sample
 // positions; the closest hits come from the DBG instantiation of render_kernel (launch_debug_world_hit, no candidate bitmap);
 // guide_fill_kernel turns them into the per-texel record the filter reads.
-// Filter: atrous_kernel, one launch per iteration, colour and variance ping-ponged as one float4; with a variance mode
-// (mrt_set_denoise_variance) atrous_prefilter_kernel instead, behind spatial_variance_kernel while the history is short.  Only + - * /, sqrtf, fminf,
-// fmaxf in a fixed order (-ffp-contract=off; hipcc's `/` and sqrtf are correctly rounded), so tests/denoise_ref.py restates it
-// bit for bit in float32 numpy.
+// Filter: atrous_pixel is the a-trous iteration of one pixel, colour and variance ping-ponged as one float4, one launch per
+// iteration.  Its three entry points are a bounds check and a call each, and differ in the centre's luminance stop alone:
+// atrous_kernel (uniform, A.lum_stop), atrous_prefilter_kernel (always, on the prefiltered variance: the variance modes of
+// mrt_set_denoise_variance) and atrous_tiles_kernel (per pixel, from its tile's frame count: an adaptive accumulation).
+// Estimate: spatial_estimate is the 7 x 7 weighted luminance variance of one pixel, for a field that has none of its own yet.
+// Its entry points make the field iteration 0 reads: spatial_variance_kernel (a short uniform history), tile_variance_kernel (per
+// tile) and temporal_variance_kernel (the short histories of the temporal image).
+// Only + - * /, sqrtf, fminf, fmaxf in a fixed order (-ffp-contract=off; hipcc's `/` and sqrtf are correctly rounded), so
+// tests/denoise_ref.py and its siblings restate all of it bit for bit in float32 numpy.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "mrt_internal.h"
 #include "rt_math.h"
 
@@ -23,9 +29,10 @@ __device__ __forceinline__ float tukey(float x) {
     const float u = 1.0f - x * x;
     return x < 1.0f ? u * u : 0.0f;
 }
-__device__ __forceinline__ bool finite4(float4 v) {
-    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z) && __builtin_isfinite(v.w);
+__device__ __forceinline__ bool finite3(float4 v) {            // (the colour of a texel alone)
+    return __builtin_isfinite(v.x) && __builtin_isfinite(v.y) && __builtin_isfinite(v.z);
 }
+__device__ __forceinline__ bool finite4(float4 v) { return finite3(v) && __builtin_isfinite(v.w); }
 
 // One ray per image pixel (world 1: texel = y * width + x), as render_kernel's new_sample_head makes a sample's camera ray
 // with u = v = 0.5 (fs_main :373-381) and, for the look-at camera, the lens centre; normalised as the render normalises
@@ -136,72 +143,7 @@ __device__ __forceinline__ float prefiltered_var(const AtrousArgs& A, uint32_t x
     return num / den;
 }
 
-// grid (ceil(W / 32), ceil(H / 8)), 32 x 8 threads; one pixel per thread.  Taps at offsets {-2..2} x step, rows then columns in
-// increasing order, B3-spline weights {1/16, 1/4, 3/8, 1/4, 1/16}; outside the image or not finite: skipped.  The centre tap
-// weighs (3/8)^2 without stops; any other tap k_x k_y w_lum w_normal w_depth w_albedo, multiplied in that order.
-template <bool FIRST, bool LAST>
-__global__ void __launch_bounds__(kTileX * kTileY) atrous_kernel(const AtrousArgs A) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const size_t i = (size_t)y * A.width + x;
-    const float4 cp = load_cv<FIRST>(A, i);
-    float4 res = cp;
-    // passed through: not finite, or (with a luminance stop) a variance of 0
-    if (finite4(cp) && !(A.lum_stop && cp.w == 0.0f)) {
-        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
-        const bool miss_p = __float_as_int(gp1.w) < 0;
-        const float lp = lumf(cp.x, cp.y, cp.z);
-        const float inv_l = A.lum_stop ? 1.0f / (A.sigma_l * sqrtf(cp.w) + 1.0e-6f) : 0.0f;
-        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
-        const float kern[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-        float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
-        const int step = (int)A.step;
-#pragma unroll
-        for (int ty = 0; ty < 5; ty++) {
-            const int yq = (int)y + (ty - 2) * step;
-            if (yq < 0 || yq >= (int)A.height) continue;
-#pragma unroll
-            for (int tx = 0; tx < 5; tx++) {
-                const int xq = (int)x + (tx - 2) * step;
-                if (xq < 0 || xq >= (int)A.width) continue;
-                const float kxy = kern[tx] * kern[ty];
-                float w;
-                float4 cq;
-                if (tx == 2 && ty == 2) {
-                    cq = cp;
-                    w = kxy;
-                } else {
-                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                    cq = load_cv<FIRST>(A, q);
-                    if (!finite4(cq)) continue;
-                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
-                    const bool miss_q = __float_as_int(gq1.w) < 0;
-                    const float wl = A.lum_stop ? tukey(fabsf(lp - lumf(cq.x, cq.y, cq.z)) * inv_l) : 1.0f;
-                    float wn = fmaxf(0.0f, (gp0.x * gq0.x + gp0.y * gq0.y) + gp0.z * gq0.z);
-                    for (uint32_t e = 0; e < A.normal_exp; e++) wn = wn * wn;
-                    const float wz = miss_p != miss_q ? 0.0f : miss_p ? 1.0f : tukey(fabsf(gp0.w - gq0.w) * inv_z);
-                    const float da = fmaxf(fmaxf(fabsf(gp1.x - gq1.x), fabsf(gp1.y - gq1.y)), fabsf(gp1.z - gq1.z));
-                    const float wa = tukey(da * A.inv_sigma_a);
-                    w = kxy * wl;
-                    w = w * wn;
-                    w = w * wz;
-                    w = w * wa;
-                }
-                sw = sw + w;
-                sr = sr + w * cq.x;
-                sg = sg + w * cq.y;
-                sb = sb + w * cq.z;
-                sv = sv + (w * w) * cq.w;
-            }
-        }
-        res = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
-    }
-    if (LAST) res.w = A.fb[i].w;
-    A.out[i] = res;
-}
-
-// The edge stops of a tap q of p, as atrous_kernel forms them (for the kernels of the variance modes below; atrous_kernel keeps
-// its own text, so that the default mode's four instantiations stay the same instructions).
+// The edge stops of a tap q of p that read the guides alone (the luminance stop is the filter's own)
 __device__ __forceinline__ float stop_normal(const AtrousArgs& A, float4 gp0, float4 gq0) {
     float wn = fmaxf(0.0f, (gp0.x * gq0.x + gp0.y * gq0.y) + gp0.z * gq0.z);
     for (uint32_t e = 0; e < A.normal_exp; e++) wn = wn * wn;
@@ -215,314 +157,21 @@ __device__ __forceinline__ float stop_albedo(const AtrousArgs& A, float4 gp1, fl
     return tukey(da * A.inv_sigma_a);
 }
 
-// The prefiltering a-trous iteration (PREFILTERED, SPATIAL_EARLY; launched only with a luminance stop): atrous_kernel, except
-// that the luminance stop and the pass-through rule read g_p (prefiltered_var: 9 more loads, for the centre texel only).  The
-// propagated variance still sums the unfiltered var_q.
-template <bool FIRST, bool LAST>
-__global__ void __launch_bounds__(kTileX * kTileY) atrous_prefilter_kernel(const AtrousArgs A) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
+// The a-trous iteration of pixel (x, y), inside the image.  Taps at offsets {-2..2} x step, rows then columns in increasing
+// order, B3-spline weights {1/16, 1/4, 3/8, 1/4, 1/16}; outside the image or not finite: skipped.  The centre tap weighs (3/8)^2
+// without stops; any other tap k_x k_y w_lum w_normal w_depth w_albedo, multiplied in that order.  The CENTRE decides on the
+// luminance stop (a tap's own is never read).  With `stop`: w_lum is Tukey's weight of the luminance difference over sigma_l
+// sqrt(var_p), and a variance of 0 passes the texel through; with PF both read g_p instead of var_p (prefiltered_var: 9 more
+// loads, for the centre texel only), while the propagated variance still sums the unfiltered var_q.  Without: w_lum = 1 for all
+// its taps, no prefilter, and a variance of 0 does not pass through.  FIRST: the taps are the frame's (load_cv); LAST: the alpha is.
+template <bool FIRST, bool PF, bool LAST>
+__device__ __forceinline__ void atrous_pixel(const AtrousArgs& A, uint32_t x, uint32_t y, bool stop) {
     const size_t i = (size_t)y * A.width + x;
     const float4 cp = load_cv<FIRST>(A, i);
     float4 res = cp;
-    const float gv = finite4(cp) ? prefiltered_var<FIRST>(A, x, y, cp) : 0.0f;
-    // passed through: not finite, or a prefiltered variance of 0
-    if (finite4(cp) && gv != 0.0f) {
-        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
-        const bool miss_p = __float_as_int(gp1.w) < 0;
-        const float lp = lumf(cp.x, cp.y, cp.z);
-        const float inv_l = 1.0f / (A.sigma_l * sqrtf(gv) + 1.0e-6f);
-        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
-        const float kern[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
-        float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
-        const int step = (int)A.step;
-#pragma unroll
-        for (int ty = 0; ty < 5; ty++) {
-            const int yq = (int)y + (ty - 2) * step;
-            if (yq < 0 || yq >= (int)A.height) continue;
-#pragma unroll
-            for (int tx = 0; tx < 5; tx++) {
-                const int xq = (int)x + (tx - 2) * step;
-                if (xq < 0 || xq >= (int)A.width) continue;
-                float w = kern[tx] * kern[ty];
-                float4 cq = cp;
-                if (!(tx == 2 && ty == 2)) {
-                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                    cq = load_cv<FIRST>(A, q);
-                    if (!finite4(cq)) continue;
-                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
-                    const bool miss_q = __float_as_int(gq1.w) < 0;
-                    w = w * tukey(fabsf(lp - lumf(cq.x, cq.y, cq.z)) * inv_l);
-                    w = w * stop_normal(A, gp0, gq0);
-                    w = w * stop_depth(gp0, gq0, miss_p, miss_q, inv_z);
-                    w = w * stop_albedo(A, gp1, gq1);
-                }
-                sw = sw + w;
-                sr = sr + w * cq.x;
-                sg = sg + w * cq.y;
-                sb = sb + w * cq.z;
-                sv = sv + (w * w) * cq.w;
-            }
-        }
-        res = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
-    }
-    if (LAST) res.w = A.fb[i].w;
-    A.out[i] = res;
-}
-
-// The spatial initial variance (SPATIAL_EARLY while the history is short): per texel the weighted variance of the luminance over
-// the 7 x 7 window, the weights the filter's own normal, depth and albedo stops (the centre's 1); out = (r, g, b, var), which the
-// first a-trous iteration then reads as a non-first one.  Same grid and block as atrous_kernel.  Two passes over the taps (the
-// mean, then the squares about it): the 49 weights and luminances of the first stay in registers (the loops are fully unrolled,
-// every index a constant), so the second pass loads nothing -- recomputing them would cost 49 x 52 more bytes of loads and the
-// stops' arithmetic per pixel.  132 VGPRs, no scratch: 3 waves per SIMD.
-__global__ void __launch_bounds__(kTileX * kTileY) spatial_variance_kernel(const AtrousArgs A) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const size_t i = (size_t)y * A.width + x;
-    const float4 cp = A.fb[i];
-    const float sp = A.S[i];
-    float var = sp;                             // S not finite: kept (the texel passes through)
-    if (__builtin_isfinite(sp)) {
-        var = 0.0f;                             // a colour that is not finite: passes through as well
-        if (__builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
-            const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
-            const bool miss_p = __float_as_int(gp1.w) < 0;
-            const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
-            float w[49], l[49];
-            uint64_t used = 0;
-            float m0 = 0.0f, m1 = 0.0f;
-#pragma unroll
-            for (int ty = 0; ty < 7; ty++) {
-#pragma unroll
-                for (int tx = 0; tx < 7; tx++) {
-                    const int t = ty * 7 + tx;
-                    w[t] = 0.0f;
-                    l[t] = 0.0f;
-                    const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
-                    if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
-                    float wq, lq;
-                    if (tx == 3 && ty == 3) {
-                        wq = 1.0f;
-                        lq = lumf(cp.x, cp.y, cp.z);
-                    } else {
-                        const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                        const float4 cq = A.fb[q];
-                        const float sq = A.S[q];
-                        if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && __builtin_isfinite(sq)))
-                            continue;
-                        const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
-                        const bool miss_q = __float_as_int(gq1.w) < 0;
-                        wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
-                        lq = lumf(cq.x, cq.y, cq.z);
-                    }
-                    w[t] = wq;
-                    l[t] = lq;
-                    used |= 1ull << t;
-                    m0 = m0 + wq;
-                    m1 = m1 + wq * lq;
-                }
-            }
-            const float mean = m1 / m0;
-            float m2 = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 49; t++) {
-                if (!(used >> t & 1ull)) continue;
-                const float d = l[t] - mean;
-                m2 = m2 + w[t] * (d * d);
-            }
-            var = m2 / m0;
-        }
-    }
-    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
-}
-
-template <bool PF>
-void launch_atrous(bool first, bool last, dim3 grid, dim3 block, hipStream_t st, const AtrousArgs& A) {
-    if (PF) {
-        if (first && last) hipLaunchKernelGGL((atrous_prefilter_kernel<true, true>), grid, block, 0, st, A);
-        else if (first) hipLaunchKernelGGL((atrous_prefilter_kernel<true, false>), grid, block, 0, st, A);
-        else if (last) hipLaunchKernelGGL((atrous_prefilter_kernel<false, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((atrous_prefilter_kernel<false, false>), grid, block, 0, st, A);
-    } else {
-        if (first && last) hipLaunchKernelGGL((atrous_kernel<true, true>), grid, block, 0, st, A);
-        else if (first) hipLaunchKernelGGL((atrous_kernel<true, false>), grid, block, 0, st, A);
-        else if (last) hipLaunchKernelGGL((atrous_kernel<false, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((atrous_kernel<false, false>), grid, block, 0, st, A);
-    }
-}
-
-// The temporal image's field (variance 3; include/myraytracer_amd.h, "temporal reprojection", 5): A.fb is the history's H0 =
-// (r, g, b, len), h1 its H1 = (m1, m2, t, index); out = (r, g, b, var).  A history of len >= max(2, spatial_len) takes the variance
-// of its own luminance moments.  A shorter one -- a disocclusion, the first frames -- takes spatial_variance_kernel's estimate
-// over L of the history's colours, "S finite" read as len >= 1: 49 taps for those pixels alone, so the kernel is divergent by
-// design, and the pixels that pay are the few that just restarted.  Any other texel -- len < 1, or short with a colour that is
-// not finite -- gets var 0.
-__global__ void __launch_bounds__(kTileX * kTileY) temporal_variance_kernel(const AtrousArgs A, const float4* __restrict__ h1,
-                                                                            float min_len) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const size_t i = (size_t)y * A.width + x;
-    const float4 cp = A.fb[i];
-    const float N = cp.w;
-    float var = 0.0f;
-    if (N >= min_len) {
-        const float4 mp = h1[i];
-        var = fmaxf(0.0f, mp.y - mp.x * mp.x) / (N - 1.0f);
-    } else if (N >= 1.0f && __builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
-        const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
-        const bool miss_p = __float_as_int(gp1.w) < 0;
-        const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
-        float w[49], l[49];
-        uint64_t used = 0;
-        float m0 = 0.0f, m1 = 0.0f;
-#pragma unroll
-        for (int ty = 0; ty < 7; ty++) {
-#pragma unroll
-            for (int tx = 0; tx < 7; tx++) {
-                const int t = ty * 7 + tx;
-                w[t] = 0.0f;
-                l[t] = 0.0f;
-                const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
-                if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
-                float wq, lq;
-                if (tx == 3 && ty == 3) {
-                    wq = 1.0f;
-                    lq = lumf(cp.x, cp.y, cp.z);
-                } else {
-                    const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                    const float4 cq = A.fb[q];
-                    if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && cq.w >= 1.0f))
-                        continue;
-                    const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
-                    const bool miss_q = __float_as_int(gq1.w) < 0;
-                    wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
-                    lq = lumf(cq.x, cq.y, cq.z);
-                }
-                w[t] = wq;
-                l[t] = lq;
-                used |= 1ull << t;
-                m0 = m0 + wq;
-                m1 = m1 + wq * lq;
-            }
-        }
-        const float mean = m1 / m0;
-        float m2 = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 49; t++) {
-            if (!(used >> t & 1ull)) continue;
-            const float d = l[t] - mean;
-            m2 = m2 + w[t] * (d * d);
-        }
-        var = m2 / m0;
-    }
-    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
-}
-
-// ---- the filter of an adaptive accumulation (include/myraytracer_amd.h, "Adaptive accumulations") ----------------------------
-// Every 8 x 8 tile has its own frame count n_t, hence its own K and its own choice between the spatial estimate and S * K.  The
-// per-pixel state is read from tile_frames and the K table by every kernel below; it is uniform over a tile, so a wave (32 x 2
-// pixels: four tiles) splits at 8-lane granularity at worst.  Kernels of their own: the uniform path's keep their text.
-struct TilePixel {
-    bool spatial;               // SPATIAL_EARLY and n_p < spatial_frames: iteration 0's variance is the spatial estimate
-    bool stop;                  // spatial, or K_p finite: the centre has a luminance stop (constant over the iterations)
-    float K;
-};
-__device__ __forceinline__ TilePixel tile_pixel(const TileField& T, uint32_t x, uint32_t y) {
-    const uint32_t n = T.tile_frames[(size_t)(y / kBandRows) * T.tiles_x + x / kTileW];
-    TilePixel s;
-    s.K = T.Kf[n];
-    s.spatial = T.mode == MRT_DENOISE_VAR_SPATIAL_EARLY && n < T.spatial_frames;
-    s.stop = s.spatial || !__builtin_isinf(s.K);
-    return s;
-}
-
-// The field iteration 0 reads "as the previous iteration's": out = (r, g, b, var0).  A pixel of a tile that is still in its
-// spatial phase takes spatial_variance_kernel's estimate (its taps need a finite colour and S, whatever their own tile's count):
-// 49 taps for those pixels alone, divergent by design, as temporal_variance_kernel is.  Any other pixel: S * K_p, or without an
-// estimate (K_p = +inf) 0 for a finite S and S itself otherwise.
-__global__ void __launch_bounds__(kTileX * kTileY) tile_variance_kernel(const AtrousArgs A, const TileField T) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const size_t i = (size_t)y * A.width + x;
-    const TilePixel tp = tile_pixel(T, x, y);
-    const float4 cp = A.fb[i];
-    const float sp = A.S[i];
-    float var;
-    if (!tp.spatial) {
-        var = !__builtin_isinf(tp.K) ? sp * tp.K : (__builtin_isfinite(sp) ? 0.0f : sp);
-    } else {
-        var = sp;                               // S not finite: kept (the texel passes through)
-        if (__builtin_isfinite(sp)) {
-            var = 0.0f;                         // a colour that is not finite: passes through as well
-            if (__builtin_isfinite(cp.x) && __builtin_isfinite(cp.y) && __builtin_isfinite(cp.z)) {
-                const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
-                const bool miss_p = __float_as_int(gp1.w) < 0;
-                const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
-                float w[49], l[49];
-                uint64_t used = 0;
-                float m0 = 0.0f, m1 = 0.0f;
-#pragma unroll
-                for (int ty = 0; ty < 7; ty++) {
-#pragma unroll
-                    for (int tx = 0; tx < 7; tx++) {
-                        const int t = ty * 7 + tx;
-                        w[t] = 0.0f;
-                        l[t] = 0.0f;
-                        const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
-                        if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
-                        float wq, lq;
-                        if (tx == 3 && ty == 3) {
-                            wq = 1.0f;
-                            lq = lumf(cp.x, cp.y, cp.z);
-                        } else {
-                            const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                            const float4 cq = A.fb[q];
-                            const float sq = A.S[q];
-                            if (!(__builtin_isfinite(cq.x) && __builtin_isfinite(cq.y) && __builtin_isfinite(cq.z) && __builtin_isfinite(sq)))
-                                continue;
-                            const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
-                            const bool miss_q = __float_as_int(gq1.w) < 0;
-                            wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
-                            lq = lumf(cq.x, cq.y, cq.z);
-                        }
-                        w[t] = wq;
-                        l[t] = lq;
-                        used |= 1ull << t;
-                        m0 = m0 + wq;
-                        m1 = m1 + wq * lq;
-                    }
-                }
-                const float mean = m1 / m0;
-                float m2 = 0.0f;
-#pragma unroll
-                for (int t = 0; t < 49; t++) {
-                    if (!(used >> t & 1ull)) continue;
-                    const float d = l[t] - mean;
-                    m2 = m2 + w[t] * (d * d);
-                }
-                var = m2 / m0;
-            }
-        }
-    }
-    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
-}
-
-// An a-trous iteration whose CENTRE decides (a tap's own stop is never read).  A centre with a stop: atrous_kernel's luminance
-// stop and pass-through rule, with PF (PREFILTERED / SPATIAL_EARLY) on g_p as in atrous_prefilter_kernel.  A centre without
-// one: w_lum = 1 for all its taps, no prefilter, and a variance of 0 does not pass through.  Never the first reader of the
-// framebuffer: A.in is tile_variance_kernel's field or the previous iteration's output.
-template <bool PF, bool LAST>
-__global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const AtrousArgs A, const TileField T) {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const size_t i = (size_t)y * A.width + x;
-    const bool stop = tile_pixel(T, x, y).stop;
-    const float4 cp = A.in[i];
-    float4 res = cp;
     const bool fin = finite4(cp);
     float gv = cp.w;
-    if (PF && stop && fin) gv = prefiltered_var<false>(A, x, y, cp);
+    if (PF && stop && fin) gv = prefiltered_var<FIRST>(A, x, y, cp);
     // passed through: not finite, or (with a luminance stop) a (prefiltered) variance of 0
     if (fin && !(stop && gv == 0.0f)) {
         const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
@@ -545,7 +194,7 @@ __global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const Atr
                 float4 cq = cp;
                 if (!(tx == 2 && ty == 2)) {
                     const size_t q = (size_t)yq * A.width + (uint32_t)xq;
-                    cq = A.in[q];
+                    cq = load_cv<FIRST>(A, q);
                     if (!finite4(cq)) continue;
                     const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
                     const bool miss_q = __float_as_int(gq1.w) < 0;
@@ -567,6 +216,172 @@ __global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const Atr
     A.out[i] = res;
 }
 
+// The entry points of the iteration: grid (ceil(W / 32), ceil(H / 8)), 32 x 8 threads, one pixel per thread.
+// The default mode (ACCUMULATED), and every mode without an estimate (K = +inf): the stop is uniform, var = S * K.
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    atrous_pixel<FIRST, false, LAST>(A, x, y, A.lum_stop != 0);
+}
+
+// PREFILTERED, SPATIAL_EARLY and the temporal image (launched only with a luminance stop): the stop reads g_p.
+template <bool FIRST, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_prefilter_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    atrous_pixel<FIRST, true, LAST>(A, x, y, true);
+}
+
+// The 7 x 7 weighted variance of the luminance around pixel (x, y) of A.fb: the weights are the filter's own normal, depth and
+// albedo stops (the centre's 1); a tap counts if it lies inside the image, its colour is finite and tap_ok(cq, q) says so.  A
+// centre whose colour is not finite: 0 (the texel passes through the filter anyway).  Two passes over the taps (the mean, then
+// the squares about it): the 49 weights and luminances of the first stay in registers (the loops are fully unrolled, every
+// index a constant), so the second pass loads nothing -- recomputing them would cost 49 x 52 more bytes of loads and the stops'
+// arithmetic per pixel.  Some 132 VGPRs, no scratch: 3 waves per SIMD.
+template <class TapOk>
+__device__ __forceinline__ float spatial_estimate(const AtrousArgs& A, uint32_t x, uint32_t y, float4 cp, TapOk tap_ok) {
+    if (!finite3(cp)) return 0.0f;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 gp0 = A.guides[2u * i], gp1 = A.guides[2u * i + 1u];
+    const bool miss_p = __float_as_int(gp1.w) < 0;
+    const float inv_z = miss_p ? 0.0f : 1.0f / (A.sigma_z * gp0.w);
+    float w[49], l[49];
+    uint64_t used = 0;
+    float m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+    for (int ty = 0; ty < 7; ty++) {
+#pragma unroll
+        for (int tx = 0; tx < 7; tx++) {
+            const int t = ty * 7 + tx;
+            w[t] = 0.0f;
+            l[t] = 0.0f;
+            const int yq = (int)y + (ty - 3), xq = (int)x + (tx - 3);
+            if (yq < 0 || yq >= (int)A.height || xq < 0 || xq >= (int)A.width) continue;
+            float wq, lq;
+            if (tx == 3 && ty == 3) {
+                wq = 1.0f;
+                lq = lumf(cp.x, cp.y, cp.z);
+            } else {
+                const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+                const float4 cq = A.fb[q];
+                const bool fin_q = finite3(cq), ok = tap_ok(cq, q);     // (both, always: what tap_ok loads is loaded with the colour)
+                if (!(fin_q && ok)) continue;
+                const float4 gq0 = A.guides[2u * q], gq1 = A.guides[2u * q + 1u];
+                const bool miss_q = __float_as_int(gq1.w) < 0;
+                wq = (stop_normal(A, gp0, gq0) * stop_depth(gp0, gq0, miss_p, miss_q, inv_z)) * stop_albedo(A, gp1, gq1);
+                lq = lumf(cq.x, cq.y, cq.z);
+            }
+            w[t] = wq;
+            l[t] = lq;
+            used |= 1ull << t;
+            m0 = m0 + wq;
+            m1 = m1 + wq * lq;
+        }
+    }
+    const float mean = m1 / m0;
+    float m2 = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 49; t++) {
+        if (!(used >> t & 1ull)) continue;
+        const float d = l[t] - mean;
+        m2 = m2 + w[t] * (d * d);
+    }
+    return m2 / m0;
+}
+
+// The spatial initial variance of a texel of an accumulation (colour A.fb, luminance variance A.S): the estimate over the taps
+// with a finite S; an S that is not finite is kept (the texel passes through).
+__device__ __forceinline__ float spatial_initial_variance(const AtrousArgs& A, uint32_t x, uint32_t y, float4 cp, float sp) {
+    if (!__builtin_isfinite(sp)) return sp;
+    return spatial_estimate(A, x, y, cp, [&A](float4, size_t q) { return __builtin_isfinite(A.S[q]); });
+}
+
+// The entry points of the estimate make the field iteration 0 then reads "as the previous iteration's", out = (r, g, b, var).
+// Same grid and block as atrous_kernel.  SPATIAL_EARLY while the history is short: every texel takes the estimate.
+__global__ void __launch_bounds__(kTileX * kTileY) spatial_variance_kernel(const AtrousArgs A) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = A.fb[i];
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, spatial_initial_variance(A, x, y, cp, A.S[i]));
+}
+
+// The temporal image's field (include/myraytracer_amd.h, "temporal reprojection", 5): A.fb is the history's H0 = (r, g, b, len),
+// h1 its H1 = (m1, m2, t, index).  A history of len >= max(2, spatial_len) takes the variance of its own luminance moments.  A
+// shorter one -- a disocclusion, the first frames -- takes the estimate over L of the history's colours, a tap counting with
+// len >= 1: 49 taps for those pixels alone, so the kernel is divergent by design, and the pixels that pay are the few that just
+// restarted.  Any other texel -- len < 1, or short with a colour that is not finite -- gets var 0.
+__global__ void __launch_bounds__(kTileX * kTileY) temporal_variance_kernel(const AtrousArgs A, const float4* __restrict__ h1,
+                                                                            float min_len) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const float4 cp = A.fb[i];
+    const float N = cp.w;
+    float var = 0.0f;
+    if (N >= min_len) {
+        const float4 mp = h1[i];
+        var = fmaxf(0.0f, mp.y - mp.x * mp.x) / (N - 1.0f);
+    } else if (N >= 1.0f) {
+        var = spatial_estimate(A, x, y, cp, [](float4 cq, size_t) { return cq.w >= 1.0f; });
+    }
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
+}
+
+// ---- the filter of an adaptive accumulation (include/myraytracer_amd.h, "Adaptive accumulations") ----------------------------
+// Every 8 x 8 tile has its own frame count n_t, hence its own K and its own choice between the spatial estimate and S * K.  The
+// per-pixel state is read from tile_frames and the K table by both kernels below; it is uniform over a tile, so a wave (32 x 2
+// pixels: four tiles) splits at 8-lane granularity at worst.
+struct TilePixel {
+    bool spatial;               // SPATIAL_EARLY and n_p < spatial_frames: iteration 0's variance is the spatial estimate
+    bool stop;                  // spatial, or K_p finite: the centre has a luminance stop (constant over the iterations)
+    float K;
+};
+__device__ __forceinline__ TilePixel tile_pixel(const TileField& T, uint32_t x, uint32_t y) {
+    const uint32_t n = T.tile_frames[(size_t)(y / kBandRows) * T.tiles_x + x / kTileW];
+    TilePixel s;
+    s.K = T.Kf[n];
+    s.spatial = T.mode == MRT_DENOISE_VAR_SPATIAL_EARLY && n < T.spatial_frames;
+    s.stop = s.spatial || !__builtin_isinf(s.K);
+    return s;
+}
+
+// The per-tile field.  A pixel of a tile that is still in its spatial phase takes the estimate as spatial_variance_kernel does
+// (its taps need a finite colour and S, whatever their own tile's count): 49 taps for those pixels alone, divergent by design, as
+// temporal_variance_kernel is.  Any other pixel: S * K_p, or without an estimate (K_p = +inf) 0 for a finite S and S itself
+// otherwise.
+__global__ void __launch_bounds__(kTileX * kTileY) tile_variance_kernel(const AtrousArgs A, const TileField T) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const TilePixel tp = tile_pixel(T, x, y);
+    const float4 cp = A.fb[i];
+    const float sp = A.S[i];
+    float var;
+    if (tp.spatial) var = spatial_initial_variance(A, x, y, cp, sp);
+    else var = !__builtin_isinf(tp.K) ? sp * tp.K : (__builtin_isfinite(sp) ? 0.0f : sp);
+    A.out[i] = make_float4(cp.x, cp.y, cp.z, var);
+}
+
+// The iteration's entry point for the per-tile field; PF: PREFILTERED / SPATIAL_EARLY.  Never the first reader of the
+// framebuffer: A.in is tile_variance_kernel's field or the previous iteration's output.
+template <bool PF, bool LAST>
+__global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const AtrousArgs A, const TileField T) {
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    atrous_pixel<false, PF, LAST>(A, x, y, tile_pixel(T, x, y).stop);
+}
+
+// f(std::bool_constant<a>, std::bool_constant<b>): two run-time flags as the template arguments of a launch
+template <class F>
+void with_flags(bool a, bool b, F f) {
+    if (a && b) f(std::true_type{}, std::true_type{});
+    else if (a) f(std::true_type{}, std::false_type{});
+    else if (b) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
+
 }  // namespace
 
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream) {
@@ -584,67 +399,73 @@ int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade
     return (int)hipGetLastError();
 }
 
-int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
-                   const TemporalField* temporal, const TileField* tiles) {
+int launch_denoise(const DenoiseJob& job, void* stream) {
+    const uint32_t width = job.width, height = job.height, n = job.prm.iterations;
     if (width == 0 || height == 0) return 0;
-    if ((variance == 3) != (temporal != nullptr) || (tiles && temporal)) return (int)hipErrorInvalidValue;
-    const bool spatial = variance >= 2;         // (iteration 0 reads a field made before it: the spatial estimate's, the history's)
     AtrousArgs A;
-    A.fb = reinterpret_cast<const float4*>(fb);
-    A.S = S;
+    A.fb = reinterpret_cast<const float4*>(job.fb);
+    A.S = job.S;
     A.in = nullptr;
-    A.guides = reinterpret_cast<const float4*>(guides);
+    A.guides = reinterpret_cast<const float4*>(job.guides);
     A.width = width; A.height = height; A.step = 1;
-    A.K = spatial ? 0.0f : K;
-    A.lum_stop = spatial || !__builtin_isinf(K) ? 1u : 0u;
-    A.sigma_l = prm.sigma_l; A.sigma_z = prm.sigma_z;
-    A.inv_sigma_a = 1.0f / prm.sigma_a;
-    A.normal_exp = prm.normal_exp;
+    A.K = 0.0f; A.lum_stop = 1u;                // (the uniform source's own below; K is read by an accumulated first iteration alone)
+    A.sigma_l = job.prm.sigma_l; A.sigma_z = job.prm.sigma_z;
+    A.inv_sigma_a = 1.0f / job.prm.sigma_a;
+    A.normal_exp = job.prm.normal_exp;
     const dim3 grid((width + kTileX - 1) / kTileX, (height + kTileY - 1) / kTileY), block(kTileX, kTileY);
     hipStream_t st = (hipStream_t)stream;
-    float4* buf[2] = {reinterpret_cast<float4*>(ping), reinterpret_cast<float4*>(pong)};
-    if (tiles) {            // an adaptive accumulation: the per-pixel field into pong, then iterations whose centre decides
-        if (tiles->mode > MRT_DENOISE_VAR_SPATIAL_EARLY || !tiles->tile_frames || !tiles->Kf ||
-            tiles->tiles_x != (width + kTileW - 1) / kTileW)
+    float4* buf[2] = {reinterpret_cast<float4*>(job.ping), reinterpret_cast<float4*>(job.pong)};
+    // A field made before iteration 0 goes into pong, where iteration 0 reads it as "the previous iteration's" (and iteration 1
+    // writes pong after it); without one, iteration 0 is the first reader of the frame.
+    bool field = true, prefilter = true;
+    A.out = buf[1];
+    switch (job.source) {
+    case DenoiseSource::Uniform: {
+        const UniformField& u = job.uniform;
+        field = u.variance == UniformVariance::Spatial;
+        if (!field) {
+            A.K = u.K;
+            A.lum_stop = !__builtin_isinf(u.K) ? 1u : 0u;
+        }
+        // without a luminance stop there is nothing to prefilter
+        prefilter = u.variance != UniformVariance::Accumulated && A.lum_stop;
+        if (field) hipLaunchKernelGGL(spatial_variance_kernel, grid, block, 0, st, A);
+        break;
+    }
+    case DenoiseSource::Temporal: {
+        const TemporalField& t = job.temporal;
+        const uint32_t min_len = t.spatial_len > 2u ? t.spatial_len : 2u;
+        A.fb = reinterpret_cast<const float4*>(t.h0);
+        hipLaunchKernelGGL(temporal_variance_kernel, grid, block, 0, st, A, reinterpret_cast<const float4*>(t.h1), (float)min_len);
+        A.fb = reinterpret_cast<const float4*>(job.fb);
+        break;
+    }
+    case DenoiseSource::Tiles: {            // an adaptive accumulation: the per-pixel field, then iterations whose centre decides
+        const TileField& T = job.tiles;
+        if (T.mode > MRT_DENOISE_VAR_SPATIAL_EARLY || !T.tile_frames || !T.Kf || T.tiles_x != (width + kTileW - 1) / kTileW)
             return (int)hipErrorInvalidValue;
-        A.K = 0.0f; A.lum_stop = 0u;            // (not read: K and the stop are per pixel)
-        A.out = buf[1];
-        hipLaunchKernelGGL(tile_variance_kernel, grid, block, 0, st, A, *tiles);
-        const bool pf = tiles->mode != MRT_DENOISE_VAR_ACCUMULATED;
-        for (uint32_t it = 0; it < prm.iterations; it++) {
-            const bool last = it + 1 == prm.iterations;
-            A.step = 1u << it;
-            A.in = buf[(it + 1) & 1u];
-            A.out = last ? reinterpret_cast<float4*>(out) : buf[it & 1u];
-            if (pf && last) hipLaunchKernelGGL((atrous_tiles_kernel<true, true>), grid, block, 0, st, A, *tiles);
-            else if (pf) hipLaunchKernelGGL((atrous_tiles_kernel<true, false>), grid, block, 0, st, A, *tiles);
-            else if (last) hipLaunchKernelGGL((atrous_tiles_kernel<false, true>), grid, block, 0, st, A, *tiles);
-            else hipLaunchKernelGGL((atrous_tiles_kernel<false, false>), grid, block, 0, st, A, *tiles);
-        }
-        return (int)hipGetLastError();
+        A.lum_stop = 0u;                        // (not read: K and the stop are per pixel)
+        prefilter = T.mode != MRT_DENOISE_VAR_ACCUMULATED;
+        hipLaunchKernelGGL(tile_variance_kernel, grid, block, 0, st, A, T);
+        break;
     }
-    // without a luminance stop there is nothing to prefilter: today's kernels
-    const bool prefilter = variance != 0 && A.lum_stop;
-    if (spatial) {          // into pong, where iteration 0 reads it as "the previous iteration's" (and iteration 1 writes pong after it)
-        A.out = buf[1];
-        if (temporal) {
-            const uint32_t min_len = temporal->spatial_len > 2u ? temporal->spatial_len : 2u;
-            A.fb = reinterpret_cast<const float4*>(temporal->h0);
-            hipLaunchKernelGGL(temporal_variance_kernel, grid, block, 0, st, A, reinterpret_cast<const float4*>(temporal->h1), (float)min_len);
-            A.fb = reinterpret_cast<const float4*>(fb);
-        } else {
-            hipLaunchKernelGGL(spatial_variance_kernel, grid, block, 0, st, A);
-        }
+    default:
+        return (int)hipErrorInvalidValue;
     }
-    const uint32_t n = prm.iterations;
     for (uint32_t it = 0; it < n; it++) {
-        const bool first = it == 0 && !spatial, last = it + 1 == n;
+        const bool first = it == 0 && !field, last = it + 1 == n;
         A.step = 1u << it;
         A.in = first ? nullptr : buf[(it + 1) & 1u];
-        A.out = last ? reinterpret_cast<float4*>(out) : buf[it & 1u];
-        if (prefilter) launch_atrous<true>(first, last, grid, block, st, A);
-        else launch_atrous<false>(first, last, grid, block, st, A);
+        A.out = last ? reinterpret_cast<float4*>(job.out) : buf[it & 1u];
+        if (job.source == DenoiseSource::Tiles)
+            with_flags(prefilter, last, [&](auto PF, auto LAST) {
+                hipLaunchKernelGGL((atrous_tiles_kernel<decltype(PF)::value, decltype(LAST)::value>), grid, block, 0, st, A, job.tiles);
+            });
+        else
+            with_flags(first, last, [&](auto FIRST, auto LAST) {
+                if (prefilter) hipLaunchKernelGGL((atrous_prefilter_kernel<decltype(FIRST)::value, decltype(LAST)::value>), grid, block, 0, st, A);
+                else hipLaunchKernelGGL((atrous_kernel<decltype(FIRST)::value, decltype(LAST)::value>), grid, block, 0, st, A);
+            });
     }
     return (int)hipGetLastError();
 }

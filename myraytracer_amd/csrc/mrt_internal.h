@@ -323,25 +323,42 @@ int launch_regroup(const RegroupArgs& a, void* stream);
 // denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
 // pixel (launch_debug_world_hit) -> 2 float4 per pixel {normal, t} {albedo, bits of the index}; shade / mat_ty: KParams' shade and
-// the spheres' material types (i32_data + material_ty_base_idx).  launch_denoise: prm.iterations launches; ping / pong: scratch of
-// width x height float4 each (unused for 1 iteration / ping only for 2); out: width x height RGBA32F.  variance: 0 var = S * K,
-// today's four kernels; 1 the prefiltered luminance stop (with K = +inf exactly 0); 2 the spatial initial variance into pong (one
-// more launch; K is not read) and every iteration prefiltered.
+// the spheres' material types (i32_data + material_ty_base_idx).
 int launch_guide_rays(float* rays, uint32_t width, uint32_t height, const mrt_camera_raw& cam, void* stream);
 int launch_guide_fill(const float* rays, const int32_t* hits, const float* shade, const int32_t* mat_ty, float* guides,
                       uint32_t width, uint32_t height, void* stream);
-// variance 3 (the temporal image, mrt_read_temporal): the field is the history's -- colour and length from h0, the luminance
-// moments from h1, var as "temporal reprojection" defines it (temporal_variance_kernel, into pong as variance 2's) -- and every
-// iteration prefiltered; S and K are not read, fb gives the alpha.
+// launch_denoise filters one frame: prm.iterations launches of the a-trous iteration, behind one launch for the variance field
+// where the source has to make one first (into pong, where iteration 0 reads it as "the previous iteration's").  `source` names
+// where the variance comes from, and with it which ONE of the three payloads below is read.
+enum class DenoiseSource : uint32_t { Uniform, Temporal, Tiles };
+// Uniform (an accumulation of one frame count): var = S * K.  Accumulated: the luminance stop reads var; Prefiltered: it reads the
+// prefiltered var (with K = +inf there is no stop, as for Accumulated); Spatial: the spatial initial variance is the field (K is
+// not read) and every iteration is prefiltered.  The values are mrt_debug_denoise_variance's.
+enum class UniformVariance : uint32_t { Accumulated = 0, Prefiltered = 1, Spatial = 2 };
+struct UniformField { float K; UniformVariance variance; };
+// Temporal (the temporal image, mrt_read_temporal): the field is the history's -- colour and length from h0, the luminance
+// moments from h1, var as "temporal reprojection" defines it (temporal_variance_kernel) -- and every iteration prefiltered; fb
+// gives the alpha alone.
 struct TemporalField { const float* h0; const float* h1; uint32_t spatial_len; };
-// `tiles` (an adaptive accumulation, "Adaptive accumulations" of the header's denoiser section; not with `temporal`): K and
-// `variance` are not read.  Pixel p of tile (y / 8) * tiles_x + x / 8 has n_p = tile_frames[tile], K_p = Kf[n_p] (Kf: K(n) as
-// float for every n the map holds) and mode / spatial_frames choose its variance and stop: one launch for the field (into pong,
-// as variance 2's) and prm.iterations launches whose centre pixel decides on the luminance stop.  ping and pong are both used.
+// Tiles (an adaptive accumulation, "Adaptive accumulations" of the header's denoiser section): pixel p of tile (y / 8) * tiles_x +
+// x / 8 has n_p = tile_frames[tile], K_p = Kf[n_p] (Kf: K(n) as float for every n the map holds) and mode / spatial_frames choose
+// its variance and stop: the field is tile_variance_kernel's, and the centre pixel of an iteration decides on the luminance stop.
 struct TileField { const uint32_t* tile_frames; const float* Kf; uint32_t tiles_x, mode, spatial_frames; };
-int launch_denoise(const float* fb, const float* S, float K, const float* guides, float* ping, float* pong, float* out,
-                   uint32_t width, uint32_t height, const mrt_denoise_params& prm, uint32_t variance, void* stream,
-                   const TemporalField* temporal = nullptr, const TileField* tiles = nullptr);
+struct DenoiseJob {
+    const float* fb;            // the frame, width x height RGBA32F
+    const float* S;             // its luminance variance (Uniform and Tiles; the temporal image's is in its history)
+    const float* guides;
+    float* ping;                // scratch of width x height float4 each: without a field unused for 1 iteration, and ping
+    float* pong;                // alone used for 2; with a field pong always
+    float* out;                 // width x height RGBA32F
+    uint32_t width, height;
+    mrt_denoise_params prm;
+    DenoiseSource source;
+    UniformField uniform;
+    TemporalField temporal;
+    TileField tiles;
+};
+int launch_denoise(const DenoiseJob& job, void* stream);
 inline mrt_denoise_params denoise_defaults() {
     mrt_denoise_params p{};
     p.size = sizeof(mrt_denoise_params);

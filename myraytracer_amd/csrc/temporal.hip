@@ -3,7 +3,7 @@
 // is analytic: the first-hit guides hold the sphere index and distance, `shade` the spheres as they are, prev_xyzr the spheres as
 // they were at the previous step.  Only + - * /, sqrtf, floorf, fminf, fmaxf and comparisons in a fixed order (-ffp-contract=off),
 // so tests/temporal_ref.py restates it bit for bit in float32 numpy.  The variance of the history and the filter over it are
-// denoise.hip's (temporal_variance_kernel, launch_denoise's variance 3).  The response (steps 4b and 4c): a fast
+// denoise.hip's (temporal_variance_kernel, launch_denoise's Temporal source).  The response (steps 4b and 4c): a fast
 // history H2 carried by the same taps, and temporal_clamp_kernel behind the step; tests/temporal_response_ref.py restates both.
 #include <hip/hip_runtime.h>
 #include "mrt_internal.h"

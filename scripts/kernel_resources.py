@@ -25,4 +25,4 @@ for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S
     # the directive values are granulated; the comment block after the kernel has the exact numbers
     tail = txt[m.end():m.end() + 3000]
     ex = lambda k: (re.search(r";\s*" + k + r":\s*(\d+)", tail) or [None, "?"])[1]
-    print(f"{dem[:95]:95s} vgpr {ex('NumVgprs'):>3s} agpr {ex('NumAgprs'):>2s} sgpr {ex('NumSgprs'):>3s} scratch {ex('ScratchSize'):>4s} occupancy {ex('Occupancy')}")
+    print(f"{dem[:95]:95s} vgpr {ex('NumVgprs'):>3s} agpr {ex('NumAgprs'):>2s} sgpr {ex('(?:Total)?NumSgprs'):>3s} scratch {ex('ScratchSize'):>4s} occupancy {ex('Occupancy')}")
