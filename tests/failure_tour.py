@@ -19,36 +19,20 @@ import argparse
 import ctypes as C
 import hashlib
 import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-OK, ERR_HIP, ERR_STALLED = 0, 3, 9
-W, H = 37, 29                       # ragged: 5 tile columns (the last 5 pixels wide), 4 bands (the last 5 rows high)
-
-
-class Unexpected(RuntimeError):
-    """Not an injected refusal: the child stops here."""
+from failure_walks import OK, H, W, Shim, Unexpected, c1_findings, logged_main      # (puts the repository on sys.path)
 
 
 class Tour:
     def __init__(self):
         from myraytracer_amd import _lib, api
         self.lib, self.api = _lib, api
-        self.L = L = _lib.load()
-        u64, sz = C.c_uint64, C.c_size_t
-        for name, res, args in (("mrt_fi_arm", None, [u64]), ("mrt_fi_disarm", None, []), ("mrt_fi_calls", u64, []),
-                                ("mrt_fi_fired", C.c_int, [C.c_char_p, sz]), ("mrt_fi_sites", sz, [C.c_char_p, sz]),
-                                ("mrt_fi_live", None, [C.POINTER(u64)]), ("mrt_fi_violations", sz, [C.c_char_p, sz]),
-                                ("mrt_fi_reset", None, [])):
-            fn = getattr(L, name)           # AttributeError: not the failure-injecting build
-            fn.restype, fn.argtypes = res, args
+        self.L = _lib.load()
+        self.shim = Shim(self.L)
         self.ctx = {}
         self.small, self.small_cam = api.scene_cover(1, True)
         self.large, self.large_cam = api.scene_stress(1, 40)
@@ -57,27 +41,6 @@ class Tour:
         self.seeds = rng.integers(1, 2 ** 32, (H, W, 4), dtype=np.uint64).astype(np.uint32)
         self.last_seq = 0
         self.steps = self.build()
-
-    # ---- the shim
-    def live(self):
-        out = (C.c_uint64 * 4)()
-        self.L.mrt_fi_live(out)
-        return list(out)
-
-    def fired(self):
-        buf = C.create_string_buffer(256)
-        return buf.value.decode() if self.L.mrt_fi_fired(buf, len(buf)) else None
-
-    def sites(self):
-        n = self.L.mrt_fi_sites(None, 0)
-        buf = C.create_string_buffer(n)
-        self.L.mrt_fi_sites(buf, n)
-        return [s for s in buf.value.decode().split("\n") if s]
-
-    def violations(self):
-        buf = C.create_string_buffer(1 << 16)
-        n = self.L.mrt_fi_violations(buf, len(buf))
-        return [s for s in buf.value.decode().split("\n") if s] if n else []
 
     # ---- the library
     def err(self, name):
@@ -385,29 +348,24 @@ class Tour:
     # ---- one pass over the tour
     def run(self, n_arm, mode, clean_obs):
         """Returns the case's record.  mode: "clean", "destroy" or "continue"."""
-        L = self.L
+        L, shim = self.L, self.shim
         rec = {"n": n_arm, "mode": mode, "findings": []}
         bad = rec["findings"].append
         self.last_seq = 0
-        base = self.live()
+        base = shim.live()
         L.mrt_fi_reset()
         L.mrt_fi_arm(n_arm)
         obs = []
         sound = True
         for i, (label, ctx_name, fn) in enumerate(self.steps):
-            was_fired = self.fired() is not None
+            was_fired = shim.fired() is not None
             st, o = fn()
-            site = self.fired()
+            site = shim.fired()
             if site is not None and not was_fired:                     # the armed call was refused in this step
                 rec["site"], rec["step"] = site, label
-                msg = self.err(ctx_name)
-                name = site.split(" ")[1]
-                if st != ERR_HIP:
-                    bad(f"C1: {label}: the refusal at {site} came back as status {st}, not MRT_ERR_HIP ({msg})")
-                    if st == OK:
-                        raise Unexpected(f"{label}: a refused {site} was swallowed; the case cannot go on")
-                if name + "(" not in msg:
-                    bad(f"C1: {label}: mrt_last_error does not name the refused call {name} at {site}: {msg!r}")
+                if st == OK:
+                    raise Unexpected(f"{label}: a refused {site} was swallowed; the case cannot go on")
+                rec["findings"] += c1_findings(site, st, self.err(ctx_name), label + ": ")
                 if mode == "destroy":
                     break
                 why = self.check_contexts()
@@ -436,15 +394,15 @@ class Tour:
         rec["reached"] = "site" in rec
         rec["calls"] = int(L.mrt_fi_calls())
         if mode == "clean":
-            rec["sites"] = self.sites()
+            rec["sites"] = shim.sites()
         if not sound:
             rec["ended"] = "destroyed without another launch"
         self.destroy_all()
-        live = self.live()
+        live = shim.live()
         if live != base:
             bad(f"C2: live {{device, pinned, streams, events}} {live} after mrt_destroy, {base} before mrt_create"
                 + (f" (refusal at {rec['site']})" if "site" in rec else ""))
-        for v in self.violations():
+        for v in shim.violations():
             bad("shim: " + v)
         return rec, obs
 
@@ -459,60 +417,42 @@ def main():
     a = ap.parse_args()
     from failure_sites import key_of, source_sites
     src = source_sites()
-    log = open(a.log, "a")
 
-    def emit(rec):
-        log.write(json.dumps(rec) + "\n")
-        log.flush()
-        os.fsync(log.fileno())
-
-    findings = 0
-    try:
+    def body(emit):
         t = Tour()
         t0 = time.time()
         clean, clean_obs = t.run(0, "clean", None)
         clean["seconds"] = round(time.time() - t0, 3)
         clean["keys"] = sorted({key_of(s, src) or ("? " + s) for s in clean["sites"]})
         emit(clean)
-        findings += len(clean["findings"])
         T = clean["calls"]
         if a.sites_out:
             with open(a.sites_out, "w") as f:
                 json.dump({"sites": clean["keys"]}, f, indent=1)
                 f.write("\n")
-        if a.mode != "clean" and not clean["findings"]:
-            failed_at, not_reached = set(), 0
-            last = a.last or T
-            t0 = time.time()
-            for n in range(a.first, last + 1):
-                rec, _ = t.run(n, a.mode, clean_obs if a.mode == "continue" else None)
-                emit(rec)
-                findings += len(rec["findings"])
-                if rec["reached"]:
-                    failed_at.add(rec["site"])
-                else:
-                    not_reached += 1                  # (the tour made fewer calls this time: logged, no failure)
-            summary = {"summary": a.mode, "T": T, "first": a.first, "last": last, "not_reached": not_reached,
-                       "seconds": round(time.time() - t0, 3), "findings": []}
-            if a.first == 1 and last == T:
-                never = sorted(set(clean["sites"]) - failed_at)
-                extra = sorted(failed_at - set(clean["sites"]))
-                if never:
-                    summary["findings"].append(f"sites of the clean run at which no refusal was injected: {never}")
-                if extra:
-                    summary["findings"].append(f"refusals at sites the clean run did not see: {extra}")
-            findings += len(summary["findings"])
-            emit(summary)
-    except Unexpected as e:
-        emit({"stopped": str(e)})
-        print("stopped:", e, file=sys.stderr)
-        return 3
-    except Exception as e:          # noqa: BLE001  (whatever it is, the walk ends here and says why)
-        import traceback
-        emit({"stopped": "exception: " + repr(e), "traceback": traceback.format_exc()})
-        traceback.print_exc()
-        return 3
-    return 1 if findings else 0
+        if a.mode == "clean" or clean["findings"]:
+            return
+        failed_at, not_reached = set(), 0
+        last = a.last or T
+        t0 = time.time()
+        for n in range(a.first, last + 1):
+            rec, _ = t.run(n, a.mode, clean_obs if a.mode == "continue" else None)
+            emit(rec)
+            if rec["reached"]:
+                failed_at.add(rec["site"])
+            else:
+                not_reached += 1                  # (the tour made fewer calls this time: logged, no failure)
+        summary = {"summary": a.mode, "T": T, "first": a.first, "last": last, "not_reached": not_reached,
+                   "seconds": round(time.time() - t0, 3), "findings": []}
+        if a.first == 1 and last == T:
+            never = sorted(set(clean["sites"]) - failed_at)
+            extra = sorted(failed_at - set(clean["sites"]))
+            if never:
+                summary["findings"].append(f"sites of the clean run at which no refusal was injected: {never}")
+            if extra:
+                summary["findings"].append(f"refusals at sites the clean run did not see: {extra}")
+        emit(summary)
+    return logged_main(a.log, body)
 
 
 if __name__ == "__main__":

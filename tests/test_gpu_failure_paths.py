@@ -10,48 +10,20 @@ again.  If the child dies or runs into its limit the test fails with the last lo
 The limits are three times what the walks took on an MI355X (profiles/failure_paths.txt)."""
 import json
 import os
-import subprocess
-import sys
-import time
 
 import pytest
 
-from failure_sites import ROOT
+from failure_sites import GOLDEN, ROOT, run_child
 
 pytestmark = pytest.mark.gpu
 
 TOUR = os.path.join(ROOT, "tests", "failure_tour.py")
-FI_LIB = os.path.join(ROOT, "myraytracer_amd", "lib", "libmyraytracer_amd_failinject.so")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "failure_sites.json")
 # 3 x what the child took on an MI355X, start-up included: about 4 s for the clean tour alone, + 24 s / + 49 s for the walks
 LIMIT_S = {"clean": 15, "destroy": 85, "continue": 160}
 
 
 def walk(mode, tmp_path):
-    assert os.path.exists(FI_LIB), "build the failure-injecting library first (make)"
-    log = tmp_path / f"{mode}.jsonl"
-    # the child alone loads the substituted library; twenty hardware queues, as the package asks for where the host sets none
-    env = dict(os.environ, MRT_LIB_OVERRIDE=FI_LIB, GPU_MAX_HW_QUEUES="20")
-
-    def records():
-        return [json.loads(line) for line in open(log)] if log.exists() else []
-
-    def last_case():
-        r = [x for x in records() if "n" in x]
-        return {k: v for k, v in r[-1].items() if k not in ("sites", "keys")} if r else "none"
-    t0 = time.time()
-    try:
-        p = subprocess.run([sys.executable, TOUR, "--mode", mode, "--log", str(log)], env=env, timeout=LIMIT_S[mode],
-                           capture_output=True, text=True, cwd=ROOT)
-    except subprocess.TimeoutExpired:
-        pytest.fail(f"the {mode} walk did not end within {LIMIT_S[mode]} s; last logged case: {last_case()} (find the cause there; not run again)")
-    print(f"{mode}: the child took {time.time() - t0:.1f} s of its {LIMIT_S[mode]} s")
-    recs = records()
-    if p.returncode not in (0, 1):
-        stopped = [r for r in recs if "stopped" in r]
-        pytest.fail(f"the {mode} walk's process ended with {p.returncode}; last logged case: {last_case()}; "
-                    f"{stopped[-1]['stopped'] if stopped else p.stderr[-2000:]}")
-    return recs
+    return run_child(TOUR, ["--mode", mode], tmp_path / f"{mode}.jsonl", LIMIT_S[mode])
 
 
 def check(mode, recs):
