@@ -84,6 +84,12 @@ stamps: $(SRCS) $(HDRS) $(OBJDIR)/build_id.cpp
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DMRT_STAMPS -shared -o $(LIBDIR)/libmyraytracer_amd_stamps.so $(SRCS) $(OBJDIR)/build_id.cpp -ldl
 
+# the same with the tail split into primary hit / shading / rejection loop / scatter + normalize instead of the walk's phases
+# (-DMRT_STAMPS=2, kernels.hip; scripts/cam_list_profile.py ... tail, scripts/phase_profile.py with MRT_STAMPS_TAIL=1)
+stamps-tail: $(SRCS) $(HDRS) $(OBJDIR)/build_id.cpp
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -DMRT_STAMPS=2 -shared -o $(LIBDIR)/libmyraytracer_amd_stamps_tail.so $(SRCS) $(OBJDIR)/build_id.cpp -ldl
+
 # experiment builds (never the product): make variant NAME=slots16 FLAGS="-DMRT_MAX_SLOTS=16" -> lib/libmyraytracer_amd_slots16.so,
 # selected at run time by MRT_LIB_OVERRIDE (bench.py refuses a headline from it)
 variant: $(SRCS) $(HDRS) $(OBJDIR)/build_id.cpp

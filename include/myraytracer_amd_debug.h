@@ -123,6 +123,10 @@ int mrt_debug_sweep_axes(mrt_ctx* ctx, float axis_out[3]);
  * claim of DESIGN.md 4 is that this set equals {s : discriminant_s >= 0} for every ray (tests/test_gpu_superset.py). */
 int mrt_debug_world_hit(mrt_ctx* ctx, const float* rays, size_t n, int32_t* hit_out, uint32_t* candidates_out,
                         size_t cand_words_per_ray);
+/* Diagnostic: what the last mrt_debug_world_hit call that asked for candidates counted -- out[0] = rays traced (lane slots of
+ * its world_hit), out[1] = member tests (4 per cluster item of the walk + one per direct sphere and usable ray): the number
+ * of work items the walk ran, which the winners and candidate sets alone do not show.  Zeros before such a call. */
+int mrt_debug_world_hit_stats(mrt_ctx* ctx, uint64_t out[2]);
 /* Diagnostic: the render kernel's own forms of division and square root -- the correctly rounded expansions of `/` and
  * sqrtf() WITHOUT their operand-scaling steps, used at every root, hit normal and normalize (shader.wgsl:286-299, :354,
  * :381) where the operands cannot need those steps -- against hipcc's `/` and sqrtf() on the device, bit for bit (two NaNs

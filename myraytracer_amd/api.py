@@ -508,6 +508,13 @@ class State:
         bits = np.unpackbits(cand.view(np.uint8), axis=1, bitorder="little")[:, :n_spheres].astype(bool)
         return hit[:, 0].copy(), hit[:, 1].copy().view(np.float32), bits
 
+    def debug_world_hit_stats(self):
+        """(rays traced, member tests) of the last debug_world_hit: member tests = 4 per cluster item of the walk + one per direct
+        sphere and usable ray (mrt_debug_world_hit_stats)"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.mrt_debug_world_hit_stats(self._ctx, out), "mrt_debug_world_hit_stats")
+        return int(out[0]), int(out[1])
+
     def debug_last_launch(self):
         """(main, pilot or None): template-argument bits of the last render launch -- 1 COUNT, 2 PILOT, 4 CTR, 8 SMALL, 16 MFMA."""
         out = (C.c_uint32 * 2)()

@@ -126,8 +126,16 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
     // render kernel has completed (a swap-chain's back-pressure; the GPU still holds a full set of frames, queued or
     // running).  It bounds the queued work and is what lets the samples below arrive while they can still matter -- a
     // caller that issues its redraws in one burst would otherwise see none of them before its last call.
+    // The frames still queued or running beside the slot this frame takes are counted HERE, before that wait: what the caller
+    // keeps in flight is what it has issued when it calls.  Counted after the wait the number is taken at the one moment a
+    // convoy of frames has just ended -- frames launched together end within a fraction of a millisecond of each other -- and
+    // says 0 to 2 of a caller that was a full set of frames ahead; which of the frames' events had landed by then is a race.
+    uint32_t running = 0;
     {
         const uint32_t own = (uint32_t)(c->frame_seq % c->frame_slots);
+        for (uint32_t i = 0; i < c->frame_slots; i++)
+            if (i != own && c->slot[i].render_pending && hipEventQuery(c->slot[i].render_done) != hipSuccess) running++;
+        (void)hipGetLastError();        // (hipEventQuery's hipErrorNotReady is not an error)
         mrt_ctx::FrameSlot& Own = c->slot[own];
         if (Own.stats_pending) {
             char what[160];
@@ -136,14 +144,10 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
             MRT_TRY(mrt::wait_event(c, Own.stats_ready, what));
         }
     }
-    // lane-utilisation samples that have landed (an event that is not ready yet is looked at next time), and the frames still
-    // queued or running
-    uint32_t running = 0;
+    // lane-utilisation samples that have landed (an event that is not ready yet is looked at next time)
     for (uint32_t i = 0; i < c->frame_slots; i++) {
         mrt_ctx::FrameSlot& T = c->slot[i];
-        if (T.render_pending) {
-            if (hipEventQuery(T.render_done) == hipSuccess) T.render_pending = false; else running++;
-        }
+        if (T.render_pending && hipEventQuery(T.render_done) == hipSuccess) T.render_pending = false;
         if (!T.stats_pending || hipEventQuery(T.stats_ready) != hipSuccess) continue;
         T.stats_pending = false;
         if (T.stats_seq < c->width_valid_from) continue;

@@ -87,25 +87,38 @@ __device__ __forceinline__ void literal_test(const SphereRec s, uint32_t idx, V3
 #else
 #define MRT_STAMP(k) do { } while (0)
 #endif
+// -DMRT_STAMPS=2 (make stamps-tail): the same counters with the TAIL split instead of the walk -- the primary hit, shading and
+// the rejection loop take the slots of the node rounds, the root rounds and the unpack phase, whose cycles go to the sweep's;
+// "tail" is then what follows the rejection loop: scatter + normalize (scripts/cam_list_profile.py ... tail).
+#if defined(MRT_STAMPS) && MRT_STAMPS + 0 == 2
+#define MRT_WALK_STAMP(k) MRT_STAMP(1)
+#define MRT_TAIL_STAMP(k) MRT_STAMP(k)
+#else
+#define MRT_WALK_STAMP(k) MRT_STAMP(k)
+#define MRT_TAIL_STAMP(k) do { } while (0)
+#endif
 
-constexpr int kUnpackMore = 1;            // extra records unpacked per trip of the owners' loop (1, 2, 3 measured alike)
 constexpr uint32_t kBlockChunks = 16;     // 16 chunks x 16 clusters x 4 = 1024 spheres per sweep block
 
 // The cooperative walk: candidates found by the sweep become wave-wide work items
 // (owner lane, node) in small LDS queues; every round 64 lanes take 64 items, whoever owns them.
 // The bounds form a 4-ary hierarchy of P.levels levels above the member spheres (level 0);
 // the sweep tests the top level's bounding spheres, the walk descends.  Small scenes (one level):
-//   queue 1 : (owner, cluster)  written by the owners from their sweep masks
+//   (owner, cluster) items are never stored: node round k of a block DERIVES its 64 items -- lane j takes the block's item
+//   64 k + j -- from the lanes' candidate counts and the sweep masks in LDS (render_kernel, "Small scenes"; the derivation
+//   is restated and tested in tests/test_walk_items_host.py)
 //   queue 0 : (owner, member)   members whose discriminant is >= 0, waiting for the root tests
 // Large scenes: every owner filters its candidates against their boxes in the lane -> one stack of inner nodes of every
 // level -> clusters -> members (render_kernel, "Large scenes").
-// (kQueueCap, mrt_internal.h: < 64 left over + 4 x 64 pushed by one round; the small scenes' top queue: P.gen_cap)
+// (kQueueCap, mrt_internal.h: < 64 left over + 4 x 64 pushed by one round; the small scenes' P.gen_cap u16 entries behind
+// queue 0 held the stored cluster items once: their first kItemWindow x 4 bytes are the table of the derivation, the rest is
+// unused -- the footprint, hence 5 workgroups per CU, is kept as it was)
 // Large scenes keep ONE work stack of P.gen_cap entries for all inner levels (render_kernel) + this reserve: a round is sized
 // so that its pushes fit (<= 4 per item), down to one item per round, which may exceed the capacity by 3 entries per level
 // (kStackReserve, mrt_internal.h)
 constexpr unsigned long long kNoHitKey = 0x461C4000FFFFFFFFull;   // (bits(1e4f) << 32) | -1
 
-// The owners' side of the walk reads a lane's candidates off its masks one bit at a time.  wm: the 32-record mask word being
+// The owners' filter of the large scenes' walk reads a lane's candidates off its masks one bit at a time.  wm: the 32-record mask word being
 // unpacked, refilled from the block's next non-empty word (a bit of nz) when it has run out; ebase: `owner_bits` | first record id
 // of that word (the block starts at record `first`); the next candidate is wm's highest bit (clz = record within the word).
 __device__ __forceinline__ void refill_mask_word(uint32_t& nz, uint32_t& wm, const uint32_t* masks, uint32_t& ebase,
@@ -151,6 +164,22 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 #undef MRT_DPP_ADD
     return x;
 }
+// inclusive running maximum over the 64 lanes of a wave (all lanes active), the same six steps
+__device__ __forceinline__ uint32_t wave_incl_max(uint32_t x) {
+#define MRT_DPP_MAX(ctrl, rmask) { const uint32_t y_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rmask, 0xF, false); x = x < y_ ? y_ : x; }
+    MRT_DPP_MAX(0x111, 0xF);
+    MRT_DPP_MAX(0x112, 0xF);
+    MRT_DPP_MAX(0x114, 0xF);
+    MRT_DPP_MAX(0x118, 0xF);
+    MRT_DPP_MAX(0x142, 0xA);
+    MRT_DPP_MAX(0x143, 0xC);
+#undef MRT_DPP_MAX
+    return x;
+}
+constexpr uint32_t kItemWindow = 256;     // small scenes' walk: items whose owners one fill of the table covers (4 node rounds)
+// the table fits the entries that held the stored items, and what pick_word reads below a short block's masks -- at most 3 words
+// x 64 lanes x 4 bytes -- stays inside them: this wave's own LDS
+static_assert(kSmallGenCap * 2u >= kItemWindow * 4u && kSmallGenCap * 2u >= 3u * 64u * 4u, "the small scenes' table and pick_word's reads below the masks");
 __device__ __forceinline__ void lds_order() { asm volatile("" ::: "memory"); }   // compiler-level only: LDS runs a wave's accesses in order
 // lanes below `lane` whose bit is set in the 64-bit ballot `mask`
 __device__ __forceinline__ uint32_t rank_in(unsigned long long mask) {
@@ -514,40 +543,9 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 lds_order();
 
                 // ---- cooperative walk over this block's candidates
-                uint32_t wm = 0, ebase = 0;               // owner side: see the unpacking loop
-                uint32_t incl = wave_incl_scan(rem);
-                uint32_t total_rem = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                // owners unpack their masks into `n_new` (owner, top record) items at their scanned positions behind dst[0].
-                // `room` >= n_new entries are free behind dst.
-                auto unpack = [&](auto* const dst, const uint32_t room, const uint32_t owner_shift) -> uint32_t {
-                    typedef typename std::remove_pointer<decltype(dst)>::type item_t;
-                    const uint32_t excl = incl - rem;
-                    const uint32_t n_new = total_rem < room ? total_rem : room;
-                    item_t* wp = dst + excl;
-                    if (total_rem <= room) {             // the usual case: everything fits, no bound to watch
-                        while ((nz | wm) != 0u) {
-                            if (wm == 0u) refill_mask_word(nz, wm, masks, ebase, lane << owner_shift, blk);
-                            *wp++ = (item_t)take_mask_bit(wm, ebase);
-                            // further records of the same word in the same trip: fewer trips, i.e. fewer taken branches
-#pragma unroll
-                            for (int more = 0; more < kUnpackMore; more++) {
-                                if (wm != 0u) *wp++ = (item_t)take_mask_bit(wm, ebase);
-                            }
-                        }
-                    } else {
-                        item_t* const wend = dst + n_new;
-                        while ((nz | wm) != 0u && wp < wend) {
-                            if (wm == 0u) refill_mask_word(nz, wm, masks, ebase, lane << owner_shift, blk);
-                            *wp++ = (item_t)take_mask_bit(wm, ebase);
-                        }
-                    }
-                    rem -= (uint32_t)(wp - (dst + excl));
-                    total_rem -= n_new;
-                    if (total_rem != 0u) incl = wave_incl_scan(rem);
-                    lds_order();
-                    MRT_STAMP(6);
-                    return n_new;
-                };
+                uint32_t wm = 0, ebase = 0;               // owner side of the large scenes' filter: see refill_mask_word
+                const uint32_t incl = wave_incl_scan(rem);
+                const uint32_t total_rem = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 // the ray of the lane that owns a work item, from where every lane left its own
                 auto fetch_ray = [&](const uint32_t owner, V3& ro, V3& rd) {
                     const float4 r0 = rays[2u * owner];
@@ -596,7 +594,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     rounds_b_++; items_b_ += take;
 #endif
                     lds_order();
-                    MRT_STAMP(3);
+                    MRT_WALK_STAMP(3);
                 };
                 // The reference's discriminant (shader.wgsl:274-282) for the 4 members of a cluster; members with disc >= 0
                 // become (owner, member) items at dst[dn ..].  A member that lies entirely behind the ray's origin -- origin
@@ -638,37 +636,91 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     return pushed;
                 };
                 if constexpr (SMALL) {
-                    // Small scenes (one level): queue 1 = (owner, cluster) from the owners' masks, queue 0 = (owner, member)
-                    // waiting for the root tests.  A full round at the deeper queue that has one; else refill queue 1; else
-                    // a partial round at queue 1, then queue 0.
-                    uint32_t qn0 = 0, qn1 = 0;
-                    entry_t* const q0 = queues, * const q1 = queues + kQueueCap;
-                    for (;;) {
-                        int k = qn0 >= 64u ? 0 : qn1 >= 64u ? 1 : -1;
-                        if (k < 0) {
-                            if (total_rem != 0u) { qn1 += unpack(q1 + qn1, gen_cap - qn1, kIdBits); continue; }
-                            k = qn1 != 0u ? 1 : qn0 != 0u ? 0 : -1;
-                            if (k < 0) break;
+                    // Small scenes (one level).  The block's items are the set mask bits of its usable lanes, numbered lane by lane:
+                    // lane l owns items [excl, incl) of the scan of `rem`.  ceil(total_rem / 64) node rounds, each deriving its own 64
+                    // items with every lane busy -- owner from a table of the owners' first items and a running maximum, record as the
+                    // r-th set bit of the owner's mask words -- instead of every owner peeling its bits into a queue at the pace of the
+                    // busiest lane (round 2 .. 9: the wave's poorest filled phase).  The order of a block's items is free: the root
+                    // rounds merge by a 64-bit minimum and the counters are totals.  queue 0 = (owner, member) waiting for the root
+                    // tests: a full root round as soon as 64 wait, the remainder at the block's end.
+                    uint32_t qn0 = 0;
+                    entry_t* const q0 = queues;
+                    uint32_t* const starts = reinterpret_cast<uint32_t*>(queues + kQueueCap);
+                    const uint32_t* const masks0 = masks - lane;                    // the block's word w of lane l at masks0[w * 64 + l]
+                    const uint32_t words = (blk_end - blk) / (2u * kChunk);         // 1 .. 8
+                    // (first item << 6 | lane; all ones for a lane without items: its "first item" is beyond every window.  The one
+                    // value an owner keeps through the block's rounds)
+                    const uint32_t start_entry = rem != 0u ? ((incl - rem) << 6) | lane : 0xFFFFFFFFu;
+                    uint32_t carry = 0u;                                            // wave-uniform, like every counter of the scheduling
+                    // Item `r` of the owner lies in the highest slot at which the count of set bits, from the top slot down and that
+                    // slot included, exceeds r.  `n` slots ending at the block's last word are read, so a block of fewer
+                    // words reads what lies below its masks (the table or the unused entries behind it: this wave's own LDS) into the lowest slots:
+                    // r is below the owner's total, which the real words reach first, so those slots are never chosen.
+                    auto pick_word = [&](auto NW, const uint32_t owner, const uint32_t r, uint32_t& sel, uint32_t& r_in) -> uint32_t {
+                        constexpr int n = decltype(NW)::value;
+                        const uint32_t* const mo = masks0 + (int32_t)(words - (uint32_t)n) * 64 + owner;
+                        // (from the top slot down, one word at a time: `found` = a slot above already exceeds r)
+                        uint32_t cnt = 0u, above = 0u, below = 0u;
+                        bool found = false;
+                        sel = 0u;
+#pragma unroll
+                        for (int i = n - 1; i >= 0; i--) {
+                            const uint32_t m = mo[i * 64];
+                            sel = found ? sel : m;
+                            above = found ? above : cnt;
+                            cnt += (uint32_t)__builtin_popcount(m);
+                            found = r < cnt;
+                            below += found ? 0u : 1u;                                // slots passed over
                         }
-                        if (k == 0) { root_round(q0, qn0); continue; }
-                        // node round: 64 lanes take the last 64 (owner, cluster) items, whoever owns them
-                        // (Round 1 rotated the four reads by node/4 to spread one read's 64 lanes over all LDS banks; the 8
-                        // VALU of address arithmetic per round cost more than the bank conflicts they avoided: round 2.)
-                        const uint32_t take = qn1 < 64u ? qn1 : 64u, start = qn1 - take;
-                        const bool act = lane < take;
-                        const uint32_t it = q1[act ? start + lane : 0u];
-                        const uint32_t owner = it >> kIdBits, node = it & ((1u << kIdBits) - 1u);
-                        V3 ro, rd;
-                        fetch_ray(owner, ro, rd);
-                        qn0 += members_round(nodes + 4u * node, ro, rd, dot3(rd, rd), act, (owner << kIdBits) | (4u * node), q0 + qn0);
-                        qn1 = start;
-                        if (!PILOT) mtests += kClusterK * take;
-#ifdef MRT_STAMPS
-                        rounds_a_++; items_a_ += take;
-#endif
+                        r_in = r - above;
+                        return blk + (words - 1u - below) * (2u * kChunk);          // the word's first record
+                    };
+                    for (uint32_t base = 0; base < total_rem; base += kItemWindow) {
+                        // the window's table: cleared, then every owner whose items start inside the window leaves its entry
+                        // at its first item (one that started earlier and reaches in comes with `carry`)
+#pragma unroll
+                        for (uint32_t i = 0; i < kItemWindow; i += 64u) starts[i + lane] = 0u;      // (one zero register, two writes)
                         lds_order();
-                        MRT_STAMP(2);
+                        if ((start_entry >> 6) - base < kItemWindow) starts[(start_entry >> 6) - base] = start_entry;
+                        lds_order();
+                        const uint32_t window_end = total_rem - base < kItemWindow ? total_rem : base + kItemWindow;
+                        for (uint32_t g0 = base; g0 < window_end; g0 += 64u) {
+                            // node round: lane j takes item g0 + j of the block.  Entries grow with the lane, so a running maximum
+                            // hands every lane the entry of the owner it falls to; lanes past the block's last item repeat that item
+                            // (`act` keeps them from pushing), so every lane's reads are some real item's.
+                            const uint32_t take = total_rem - g0 < 64u ? total_rem - g0 : 64u;
+                            const bool act = lane < take;
+                            uint32_t e = starts[g0 - base + lane];
+                            e = wave_incl_max(e < carry ? carry : e);
+                            carry = (uint32_t)__builtin_amdgcn_readlane((int)e, 63);
+                            const uint32_t owner = e & 63u;
+                            const uint32_t r = g0 + (act ? lane : take - 1u) - (e >> 6);    // its number among the owner's items
+                            uint32_t sel, r_in;
+                            const uint32_t first = words <= 4u ? pick_word(IC<4>{}, owner, r, sel, r_in) : pick_word(IC<8>{}, owner, r, sel, r_in);
+                            // the r_in-th set bit of the word from below (a word rarely holds more than two): a wave-level loop, at
+                            // most 31 trips whatever the lanes hold.  (hipcc unrolls it into 31 guarded steps, about 150 instructions
+                            // per instantiation; kept rolled -- `#pragma unroll 1` -- C3 gained 1.2 % instead of 3.0 %:
+                            // profiles/walk_items_rates.txt)
+                            for (uint32_t trip = 0; trip < 31u && __any(r_in != 0u); trip++) {
+                                if (r_in != 0u) { sel &= sel - 1u; r_in--; }
+                            }
+                            const uint32_t node = first + 31u - (uint32_t)__builtin_ctz(sel);       // bit 31 = the word's first record
+                            V3 ro, rd;
+                            fetch_ray(owner, ro, rd);
+                            MRT_WALK_STAMP(6);
+                            // (Round 1 rotated the four reads by node/4 to spread one read's 64 lanes over all LDS banks; the 8
+                            // VALU of address arithmetic per round cost more than the bank conflicts they avoided: round 2.)
+                            qn0 += members_round(nodes + 4u * node, ro, rd, dot3(rd, rd), act, (owner << kIdBits) | (4u * node), q0 + qn0);
+                            if (!PILOT) mtests += kClusterK * take;
+#ifdef MRT_STAMPS
+                            rounds_a_++; items_a_ += take;
+#endif
+                            lds_order();
+                            MRT_WALK_STAMP(2);
+                            while (qn0 >= 64u) root_round(q0, qn0);
+                        }
                     }
+                    while (qn0 != 0u) root_round(q0, qn0);
                 } else {
                     // Large scenes.  Every owner first FILTERS its own candidates -- does its line touch the record's BOX (the
                     // sweep tested its bounding sphere)? -- in the lane: one record of its masks per trip, its ray in registers,
@@ -761,7 +813,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                                 if ((int32_t)left < 0) wm |= 0x80000000u >> ((left & 0x7FFFFFFFu) - ebase);
                                 if (levels == 1u) cn = qn; else sn = qn;
                                 lds_order();
-                                MRT_STAMP(6);
+                                MRT_WALK_STAMP(6);
                                 continue;
                             }
                             k = sn != 0u ? 2 : cn != 0u ? 1 : rn != 0u ? 0 : -1;
@@ -833,7 +885,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         rounds_a_++; items_a_ += take;
 #endif
                         lds_order();
-                        MRT_STAMP(2);
+                        MRT_WALK_STAMP(2);
                     }
                 }
             }
@@ -848,7 +900,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 }
             }
         }
-        MRT_STAMP(3);
+        MRT_WALK_STAMP(3);
         if (DBG && live) {
             P.dbg_hit[2u * texel] = best;
             P.dbg_hit[2u * texel + 1u] = (int32_t)__float_as_uint(t_sup);
@@ -1055,6 +1107,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     }
                 }
             } else if (start_sample) need_lens = new_sample_head(ndir, cam_p);
+            MRT_TAIL_STAMP(2);
             // -- (b) lanes with a hit: the rest of sphere_hit for the winning sphere (:298-309) and the material's own part
             // (centre, radius) and (material colour, fuzz | ior) of sphere `best` come packed in two 16-byte records built
             // at upload from the reference's SoA arrays (sphere_load_* :254-268, albedo / fuzz loads :205, :232-240): the
@@ -1119,6 +1172,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 }
                 o = at;
             }
+            MRT_TAIL_STAMP(3);
             // -- (c) ONE rejection loop for both kinds of lanes (each lane draws only its own numbers, in its own order):
             // Lambertian / Metal lanes a point of the unit ball (:84-90: three draws per try), lanes starting a sample
             // under a defocusing camera a point of the unit disk (two draws per try; z = 0 leaves the test's value as it is)
@@ -1131,6 +1185,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     if (need_ball) bz = rng_pm1(rng);
                 } while (__builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx)) > 1.0f);
             }
+            MRT_TAIL_STAMP(6);
             // -- (d) what the draws are for
             if (need_lens) new_sample_lens(ndir, cam_p, bx, by);
             if (hit) {

@@ -156,6 +156,7 @@ struct mrt_ctx {
     uint32_t hint_div = 0, hint_mult = 0;           // mrt_set_schedule_hint: the caller's setting (0 = the controller decides)
     uint32_t max_slots = kMaxFrameSlots;            // frames that can really run side by side (probe_stream_concurrency)
     bool slots_probed = false;
+    unsigned long long dbg_world_hit_stats[2] = {0, 0};     // mrt_debug_world_hit_stats
     uint32_t last_launch_div = 1, last_frames_running = 0;   // mrt_get_schedule: what the most recent launch was issued with
     uint32_t running_seen[kMaxFrameSlots] = {}, running_seen_n = 0;    // frames seen queued or running at the last calls (schedule_frame)
     uint32_t nothing_running_calls = 0;             // consecutive calls that found no earlier frame queued or running

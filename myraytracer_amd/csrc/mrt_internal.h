@@ -20,6 +20,10 @@ constexpr float kBoundStretch = 1.0001f;
 constexpr double kBoundInflate = 1.015;
 constexpr uint32_t kMaxFrameBatch = 32;   // frames one render launch may cover (stream mode, mrt_render)
 constexpr uint32_t kQueueCap = 320;      // a work queue of the walk: < 64 left over + 4 x 64 pushed by one round
+// small scenes' KParams::gen_cap: u16 entries behind the root queue, directly below the wave's candidate masks.  They held the
+// stored cluster items once; the walk's table of first items lives in them and its word selection may read up to 3 x 256 bytes
+// below the masks (kernels.hip, static_assert at kItemWindow).  Kept at this size for the LDS footprint (5 workgroups per CU)
+constexpr uint32_t kSmallGenCap = 576;
 constexpr uint32_t kStackReserve = 16;   // large scenes' work stack: entries beyond its capacity a one-item round may use (3 per level)
 constexpr uint32_t kMaxDirect = 4;       // very large spheres tested by every ray directly, outside the hierarchy
 constexpr uint32_t kCamMaskRecords = 128; // camera-ray cluster masks (cam_mask.hip): one 128-bit entry covers at most this many top records

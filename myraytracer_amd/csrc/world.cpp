@@ -106,7 +106,7 @@ void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
     p.levels = c->levels; p.n_nodes = c->n_nodes; p.n_members = c->n_members;
     // small scenes: the top queue holds a ray's candidates among ALL top records; large scenes: the wave's one work stack
     p.box_lds_count = mrt::scene_is_small(c->n_members) ? 0u : mrt::large_scene_box_lds_count(c->n_padded, c->levels, p.mask_chunks, mrt::kBoxLdsCap);
-    p.gen_cap = mrt::scene_is_small(c->n_members) ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    p.gen_cap = mrt::scene_is_small(c->n_members) ? mrt::kSmallGenCap : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
     for (uint32_t k = 0; k < mrt::kMaxLevels; k++) p.level_base[k] = c->level_base[k];
     // large scenes only (kernels.hip: !SMALL): every node's box, in the kernel's top-down numbering
     p.boxes = c->boxes_mode == 0 ? c->d_boxes_open : c->d_boxes;
@@ -515,6 +515,12 @@ int mrt_debug_set_sweep(mrt_ctx* c, int mode) {
     return MRT_OK;
 }
 
+int mrt_debug_world_hit_stats(mrt_ctx* c, uint64_t out[2]) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    out[0] = c->dbg_world_hit_stats[0]; out[1] = c->dbg_world_hit_stats[1];
+    return MRT_OK;
+}
+
 int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_out, uint32_t* cand_out, size_t cand_words) {
     if (!c || !rays || !hit_out || n == 0) return MRT_ERR_INVALID_ARG;
     if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_debug_world_hit: no scene");
@@ -526,11 +532,13 @@ int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_ou
     HIP_TRY(c, hipSetDevice(c->device));
     MRT_TRY(mrt::wait_all(c, __func__));
     // rays become the texels of an 8-pixel-wide virtual image (one 8x8 tile per 64 rays), padded with copies of ray 0
-    const size_t n_pad = (n + 63) / 64 * 64;
+    const size_t n_rays = (n + 63) / 64 * 64;
+    // rows allocated: 64 spare rows of candidate words (>= 256 bytes) hold the launch's 16 counters, cleared and read back with them
+    const size_t n_pad = n_rays + 64;
     const size_t words = need_words ? need_words : 1;
-    std::vector<float> host_rays(6 * n_pad);
+    std::vector<float> host_rays(6 * n_rays);
     std::memcpy(host_rays.data(), rays, 6 * n * sizeof(float));
-    for (size_t i = n; i < n_pad; i++) std::memcpy(host_rays.data() + 6 * i, rays, 6 * sizeof(float));
+    for (size_t i = n; i < n_rays; i++) std::memcpy(host_rays.data() + 6 * i, rays, 6 * sizeof(float));
     float* d_rays = nullptr; int32_t* d_hit = nullptr; uint32_t* d_cand = nullptr; uint32_t* d_queue = nullptr;
     auto cleanup = [&]() { (void)hipFree(d_rays); (void)hipFree(d_hit); (void)hipFree(d_cand); (void)hipFree(d_queue); };
     hipError_t e = hipSuccess;
@@ -548,14 +556,15 @@ int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_ou
     mrt::KParams p;
     std::memset(&p, 0, sizeof p);
     p.locals = c->locals;
-    p.locals.shape[0] = 8; p.locals.shape[1] = (uint32_t)(n_pad / 8);
+    p.locals.shape[0] = 8; p.locals.shape[1] = (uint32_t)(n_rays / 8);
     p.locals.samples_per_frame = 1; p.locals.ray_depth = 1;
     fill_scene_params(c, p);
     p.shard_rank = 0; p.shard_world = 1;
-    p.tiles_x = 1; p.n_tiles = (uint32_t)(n_pad / 64);
+    p.tiles_x = 1; p.n_tiles = (uint32_t)(n_rays / 64);
     p.tile_queue = d_queue;
     p.n_blocks = 1; p.pix_stride = 0; p.queue_layers = 1; p.lane_frames = 1;
     p.dbg_rays = d_rays; p.dbg_hit = d_hit; p.dbg_cand = d_cand; p.dbg_words = (uint32_t)words;
+    p.counters = reinterpret_cast<unsigned long long*>(d_cand + n_rays * words);      // (n_rays x words x 4 bytes: a multiple of 256)
     int le = mrt::launch_debug_world_hit(p, c->n_waves, c->stream);
     int ws = MRT_OK;
     if (le == 0) ws = mrt::wait_stream(c, c->stream, "mrt_debug_world_hit");
@@ -567,6 +576,11 @@ int mrt_debug_world_hit(mrt_ctx* c, const float* rays, size_t n, int32_t* hit_ou
     if (e == hipSuccess && cand_out) {
         std::vector<uint32_t> cand(n_pad * words);
         e = hipMemcpy(cand.data(), d_cand, cand.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) {
+            unsigned long long cnt[16];
+            std::memcpy(cnt, cand.data() + n_rays * words, sizeof cnt);
+            c->dbg_world_hit_stats[0] = cnt[1]; c->dbg_world_hit_stats[1] = cnt[4];
+        }
         if (e == hipSuccess)
             for (size_t i = 0; i < n; i++) {
                 std::memset(cand_out + i * cand_words, 0, cand_words * sizeof(uint32_t));
@@ -603,7 +617,7 @@ int mrt_debug_lds_layout(uint32_t n_members, uint32_t n_nodes, uint32_t levels, 
     p.n_members = n_members; p.n_nodes = n_nodes; p.levels = levels; p.n_padded = n_top_padded;
     { const uint32_t ch = (n_top_padded + mrt::kChunk - 1) / mrt::kChunk; p.mask_chunks = ch < 16u ? ch : 16u; }
     p.box_lds_count = mrt::scene_is_small(n_members) ? 0u : mrt::large_scene_box_lds_count(n_top_padded, levels, p.mask_chunks, mrt::kBoxLdsCap);
-    p.gen_cap = mrt::scene_is_small(n_members) ? 576u : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
+    p.gen_cap = mrt::scene_is_small(n_members) ? mrt::kSmallGenCap : mrt::large_scene_stack_cap(p.mask_chunks, p.box_lds_count);
     uint32_t lay[2];
     mrt::render_lds_layout(p, lay);
     out[0] = lay[0]; out[1] = lay[1]; out[2] = p.gen_cap;

@@ -4,17 +4,22 @@ mode (mrt_debug_set_camera_masks: 0 neither table, 1 the library's rule, 2 the s
 counters that tell wave iterations from lane slots: lane_slots counts a slot for every camera ray resolved in the lane, so with
 the lists in force wave iterations = (lane slots - samples) / 64 (exact while no entry overflows).
    MRT_LIB_OVERRIDE=myraytracer_amd/lib/libmyraytracer_amd_stamps.so python scripts/cam_list_profile.py [scene w h spp frames [modes]]
-A tree from before the lists knows modes 0 and 1 only."""
+A tree from before the lists knows modes 0 and 1 only.  A last argument `tail` names the phases of the tail-split build
+(make stamps-tail, libmyraytracer_amd_stamps_tail.so: the walk's cycles are in the sweep's line)."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import myraytracer_amd as M
 from myraytracer_amd import _lib
 a = sys.argv[1:]
+TAIL = bool(a) and a[-1] == "tail"
+if TAIL: a.pop()
 scene = a[0] if a else "cover-glass"
 w, h, spp, frames = (int(x) for x in a[1:5]) if len(a) >= 5 else (1920, 1080, 512, 1)
 modes = [int(x) for x in a[5].split(",")] if len(a) > 5 else [1, 0]
 sp, cam = M.scene_cover(1, scene == "cover-glass")
 NAMES = ["tail", "sweep", "node rounds", "root rounds", "no-scatter", "release/refill/acquire", "unpack"]
+if TAIL:
+    NAMES = ["tail: scatter + normalize", "sweep + walk", "tail: primary hit", "tail: shading", "no-scatter", "release/refill/acquire", "tail: rejection loop"]
 
 
 def counters(st):

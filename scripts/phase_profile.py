@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Dev helper (GPU box): phase shares of the bounce loop from the -DMRT_STAMPS build.
-   MRT_LIB_OVERRIDE=myraytracer_amd/lib/libmyraytracer_amd_stamps.so python scripts/phase_profile.py"""
+   MRT_LIB_OVERRIDE=myraytracer_amd/lib/libmyraytracer_amd_stamps.so python scripts/phase_profile.py
+   MRT_STAMPS_TAIL=1 MRT_LIB_OVERRIDE=myraytracer_amd/lib/libmyraytracer_amd_stamps_tail.so python scripts/phase_profile.py"""
 import ctypes as C, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import myraytracer_amd as M
@@ -20,7 +21,9 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1) as st:
     names = ["tail: camera rays, hit records, rejection loop, scatter, normalize", "sweep", "walk: node rounds", "walk: root rounds",
              "paths ending without a scatter", "release/refill/acquire"]
     ph = [raw[6 + k] for k in range(6)] + [raw[5]]
-    names = names + ["walk: owners unpack masks into items"]
+    names = names + ["walk: item derivation (large scenes: the owners' filter)"]
+    if os.environ.get("MRT_STAMPS_TAIL"):      # the tail-split build (make stamps-tail): the walk's cycles are in the sweep's line
+        names = ["tail: scatter, normalize", "sweep + walk", "tail: camera rays, primary hit", "tail: hit records, shading", names[4], names[5], "tail: rejection loop"]
     tot = sum(ph)
     print("kernel ms", st.last_kernel_ms(), "wave sweeps", raw[3] / 64)
     for n, v in zip(names, ph):
