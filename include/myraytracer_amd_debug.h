@@ -145,8 +145,10 @@ int mrt_debug_arith_pairs(mrt_ctx* ctx, const float* x, const float* y, size_t n
 /* Diagnostic: which instantiation of the render kernel the most recent redraw launched (out[0]) and, if it was preceded by
  * a cost-estimating pilot launch not yet reported, which one that was (out[1], else 0xFFFFFFFF): bit 0 = with the RNG draw
  * counter, 1 = pilot, 2 = counter-RNG mode, 3 = small-scene layout, 4 = matrix-core sweep, 5 = large-scene layout with the
- * quadratic form of the box test's slack (else the linear form)
- * (tests/test_gpu_parity.py::test_every_render_kernel_instantiation_against_the_oracle). */
+ * quadratic form of the box test's slack (else the linear form), 6 = the launch got the camera-ray sphere lists (the SC = 3
+ * instantiations; set for the pilot and the main launch alike)
+ * (tests/test_gpu_parity.py::test_every_render_kernel_instantiation_against_the_oracle,
+ * tests/test_gpu_camera_list_launches.py::test_every_list_instantiation_against_the_oracle). */
 int mrt_debug_last_launch(mrt_ctx* ctx, uint32_t out[2]);
 /* Diagnostic A/B switch (large scenes, > 1,024 member slots, whose walk tests the axis-aligned box of every node): 0 opens
  * every box wide, so that the box tests never reject and the walk reaches every member below the swept candidates; 1 (default)

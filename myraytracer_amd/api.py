@@ -516,7 +516,8 @@ class State:
         return int(out[0]), int(out[1])
 
     def debug_last_launch(self):
-        """(main, pilot or None): template-argument bits of the last render launch -- 1 COUNT, 2 PILOT, 4 CTR, 8 SMALL, 16 MFMA."""
+        """(main, pilot or None): template-argument bits of the last render launch -- 1 COUNT, 2 PILOT, 4 CTR, 8 SMALL, 16 MFMA,
+        32 quadratic box slack (large scenes), 64 the camera-ray sphere lists (SC = 3)."""
         out = (C.c_uint32 * 2)()
         self._check(self._L.mrt_debug_last_launch(self._ctx, out), "mrt_debug_last_launch")
         return int(out[0]), (None if out[1] == 0xFFFFFFFF else int(out[1]))

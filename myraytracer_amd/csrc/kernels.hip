@@ -1395,9 +1395,10 @@ int launch_render(const KParams& p, bool pilot, uint32_t n_waves, void* stream, 
     const bool small = scene_is_small(p.n_members);
     const bool ctr = p.locals.rng_mode == MRT_RNG_COUNTER;
     const bool mfma = p.use_mfma != 0, quad = p.box_quad != 0;
-    // which instantiation this is, for mrt_debug_last_launch: bit 0 COUNT, 1 PILOT, 2 CTR, 3 SMALL, 4 MFMA, 5 quadratic box slack
+    // which instantiation this is, for mrt_debug_last_launch: bit 0 COUNT, 1 PILOT, 2 CTR, 3 SMALL, 4 MFMA, 5 quadratic box slack,
+    // 6 the camera-ray lists (SC = 3; the pilot and the main launch of a frame get the same p.cam_lists)
     if (which) *which = ((!pilot && p.count_draws) ? 1u : 0u) | (pilot ? 2u : 0u) | (ctr ? 4u : 0u) | (small ? 8u : 0u) | (mfma ? 16u : 0u) |
-                        ((!small && quad) ? 32u : 0u);
+                        ((!small && quad) ? 32u : 0u) | (p.cam_lists != nullptr ? 64u : 0u);
     if (pilot) {
         if (ctr) launch_render_kernel<false, true, true, false>(p, n_waves, st);
         else launch_render_kernel<false, true, false, false>(p, n_waves, st);

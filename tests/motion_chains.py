@@ -12,7 +12,8 @@ chain(case) draws (params, ops) from np.random.default_rng(case); ops are plain 
   ("update", kind, seed[, k])      UPDATE_KINDS; "drift" moves k scene sizes in ONE mrt_update_spheres (see drift below) and takes
                                    the camera along; "tiny" is two one-sphere updates
   ("regroup",) ("set_regroup_block", 4 | 0) ("set_camera", angle, distance, height)
-  ("render", k) ("reset",) ("set_frames_in_flight", n) ("set_frame_batching", 0) ("set_sweep", m) ("set_camera_masks", on)
+  ("render", k) ("reset",) ("set_frames_in_flight", n) ("set_frame_batching", 0) ("set_sweep", m)
+  ("set_camera_masks", on)         False / True (1: the library's rule); the list chains: 0, 2 (the lists), 3 (the masks)
   ("set_temporal", on) ("temporal_step",) ("temporal_reset",)
   ("refused", kind, seed)          one call the header refuses, REFUSALS
   ("check",)
@@ -20,7 +21,8 @@ Shadow turns an op into calls -- it follows the geometry and the camera the way 
 an oracle -- and Run applies every call to the implementation and to the model and compares statuses; a check compares what the
 model can say (frames_done, framebuffer, counters, guides, the temporal history and image) bit for bit and, on a real context,
 the hierarchy (tests/refit_ref.py), member_index (tests/regroup_ref.py), the candidate sets under both sweeps, the camera masks
-(tests/camera_mask_ref.py) and mrt_debug_check_context.
+(tests/camera_mask_ref.py), the camera-ray sphere lists (tests/camera_list_ref.py) and mrt_debug_check_context.  Behind every
+render the launch's table -- none, the masks, the lists -- is held to CameraTables, a host model of the library's decision.
 
 Drift: a drift op carries the number of scene sizes it moves in ONE mrt_update_spheres.  Chain 8 is the long one: fifty-two drifts of
 one scene size each, with frames and checks at the positions between, about 120 ops.  The other chains are kept to forty ops;
@@ -47,6 +49,7 @@ import math
 
 import numpy as np
 
+import camera_list_ref as CL
 import camera_mask_ref as CM
 import denoise_ref
 import myraytracer_amd as M
@@ -58,7 +61,7 @@ from test_gpu_superset import _rays_for
 from test_gpu_update_spheres import DEPTH, H, HASH_LAYOUTS, KEYS, SEED, SPP, W, scene
 
 OK, INVALID_ARG, HIP, NO_SCENE, BAD_SCENE, STATE, STALLED = 0, 1, 3, 4, 5, 7, 9
-SUITE_CASES = tuple(range(12))
+SUITE_CASES = tuple(range(16))
 UPDATE_KINDS = ("jitter", "scatter", "drift", "shrink", "grow", "flip", "tiny", "partial", "ground")
 REFUSALS = ("step-after-reset", "step-while-off", "range-past-the-end", "coordinate-too-large", "radius-nan")
 VOCABULARY = ("set_world", "update", "regroup", "set_regroup_block", "set_camera", "render", "reset", "set_frames_in_flight",
@@ -69,10 +72,13 @@ GENERATION_CALLS = ("set_world", "update_spheres", "regroup_spheres", "set_camer
 # case -> (layout, flavour).  masks: frame batching off, 4 or 8 frames in flight, generation changes with two frames between them
 # and with none; temporal: max_framebuffer_weight 0, a step per frame; world: mrt_set_world to another sphere count while temporal
 # reprojection is on; drift: ends fifty scene sizes away, in a few jumps; long drift: the one chain beyond forty ops, fifty-two drifts of
-# ONE scene size each with frames and checks at the positions between; shrink: three shrinks in a row and the tiny radii
+# ONE scene size each with frames and checks at the positions between; shrink: three shrinks in a row and the tiny radii;
+# lists: a masks flavour that asks for the camera-ray sphere lists (mrt_debug_set_camera_masks(2)) right behind mrt_set_world and
+# whose seg_masks switches between no table, the masks and the lists on one built generation (0, 3, 2 in a seeded order)
 PLAN = {0: ("small", "masks"), 1: ("small", "masks"), 2: ("small", "masks drift"), 3: ("small", "masks shrink"),
         4: ("small", "temporal"), 5: ("small", "temporal world"), 6: ("large-quad", "shrink"), 7: ("large-quad", "temporal world"),
-        8: ("large-quad", "long drift"), 9: ("large-lin", "temporal world"), 10: ("large-lin", "shrink drift"), 11: ("deep-4200", "mixed")}
+        8: ("large-quad", "long drift"), 9: ("large-lin", "temporal world"), 10: ("large-lin", "shrink drift"), 11: ("deep-4200", "mixed"),
+        12: ("small", "lists"), 13: ("small", "lists drift"), 14: ("small", "lists shrink"), 15: ("small", "lists temporal")}
 DRIFT_STEPS = (1, 3, 8, 8, 16, 16)             # 52 scene sizes
 
 
@@ -249,8 +255,10 @@ def chain(case: int):
     """-> (params, ops): params = dict(layout, flavour, max_w); ops = the case's list of tuples"""
     rng = np.random.default_rng(case)
     layout, flavour = PLAN[case % len(PLAN)]
+    p = dict(layout=layout, flavour=flavour, max_w=0.0 if "temporal" in flavour else 1.0)
+    lists = "lists" in flavour
+    flavour = flavour.replace("lists", "masks")     # (a lists flavour is the masks flavour of the same name, but for `lists` below)
     temporal, masks = "temporal" in flavour, "masks" in flavour
-    p = dict(layout=layout, flavour=flavour, max_w=0.0 if temporal else 1.0)
     sh = Shadow()
     ops = []
     g = dict(frames=0, temporal=False, updates=0, owed=False)
@@ -331,13 +339,22 @@ def chain(case: int):
                 emit("set_camera", float(rng.uniform(-0.4, 0.4)), float(rng.uniform(11.0, 15.0)), float(rng.uniform(2.0, 3.0)))
             if i % 2 == 0 or i == len(kinds) - 1:
                 emit("render", 2 if chance(0.5) else 3)
+                if g["temporal"]:               # (lists temporal: a step behind the frames of every generation that got a table)
+                    emit("temporal_step")
             elif chance(0.5):
                 emit("render", 1)
         if chance(0.5):                         # a built table left unused for a launch, then used again
-            emit("set_camera_masks", False)
-            emit("render", 1)
-            emit("set_camera_masks", True)
-            emit("render", 1)
+            if lists:                           # ... no table, the masks and the lists on one built generation, ending on the lists
+                modes = [0, 3]
+                rng.shuffle(modes)
+                for mode in modes + [2]:
+                    emit("set_camera_masks", mode)
+                    emit("render", 1)
+            else:
+                emit("set_camera_masks", False)
+                emit("render", 1)
+                emit("set_camera_masks", True)
+                emit("render", 1)
         emit("check")
 
     def seg_drift(steps):
@@ -409,6 +426,8 @@ def chain(case: int):
         emit("check")
 
     emit("set_world", layout)
+    if lists:
+        emit("set_camera_masks", 2)
     if masks:
         emit("set_frame_batching", 0)
     if temporal:
@@ -418,8 +437,8 @@ def chain(case: int):
     body = [seg_refusal]
     if masks:
         body += [seg_masks, seg_masks] if flavour == "masks" else [seg_masks]
-    if temporal:
-        body += [seg_pan, seg_temporal_toggles, seg_regroup_then_partial]
+    if temporal:                                # (the list chains' seg_masks steps too and toggles for longer: two segments less keep them to forty ops)
+        body += [seg_temporal_toggles] if lists else [seg_pan, seg_temporal_toggles, seg_regroup_then_partial]
         if flavour == "temporal":
             body.append(lambda: seg_drift([2]))
     if flavour == "long drift":
@@ -432,7 +451,7 @@ def chain(case: int):
         body.append(seg_shrink)
     if flavour in ("shrink", "long drift", "mixed", "masks"):
         body += [seg_two_regroups] if masks else [seg_two_regroups, seg_reset]
-    if flavour in ("shrink", "mixed", "masks drift", "shrink drift"):
+    if flavour in ("shrink", "mixed", "masks drift", "shrink drift") and not (lists and "drift" in flavour):
         body.append(seg_regroup_then_partial)
     if flavour in ("mixed", "long drift", "masks shrink"):
         body.append(lambda: animate(["grow", "scatter", "ground"]))
@@ -683,6 +702,69 @@ def new_state(params):
     return st
 
 
+# ------------------------------------------------------------------ which launches get a camera-ray table
+
+class CameraTables:
+    """Host model of the library's decision which render launches run with a camera-ray table, and with which of the two
+    (frames.cpp, the comment above camera_masks), from the calls alone:
+
+    * mrt_set_world, mrt_update_spheres, mrt_regroup_spheres and mrt_set_camera begin a new generation: what was built is stale.
+    * Every frame launch, with or without a table, is "the previous frame" of the next one: a generation has survived a frame
+      when the launch before this one was made under it.
+    * The switch (mrt_debug_set_camera_masks): 0 no table, 2 the lists, 3 the masks, 1 the library's rule, which reads the
+      device (pixels per lane the chip holds): `lists` is None then, open.
+    * The tables apply to the small layout and to launches whose texel is the pixel's own (no queue-layer batch).
+    * A launch the tables apply to gets one when its slot has built for the generation; else the slot builds first -- at once
+      when some slot has built for the generation, or the generation has survived a frame, or the launch's samples per pixel
+      (per frame x frames per lane) reach the threshold of the table it gets (96 the lists, 512 the masks) -- and else runs
+      without.
+
+    The slot (frame sequence number modulo the frames in flight) decides who builds, not whether the launch gets a table: a
+    slot follows "some slot has built" at once.  That is what makes the outcome independent of how many frames the library's
+    controller keeps in flight, which follows measured times; the model keeps the slots' records all the same, and the seeded
+    defects of tests/test_motion_chains_host.py show that the comparison notices a rule that reads them wrongly."""
+    LISTS_ALWAYS_SPP, MASKS_ALWAYS_SPP = 96, 512
+
+    def __init__(self):
+        self.mode = 1
+        self.gen = 0                            # the calls that made a table stale so far
+        self.frame_gen = None                   # the generation the previous frame was launched under
+        self.slot_gen = {}                      # slot -> the generation it last built for
+        self.built_gen = None                   # the generation some slot has built
+        self.seq = 0                            # frames launched
+
+    # ---- what the seeded defects change
+    def stale_after(self, call):
+        return call in GENERATION_CALLS
+
+    def slot_has_built(self, slot):
+        return self.slot_gen.get(slot) == self.gen
+
+    # ----
+    def call(self, name):
+        if self.stale_after(name):
+            self.gen += 1
+
+    def launch(self, applies, slots, spp_lane):
+        """one frame launch -> (in_force, lists); lists None: open (mode 1)"""
+        slot = self.seq % max(slots, 1)
+        self.seq += 1
+        survived = self.frame_gen == self.gen
+        self.frame_gen = self.gen
+        if self.mode == 0 or not applies:
+            return False, False
+        lists = {1: None, 2: True, 3: False}[self.mode]
+        if not self.slot_has_built(slot):
+            if self.built_gen != self.gen and not survived:
+                if lists is None and self.LISTS_ALWAYS_SPP <= spp_lane < self.MASKS_ALWAYS_SPP:
+                    raise NotImplementedError("mode 1 between the two thresholds: the build depends on the device's rule")
+                if spp_lane < (self.LISTS_ALWAYS_SPP if lists else self.MASKS_ALWAYS_SPP):
+                    return False, False
+            self.slot_gen[slot] = self.gen
+            self.built_gen = self.gen
+        return True, lists
+
+
 # ------------------------------------------------------------------ applying and comparing
 
 def _call(obj, name, args):
@@ -739,8 +821,10 @@ def reference_hits(O, spheres, rays):
 class Run:
     """One chain on one implementation and one model, op by op.  after(i, op, run): called behind every op that compared equal."""
 
-    def __init__(self, label, params, impl, model, O, stats=None, after=None, device_checks=True):
+    def __init__(self, label, params, impl, model, O, stats=None, after=None, device_checks=True, tables=None):
         self.label, self.p, self.impl, self.model, self.O = label, params, impl, model, O
+        self.tables = (tables or CameraTables)()        # the prediction of every render launch's table
+        self.batching, self.tables_lost = 1, False      # mrt_debug_set_frame_batching: automatic until a chain switches it off
         self.device_checks = device_checks      # (off: what the model can say alone -- the liveness test's view of a real context)
         self.stats, self.after = stats if stats is not None else {}, after
         self.sh = Shadow()
@@ -781,10 +865,16 @@ class Run:
 
     def step(self, op):
         self.ops.append(op)
-        for name, args in self.sh.calls(op):
+        calls = self.sh.calls(op)
+        if op[0] == "render" and self.batching == 0 and self.sh.layout == "small":
+            # frame batching off: mrt_render(k) is k launches, queued without a wait.  The runner makes them one call each, which
+            # queues the same launches, so that EVERY launch's table is compared with the prediction and not the last one's alone
+            calls = [("render", (1,))] * op[1]
+        for name, args in calls:
             status, _, _ = self._both(name, args)
             if status == OK and name in GENERATION_CALLS and not (name == "update_spheres" and len(args[1]) == 0):
                 self.gen += 1
+                self.tables.call(name)
                 self._bump("generation changes")
             if status == OK and name == "set_world" and self.device:
                 h = self._dev("debug_read_hierarchy")
@@ -797,9 +887,12 @@ class Run:
                 self.sweep = args[0]
             if name == "debug_set_frames_in_flight":
                 self.fif = args[0]
-            if status == OK and name == "render" and self.device and self.sh.layout == "small":
-                info = self._dev("debug_read_camera_masks", table=False)       # (host only: no wait)
-                self.stats.setdefault("mask launches", []).append((self.gen, info["in_force"], self.fif))
+            if name == "debug_set_camera_masks" and status == OK:
+                self.tables.mode = int(args[0])
+            if name == "debug_set_frame_batching":
+                self.batching = int(args[0])
+            if status == OK and name == "render":
+                self.rendered(args[0])
         if op[0] == "check":
             self.check()
             self._bump("checks")
@@ -808,6 +901,27 @@ class Run:
         self.stats["smallest radius"] = min(self.stats.get("smallest radius", math.inf), self.sh.smallest_clustered_radius())
         if self.after is not None:
             self.after(len(self.ops) - 1, op, self)
+
+    def rendered(self, k):
+        """render(k) went through: CameraTables' prediction of its last launch against what the implementation reports"""
+        small = self.sh.layout == "small"
+        if k > 1 and self.batching != 0 and small:      # (one launch of several frames, in a form the library chooses: no chain does
+            self.tables_lost = True             # that on the small layout; if one ever does, the prediction ends there.  On the other
+        if self.tables_lost:                    # layouts no launch gets a table, however many launches the frames take)
+            return
+        for _ in range(k):                      # (0 frames in flight: the library's choice, two or more -- see CameraTables on the slots)
+            want = self.tables.launch(small, self.fif or 2, SPP)
+        if not small:
+            return
+        self.stats.setdefault("predicted launches", []).append((self.gen, want[0], want[1], self.fif))
+        if not hasattr(self.impl, "debug_read_camera_masks"):
+            return
+        info = self._dev("debug_read_camera_masks", table=False)       # (host only: no wait)
+        self.stats.setdefault("mask launches", []).append((self.gen, info["in_force"], self.fif))
+        self.stats.setdefault("list launches", []).append((self.gen, info["lists"], self.fif))
+        if info["in_force"] != want[0] or (want[1] is not None and info["lists"] != want[1]):
+            self._fail(f"the last launch of render({k}) ran with (a table, the lists) = {(info['in_force'], info['lists'])}, the calls say "
+                       f"{want} (switch {self.tables.mode}, generation {self.gen}, {self.fif} frames in flight)")
 
     def check(self):
         m = self.model
@@ -880,15 +994,44 @@ class Run:
                 self._bump("mask tables checked")
                 if len(ri):
                     self._fail(f"camera masks: {len(ri)} required (ray, sphere) pairs lie in a cluster the table's entry does not set")
+                self.check_lists(full, ray_tex, required[first_cam:])
         why = self._dev("debug_check_context")
         if why is not None:
             self._fail(f"the context is not sound: {why}")
 
+    def check_lists(self, full, ray_tex, required):
+        """the sphere lists of the build the masks came from: tests/camera_list_ref.py's for the hierarchy as the device holds it
+        and the model's camera, and on them every (ray, sphere) pair the oracle requires of the check's camera rays"""
+        m = self.model
+        members, n_top, direct_first = full["nodes"][:full["n_members"]], len(full["top"]), full["direct_first"]
+        n_slots = min(4 * n_top, direct_first, len(members))
+        words = self._dev("debug_read_camera_lists")
+        ref = CL.camera_lists_ref(members, n_top, direct_first, m.cam_raw, W, H)
+        try:
+            got, over = CL.unpack(words, n_slots)
+        except AssertionError as e:
+            self._fail(f"camera lists: an entry is malformed (entry, its slots or count): {e}")
+        self._bump("list tables checked")
+        if got.shape != ref.shape:
+            self._fail(f"camera lists: {got.shape} entries x slots against the reference's {ref.shape}")
+        want_over = ref.sum(1) > CL.CAP
+        if not np.array_equal(over, want_over):
+            bad = np.nonzero(over != want_over)[0]
+            self._fail(f"camera lists: the overflow flags of {len(bad)} entries differ from the reference's; first: entry {bad[0]}")
+        if not np.array_equal(got[~over], ref[~over]):
+            bad = np.argwhere(got != ref)
+            bad = bad[~over[bad[:, 0]]]
+            self._fail(f"camera lists: {len(bad)} (entry, slot) answers differ from the reference's; first: entry {bad[0][0]}, slot {bad[0][1]}: "
+                       f"{got[tuple(bad[0])]} against {ref[tuple(bad[0])]}")
+        ri, si = CL.missing_pairs(got, over, ray_tex, required, CL.slot_of_sphere(full["midx"], n_slots, members, len(m.spheres)))
+        if len(ri):
+            self._fail(f"camera lists: {len(ri)} required (ray, sphere) pairs are not on the list of the ray's entry")
 
-def run(case, impl, model, O, stats=None, after=None, device_checks=True):
+
+def run(case, impl, model, O, stats=None, after=None, device_checks=True, tables=None):
     """Applies chain `case` to impl and model in lock step; raises ChainMismatch at the first difference."""
     p, ops = chain(case)
-    r = Run(f"chain {case}", p, impl, model, O, stats, after, device_checks)
+    r = Run(f"chain {case}", p, impl, model, O, stats, after, device_checks, tables)
     for op in ops:
         r.step(op)
     return r

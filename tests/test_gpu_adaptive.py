@@ -65,7 +65,7 @@ def _schedule(rng, n_tiles, steps):
     return out
 
 
-def _run_and_expect(st, acc, means, schedule, per_call):
+def _run_and_expect(st, acc, means, schedule, per_call, after_tiles=None):
     for step in schedule:
         k = step[-1] if per_call else 1
         reps = 1 if per_call else step[-1]
@@ -78,22 +78,32 @@ def _run_and_expect(st, acc, means, schedule, per_call):
                 st.render_tiles(step[1], k)
                 for _ in range(k):
                     acc.frame(means[acc.frames_done], step[1])
+                if after_tiles is not None:
+                    after_tiles(st)
 
 
 @pytest.mark.parametrize("schedule", ["single", "multi", "pinned-8x2"])
 @pytest.mark.parametrize("max_w", [1.0, 0.75])
 @pytest.mark.parametrize("scene,rng_mode", [("default", 0), ("cover-glass", 0), ("cover", 1), ("default", 1)])
 def test_mixed_schedules_match_the_oracle_bit_for_bit(mrt, oracle, scene, rng_mode, max_w, schedule):
+    mixed_schedule_matches_the_oracle(mrt, oracle, scene, rng_mode, max_w, schedule)
+
+
+def mixed_schedule_matches_the_oracle(mrt, oracle, scene, rng_mode, max_w, schedule, camera_tables=None, after_tiles=None):
+    """the body of the test above; camera_tables: mrt_debug_set_camera_masks' value (None: the library's rule, which gives a
+    48x27 image the masks); after_tiles(st): called behind every render_tiles (tests/test_gpu_camera_list_launches.py)"""
     means = Means(oracle, mrt, scene, 11, W, H, SPP, DEPTH, rng_mode)
     acc = adaptive_ref.Accum(H, W, max_w)
     sched = _schedule(np.random.default_rng(zlib.crc32(f"{scene} {rng_mode} {max_w} {schedule}".encode())), acc.n_tiles, 5)
     with mrt.State(mrt.Args(W, H, SPP, DEPTH, max_w), seed=11) as st:
+        if camera_tables is not None:
+            st.debug_set_camera_masks(camera_tables)
         _setup(mrt, st, scene, rng_mode)
         if schedule == "pinned-8x2":
             st.set_schedule_hint(8, 2)
         if schedule == "multi":
             st.debug_set_frame_batching(2)          # k frames of one call in one launch, the in-lane form (stream mode)
-        _run_and_expect(st, acc, means, sched, per_call=schedule == "multi")
+        _run_and_expect(st, acc, means, sched, per_call=schedule == "multi", after_tiles=after_tiles)
         st.sync()
         assert st.frames_done == acc.frames_done
         assert np.array_equal(st.tile_frames(), acc.tile_frames())

@@ -152,8 +152,10 @@ def test_counter_mode_large_scene_and_shards(mrt, oracle):
 
 
 def test_every_render_kernel_instantiation_against_the_oracle(mrt, oracle):
-    """render_kernel<COUNT, PILOT, CTR, SC, MFMA> has 24 frame instantiations and 12 pilot ones (the pilot never counts);
-    the DBG ones (6) are what tests/test_gpu_superset.py drives.  Every one of them renders a frame here that must equal the
+    """render_kernel<COUNT, PILOT, CTR, SC, MFMA> has 32 frame instantiations and 16 pilot ones (the pilot never counts);
+    the DBG ones (6) are what tests/test_gpu_superset.py drives.  The 8 frame and 4 pilot ones of SC = 3 (the camera-ray
+    sphere lists, bit 6 of mrt_debug_last_launch) need a built table, which a first frame of 16 spp never has: they are
+    tests/test_gpu_camera_list_launches.py's.  Every one of the other 24 and 12 renders a frame here that must equal the
     oracle's: {with, without the RNG draw counter} x {stream, counter RNG} x {small-scene layout: cover scene; large-scene
     layout with the quadratic form of the box slack: 1,297 spheres; with the linear form: the same plus 100 spheres up to 5,000
     units away} x {SGPR-fed VALU sweep, matrix-core sweep}, each with the schedule forced so that the frame is preceded by a

@@ -1,6 +1,10 @@
 """Host tests of the motion chains (tests/motion_chains.py): the generator is deterministic and covers its vocabulary and the three
 call patterns the chains exist for; the reference alone meets the conditions without which the GPU tests would pass vacuously;
 and the runner, driven with the model in the implementation's place, reports every seeded defect of that stand-in."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -33,6 +37,49 @@ def test_a_case_number_reproduces_its_chain():
     for case in MC.SUITE_CASES:
         assert MC.chain(case) == MC.chain(case)
     assert MC.chain(0)[1] != MC.chain(1)[1]
+
+
+def test_the_generator_still_draws_the_recorded_chains():
+    """tests/golden/motion_chain_digests.json: sha256 of repr(chain(case)), cases 0 .. 11 recorded before the list flavours were
+    added to the generator (they must not change by one op: the suite's statistics were set for them), 12 .. 15 when they were final"""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "motion_chain_digests.json")) as f:
+        want = json.load(f)
+    assert sorted(want, key=int) == [str(c) for c in MC.SUITE_CASES]
+    got = {str(c): hashlib.sha256(repr(MC.chain(c)).encode()).hexdigest() for c in MC.SUITE_CASES}
+    assert got == want, [c for c in got if got[c] != want[c]]
+
+
+LIST_CASES = (12, 13, 14, 15)
+
+
+def test_the_list_chains_switch_between_no_table_the_masks_and_the_lists():
+    modes = set()
+    for case in LIST_CASES:
+        p, ops = MC.chain(case)
+        assert "lists" in p["flavour"] and p["layout"] == "small"
+        assert ops[1] == ("set_camera_masks", 2) and ("set_frame_batching", 0) in ops[:4]
+        assert {op[0] for op in ops} <= set(MC.VOCABULARY)
+        switch = [op[1] for op in ops if op[0] == "set_camera_masks"]
+        assert all(type(v) is int and v in (0, 2, 3) for v in switch) and switch[-1] == 2, (case, switch)
+        modes |= set(switch)
+    assert modes == {0, 2, 3}
+    for case in (0, 1, 2, 3):                   # the mask chains: off and the library's rule
+        assert {op[1] for op in MC.chain(case)[1] if op[0] == "set_camera_masks"} <= {False, True}
+
+
+def _predicted(stats):
+    """(generations with the lists in force, most frames in flight among them) from the decision model's own predictions"""
+    on = [(gen, fif) for gen, in_force, lists, fif in stats.get("predicted launches", []) if in_force and lists]
+    return len({gen for gen, _ in on}), max([fif for _, fif in on], default=0)
+
+
+def test_the_calls_alone_put_the_lists_in_force_across_generations(reference_runs):
+    """what tests/test_gpu_motion_chains.py::test_lists_were_in_force_across_generations asks of the device, asked of
+    CameraTables with no device: the condition can be met by the calls alone"""
+    seen = {case: _predicted(reference_runs[case][6]) for case in LIST_CASES}
+    assert sum(gens >= 2 and fif >= 4 for gens, fif in seen.values()) >= 3, seen
+    for case in (0, 1, 2, 3):                   # (the mask chains never ask for the lists: mode 1 leaves `lists` open)
+        assert all(lists is None or not in_force for _, in_force, lists, _ in reference_runs[case][6]["predicted launches"])
 
 
 def test_the_in_suite_cases_cover_the_vocabulary_and_the_patterns():
@@ -93,7 +140,7 @@ def test_the_in_suite_cases_cover_the_vocabulary_and_the_patterns():
         assert len(kinds_in.get(kind, ())) >= 2, kind
     assert all(v >= 3 for v in patterns.values()), patterns
     assert refusals == set(MC.REFUSALS)
-    assert blocks == {0, 4} and in_flight == {0, 1, 4, 8} and sweeps == {0, 1, 2} and mask_switch == {False, True}
+    assert blocks == {0, 4} and in_flight == {0, 1, 4, 8} and sweeps == {0, 1, 2} and mask_switch == {False, True, 2, 3}
     layouts = {MC.chain(c)[0]["layout"] for c in MC.SUITE_CASES}
     assert layouts == {"small", "large-quad", "large-lin", "deep-4200"}
     # the partial updates: a range that ends at the last sphere, one of exactly one sphere, one anywhere
@@ -103,7 +150,7 @@ def test_the_in_suite_cases_cover_the_vocabulary_and_the_patterns():
 @pytest.fixture(scope="module")
 def reference_runs(oracle):
     """every in-suite case run with the model in both places: per case (params, ops, per check: (guide hits, ray hit share, pairs per
-    ray), the model, the shadow, the shadow's figures behind every op)"""
+    ray), the model, the shadow, the shadow's figures behind every op, the runner's statistics)"""
     out = {}
     for case in MC.SUITE_CASES:
         checks, trace = [], []
@@ -119,13 +166,13 @@ def reference_runs(oracle):
                 checks.append((int((g["index"] >= 0).sum()), float((hit >= 0).mean()), float(required.sum()) / len(rays), bool(unit.all())))
         p, ops = MC.chain(case)
         run = MC.run(case, MC.new_model(oracle, p), MC.new_model(oracle, p), oracle, after=after)
-        out[case] = (p, ops, checks, run.model, run.sh, trace)
+        out[case] = (p, ops, checks, run.model, run.sh, trace, run.stats)
     return out
 
 
 def test_the_reference_meets_the_conditions_the_gpu_tests_rest_on(reference_runs):
     drift_cases = shrink_cases = temporal_cases = 0
-    for case, (p, ops, checks, model, sh, trace) in reference_runs.items():
+    for case, (p, ops, checks, model, sh, trace, _) in reference_runs.items():
         assert len(checks) == sum(op[0] == "check" for op in ops)
         for k, (guide_hits, hit_share, pairs, unit) in enumerate(checks):
             assert 0 < guide_hits < W * H, (case, k, "the guides need hit pixels and sky pixels")
@@ -226,6 +273,87 @@ def test_the_runner_catches_a_defective_stand_in(oracle, defect):
         try:
             MC.run(case, MC.new_model(oracle, p, defect), MC.new_model(oracle, p), oracle)
         except MC.ChainMismatch:
+            caught.append(case)
+        if len(caught) >= 2:
+            break
+    assert len(caught) >= 2, (defect.__name__, caught)
+
+
+# ------------------------------------------------------------------ ... and a defective decision model
+
+class FollowsTheRule(MC.Model):
+    """A stand-in for the implementation that reports which table its last launch got, by the true rule (its own CameraTables,
+    driven by the calls it receives: every render of these chains is a launch per frame)"""
+
+    def __init__(self, O, max_w):
+        self.cam_tables, self.cam_last, self.cam_slots = MC.CameraTables(), (False, False), 2
+        super().__init__(O, max_w)
+
+    def _small(self):
+        return len(self.spheres) == len(MC.layout_scene("small"))
+
+    def set_world(self, spheres):
+        super().set_world(spheres)
+        self.cam_tables.call("set_world")
+
+    def update_spheres(self, first, xyzr):
+        super().update_spheres(first, xyzr)     # (a refused one raises before this)
+        if len(xyzr):
+            self.cam_tables.call("update_spheres")
+
+    def regroup_spheres(self):
+        super().regroup_spheres()
+        self.cam_tables.call("regroup_spheres")
+
+    def set_camera(self, cam):
+        super().set_camera(cam)
+        if cam is not None:
+            self.cam_tables.call("set_camera")
+
+    def debug_set_camera_masks(self, on):
+        self.cam_tables.mode = int(on)
+
+    def debug_set_frames_in_flight(self, slots):
+        self.cam_slots = slots or 2
+
+    def render(self, frames=1):
+        super().render(frames)
+        for _ in range(frames):
+            self.cam_last = self.cam_tables.launch(self._small(), self.cam_slots, MC.SPP)
+
+    def debug_read_camera_masks(self, table=True):
+        in_force, lists = self.cam_last
+        return dict(in_force=in_force, lists=bool(lists), built=False, masks=None)
+
+
+class CameraChangeLeavesTheTable(MC.CameraTables):
+    """a camera change does not make the table stale"""
+    def stale_after(self, call):
+        return call != "set_camera" and super().stale_after(call)
+
+
+class EverySlotBuiltOnceAnyIs(MC.CameraTables):
+    """every slot counts as built once any slot is: the slots' records are not read against the generation"""
+    def slot_has_built(self, slot):
+        return bool(self.slot_gen)
+
+
+def test_the_correct_decision_model_agrees_with_the_stand_in(oracle):
+    for case in (1, 12):
+        p, _ = MC.chain(case)
+        run = MC.run(case, MC.new_model(oracle, p, FollowsTheRule), MC.new_model(oracle, p), oracle)
+        assert len(run.stats["list launches"]) == len(run.stats["predicted launches"]) >= 8
+
+
+@pytest.mark.parametrize("defect", [CameraChangeLeavesTheTable, EverySlotBuiltOnceAnyIs], ids=lambda c: c.__name__)
+def test_the_runner_catches_a_defective_decision_model(oracle, defect):
+    caught = []
+    for case in (0, 1, 2, 3) + LIST_CASES:
+        p, _ = MC.chain(case)
+        try:
+            MC.run(case, MC.new_model(oracle, p, FollowsTheRule), MC.new_model(oracle, p), oracle, tables=defect)
+        except MC.ChainMismatch as e:
+            assert "the calls say" in str(e), e
             caught.append(case)
         if len(caught) >= 2:
             break
