@@ -45,7 +45,8 @@ extern "C" {
  * MRT_PRESENT_TEMPORAL); the temporal response (mrt_temporal_response, mrt_temporal_response_default,
  * mrt_set_temporal_response, mrt_get_temporal_response); the noise estimate across shards and the gathered frame's denoise
  * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED); the denoise of
- * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive). */
+ * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive); the auto-regroup policy (mrt_auto_regroup,
+ * mrt_auto_regroup_default, mrt_set_auto_regroup, mrt_get_auto_regroup, mrt_regroup_stats, mrt_read_regroup_stats). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -230,7 +231,8 @@ int mrt_set_world(mrt_ctx* ctx, const mrt_sphere* spheres, size_t n);
  *   The launch schedule is not restarted and the tile costs stay valid: a caller that updates every frame still reaches a
  *     settled schedule (mrt_get_schedule), and a pinned hint stays as it is.
  *   Regrouping: the bounds only get looser as spheres leave the groups they were built in.  The image never changes, only the
- *     speed; mrt_read_counters' member_tests per world_hit_calls is the signal to watch, and mrt_regroup_spheres regroups.
+ *     speed; mrt_read_counters' member_tests per world_hit_calls is the signal to watch, and mrt_regroup_spheres regroups --
+ *     or mrt_set_auto_regroup has the library judge the bounds itself and regroup when they have loosened.
  *   The matrix-core sweep runs in the world's own space (no per-scene axis scale) after an update; the scaled space comes back
  *     with the next mrt_set_world*.
  *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as a failed mrt_set_world* does. */
@@ -252,6 +254,49 @@ int mrt_update_spheres(mrt_ctx* ctx, uint32_t first, uint32_t count, const float
  *     axis scale until the next mrt_set_world*.
  *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as for mrt_update_spheres. */
 int mrt_regroup_spheres(mrt_ctx* ctx);
+/* WHEN to regroup, decided by the library (opt-in; off by default, and off every call queues exactly the launches it queues
+ * without this and the policy's state is never written).  With the policy on, every check_every-th successful non-empty
+ * mrt_update_spheres call queues, behind its scatter, a judgement of the hierarchy and a regroup that runs only if the
+ * judgement says so; the refit follows as always.  The decision is made on the device: nothing waits on the host, the host
+ * never learns the verdict (mrt_read_regroup_stats reads it, and synchronises), no buffer is created or freed.
+ *   The figure: for each level k = 1 .. levels, Q_k = the sum of R^2 (in double, from the records' -R^2) over the level's nodes
+ *     whose span begins inside the pool of clustered spheres, never-hit nodes aside; Q = ((Q_1 + Q_2) + ..), in a fixed order of
+ *     additions (tests/regroup_policy_ref.py restates it; the device matches it bit for bit).  It depends on the geometry and the
+ *     grouping alone -- not on the camera -- so the ranks of a sharded frame decide alike.
+ *   The rule: regroup when Q > (double)ratio x Q_ref, Q_ref being Q right after the last regroup (the policy's or the caller's
+ *     own mrt_regroup_spheres), or when the policy was turned on, or -- for a scene set with the policy on -- at its first check.
+ *   One update stale: the judgement reads the bounds the previous update's refit left, those the last frames were rendered
+ *     with, before this update's refit replaces them (so that no second, conditional refit is needed); the regroup itself
+ *     orders the spheres as this update leaves them.
+ *   check_every 1 .. 1024, ratio finite and >= 1, enabled 0 or 1, size = sizeof(mrt_auto_regroup), reserved 0: anything else is
+ *     MRT_ERR_INVALID_ARG with nothing changed.  ctx NULL: mrt_set_auto_regroup checks p only (host only).
+ *   The defaults (check_every 8, ratio 1.5) are measured on the animated 10,001-sphere stress scene: check_every is the smallest
+ *     power of two at which a check that does not fire costs under 1 % of a step, ratio the fastest of 1.5, 2, 3 and 4
+ *     (profiles/animation_rates.txt, section "auto-regroup").
+ *   The setting survives mrt_reset, mrt_set_world*, mrt_set_camera and mrt_set_shard; the statistics restart with every
+ *     mrt_set_world*.  A scene whose spheres share at most one cluster is never checked: MRT_OK, statistics all zero.
+ *   Everything mrt_update_spheres and mrt_regroup_spheres promise holds with the policy on: images, the accumulation and the
+ *     counters samples / world_hit_calls / rng_draws never depend on it; tile costs, schedule and hint stay.
+ *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as for mrt_update_spheres. */
+typedef struct {
+    uint32_t size;          /* sizeof(mrt_auto_regroup): the version of this struct */
+    uint32_t enabled;       /* 0 (default) | 1 */
+    uint32_t check_every;   /* judge the hierarchy at every check_every-th update: 1 .. 1024 */
+    float ratio;            /* regroup when Q > ratio x Q_ref: finite, >= 1 */
+    uint32_t reserved[4];   /* 0 */
+} mrt_auto_regroup;          /* sizeof 32 */
+void mrt_auto_regroup_default(mrt_auto_regroup* out);      /* enabled 0 */
+int mrt_set_auto_regroup(mrt_ctx* ctx, const mrt_auto_regroup* p);
+int mrt_get_auto_regroup(mrt_ctx* ctx, mrt_auto_regroup* out);
+typedef struct {
+    uint64_t checks, regroups;      /* judgements made / regroups they let run, since mrt_set_world* */
+    double q_ref, q_last;           /* Q_ref; Q as the last judgement (or reference taking) saw it */
+    double q_level[4];              /* Q_1 .. Q_levels of q_last */
+    uint32_t levels, pending;       /* pending 1: the next judgement takes Q_ref instead of deciding */
+} mrt_regroup_stats;                /* sizeof 72 */
+/* The policy's state as the device holds it; waits for the ctx's stream as mrt_read_counters does.  MRT_ERR_NO_SCENE without a
+ * scene; all zeros for a scene that is never checked. */
+int mrt_read_regroup_stats(mrt_ctx* ctx, mrt_regroup_stats* out);
 /* The AoS -> SoA packing of lib.rs:722-799 (host only, no GPU needed).  Capacities are
  * in elements (vec4: 4 floats each); returns MRT_ERR_TOO_SMALL if any is short.
  * Needs at most 2n vec4, 2n f32, 2n i32. */

@@ -54,6 +54,7 @@ EXPORTS = [
     "mrt_debug_read_temporal_fast", "mrt_debug_load_temporal_fast",
     "mrt_set_gather_noise", "mrt_read_gathered_noise", "mrt_read_gathered_denoised", "mrt_debug_read_gathered_guides",
     "mrt_set_denoise_adaptive", "mrt_get_denoise_adaptive", "mrt_debug_load_accumulation",
+    "mrt_auto_regroup_default", "mrt_set_auto_regroup", "mrt_get_auto_regroup", "mrt_read_regroup_stats",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -127,6 +128,16 @@ class MrtTemporalParams(C.Structure):
 class MrtTemporalResponse(C.Structure):
     _fields_ = [("size", C.c_uint32), ("enabled", C.c_uint32), ("fast_history", C.c_uint32), ("clamp_sigma", C.c_float),
                 ("antilag", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class MrtAutoRegroup(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("enabled", C.c_uint32), ("check_every", C.c_uint32), ("ratio", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class MrtRegroupStats(C.Structure):
+    _fields_ = [("checks", C.c_uint64), ("regroups", C.c_uint64), ("q_ref", C.c_double), ("q_last", C.c_double),
+                ("q_level", C.c_double * 4), ("levels", C.c_uint32), ("pending", C.c_uint32)]
 
 
 class MrtSphere(C.Structure):
@@ -253,6 +264,10 @@ def load():
         "mrt_update_spheres": (i32, [vp, u32, u32, vp]),
         "mrt_regroup_spheres": (i32, [vp]),
         "mrt_debug_regroup_info": (i32, [vp, vp]),
+        "mrt_auto_regroup_default": (None, [P(MrtAutoRegroup)]),
+        "mrt_set_auto_regroup": (i32, [vp, P(MrtAutoRegroup)]),
+        "mrt_get_auto_regroup": (i32, [vp, P(MrtAutoRegroup)]),
+        "mrt_read_regroup_stats": (i32, [vp, P(MrtRegroupStats)]),
         "mrt_debug_set_regroup_block": (i32, [vp, u32]),
         "mrt_debug_set_camera_masks": (i32, [vp, i32]),
         "mrt_debug_read_camera_masks": (i32, [vp, vp, vp, sz]),

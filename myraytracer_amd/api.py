@@ -308,6 +308,33 @@ class State:
         update_spheres calls have moved them), refitted in stream order; images do not change, member_tests do."""
         self._check(self._L.mrt_regroup_spheres(self._ctx), "mrt_regroup_spheres")
 
+    def set_auto_regroup(self, enabled: bool = True, ratio: Optional[float] = None, check_every: Optional[int] = None):
+        """mrt_set_auto_regroup: have update_spheres judge the hierarchy on the device at every check_every-th call and regroup
+        when the sum of R^2 over its nodes exceeds `ratio` x its value after the last regroup; None keeps the current number.
+        Off by default; images never depend on it."""
+        p = _lib.MrtAutoRegroup()
+        self._check(self._L.mrt_get_auto_regroup(self._ctx, C.byref(p)), "mrt_get_auto_regroup")
+        p.enabled = int(bool(enabled))
+        if ratio is not None:
+            p.ratio = ratio
+        if check_every is not None:
+            p.check_every = check_every
+        self._check(self._L.mrt_set_auto_regroup(self._ctx, C.byref(p)), "mrt_set_auto_regroup")
+
+    def get_auto_regroup(self) -> dict:
+        """enabled, ratio, check_every (mrt_get_auto_regroup)"""
+        p = _lib.MrtAutoRegroup()
+        self._check(self._L.mrt_get_auto_regroup(self._ctx, C.byref(p)), "mrt_get_auto_regroup")
+        return dict(enabled=bool(p.enabled), ratio=float(p.ratio), check_every=int(p.check_every))
+
+    def read_regroup_stats(self) -> dict:
+        """the auto-regroup policy's state on the device: checks, regroups, q_ref, q_last, q_level (one float64 per level), pending
+        (mrt_read_regroup_stats; waits for the context's stream)"""
+        s = _lib.MrtRegroupStats()
+        self._check(self._L.mrt_read_regroup_stats(self._ctx, C.byref(s)), "mrt_read_regroup_stats")
+        return dict(checks=int(s.checks), regroups=int(s.regroups), q_ref=float(s.q_ref), q_last=float(s.q_last),
+                    q_level=[float(v) for v in s.q_level[:s.levels]], levels=int(s.levels), pending=bool(s.pending))
+
     def debug_regroup_info(self) -> dict:
         """n_pool, the block capacity in force, and the global / in-LDS depths of the last regroup (mrt_debug_regroup_info)"""
         out = (C.c_uint32 * 4)()

@@ -33,6 +33,8 @@ static_assert(sizeof(mrt::SphereRec) == 16, "SphereRec layout");
 static_assert(sizeof(mrt_noise_report) == 96 && offsetof(mrt_noise_report, pixels) == 16 && offsetof(mrt_noise_report, threshold) == 40 &&
               offsetof(mrt_noise_report, noise_factor) == 48 && offsetof(mrt_noise_report, max_se) == 88, "mrt_noise_report layout");
 static_assert(sizeof(mrt::NoiseSums) == 48, "NoiseSums layout");
+static_assert(sizeof(mrt_auto_regroup) == 32 && sizeof(mrt_regroup_stats) == 72 && offsetof(mrt_regroup_stats, q_ref) == 16 &&
+              offsetof(mrt_regroup_stats, levels) == 64, "mrt_auto_regroup / mrt_regroup_stats layout");
 static_assert(sizeof(mrt_present_info) == 40 && offsetof(mrt_present_info, frames_done) == 8 &&
               offsetof(mrt_present_info, ring_depth) == 36, "mrt_present_info layout");
 
@@ -828,6 +830,8 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
     if (c->have_world) {
         if (!c->d_spheres || !c->d_clusters || !c->d_nodes || !c->d_top_mfma || !c->d_member_index || !c->d_regroup || !c->d_prev_xyzr || !c->d_shade || !c->d_vec4 || !c->d_f32 || !c->d_i32)
             return check_finding(why, cap, "have_world without one of the scene's arrays");
+        if (c->regroup_words != (c->n_pool > 1 ? mrt::regroup_layout(c->n_pool, c->n_pooled).words : 0))
+            return check_finding(why, cap, "a regroup scratch of %zu words for %u pool clusters of %u spheres (the policy's state is its tail)", c->regroup_words, c->n_pool, c->n_pooled);
         if (!mrt::scene_is_small(c->n_members) && (!c->d_boxes || !c->d_boxes_open)) return check_finding(why, cap, "a large scene (%u members) without its boxes", c->n_members);
         if (mrt::scene_is_small(c->n_members) && c->n_padded <= mrt::kCamMaskRecords && (!c->d_cam_masks || c->cam_mask_entries == 0))
             return check_finding(why, cap, "a small scene of %u top records without its camera masks", c->n_padded);
@@ -864,6 +868,8 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
     if (!c->temporal_on && (c->d_den[7] || c->d_den[8])) return check_finding(why, cap, "fast history buffers exist while temporal reprojection is off");
     if (c->temporal_response.enabled > 1 || c->temporal_response.size != sizeof(mrt_temporal_response))
         return check_finding(why, cap, "temporal response enabled %u, size %u", c->temporal_response.enabled, c->temporal_response.size);
+    if (c->auto_regroup.enabled > 1 || c->auto_regroup.size != sizeof(mrt_auto_regroup) || c->auto_regroup.check_every < 1 || c->auto_regroup.check_every > 1024)
+        return check_finding(why, cap, "auto regroup enabled %u, size %u, check_every %u", c->auto_regroup.enabled, c->auto_regroup.size, c->auto_regroup.check_every);
     if (c->d_guide_cand == nullptr ? c->guide_cand_words != 0 : c->guide_cand_words == 0) return check_finding(why, cap, "guide bitmap %p of %zu words", (void*)c->d_guide_cand, c->guide_cand_words);
     if (c->tiles_diverged) {
         if (c->n_tiles && !c->d_tile_frames) return check_finding(why, cap, "the accumulation has diverged without the tile frame counts");

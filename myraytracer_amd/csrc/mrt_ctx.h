@@ -49,6 +49,12 @@ struct mrt_ctx {
     uint32_t* d_regroup = nullptr;
     uint32_t n_pool = 0, n_pooled = 0;
     uint32_t regroup_block = 0, regroup_last[3] = {0, 0, 0};
+    // the auto-regroup policy (mrt_set_auto_regroup; regroup_policy.hip): the setting, which outlives the scene; the words of
+    // d_regroup (0: the stub of a scene without a pool), whose last ones are the policy's RegroupState; the scene's successful
+    // non-empty mrt_update_spheres calls since the policy or the scene was set (every check_every-th of them checks)
+    mrt_auto_regroup auto_regroup = mrt::auto_regroup_defaults();
+    size_t regroup_words = 0;
+    uint32_t auto_updates = 0;
     // Camera-ray cluster masks (cam_mask.hip; frames.cpp, camera_masks): a scene buffer (mrt_set_world_raw makes it for a small
     // scene of at most kCamMaskRecords top records, all ones, sized for the shard as it is then; free_world frees it) of
     // cam_mask_entries entries of 4 words.  ONE staleness generation, bumped by everything the masks depend on (scene, camera,

@@ -292,10 +292,21 @@ int launch_refit(const RefitArgs& a, void* stream);
 //   ord    two orders of the pool, written in turn by the depths whose segments are wider than a block
 //   box    6 words per segment of such a depth: min x, y, z and max x, y, z of the centres in key form
 //   keys   n_sort u64 composite keys (segment, key along the segment's axis, rank), sorted in place
+//   state  the auto-regroup policy's RegroupState (regroup_policy.hip), 8-byte aligned: uploaded as "baseline pending, counters 0",
+//          written by the device alone from then on, and only while the policy is on (mrt_set_auto_regroup)
 constexpr uint32_t kRegroupBlock = 512;      // clusters per workgroup of the block kernel: at most 2,048 spheres in LDS
 constexpr uint32_t kRegroupChunk = 4 * kRegroupBlock;
 constexpr uint32_t kRegroupMaxSegments = 4096;   // 12 bits of a composite key; 32 for the key, 20 for the rank (kMaxSpheres)
-struct RegroupLayout { size_t pool, clus, pref, ord[2], box, keys, words; uint32_t n_sort; };
+// The policy's state: q_level[k - 1] = the quality figure of level k (the sum of R^2 over its nodes that begin inside the pool), q_last
+// their sum as the last judgement saw it, q_ref the sum right after the last regroup (or when the policy was turned on); pending: the
+// next judgement takes q_ref instead of deciding; gate: what the regroup kernels queued behind a check read (0: return at once).
+struct RegroupState {
+    double q_ref, q_last, q_level[kMaxLevels];
+    uint32_t pending, gate;
+    uint64_t checks, regroups;
+};
+static_assert(sizeof(RegroupState) == 72 && sizeof(RegroupState) % 8 == 0, "RegroupState is 18 words of the scratch");
+struct RegroupLayout { size_t pool, clus, pref, ord[2], box, keys, state, words; uint32_t n_sort; };
 inline RegroupLayout regroup_layout(uint32_t n_pool, uint32_t pooled) {
     RegroupLayout l{};
     l.n_sort = kRegroupChunk;
@@ -309,6 +320,7 @@ inline RegroupLayout regroup_layout(uint32_t n_pool, uint32_t pooled) {
     l.box = at; at += 6 * ((size_t)n_pool / 8 + 2);      // the narrowest such depth has segments of 8 clusters (a block of 4)
     at += at & 1;                                        // (the keys are 8 bytes each)
     l.keys = at; at += 2 * (size_t)l.n_sort;
+    l.state = at; at += sizeof(RegroupState) / sizeof(uint32_t);     // (at is even here: the state is 8-byte aligned)
     l.words = at;
     return l;
 }
@@ -318,11 +330,32 @@ struct RegroupArgs {
     uint32_t* scratch;
     uint32_t n_pool, pooled;
     uint32_t block;             // clusters per workgroup of the block kernel: a power of two, 4 .. kRegroupBlock
+    const uint32_t* gate;       // null: run (mrt_regroup_spheres); else every kernel returns at once where *gate == 0
 };
 // the block in force for n_pool clusters (raised while a depth above it would have more than kRegroupMaxSegments segments), and
 // the depths above it / within it: host only
 void regroup_plan(uint32_t n_pool, uint32_t block, uint32_t out[3]);
 int launch_regroup(const RegroupArgs& a, void* stream);
+
+// regroup_policy.hip (include/myraytracer_amd.h, mrt_set_auto_regroup): the hierarchy judged on the device.  Q_k = the sum of
+// (double)(-neg_r2) over the records j of level k (1 .. levels; the top is `clusters`, the others nodes + level_base[k]) with
+// j 4^(k-1) < n_pool, never-hit records skipped, in a FIXED order (tests/regroup_policy_ref.py): lane l of the one 256-thread
+// workgroup takes j = l, l + 256, .. ascending, lane 0 adds the 256 partials in lane order; Q = ((Q_1 + Q_2) + ..).
+//   kQualityDecide: Q -> q_level, q_last; checks++; pending ? (q_ref = Q, pending = gate = 0)
+//                   : Q > (double)ratio * q_ref ? (gate = pending = 1, regroups++) : gate = 0.
+//   kQualityBaseline: if pending (or `mark`, which sets it first: a regroup the policy did not decide): Q -> q_ref, q_last, q_level,
+//                   pending = 0; else nothing.
+struct QualityArgs {
+    const SphereRec* nodes;
+    const SphereRec* clusters;
+    RegroupState* state;
+    uint32_t levels, n_nodes, n_padded, n_pool;
+    uint32_t level_base[kMaxLevels];
+    uint32_t mode, mark;
+    float ratio;
+};
+constexpr uint32_t kQualityDecide = 0, kQualityBaseline = 1;
+int launch_regroup_quality(const QualityArgs& a, void* stream);
 
 // denoise.hip (include/myraytracer_amd.h, "denoiser"): world-1 texels (y * width + x), rows < height only.
 // launch_guide_rays: 6 floats per pixel, the centre ray of the render's camera; launch_guide_fill: {sphere | -1, bits of t} per
@@ -419,6 +452,12 @@ inline mrt_temporal_response temporal_response_defaults() {
     mrt_temporal_response p{};
     p.size = sizeof(mrt_temporal_response);
     p.enabled = 0; p.fast_history = 4; p.clamp_sigma = 2.0f; p.antilag = 1.0f;      // the grid: profiles/temporal_response_quality.txt
+    return p;
+}
+inline mrt_auto_regroup auto_regroup_defaults() {
+    mrt_auto_regroup p{};
+    p.size = sizeof(mrt_auto_regroup);
+    p.enabled = 0; p.check_every = 8; p.ratio = 1.5f;       // measured: profiles/animation_rates.txt, section "auto-regroup"
     return p;
 }
 

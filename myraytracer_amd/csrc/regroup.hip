@@ -104,9 +104,15 @@ __device__ __forceinline__ void lds_bitonic(uint64_t* sh, uint32_t n, uint32_t g
     }
 }
 
+// The gate of a regroup queued behind the auto-regroup policy's judgement (regroup_policy.hip): null, or a word that kernel wrote --
+// 0: the hierarchy is good enough, every kernel of launch_regroup returns at once.  One uniform read for the whole grid, taken
+// before any barrier or LDS use, so that no barrier is ever reached by part of a workgroup.
+__device__ __forceinline__ bool gate_shut(const uint32_t* gate) { return gate != nullptr && *gate == 0u; }
+
 // ---- the depths above a block: global memory ----
 
-__global__ void __launch_bounds__(kFlat) regroup_box_clear_kernel(uint32_t* box, uint32_t n_seg) {
+__global__ void __launch_bounds__(kFlat) regroup_box_clear_kernel(uint32_t* box, uint32_t n_seg, const uint32_t* gate) {
+    if (gate_shut(gate)) return;
     const uint32_t i = blockIdx.x * kFlat + threadIdx.x;
     if (i < 6u * n_seg) box[i] = (i % 6u) < 3u ? 0xFFFFFFFFu : 0u;
 }
@@ -114,6 +120,7 @@ __global__ void __launch_bounds__(kFlat) regroup_box_clear_kernel(uint32_t* box,
 // one lane per rank of the current order: its centre into its segment's box (only sorted segments read theirs)
 __global__ void __launch_bounds__(kFlat) regroup_box_kernel(const RegroupArgs a, const uint32_t* order, const uint32_t* clus,
                                                             uint32_t* box, uint32_t size) {
+    if (gate_shut(a.gate)) return;
     const uint32_t i = blockIdx.x * kFlat + threadIdx.x;
     const bool active = i < a.pooled;
     uint32_t seg = 0, k[3] = {0, 0, 0};
@@ -127,6 +134,7 @@ __global__ void __launch_bounds__(kFlat) regroup_box_kernel(const RegroupArgs a,
 
 __global__ void __launch_bounds__(kFlat) regroup_key_kernel(const RegroupArgs a, const uint32_t* order, const uint32_t* clus,
                                                             const uint32_t* box, uint32_t size, uint64_t* keys, uint32_t n_sort) {
+    if (gate_shut(a.gate)) return;
     const uint32_t i = blockIdx.x * kFlat + threadIdx.x;
     if (i >= n_sort) return;
     uint64_t key = ~0ull;                                   // the padding sorts last
@@ -144,8 +152,9 @@ __global__ void __launch_bounds__(kFlat) regroup_key_kernel(const RegroupArgs a,
 }
 
 // the stages k_first .. k_last of the sort of n_sort keys, the steps below kRegroupChunk: one chunk a workgroup, in LDS
-__global__ void __launch_bounds__(kThreads) regroup_sort_local_kernel(uint64_t* keys, uint32_t k_first, uint32_t k_last) {
+__global__ void __launch_bounds__(kThreads) regroup_sort_local_kernel(uint64_t* keys, uint32_t k_first, uint32_t k_last, const uint32_t* gate) {
     __shared__ uint64_t sh[kRegroupChunk];
+    if (gate_shut(gate)) return;
     const uint32_t gbase = blockIdx.x * kRegroupChunk;
     for (uint32_t t = threadIdx.x; t < kRegroupChunk; t += kThreads) sh[t] = keys[gbase + t];
     __syncthreads();
@@ -154,7 +163,8 @@ __global__ void __launch_bounds__(kThreads) regroup_sort_local_kernel(uint64_t* 
 }
 
 // step j >= kRegroupChunk of stage k: one compare-exchange a lane
-__global__ void __launch_bounds__(kFlat) regroup_sort_step_kernel(uint64_t* keys, uint32_t n_sort, uint32_t k, uint32_t j) {
+__global__ void __launch_bounds__(kFlat) regroup_sort_step_kernel(uint64_t* keys, uint32_t n_sort, uint32_t k, uint32_t j, const uint32_t* gate) {
+    if (gate_shut(gate)) return;
     const uint32_t t = blockIdx.x * kFlat + threadIdx.x;
     if (t >= n_sort / 2) return;
     const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;
@@ -163,7 +173,9 @@ __global__ void __launch_bounds__(kFlat) regroup_sort_step_kernel(uint64_t* keys
     if ((x > y) == up) { keys[i] = y; keys[l] = x; }
 }
 
-__global__ void __launch_bounds__(kFlat) regroup_gather_kernel(const uint64_t* keys, const uint32_t* order, uint32_t* order_out, uint32_t pooled) {
+__global__ void __launch_bounds__(kFlat) regroup_gather_kernel(const uint64_t* keys, const uint32_t* order, uint32_t* order_out, uint32_t pooled,
+                                                               const uint32_t* gate) {
+    if (gate_shut(gate)) return;
     const uint32_t i = blockIdx.x * kFlat + threadIdx.x;
     if (i >= pooled) return;
     const uint32_t rank = (uint32_t)keys[i] & kRankMask;
@@ -182,6 +194,7 @@ __global__ void __launch_bounds__(kThreads) regroup_block_kernel(const RegroupAr
     __shared__ uint32_t ck[3][kRegroupChunk];
     __shared__ uint32_t box[6 * (kRegroupBlock / 2)];
     __shared__ uint16_t ord[kRegroupChunk];
+    if (gate_shut(a.gate)) return;
     const uint32_t tid = threadIdx.x;
     const uint32_t c0 = blockIdx.x * a.block, c1 = min(a.n_pool, c0 + a.block), nc = c1 - c0;
     const uint32_t r0 = pref[c0], cnt = pref[c1] - r0;
@@ -295,17 +308,17 @@ int launch_regroup(const RegroupArgs& a_in, void* stream) {
     auto blocks = [](uint32_t n) { return dim3((n + kFlat - 1) / kFlat); };
     for (uint32_t size = size0; size > a.block; size >>= 1) {
         const uint32_t n_seg = (a.n_pool + size - 1) / size;
-        hipLaunchKernelGGL(regroup_box_clear_kernel, blocks(6 * n_seg), dim3(kFlat), 0, st, box, n_seg);
+        hipLaunchKernelGGL(regroup_box_clear_kernel, blocks(6 * n_seg), dim3(kFlat), 0, st, box, n_seg, a.gate);
         hipLaunchKernelGGL(regroup_box_kernel, blocks(a.pooled), dim3(kFlat), 0, st, a, order, clus, box, size);
         hipLaunchKernelGGL(regroup_key_kernel, blocks(n_sort), dim3(kFlat), 0, st, a, order, clus, (const uint32_t*)box, size, keys, n_sort);
-        hipLaunchKernelGGL(regroup_sort_local_kernel, dim3(n_sort / kRegroupChunk), dim3(kThreads), 0, st, keys, 2u, kRegroupChunk);
+        hipLaunchKernelGGL(regroup_sort_local_kernel, dim3(n_sort / kRegroupChunk), dim3(kThreads), 0, st, keys, 2u, kRegroupChunk, a.gate);
         for (uint32_t k = 2 * kRegroupChunk; k != 0 && k <= n_sort; k <<= 1) {
             for (uint32_t j = k >> 1; j >= kRegroupChunk; j >>= 1)
-                hipLaunchKernelGGL(regroup_sort_step_kernel, blocks(n_sort / 2), dim3(kFlat), 0, st, keys, n_sort, k, j);
-            hipLaunchKernelGGL(regroup_sort_local_kernel, dim3(n_sort / kRegroupChunk), dim3(kThreads), 0, st, keys, k, k);
+                hipLaunchKernelGGL(regroup_sort_step_kernel, blocks(n_sort / 2), dim3(kFlat), 0, st, keys, n_sort, k, j, a.gate);
+            hipLaunchKernelGGL(regroup_sort_local_kernel, dim3(n_sort / kRegroupChunk), dim3(kThreads), 0, st, keys, k, k, a.gate);
         }
         uint32_t* const out = a.scratch + L.ord[turn];
-        hipLaunchKernelGGL(regroup_gather_kernel, blocks(a.pooled), dim3(kFlat), 0, st, (const uint64_t*)keys, order, out, a.pooled);
+        hipLaunchKernelGGL(regroup_gather_kernel, blocks(a.pooled), dim3(kFlat), 0, st, (const uint64_t*)keys, order, out, a.pooled, a.gate);
         order = out;
         turn ^= 1u;
     }

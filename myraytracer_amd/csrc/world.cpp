@@ -42,6 +42,29 @@ mrt::RefitArgs refit_args(const mrt_ctx* c) {
     return a;
 }
 
+// The auto-regroup policy (mrt_set_auto_regroup; regroup_policy.hip): its state is the tail of the regroup scratch, there for every
+// scene with a pool of more than one cluster.  The judgement reads the records of the levels as the last refit left them.
+mrt::RegroupState* regroup_state(const mrt_ctx* c) {
+    return reinterpret_cast<mrt::RegroupState*>(c->d_regroup + mrt::regroup_layout(c->n_pool, c->n_pooled).state);
+}
+mrt::QualityArgs quality_args(const mrt_ctx* c, uint32_t mode, bool mark) {
+    mrt::QualityArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.nodes = c->d_nodes; q.clusters = c->d_clusters; q.state = regroup_state(c);
+    q.levels = c->levels; q.n_nodes = c->n_nodes; q.n_padded = c->n_padded; q.n_pool = c->n_pool;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) q.level_base[k] = c->level_base[k];
+    q.mode = mode; q.mark = mark ? 1u : 0u; q.ratio = c->auto_regroup.ratio;
+    return q;
+}
+mrt::RegroupArgs regroup_args(mrt_ctx* c, bool gated) {
+    mrt::RegroupArgs g;
+    g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
+    g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
+    g.gate = gated ? &regroup_state(c)->gate : nullptr;
+    if (!gated) mrt::regroup_plan(g.n_pool, g.block, c->regroup_last);       // (whether a gated one ran, only the device knows)
+    return g;
+}
+
 // The device arrays of the scene change (mrt_update_spheres, mrt_regroup_spheres; `who` for the messages): the ctx's stream waits
 // for the render kernels in flight, which read them; later frames wait for ev_inputs (inputs_dirty); the camera masks, which are
 // per cluster slot, are built anew; `change` queues what the call is about (-> 0 or a HIP error) and refit.hip derives
@@ -50,7 +73,10 @@ mrt::RefitArgs refit_args(const mrt_ctx* c) {
 // mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack is small against
 // R^2, a speed rule -- the sweep is conservative wherever it runs.  A failure leaves the device arrays between
 // two scenes: the context then has no scene until the next mrt_set_world*.
-template <class F> int change_scene(mrt_ctx* c, const char* who, F&& change) {
+// `rebaseline` (the auto-regroup policy, below): behind the refit, the policy's reference figure is taken anew where its state
+// says "pending" -- the judgement queued by `change` opened the gate -- or, with kMark, in any case (a regroup the caller asked for).
+enum Rebaseline { kNone, kIfPending, kMark };
+template <class F> int change_scene(mrt_ctx* c, const char* who, F&& change, Rebaseline rebaseline = kNone) {
     auto lost = [&](const char* what, hipError_t e) { c->have_world = false; return fail(c, MRT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e)); };
     for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
         mrt_ctx::FrameSlot& S = c->slot[i];
@@ -65,7 +91,19 @@ template <class F> int change_scene(mrt_ctx* c, const char* who, F&& change) {
     c->mfma_axis[0] = c->mfma_axis[1] = c->mfma_axis[2] = 1.0f;
     le = mrt::launch_refit(refit_args(c), c->stream);
     if (le) return lost("launch", (hipError_t)le);
+    if (rebaseline != kNone) {
+        le = mrt::launch_regroup_quality(quality_args(c, mrt::kQualityBaseline, rebaseline == kMark), c->stream);
+        if (le) return lost("launch", (hipError_t)le);
+    }
     return MRT_OK;
+}
+
+bool auto_regroup_ok(const mrt_auto_regroup* p) {
+    if (p->size != sizeof(mrt_auto_regroup) || p->enabled > 1 || p->check_every < 1 || p->check_every > 1024) return false;
+    if (!(std::isfinite(p->ratio) && p->ratio >= 1.0f)) return false;
+    for (uint32_t r : p->reserved)
+        if (r != 0) return false;
+    return true;
 }
 
 }  // namespace
@@ -249,9 +287,16 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
                     }
             std::sort(scratch.begin() + (long)L.pool, scratch.begin() + (long)(L.pool + pooled));
             std::copy(pref.begin(), pref.end(), scratch.begin() + (long)L.pref);
+            // the auto-regroup policy's state: baseline pending, counters 0 (the device's alone from here on)
+            mrt::RegroupState st0;
+            std::memset(&st0, 0, sizeof st0);
+            st0.pending = 1u;
+            std::memcpy(scratch.data() + L.state, &st0, sizeof st0);
         }
         MRT_TRY(upload((void**)&c->d_regroup, scratch.data(), scratch.size() * sizeof(uint32_t)));
         c->n_pool = hier.n_pool; c->n_pooled = pooled;
+        c->regroup_words = scratch.size();
+        c->auto_updates = 0;
         c->regroup_last[0] = c->regroup_last[1] = c->regroup_last[2] = 0;
     }
     // what shading a hit on sphere i reads, gathered per sphere (bit copies of the SoA entries)
@@ -342,7 +387,12 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
             return fail(c, MRT_ERR_BAD_SCENE, "mrt_update_spheres: sphere %zu: centre/radius not finite or |v| > 1e7", first + i / 4);
     if (count == 0) return MRT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    return change_scene(c, "mrt_update_spheres", [&]() -> int {
+    // The auto-regroup policy: every check_every-th call queues, behind the scatter, the judgement of the hierarchy and the regroup
+    // whose kernels the judgement's gate word lets run or return at once; the refit follows in any case, and the policy's
+    // reference figure is taken anew behind it where the gate opened.  The judgement reads the bounds of the PREVIOUS update's
+    // refit -- those the last frames were rendered with -- so no second, gated refit is needed.  The host never learns the verdict.
+    const bool check = c->auto_regroup.enabled && c->n_pool > 1 && (c->auto_updates + 1) % c->auto_regroup.check_every == 0;
+    const int st = change_scene(c, "mrt_update_spheres", [&]() -> int {
         c->guides_stale = true;
         const bool boxed = !mrt::scene_is_small(c->n_members);
         double reach = c->mfma_reach;
@@ -373,8 +423,12 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
         }
         c->mfma_reach = reach;
         c->box_kc = kc;
-        return 0;
-    });
+        if (!check) return 0;
+        const int le = mrt::launch_regroup_quality(quality_args(c, mrt::kQualityDecide, false), c->stream);
+        return le ? le : mrt::launch_regroup(regroup_args(c, true), c->stream);
+    }, check ? kIfPending : kNone);
+    if (st == MRT_OK && c->auto_regroup.enabled && c->n_pool > 1) c->auto_updates++;
+    return st;
 }
 
 // The grouping made anew from the spheres as the device holds them (include/myraytracer_amd.h): regroup.hip permutes the pooled
@@ -385,13 +439,51 @@ int mrt_regroup_spheres(mrt_ctx* c) {
     if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_regroup_spheres: no scene");
     if (c->n_pool <= 1) return MRT_OK;                  // no clustering, or nothing to trade between clusters
     HIP_TRY(c, hipSetDevice(c->device));
-    return change_scene(c, "mrt_regroup_spheres", [&]() -> int {          // (the guides stay current: the geometry did not change)
-        mrt::RegroupArgs g;
-        g.spheres = c->d_spheres; g.member_index = c->d_member_index; g.scratch = c->d_regroup;
-        g.n_pool = c->n_pool; g.pooled = c->n_pooled; g.block = c->regroup_block ? c->regroup_block : mrt::kRegroupBlock;
-        mrt::regroup_plan(g.n_pool, g.block, c->regroup_last);
-        return mrt::launch_regroup(g, c->stream);
-    });
+    // (the guides stay current: the geometry did not change; with the auto-regroup policy on, its reference figure is this grouping's)
+    return change_scene(c, "mrt_regroup_spheres", [&]() -> int { return mrt::launch_regroup(regroup_args(c, false), c->stream); },
+                        c->auto_regroup.enabled ? kMark : kNone);
+}
+
+void mrt_auto_regroup_default(mrt_auto_regroup* out) {
+    if (out) *out = mrt::auto_regroup_defaults();
+}
+
+int mrt_set_auto_regroup(mrt_ctx* c, const mrt_auto_regroup* p) {
+    if (!p) return MRT_ERR_INVALID_ARG;
+    if (!auto_regroup_ok(p))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_auto_regroup: size %u (%zu), enabled %u (0, 1), check_every %u (1..1024), "
+                    "ratio %g (finite, >= 1), reserved 0", p->size, sizeof(mrt_auto_regroup), p->enabled, p->check_every, (double)p->ratio);
+    if (!c) return MRT_OK;              // (ctx NULL: a check of the setting alone)
+    // turned on with a scene present: the reference figure is the hierarchy's as it is now, taken in stream order
+    if (p->enabled && !c->auto_regroup.enabled && c->have_world && c->n_pool > 1) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        const int le = mrt::launch_regroup_quality(quality_args(c, mrt::kQualityBaseline, true), c->stream);
+        if (le) { c->have_world = false; return fail(c, MRT_ERR_HIP, "mrt_set_auto_regroup: launch failed: %s", hipGetErrorString((hipError_t)le)); }
+    }
+    c->auto_regroup = *p;
+    c->auto_updates = 0;
+    return MRT_OK;
+}
+
+int mrt_get_auto_regroup(mrt_ctx* c, mrt_auto_regroup* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = c->auto_regroup;
+    return MRT_OK;
+}
+
+int mrt_read_regroup_stats(mrt_ctx* c, mrt_regroup_stats* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_read_regroup_stats: no scene");
+    std::memset(out, 0, sizeof *out);
+    if (c->n_pool <= 1) return MRT_OK;                  // no pool to regroup: the policy never checks
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_read_regroup_stats"));
+    mrt::RegroupState s;
+    HIP_TRY(c, hipMemcpy(&s, regroup_state(c), sizeof s, hipMemcpyDeviceToHost));
+    out->checks = s.checks; out->regroups = s.regroups; out->q_ref = s.q_ref; out->q_last = s.q_last;
+    for (uint32_t k = 0; k < mrt::kMaxLevels; k++) out->q_level[k] = s.q_level[k];
+    out->levels = c->levels; out->pending = s.pending;
+    return MRT_OK;
 }
 
 int mrt_debug_regroup_info(mrt_ctx* c, uint32_t out[4]) {

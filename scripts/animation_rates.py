@@ -21,7 +21,14 @@
    --response (with or without --temporal) prints that section with a third way, the temporal response on (mrt_set_temporal_response,
    DESIGN.md 7h: the reprojection with the fast history, then the clamp), and the ways alternate over `--rounds` rounds in the one
    process: the response's cost is its step's device time against the response-off step's of the same round, and the difference
-   between the rounds is the spread to read it against."""
+   between the rounds is the spread to read it against.
+   --auto-regroup prints the section "auto-regroup" instead (mrt_set_auto_regroup): the animated C5 with the library
+   deciding when to regroup.  With --ratio and / or --check-every: a regroup every N steps (--regroup-every, default 50) against
+   the policy with those numbers, one run each, with the policy's statistics at the end.  With neither, the measurement the
+   defaults come from, in one process: (1) the cost of a check that does not fire -- the policy at ratio 1e6, check_every 1
+   against the policy off, as step time and as the device time of the update call between HIP events -- and from it the
+   smallest power-of-two check_every that keeps the cost under 1 % of the every-N step; (2) ratios 1.5, 2, 3, 4 at that
+   check_every, of which the largest within --spread steps/s of the fastest is taken; (3) the slow walk (0.2 x --walk) every N against the policy; (4) the C3 walk with the policy off and on."""
 import argparse
 import os
 import sys
@@ -42,25 +49,31 @@ ap.add_argument("--regroup-every", type=int, default=0)
 ap.add_argument("--temporal", action="store_true")
 ap.add_argument("--response", action="store_true")
 ap.add_argument("--rounds", type=int, default=2)
+ap.add_argument("--auto-regroup", action="store_true")
+ap.add_argument("--ratio", type=float, default=None)
+ap.add_argument("--check-every", type=int, default=None)
+ap.add_argument("--spread", type=float, default=0.0, help="steps/s within which two ratios tie (the larger is taken)")
 a = ap.parse_args()
 W, H = a.size
 
 
-def walk(spheres, steps, rng):
+def walk(spheres, steps, rng, amount=None):
     """the scene's (n, 4) centre + radius per step: every sphere but the last (the ground) on a random walk"""
     xyzr = np.concatenate([spheres["center"].reshape(-1, 3), spheres["radius"].reshape(-1, 1)], axis=1).astype(np.float32)
     size = float(np.ptp(xyzr[:-1, :3], axis=0).max())
+    amount = a.walk if amount is None else amount
     out = []
     for _ in range(steps):
         xyzr = xyzr.copy()
-        xyzr[:-1, :3] += (rng.normal(size=(len(xyzr) - 1, 3)) * a.walk * size).astype(np.float32)
+        xyzr[:-1, :3] += (rng.normal(size=(len(xyzr) - 1, 3)) * amount * size).astype(np.float32)
         out.append(xyzr)
     return out
 
 
-def run(name, spheres, cam, way, path, every=0):
+def run(name, spheres, cam, way, path, every=0, auto=None):
     """way: set_world | update | regroup (update, and mrt_regroup_spheres every `every` steps) | rebuild (update, but mrt_set_world
-    every `every` steps); with `every` the member tests are reported for each quarter of the run"""
+    every `every` steps) | auto (update with mrt_set_auto_regroup(**auto) on); with `every` the member tests are reported for each
+    quarter of the run.  run.last: the update call's median device time and the policy's statistics of the run"""
     stream = torch.cuda.Stream()
     quarter = max(1, len(path) // 4)
     bounds = (quarter, 2 * quarter, 3 * quarter) if every else (quarter, len(path) - quarter)
@@ -69,6 +82,8 @@ def run(name, spheres, cam, way, path, every=0):
         st.set_camera(cam)
         st.render(8)
         st.sync()
+        if way == "auto":
+            st.set_auto_regroup(True, **auto)
         sc = spheres.copy()
         host, pairs, early, marks = [], [], 0, []
         behind_frame = None
@@ -104,14 +119,18 @@ def run(name, spheres, cam, way, path, every=0):
         sec = time.perf_counter() - t0
         marks.append(st.read_counters())
         sch = st.get_schedule()
+        stats = st.read_regroup_stats() if way == "auto" else None
 
     def tests_per_hit(c0, c1):
         return (c1["member_tests"] - c0["member_tests"]) / max(1, c1["world_hit_calls"] - c0["world_hit_calls"])
     host = np.array(host) * 1e3
-    line = (f"  {name} {way:9s} {len(path) / sec:8.1f} steps/s  call on the host: median {np.median(host):8.3f} ms, mean {host.mean():8.3f}, "
+    label = way if way != "auto" else f"auto r{auto['ratio']:g}/{auto['check_every']}"
+    run.last = dict(dev=None, stats=stats)
+    line = (f"  {name} {label:9s} {len(path) / sec:8.1f} steps/s  call on the host: median {np.median(host):8.3f} ms, mean {host.mean():8.3f}, "
             f"max {host.max():8.3f}")
     if pairs:
         dev = np.array([p[0].elapsed_time(p[1]) for p in pairs])
+        run.last["dev"] = float(np.median(dev))
         line += f"  refit on the device (events): median {np.median(dev):.4f} ms, max {dev.max():.4f}"
     line += f"  returned before the previous frame had ended: {early} of {len(path) - 1} calls"
     if every:
@@ -119,6 +138,9 @@ def run(name, spheres, cam, way, path, every=0):
     else:
         line += f"  member tests / world_hit: first quarter {tests_per_hit(marks[0], marks[1]):.2f}, last quarter {tests_per_hit(marks[2], marks[3]):.2f}"
     line += (f"  schedule at the end: div {sch['div']} x {sch['mult']}, settled {sch['settled']}")
+    if stats:
+        line += (f"  policy: {stats['checks']} checks, {stats['regroups']} regroups, Q_ref {stats['q_ref']:.6g}, Q last {stats['q_last']:.6g}"
+                 f" (by level {', '.join(f'{v:.6g}' for v in stats['q_level'])})")
     print(line, flush=True)
     return len(path) / sec
 
@@ -250,6 +272,50 @@ if a.temporal or a.response:
           f"step), one frame a step; build {M._lib.load().mrt_build_id().decode()}", flush=True)
     for name, (spheres, cam) in (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100))):
         temporal_cost(name, spheres, cam, walk(spheres, a.steps, np.random.default_rng(1)), a.response, a.rounds if a.response else 1)
+    sys.exit(0)
+
+if a.auto_regroup:
+    N = a.regroup_every or 50
+    scenes = (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100)))
+    name, (spheres, cam) = scenes[1]
+    path = walk(spheres, a.steps, np.random.default_rng(1))
+    d = M._lib.MrtAutoRegroup()
+    M._lib.load().mrt_auto_regroup_default(d)
+    print(f"auto-regroup: {W}x{H} x 1 spp, depth {a.depth}; {a.steps} steps of the walk of {a.walk} x the scene's size a step, one frame a step; "
+          f"library defaults ratio {d.ratio:g}, check_every {d.check_every}; build {M._lib.load().mrt_build_id().decode()}", flush=True)
+    if a.ratio is not None or a.check_every is not None:
+        cfg = dict(ratio=d.ratio if a.ratio is None else a.ratio, check_every=d.check_every if a.check_every is None else a.check_every)
+        run(name, spheres, cam, "regroup", path, every=N)
+        run(name, spheres, cam, "auto", path, every=N, auto=cfg)
+        sys.exit(0)
+    print(f"(1) {name}: a regroup every {N} steps; the policy off; the policy at ratio 1e6, check_every 1 (every update checks, none fires)", flush=True)
+    every_n = run(name, spheres, cam, "regroup", path, every=N)
+    off = run(name, spheres, cam, "update", path, every=N)
+    off_dev = run.last["dev"]
+    on = run(name, spheres, cam, "auto", path, every=N, auto=dict(ratio=1e6, check_every=1))
+    on_dev = run.last["dev"]
+    cost_step, cost_dev, budget = (1.0 / on - 1.0 / off) * 1e3, on_dev - off_dev, 0.01 * 1e3 / every_n
+    cost = max(cost_step, cost_dev, 0.0)
+    k = 1
+    while cost / k >= budget and k < 1024:
+        k *= 2
+    print(f"  a check that does not fire costs {cost_step:+.4f} ms of step time ({1e3 / off:.3f} -> {1e3 / on:.3f} ms a step), {cost_dev:+.4f} ms of the update's "
+          f"device time (median {off_dev:.4f} -> {on_dev:.4f} ms); 1 % of the every-{N} step ({1e3 / every_n:.3f} ms) is {budget:.4f} ms: "
+          f"the larger of the two costs, {cost:.4f} ms, stays under it from check_every {k}", flush=True)
+    print(f"(2) {name}: ratios at check_every {k}", flush=True)
+    rates = {r: run(name, spheres, cam, "auto", path, every=N, auto=dict(ratio=r, check_every=k)) for r in (1.5, 2.0, 3.0, 4.0)}
+    print("  steps/s by ratio: " + ", ".join(f"{r:g}: {v:.1f}" for r, v in rates.items()) + f"; every {N}: {every_n:.1f}", flush=True)
+    best = max(r for r in rates if rates[r] >= max(rates.values()) - a.spread)
+    print(f"  the largest ratio within {a.spread:.1f} steps/s of the fastest: {best:g}", flush=True)
+    slow = walk(spheres, a.steps, np.random.default_rng(1), 0.2 * a.walk)
+    print(f"(3) {name}: the slow walk ({0.2 * a.walk:g} x the scene's size a step): every {N} against the policy at ratio {best:g}, check_every {k}", flush=True)
+    run(name, spheres, cam, "regroup", slow, every=N)
+    run(name, spheres, cam, "auto", slow, every=N, auto=dict(ratio=best, check_every=k))
+    name, (spheres, cam) = scenes[0]
+    path = walk(spheres, a.steps, np.random.default_rng(1))
+    print(f"(4) {name} (a single block kernel): the policy off and on (ratio {best:g}, check_every {k})", flush=True)
+    run(name, spheres, cam, "update", path, every=N)
+    run(name, spheres, cam, "auto", path, every=N, auto=dict(ratio=best, check_every=k))
     sys.exit(0)
 
 if a.regroup_every:
