@@ -46,7 +46,8 @@ extern "C" {
  * mrt_set_temporal_response, mrt_get_temporal_response); the noise estimate across shards and the gathered frame's denoise
  * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED); the denoise of
  * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive); the auto-regroup policy (mrt_auto_regroup,
- * mrt_auto_regroup_default, mrt_set_auto_regroup, mrt_get_auto_regroup, mrt_regroup_stats, mrt_read_regroup_stats). */
+ * mrt_auto_regroup_default, mrt_set_auto_regroup, mrt_get_auto_regroup, mrt_regroup_stats, mrt_read_regroup_stats); the
+ * denoiser's blend with the accumulation (mrt_denoise_mix, mrt_denoise_mix_default, mrt_set_denoise_mix, mrt_get_denoise_mix). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -608,7 +609,33 @@ int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tile
  *   the edge stops alone, as far as the taps reach (in SPATIAL_EARLY it is in its spatial phase and has a stop: its estimate is 0
  *   over a black tile, so its interior passes through until its border has been filled).  When every n_t equals n, the image is bit for bit the uniform filter's for n frames in the same mode.
  *   The first such denoise, and the first after a tile has passed the K table's length, may wait once (bounded) for the ctx's
- *   stream while the device's table of K(n) is made (the table of the per-tile noise report; nothing else is created). */
+ *   stream while the device's table of K(n) is made (the table of the per-tile noise report; nothing else is created).
+ *
+ * Blend with the accumulation (mrt_set_denoise_mix; off by default, and then every launch and bit is what it is without it).  The
+ * filter trades noise for bias, and the accumulation's noise falls with the frame count while the filter's bias does not: from
+ * some count on -- scene dependent -- the accumulated image is the better one.  With the setting on, one more pass behind the last
+ * iteration mixes the two per pixel by how much of their difference the noise estimate explains (a local Wiener shrinkage): where
+ * the noise dominates the result is the filter, where the filter's bias dominates it is the accumulation.  Float32 in this order;
+ * only + - * /, fminf, fmaxf and comparisons.  Per pixel p:
+ *     c_p          the input frame's texel (the framebuffer, or the gathered frame)
+ *     (f_p, u_p)   the colour and the propagated variance of the last iteration, before alpha replaces the variance
+ *     v_p        = S_p * (float)K, the accumulated estimate in every variance mode; an adaptive accumulation: S_p * K_p
+ *     d_p        = L(f_p) - L(c_p)
+ *     n_p        = fmaxf(v_p - u_p, 0.0f)
+ *     valid_p    = r, g, b of c_p, S_p, r, g, b of f_p and u_p are all finite (an adaptive accumulation: and K_p is finite)
+ *   n_p is the noise variance of f - c: an averaging filter contains its own centre, so Var(f - c) = v - u, not v + u.  Window:
+ *   the 5 x 5 pixels q around p, dy then dx from -2 to 2, the centre included; q counts if it lies inside the image, valid_q holds
+ *   and the guides' sphere-index bits of q equal those of p.  In tap order, from 0: e += d_q * d_q, m += n_q.
+ *     a          = e > 0.0f ? fminf(m / (gain * e), 1.0f) : 0.0f
+ *     out.rgb    = c_p + a * (f_p - c_p)        (per channel);   out.a = the frame's alpha
+ *   A pixel that is not valid gets out.rgb = f_p (the filter has passed it through, or it has no v).  Where K = +inf (fewer than 2
+ *   frames) there is no v: the image is the filter's, and for a uniform accumulation the launches are exactly those without the
+ *   setting.  gain: the luminance stop picks neighbours that resemble the noisy centre, so f follows c's noise and d^2
+ *   underestimates the true difference; gain corrects that (default 1: the smallest worst case over profiles/denoise_mix_quality.txt).
+ *   It applies to every denoise of an accumulation -- mrt_read_denoised, MRT_PRESENT_DENOISED, mrt_read_gathered_denoised and
+ *   MRT_PRESENT_GATHERED_DENOISED (with the gather's snapshot of K), the per-tile filter -- and not to the temporal image, whose
+ *   history has no accumulated alternative: mrt_read_temporal and MRT_PRESENT_TEMPORAL stay bit for bit.  It needs no buffer, stream
+ *   or event of its own (the pass reads the filter's idle scratch), and every refusal of every denoise is what it is without it. */
 typedef struct {                 /* 48 bytes */
     uint32_t size;               /* sizeof(mrt_denoise_params): the version of this struct */
     uint32_t iterations;         /* 1 .. 8 (default 5: steps 1 .. 16) */
@@ -642,6 +669,20 @@ int mrt_get_denoise_variance(mrt_ctx* ctx, uint32_t* mode, uint32_t* spatial_fra
  * mrt_set_world* and mrt_set_camera) and takes effect at the next denoise.  ctx NULL, or enabled NULL: MRT_ERR_INVALID_ARG. */
 int mrt_set_denoise_adaptive(mrt_ctx* ctx, int enabled);
 int mrt_get_denoise_adaptive(mrt_ctx* ctx, int* enabled);
+/* The blend with the accumulation ("Blend with the accumulation" above). */
+typedef struct {
+    uint32_t size;               /* sizeof(mrt_denoise_mix): the version of this struct */
+    uint32_t enabled;            /* 0 (default) | 1 */
+    float gain;                  /* finite, 0.25 .. 16 (default 1: profiles/denoise_mix_quality.txt) */
+    uint32_t reserved[5];        /* 0 */
+} mrt_denoise_mix;               /* sizeof 32 */
+/* Host only: the defaults (enabled 0). */
+void mrt_denoise_mix_default(mrt_denoise_mix* out);
+/* Anything out of range, size or reserved wrong: MRT_ERR_INVALID_ARG with nothing changed.  ctx NULL: checks p only (host only).
+ * The setting creates nothing, takes effect at the next denoise and lives as long as the denoise parameters do (it survives
+ * mrt_reset, mrt_set_shard, mrt_set_world* and mrt_set_camera). */
+int mrt_set_denoise_mix(mrt_ctx* ctx, const mrt_denoise_mix* p);
+int mrt_get_denoise_mix(mrt_ctx* ctx, mrt_denoise_mix* out);
 /* Denoises the most recent frame (queued on the ctx's stream behind its blend) and reads it back: height * width * 4 floats,
  * row 0 = bottom, as mrt_read_framebuffer; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE with tracking off or on a
  * shard, or after divergence without mrt_set_denoise_adaptive; MRT_ERR_NO_SCENE without a scene. */

@@ -41,6 +41,10 @@ int mrt_debug_denoise(mrt_ctx* ctx, const float* rgba, const float* S, double K,
  * prefiltered, 2 prefiltered with the spatial initial variance (K is ignored); anything else: MRT_ERR_INVALID_ARG. */
 int mrt_debug_denoise_variance(mrt_ctx* ctx, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
                                uint32_t rows, const mrt_denoise_params* params, uint32_t variance, float* out);
+/* Diagnostic: mrt_debug_denoise_variance with the blend ("Blend with the accumulation"): mix as mrt_set_denoise_mix takes it (NULL
+ * or out of range: MRT_ERR_INVALID_ARG).  With mix->enabled, K is read in every variance, 2 included (v = S * K). */
+int mrt_debug_denoise_mix(mrt_ctx* ctx, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
+                          uint32_t rows, const mrt_denoise_params* params, uint32_t variance, const mrt_denoise_mix* mix, float* out);
 /* Diagnostic: the ctx's guides (rebuilt first if stale), height x width pixels, row 0 = bottom: rays 6 floats (origin,
  * direction), index 1 int32, t 1 float, normal 3 floats, albedo 3 floats per pixel; any pointer may be NULL.  cap_pixels >=
  * width * height.  Synchronous.  MRT_ERR_STATE on a shard, MRT_ERR_NO_SCENE without a scene. */

@@ -55,6 +55,7 @@ EXPORTS = [
     "mrt_set_gather_noise", "mrt_read_gathered_noise", "mrt_read_gathered_denoised", "mrt_debug_read_gathered_guides",
     "mrt_set_denoise_adaptive", "mrt_get_denoise_adaptive", "mrt_debug_load_accumulation",
     "mrt_auto_regroup_default", "mrt_set_auto_regroup", "mrt_get_auto_regroup", "mrt_read_regroup_stats",
+    "mrt_denoise_mix_default", "mrt_set_denoise_mix", "mrt_get_denoise_mix", "mrt_debug_denoise_mix",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -118,6 +119,10 @@ class MrtNoiseReport(C.Structure):
 class MrtDenoiseParams(C.Structure):
     _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_l", C.c_float), ("normal_exp", C.c_uint32),
                 ("sigma_z", C.c_float), ("sigma_a", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class MrtDenoiseMix(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("enabled", C.c_uint32), ("gain", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
 class MrtTemporalParams(C.Structure):
@@ -375,6 +380,10 @@ def load():
         "mrt_get_denoise_adaptive": (i32, [vp, P(C.c_int)]),
         "mrt_debug_load_accumulation": (i32, [vp, vp, vp, vp]),
         "mrt_debug_denoise_variance": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), u32, vp]),
+        "mrt_denoise_mix_default": (None, [P(MrtDenoiseMix)]),
+        "mrt_set_denoise_mix": (i32, [vp, P(MrtDenoiseMix)]),
+        "mrt_get_denoise_mix": (i32, [vp, P(MrtDenoiseMix)]),
+        "mrt_debug_denoise_mix": (i32, [vp, vp, vp, C.c_double, vp, u32, u32, P(MrtDenoiseParams), u32, P(MrtDenoiseMix), vp]),
         "mrt_debug_read_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
         "mrt_render_tiles": (i32, [vp, vp, sz, u32]),
         "mrt_render_adaptive": (i32, [vp, u32, C.c_uint64, P(C.c_uint64), P(u32)]),

@@ -901,6 +901,22 @@ class State:
         self._check(self._L.mrt_get_denoise_adaptive(self._ctx, C.byref(on)), "mrt_get_denoise_adaptive")
         return bool(on.value)
 
+    def set_denoise_mix(self, enabled: bool, gain: Optional[float] = None):
+        """The blend of the filtered with the accumulated image behind every denoise of an accumulation (off by default); gain
+        None keeps the State's (0.25 .. 16; the default is denoise_mix_default()'s)."""
+        p = _lib.MrtDenoiseMix()
+        self._check(self._L.mrt_get_denoise_mix(self._ctx, C.byref(p)), "mrt_get_denoise_mix")
+        p.enabled = int(bool(enabled))
+        if gain is not None:
+            p.gain = gain
+        self._check(self._L.mrt_set_denoise_mix(self._ctx, C.byref(p)), "mrt_set_denoise_mix")
+
+    def denoise_mix(self) -> Tuple[bool, float]:
+        """(enabled, gain) as set_denoise_mix left them."""
+        p = _lib.MrtDenoiseMix()
+        self._check(self._L.mrt_get_denoise_mix(self._ctx, C.byref(p)), "mrt_get_denoise_mix")
+        return bool(p.enabled), float(p.gain)
+
     def debug_load_accumulation(self, rgba=None, S=None, tile_frames=None):
         """Overwrite what read_framebuffer (rgba (H, W, 4) f32), read_noise (S (H, W) f32) and tile_frames (one u32 per tile;
         makes the accumulation adaptive) read; None leaves a part as it is.  World 1 only."""
@@ -954,6 +970,30 @@ class State:
         else:
             self._check(self._L.mrt_debug_denoise_variance(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows,
                                                            C.byref(p), variance, out.ctypes.data), "mrt_debug_denoise_variance")
+        return out
+
+    def debug_denoise_mix(self, rgba: np.ndarray, S: np.ndarray, K: float, guides: dict, params: Optional[dict] = None,
+                          variance: int = 0, enabled: bool = True, gain: Optional[float] = None) -> np.ndarray:
+        """debug_denoise with the blend (mrt_debug_denoise_mix): gain None is the default's; with the blend on K is read in
+        every variance."""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        S = np.ascontiguousarray(S, np.float32)
+        rows, width = S.shape
+        assert rgba.shape == (rows, width, 4)
+        g = pack_guides(guides)
+        assert g.shape == (rows, width, 8)
+        p = _lib.MrtDenoiseParams()
+        self._check(self._L.mrt_get_denoise_params(self._ctx, C.byref(p)), "mrt_get_denoise_params")
+        for k, v in (params or {}).items():
+            setattr(p, k, v)
+        m = _lib.MrtDenoiseMix()
+        self._L.mrt_denoise_mix_default(C.byref(m))
+        m.enabled = int(bool(enabled))
+        if gain is not None:
+            m.gain = gain
+        out = np.empty_like(rgba)
+        self._check(self._L.mrt_debug_denoise_mix(self._ctx, rgba.ctypes.data, S.ctypes.data, K, g.ctypes.data, width, rows, C.byref(p),
+                                                  variance, C.byref(m), out.ctypes.data), "mrt_debug_denoise_mix")
         return out
 
     # -- temporal reprojection (include/myraytracer_amd.h, "temporal reprojection"): a per-pixel history that follows the spheres'
@@ -1069,6 +1109,13 @@ def denoise_params_default() -> dict:
     p = _lib.MrtDenoiseParams()
     _lib.load().mrt_denoise_params_default(C.byref(p))
     return denoise_params_dict(p)
+
+
+def denoise_mix_default() -> dict:
+    """mrt_denoise_mix_default as a dict (host only; enabled is 0)."""
+    p = _lib.MrtDenoiseMix()
+    _lib.load().mrt_denoise_mix_default(C.byref(p))
+    return {"enabled": int(p.enabled), "gain": float(p.gain)}
 
 
 def pack_guides(guides: dict) -> np.ndarray:

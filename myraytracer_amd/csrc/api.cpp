@@ -870,6 +870,8 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
         return check_finding(why, cap, "temporal response enabled %u, size %u", c->temporal_response.enabled, c->temporal_response.size);
     if (c->auto_regroup.enabled > 1 || c->auto_regroup.size != sizeof(mrt_auto_regroup) || c->auto_regroup.check_every < 1 || c->auto_regroup.check_every > 1024)
         return check_finding(why, cap, "auto regroup enabled %u, size %u, check_every %u", c->auto_regroup.enabled, c->auto_regroup.size, c->auto_regroup.check_every);
+    if (c->denoise_mix.enabled > 1 || c->denoise_mix.size != sizeof(mrt_denoise_mix) || !(c->denoise_mix.gain >= 0.25f && c->denoise_mix.gain <= 16.0f))
+        return check_finding(why, cap, "denoise mix enabled %u, size %u, gain %g", c->denoise_mix.enabled, c->denoise_mix.size, c->denoise_mix.gain);
     if (c->d_guide_cand == nullptr ? c->guide_cand_words != 0 : c->guide_cand_words == 0) return check_finding(why, cap, "guide bitmap %p of %zu words", (void*)c->d_guide_cand, c->guide_cand_words);
     if (c->tiles_diverged) {
         if (c->n_tiles && !c->d_tile_frames) return check_finding(why, cap, "the accumulation has diverged without the tile frame counts");

@@ -41,6 +41,14 @@ bool denoise_params_ok(const mrt_denoise_params* p) {
     return true;
 }
 
+bool denoise_mix_ok(const mrt_denoise_mix* p) {
+    if (p->size != sizeof(mrt_denoise_mix) || p->enabled > 1) return false;
+    if (!(std::isfinite(p->gain) && p->gain >= 0.25f && p->gain <= 16.0f)) return false;
+    for (uint32_t r : p->reserved)
+        if (r != 0) return false;
+    return true;
+}
+
 int ensure_denoise_buffers(mrt_ctx* c) {
     const size_t n = (size_t)c->args.width * c->args.height;
     // the filter's three buffers; with temporal reprojection on -- and only then -- the history's four behind them, and with its
@@ -139,6 +147,7 @@ mrt::DenoiseJob denoise_job(const mrt_ctx* c, const float* fb, mrt::DenoiseSourc
     j.width = c->args.width; j.height = c->args.height;
     j.prm = c->denoise;
     j.source = source;
+    j.mix = c->denoise_mix;         // (launch_denoise reads it for an accumulation alone)
     return j;
 }
 
@@ -278,6 +287,46 @@ int queue_temporal_image(mrt_ctx* c) {
     return MRT_OK;
 }
 
+// mrt_debug_denoise_variance and mrt_debug_denoise_mix: a uniform accumulation given by the caller, filtered in buffers of its
+// own; `mix` NULL: no blend.  With a blend on, K is read in every variance (v = S * K), the spatial one included.
+int debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width, uint32_t rows,
+                  const mrt_denoise_params* params, uint32_t variance, const mrt_denoise_mix* mix, float* out) {
+    if (!c || !rgba || !S || !guides || !out || !width || !rows || (uint64_t)width * rows > (1ull << 26) || variance > 2)
+        return MRT_ERR_INVALID_ARG;
+    if (variance == 2 && !(mix && mix->enabled)) K = 0.0;       // (the spatial initial variance: K is not read)
+    if (std::isnan(K) || K < 0.0) return MRT_ERR_INVALID_ARG;
+    const mrt_denoise_params prm = params ? *params : c->denoise;
+    if (!denoise_params_ok(&prm)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_denoise: bad parameters");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * rows;
+    float *d_fb = nullptr, *d_s = nullptr, *d_g = nullptr, *d_b[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_denoise";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_fb, n * 16));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_s, n * sizeof(float)));
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_g, n * 32));
+    for (auto& b : d_b) HIP_CHAIN(e, what, hipMalloc((void**)&b, n * 16));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
+    mrt::DenoiseJob job{};
+    job.fb = d_fb; job.S = d_s; job.guides = d_g;
+    job.ping = d_b[0]; job.pong = d_b[1]; job.out = d_b[2];
+    job.width = width; job.height = rows;
+    job.prm = prm;
+    job.source = mrt::DenoiseSource::Uniform;
+    job.uniform = {(float)K, (mrt::UniformVariance)variance};
+    if (mix) job.mix = *mix;
+    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(job, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_b[2], n * 16, hipMemcpyDeviceToHost, c->stream);
+    int ws = MRT_OK;
+    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");
+    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
+    mrt::free_device(d_fb, d_s, d_g, d_b[0], d_b[1], d_b[2]);
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    return MRT_OK;
+}
+
 }  // namespace
 
 namespace mrt {
@@ -337,6 +386,25 @@ int mrt_get_denoise_variance(mrt_ctx* c, uint32_t* mode, uint32_t* spatial_frame
     if (!c) return MRT_ERR_INVALID_ARG;
     if (mode) *mode = c->denoise_var_mode;
     if (spatial_frames) *spatial_frames = c->denoise_spatial_frames;
+    return MRT_OK;
+}
+
+void mrt_denoise_mix_default(mrt_denoise_mix* out) {
+    if (out) *out = mrt::denoise_mix_defaults();
+}
+
+int mrt_set_denoise_mix(mrt_ctx* c, const mrt_denoise_mix* p) {
+    if (!p) return MRT_ERR_INVALID_ARG;
+    if (!denoise_mix_ok(p))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_denoise_mix: size %u (%zu), enabled %u (0, 1), gain %g (finite, 0.25..16), "
+                    "reserved 0", p->size, sizeof(mrt_denoise_mix), p->enabled, p->gain);
+    if (c) c->denoise_mix = *p;           // (ctx NULL: a check of the setting alone)
+    return MRT_OK;
+}
+
+int mrt_get_denoise_mix(mrt_ctx* c, mrt_denoise_mix* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = c->denoise_mix;
     return MRT_OK;
 }
 
@@ -568,39 +636,14 @@ int mrt_debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, c
 
 int mrt_debug_denoise_variance(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
                                uint32_t rows, const mrt_denoise_params* params, uint32_t variance, float* out) {
-    if (!c || !rgba || !S || !guides || !out || !width || !rows || (uint64_t)width * rows > (1ull << 26) || variance > 2)
-        return MRT_ERR_INVALID_ARG;
-    if (variance == 2) K = 0.0;             // (the spatial initial variance: K is not read)
-    if (std::isnan(K) || K < 0.0) return MRT_ERR_INVALID_ARG;
-    const mrt_denoise_params prm = params ? *params : c->denoise;
-    if (!denoise_params_ok(&prm)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_denoise: bad parameters");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n = (size_t)width * rows;
-    float *d_fb = nullptr, *d_s = nullptr, *d_g = nullptr, *d_b[3] = {nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    const char* what = "mrt_debug_denoise";
-    HIP_CHAIN(e, what, hipMalloc((void**)&d_fb, n * 16));
-    HIP_CHAIN(e, what, hipMalloc((void**)&d_s, n * sizeof(float)));
-    HIP_CHAIN(e, what, hipMalloc((void**)&d_g, n * 32));
-    for (auto& b : d_b) HIP_CHAIN(e, what, hipMalloc((void**)&b, n * 16));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_fb, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_g, guides, n * 32, hipMemcpyHostToDevice, c->stream);
-    mrt::DenoiseJob job{};
-    job.fb = d_fb; job.S = d_s; job.guides = d_g;
-    job.ping = d_b[0]; job.pong = d_b[1]; job.out = d_b[2];
-    job.width = width; job.height = rows;
-    job.prm = prm;
-    job.source = mrt::DenoiseSource::Uniform;
-    job.uniform = {(float)K, (mrt::UniformVariance)variance};
-    if (e == hipSuccess) e = (hipError_t)mrt::launch_denoise(job, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_b[2], n * 16, hipMemcpyDeviceToHost, c->stream);
-    int ws = MRT_OK;
-    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_denoise");
-    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
-    mrt::free_device(d_fb, d_s, d_g, d_b[0], d_b[1], d_b[2]);
-    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-    return MRT_OK;
+    return debug_denoise(c, rgba, S, K, guides, width, rows, params, variance, nullptr, out);
+}
+
+int mrt_debug_denoise_mix(mrt_ctx* c, const float* rgba, const float* S, double K, const float* guides, uint32_t width,
+                          uint32_t rows, const mrt_denoise_params* params, uint32_t variance, const mrt_denoise_mix* mix, float* out) {
+    if (!c || !mix) return MRT_ERR_INVALID_ARG;
+    if (!denoise_mix_ok(mix)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_denoise_mix: bad setting");
+    return debug_denoise(c, rgba, S, K, guides, width, rows, params, variance, mix, out);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@
 // Estimate: spatial_estimate is the 7 x 7 weighted luminance variance of one pixel, for a field that has none of its own yet.
 // Its entry points make the field iteration 0 reads: spatial_variance_kernel (a short uniform history), tile_variance_kernel (per
 // tile) and temporal_variance_kernel (the short histories of the temporal image).
+// Blend (mrt_set_denoise_mix): mix_kernel, one launch behind the iterations of an accumulation, mixes the filtered with the
+// accumulated image per pixel from 5 x 5 records held in LDS.
 // Only + - * /, sqrtf, fminf, fmaxf in a fixed order (-ffp-contract=off; hipcc's `/` and sqrtf are correctly rounded), so
 // tests/denoise_ref.py and its siblings restate all of it bit for bit in float32 numpy.
 #include <hip/hip_runtime.h>
@@ -373,6 +375,72 @@ __global__ void __launch_bounds__(kTileX * kTileY) atrous_tiles_kernel(const Atr
     atrous_pixel<false, PF, LAST>(A, x, y, tile_pixel(T, x, y).stop);
 }
 
+// ---- the blend of the filtered and the accumulated image (include/myraytracer_amd.h, "Blend with the accumulation") -----------
+// One launch behind the last iteration, which has then run as a non-LAST one: f = (colour, propagated variance u) of that
+// iteration, c and S the frame's.  A workgroup first makes the record (d^2, n, index bits, valid) of its 32 x 8 pixels and a
+// 2-pixel halo -- 36 x 12 records, 6912 bytes of LDS, at most two a thread -- then every pixel sums the 25 records around it from
+// LDS and blends.  The halo costs 1.7 x the records' loads (52 bytes a pixel: f, c, S, half a guide), most of them cache hits of
+// the neighbouring workgroups'; 25 direct taps would load those 52 bytes 25 times, and a records pass of its own would write and
+// read 16 more bytes a pixel through memory and add a launch.  TILES: K per pixel from its tile (T), +inf making it not valid.
+struct MixArgs {
+    const float4* fb;            // the frame: c, alpha
+    const float* S;
+    const float4* f;             // the last iteration's (r, g, b, var)
+    const float4* guides;
+    float4* out;
+    uint32_t width, height;
+    float K, gain;               // K: not TILES; finite
+};
+constexpr int kMixR = 2, kMixW = (int)kTileX + 2 * kMixR, kMixH = (int)kTileY + 2 * kMixR;
+
+template <bool TILES>
+__global__ void __launch_bounds__(kTileX * kTileY) mix_kernel(const MixArgs A, const TileField T) {
+    __shared__ float4 rec[kMixW * kMixH];
+    const int x0 = (int)(blockIdx.x * kTileX) - kMixR, y0 = (int)(blockIdx.y * kTileY) - kMixR;
+    for (int s = (int)(threadIdx.y * kTileX + threadIdx.x); s < kMixW * kMixH; s += (int)(kTileX * kTileY)) {
+        const int xq = x0 + s % kMixW, yq = y0 + s / kMixW;
+        float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);         // (w = 0: the tap does not count)
+        if (xq >= 0 && xq < (int)A.width && yq >= 0 && yq < (int)A.height) {
+            const size_t q = (size_t)yq * A.width + (uint32_t)xq;
+            const float4 cq = A.fb[q], fq = A.f[q];
+            const float sq = A.S[q];
+            const float K = TILES ? tile_pixel(T, (uint32_t)xq, (uint32_t)yq).K : A.K;
+            if (finite3(cq) && __builtin_isfinite(sq) && finite4(fq) && !(TILES && __builtin_isinf(K))) {
+                const float d = lumf(fq.x, fq.y, fq.z) - lumf(cq.x, cq.y, cq.z);
+                r = make_float4(d * d, fmaxf(sq * K - fq.w, 0.0f), A.guides[2u * q + 1u].w, 1.0f);
+            }
+        }
+        rec[s] = r;
+    }
+    __syncthreads();
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const size_t i = (size_t)y * A.width + x;
+    const int at = ((int)threadIdx.y + kMixR) * kMixW + (int)threadIdx.x + kMixR;
+    const float4 rp = rec[at], cp = A.fb[i];
+    float4 res = A.f[i];                                        // not valid: the filter's own colour
+    if (rp.w != 0.0f) {
+        float e = 0.0f, m = 0.0f;
+#pragma unroll
+        for (int dy = -kMixR; dy <= kMixR; dy++) {
+#pragma unroll
+            for (int dx = -kMixR; dx <= kMixR; dx++) {
+                const float4 rq = rec[at + dy * kMixW + dx];
+                if (rq.w != 0.0f && __float_as_int(rq.z) == __float_as_int(rp.z)) {
+                    e = e + rq.x;
+                    m = m + rq.y;
+                }
+            }
+        }
+        const float a = e > 0.0f ? fminf(m / (A.gain * e), 1.0f) : 0.0f;
+        res.x = cp.x + a * (res.x - cp.x);
+        res.y = cp.y + a * (res.y - cp.y);
+        res.z = cp.z + a * (res.z - cp.z);
+    }
+    res.w = cp.w;
+    A.out[i] = res;
+}
+
 // f(std::bool_constant<a>, std::bool_constant<b>): two run-time flags as the template arguments of a launch
 template <class F>
 void with_flags(bool a, bool b, F f) {
@@ -452,8 +520,11 @@ int launch_denoise(const DenoiseJob& job, void* stream) {
     default:
         return (int)hipErrorInvalidValue;
     }
+    // The blend (job.mix) follows an accumulation's iterations wherever a K is finite: uniformly, or per pixel in the kernel.
+    const bool mix = job.mix.enabled && (job.source == DenoiseSource::Tiles ||
+                                         (job.source == DenoiseSource::Uniform && !__builtin_isinf(job.uniform.K)));
     for (uint32_t it = 0; it < n; it++) {
-        const bool first = it == 0 && !field, last = it + 1 == n;
+        const bool first = it == 0 && !field, last = it + 1 == n && !mix;     // (with the blend no iteration is the LAST one)
         A.step = 1u << it;
         A.in = first ? nullptr : buf[(it + 1) & 1u];
         A.out = last ? reinterpret_cast<float4*>(job.out) : buf[it & 1u];
@@ -466,6 +537,15 @@ int launch_denoise(const DenoiseJob& job, void* stream) {
                 if (prefilter) hipLaunchKernelGGL((atrous_prefilter_kernel<decltype(FIRST)::value, decltype(LAST)::value>), grid, block, 0, st, A);
                 else hipLaunchKernelGGL((atrous_kernel<decltype(FIRST)::value, decltype(LAST)::value>), grid, block, 0, st, A);
             });
+    }
+    if (mix) {                                  // f: where the last iteration wrote as a non-last one
+        MixArgs M;
+        M.fb = A.fb; M.S = A.S; M.f = buf[(n - 1u) & 1u]; M.guides = A.guides;
+        M.out = reinterpret_cast<float4*>(job.out);
+        M.width = width; M.height = height;
+        M.K = job.uniform.K; M.gain = job.mix.gain;
+        if (job.source == DenoiseSource::Tiles) hipLaunchKernelGGL(mix_kernel<true>, grid, block, 0, st, M, job.tiles);
+        else hipLaunchKernelGGL(mix_kernel<false>, grid, block, 0, st, M, TileField{});
     }
     return (int)hipGetLastError();
 }

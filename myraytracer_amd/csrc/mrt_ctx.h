@@ -255,6 +255,7 @@ struct mrt_ctx {
     uint32_t denoise_var_mode = MRT_DENOISE_VAR_ACCUMULATED;   // mrt_set_denoise_variance: where the luminance stop's variance comes from
     uint32_t denoise_spatial_frames = 3;                       // SPATIAL_EARLY: the spatial estimate while frames_done < this
     bool denoise_adaptive = false;                  // mrt_set_denoise_adaptive: a diverged accumulation is filtered per tile, not refused
+    mrt_denoise_mix denoise_mix = mrt::denoise_mix_defaults();  // mrt_set_denoise_mix: the blend behind every denoise of an accumulation
     bool guides_stale = true;
     float* d_guide_rays = nullptr;                  // 6 floats per pixel
     int32_t* d_guide_hits = nullptr;                // {sphere | -1, bits of t} per pixel (the DBG render kernel's output)

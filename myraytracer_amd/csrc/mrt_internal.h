@@ -394,8 +394,18 @@ struct DenoiseJob {
     UniformField uniform;
     TemporalField temporal;
     TileField tiles;
+    // The blend with the accumulation ("Blend with the accumulation"): with mix.enabled, for Uniform with a finite K and for
+    // Tiles, no iteration runs as the last one -- the last writes the ping / pong buffer its parity names -- and one more launch
+    // blends into `out`.  Uniform with K = +inf, and Temporal always: not read, the launches are the ones without it.
+    mrt_denoise_mix mix;
 };
 int launch_denoise(const DenoiseJob& job, void* stream);
+inline mrt_denoise_mix denoise_mix_defaults() {
+    mrt_denoise_mix p{};
+    p.size = sizeof(mrt_denoise_mix);
+    p.enabled = 0; p.gain = 1.0f;       // chosen from the table: profiles/denoise_mix_quality.txt
+    return p;
+}
 inline mrt_denoise_params denoise_defaults() {
     mrt_denoise_params p{};
     p.size = sizeof(mrt_denoise_params);

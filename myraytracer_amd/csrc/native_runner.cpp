@@ -26,7 +26,7 @@ static void usage() {
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
                          "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive]]\n"
-        "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]]]\n"
+        "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]] [--denoise-mix [GAIN]]]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
@@ -36,7 +36,9 @@ static void usage() {
         "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame; with\n"
         "                      --adaptive the per-tile filter of an adaptive accumulation is turned on (mrt_set_denoise_adaptive)\n"
         "  --denoise-variance: the luminance stop's variance (mrt_set_denoise_variance): the pixel's own accumulated estimate\n"
-        "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n");
+        "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n"
+        "  --denoise-mix [GAIN]: with --denoise-out: blend the filtered with the accumulated image per pixel by the estimated error\n"
+        "                      (mrt_set_denoise_mix); GAIN 0.25 .. 16, default the library's\n");
 }
 
 int main(int argc, char** argv) {
@@ -50,6 +52,8 @@ int main(int argc, char** argv) {
     uint32_t hint_div = 0, hint_mult = 0, check_every = 16, denoise_var = MRT_DENOISE_VAR_ACCUMULATED, spatial_frames = 3;
     double target_noise = -1.0;
     bool adaptive = false;
+    mrt_denoise_mix mix;
+    mrt_denoise_mix_default(&mix);
     std::string scene = "default", scene_file, save_scene, out, denoise_out;
     std::vector<int> devices;
     for (int i = 1; i < argc; i++) {
@@ -58,6 +62,7 @@ int main(int argc, char** argv) {
         if (eq != std::string::npos) { v = a.substr(eq + 1); a = a.substr(0, eq); }
         else if (a == "--help" || a == "-h") { usage(); return 0; }
         else if (a == "--adaptive") { adaptive = true; continue; }
+        else if (a == "--denoise-mix" && (i + 1 >= argc || !std::strncmp(argv[i + 1], "--", 2))) { mix.enabled = 1; continue; }   // (no GAIN)
         else if (i + 1 < argc) v = argv[++i];
         else { usage(); return 2; }
         if (a == "--width") args.width = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
@@ -80,6 +85,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--out") out = v;
         else if (a == "--denoise-out") denoise_out = v;
+        else if (a == "--denoise-mix") { mix.enabled = 1; mix.gain = std::strtof(v.c_str(), nullptr); }
         else if (a == "--denoise-variance") {
             const size_t colon = v.find(':');
             const std::string m = v.substr(0, colon);
@@ -147,9 +153,11 @@ int main(int argc, char** argv) {
         TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
         // an adaptive run's tiles end at their own frame counts: its denoise is the per-tile filter (one GPU: checked below)
         if (adaptive && !denoise_out.empty()) TRY(ctxs[i], mrt_set_denoise_adaptive(ctxs[i], 1));
+        TRY(ctxs[i], mrt_set_denoise_mix(ctxs[i], &mix));
     }
     // several GPUs: the noise estimate travels with the gather, and the first GPU denoises the gathered frame
     if (!denoise_out.empty() && n_gpus > 1) TRY(ctxs[0], mrt_set_gather_noise(ctxs[0], 1));
+    if (mix.enabled && denoise_out.empty()) { std::fprintf(stderr, "--denoise-mix wants --denoise-out\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
