@@ -47,7 +47,8 @@ extern "C" {
  * (mrt_set_gather_noise, mrt_read_gathered_noise, mrt_read_gathered_denoised, MRT_PRESENT_GATHERED_DENOISED); the denoise of
  * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive); the auto-regroup policy (mrt_auto_regroup,
  * mrt_auto_regroup_default, mrt_set_auto_regroup, mrt_get_auto_regroup, mrt_regroup_stats, mrt_read_regroup_stats); the
- * denoiser's blend with the accumulation (mrt_denoise_mix, mrt_denoise_mix_default, mrt_set_denoise_mix, mrt_get_denoise_mix). */
+ * denoiser's blend with the accumulation (mrt_denoise_mix, mrt_denoise_mix_default, mrt_set_denoise_mix, mrt_get_denoise_mix);
+ * material edits without a rebuild (mrt_material, mrt_update_materials, MRT_MATERIALS_RESTART_HISTORY). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -238,6 +239,36 @@ int mrt_set_world(mrt_ctx* ctx, const mrt_sphere* spheres, size_t n);
  *     with the next mrt_set_world*.
  *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as a failed mrt_set_world* does. */
 int mrt_update_spheres(mrt_ctx* ctx, uint32_t first, uint32_t count, const float* xyzr);
+/* New materials for spheres [first, first + count) of the current scene; geometry, the sphere count and the grouping stay.
+ * mrt_material is the last five fields of mrt_sphere, same meaning: albedo for Lambertian and Metal, param = fuzz (Metal) | ior
+ * (Dielectric).  The host does O(count) work; one scatter is queued on the ctx's stream.
+ *   What changes: from the call on the device holds, for these spheres, exactly what a mrt_set_world of the same sphere list
+ *     with these materials would hold of what shading reads -- the sphere's type word, and floats 4..7 of its shade record as bit
+ *     copies, including what mrt_set_world_raw derives for a Dielectric on the host (1/ior, the two Schlick r0, ior): the build
+ *     and this call share one derivation (mrt_debug_material_shade exposes it).  Any material_ty is accepted: 1..3 are the known
+ *     types, anything else absorbs, as raw::World allows.  Values are not validated, as the build does not validate them.
+ *     The device copies of the SoA material arrays (albedo / fuzz / ior entries, material_idx) are NOT kept up: no kernel reads
+ *     them (the render kernel and the denoiser's guide fill read the shade record and the type word alone).
+ *   What does not change: geometry and every hierarchy array, bit for bit.  No refit is queued; the per-scene sweep axis scale
+ *     stays (unlike after mrt_update_spheres); the camera-ray masks and lists stay built (they are geometry only); the tile
+ *     costs, the launch schedule and a pinned hint stay; the auto-regroup policy's update count and statistics stay; the
+ *     accumulation and the noise estimate are not restarted (only mrt_reset does that); no buffer, stream or event is created
+ *     or freed.
+ *   Refusals, each before anything is changed or queued: MRT_ERR_INVALID_ARG for ctx NULL, first + count beyond the sphere count,
+ *     materials NULL with count > 0, or a flag bit other than the one defined; MRT_ERR_NO_SCENE without a scene.  count == 0:
+ *     MRT_OK, nothing queued.
+ *   Ordering: as mrt_update_spheres -- frames queued before the call shade with the old materials, frames queued after it with
+ *     the new ones; the call never waits on the host, and materials may be reused as soon as it returns.
+ *   The denoiser's guides are marked stale (the albedo guide, and its rule for a Dielectric) and rebuilt at the next denoise.
+ *   Temporal reprojection: sphere indices keep their meaning, so the history is kept: a recoloured sphere converges over
+ *     max_history steps, or faster with the temporal response on.  With MRT_MATERIALS_RESTART_HISTORY every pixel whose first hit
+ *     is one of the updated spheres finds no history at the next mrt_temporal_step (it starts over at length 1 from the current
+ *     frame); every other pixel is untouched, bit for bit, and the step after that is an ordinary one.
+ *   Shards: works on any shard; every context of a multi-GPU frame must be given the same call, as for mrt_update_spheres.
+ *   MRT_ERR_HIP (a launch the runtime refuses) leaves the context without a scene, as for mrt_update_spheres. */
+typedef struct { int32_t material_ty; float albedo[3]; float param; } mrt_material;      /* 20 bytes */
+enum { MRT_MATERIALS_RESTART_HISTORY = 1u };
+int mrt_update_materials(mrt_ctx* ctx, uint32_t first, uint32_t count, const mrt_material* materials, uint32_t flags);
 /* The hierarchy's grouping made anew, on the device, from the spheres as they are now: the spheres that share clusters (all but
  * the few far larger than the rest) are permuted over the member slots they occupy -- a kd ordering whose cuts fall on
  * power-of-two blocks of clusters, so that every level's nodes are compact -- and everything derived from the grouping is refitted

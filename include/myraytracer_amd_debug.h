@@ -235,6 +235,10 @@ int mrt_debug_check_context(mrt_ctx* ctx, char* why, size_t cap);
 int mrt_debug_read_hierarchy(mrt_ctx* ctx, uint32_t info[16], double scalars[8], float* direct_out, uint32_t* direct_index_out,
                              float* top_out, float* nodes_out, uint32_t* member_index_out, float* boxes_out, float* boxes_open_out,
                              uint16_t* mfma_out, float* spheres_out, float* shade_out, float* centres_out, float* radii_out);
+/* Host only: floats 4..7 of the shade record of a sphere with this material -- the one derivation mrt_set_world_raw and
+ * mrt_update_materials share.  Lambertian: albedo, 0; Metal: albedo, fuzz; Dielectric: 1/ior, ((1 - ri)/(1 + ri))^2 for ri =
+ * 1/ior and for ri = ior, ior (every operation rounded to float); any other type: 1, 1, 1, 0.  MRT_ERR_INVALID_ARG for NULL. */
+int mrt_debug_material_shade(const mrt_material* material, float out[4]);
 /* Diagnostics of mrt_regroup_spheres.  mrt_debug_regroup_info: out[4] = {the clusters the builder made from the spheres that may
  * share one (the regroup permutes over their slots), the block capacity in force (clusters a workgroup of the block kernel
  * takes), the depths the last regroup ran over global memory, the depths it ran in LDS}; the last two are 0 before the first

@@ -56,6 +56,7 @@ EXPORTS = [
     "mrt_set_denoise_adaptive", "mrt_get_denoise_adaptive", "mrt_debug_load_accumulation",
     "mrt_auto_regroup_default", "mrt_set_auto_regroup", "mrt_get_auto_regroup", "mrt_read_regroup_stats",
     "mrt_denoise_mix_default", "mrt_set_denoise_mix", "mrt_get_denoise_mix", "mrt_debug_denoise_mix",
+    "mrt_update_materials", "mrt_debug_material_shade",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -66,6 +67,8 @@ ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
 # the denoiser's variance modes (mrt_set_denoise_variance)
 DENOISE_VAR_ACCUMULATED, DENOISE_VAR_PREFILTERED, DENOISE_VAR_SPATIAL_EARLY = 0, 1, 2
+# mrt_update_materials' flag
+MATERIALS_RESTART_HISTORY = 1
 
 
 class MrtArgs(C.Structure):
@@ -148,6 +151,10 @@ class MrtRegroupStats(C.Structure):
 class MrtSphere(C.Structure):
     _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("material_ty", C.c_int32),
                 ("albedo", C.c_float * 3), ("param", C.c_float)]
+
+
+class MrtMaterial(C.Structure):       # the last five fields of MrtSphere (mrt_update_materials)
+    _fields_ = [("material_ty", C.c_int32), ("albedo", C.c_float * 3), ("param", C.c_float)]
 
 
 class MrtCamera(C.Structure):
@@ -267,6 +274,8 @@ def load():
         "mrt_set_world_raw": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, sz]),
         "mrt_set_world": (i32, [vp, vp, sz]),
         "mrt_update_spheres": (i32, [vp, u32, u32, vp]),
+        "mrt_update_materials": (i32, [vp, u32, u32, vp, u32]),
+        "mrt_debug_material_shade": (i32, [P(MrtMaterial), P(f32)]),
         "mrt_regroup_spheres": (i32, [vp]),
         "mrt_debug_regroup_info": (i32, [vp, vp]),
         "mrt_auto_regroup_default": (None, [P(MrtAutoRegroup)]),

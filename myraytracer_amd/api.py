@@ -14,12 +14,14 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import MrtArgs, MrtCamera, MrtCameraRaw, MrtCounters, MrtLocals, MrtSphere, MrtWorld
+from ._lib import MrtArgs, MrtCamera, MrtCameraRaw, MrtCounters, MrtLocals, MrtMaterial, MrtSphere, MrtWorld
 
 LAMBERTIAN, METAL, DIELECTRIC = 1, 2, 3          # raw::MaterialTy, lib.rs:644-648 (+ extension)
 SPHERE_DTYPE = np.dtype([("center", "<f4", 3), ("radius", "<f4"), ("material_ty", "<i4"),
                          ("albedo", "<f4", 3), ("param", "<f4")])
 assert SPHERE_DTYPE.itemsize == C.sizeof(MrtSphere) == 36
+MATERIAL_DTYPE = np.dtype([("material_ty", "<i4"), ("albedo", "<f4", 3), ("param", "<f4")])     # mrt_material
+assert MATERIAL_DTYPE.itemsize == C.sizeof(MrtMaterial) == 20
 
 
 class MrtError(RuntimeError):
@@ -133,6 +135,32 @@ def pack_world(spheres: np.ndarray):
     if st:
         raise MrtError(st, "mrt_pack_world")
     return w, vec4[:nv.value].copy(), f32[:nf.value].copy(), i32[:ni.value].copy()
+
+
+def materials_of(materials) -> np.ndarray:
+    """A contiguous MATERIAL_DTYPE array from one, or from the material fields of a SPHERE_DTYPE array."""
+    arr = np.asarray(materials)
+    if arr.dtype == SPHERE_DTYPE:
+        out = np.zeros(arr.shape, MATERIAL_DTYPE)
+        for k in MATERIAL_DTYPE.names:
+            out[k] = arr[k]
+        arr = out
+    elif arr.dtype != MATERIAL_DTYPE:
+        raise TypeError(f"materials must be a MATERIAL_DTYPE or SPHERE_DTYPE array, got {arr.dtype}")
+    if arr.ndim != 1:
+        raise ValueError(f"materials must be one-dimensional, got {arr.shape}")
+    return np.ascontiguousarray(arr)
+
+
+def material_shade(material) -> np.ndarray:
+    """mrt_debug_material_shade (host only): floats 4..7 of the shade record of a sphere with this material (one MATERIAL_DTYPE
+    record) -- the derivation mrt_set_world_raw and mrt_update_materials share."""
+    m = materials_of(np.asarray(material).reshape(1))
+    out = np.zeros(4, np.float32)
+    st = _lib.load().mrt_debug_material_shade(C.cast(m.ctypes.data, C.POINTER(MrtMaterial)), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if st:
+        raise MrtError(st, "mrt_debug_material_shade")
+    return out
 
 
 def camera_derive(cam: Camera) -> MrtCameraRaw:
@@ -302,6 +330,15 @@ class State:
         if arr.ndim != 2 or arr.shape[1] != 4:
             raise ValueError(f"update_spheres: xyzr must be (count, 4), got {arr.shape}")
         self._check(self._L.mrt_update_spheres(self._ctx, first, len(arr), arr.ctypes.data if len(arr) else None), "mrt_update_spheres")
+
+    def update_materials(self, first: int, materials, restart_history: bool = False):
+        """mrt_update_materials: new materials for spheres first .. first + len(materials) - 1 of the current scene -- a
+        MATERIAL_DTYPE array, or a SPHERE_DTYPE array whose material fields are taken; geometry, grouping and the hierarchy stay,
+        nothing is refitted and nothing waits for the frames in flight.  restart_history: the next temporal_step finds no history
+        for the pixels that show these spheres."""
+        arr = materials_of(materials)
+        flags = _lib.MATERIALS_RESTART_HISTORY if restart_history else 0
+        self._check(self._L.mrt_update_materials(self._ctx, first, len(arr), arr.ctypes.data if len(arr) else None, flags), "mrt_update_materials")
 
     def regroup_spheres(self):
         """mrt_regroup_spheres: the hierarchy's grouping made anew on the device from the spheres as they are now (after

@@ -27,6 +27,7 @@ static_assert(sizeof(mrt_locals) == 48, "Locals is 48 bytes (lib.rs:368-377)");
 static_assert(sizeof(mrt_world) == 80, "raw::World 64 B + DielectricRange 16 B");
 static_assert(offsetof(mrt_world, dielectrics) == MRT_WORLD_BYTES_REFERENCE, "raw::World is the first 64 bytes of mrt_world");
 static_assert(sizeof(mrt_sphere) == 36, "mrt_sphere layout");
+static_assert(sizeof(mrt_material) == 20 && offsetof(mrt_sphere, material_ty) == 16, "mrt_material is the last five fields of mrt_sphere");
 static_assert(sizeof(mrt_camera) == 52, "mrt_camera layout");
 static_assert(sizeof(mrt_camera_raw) == 80, "mrt_camera_raw layout");
 static_assert(sizeof(mrt::SphereRec) == 16, "SphereRec layout");

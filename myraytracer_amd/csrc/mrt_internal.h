@@ -282,6 +282,26 @@ int launch_cam_masks(const KParams& p, uint32_t* masks, uint32_t* lists, uint32_
 int launch_refit_scatter(const RefitScatterArgs& a, void* stream);
 int launch_refit(const RefitArgs& a, void* stream);
 
+// refit.hip too (include/myraytracer_amd.h, mrt_update_materials): the device side of a material edit.  `count` <= kMaterialBatch
+// spheres, BY VALUE in the kernel arguments as a geometry update's are: per sphere the four floats 4..7 of its shade record, as
+// material_shade derives them on the host, and its type word (types = i32_data + material_ty_base_idx).  With restart_history the
+// radius of the sphere's entry in prev_xyzr becomes a NaN: the next temporal step finds no history for the pixels that show it
+// and its own snapshot restores the entry.  Nothing else is written.
+constexpr uint32_t kMaterialBatch = 192;  // 20 bytes a sphere: 3,840 of the 4 KB a launch's arguments may take
+struct MaterialScatterArgs {
+    float* shade;
+    int32_t* types;
+    float* prev_xyzr;
+    uint32_t first, count, restart_history, _pad;
+    float words[4 * kMaterialBatch];
+    int32_t ty[kMaterialBatch];
+};
+static_assert(sizeof(MaterialScatterArgs) <= 4096, "the batch rides in the kernel arguments: 4 KB a launch");
+int launch_material_scatter(const MaterialScatterArgs& a, void* stream);
+// What shading a hit reads of a sphere's material: floats 4..7 of its shade record.  The ONE derivation, for the build
+// (mrt_set_world_raw) and for mrt_update_materials; param = fuzz (Metal) | ior (Dielectric).
+void material_shade(int32_t ty, const float* albedo, float param, float out[4]);
+
 // regroup.hip (include/myraytracer_amd.h, mrt_regroup_spheres): the pooled spheres -- those of the clusters [0, n_pool) that
 // build_clusters made from its pool -- permuted over the member slots they occupy, by the ordering of tests/regroup_ref.py: a kd
 // split whose cuts fall on power-of-two blocks of clusters.  Only member_index is written (and the scratch); launch_refit follows.

@@ -30,6 +30,18 @@ __global__ void __launch_bounds__(kRefitBlock) refit_scatter_kernel(const RefitS
     a.radii[s] = r;
 }
 
+// mrt_update_materials: one lane per edited sphere of the batch, which rides in the kernel arguments like a geometry update's.
+// The upper half of the shade record in one 16-byte store (records are 32 bytes, the array hipMalloc's: aligned), the type word,
+// and with restart_history a NaN for the radius of the temporal step's "previous" sphere (world.cpp says why).
+__global__ void __launch_bounds__(kRefitBlock) material_scatter_kernel(const MaterialScatterArgs a) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= a.count) return;
+    const size_t s = (size_t)a.first + i;
+    reinterpret_cast<float4*>(a.shade)[2 * s + 1] = make_float4(a.words[4 * i], a.words[4 * i + 1], a.words[4 * i + 2], a.words[4 * i + 3]);
+    a.types[s] = a.ty[i];
+    if (a.restart_history) a.prev_xyzr[4 * s + 3] = __builtin_nanf("");
+}
+
 // level 0: slot m takes its record from sphere member_index[m]; a never-hit padding slot stays as it is
 __global__ void __launch_bounds__(kRefitBlock) refit_members_kernel(const RefitArgs a) {
     const uint32_t m = blockIdx.x * kRefitBlock + threadIdx.x;
@@ -119,6 +131,12 @@ template <uint32_t L> void launch_level(const RefitArgs& a, uint32_t k, uint32_t
 int launch_refit_scatter(const RefitScatterArgs& a, void* stream) {
     if (a.count == 0 || a.count > kRefitBatch) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(refit_scatter_kernel, dim3((a.count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int launch_material_scatter(const MaterialScatterArgs& a, void* stream) {
+    if (a.count == 0 || a.count > kMaterialBatch) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(material_scatter_kernel, dim3((a.count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -65,10 +65,28 @@ mrt::RegroupArgs regroup_args(mrt_ctx* c, bool gated) {
     return g;
 }
 
-// The device arrays of the scene change (mrt_update_spheres, mrt_regroup_spheres; `who` for the messages): the ctx's stream waits
-// for the render kernels in flight, which read them; later frames wait for ev_inputs (inputs_dirty); the camera masks, which are
+// The ordering of every call that changes device arrays of the scene behind the frames in flight (mrt_update_spheres,
+// mrt_regroup_spheres, mrt_update_materials; `who` for the messages): the ctx's stream waits for the render kernels in flight,
+// which read them; later frames wait for ev_inputs (inputs_dirty), recorded on the ctx's stream behind whatever the caller queues
+// next (frames.cpp, enter_slot).  Nothing waits on the host.  -> MRT_OK, or MRT_ERR_HIP with the scene lost.
+int lose_scene(mrt_ctx* c, const char* who, const char* what, hipError_t e) {
+    c->have_world = false;
+    return fail(c, MRT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+}
+int order_behind_frames(mrt_ctx* c, const char* who) {
+    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
+        mrt_ctx::FrameSlot& S = c->slot[i];
+        if (!S.render_pending) continue;
+        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
+        if (e != hipSuccess) return lose_scene(c, who, "hipStreamWaitEvent", e);
+    }
+    c->inputs_dirty = true;
+    return MRT_OK;
+}
+
+// The geometry or the grouping changes (mrt_update_spheres, mrt_regroup_spheres): ordered as above; the camera masks, which are
 // per cluster slot, are built anew; `change` queues what the call is about (-> 0 or a HIP error) and refit.hip derives
-// everything else behind it, in stream order.  Nothing waits on the host.  The refit's operand is the one for D = I: the scaled
+// everything else behind it, in stream order.  The refit's operand is the one for D = I: the scaled
 // sweep space's proof (hierarchy.cpp, scaled_top_records) needs scene statistics only the device now has, so D = I until the next
 // mrt_set_world*.  mfma_scene_ok / mfma_r2_ref stay the build's: they say where the matrix-core sweep's slack is small against
 // R^2, a speed rule -- the sweep is conservative wherever it runs.  A failure leaves the device arrays between
@@ -77,14 +95,8 @@ mrt::RegroupArgs regroup_args(mrt_ctx* c, bool gated) {
 // says "pending" -- the judgement queued by `change` opened the gate -- or, with kMark, in any case (a regroup the caller asked for).
 enum Rebaseline { kNone, kIfPending, kMark };
 template <class F> int change_scene(mrt_ctx* c, const char* who, F&& change, Rebaseline rebaseline = kNone) {
-    auto lost = [&](const char* what, hipError_t e) { c->have_world = false; return fail(c, MRT_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e)); };
-    for (uint32_t i = 0; i < mrt_ctx::kMaxFrameSlots; i++) {
-        mrt_ctx::FrameSlot& S = c->slot[i];
-        if (!S.render_pending) continue;
-        const hipError_t e = hipStreamWaitEvent(c->stream, S.render_done, 0);
-        if (e != hipSuccess) return lost("hipStreamWaitEvent", e);
-    }
-    c->inputs_dirty = true;
+    auto lost = [&](const char* what, hipError_t e) { return lose_scene(c, who, what, e); };
+    MRT_TRY(order_behind_frames(c, who));
     c->cam_mask_gen++;
     int le = change();
     if (le) return lost("launch", (hipError_t)le);
@@ -109,6 +121,27 @@ bool auto_regroup_ok(const mrt_auto_regroup* p) {
 }  // namespace
 
 namespace mrt {
+
+// What shading a hit reads of a sphere's material (mrt_internal.h): the build's per-sphere derivation and mrt_update_materials'.
+void material_shade(int32_t ty, const float* albedo, float param, float out[4]) {
+    out[0] = out[1] = out[2] = 1.0f; out[3] = 0.0f;         // an unknown type absorbs: the kernel reads none of these
+    if (ty == MRT_LAMBERTIAN) {
+        std::memcpy(out, albedo, 3 * sizeof(float));
+    } else if (ty == MRT_METAL) {
+        std::memcpy(out, albedo, 3 * sizeof(float));
+        out[3] = param;
+    } else if (ty == MRT_DIELECTRIC) {
+        // A Dielectric attenuates by (1,1,1) (a constant in the kernel), so its colour slots carry what its
+        // scatter derives from the sphere alone, evaluated here with the same f32 operations in the same order
+        // (correctly rounded '/', no contraction): ri = 1/ior for a front-face hit, and the Schlick r0 =
+        // ((1-ri)/(1+ri))^2 for either face.  Bit-identical to evaluating them per hit.
+        const float ior = param;
+        auto schlick_r0 = [](float ri) { float r0 = (1.0f - ri) / (1.0f + ri); return r0 * r0; };
+        const float inv_ior = 1.0f / ior;
+        out[0] = inv_ior; out[1] = schlick_r0(inv_ior); out[2] = schlick_r0(ior);
+        out[3] = ior;
+    }
+}
 
 // the scene / hierarchy / sweep-variant part of the kernel arguments (everything that does not depend on the frame)
 void fill_scene_params(const mrt_ctx* c, mrt::KParams& p) {
@@ -308,23 +341,11 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
         sh[3] = f32[w->spheres.radius_base_idx + i];
         const int32_t ty = i32[w->spheres.material_ty_base_idx + i];
         const int32_t mi = i32[w->spheres.material_idx_base_idx + i];
-        sh[4] = sh[5] = sh[6] = 1.0f; sh[7] = 0.0f;
-        if (ty == MRT_LAMBERTIAN) {
-            std::memcpy(sh + 4, vec4 + 4 * (w->lambertians.albedo_base_idx + mi), 3 * sizeof(float));
-        } else if (ty == MRT_METAL) {
-            std::memcpy(sh + 4, vec4 + 4 * (w->metals.albedo_base_idx + mi), 3 * sizeof(float));
-            sh[7] = f32[w->metals.fuzz_base_idx + mi];
-        } else if (ty == MRT_DIELECTRIC) {
-            // A Dielectric attenuates by (1,1,1) (a constant in the kernel), so its colour slots carry what its
-            // scatter derives from the sphere alone, evaluated here with the same f32 operations in the same order
-            // (correctly rounded '/', no contraction): ri = 1/ior for a front-face hit, and the Schlick r0 =
-            // ((1-ri)/(1+ri))^2 for either face.  Bit-identical to evaluating them per hit.
-            const float ior = f32[w->dielectrics.ior_base_idx + mi];
-            auto schlick_r0 = [](float ri) { float r0 = (1.0f - ri) / (1.0f + ri); return r0 * r0; };
-            const float inv_ior = 1.0f / ior;
-            sh[4] = inv_ior; sh[5] = schlick_r0(inv_ior); sh[6] = schlick_r0(ior);
-            sh[7] = ior;
-        }
+        // (an unknown type's index is unused; material_shade is mrt_update_materials' derivation too)
+        const float* albedo = ty == MRT_LAMBERTIAN ? vec4 + 4 * (w->lambertians.albedo_base_idx + mi)
+                            : ty == MRT_METAL ? vec4 + 4 * (w->metals.albedo_base_idx + mi) : nullptr;
+        const float param = ty == MRT_METAL ? f32[w->metals.fuzz_base_idx + mi] : ty == MRT_DIELECTRIC ? f32[w->dielectrics.ior_base_idx + mi] : 0.0f;
+        mrt::material_shade(ty, albedo, param, sh + 4);
     }
     MRT_TRY(upload((void**)&c->d_shade, shade.data(), shade.size() * sizeof(float)));
     {
@@ -429,6 +450,45 @@ int mrt_update_spheres(mrt_ctx* c, uint32_t first, uint32_t count, const float* 
     }, check ? kIfPending : kNone);
     if (st == MRT_OK && c->auto_regroup.enabled && c->n_pool > 1) c->auto_updates++;
     return st;
+}
+
+// New materials for spheres whose geometry stays (include/myraytracer_amd.h): the two things shading reads of a sphere's material
+// -- floats 4..7 of its shade record and its type word -- derived here by the build's own function and scattered in stream order,
+// kMaterialBatch spheres a launch, in the kernel arguments as a geometry update's are.  Ordered like an update and nothing more:
+// no refit (the hierarchy does not know materials), no new camera masks (geometry only), the sweep's space, the schedule, the
+// tile costs and the auto-regroup policy's count as they are.  The SoA copies of the materials on the device (albedo / fuzz /
+// ior entries, material_idx) are left as the last mrt_set_world* wrote them: no kernel reads them.
+int mrt_update_materials(mrt_ctx* c, uint32_t first, uint32_t count, const mrt_material* materials, uint32_t flags) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (flags & ~(uint32_t)MRT_MATERIALS_RESTART_HISTORY) return fail(c, MRT_ERR_INVALID_ARG, "mrt_update_materials: flags 0x%x", flags);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_update_materials: no scene");
+    if ((uint64_t)first + count > c->n_spheres)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_update_materials: spheres [%u, %llu) of a scene of %u", first, (unsigned long long)first + count, c->n_spheres);
+    if (count && !materials) return fail(c, MRT_ERR_INVALID_ARG, "mrt_update_materials: null array");
+    if (count == 0) return MRT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(order_behind_frames(c, "mrt_update_materials"));
+    c->guides_stale = true;             // (the albedo guide, and its rule for a Dielectric)
+    for (uint32_t b = 0; b < count; b += mrt::kMaterialBatch) {
+        mrt::MaterialScatterArgs s;
+        s.shade = c->d_shade; s.types = c->d_i32 + c->world.spheres.material_ty_base_idx; s.prev_xyzr = c->d_prev_xyzr;
+        s.first = first + b; s.count = std::min(mrt::kMaterialBatch, count - b);
+        s.restart_history = (flags & MRT_MATERIALS_RESTART_HISTORY) ? 1u : 0u; s._pad = 0;
+        for (uint32_t i = 0; i < s.count; i++) {
+            const mrt_material& m = materials[(size_t)b + i];
+            mrt::material_shade(m.material_ty, m.albedo, m.param, s.words + 4 * i);
+            s.ty[i] = m.material_ty;
+        }
+        const int le = mrt::launch_material_scatter(s, c->stream);
+        if (le) return lose_scene(c, "mrt_update_materials", "launch", (hipError_t)le);
+    }
+    return MRT_OK;
+}
+
+int mrt_debug_material_shade(const mrt_material* material, float out[4]) {
+    if (!material || !out) return MRT_ERR_INVALID_ARG;
+    mrt::material_shade(material->material_ty, material->albedo, material->param, out);
+    return MRT_OK;
 }
 
 // The grouping made anew from the spheres as the device holds them (include/myraytracer_amd.h): regroup.hip permutes the pooled

@@ -28,7 +28,12 @@
    defaults come from, in one process: (1) the cost of a check that does not fire -- the policy at ratio 1e6, check_every 1
    against the policy off, as step time and as the device time of the update call between HIP events -- and from it the
    smallest power-of-two check_every that keeps the cost under 1 % of the every-N step; (2) ratios 1.5, 2, 3, 4 at that
-   check_every, of which the largest within --spread steps/s of the fastest is taken; (3) the slow walk (0.2 x --walk) every N against the policy; (4) the C3 walk with the policy off and on."""
+   check_every, of which the largest within --spread steps/s of the fastest is taken; (3) the slow walk (0.2 x --walk) every N against the policy; (4) the C3 walk with the policy off and on.
+   --materials prints the section "materials" instead (mrt_update_materials): (1) the call for 1 sphere and for all
+   10,001 of C5 -- host time, device time between HIP events on the context's stream around it -- next to the same context's
+   mrt_set_world; (2) on C3 and C5, `steps` steps of "recolour every sphere, then one frame" four ways, twice in turn in one
+   process: no edit at all (the ceiling), the edit through mrt_update_materials, the same with the schedule pinned to full-width
+   frames (mrt_set_schedule_hint(1, 1)), the edit through mrt_set_world."""
 import argparse
 import os
 import sys
@@ -50,6 +55,7 @@ ap.add_argument("--temporal", action="store_true")
 ap.add_argument("--response", action="store_true")
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--auto-regroup", action="store_true")
+ap.add_argument("--materials", action="store_true")
 ap.add_argument("--ratio", type=float, default=None)
 ap.add_argument("--check-every", type=int, default=None)
 ap.add_argument("--spread", type=float, default=0.0, help="steps/s within which two ratios tie (the larger is taken)")
@@ -266,6 +272,97 @@ def temporal_cost(name, spheres, cam, path, response=False, rounds=1):
               + f" ({', '.join(f'{r:.3f}' for r in on / off)} x the step); the step's median between the rounds: off "
               + " / ".join(f"{v:.4f}" for v in off) + ", on " + " / ".join(f"{v:.4f}" for v in on), flush=True)
 
+
+def recolours(spheres, steps, rng):
+    """per step, every sphere's material with a new albedo (and a new fuzz for the metals): a MATERIAL_DTYPE array of the scene"""
+    out = []
+    for _ in range(steps):
+        m = M.materials_of(spheres)
+        m["albedo"] = rng.uniform(0.05, 0.95, (len(m), 3)).astype(np.float32)
+        m["param"] = np.where(m["material_ty"] == 2, rng.uniform(0.0, 0.5, len(m)), m["param"]).astype(np.float32)
+        out.append(m)
+    return out
+
+
+def materials_cost(name, spheres, cam):
+    """(1): the call for 1 sphere and for all of them -- host time, device time between HIP events on the context's stream around
+    it, the context idle -- next to the same context's mrt_set_world of the same list"""
+    stream = torch.cuda.Stream()
+    edits = recolours(spheres, 50, np.random.default_rng(2))
+    with M.State(M.Args(W, H, 1, a.depth, 1.0), seed=1, stream=stream.cuda_stream) as st:
+        st.set_world(spheres)
+        st.set_camera(cam)
+        st.render(4)
+        st.sync()
+        for count in (1, len(spheres)):
+            host, dev = [], []
+            for m in edits:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                c0 = time.perf_counter()
+                st.update_materials(0, m[:count])
+                host.append((time.perf_counter() - c0) * 1e3)
+                e1.record(stream)
+                st.sync()
+                dev.append(e0.elapsed_time(e1))
+            print(f"  {name}: mrt_update_materials of {count} sphere{'s' if count > 1 else ''} ({-(-count // 192)} launch{'es' if count > 192 else ''}): "
+                  f"host median {np.median(host):.4f} ms, max {max(host):.4f}; device (events) median {np.median(dev):.4f} ms, max {max(dev):.4f}", flush=True)
+        built = []
+        for _ in range(5):
+            c0 = time.perf_counter()
+            st.set_world(spheres)
+            built.append((time.perf_counter() - c0) * 1e3)
+        print(f"  {name}: mrt_set_world of the same {len(spheres)} spheres: host median {np.median(built):.3f} ms", flush=True)
+
+
+def materials_loop(name, spheres, cam, way, edits):
+    """(2): `way` = none | materials | mat-wide (materials with mrt_set_schedule_hint(1, 1)) | set_world: per step the edit (or
+    nothing), then one frame; steps per second over the loop and the final mrt_sync"""
+    stream = torch.cuda.Stream()
+    with M.State(M.Args(W, H, 1, a.depth, 1.0), seed=1, stream=stream.cuda_stream) as st:
+        st.set_world(spheres)
+        st.set_camera(cam)
+        if way == "mat-wide":                   # every frame on all the waves: an edit between two frames keeps them from overlapping anyway
+            st.set_schedule_hint(1, 1)
+        st.render(8)
+        st.sync()
+        sc = spheres.copy()
+        host = []
+        t0 = time.perf_counter()
+        for m in edits:
+            c0 = time.perf_counter()
+            if way in ("materials", "mat-wide"):
+                st.update_materials(0, m)
+            elif way == "set_world":
+                for k in M.MATERIAL_DTYPE.names:
+                    sc[k] = m[k]
+                st.set_world(sc)
+            host.append((time.perf_counter() - c0) * 1e3)
+            st.redraw()
+        st.sync()
+        sec = time.perf_counter() - t0
+        sch = st.get_schedule()
+    print(f"  {name} {way:9s} {len(edits) / sec:8.1f} steps/s ({1e3 * sec / len(edits):.3f} ms a step)  call on the host: median {np.median(host):8.4f} ms, "
+          f"max {max(host):8.4f}  schedule at the end: div {sch['div']} x {sch['mult']}, settled {sch['settled']}, {sch['frames_in_flight']} frames in flight", flush=True)
+    return len(edits) / sec
+
+
+if a.materials:
+    print(f"materials: {W}x{H} x 1 spp, depth {a.depth}; {a.steps} steps of \"recolour every sphere, then one frame\"; build {M._lib.load().mrt_build_id().decode()}",
+          flush=True)
+    scenes = (("C3 cover-glass", M.scene_cover(1, True)), ("C5 stress 100x100", M.scene_stress(1, 100)))
+    print("(1) the call alone, 50 calls each, the context idle", flush=True)
+    materials_cost(*scenes[1][:1], *scenes[1][1])
+    print("(2) the loop four ways, twice in turn in one process", flush=True)
+    for name, (spheres, cam) in scenes:
+        edits = recolours(spheres, a.steps, np.random.default_rng(1))
+        print(f"{name}: {len(spheres)} spheres", flush=True)
+        for rnd in range(2):
+            r = {way: materials_loop(name, spheres, cam, way, edits) for way in ("none", "materials", "mat-wide", "set_world")}
+            print(f"  {name}, round {rnd + 1}: mrt_update_materials {r['materials'] / r['none']:.3f} x the no-edit loop ({1e3 / r['materials'] - 1e3 / r['none']:+.4f} ms a step), "
+                  f"with the schedule pinned to full-width frames {r['mat-wide'] / r['none']:.3f} x ({1e3 / r['mat-wide'] - 1e3 / r['none']:+.4f} ms a step), "
+                  f"mrt_set_world {r['set_world'] / r['none']:.3f} x ({1e3 / r['set_world'] - 1e3 / r['none']:+.4f} ms a step)", flush=True)
+    sys.exit(0)
 
 if a.temporal or a.response:
     print(f"temporal{' + response' if a.response else ''}: {W}x{H} x 1 spp, depth {a.depth}, max_framebuffer_weight 0; {a.steps} steps of a random walk ({a.walk} x the scene's size a "

@@ -34,6 +34,17 @@ def _phase(name, pattern):
     raise KeyError(pattern)
 
 
+def _mat(line_pattern, pattern):
+    """a figure of the first line matching `line_pattern` in the section "materials" of profiles/animation_rates.txt (round 1 of two)"""
+    inside = False
+    for line in open(os.path.join(ROOT, "profiles", "animation_rates.txt")):
+        if line.startswith("== "):
+            inside = line.startswith("== materials ==")
+        elif inside and re.search(line_pattern, line):
+            return float(re.search(pattern, line).group(1))
+    raise KeyError(line_pattern)
+
+
 def _anim(scene, way, pattern):
     """a figure of the line of profiles/animation_rates.txt for `scene` ("C3" / "C5") rendered through `way` ("set_world" / "update")"""
     for line in open(os.path.join(ROOT, "profiles", "animation_rates.txt")):
@@ -93,6 +104,24 @@ TOKENS = {
     "ANIM_C5_UPD_MS": (lambda: _anim("C5", "update", r"median\s+([\d.]+) ms"), ".3f"),
     "ANIM_C3_REFIT_MS": (lambda: _anim("C3", "update", r"events\): median ([\d.]+) ms"), ".3f"),
     "ANIM_C5_REFIT_MS": (lambda: _anim("C5", "update", r"events\): median ([\d.]+) ms"), ".3f"),
+    "MAT_ONE_HOST_MS": (lambda: _mat(r"mrt_update_materials of 1 sphere", r"host median ([\d.]+) ms"), ".4f"),
+    "MAT_ONE_DEV_MS": (lambda: _mat(r"mrt_update_materials of 1 sphere", r"events\) median ([\d.]+) ms"), ".4f"),
+    "MAT_C5_HOST_MS": (lambda: _mat(r"mrt_update_materials of 10001 spheres", r"host median ([\d.]+) ms"), ".3f"),
+    "MAT_C5_DEV_MS": (lambda: _mat(r"mrt_update_materials of 10001 spheres", r"events\) median ([\d.]+) ms"), ".3f"),
+    "MAT_C5_WORLD_MS": (lambda: _mat(r"mrt_set_world of the same 10001 spheres", r"host median ([\d.]+) ms"), ".1f"),
+    "MAT_C5_RATE": (lambda: _mat(r"\s+C5 \S.* materials\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C5_NONE_RATE": (lambda: _mat(r"\s+C5 \S.* none\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C5_SET_RATE": (lambda: _mat(r"\s+C5 \S.* set_world\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C5_WIDE_RATE": (lambda: _mat(r"\s+C5 \S.* mat-wide\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C3_RATE": (lambda: _mat(r"\s+C3 \S.* materials\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C3_NONE_RATE": (lambda: _mat(r"\s+C3 \S.* none\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C3_SET_RATE": (lambda: _mat(r"\s+C3 \S.* set_world\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C3_WIDE_RATE": (lambda: _mat(r"\s+C3 \S.* mat-wide\s", r"([\d.]+) steps/s"), ",.0f"),
+    "MAT_C5_STEP_MS": (lambda: _mat(r"\s+C5 \S.* materials\s", r"\(([\d.]+) ms a step\)"), ".2f"),
+    "MAT_C5_NONE_STEP_MS": (lambda: _mat(r"\s+C5 \S.* none\s", r"\(([\d.]+) ms a step\)"), ".2f"),
+    "MAT_C5_SET_STEP_MS": (lambda: _mat(r"\s+C5 \S.* set_world\s", r"\(([\d.]+) ms a step\)"), ".1f"),
+    "MAT_C5_GAP_MS": (lambda: _mat(r"\s+C5 \S.*, round 1:", r"no-edit loop \(\+([\d.]+) ms a step\)"), ".2f"),
+    "MAT_C3_GAP_MS": (lambda: _mat(r"\s+C3 \S.*, round 1:", r"no-edit loop \(\+([\d.]+) ms a step\)"), ".2f"),
     "C5_NODE_ROUNDS": (lambda: _phase("c5", r"node rounds/sweep ([\d.]+)"), ".1f"),
     "C5_ROUND_ITEMS": (lambda: _phase("c5", r"node rounds/sweep [\d.]+ \(items/round ([\d.]+)\)"), ".0f"),
 }
