@@ -104,9 +104,10 @@ constexpr uint32_t kBlockChunks = 16;     // 16 chunks x 16 clusters x 4 = 1024 
 // (owner lane, node) in small LDS queues; every round 64 lanes take 64 items, whoever owns them.
 // The bounds form a 4-ary hierarchy of P.levels levels above the member spheres (level 0);
 // the sweep tests the top level's bounding spheres, the walk descends.  Small scenes (one level):
-//   (owner, cluster) items are never stored: node round k of a block DERIVES its 64 items -- lane j takes the block's item
-//   64 k + j -- from the lanes' candidate counts and the sweep masks in LDS (render_kernel, "Small scenes"; the derivation
-//   is restated and tested in tests/test_walk_items_host.py)
+//   (owner, cluster) items are never stored: every owner tests its first candidate itself (round 0), and node round k of a
+//   block DERIVES its 64 items of the rest -- lane j takes the block's item 64 k + j -- from the lanes' candidate counts and the
+//   sweep masks in LDS (render_kernel, "Small scenes"; the numbering is restated and tested in tests/test_walk_items_host.py
+//   and tests/test_walk_first_item_host.py)
 //   queue 0 : (owner, member)   members whose discriminant is >= 0, waiting for the root tests
 // Large scenes: every owner filters its candidates against their boxes in the lane -> one stack of inner nodes of every
 // level -> clusters -> members (render_kernel, "Large scenes").
@@ -544,8 +545,6 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
 
                 // ---- cooperative walk over this block's candidates
                 uint32_t wm = 0, ebase = 0;               // owner side of the large scenes' filter: see refill_mask_word
-                const uint32_t incl = wave_incl_scan(rem);
-                const uint32_t total_rem = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 // the ray of the lane that owns a work item, from where every lane left its own
                 auto fetch_ray = [&](const uint32_t owner, V3& ro, V3& rd) {
                     const float4 r0 = rays[2u * owner];
@@ -637,7 +636,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 };
                 if constexpr (SMALL) {
                     // Small scenes (one level).  The block's items are the set mask bits of its usable lanes, numbered lane by lane:
-                    // lane l owns items [excl, incl) of the scan of `rem`.  ceil(total_rem / 64) node rounds, each deriving its own 64
+                    // lane l owns rem items, the first of which it tests itself (round 0 below), and items [excl, incl) of the scan of
+                    // `rem - 1` among the rest.  ceil(total_rem / 64) node rounds, each deriving its own 64
                     // items with every lane busy -- owner from a table of the owners' first items and a running maximum, record as the
                     // r-th set bit of the owner's mask words -- instead of every owner peeling its bits into a queue at the pace of the
                     // busiest lane (round 2 .. 9: the wave's poorest filled phase).  The order of a block's items is free: the root
@@ -648,9 +648,34 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     uint32_t* const starts = reinterpret_cast<uint32_t*>(queues + kQueueCap);
                     const uint32_t* const masks0 = masks - lane;                    // the block's word w of lane l at masks0[w * 64 + l]
                     const uint32_t words = (blk_end - blk) / (2u * kChunk);         // 1 .. 8
+                    // Round 0, in the lane: every owner tests its own item 0 -- the lowest set bit of the top-most non-zero word of
+                    // its block, the word read back from its own masks -- with its ray in registers: no table, no running maximum, no
+                    // rank, no ray fetch.  A bounce ray carries 1.84 candidates: at C3 round 0 takes about 45 of a wave's 108 items and
+                    // leaves the cooperative rounds below, which level out the rest, 1.20 derivations per iteration instead of 2.14
+                    // (profiles/walk_first_item_c3_phase_profile.txt).  (A lane without an item reads word 0 and tests the block's
+                    // first record: `on` keeps it from pushing.)
+                    const bool own = rem != 0u;
+                    const unsigned long long own_mask = __builtin_amdgcn_ballot_w64(own);
+                    if (own_mask != 0ull) {
+                        const uint32_t w0 = own ? 31u - (uint32_t)__builtin_clz(nz) : 0u;
+                        const uint32_t m0 = masks[w0 * 64u];
+                        const uint32_t node = blk + w0 * (2u * kChunk) + (own ? 31u - (uint32_t)__builtin_ctz(m0) : 0u);
+                        qn0 += members_round(nodes + 4u * node, o, d, a, own, (lane << kIdBits) | (4u * node), q0 + qn0);
+                        if (!PILOT) mtests += kClusterK * (uint32_t)__popcll(own_mask);
+#ifdef MRT_STAMPS
+                        rounds_a_++; items_a_ += (uint32_t)__popcll(own_mask);
+#endif
+                        lds_order();
+                        MRT_WALK_STAMP(2);
+                        while (qn0 >= 64u) root_round(q0, qn0);
+                    }
+                    // The cooperative rounds take the rest: the owners' items 1 .. rem - 1, numbered on the reduced counts
+                    const uint32_t rest = rem - (own ? 1u : 0u);
+                    const uint32_t incl = wave_incl_scan(rest);
+                    const uint32_t total_rem = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                     // (first item << 6 | lane; all ones for a lane without items: its "first item" is beyond every window.  The one
                     // value an owner keeps through the block's rounds)
-                    const uint32_t start_entry = rem != 0u ? ((incl - rem) << 6) | lane : 0xFFFFFFFFu;
+                    const uint32_t start_entry = rest != 0u ? ((incl - rest) << 6) | lane : 0xFFFFFFFFu;
                     uint32_t carry = 0u;                                            // wave-uniform, like every counter of the scheduling
                     // Item `r` of the owner lies in the highest slot at which the count of set bits, from the top slot down and that
                     // slot included, exceeds r.  `n` slots ending at the block's last word are read, so a block of fewer
@@ -694,7 +719,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                             e = wave_incl_max(e < carry ? carry : e);
                             carry = (uint32_t)__builtin_amdgcn_readlane((int)e, 63);
                             const uint32_t owner = e & 63u;
-                            const uint32_t r = g0 + (act ? lane : take - 1u) - (e >> 6);    // its number among the owner's items
+                            // its number among the owner's items: round 0 took item 0, the masks still hold its bit
+                            const uint32_t r = g0 + (act ? lane : take - 1u) - (e >> 6) + 1u;
                             uint32_t sel, r_in;
                             const uint32_t first = words <= 4u ? pick_word(IC<4>{}, owner, r, sel, r_in) : pick_word(IC<8>{}, owner, r, sel, r_in);
                             // the r_in-th set bit of the word from below (a word rarely holds more than two): a wave-level loop, at
