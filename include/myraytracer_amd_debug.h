@@ -288,6 +288,24 @@ int mrt_debug_load_temporal_fast(mrt_ctx* ctx, const float* h2);
  * the first subset frame of mrt_render_tiles would, with the one allocation of that step -- and sets the device's and the host's
  * copy of the map; nothing else is allocated.  mrt_frames_done is untouched; mrt_reset returns to the uniform state. */
 int mrt_debug_load_accumulation(mrt_ctx* ctx, const float* rgba, const float* S, const uint32_t* tile_frames);
+/* Diagnostic of the stream ordering (tests/order_walks.py): queues ONE single-wave kernel on a stream of the context that stays
+ * resident for `ticks` of the device's 100 MHz wall clock or for `max_polls` polls of it (about a microsecond each), whichever
+ * comes first -- the exit never depends on the clock alone -- so that whatever is queued behind it on that stream starts late
+ * while the other streams run on.  which: MRT_HOLD_CONTEXT the context's stream (the caller's after mrt_set_stream),
+ * MRT_HOLD_SLOT the side stream of frame slot `index` (a frame lands on slot frame number % frames in flight), MRT_HOLD_PRESENT
+ * the present's copy stream, MRT_HOLD_NOISE the stream of the tile map's copy; index must be 0 except for MRT_HOLD_SLOT.
+ * Creates nothing: MRT_ERR_STATE where the stream does not exist yet (a slot beyond the first two that no schedule has used, no present with
+ * mrt_debug_set_present_copy(0), no mrt_read_noise_tiles so far).  ticks == 0, ticks > MRT_HOLD_MAX_TICKS (half a second),
+ * max_polls == 0 or an unknown `which` / slot: MRT_ERR_INVALID_ARG.  Returns at once.  mrt_debug_hold_stamps (host only; after
+ * the hold has ended, e.g. behind mrt_sync): out[0], out[1] = the {start, end} ticks the most recent hold wrote, out[2] = the
+ * polls it was given (zeros before the first hold). */
+#define MRT_HOLD_CONTEXT 0u
+#define MRT_HOLD_SLOT 1u
+#define MRT_HOLD_PRESENT 2u
+#define MRT_HOLD_NOISE 3u
+#define MRT_HOLD_MAX_TICKS 50000000ull
+int mrt_debug_hold(mrt_ctx* ctx, uint32_t which, uint32_t index, uint64_t ticks, uint32_t max_polls);
+int mrt_debug_hold_stamps(mrt_ctx* ctx, uint64_t out[3]);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,7 @@ EXPORTS = [
     "mrt_auto_regroup_default", "mrt_set_auto_regroup", "mrt_get_auto_regroup", "mrt_read_regroup_stats",
     "mrt_denoise_mix_default", "mrt_set_denoise_mix", "mrt_get_denoise_mix", "mrt_debug_denoise_mix",
     "mrt_update_materials", "mrt_debug_material_shade",
+    "mrt_debug_hold", "mrt_debug_hold_stamps",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -69,6 +70,9 @@ TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
 DENOISE_VAR_ACCUMULATED, DENOISE_VAR_PREFILTERED, DENOISE_VAR_SPATIAL_EARLY = 0, 1, 2
 # mrt_update_materials' flag
 MATERIALS_RESTART_HISTORY = 1
+# mrt_debug_hold's streams and the most ticks (100 MHz) it takes
+HOLD_CONTEXT, HOLD_SLOT, HOLD_PRESENT, HOLD_NOISE = 0, 1, 2, 3
+HOLD_MAX_TICKS = 50_000_000
 
 
 class MrtArgs(C.Structure):
@@ -418,6 +422,8 @@ def load():
         "mrt_read_gathered_noise": (i32, [vp, vp, sz]),
         "mrt_read_gathered_denoised": (i32, [vp, vp, sz]),
         "mrt_debug_read_gathered_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
+        "mrt_debug_hold": (i32, [vp, u32, u32, u64, u32]),
+        "mrt_debug_hold_stamps": (i32, [vp, P(u64)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

@@ -616,6 +616,20 @@ class State:
         """How many frames may be in flight, each on a side stream of its own (1..8; 0 = automatic)."""
         self._check(self._L.mrt_debug_set_frames_in_flight(self._ctx, slots), "mrt_debug_set_frames_in_flight")
 
+    _HOLD_STREAMS = {"context": _lib.HOLD_CONTEXT, "slot": _lib.HOLD_SLOT, "present": _lib.HOLD_PRESENT, "noise": _lib.HOLD_NOISE}
+
+    def debug_hold(self, which: str, index: int = 0, ticks: int = 1_000_000, max_polls: int = 1 << 20):
+        """mrt_debug_hold: one kernel on the "context" stream, the side stream of frame "slot" `index`, the "present" or the
+        "noise" stream that ends after `ticks` of the 100 MHz clock or `max_polls` polls, whichever comes first; what is queued
+        behind it on that stream starts late.  Creates nothing: MrtError (MRT_ERR_STATE) where the stream does not exist yet."""
+        self._check(self._L.mrt_debug_hold(self._ctx, self._HOLD_STREAMS[which], index, ticks, max_polls), "mrt_debug_hold")
+
+    def debug_hold_stamps(self):
+        """(start tick, end tick, polls given) of the most recent debug_hold, once it has ended (after sync())"""
+        out = (C.c_uint64 * 3)()
+        self._check(self._L.mrt_debug_hold_stamps(self._ctx, out), "mrt_debug_hold_stamps")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def debug_set_schedule(self, pilot_spp: int, waves_per_cu: int):
         """Before the first redraw: samples per pixel of the pilot launch, persistent waves per CU (0 = automatic)."""
         self._check(self._L.mrt_debug_set_schedule(self._ctx, pilot_spp, waves_per_cu), "mrt_debug_set_schedule")

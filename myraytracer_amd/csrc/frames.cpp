@@ -882,6 +882,30 @@ int mrt_debug_set_frames_in_flight(mrt_ctx* c, int slots) {
     return MRT_OK;
 }
 
+// diagnostic of the stream ordering: one clock- and poll-bounded single-wave kernel (launch_hold) on a stream the context HAS
+int mrt_debug_hold(mrt_ctx* c, uint32_t which, uint32_t index, uint64_t ticks, uint32_t max_polls) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    if (ticks == 0 || ticks > MRT_HOLD_MAX_TICKS || max_polls == 0 || which > MRT_HOLD_NOISE ||
+        index >= (which == MRT_HOLD_SLOT ? mrt_ctx::kMaxFrameSlots : 1u))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_hold: stream %u, index %u, %llu ticks (1..%llu), %u polls (>= 1)", which, index,
+                    (unsigned long long)ticks, (unsigned long long)MRT_HOLD_MAX_TICKS, max_polls);
+    const hipStream_t s = which == MRT_HOLD_CONTEXT ? c->stream : which == MRT_HOLD_SLOT ? c->slot[index].stream
+                          : which == MRT_HOLD_PRESENT ? c->present_stream : c->noise_stream;
+    if (!s || !c->h_stats) return fail(c, MRT_ERR_STATE, "mrt_debug_hold: stream %u (index %u) does not exist yet", which, index);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int e = mrt::launch_hold(ticks, max_polls, c->h_stats + 5 * mrt_ctx::kMaxFrameSlots - 2, s);
+    if (e) return fail(c, MRT_ERR_HIP, "mrt_debug_hold: launch failed: %s", hipGetErrorString((hipError_t)e));
+    c->hold_polls = max_polls;
+    return MRT_OK;
+}
+
+int mrt_debug_hold_stamps(mrt_ctx* c, uint64_t out[3]) {
+    if (!c || !out || !c->h_stats) return MRT_ERR_INVALID_ARG;
+    const unsigned long long* const stamps = c->h_stats + 5 * mrt_ctx::kMaxFrameSlots - 2;
+    out[0] = c->hold_polls ? stamps[0] : 0; out[1] = c->hold_polls ? stamps[1] : 0; out[2] = c->hold_polls;
+    return MRT_OK;
+}
+
 // n_t per tile (frames_done everywhere while the accumulation is uniform); synchronises as mrt_read_framebuffer does
 int mrt_read_tile_frames(mrt_ctx* c, uint32_t* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows) {
     if (!c) return MRT_ERR_INVALID_ARG;

@@ -176,6 +176,7 @@ struct mrt_ctx {
     std::chrono::steady_clock::time_point width_t0;
     struct LaneStat { uint64_t seq = 0, hits = 0, slots = 0; bool valid = false; } stat_base, stat_last;
     unsigned long long* h_stats = nullptr;          // pinned, 3 x kMaxFrameSlots (+ 2 x kMaxFrameSlots: the concurrency probe's stamps)
+    uint32_t hold_polls = 0;                        // mrt_debug_hold: the polls its most recent kernel was given (its stamps: the probe's last pair)
     hipEvent_t ev_inputs = nullptr;            // scene / seeds uploads on the caller's stream
     bool inputs_dirty = true;
     uint64_t frame_seq = 0;

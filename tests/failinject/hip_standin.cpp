@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 static unsigned long long g_counts[4];      // creations, releases, copies, memsets
+static unsigned long long g_waits;          // stream waits
 
 extern "C" {
 void standin_counts(unsigned long long out[4]) { for (int i = 0; i < 4; i++) out[i] = g_counts[i]; }
@@ -27,4 +28,6 @@ hipError_t hipMemcpyPeerAsync(void*, int, const void*, int, size_t, hipStream_t)
 hipError_t hipMemset(void*, int, size_t) { g_counts[3]++; return hipSuccess; }
 hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { g_counts[3]++; return hipSuccess; }
 hipError_t hipMemsetD32Async(hipDeviceptr_t, int, size_t, hipStream_t) { g_counts[3]++; return hipSuccess; }
+unsigned long long standin_waits(void) { return g_waits; }
+hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t e, unsigned) { g_waits++; return e ? hipSuccess : hipErrorInvalidHandle; }
 }

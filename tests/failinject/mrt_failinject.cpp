@@ -1,5 +1,5 @@
 // The failure-injection shim behind mrt_failinject.h: counts the library's creator calls and refuses the armed one without
-// calling the runtime, keeps the live device / pinned allocations, streams and events, withholds releases of what is not live
+// calling the runtime, counts its stream waits and drops the chosen one, keeps the live device / pinned allocations, streams and events, withholds releases of what is not live
 // and copies / memsets that leave the live device allocations, and reports all of it to the tests.  Host code only; the one
 // thing it needs from HIP are the functions it forwards to (tests/test_failinject_shim.py links it against a stand-in).
 #define MRT_FAILINJECT_SHIM
@@ -25,6 +25,10 @@ struct Shim {
     std::vector<std::string> violations;
     std::map<uintptr_t, size_t> device;          // base -> bytes
     std::set<uintptr_t> pinned, streams, events;
+    uint64_t waits = 0, skip = 0;                // the stream waits, counted apart: the skip-th is dropped
+    bool skipped = false;
+    std::string skipped_site;
+    std::set<std::string> wait_sites;
 };
 Shim& shim() { static Shim s; return s; }
 
@@ -241,6 +245,51 @@ hipError_t mrt_fi_memset_d32_async(const char* file, int line, hipDeviceptr_t ds
     return hipMemsetD32Async(dst, value, count, stream);
 }
 
+hipError_t mrt_fi_stream_wait_event(const char* file, int line, hipStream_t stream, hipEvent_t event, unsigned flags) {
+    Shim& s = shim();
+    {
+        std::lock_guard<std::mutex> g(s.mu);
+        const std::string site = site_of(file, line, "hipStreamWaitEvent");
+        s.wait_sites.insert(site);
+        s.waits++;
+        if (s.skip != 0 && s.waits == s.skip) {      // dropped: the caller sees success, the runtime sees nothing
+            s.skip = 0;
+            s.skipped = true;
+            s.skipped_site = site;
+            return hipSuccess;
+        }
+    }
+    return hipStreamWaitEvent(stream, event, flags);
+}
+
+void mrt_fi_skip_wait(uint64_t n) {
+    Shim& s = shim();
+    std::lock_guard<std::mutex> g(s.mu);
+    s.skip = n; s.waits = 0; s.skipped = false; s.skipped_site.clear();
+}
+
+uint64_t mrt_fi_waits(void) {
+    Shim& s = shim();
+    std::lock_guard<std::mutex> g(s.mu);
+    return s.waits;
+}
+
+int mrt_fi_skipped(char* site, size_t cap) {
+    Shim& s = shim();
+    std::lock_guard<std::mutex> g(s.mu);
+    if (site && cap) std::snprintf(site, cap, "%s", s.skipped ? s.skipped_site.c_str() : "");
+    return s.skipped ? 1 : 0;
+}
+
+size_t mrt_fi_wait_sites(char* buf, size_t cap) {
+    Shim& s = shim();
+    std::lock_guard<std::mutex> g(s.mu);
+    std::string all;
+    for (const auto& x : s.wait_sites) all += x + "\n";
+    if (buf && cap) std::snprintf(buf, cap, "%s", all.c_str());
+    return all.size() + 1;
+}
+
 void mrt_fi_arm(uint64_t n) {
     Shim& s = shim();
     std::lock_guard<std::mutex> g(s.mu);
@@ -295,6 +344,8 @@ void mrt_fi_reset(void) {
     std::lock_guard<std::mutex> g(s.mu);
     s.sites.clear(); s.violations.clear();
     s.calls = 0; s.armed = 0; s.fired = false; s.fired_site.clear();
+    s.wait_sites.clear();
+    s.waits = 0; s.skip = 0; s.skipped = false; s.skipped_site.clear();
 }
 
 }  // extern "C"

@@ -24,7 +24,11 @@ WALKS = os.path.join(ROOT, "tests", "failure_walks.py")
 HOST_FILES = ("api.cpp", "frames.cpp", "world.cpp", "noise.cpp", "present.cpp", "denoise.cpp", "multi_gpu.cpp", "hierarchy.cpp",
               "scenes.cpp", "image_io.cpp", "mrt_ctx.h", "mrt_internal.h", "hierarchy.h", "bounds.h", "width_policy.h")
 CREATORS = ("hipMalloc", "hipHostMalloc", "hipStreamCreate", "hipStreamCreateWithFlags", "hipEventCreate", "hipEventCreateWithFlags")
-_CALL = re.compile(r"\b(" + "|".join(sorted(CREATORS, key=len, reverse=True)) + r")\s*\(")
+WAITS = ("hipStreamWaitEvent",)       # the stream waits (tests/order_walks.py, tests/test_stream_wait_sites.py)
+
+
+def _call(names):
+    return re.compile(r"\b(" + "|".join(sorted(names, key=len, reverse=True)) + r")\s*\(")
 
 
 def _code(line):
@@ -32,15 +36,17 @@ def _code(line):
     return line.split("//", 1)[0].strip()
 
 
-def source_sites(csrc=CSRC, files=HOST_FILES):
-    """{(file, line number): key} for every creator call in the host files; a line with two calls is one site."""
+def source_sites(csrc=CSRC, files=HOST_FILES, calls=CREATORS):
+    """{(file, line number): key} for every call of one of `calls` (the creators) in the host files; a line with two calls is
+    one site."""
     sites = {}
+    call = _call(calls)
     for name in files:
         seen = {}
         with open(os.path.join(csrc, name)) as f:
             for no, line in enumerate(f, 1):
                 code = _code(line)
-                if code.startswith("#define") or not _CALL.search(code):
+                if code.startswith("#define") or not call.search(code):
                     continue
                 k = seen[code] = seen.get(code, 0) + 1
                 sites[(name, no)] = f"{name} | {code} | {k}"

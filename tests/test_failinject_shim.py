@@ -32,7 +32,9 @@ def shim(tmp_path_factory):
             ("mrt_fi_memset_d32_async", i, [cs, i, vp, i, sz, vp]),
             ("mrt_fi_arm", None, [u64]), ("mrt_fi_disarm", None, []), ("mrt_fi_calls", u64, []), ("mrt_fi_fired", i, [cs, sz]),
             ("mrt_fi_sites", sz, [cs, sz]), ("mrt_fi_live", None, [C.POINTER(u64)]), ("mrt_fi_violations", sz, [cs, sz]),
-            ("mrt_fi_reset", None, []), ("standin_counts", None, [C.POINTER(C.c_ulonglong)])):
+            ("mrt_fi_reset", None, []), ("standin_counts", None, [C.POINTER(C.c_ulonglong)]),
+            ("mrt_fi_stream_wait_event", i, [cs, i, vp, vp, C.c_uint]), ("mrt_fi_skip_wait", None, [u64]), ("mrt_fi_waits", u64, []),
+            ("mrt_fi_skipped", i, [cs, sz]), ("mrt_fi_wait_sites", sz, [cs, sz]), ("standin_waits", C.c_ulonglong, [])):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     return L
@@ -138,3 +140,46 @@ def test_copies_and_memsets_outside_the_live_device_allocations_are_withheld(shi
     assert L.mrt_fi_memset_async(F, 51, p, 0, 1, None) == INVALID, "a stale pointer"
     assert L.mrt_fi_memcpy_async(F, 52, p, h, 0, H2D, None) == SUCCESS, "nothing to copy touches nothing"
     L.mrt_fi_reset()
+
+
+def test_the_chosen_stream_wait_is_dropped_without_reaching_the_runtime(shim):
+    L = shim
+    L.mrt_fi_reset()
+    s, e = C.c_void_p(), C.c_void_p()
+    assert L.mrt_fi_stream_create(F, 10, C.byref(s), 1, 1) == SUCCESS and L.mrt_fi_event_create(F, 11, C.byref(e), 1, 2) == SUCCESS
+    site = C.create_string_buffer(64)
+    reached_before = L.standin_waits()
+    # counting only: every wait is forwarded, with the runtime's own result
+    assert L.mrt_fi_stream_wait_event(F, 20, s, e, 0) == SUCCESS and L.mrt_fi_stream_wait_event(F, 21, s, e, 0) == SUCCESS
+    assert L.mrt_fi_stream_wait_event(F, 22, s, None, 0) != SUCCESS, "the runtime's refusal comes back as it is"
+    assert L.mrt_fi_waits() == 3 and L.standin_waits() == reached_before + 3 and L.mrt_fi_skipped(site, len(site)) == 0
+    # the second from now on is dropped: success, and the runtime has not seen it -- not even one it would have refused
+    L.mrt_fi_skip_wait(2)
+    assert L.mrt_fi_waits() == 0, "the count restarts"
+    assert L.mrt_fi_stream_wait_event(F, 20, s, e, 0) == SUCCESS and L.mrt_fi_skipped(site, len(site)) == 0
+    assert L.mrt_fi_stream_wait_event(F, 22, s, None, 0) == SUCCESS
+    assert L.mrt_fi_skipped(site, len(site)) == 1 and site.value == b"api.cpp:22 hipStreamWaitEvent"
+    assert L.standin_waits() == reached_before + 4, "the dropped wait must not reach the runtime"
+    assert L.mrt_fi_stream_wait_event(F, 21, s, e, 0) == SUCCESS and L.standin_waits() == reached_before + 5, "one shot"
+    assert L.mrt_fi_waits() == 3
+    buf = C.create_string_buffer(L.mrt_fi_wait_sites(None, 0))
+    L.mrt_fi_wait_sites(buf, len(buf))
+    assert buf.value.decode().split("\n")[:-1] == [f"api.cpp:{n} hipStreamWaitEvent" for n in (20, 21, 22)]
+    # the waits and the creators are counted apart, and neither arms the other
+    assert L.mrt_fi_calls() == 2 and L.mrt_fi_fired(None, 0) == 0
+    creators = C.create_string_buffer(L.mrt_fi_sites(None, 0))
+    L.mrt_fi_sites(creators, len(creators))
+    assert b"hipStreamWaitEvent" not in creators.value
+    L.mrt_fi_skip_wait(1)
+    p = C.c_void_p()
+    assert L.mrt_fi_malloc(F, 30, C.byref(p), 16) == SUCCESS and L.mrt_fi_skipped(None, 0) == 0
+    L.mrt_fi_arm(1)
+    assert L.mrt_fi_stream_wait_event(F, 20, s, e, 0) == SUCCESS and L.mrt_fi_skipped(None, 0) == 1 and L.mrt_fi_fired(None, 0) == 0
+    L.mrt_fi_disarm()
+    # reset forgets the waits too
+    L.mrt_fi_skip_wait(1)
+    L.mrt_fi_reset()
+    assert L.mrt_fi_waits() == 0 and L.mrt_fi_wait_sites(None, 0) == 1 and L.mrt_fi_skipped(None, 0) == 0
+    assert L.mrt_fi_stream_wait_event(F, 20, s, e, 0) == SUCCESS and L.mrt_fi_skipped(None, 0) == 0, "reset cancels a pending drop"
+    assert L.mrt_fi_free(F, 40, p) == SUCCESS and L.mrt_fi_stream_destroy(F, 41, s) == SUCCESS and L.mrt_fi_event_destroy(F, 42, e) == SUCCESS
+    assert violations(L)[0] == 0
