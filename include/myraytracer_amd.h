@@ -48,7 +48,9 @@ extern "C" {
  * an adaptive accumulation (mrt_set_denoise_adaptive, mrt_get_denoise_adaptive); the auto-regroup policy (mrt_auto_regroup,
  * mrt_auto_regroup_default, mrt_set_auto_regroup, mrt_get_auto_regroup, mrt_regroup_stats, mrt_read_regroup_stats); the
  * denoiser's blend with the accumulation (mrt_denoise_mix, mrt_denoise_mix_default, mrt_set_denoise_mix, mrt_get_denoise_mix);
- * material edits without a rebuild (mrt_material, mrt_update_materials, MRT_MATERIALS_RESTART_HISTORY). */
+ * material edits without a rebuild (mrt_material, mrt_update_materials, MRT_MATERIALS_RESTART_HISTORY); adaptive sampling by
+ * budget (MRT_TILE_MAP_MAX_REL, MRT_TILE_MAP_SUM_S, mrt_noise_query_map, mrt_budget_result, mrt_budget_allocate,
+ * mrt_render_budget; mrt_noise_report::reserved carries the report's map kind). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -501,7 +503,7 @@ int mrt_set_present_ring(mrt_ctx* ctx, uint32_t depth);
 typedef struct {                 /* 96 bytes */
     uint64_t seq;                /* the query's number on this ctx: 1, 2, ...; 0 = no report */
     uint32_t frames_done;        /* mrt_frames_done at the query: the accumulation the report describes */
-    uint32_t reserved;
+    uint32_t reserved;           /* the kind of this report's tile map (mrt_noise_query_map): 0 for mrt_noise_query's */
     uint64_t pixels;             /* finite pixels (image rows of this ctx; shard padding excluded) */
     uint64_t non_finite;         /* pixels whose S or luminance is NaN / Inf (in nothing else) */
     uint64_t above;              /* finite pixels with rel > threshold */
@@ -523,14 +525,27 @@ int mrt_set_noise_tracking(mrt_ctx* ctx, int enabled);
  * flight the call waits for it (bounded, mrt_set_wait_timeout).  rel_threshold, rel_floor: finite, rel_floor >= 0.
  * MRT_ERR_STATE if tracking is off.  Must not be called while the ctx's stream is being captured into a graph. */
 int mrt_noise_query(mrt_ctx* ctx, float rel_threshold, float rel_floor);
+/* mrt_noise_query with the kind of tile map the report's ring entry gets.  MRT_TILE_MAP_MAX_REL is mrt_noise_query exactly: the
+ * same launches, the same bits.  MRT_TILE_MAP_SUM_S differs in one way only: every scalar field of the report is bit for bit
+ * what kind 0 gives on the same state (uniform or per-tile, a shard, K = +inf), and the map entry of tile t is (float)s_t, s_t the
+ * tile's summed S in double: a pixel counts if it is inside the image (shard padding rows excluded) and its S and
+ * lum(framebuffer) are finite -- the report's own rule -- and contributes (double)S_p, any other pixel +0.0; per tile row the
+ * eight columns are added as ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), then the eight row sums one after the other
+ * from the tile's bottom row, starting at 0.0.  No K and no n_t enter it: s_t * K(n_t) is the tile's summed variance in a
+ * uniform and in an adaptive accumulation alike (mrt_budget_allocate).  The report's `reserved` field holds map_kind.  Any other
+ * map_kind: MRT_ERR_INVALID_ARG; everything else as mrt_noise_query. */
+enum { MRT_TILE_MAP_MAX_REL = 0, MRT_TILE_MAP_SUM_S = 1 };
+int mrt_noise_query_map(mrt_ctx* ctx, float rel_threshold, float rel_floor, uint32_t map_kind);
 /* The newest finished report.  wait == 0: out->seq == 0 when none has finished; wait != 0: polls (bounded) for the newest
  * queued report first.  Never waits for frames queued after that query.  out->seq == 0 before the first query. */
 int mrt_noise_result(mrt_ctx* ctx, int wait, mrt_noise_report* out);
 /* S in mrt_read_framebuffer's texel order (world 1: height rows of width; a shard: its packed local rows), one float per
  * texel; synchronises as mrt_read_framebuffer does.  MRT_ERR_STATE if tracking is off. */
 int mrt_read_noise(mrt_ctx* ctx, float* out, size_t cap);
-/* The per-8x8-tile maximum of rel of the latest queued query, tiles_rows rows of tiles_x (tile = band x tiles_x + column, a
- * shard's packed bands); waits for that query only.  MRT_ERR_STATE before the first query. */
+/* The tile map of the latest queued query, whatever its kind -- the per-8x8-tile maximum of rel (mrt_noise_query,
+ * MRT_TILE_MAP_MAX_REL) or the tile's summed S (MRT_TILE_MAP_SUM_S; that query's report names the kind in `reserved`) -- as
+ * tiles_rows rows of tiles_x (tile = band x tiles_x + column, a shard's packed bands); waits for that query only.
+ * MRT_ERR_STATE before the first query. */
 int mrt_read_noise_tiles(mrt_ctx* ctx, float* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
 /* Host only: K after frames_done uninterrupted frames with the weights of mrt_frame_weight (+inf for frames_done < 2). */
 double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
@@ -560,14 +575,69 @@ double mrt_noise_factor(uint32_t frames_done, float max_framebuffer_weight);
  * A list of every tile renders whole frames: while the accumulation is uniform, exactly mrt_render's. */
 int mrt_render_tiles(mrt_ctx* ctx, const uint32_t* tiles, size_t n, uint32_t frames);
 /* Selects the tiles whose tile-map entry in one noise report is > that report's threshold (the tiles holding a pixel counted in
- * its `above`) and renders `frames` subset frames over them (mrt_render_tiles).  report_seq == 0: the newest finished report,
+ * its `above`) and renders `frames` subset frames over them (mrt_render_tiles).  report_seq == 0: the newest finished report
+ * whose map holds the maximum of rel (MRT_TILE_MAP_MAX_REL: reports of mrt_noise_query_map's other kind are passed over),
  * without waiting (none finished: every tile); report_seq == k: report k, waiting (bounded) for that query only.  A report not
- * queued, or older than the ring of 8: MRT_ERR_STATE; tracking off: MRT_ERR_STATE.  *used_seq = the report used (0: none),
+ * queued, older than the ring of 8, or of the kind MRT_TILE_MAP_SUM_S: MRT_ERR_STATE; tracking off: MRT_ERR_STATE.  *used_seq = the report used (0: none),
  * *tiles_selected = the selection's size (either may be NULL).  No tile selected: MRT_OK and nothing queued (converged). */
 int mrt_render_adaptive(mrt_ctx* ctx, uint32_t frames, uint64_t report_seq, uint64_t* used_seq, uint32_t* tiles_selected);
 /* n_t per tile, tiles_rows rows of tiles_x (frames_done everywhere while the accumulation is uniform); synchronises as
  * mrt_read_framebuffer does. */
 int mrt_read_tile_frames(mrt_ctx* ctx, uint32_t* out, size_t cap, uint32_t* tiles_x, uint32_t* tiles_rows);
+
+/* ---- adaptive sampling by budget: a fixed number of tile-frames, spent where they lower the estimated variance most ----
+ * Model: a tile with n frames shows the summed variance s_t * K(n), s_t its entry in a MRT_TILE_MAP_SUM_S map and K(n) =
+ * mrt_noise_factor(n, max_framebuffer_weight) in double.  One tile-frame is one subset frame over one tile.
+ *
+ * mrt_budget_allocate (host only) gives tile t k_t of at most `budget` tile-frames, k_t <= max_frames:
+ *   s'_t = s[t], a NaN or a negative value read as 0.  Candidate (t, j), j = 0 .. max_frames - 1, is tile t's j-th extra frame.
+ *   Mandatory frames come first and cost 1 each: a tile with n[t] < 2 (K = +inf: no estimate yet) gets m_t = min(2 - n[t],
+ *     max_frames) of them (m_t = 0 for the others), served in the order j ascending, then t ascending, until the budget ends.
+ *   Gains, for a tile with n[t] + m_t >= 2 and j >= m_t:  g(t, j) = s'_t * (K(n[t] + j) - K(n[t] + j + 1)) -- one difference, one
+ *     product, in double -- and g'(t, j) = the minimum of g(t, i) over m_t <= i <= j, which never increases with j.  Only
+ *     candidates with g' > 0 and a finite s'_t count.
+ *   Selection: what is left of the budget takes that many candidates in the order g' descending, then j ascending, then t
+ *     ascending (all of them if there are fewer).  k_t = the candidates of tile t taken, its mandatory frames included: a prefix
+ *     in j by construction.
+ *   Result: tile_frames = the sum of k_t; tiles = the tiles with k_t > 0; frames = the largest k_t; var_before = the sum of
+ *     s'_t * K(n[t]) and var_after = the sum of s'_t * K(n[t] + k_t), both over the tiles with n[t] >= 2 (K finite before and
+ *     after), t ascending, in double; size = sizeof(mrt_budget_result); used_seq and the reserved words 0.
+ *   tiles >= 1, max_frames 1 .. 32, every n[t] <= 2^24, max_framebuffer_weight finite and > 0; s, n,
+ *   k_out or res NULL or a value outside these: MRT_ERR_INVALID_ARG with nothing written.  The sums are over the tiles as given:
+ *   the caller's maps need not be a context's.
+ *
+ * mrt_render_budget allocates from one MRT_TILE_MAP_SUM_S report and renders the allocation through mrt_render_tiles.
+ *   The report: mrt_render_adaptive's rule over the reports of that kind.  report_seq == 0: the newest finished one, without
+ *     waiting; none: MRT_OK, nothing queued, res->used_seq 0.  report_seq == k: report k, waiting (bounded) for that query only;
+ *     a report not queued, older than the ring of 8, or of the kind MRT_TILE_MAP_MAX_REL: MRT_ERR_STATE.  Tracking off:
+ *     MRT_ERR_STATE.
+ *   The allocation: mrt_budget_allocate(s = that report's map, n = the host's current n_t -- mrt_frames_done everywhere while
+ *     the accumulation is uniform --, the ctx's max_framebuffer_weight, budget, max_frames).  The map is as old as its report:
+ *     frames queued since the query are in n but not in s.
+ *   The frames: L_j = {t : k_t >= j} in ascending tile id, j = 1 .. the largest k_t; consecutive j with the same list are one
+ *     mrt_render_tiles(L_j, run length) call, so that those frames share a launch.  A list of every tile renders whole frames
+ *     (mrt_render_tiles' rule): a budget that gives every tile the same count leaves a uniform accumulation uniform.  The
+ *     framebuffer, S, n_t, mrt_frames_done and the counters are exactly those of that sequence of mrt_render_tiles calls.
+ *   Every refusal of mrt_render_tiles applies and is returned before anything is queued: a shard (MRT_ERR_STATE), no scene
+ *     (MRT_ERR_NO_SCENE), counter-RNG mode above MRT_COUNTER_BLOCK samples per frame (MRT_ERR_INVALID_ARG).  max_frames outside
+ *     1 .. 32: MRT_ERR_INVALID_ARG.  budget == 0, or no candidate with a gain and no mandatory frame: MRT_OK, nothing queued.
+ *   *res (may be NULL) = the allocation's result with used_seq = the report used; k_out (may be NULL; cap >= the tile count,
+ *     else MRT_ERR_TOO_SMALL) = k_t per tile.  The call creates nothing of its own: the report's map is read back as
+ *     mrt_render_adaptive reads it. */
+typedef struct {
+    uint32_t size;               /* sizeof(mrt_budget_result), written by the library */
+    uint32_t frames;             /* the largest k_t: the subset frames the allocation takes */
+    uint32_t tiles;              /* tiles with k_t > 0 */
+    uint32_t reserved0;          /* 0 */
+    uint64_t tile_frames;        /* the sum of k_t (<= budget) */
+    uint64_t used_seq;           /* mrt_render_budget: the report used (0: none); mrt_budget_allocate: 0 */
+    double var_before, var_after;
+    uint32_t reserved[4];        /* 0 */
+} mrt_budget_result;             /* sizeof 64 */
+int mrt_budget_allocate(const float* s, const uint32_t* n, size_t tiles, float max_framebuffer_weight, uint64_t budget,
+                        uint32_t max_frames, uint32_t* k_out, mrt_budget_result* res);
+int mrt_render_budget(mrt_ctx* ctx, uint64_t budget, uint32_t max_frames, uint64_t report_seq, mrt_budget_result* res,
+                      uint32_t* k_out, size_t cap);
 
 /* ------------------------------------------------------------------ denoiser (no reference counterpart)
  *

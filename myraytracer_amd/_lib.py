@@ -58,6 +58,7 @@ EXPORTS = [
     "mrt_denoise_mix_default", "mrt_set_denoise_mix", "mrt_get_denoise_mix", "mrt_debug_denoise_mix",
     "mrt_update_materials", "mrt_debug_material_shade",
     "mrt_debug_hold", "mrt_debug_hold_stamps",
+    "mrt_noise_query_map", "mrt_budget_allocate", "mrt_render_budget",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -68,6 +69,9 @@ ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
 # the denoiser's variance modes (mrt_set_denoise_variance)
 DENOISE_VAR_ACCUMULATED, DENOISE_VAR_PREFILTERED, DENOISE_VAR_SPATIAL_EARLY = 0, 1, 2
+# the kinds of tile map a noise query leaves (mrt_noise_query_map)
+TILE_MAP_MAX_REL, TILE_MAP_SUM_S = 0, 1
+TILE_MAP_KINDS = ("max_rel", "sum_s")
 # mrt_update_materials' flag
 MATERIALS_RESTART_HISTORY = 1
 # mrt_debug_hold's streams and the most ticks (100 MHz) it takes
@@ -121,6 +125,12 @@ class MrtNoiseReport(C.Structure):
                 ("non_finite", C.c_uint64), ("above", C.c_uint64), ("threshold", C.c_float), ("floor", C.c_float),
                 ("noise_factor", C.c_double), ("sum_var", C.c_double), ("sum_lum", C.c_double), ("rmse", C.c_double),
                 ("rel_rmse", C.c_double), ("max_se", C.c_float), ("reserved2", C.c_uint32)]
+
+
+class MrtBudgetResult(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("frames", C.c_uint32), ("tiles", C.c_uint32), ("reserved0", C.c_uint32),
+                ("tile_frames", C.c_uint64), ("used_seq", C.c_uint64), ("var_before", C.c_double), ("var_after", C.c_double),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class MrtDenoiseParams(C.Structure):
@@ -377,6 +387,9 @@ def load():
         "mrt_debug_set_present_copy": (i32, [vp, i32]),
         "mrt_set_noise_tracking": (i32, [vp, i32]),
         "mrt_noise_query": (i32, [vp, f32, f32]),
+        "mrt_noise_query_map": (i32, [vp, f32, f32, u32]),
+        "mrt_budget_allocate": (i32, [vp, vp, sz, f32, C.c_uint64, u32, vp, P(MrtBudgetResult)]),
+        "mrt_render_budget": (i32, [vp, C.c_uint64, u32, C.c_uint64, P(MrtBudgetResult), vp, sz]),
         "mrt_noise_result": (i32, [vp, i32, P(MrtNoiseReport)]),
         "mrt_read_noise": (i32, [vp, vp, sz]),
         "mrt_read_noise_tiles": (i32, [vp, vp, sz, P(u32), P(u32)]),

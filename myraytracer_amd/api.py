@@ -803,10 +803,17 @@ class State:
         """Turn noise tracking on / off; only while frames_done == 0 (after creation or reset()).  Survives reset()."""
         self._check(self._L.mrt_set_noise_tracking(self._ctx, int(enabled)), "mrt_set_noise_tracking")
 
-    def noise_query(self, threshold: float = 0.02, floor: float = 0.01):
+    def noise_query(self, threshold: float = 0.02, floor: float = 0.01, tile_map: str = "max_rel"):
         """Queue the noise report of the most recent frame (asynchronous).  threshold: the relative standard error above which a
-        pixel counts as noisy; floor: the luminance below which the relative error is taken against the floor instead."""
-        self._check(self._L.mrt_noise_query(self._ctx, threshold, floor), "mrt_noise_query")
+        pixel counts as noisy; floor: the luminance below which the relative error is taken against the floor instead.
+        tile_map: what the report's tile map holds -- "max_rel", the tile's largest relative error (render_adaptive selects from
+        it), or "sum_s", the tile's summed S (render_budget allocates from it); the report's scalar fields are the same."""
+        if tile_map not in _lib.TILE_MAP_KINDS:
+            raise ValueError(f"noise_query: unknown tile_map {tile_map!r} ({', '.join(_lib.TILE_MAP_KINDS)})")
+        if tile_map == "max_rel":
+            self._check(self._L.mrt_noise_query(self._ctx, threshold, floor), "mrt_noise_query")
+        else:
+            self._check(self._L.mrt_noise_query_map(self._ctx, threshold, floor, _lib.TILE_MAP_KINDS.index(tile_map)), "mrt_noise_query_map")
 
     def noise_result(self, wait: bool = True) -> Optional[dict]:
         """The newest finished report as a dict, or None if none has finished (wait=False) or none was queued.  wait=True waits
@@ -824,8 +831,9 @@ class State:
         return out
 
     def read_noise_tiles(self) -> np.ndarray:
-        """The latest query's per-8x8-tile maximum of the relative error: (tile rows, tiles_x) f32, numbered as the framebuffer's
-        bands (a shard's packed bands).  Waits for that query only."""
+        """The latest query's tile map -- the per-8x8-tile maximum of the relative error, or the tile's summed S after
+        noise_query(tile_map="sum_s") --: (tile rows, tiles_x) f32, numbered as the framebuffer's bands (a shard's packed bands).
+        Waits for that query only."""
         tx, tr = C.c_uint32(), C.c_uint32()
         self._L.mrt_read_noise_tiles(self._ctx, None, 0, C.byref(tx), C.byref(tr))     # (the shape; the status comes below)
         out = np.empty((tr.value, tx.value), np.float32)
@@ -834,7 +842,7 @@ class State:
         return out
 
     def render_until(self, target_rel_rmse: float, max_frames: int, check_every: int = 16, threshold: float = 0.02,
-                     floor: float = 0.01, adaptive: bool = False) -> Tuple[int, dict]:
+                     floor: float = 0.01, adaptive: bool = False, budget: Optional[int] = None) -> Tuple[int, dict]:
         """Render chunks of check_every frames until a noise report's rel_rmse <= target_rel_rmse or frames_done reaches
         max_frames; returns (frames_done, report).  Keeps the pipeline full by lagging one check: chunk k + 1 is queued before
         report k is waited for, so the stop overshoots the first report that meets the target by at most check_every frames
@@ -844,25 +852,37 @@ class State:
 
         adaptive=True: every chunk after the first is render_adaptive over the tiles that the report queued one chunk
         earlier counts as noisy (that report has been waited for already, so a chunk stays in flight), and the loop also
-        stops at a report with above == 0 (no tile left above `threshold`).  frames_done counts subset frames as frames."""
+        stops at a report with above == 0 (no tile left above `threshold`).  frames_done counts subset frames as frames.
+
+        budget=N (not with adaptive=True): every chunk after the first is render_budget(N, min(check_every, 32), report): N
+        tile-frames allocated from the summed-S map of the report queued one chunk earlier -- the same lag -- so the queries
+        are noise_query(tile_map="sum_s").  The loop also stops when a chunk finds nothing worth a frame."""
         if check_every < 1 or max_frames < 0:
             raise ValueError("render_until: check_every >= 1, max_frames >= 0")
+        if budget is not None and (adaptive or budget < 1):
+            raise ValueError("render_until: budget >= 1, and not together with adaptive=True")
         if self.frames_done == 0:
             self.set_noise_tracking(True)
+        tile_map = "max_rel" if budget is None else "sum_s"
 
         def chunk(select_from=None):
+            """whether the chunk had anything to queue"""
             n = min(check_every, max_frames - self.frames_done)
             if n > 0:
                 if select_from is None:
                     self.render(n)
+                elif budget is not None:
+                    return self.render_budget(budget, min(n, 32), select_from)["tile_frames"] != 0
                 else:
                     self.render_adaptive(n, select_from)
+            return True
 
         chunk()
-        self.noise_query(threshold, floor)
-        earlier = None                                     # adaptive: the report one chunk before the newest
+        self.noise_query(threshold, floor, tile_map)
+        earlier = None                                     # adaptive, budget: the report one chunk before the newest
         while True:
-            chunk(earlier["seq"] if adaptive and earlier is not None else None)   # the lagged chunk
+            lagged = adaptive or budget is not None
+            spent = chunk(earlier["seq"] if lagged and earlier is not None else None)   # the lagged chunk
             rep = self.noise_result(wait=True)             # the newest queued: the check before that chunk
             if rep["rel_rmse"] <= target_rel_rmse:
                 return self.frames_done, rep
@@ -870,8 +890,10 @@ class State:
                 return self.frames_done, rep
             if adaptive and rep["above"] == 0:
                 return self.frames_done, rep
+            if not spent:
+                return self.frames_done, rep
             earlier = rep
-            self.noise_query(threshold, floor)
+            self.noise_query(threshold, floor, tile_map)
 
     # -- adaptive sampling (include/myraytracer_amd.h, "adaptive sampling"): frames over a list of 8x8 tiles, each tile blended
     #    at its own frame count
@@ -887,6 +909,36 @@ class State:
         used, sel = C.c_uint64(), C.c_uint32()
         self._check(self._L.mrt_render_adaptive(self._ctx, frames, report_seq, C.byref(used), C.byref(sel)), "mrt_render_adaptive")
         return int(used.value), int(sel.value)
+
+    def render_budget(self, budget: int, max_frames: int = 8, report_seq: int = 0) -> dict:
+        """Spend `budget` tile-frames (one subset frame over one 8x8 tile each) where the model s_t * K(n_t) says they lower the
+        image's summed variance most, at most max_frames (1 .. 32) per tile: allocated from the summed-S map of noise report
+        `report_seq` (0: the newest finished report queued with tile_map="sum_s"; none: nothing is queued and used_seq is 0) and
+        rendered level by level through render_tiles.  Returns {used_seq, tile_frames, tiles, frames, var_before, var_after, k}
+        with k the frames given to every tile, (tile rows, tiles_x) uint32."""
+        r = _lib.MrtBudgetResult()
+        tx, tr = C.c_uint32(), C.c_uint32()
+        self._L.mrt_read_tile_frames(self._ctx, None, 0, C.byref(tx), C.byref(tr))     # (the shape)
+        k = np.zeros((tr.value, tx.value), np.uint32)
+        self._check(self._L.mrt_render_budget(self._ctx, budget, max_frames, report_seq, C.byref(r), k.ctypes.data, k.size),
+                    "mrt_render_budget")
+        return dict(budget_result_dict(r), k=k)
+
+    @staticmethod
+    def budget_allocate(s, n, max_framebuffer_weight: float, budget: int, max_frames: int = 8) -> Tuple[np.ndarray, dict]:
+        """mrt_budget_allocate (host only): (k, result) for the summed-S map `s` and the frame counts `n` of the same shape; k
+        has that shape too."""
+        s = np.ascontiguousarray(s, np.float32)
+        n = np.ascontiguousarray(n, np.uint32)
+        if s.shape != n.shape:
+            raise ValueError("budget_allocate: s and n differ in shape")
+        k = np.zeros(s.shape, np.uint32)
+        r = _lib.MrtBudgetResult()
+        st = _lib.load().mrt_budget_allocate(s.ctypes.data, n.ctypes.data, s.size, max_framebuffer_weight, budget, max_frames,
+                                             k.ctypes.data, C.byref(r))
+        if st != 0:
+            raise MrtError(st, "mrt_budget_allocate", "")
+        return k, budget_result_dict(r)
 
     def tile_frames(self) -> np.ndarray:
         """Every tile's frame count n_t: (tile rows, tiles_x) uint32.  Waits for the frames in flight, as read_framebuffer does."""
@@ -1186,6 +1238,12 @@ def noise_report_dict(r) -> dict:
         d[k] = int(d[k])
     for k in ("threshold", "floor", "noise_factor", "sum_var", "sum_lum", "rmse", "rel_rmse", "max_se"):
         d[k] = float(d[k])
+    return d
+
+
+def budget_result_dict(r) -> dict:
+    d = {k: int(getattr(r, k)) for k in ("used_seq", "tile_frames", "tiles", "frames")}
+    d.update(var_before=float(r.var_before), var_after=float(r.var_after))
     return d
 
 

@@ -224,6 +224,13 @@ int launch_noise_reduce(const float* S, const float* rgba, uint32_t width, uint3
 int launch_noise_reduce_tiles(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
                               const uint32_t* tile_frames, const float* Kf, const double* Kd, float threshold, float floor_,
                               void* partials, float* tiles, NoiseSums* out, void* stream);
+// either of the two with the other kind of tile map (mrt_noise_query_map, MRT_TILE_MAP_SUM_S): *out is bit for bit what
+// launch_noise_reduce (tile_frames null: K, rank and world count) or launch_noise_reduce_tiles (tile_frames, Kf and Kd given: K,
+// rank and world are not read) leaves, and tiles[t] = (float) of the tile's summed S, a double sum in the order the header
+// states.  One pass over the same 20 B per pixel, then noise_final_kernel.
+int launch_noise_reduce_sum(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
+                            uint32_t rank, uint32_t world, float K, const uint32_t* tile_frames, const float* Kf, const double* Kd,
+                            float threshold, float floor_, void* partials, float* tiles, NoiseSums* out, void* stream);
 
 // adaptive.hip (include/myraytracer_amd.h, "adaptive sampling"): the per-tile blend of a frame whose tiles have their own frame
 // counts.  One wave per tile of `list` (null: every tile 0 .. n - 1), in place on `fb` (and S with noise_s): w =

@@ -25,13 +25,16 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive]]\n"
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive | --budget N]]\n"
         "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]] [--denoise-mix [GAIN]]]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
         "                      check earlier finds noisy, and the loop also stops when no pixel is above rel 0.02; prints frames,\n"
         "                      samples and tiles selected per check\n"
+        "  --budget N:         with --target-noise (one GPU): every chunk after the first spends N tile-frames (one frame of one 8x8\n"
+        "                      tile each) where the summed-S map of the report one check earlier says they lower the image's\n"
+        "                      variance most, at most min(--check-every, 32) per tile (mrt_render_budget); prints each chunk's allocation\n"
         "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png); with several GPUs the\n"
         "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame; with\n"
         "                      --adaptive the per-tile filter of an adaptive accumulation is turned on (mrt_set_denoise_adaptive)\n"
@@ -52,6 +55,7 @@ int main(int argc, char** argv) {
     uint32_t hint_div = 0, hint_mult = 0, check_every = 16, denoise_var = MRT_DENOISE_VAR_ACCUMULATED, spatial_frames = 3;
     double target_noise = -1.0;
     bool adaptive = false;
+    uint64_t budget = 0;
     mrt_denoise_mix mix;
     mrt_denoise_mix_default(&mix);
     std::string scene = "default", scene_file, save_scene, out, denoise_out;
@@ -100,6 +104,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--device") device = std::atoi(v.c_str());
         else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
+        else if (a == "--budget") budget = std::strtoull(v.c_str(), nullptr, 10);
         else if (a == "--check-every") check_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (a == "--gpus") { devices.clear(); for (int d = 0; d < std::atoi(v.c_str()); d++) devices.push_back(d); }
         else if (a == "--devices") {
@@ -152,7 +157,7 @@ int main(int argc, char** argv) {
         if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
         TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
         // an adaptive run's tiles end at their own frame counts: its denoise is the per-tile filter (one GPU: checked below)
-        if (adaptive && !denoise_out.empty()) TRY(ctxs[i], mrt_set_denoise_adaptive(ctxs[i], 1));
+        if ((adaptive || budget) && !denoise_out.empty()) TRY(ctxs[i], mrt_set_denoise_adaptive(ctxs[i], 1));
         TRY(ctxs[i], mrt_set_denoise_mix(ctxs[i], &mix));
     }
     // several GPUs: the noise estimate travels with the gather, and the first GPU denoises the gathered frame
@@ -160,6 +165,7 @@ int main(int argc, char** argv) {
     if (mix.enabled && denoise_out.empty()) { std::fprintf(stderr, "--denoise-mix wants --denoise-out\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
+    if (budget && (adaptive || target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--budget wants --target-noise and one GPU, and not --adaptive\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
         if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));
@@ -184,10 +190,14 @@ int main(int argc, char** argv) {
         // full), so the stop overshoots the first report that meets the target by at most one chunk
         // --adaptive: every chunk after the first renders the tiles that the report one check before the newest finds noisy
         // (State.render_until(adaptive=True)'s loop); subset frames count as frames
+        // --budget: every chunk after the first is mrt_render_budget from that report's summed-S map (render_until(budget=N)'s
+        // loop: the queries leave that kind of map), and the loop also stops when a chunk finds nothing worth a frame
         uint32_t done = 0;
         uint64_t earlier = 0;             // that report (0: none yet)
         uint32_t selected = 0;            // the tiles of the latest chunk
         uint64_t tile_frames = 0;         // tiles x frames queued: at most 64 x spp samples each
+        mrt_budget_result spent{};        // --budget: the latest chunk's allocation
+        bool idle = false;                // ... which found nothing to spend on
         auto chunk = [&]() -> int {
             const uint32_t k = std::min(check_every, frames - done);
             for (mrt_ctx* c : ctxs) {
@@ -196,6 +206,11 @@ int main(int argc, char** argv) {
                 if (adaptive && earlier != 0) {
                     uint64_t used = 0;
                     s_ = mrt_render_adaptive(c, k, earlier, &used, &selected);
+                } else if (budget && earlier != 0) {
+                    s_ = mrt_render_budget(c, budget, std::min(k, 32u), earlier, &spent, nullptr, 0);
+                    idle = spent.tile_frames == 0;
+                    tile_frames += spent.tile_frames;
+                    selected = 0;                       // (counted above: the levels differ in length)
                 } else {
                     s_ = mrt_render(c, k);
                     uint32_t tx = 0, tr = 0;
@@ -209,7 +224,10 @@ int main(int argc, char** argv) {
             return MRT_OK;
         };
         auto query = [&]() -> int {
-            for (mrt_ctx* c : ctxs) { const int s_ = mrt_noise_query(c, 0.02f, 0.01f); if (s_ != MRT_OK) return s_; }
+            for (mrt_ctx* c : ctxs) {
+                const int s_ = mrt_noise_query_map(c, 0.02f, 0.01f, budget ? MRT_TILE_MAP_SUM_S : MRT_TILE_MAP_MAX_REL);
+                if (s_ != MRT_OK) return s_;
+            }
             return MRT_OK;
         };
         TRY(ctxs[0], chunk());
@@ -235,7 +253,11 @@ int main(int argc, char** argv) {
                 std::printf("check: report at frame %u: %llu pixels above, rel_rmse %.5g; %u frames queued, %u tiles in the latest chunk, "
                             "%llu samples at most\n", r.frames_done, (unsigned long long)r.above, r.rel_rmse, done, selected,
                             (unsigned long long)(tile_frames * 64u * args.samples_per_frame));
-            if (r.rel_rmse <= target_noise || r.frames_done >= frames || (adaptive && r.above == 0)) break;
+            if (budget && earlier != 0)
+                std::printf("check: report at frame %u: rel_rmse %.5g; %u frames queued; the latest chunk: %llu tile-frames over %u tiles in "
+                            "%u frames, modelled variance %.6g -> %.6g\n", r.frames_done, r.rel_rmse, done,
+                            (unsigned long long)spent.tile_frames, spent.tiles, spent.frames, spent.var_before, spent.var_after);
+            if (r.rel_rmse <= target_noise || r.frames_done >= frames || (adaptive && r.above == 0) || idle) break;
             earlier = r.seq;
             TRY(ctxs[0], query());
         }
@@ -245,7 +267,7 @@ int main(int argc, char** argv) {
     for (mrt_ctx* c : ctxs) TRY(c, mrt_sync(c));
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     double samples = (double)args.width * args.height * args.samples_per_frame * frames;
-    if (adaptive) {                       // subset frames: the samples the render kernels counted
+    if (adaptive || budget) {             // subset frames: the samples the render kernels counted
         mrt_counters cnt{};
         TRY(ctxs[0], mrt_read_counters(ctxs[0], &cnt));
         samples = (double)cnt.samples;

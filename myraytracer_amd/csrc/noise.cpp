@@ -133,8 +133,9 @@ int mrt_set_noise_tracking(mrt_ctx* c, int enabled) {
     return MRT_OK;
 }
 
-int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
-    if (!c) return MRT_ERR_INVALID_ARG;
+// mrt_noise_query and mrt_noise_query_map: map_kind 0 queues exactly what mrt_noise_query always has
+static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_kind) {
+    if (!c || map_kind > MRT_TILE_MAP_SUM_S) return MRT_ERR_INVALID_ARG;
     if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_noise_query: noise tracking is off (mrt_set_noise_tracking)");
     if (!noise_args_ok(threshold, floor_))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
@@ -150,7 +151,12 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
     float* map = c->d_noise_tiles + (size_t)i * mrt::tiles_min1(c);
     double K = mrt::noise_factor_of(c->noise_c2);
     int e = 0;
-    if (!c->tiles_diverged) {
+    const bool sum_s = map_kind == MRT_TILE_MAP_SUM_S;
+    if (!c->tiles_diverged && sum_s) {
+        e = mrt::launch_noise_reduce_sum(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                         c->shard_rank, c->shard_world, (float)K, nullptr, nullptr, nullptr, threshold, floor_,
+                                         c->d_noise_partials, map, c->d_noise_sums + i, c->stream);
+    } else if (!c->tiles_diverged) {
         e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
                                      c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials, map,
                                      c->d_noise_sums + i, c->stream);
@@ -160,9 +166,14 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
         MRT_TRY(mrt::ensure_k_table(c, most + 1u));
         K = 0.0;
         for (uint32_t t : c->tile_frames) K = std::max(K, c->k_table[t]);
-        e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
-                                           c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials, map,
-                                           c->d_noise_sums + i, c->stream);
+        if (sum_s)
+            e = mrt::launch_noise_reduce_sum(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height, 0, 1,
+                                             0.0f, c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials,
+                                             map, c->d_noise_sums + i, c->stream);
+        else
+            e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
+                                               c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials,
+                                               map, c->d_noise_sums + i, c->stream);
     }
     if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
     HIP_TRY(c, hipMemcpyAsync(c->h_noise_sums + i, c->d_noise_sums + i, sizeof(mrt::NoiseSums), hipMemcpyDeviceToHost, c->stream));
@@ -170,12 +181,17 @@ int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) {
     E.report = mrt_noise_report{};
     E.report.seq = seq;
     E.report.frames_done = c->frames_done;
+    E.report.reserved = map_kind;
     E.report.threshold = threshold; E.report.floor = floor_;
     E.report.noise_factor = K;
     E.per_tile = c->tiles_diverged;
     c->noise_seq = seq;
     return MRT_OK;
 }
+
+int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) { return noise_query(c, threshold, floor_, MRT_TILE_MAP_MAX_REL); }
+
+int mrt_noise_query_map(mrt_ctx* c, float threshold, float floor_, uint32_t map_kind) { return noise_query(c, threshold, floor_, map_kind); }
 
 int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
@@ -225,6 +241,56 @@ int mrt_read_noise_tiles(mrt_ctx* c, float* out, size_t cap, uint32_t* tiles_x, 
     return mrt::wait_stream(c, c->noise_stream, __func__);
 }
 
+}  // extern "C"
+
+namespace {
+
+// The report a selection is made from (mrt_render_adaptive: kind MRT_TILE_MAP_MAX_REL, mrt_render_budget: MRT_TILE_MAP_SUM_S).
+// report_seq == 0: the newest finished report of that kind, without waiting (*seq = 0: none); any other: that report, which must
+// be held and of that kind, after a bounded wait on the host for its copy -- so *seq != 0 names a report whose `copied` the
+// host has seen complete.
+int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kind, uint64_t* seq) {
+    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    *seq = 0;
+    if (report_seq == 0) {
+        for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
+            if (c->noise_ring[k % kNoiseRing].report.reserved != kind) continue;
+            const hipError_t q = hipEventQuery(c->noise_ring[k % kNoiseRing].copied);
+            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
+            if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "%s: %s", who, hipGetErrorString(q));
+            *seq = k;
+            break;
+        }
+        return MRT_OK;
+    }
+    if (report_seq > c->noise_seq || report_seq < oldest)
+        return fail(c, MRT_ERR_STATE, "%s: report %llu is not among the reports held (%llu .. %llu)", who,
+                    (unsigned long long)report_seq, (unsigned long long)oldest, (unsigned long long)c->noise_seq);
+    if (c->noise_ring[report_seq % kNoiseRing].report.reserved != kind)
+        return fail(c, MRT_ERR_STATE, "%s: report %llu holds a tile map of kind %u, not %u (mrt_noise_query_map)", who,
+                    (unsigned long long)report_seq, c->noise_ring[report_seq % kNoiseRing].report.reserved, kind);
+    char what[96];
+    std::snprintf(what, sizeof what, "%s: report %llu", who, (unsigned long long)report_seq);
+    MRT_TRY(mrt::wait_event(c, c->noise_ring[report_seq % kNoiseRing].copied, what));
+    *seq = report_seq;
+    return MRT_OK;
+}
+
+// report `seq`'s tile map (choose_report's: its copy has landed) into c->h_select_map
+int read_report_map(mrt_ctx* c, const char* who, uint64_t seq, uint32_t nt) {
+    // the map was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
+    if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
+    c->h_select_map.resize(nt);
+    HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[seq % kNoiseRing].copied, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->h_select_map.data(), c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float),
+                              hipMemcpyDeviceToHost, c->noise_stream));
+    return mrt::wait_stream(c, c->noise_stream, who);
+}
+
+}  // namespace
+
+extern "C" {
+
 // Adaptive sampling's selection: the tiles whose entry in report `report_seq`'s tile map is > its threshold (the tiles holding a
 // pixel counted in its `above`), from that report's own map (one per ring entry), then mrt_render_tiles.  Waits for that query only.
 int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64_t* used_seq, uint32_t* tiles_selected) {
@@ -233,37 +299,14 @@ int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64
     if (tiles_selected) *tiles_selected = 0;
     if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: noise tracking is off (mrt_set_noise_tracking)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
-    uint64_t seq = 0;
-    if (report_seq == 0) {                      // the newest finished report, without waiting; none: every tile
-        for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
-            const hipError_t q = hipEventQuery(c->noise_ring[k % kNoiseRing].copied);
-            if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
-            if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "mrt_render_adaptive: %s", hipGetErrorString(q));
-            seq = k;
-            break;
-        }
-    } else {
-        if (report_seq > c->noise_seq || report_seq < oldest)
-            return fail(c, MRT_ERR_STATE, "mrt_render_adaptive: report %llu is not among the reports held (%llu .. %llu)",
-                        (unsigned long long)report_seq, (unsigned long long)oldest, (unsigned long long)c->noise_seq);
-        char what[96];
-        std::snprintf(what, sizeof what, "mrt_render_adaptive: report %llu", (unsigned long long)report_seq);
-        MRT_TRY(mrt::wait_event(c, c->noise_ring[report_seq % kNoiseRing].copied, what));
-        seq = report_seq;
-    }
+    uint64_t seq = 0;                           // report_seq 0 and none finished: every tile
+    MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_MAX_REL, &seq));
     const uint32_t nt = c->n_tiles;
     c->selection.clear();
     if (seq == 0) {
         for (uint32_t t = 0; t < nt; t++) c->selection.push_back(t);
     } else {
-        // the map was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
-        if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
-        c->h_select_map.resize(nt);
-        HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[seq % kNoiseRing].copied, 0));
-        HIP_TRY(c, hipMemcpyAsync(c->h_select_map.data(), c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float),
-                                  hipMemcpyDeviceToHost, c->noise_stream));
-        MRT_TRY(mrt::wait_stream(c, c->noise_stream, __func__));
+        MRT_TRY(read_report_map(c, __func__, seq, nt));
         const float threshold = c->noise_ring[seq % kNoiseRing].report.threshold;
         for (uint32_t t = 0; t < nt; t++)
             if (c->h_select_map[t] > threshold) c->selection.push_back(t);
@@ -272,6 +315,128 @@ int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64
     if (tiles_selected) *tiles_selected = (uint32_t)c->selection.size();
     if (c->selection.empty()) return MRT_OK;              // converged at that threshold: nothing to render
     return mrt_render_tiles(c, c->selection.data(), c->selection.size(), frames);
+}
+
+// Adaptive sampling by budget (include/myraytracer_amd.h): the definition there, as a selection over the candidates.  K(n) comes
+// from one table made by mrt_noise_factor's own recursion (the values are its, bit for bit); the table ends where c2 has
+// reached its fixed point at a saturated weight, as mrt_noise_factor's loop does, and K is constant from there.
+int mrt_budget_allocate(const float* s, const uint32_t* n, size_t tiles, float max_w, uint64_t budget, uint32_t max_frames,
+                        uint32_t* k_out, mrt_budget_result* res) {
+    constexpr uint32_t kMaxN = 1u << 24;
+    if (!s || !n || !k_out || !res || tiles == 0 || max_frames < 1 || max_frames > mrt::kMaxFrameBatch) return MRT_ERR_INVALID_ARG;
+    if (!(max_w > 0.0f) || std::isinf(max_w)) return MRT_ERR_INVALID_ARG;
+    uint32_t most = 0;
+    for (size_t t = 0; t < tiles; t++) {
+        if (n[t] > kMaxN) return MRT_ERR_INVALID_ARG;
+        most = std::max(most, n[t]);
+    }
+    std::vector<double> table;
+    {
+        const uint32_t len = most + max_frames + 1u;
+        double c2 = 1.0;
+        for (uint32_t k = 0; k < len; k++) {
+            table.push_back(mrt::noise_factor_of(c2));          // K(k)
+            const float w = mrt_frame_weight(k, max_w);
+            const double next = mrt::noise_c2_next(c2, w);
+            if (k != 0 && w == max_w && max_w < 0.99999988f && next == c2) break;
+            c2 = next;
+        }
+    }
+    const auto K = [&](uint32_t frames) { return table[std::min<size_t>(frames, table.size() - 1)]; };
+    const auto clean = [&](size_t t) { return s[t] >= 0.0f ? (double)s[t] : 0.0; };      // (a NaN compares false)
+    std::fill(k_out, k_out + tiles, 0u);
+    uint64_t left = budget;
+    // mandatory frames: j ascending, then t ascending
+    for (uint32_t j = 0; j < std::min(2u, max_frames) && left != 0; j++)
+        for (size_t t = 0; t < tiles && left != 0; t++)
+            if (n[t] + j < 2u) { k_out[t]++; left--; }
+    if (left != 0) {
+        struct Cand { double g; uint32_t j, t; };
+        const auto before = [](const Cand& a, const Cand& b) { return a.g != b.g ? a.g > b.g : a.j != b.j ? a.j < b.j : a.t < b.t; };
+        std::vector<Cand> cand;
+        cand.reserve(std::min<size_t>(tiles * max_frames, 1u << 22));
+        std::vector<double> step(table.size());                 // K(n) - K(n + 1); 0 from the table's end on, where K stays
+        for (size_t i = 0; i + 1 < table.size(); i++) step[i] = table[i] - table[i + 1];
+        const auto gain = [&](uint32_t frames) { return frames < step.size() ? step[frames] : 0.0; };
+        for (size_t t = 0; t < tiles; t++) {
+            const double st = clean(t);
+            const uint32_t m = n[t] < 2u ? std::min(2u - n[t], max_frames) : 0u;
+            if (!(st > 0.0) || std::isinf(st) || n[t] + m < 2u) continue;
+            double g = INFINITY;
+            for (uint32_t j = m; j < max_frames; j++) {
+                g = std::min(g, st * gain(n[t] + j));
+                if (!(g > 0.0)) break;                          // g' never increases: no later candidate counts
+                cand.push_back(Cand{g, j, (uint32_t)t});
+            }
+        }
+        if (left < cand.size()) {
+            std::nth_element(cand.begin(), cand.begin() + (ptrdiff_t)left, cand.end(), before);
+            cand.resize((size_t)left);
+        }
+        for (const Cand& q : cand) k_out[q.t]++;
+    }
+    mrt_budget_result r{};
+    r.size = sizeof r;
+    for (size_t t = 0; t < tiles; t++) {
+        r.tile_frames += k_out[t];
+        r.tiles += k_out[t] ? 1u : 0u;
+        r.frames = std::max(r.frames, k_out[t]);
+        if (n[t] >= 2u) {
+            r.var_before += clean(t) * K(n[t]);
+            r.var_after += clean(t) * K(n[t] + k_out[t]);
+        }
+    }
+    *res = r;
+    return MRT_OK;
+}
+
+int mrt_render_budget(mrt_ctx* c, uint64_t budget, uint32_t max_frames, uint64_t report_seq, mrt_budget_result* res, uint32_t* k_out,
+                      size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    mrt_budget_result r{};
+    r.size = sizeof r;
+    if (res) *res = r;
+    if (max_frames < 1 || max_frames > mrt::kMaxFrameBatch)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: max_frames %u (1 .. %u)", max_frames, mrt::kMaxFrameBatch);
+    const uint32_t nt = c->n_tiles;
+    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_render_budget: need %u values", nt);
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_budget: noise tracking is off (mrt_set_noise_tracking)");
+    // mrt_render_tiles' refusals, before anything is queued
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_render_budget: a shard (world %u) renders whole frames only", c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_render_budget: no scene (call mrt_set_world first)");
+    if (c->locals.rng_mode == MRT_RNG_COUNTER && c->locals.samples_per_frame > MRT_COUNTER_BLOCK)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: counter mode renders at most %u samples per frame by tiles (%u)",
+                    (unsigned)MRT_COUNTER_BLOCK, c->locals.samples_per_frame);
+    if (k_out) std::fill(k_out, k_out + nt, 0u);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint64_t seq = 0;
+    MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq));
+    if (seq == 0 || nt == 0) return MRT_OK;               // no report of that kind has finished: nothing to allocate from
+    r.used_seq = seq;
+    if (res) *res = r;
+    if (budget == 0) return MRT_OK;
+    MRT_TRY(read_report_map(c, __func__, seq, nt));
+    std::vector<uint32_t> uniform;
+    if (!c->tiles_diverged) uniform.assign(nt, c->frames_done);
+    const uint32_t* n = c->tiles_diverged ? c->tile_frames.data() : uniform.data();
+    std::vector<uint32_t> k(nt);
+    if (mrt_budget_allocate(c->h_select_map.data(), n, nt, c->args.max_framebuffer_weight, budget, max_frames, k.data(), &r) != MRT_OK)
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: a tile has more than %u frames", 1u << 24);
+    r.used_seq = seq;
+    if (res) *res = r;
+    if (k_out) std::copy(k.begin(), k.end(), k_out);
+    // L_j = {t : k_t >= j}; consecutive j with the same list (the lists only shrink: the same size) are one call
+    for (uint32_t j = 1; j <= r.frames;) {
+        c->selection.clear();
+        for (uint32_t t = 0; t < nt; t++)
+            if (k[t] >= j) c->selection.push_back(t);
+        uint32_t run = 1;
+        const auto listed = [&](uint32_t level) { return (size_t)std::count_if(k.begin(), k.end(), [&](uint32_t v) { return v >= level; }); };
+        while (j + run <= r.frames && listed(j + run) == c->selection.size()) run++;
+        MRT_TRY(mrt_render_tiles(c, c->selection.data(), c->selection.size(), run));
+        j += run;
+    }
+    return MRT_OK;
 }
 
 int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,

@@ -217,6 +217,94 @@ __global__ void __launch_bounds__(64 * kNoiseWaves) noise_reduce_tiles_kernel(co
     }
 }
 
+// The reductions above with the other kind of tile map (mrt_noise_query_map, MRT_TILE_MAP_SUM_S): the partials are theirs,
+// statement for statement -- kPerTile = false noise_reduce_kernel's, true noise_reduce_tiles_kernel's -- and the map entry is
+// the tile's summed S instead of its largest rel: a counted pixel (in the image, S and L finite) gives (double)S_p, any other
+// +0.0; a tile row's eight columns are added by the same three xor-shuffles the maximum takes -- the tree ((p0 + p1) + (p2 +
+// p3)) + ((p4 + p5) + (p6 + p7)) in every lane, addition being commutative -- and the eight row sums through LDS, from the
+// band's bottom row up, starting at 0.0; the entry is that double rounded to float.  No K and no n_t enter the map.
+template <bool kPerTile>
+__global__ void __launch_bounds__(64 * kNoiseWaves) noise_reduce_sum_kernel(const float* __restrict__ S, const float4* __restrict__ fb,
+                                                                            uint32_t width, uint32_t height, uint32_t rank,
+                                                                            uint32_t world, float K_uniform,
+                                                                            const uint32_t* __restrict__ tile_frames,
+                                                                            const float* __restrict__ Kf, const double* __restrict__ Kd,
+                                                                            float threshold, float floor_,
+                                                                            NoisePartial* __restrict__ partials,
+                                                                            float* __restrict__ tiles, uint32_t tiles_x) {
+    __shared__ NoisePartial wave_part[kNoiseWaves];
+    __shared__ double tile_part[kNoiseWaves][kNoiseCols / kTileW];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t band = blockIdx.y, x_base = blockIdx.x * kNoiseCols;
+    const uint32_t lrow = band * kBandRows + wave;
+    const bool row_ok = kPerTile ? lrow < height : (band * world + rank) * kBandRows + wave < height;
+    const size_t row = (size_t)lrow * width;
+    double sum_s = 0.0, sum_l = 0.0;
+    uint32_t pixels = 0, non_finite = 0, above = 0;
+    float max_se = 0.0f;
+#pragma unroll
+    for (uint32_t i = 0; i < kNoiseCols / 64u; i++) {
+        const uint32_t x = x_base + 64u * i + lane;
+        double tile_s = 0.0;
+        if (row_ok && x < width) {
+            const float s = S[row + x];
+            const float4 c = fb[row + x];
+            const float L = lumf(c.x, c.y, c.z);
+            if (__builtin_isfinite(s) && __builtin_isfinite(L)) {
+                float K = K_uniform;
+                bool no_estimate;
+                pixels++;
+                if (kPerTile) {
+                    const uint32_t nt = tile_frames[(size_t)band * tiles_x + x / kTileW];
+                    K = Kf[nt];
+                    no_estimate = __builtin_isinf(K);
+                    sum_s += no_estimate ? 0.0 : (double)s * Kd[nt];
+                } else {
+                    no_estimate = __builtin_isinf(K);
+                    sum_s += (double)s;
+                }
+                sum_l += (double)L;
+                const float se = no_estimate ? __builtin_inff() : sqrtf(s * K);
+                const float rel = se / fmaxf(L, floor_);
+                above += rel > threshold ? 1u : 0u;
+                max_se = fmaxf(max_se, se);
+                tile_s = (double)s;
+            } else {
+                non_finite++;
+            }
+        }
+        tile_s += __shfl_xor(tile_s, 1);
+        tile_s += __shfl_xor(tile_s, 2);
+        tile_s += __shfl_xor(tile_s, 4);
+        if ((lane & 7u) == 0u) tile_part[wave][i * 8u + (lane >> 3)] = tile_s;
+    }
+    sum_s = wave_sum(sum_s);
+    sum_l = wave_sum(sum_l);
+    pixels = wave_sum(pixels);
+    non_finite = wave_sum(non_finite);
+    above = wave_sum(above);
+    max_se = wave_max(max_se);
+    if (lane == 0) wave_part[wave] = NoisePartial{sum_s, sum_l, pixels, non_finite, above, max_se};
+    __syncthreads();
+    if (threadIdx.x < kNoiseCols / kTileW) {
+        const uint32_t tx = blockIdx.x * (kNoiseCols / kTileW) + threadIdx.x;
+        double m = 0.0;
+#pragma unroll
+        for (uint32_t r = 0; r < kNoiseWaves; r++) m += tile_part[r][threadIdx.x];
+        if (tx < tiles_x) tiles[(size_t)band * tiles_x + tx] = (float)m;
+    }
+    if (threadIdx.x == 0) {
+        NoisePartial p = wave_part[0];
+        for (uint32_t r = 1; r < kNoiseWaves; r++) {
+            const NoisePartial& q = wave_part[r];
+            p.sum_s += q.sum_s; p.sum_l += q.sum_l;
+            p.pixels += q.pixels; p.non_finite += q.non_finite; p.above += q.above;
+            p.max_se = fmaxf(p.max_se, q.max_se);
+        }
+        partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = p;
+    }
+}
+
 }  // namespace
 
 size_t noise_partials_bytes(uint32_t width, uint32_t local_bands) {
@@ -246,6 +334,21 @@ int launch_noise_reduce_tiles(const float* S, const float* rgba, uint32_t width,
     hipLaunchKernelGGL(noise_reduce_tiles_kernel, dim3(gx, local_bands), dim3(64 * kNoiseWaves), 0, st, S,
                        reinterpret_cast<const float4*>(rgba), width, height, tile_frames, Kf, Kd, threshold, floor_,
                        reinterpret_cast<NoisePartial*>(partials), tiles, (width + kTileW - 1) / kTileW);
+    hipLaunchKernelGGL(noise_final_kernel, dim3(1), dim3(kNoiseFinalBlock), 0, st,
+                       reinterpret_cast<const NoisePartial*>(partials), gx * local_bands, out);
+    return (int)hipGetLastError();
+}
+
+int launch_noise_reduce_sum(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
+                            uint32_t rank, uint32_t world, float K, const uint32_t* tile_frames, const float* Kf, const double* Kd,
+                            float threshold, float floor_, void* partials, float* tiles, NoiseSums* out, void* stream) {
+    const uint32_t gx = (width + kNoiseCols - 1) / kNoiseCols;
+    if (gx == 0 || local_bands == 0) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    auto* kernel = tile_frames ? noise_reduce_sum_kernel<true> : noise_reduce_sum_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(gx, local_bands), dim3(64 * kNoiseWaves), 0, st, S, reinterpret_cast<const float4*>(rgba), width,
+                       height, rank, world, K, tile_frames, Kf, Kd, threshold, floor_, reinterpret_cast<NoisePartial*>(partials),
+                       tiles, (width + kTileW - 1) / kTileW);
     hipLaunchKernelGGL(noise_final_kernel, dim3(1), dim3(kNoiseFinalBlock), 0, st,
                        reinterpret_cast<const NoisePartial*>(partials), gx * local_bands, out);
     return (int)hipGetLastError();

@@ -53,6 +53,14 @@ def _anim(scene, way, pattern):
     raise KeyError((scene, way))
 
 
+def _budget(line_pattern, pattern):
+    """a figure of the first line of profiles/adaptive_budget_quality.txt (comments aside) matching `line_pattern`"""
+    for line in open(os.path.join(ROOT, "profiles", "adaptive_budget_quality.txt")):
+        if not line.startswith("#") and re.search(line_pattern, line):
+            return float(re.search(pattern, line).group(1))
+    raise KeyError(line_pattern)
+
+
 # token -> (how to get the value, format)
 TOKENS = {
     "C3_VALUE": (lambda: _json(f"{R}_bench_n1.json")["value"], ",.0f"),
@@ -122,6 +130,10 @@ TOKENS = {
     "MAT_C5_SET_STEP_MS": (lambda: _mat(r"\s+C5 \S.* set_world\s", r"\(([\d.]+) ms a step\)"), ".1f"),
     "MAT_C5_GAP_MS": (lambda: _mat(r"\s+C5 \S.*, round 1:", r"no-edit loop \(\+([\d.]+) ms a step\)"), ".2f"),
     "MAT_C3_GAP_MS": (lambda: _mat(r"\s+C3 \S.*, round 1:", r"no-edit loop \(\+([\d.]+) ms a step\)"), ".2f"),
+    "BUDGET_UNIFORM_RMSE": (lambda: _budget(r"^\s+uniform\s+frames", r"rmse ([\d.]+)"), ".5f"),
+    "BUDGET_RMSE_8": (lambda: _budget(r"^\s+budget, max_frames 8\s", r"rmse ([\d.]+)"), ".5f"),
+    "BUDGET_RATIO_8": (lambda: _budget(r"at equal samples:", r"budget 8 ([\d.]+)"), ".3f"),
+    "BUDGET_ADAPTIVE_RATIO": (lambda: _budget(r"at equal samples:", r"adaptive ([\d.]+)"), ".3f"),
     "C5_NODE_ROUNDS": (lambda: _phase("c5", r"node rounds/sweep ([\d.]+)"), ".1f"),
     "C5_ROUND_ITEMS": (lambda: _phase("c5", r"node rounds/sweep [\d.]+ \(items/round ([\d.]+)\)"), ".0f"),
 }
