@@ -42,9 +42,15 @@ Imports: the module needs no device, but it imports the package (which loads the
 batches the issue tells it to share, the gpu-marked modules tests/test_gpu_update_spheres.py and tests/test_gpu_superset.py; those
 must stay importable on a machine without a GPU (they are: their imports touch no device), or tests/test_motion_chains_host.py fails.
 
+Hooks for chains with a vocabulary of their own (tests/material_chains.py, tests/adaptive_chains.py): params["size"], an image
+other than W x H; Run's shadow, compare and extra_check; Run.rendered(k, listed) for the launches of mrt_render_tiles,
+mrt_render_adaptive and mrt_render_budget, which CameraTables.launch judges as it judges a whole frame's; the verdicts of
+mrt_set_auto_regroup, read at the next check (or regroup, or scene) and replayed from the positions each update left.  None of them changes what the chains of this module do.
+
 The model is host only.  It holds the spheres, the camera, the (scene, camera) of every frame queued since the last reset, the
 guides' staleness, and the temporal state (h0, h1, previous spheres, previous derived camera, dropped / stepped); frames and
 counters are the oracle's, guides denoise_ref's, a step and the image temporal_ref's.  Nothing is read back from the library."""
+import itertools
 import math
 
 import numpy as np
@@ -486,11 +492,11 @@ class Model:
     """State's method names for the chain vocabulary; a call the header refuses raises Refused(status).  The methods the seeded
     defects of tests/test_motion_chains_host.py override are the ones with a leading underscore."""
 
-    def __init__(self, O, max_w):
-        self.O, self.max_w = O, max_w
+    def __init__(self, O, max_w, w=W, h=H):
+        self.O, self.max_w, self.w, self.h = O, max_w, w, h     # (w, h: the image; tests/adaptive_chains.py has chains at 44 x 20)
         self.spheres = None
         self.set_camera(None)
-        self.seeds = O.fill_seeds(SEED, W, H)
+        self.seeds = O.fill_seeds(SEED, w, h)
         self.frames, self.done = [], []         # per frame queued since the reset: (spheres, cam_raw, key); (fb, counters) after it
         self.guides_built = None                # the (scene, camera) the guides were last rebuilt for
         self.guides_stale = True
@@ -522,7 +528,7 @@ class Model:
         self.stepped, self.cleared = False, True
 
     def _evaluate(self):
-        O = self.O
+        O, W, H = self.O, self.w, self.h
         for f in range(len(self.done), len(self.frames)):
             spheres, cam_raw, key = self.frames[f]
             fb, cnt = self.done[f - 1] if f else (np.zeros((H, W, 4), np.float32), (0, 0, 0))
@@ -532,24 +538,29 @@ class Model:
                 out = O.render_frame(W, H, SPP, DEPTH, O.pack_world(to_oracle_spheres(O, spheres)), cam_raw, self.seeds,
                                      O.frame_shuffle(SEED, f), O.frame_weight(f, self.max_w), fb, counters=c)
                 return out, tuple(int(c.as_dict()[k]) for k in KEYS)
-            out, add = _cached(_FRAMES, (key, f, self.max_w, _key(fb)), make)
+            out, add = _cached(_FRAMES, (key, f, self.max_w, _key(fb), W, H), make)
             self.done.append((out, tuple(a + b for a, b in zip(cnt, add))))
 
     def _guides(self, key):
         spheres, cam_raw = key[2], key[3]
+        W, H = self.w, self.h
 
         def make():
             rays = denoise_ref.centre_rays(W, H, cam_raw)
             hit, t, normal, albedo = denoise_ref.expected_guides(self.O, spheres, rays)
             return {"rays": rays, "index": hit.reshape(H, W).astype(np.int32), "t": t.reshape(H, W), "normal": normal.reshape(H, W, 3),
                     "albedo": albedo.reshape(H, W, 3)}
-        return _cached(_GUIDES, key[:2], make, 400)
+        return _cached(_GUIDES, key[:2] + (W, H), make, 400)
 
     def _ensure_guides(self):
         if self.guides_stale or self.guides_built is None:
             self.guides_built = (_key(self.spheres), self.cam_key, self.spheres, self.cam_raw)
             self.guides_stale = False
         return self._guides(self.guides_built)
+
+    def _step_guides(self):
+        """the guides a temporal step reads, rebuilt first if stale (a hook: tests/adaptive_chains.py names its consumers)"""
+        return self._ensure_guides()
 
     # ---- scene
     def debug_set_hierarchy(self, levels, target):
@@ -613,7 +624,7 @@ class Model:
 
     def read_framebuffer(self):
         self._evaluate()
-        return self.done[-1][0].copy() if self.done else np.zeros((H, W, 4), np.float32)
+        return self.done[-1][0].copy() if self.done else np.zeros((self.h, self.w, 4), np.float32)
 
     def read_counters(self):
         self._evaluate()
@@ -658,11 +669,11 @@ class Model:
         self._temporal_check("temporal_step", False)
         if self.frames_done == 0:
             raise Refused(STATE, "temporal_step")
-        g = self._ensure_guides()
+        g = self._step_guides()
         first = self.cleared
         if self.cleared:                        # every length 0: no tap of this step counts, whatever "previous" holds
-            self.h0 = np.zeros((H, W, 4), np.float32)
-            self.h1 = np.zeros((H, W, 4), np.float32)
+            self.h0 = np.zeros((self.h, self.w, 4), np.float32)
+            self.h1 = np.zeros((self.h, self.w, 4), np.float32)
             self.prev_cam = self.cam_raw
             self.cleared = False
         Mx, o = T.camera_matrix(self.prev_cam)
@@ -686,13 +697,14 @@ class Model:
 
 
 def new_model(O, params, cls=None):
-    return (cls or Model)(O, params["max_w"])
+    return (cls or Model)(O, params["max_w"], *params.get("size", ()))      # ("size": a chain's own image, (w, h); else W x H)
 
 
 def new_state(params):
     """a context for a chain; a HIP error or a stalled wait while it is made is ChainStopped, as in the runner"""
     try:
-        st = M.State(M.Args(W, H, SPP, DEPTH, params["max_w"]), seed=SEED)
+        w, h = params.get("size", (W, H))
+        st = M.State(M.Args(w, h, SPP, DEPTH, params["max_w"]), seed=SEED)
         st.set_wait_timeout(60.0)               # (a stalled wait stops the case with the wait's name long before the suite's own limit)
         st.debug_set_boxes(2)                   # the walk's box tests on (large scenes), as tests/test_gpu_update_spheres.py has them
     except M.MrtError as e:
@@ -801,7 +813,7 @@ def _last_error(impl):
         return ""
 
 
-def check_rays(spheres, cam_raw):
+def check_rays(spheres, cam_raw, W=W, H=H):
     """the rays of a check: about 2,000 random, grazing and on-surface rays around the spheres as they are, and the camera's own
     (every texel's four corner jitters and six random ones, as tests/camera_mask_cases.py samples them); -> (rays, index of the first camera ray, the camera rays' texels)"""
     rays = _rays_for(np.random.default_rng(7), spheres, 500, 900, 600)
@@ -821,13 +833,22 @@ def reference_hits(O, spheres, rays):
 class Run:
     """One chain on one implementation and one model, op by op.  after(i, op, run): called behind every op that compared equal."""
 
-    def __init__(self, label, params, impl, model, O, stats=None, after=None, device_checks=True, tables=None):
+    def __init__(self, label, params, impl, model, O, stats=None, after=None, device_checks=True, tables=None, shadow=None,
+                 compare=None, extra_check=None):
+        """The hooks of the chains that bring a vocabulary of their own (tests/adaptive_chains.py): shadow, the Shadow that knows
+        their ops; compare(name, got, want) -> None or what differs, asked behind every call that both sides accepted, for the
+        calls whose value is an observable; extra_check(run), called in every check behind the comparisons below and ahead of
+        the device's."""
         self.label, self.p, self.impl, self.model, self.O = label, params, impl, model, O
         self.tables = (tables or CameraTables)()        # the prediction of every render launch's table
         self.batching, self.tables_lost = 1, False      # mrt_debug_set_frame_batching: automatic until a chain switches it off
         self.device_checks = device_checks      # (off: what the model can say alone -- the liveness test's view of a real context)
         self.stats, self.after = stats if stats is not None else {}, after
-        self.sh = Shadow()
+        self.sh = shadow or Shadow()
+        self.compare, self.extra_check = compare, extra_check
+        self.spp = SPP                          # samples per frame and launch (mrt_set_samples_per_frame)
+        self.auto_regroup, self.auto_seen = False, 0    # mrt_set_auto_regroup: the policy is on; the regroups it has let run
+        self.auto_pending = []                  # ... the positions left by the updates whose verdict has not been read yet
         self.device = getattr(impl, "_ctx", None) is not None
         self.sweep, self.fif, self.gen = 0, 0, 0
         self.midx = self.real = self.n_pool = None
@@ -870,8 +891,30 @@ class Run:
             # frame batching off: mrt_render(k) is k launches, queued without a wait.  The runner makes them one call each, which
             # queues the same launches, so that EVERY launch's table is compared with the prediction and not the last one's alone
             calls = [("render", (1,))] * op[1]
+        if op[0] == "subset" and self.batching == 0 and self.sh.layout == "small":
+            calls = [("render_tiles", (op[1], 1))] * op[2]      # (the same for the launches of mrt_render_tiles(tiles, k))
         for name, args in calls:
-            status, _, _ = self._both(name, args)
+            if name in ("regroup_spheres", "set_world", "set_auto_regroup"):     # (they need, or end, the ordering as it is)
+                self._resolve_auto_regroups()
+            status, got, want = self._both(name, args)
+            if status == OK and self.compare is not None:
+                bad = self.compare(name, got, want)
+                if bad:
+                    self._fail(f"{name}: {bad}")
+            if name == "set_samples_per_frame" and status == OK:
+                self.spp = int(args[0])
+            if name == "set_auto_regroup" and status == OK:
+                self.auto_regroup = bool(args[0])
+            if status == OK and name == "set_world":
+                self.auto_seen = 0              # (the policy's statistics restart with the scene)
+            if status == OK and name == "render_tiles":
+                self.rendered(args[1], len(args[0]))
+            if status == OK and name == "render_adaptive" and want[1]:
+                self.rendered(args[0], want[1])
+            if status == OK and name == "render_budget":
+                levels = self.model.last_levels  # the mrt_render_tiles calls the allocation was rendered through; the device reports
+                for i, (listed, run_length) in enumerate(levels):       # the last launch of the last one
+                    self.rendered(run_length, listed, last=i == len(levels) - 1)
             if status == OK and name in GENERATION_CALLS and not (name == "update_spheres" and len(args[1]) == 0):
                 self.gen += 1
                 self.tables.call(name)
@@ -883,6 +926,11 @@ class Run:
                 self._bump("regroups")
                 if self.device:                 # the ordering tests/regroup_ref.py gives for the geometry at this regroup
                     self.midx = G.regroup(self.midx, self.real, self.n_pool, self.model.xyzr()[:, :3])
+            if status == OK and name == "update_spheres" and self.auto_regroup and self.device and len(args[1]):
+                # the policy decides on the device and the host never learns the verdict: the positions this update leaves are
+                # kept, and the verdicts are read where the runner waits anyway (_resolve_auto_regroups), so that what follows
+                # the update still queues behind the frames in flight
+                self.auto_pending.append(self.model.xyzr()[:, :3].copy())
             if name == "debug_set_sweep":
                 self.sweep = args[0]
             if name == "debug_set_frames_in_flight":
@@ -902,29 +950,60 @@ class Run:
         if self.after is not None:
             self.after(len(self.ops) - 1, op, self)
 
-    def rendered(self, k):
-        """render(k) went through: CameraTables' prediction of its last launch against what the implementation reports"""
+    def _resolve_auto_regroups(self):
+        """The policy's verdicts on the updates since the last look, read once (mrt_read_regroup_stats waits): how many regroups
+        the gate let run, from the statistics; at which of the updates, from the device's member_index -- the ordering is
+        replayed (tests/regroup_ref.py, the positions each update left) for every choice of that many updates in order, and the
+        one that gives the device's ordering is taken.  None does: the first choice stands, and the check reports member_index."""
+        if not self.auto_pending:
+            return
+        pending, self.auto_pending = self.auto_pending, []
+        fired = self._dev("read_regroup_stats")["regroups"] - self.auto_seen
+        self.auto_seen += fired
+        if not 0 <= fired <= len(pending):
+            self._fail(f"the policy reports {fired} regroups behind {len(pending)} updates")
+        if fired == 0:
+            return
+        got = self._dev("debug_read_hierarchy")["midx"]
+        replays = []
+        for which in itertools.combinations(range(len(pending)), fired):
+            midx = self.midx
+            for i in which:
+                midx = G.regroup(midx, self.real, self.n_pool, pending[i])
+            replays.append(midx)
+        match = [r for r in replays if np.array_equal(r, got)]
+        self.midx = match[0] if match else replays[0]
+        self._bump("auto regroups", fired)
+
+    def rendered(self, k, listed=None, last=True):
+        """render(k) went through: CameraTables' prediction of its last launch against what the implementation reports.
+        listed: the frames were mrt_render_tiles' over that many tiles -- subset launches unless every tile is listed, held to the
+        same rule (frames.cpp: the launch covers the list, the table the shard; a subset frame counts as a frame the generation
+        survived); the statistics keep them apart ("subset ... launches")."""
         small = self.sh.layout == "small"
-        if k > 1 and self.batching != 0 and small:      # (one launch of several frames, in a form the library chooses: no chain does
-            self.tables_lost = True             # that on the small layout; if one ever does, the prediction ends there.  On the other
-        if self.tables_lost:                    # layouts no launch gets a table, however many launches the frames take)
+        subset = listed is not None and listed < (-(-self.model.w // 8)) * (-(-self.model.h // 8))
+        if k > 1 and self.batching != 0 and small:      # (one launch of several frames, in a form the library chooses: the prediction
+            self.tables_lost = True             # ends there, for the chain.  On the other layouts no launch gets a table, however
+        if self.tables_lost:                    # many launches the frames take)
             return
         for _ in range(k):                      # (0 frames in flight: the library's choice, two or more -- see CameraTables on the slots)
-            want = self.tables.launch(small, self.fif or 2, SPP)
-        if not small:
+            want = self.tables.launch(small, self.fif or 2, self.spp)
+        if not small or not last:               # (last False: more launches of the same call follow)
             return
-        self.stats.setdefault("predicted launches", []).append((self.gen, want[0], want[1], self.fif))
+        pre = "subset " if subset else ""
+        self.stats.setdefault(pre + "predicted launches", []).append((self.gen, want[0], want[1], self.fif))
         if not hasattr(self.impl, "debug_read_camera_masks"):
             return
         info = self._dev("debug_read_camera_masks", table=False)       # (host only: no wait)
-        self.stats.setdefault("mask launches", []).append((self.gen, info["in_force"], self.fif))
-        self.stats.setdefault("list launches", []).append((self.gen, info["lists"], self.fif))
+        self.stats.setdefault(pre + "mask launches", []).append((self.gen, info["in_force"], self.fif))
+        self.stats.setdefault(pre + "list launches", []).append((self.gen, info["lists"], self.fif))
         if info["in_force"] != want[0] or (want[1] is not None and info["lists"] != want[1]):
             self._fail(f"the last launch of render({k}) ran with (a table, the lists) = {(info['in_force'], info['lists'])}, the calls say "
                        f"{want} (switch {self.tables.mode}, generation {self.gen}, {self.fif} frames in flight)")
 
     def check(self):
         m = self.model
+        self._resolve_auto_regroups()
         for name in ("frames_done", "read_framebuffer", "read_counters"):
             _, got, want = self._both(name)
             if name == "read_counters":
@@ -936,8 +1015,10 @@ class Run:
                     self._fail(f"frames_done {got} against {want}")
             elif not _same(got, want):
                 self._fail("framebuffer: " + _describe(got, want))
-        _, got, want = self._both("debug_read_guides")
-        for k in ("rays", "index", "t", "normal", "albedo"):
+        status, got, want = self._both("debug_read_guides")
+        if status != OK and not (status == STATE and getattr(getattr(m, "acc", None), "diverged", False)):
+            self._fail(f"debug_read_guides: both refuse with status {status}")     # (the one refusal a check may meet: a diverged
+        for k in ("rays", "index", "t", "normal", "albedo") if status == OK else ():        # accumulation without the per-tile denoise)
             if not _same(got[k], want[k]):
                 self._fail(f"guide {k}: " + _describe(got[k], want[k]))
         if m.temporal_on:
@@ -949,6 +1030,8 @@ class Run:
                 for k in ("h0", "h1", "prev_xyzr"):
                     if not _same(got[k], want[k]):
                         self._fail(f"temporal {k}: " + _describe(got[k], want[k]))
+        if self.extra_check is not None:
+            self.extra_check(self)
         if self.device and self.device_checks:
             self.check_device()
 
@@ -966,7 +1049,7 @@ class Run:
         bad = np.nonzero(h["midx"] != self.midx)[0]
         if len(bad):
             self._fail(f"member_index: {len(bad)} slots differ from the reference's grouping; first: slot {bad[0]} holds {h['midx'][bad[0]]}, want {self.midx[bad[0]]}")
-        rays, first_cam, ray_tex = check_rays(m.spheres, m.cam_raw)
+        rays, first_cam, ray_tex = check_rays(m.spheres, m.cam_raw, m.w, m.h)
         a2 = (rays[:, 3:].astype(np.float64) ** 2).sum(1)
         if not (np.abs(a2 - 1.0) < 5e-6).all():
             self._fail(f"{int((np.abs(a2 - 1.0) >= 5e-6).sum())} rays are not of unit length")
@@ -1006,7 +1089,7 @@ class Run:
         members, n_top, direct_first = full["nodes"][:full["n_members"]], len(full["top"]), full["direct_first"]
         n_slots = min(4 * n_top, direct_first, len(members))
         words = self._dev("debug_read_camera_lists")
-        ref = CL.camera_lists_ref(members, n_top, direct_first, m.cam_raw, W, H)
+        ref = CL.camera_lists_ref(members, n_top, direct_first, m.cam_raw, m.w, m.h)
         try:
             got, over = CL.unpack(words, n_slots)
         except AssertionError as e:
