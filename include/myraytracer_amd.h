@@ -881,7 +881,11 @@ int mrt_read_temporal(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
  * step); a call that changes only the three numbers keeps it and applies from the next step on.  With `enabled` on, the first
  * mrt_temporal_step brings two more image-sized buffers, the H2 pair (16 bytes a pixel each), with the history's and by the same
  * means; they swap with the other two pairs, are freed when temporal reprojection is disabled or the ctx destroyed (not when
- * the response alone is turned off), and a dropped history zeroes the H2 the next step reads.  MRT_ERR_INVALID_ARG, nothing
+ * the response alone is turned off), and a dropped history zeroes the H2 the next step reads.  mrt_set_shard, which replaces
+ * the ctx's image-sized buffers, releases the H2 pair with the history's four -- the history is dropped by that call anyway
+ * (Invalidation, above) -- and the next step with the response on brings a new pair, zeroed as after any drop; the setting
+ * itself stays.  While the response is off the H2 pair is neither read nor written, so what it held when the response is turned
+ * on again never reaches a step: that change of `enabled` drops the history, and the drop zeroes it.  MRT_ERR_INVALID_ARG, nothing
  * changed: a wrong size, enabled above 1, fast_history outside 1 .. 16, a clamp_sigma that is not finite and > 0, an antilag
  * outside 0 .. 1 (a NaN included), a reserved word that is not 0, a NULL argument.  Every refusal of the step, the read and the
  * present is what it was; mrt_read_temporal and MRT_PRESENT_TEMPORAL read H0 and H1 as before.

@@ -275,7 +275,9 @@ int mrt_debug_read_temporal(mrt_ctx* ctx, float* h0, float* h1, float* prev_xyzr
 int mrt_debug_load_temporal(mrt_ctx* ctx, const float* h0, const float* h1, const float* prev_xyzr, size_t n_spheres,
                             const mrt_camera_raw* prev_cam);
 /* ... and the response's fast history of that pair, H2 = (fr, fg, fb, valid), 4 floats a pixel: the refusals of the two above,
- * and MRT_ERR_STATE while the response is off or before a step with it on has brought the H2 pair; h2 NULL: MRT_ERR_INVALID_ARG.
+ * and MRT_ERR_STATE while the response is off or before a step with it on has brought the H2 pair (the pair comes with the
+ * denoiser's buffers, so with both settings on a denoise before the first step may have brought it already: between enabling
+ * and the first step the answer is either; from that step on it is defined); h2 NULL: MRT_ERR_INVALID_ARG.
  * read: cap in pixels.  load: everything else as mrt_debug_load_temporal with every array NULL leaves it. */
 int mrt_debug_read_temporal_fast(mrt_ctx* ctx, float* h2, size_t cap);
 int mrt_debug_load_temporal_fast(mrt_ctx* ctx, const float* h2);

@@ -5,8 +5,9 @@ mrt_temporal_step, up to forty ops each, checked against a host model.
 
 The runner is motion_chains' own (Run, CameraTables, ChainStopped, ChainMismatch, new_state), through the hooks it has for this
 module: an image size per chain (params["size"]), a Shadow of the caller's, a compare(name, got, want) behind every call both sides
-accepted, an extra_check in every check, and render launches that name their tile list.  The chains are written out (CHAINS); a
-name reproduces its ops anywhere.  On top of motion_chains' and material_chains' ops:
+accepted, an extra_check in every check, and render launches that name their tile list.  Seventeen chains are written out
+(CHAINS); a name reproduces its ops anywhere.  chain(case) draws further ones from a seed (its rules stand above PLAN), and
+`python tests/adaptive_chains.py CASE` prints one.  On top of motion_chains' and material_chains' ops:
 
   ("tracking", on)                          mrt_set_noise_tracking
   ("subset", tiles, k)                      mrt_render_tiles(tiles, k)
@@ -18,6 +19,8 @@ name reproduces its ops anywhere.  On top of motion_chains' and material_chains'
   ("present", "denoised" | "temporal")      mrt_present(rgba8, flip) of that source and an OLDEST acquire that waits
   ("auto_regroup", on, ratio, check_every)  mrt_set_auto_regroup
   ("spp", n) ("rng_mode", m)                mrt_set_samples_per_frame, mrt_set_rng_mode
+  ("temporal_response", enabled, fast_history, clamp_sigma, antilag)    mrt_set_temporal_response (motion_chains.Model has it)
+  ("get_temporal_response",)                mrt_get_temporal_response, compared where it stands
   ("refuse", kind[, seq])                   one call the header refuses, REFUSALS; the next check shows that nothing changed
 
 The model (Model) is material_chains.Model -- motion_chains.Model with mrt_update_materials -- with the accumulation replaced by
@@ -32,7 +35,13 @@ follows the header, not the code, and reads nothing back from the library (K is 
 A check compares what motion_chains.Run.check compares and, bit for bit as uint32 views, tile_frames, read_noise, the newest
 report (its doubles at state_sequences.REPORT_REL) and its tile map, and read_denoised where it is legal; a render_budget's doubles
 are compared bit for bit where the call stands, as tests/test_gpu_adaptive_budget.py compares them."""
+import os
+import sys
+
 import numpy as np
+
+if __name__ == "__main__":                      # (python tests/adaptive_chains.py CASE: the package lies one directory up)
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import adaptive_ref
 import budget_ref
@@ -51,15 +60,38 @@ KEYS = MC.KEYS
 COUNTER_BLOCK, NOISE_RING = 64, 8
 FLIP_Y, DENOISED, TEMPORAL = 1, 8, 16
 K_TABLE_FIRST = 4096                            # noise.cpp, ensure_k_table: the device's table of K(n) begins here and doubles
-REFUSALS = ("denoise-off", "adaptive-on-sums", "budget-on-max-rel", "old-report", "duplicate-tile", "counter-65")
+# mrt_set_temporal_response's refusals, one reason at a time: the setting as it stands but for the one number (or reserved word)
+RESPONSE_REFUSALS = {"fast-history-0": ("fast_history", 0), "fast-history-17": ("fast_history", 17), "clamp-sigma-0": ("clamp_sigma", 0.0),
+                     "clamp-sigma-nan": ("clamp_sigma", float("nan")), "clamp-sigma-inf": ("clamp_sigma", float("inf")),
+                     "antilag-negative": ("antilag", -0.1), "antilag-above-1": ("antilag", 1.5), "antilag-nan": ("antilag", float("nan")),
+                     "response-reserved": ("reserved", 1)}
+REFUSALS = ("denoise-off", "adaptive-on-sums", "budget-on-max-rel", "old-report", "duplicate-tile", "counter-65",
+            "present-temporal-dropped") + tuple(RESPONSE_REFUSALS)
+REFUSAL_STATUS = dict({"denoise-off": STATE, "adaptive-on-sums": STATE, "budget-on-max-rel": STATE, "old-report": STATE,
+                       "duplicate-tile": INVALID_ARG, "counter-65": INVALID_ARG, "present-temporal-dropped": STATE},
+                      **dict.fromkeys(RESPONSE_REFUSALS, INVALID_ARG))
 VOCABULARY = ("tracking", "subset", "query", "adaptive", "budget", "denoise_adaptive", "denoise_variance", "denoise_mix", "read_denoised",
-              "read_temporal", "present", "auto_regroup", "spp", "rng_mode", "refuse", "materials")
+              "read_temporal", "present", "auto_regroup", "spp", "rng_mode", "refuse", "materials", "temporal_response",
+              "get_temporal_response")
+UNION_VOCABULARY = tuple(dict.fromkeys(MC.VOCABULARY + ("refused_materials",) + VOCABULARY))       # what the runner accepts
 SMALL_IMAGE, WIDE_IMAGE = (20, 12), (44, 20)    # 3 x 2 and 6 x 3 tiles, both with a ragged right column and top band
 
 
 class Shadow(XC.Shadow):
+    response = (False, 4, 2.0, 1.0)             # mrt_set_temporal_response's setting as the legal calls have left it
+
     def calls(self, op):
         name, a = op[0], op[1:]
+        if name == "temporal_response":
+            self.response = tuple(a)
+        if name == "refuse" and a[0] in RESPONSE_REFUSALS:
+            field, bad = RESPONSE_REFUSALS[a[0]]
+            now = dict(zip(("enabled", "fast_history", "clamp_sigma", "antilag"), self.response))
+            if field == "reserved":
+                return [("set_temporal_response_raw", tuple(self.response) + (bad,))]
+            return [("set_temporal_response", dict(now, **{field: bad}))]
+        if name == "refuse" and a[0] == "present-temporal-dropped":
+            return [("present", ("rgba8", True, False, False, True))]
         if name == "subset":
             return [("render_tiles", (a[0], a[1]))]
         if name == "present":
@@ -432,6 +464,7 @@ _Q = lambda kind="max_rel", thr=0.3, fl=0.02: ("query", thr, fl, kind)
 _CAM = lambda a, d=13.0, h=2.5: ("set_camera", a, d, h)
 _MAT = lambda kind, seed, restart=False: ("materials", kind, seed, restart)
 _STEP = ("temporal_step",)
+_R = lambda on, fh=4, cs=2.0, al=1.0: ("temporal_response", on, fh, cs, al)
 CHECK = ("check",)
 LONG = K_TABLE_FIRST + 4                        # one tile's run of subset frames that takes its n_t past a K table's length
 
@@ -520,22 +553,479 @@ CHAINS = {
         _U("scatter", 1202), ("regroup",), _S((3,)), _STEP, ("read_denoised",), ("auto_regroup", True, 1.0, 1), _U("jitter", 1203), CHECK,
         _S((5,)), _U("scatter", 1204), _S((0, 1)), _U("jitter", 1205), ("render", 1), _STEP, ("denoise_variance", 1, 3), ("read_denoised",),
         ("read_temporal",), _Q(), CHECK]),
+    # 13: the temporal response at weight 0: steps with the fast history, the clamp and the anti-lag behind subset frames, an
+    # update and a flagged material edit (the NaN stays in "previous"); `enabled` off and on again in the middle, a check of
+    # each dropped history (the read refuses; the H2 the next step reads is zeroes); the numbers alone changed; five refusals
+    "response-0": (_p("small", 0.0), _start("small", 4, 1, temporal=True) + [
+        _R(True, 2, 1.0, 1.0), _STEP, _S((0, 1)), _STEP, _U("jitter", 1301), _S((2, 4)), _STEP, ("get_temporal_response",), CHECK,
+        _MAT("partial", 1302, True), _S((3,)), _STEP, ("read_temporal",), ("refuse", "fast-history-0"), ("refuse", "clamp-sigma-nan"),
+        ("refuse", "antilag-negative"), CHECK,
+        _R(False, 2, 1.0, 1.0), ("refuse", "present-temporal-dropped"), CHECK, _S((1, 5)), _STEP, _R(True, 2, 1.0, 1.0), CHECK,
+        _U("partial", 1303), _S((0, 2)), _STEP,
+        _R(True, 3, 0.5, 0.5), ("render", 1), _STEP, ("present", "temporal"), ("refuse", "response-reserved"), ("refuse", "antilag-nan"), CHECK]),
+    # 13 on the large layout at 0.75, the wider image: the policy regroups between two steps, the per-tile denoise is read right
+    # behind a step, fast_history 1 (every clamped length turns fractional at once)
+    "response-large": (_p("large-quad", 0.75, WIDE_IMAGE), _start("large-quad", 4, 2, temporal=True) + [
+        ("set_regroup_block", 4), ("denoise_adaptive", True), _R(True), _STEP, _S((0, 6, 12)), _STEP, ("auto_regroup", True, 1.0, 1),
+        _U("jitter", 1401), _S((1, 7), 2), _STEP, ("read_denoised",), CHECK,
+        _U("scatter", 1402), _S((2, 8)), _STEP, ("read_temporal",), ("refuse", "fast-history-17"), ("refuse", "clamp-sigma-0"), CHECK,
+        _R(True, 1, 0.5, 1.0), _U("jitter", 1403), ("render", 1), _STEP, ("read_denoised",), ("present", "temporal"),
+        ("refuse", "clamp-sigma-inf"), ("refuse", "antilag-above-1"), CHECK]),
 }
 NAMES = tuple(CHAINS)
 
 
+# ------------------------------------------------------------------ the generator
+#
+# chain(case) draws (params, ops) from np.random.default_rng(case) in a fixed order: a case number reproduces its chain anywhere
+# (`python tests/adaptive_chains.py CASE` prints it).  PLAN[case % len(PLAN)] fixes the layout, max_framebuffer_weight, image and
+# flavour, so the cross product is covered by construction; case // len(PLAN) rotates the segments a flavour is made of.  The
+# generator follows a Shadow (geometry, camera) and a few scalars of its own and emits only chains that are legal to compare:
+#   - at most 40 ops; a check at least every 8 ops and at the end; a segment that would not fit is taken back whole;
+#   - a check follows every regroup before the grouping changes again (a regroup, another scene), and every third update;
+#   - a camera the update left stale (Shadow.camera_stale) is set anew right behind it; coordinates stay below half of 1e7;
+#   - mrt_render_adaptive and mrt_render_budget always name a report (never 0): one of the ring of 8, since the last reset, of
+#     the right map kind -- unless the op is a ("refuse", ...), which breaks exactly one of these;
+#   - they are drawn on a diverged accumulation only, and a subset lists fewer tiles than the image has, so whether the
+#     accumulation has diverged never depends on what a selection or an allocation happened to hold;
+#   - a present is followed by its oldest acquire that waits (one op): at most two presented images are outstanding;
+#   - in counter mode a subset frame has at most 64 samples; 65 is set only for the "counter-65" refusal and taken back behind it;
+#     the samples stay below 96, where the camera tables' decision would depend on the device;
+#   - read_denoised and the denoised present: noise tracking on, and the per-tile denoise enabled once the accumulation has
+#     diverged; read_temporal and the temporal present: a step since the history was last dropped (mrt_set_world,
+#     mrt_temporal_reset, mrt_set_temporal off, a change of the response's `enabled`); mrt_temporal_step: a frame since the reset.
+#     Where one of them is not legal it is drawn only as a refusal, one reason at a time;
+#   - mrt_debug_set_frame_batching(0) with 4 or 8 frames in flight right behind the scene, as _start has them, or neither; the
+#     batched forms (2, 3) only in a chain that began with neither; the forced tables (3, 2) only on the small layout;
+#   - no run of subset frames past the device's K table (LONG): those stay in "denoise-long".
+PLAN = (("small", 1.0, SMALL_IMAGE, "plain"), ("small", 0.0, SMALL_IMAGE, "response"), ("large-quad", 0.75, WIDE_IMAGE, "response"),
+        ("large-lin", 1.0, SMALL_IMAGE, "denoise"), ("small", 0.75, WIDE_IMAGE, "tables"), ("large-lin", 0.0, SMALL_IMAGE, "temporal"),
+        ("large-quad", 1.0, SMALL_IMAGE, "plain"), ("small", 0.75, SMALL_IMAGE, "response"), ("large-lin", 0.75, WIDE_IMAGE, "response"),
+        ("small", 1.0, WIDE_IMAGE, "denoise"), ("large-quad", 0.0, SMALL_IMAGE, "temporal"), ("large-lin", 1.0, WIDE_IMAGE, "plain"))
+SUITE_CASES = tuple(range(24))
+FLAVOURS = ("plain", "temporal", "response", "denoise", "tables")
+MAX_OPS, CHECK_EVERY = 40, 8
+EDIT_KINDS = ("jitter", "scatter", "partial", "shrink", "ground")
+# the segments of a flavour, by the case's ordinal among the cases of that flavour (a segment that does not fit is left out)
+SEGMENTS = {
+    "plain": (("reports", "two_pictures", "refusals"), ("spp", "reset", "edits"), ("spp", "batched", "edits"),
+              ("regroups", "materials", "edits"), ("reports", "two_pictures", "refusals"), ("reset", "spp", "regroups")),
+    "temporal": (("temporal_reset", "temporal", "materials"), ("large", "temporal_reset", "temporal"), ("temporal", "reset", "edits"),
+                 ("temporal_reset", "large")),
+    "response": (("response", "temporal", "toggle"), ("large", "toggle", "response"), ("toggle", "materials", "temporal"),
+                 ("response", "toggle", "edits"), ("toggle", "temporal", "response"), ("response", "large", "toggle"),
+                 ("temporal", "toggle", "materials"), ("toggle", "response", "reports")),
+    "denoise": (("denoise", "reports"), ("denoise", "edits"), ("spp", "denoise"), ("denoise", "materials")),
+    "tables": (("tables",), ("tables",)),
+}
+
+
+def chain(case: int):
+    """-> (params, ops) of a random chain: params as the written chains', ops from the runner's vocabulary (UNION_VOCABULARY)"""
+    import copy
+    rng = np.random.default_rng(case)
+    layout, max_w, size, flavour = PLAN[case % len(PLAN)]
+    p = dict(layout=layout, flavour=flavour, max_w=max_w, size=size)
+    ordinal = [c for c in range(case + 1) if PLAN[c % len(PLAN)][3] == flavour].index(case)
+    segments = SEGMENTS[flavour][ordinal % len(SEGMENTS[flavour])]
+    n_tiles = -(-size[0] // 8) * -(-size[1] // 8)
+    temporal = flavour in ("temporal", "response")
+    sh, ops = Shadow(), []
+    g = dict(frames=0, diverged=False, temporal=False, stepped=False, response=(False, 4, 2.0, 1.0), seq=0, first=1, kinds={},
+             spp=MC.SPP, rng_mode=0, adaptive_denoise=False, owed=False, updates=0, since=0, drawn=0, edited=0)
+    chance = lambda q: bool(rng.random() < q)
+    seed = lambda: int(rng.integers(0, 2 ** 31))
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+
+    def emit(*op):
+        if op != CHECK and ops and (g["since"] >= CHECK_EVERY - 1 or (op[0] in ("regroup", "set_world") and g["owed"])):
+            emit(*CHECK)
+        if op == CHECK and ops[-1] == CHECK:
+            return
+        ops.append(op)
+        sh.calls(op)
+        assert sh.sc is None or max(float(np.abs(sh.xyzr()).max()), float(np.abs(sh.cam[0]).max())) <= 0.5 * MC.LIMIT
+        name = op[0]
+        g["since"] = 0 if name == "check" else g["since"] + 1
+        if name == "check":
+            g.update(updates=0, owed=False)
+        elif name == "regroup":
+            g["owed"] = True
+        elif name == "render":
+            g["frames"] += op[1]
+        elif name == "subset":
+            assert 0 < len(op[1]) < n_tiles and op[2] < K_TABLE_FIRST and (g["rng_mode"] == 0 or g["spp"] <= COUNTER_BLOCK)
+            g["frames"] += op[2]
+            g["diverged"] = True
+        elif name == "reset":
+            g.update(frames=0, diverged=False, first=g["seq"] + 1)
+        elif name == "set_world":
+            g["stepped"] = False
+        elif name == "set_temporal":
+            g.update(temporal=op[1], stepped=g["stepped"] and op[1])
+        elif name == "temporal_step":
+            assert g["temporal"] and g["frames"]
+            g["stepped"] = True
+        elif name == "temporal_reset":
+            g["stepped"] = False
+        elif name == "temporal_response":
+            g.update(stepped=g["stepped"] and op[1] == g["response"][0], response=op[1:])
+        elif name == "query":
+            g["seq"] += 1
+            g["kinds"][g["seq"]] = op[3]
+        elif name in ("adaptive", "budget"):
+            assert g["diverged"] and op[-1] in named({"adaptive": "max_rel", "budget": "sum_s"}[name])
+        elif name == "spp":
+            g["spp"] = op[1]
+        elif name == "rng_mode":
+            g["rng_mode"] = op[1]
+        elif name == "denoise_adaptive":
+            g["adaptive_denoise"] = op[1]
+        elif name in ("read_denoised", "present") and op[-1] != "temporal":
+            assert g["adaptive_denoise"] or not g["diverged"]
+        elif name == "read_temporal" or op == ("present", "temporal"):
+            assert g["temporal"] and g["stepped"]
+        if name == "update":
+            g["updates"] += 1
+            if sh.camera_stale():
+                emit("set_camera", float(rng.uniform(-0.5, 0.5)), float(rng.uniform(11.0, 15.0)), float(rng.uniform(2.0, 3.0)))
+            if g["updates"] >= 3:
+                emit(*CHECK)
+
+    def room(n, updates=1):                     # the next n ops stand together: no check of the two rules falls among them
+        if g["since"] + n > CHECK_EVERY - 1 or g["updates"] + updates >= 3:
+            emit(*CHECK)
+
+    def named(kind):                            # the reports of one map kind that a selection or an allocation may name
+        oldest = max(g["first"], g["seq"] - NOISE_RING + 1, 1)
+        return [s for s in range(oldest, g["seq"] + 1) if g["kinds"][s] == kind]
+
+    def report(kind):
+        if not named(kind):
+            query(kind)
+        return pick(named(kind))
+
+    def tiles(most=4):
+        k = int(rng.integers(1, min(most, n_tiles - 1) + 1))
+        return tuple(sorted(int(t) for t in rng.choice(n_tiles, k, replace=False)))
+
+    def subset(most=4, frames=None):
+        emit("subset", tiles(most), int(rng.integers(1, 3)) if frames is None else frames)
+
+    def update(kind=None):
+        g["drawn"] += 1
+        emit("update", kind or EDIT_KINDS[(case + g["drawn"]) % len(EDIT_KINDS)], seed())
+
+    def materials(restart=False):
+        g["edited"] += 1
+        emit("materials", XC.MATERIAL_KINDS[(case + g["edited"]) % len(XC.MATERIAL_KINDS)], seed(), restart)
+
+    def query(kind=None):
+        emit("query", pick((0.2, 0.3, 0.5)), 0.02, kind or pick(("max_rel", "sum_s")))
+
+    def camera():
+        emit("set_camera", float(rng.uniform(-0.4, 0.4)), float(rng.uniform(11.0, 15.0)), float(rng.uniform(2.0, 3.0)))
+
+    def step():
+        if not g["frames"]:
+            emit("render", 1)
+        emit("temporal_step")
+
+    def diverge():
+        if not g["diverged"]:
+            subset()
+
+    def numbers():
+        return pick((1, 2, 4, 16)), pick((0.5, 1.0, 2.0, 3.0)), pick((0.0, 0.5, 1.0))
+
+    # -- the segments (the situations of the written chains, with drawn tiles, kinds, seeds and numbers)
+    def seg_edits():                            # 1: updates between subset frames queued without a wait, then whole frames
+        diverge()
+        room(5, 2)
+        subset()
+        update()
+        subset()
+        update()
+        emit("render", int(rng.integers(2, 4)))
+
+    def seg_regroups():                         # 2: the caller's regroup and the policy's, subset frames on both sides
+        diverge()
+        room(4)
+        subset()
+        update(pick(("scatter", "jitter")))
+        emit("regroup")
+        subset()
+        update("jitter")
+        emit(*CHECK)
+        emit("auto_regroup", True, 1.0, 1)
+        subset()
+        update(pick(("scatter", "jitter")))
+        subset()
+        emit(*CHECK)
+        emit("auto_regroup", False, pick((1.0, 2.0)), pick((1, 2)))
+
+    def seg_materials():                        # 3: material edits between subset frames; the flagged one with a step behind it
+        diverge()
+        room(5)
+        subset()
+        materials()
+        subset()
+        materials()
+        subset()
+        if g["temporal"]:
+            room(3)
+            subset()
+            materials(True)
+            step()
+
+    def seg_two_pictures():                     # 4: another camera and another scene on a diverged accumulation, no reset
+        diverge()
+        query()
+        camera()
+        subset()
+        emit("render", 1)
+        emit("set_world", pick([l for l in ("small", "large-quad", "large-lin") if l != sh.layout]))
+        subset()
+        emit("render", int(rng.integers(1, 3)))
+        query("sum_s")
+        emit("budget", int(rng.integers(6, 25)), int(rng.integers(2, 4)), report("sum_s"))
+
+    def seg_temporal():                         # 5: steps behind subset frames, both orders of update and subset, read and presented
+        room(2)
+        subset()
+        step()
+        room(3)
+        update("jitter")
+        subset()
+        step()
+        room(3)
+        subset()
+        update(pick(("jitter", "partial")))
+        step()
+        if g["stepped"]:
+            emit("read_temporal")
+            emit("present", "temporal")
+
+    def seg_temporal_reset():
+        emit("temporal_reset")
+        emit(*CHECK)                            # dropped: the read refuses
+        emit("refuse", "present-temporal-dropped")
+        emit("render", 1)
+        step()
+
+    def seg_response():                         # the response on: steps behind subset frames, the numbers alone changed between two
+        if not g["response"][0]:
+            emit("temporal_response", True, *numbers())
+        step()
+        room(2)
+        subset()
+        step()
+        emit("get_temporal_response")
+        emit("temporal_response", True, *numbers())
+        room(3)
+        subset()
+        update("jitter")
+        step()
+        if chance(0.5):
+            emit("read_temporal")
+
+    def seg_toggle():                           # `enabled` changed between two steps, a check of each dropped history
+        if not g["stepped"]:
+            step()
+        on, *nums = g["response"]
+        emit("temporal_response", not on, *nums)
+        emit("refuse", "present-temporal-dropped") if chance(0.5) else emit(*CHECK)
+        room(2)
+        subset()
+        step()
+        emit("temporal_response", on, *(numbers() if chance(0.5) else nums))
+        emit(*CHECK)
+        room(2)
+        subset()
+        step()
+
+    def seg_denoise():                          # 6: the per-tile denoise by mode and blend, behind an update and a material edit
+        emit("denoise_adaptive", True)
+        diverge()
+        mode = (case // 3) % 3
+        emit("denoise_variance", mode, int(rng.integers(2, 7)))
+        room(3)
+        subset()
+        update("jitter")
+        emit("read_denoised")
+        emit("denoise_mix", True, pick((1.0, 2.0)))
+        room(2)
+        materials()
+        emit("read_denoised")
+        emit("denoise_variance", (mode + 1) % 3, int(rng.integers(2, 7)))
+        emit("read_denoised")
+        emit("denoise_mix", False, 1.0)
+        subset()
+        emit("read_denoised")
+        emit("present", "denoised")
+
+    def seg_reports():                          # 7: reports of both kinds on both sides of an edit, the older ones named
+        diverge()
+        query("max_rel")
+        query("sum_s")
+        before = g["seq"]
+        subset()
+        update("jitter")
+        query("max_rel")
+        query("sum_s")
+        emit("adaptive", int(rng.integers(1, 3)), [s for s in named("max_rel") if s <= before][-1])
+        emit("budget", int(rng.integers(6, 37)), int(rng.integers(2, 5)), [s for s in named("sum_s") if s <= before][-1])
+        emit("refuse", "adaptive-on-sums", named("sum_s")[-1])
+        emit("refuse", "budget-on-max-rel", named("max_rel")[-1])
+
+    def seg_refusals():
+        diverge()
+        emit("refuse", "duplicate-tile")
+        if not g["adaptive_denoise"]:
+            emit("refuse", "denoise-off")
+        emit(*CHECK)
+
+    def seg_tables():                           # 8: the masks forced, then the lists, subset launches under all three generations
+        for mode in (3, 2):
+            emit("set_camera_masks", mode)
+            if mode == 2:
+                emit("set_frames_in_flight", 8)
+            kinds = ["update", "regroup", "camera"]
+            rng.shuffle(kinds)
+            subset(2)
+            for kind in kinds:
+                update(pick(("jitter", "partial"))) if kind == "update" else emit("regroup") if kind == "regroup" else camera()
+                subset(2)
+            emit("render", int(rng.integers(1, 3)))
+            emit(*CHECK)
+
+    def seg_reset():                            # 9: a reset of a diverged, moving chain; the uniform paths; divergence again
+        diverge()
+        update("jitter")
+        subset()
+        if not g["adaptive_denoise"]:
+            emit("refuse", "denoise-off")
+        query()
+        old = g["seq"]
+        emit(*CHECK)
+        emit("reset")
+        if g["temporal"]:
+            emit("refused", "step-after-reset", seed())
+        emit("render", 2)
+        emit("read_denoised")
+        emit("refuse", "old-report", old)
+        query()
+        emit(*CHECK)
+        subset()
+
+    def seg_spp():                              # 10: the samples change between subset frames; counter mode at 64, 65 refused
+        room(3)
+        subset(2, 1)
+        emit("spp", pick((1, 3, 5)))
+        subset(2, 1)
+        room(3)
+        emit("rng_mode", 1)
+        emit("spp", 64)
+        subset(1, 1)
+        room(3)
+        emit("spp", 65)
+        emit("refuse", "counter-65")
+        emit(*CHECK)
+        emit("spp", MC.SPP)
+        emit("rng_mode", 0)
+
+    def seg_batched():                          # 11: batched whole frames behind an update, in both forms of a batch
+        diverge()
+        for form in (2, 3):
+            room(3)
+            emit("set_frame_batching", form)
+            update(pick(("jitter", "partial")))
+            emit("render", int(rng.integers(2, 5)))
+            subset()
+
+    def seg_large():                            # 12: subset frames, a regroup, the policy, a step and the per-tile denoise together
+        emit("set_regroup_block", 4)
+        emit("denoise_adaptive", True)
+        room(3)
+        subset()
+        update("jitter")
+        subset()
+        if g["temporal"]:
+            step()
+        update("scatter")
+        emit("regroup")
+        subset()
+        if g["temporal"]:
+            step()
+        emit("read_denoised")
+        emit("auto_regroup", True, 1.0, 1)
+        update("jitter")
+        emit(*CHECK)
+
+    segs = dict(edits=seg_edits, regroups=seg_regroups, materials=seg_materials, two_pictures=seg_two_pictures, temporal=seg_temporal,
+                temporal_reset=seg_temporal_reset, response=seg_response, toggle=seg_toggle, denoise=seg_denoise, reports=seg_reports,
+                refusals=seg_refusals, tables=seg_tables, reset=seg_reset, spp=seg_spp, batched=seg_batched, large=seg_large)
+
+    # -- the start: a scene, tracking, the per-launch settings as _start has them, the switches that hold for the chain
+    in_flight = 4 if flavour == "tables" else None if "batched" in segments else (4, 8, None)[case % 3]
+    for op in _start(layout, in_flight, 1 if temporal else 2, temporal):
+        emit(*op)
+    emit("set_sweep", case % 3)
+    if layout != "small":
+        emit("set_regroup_block", (4, 0)[(case // 2) % 2])
+    elif flavour != "tables" and case % 2:
+        emit("set_camera_masks", bool(case % 4 == 1))
+    if flavour == "response":
+        emit("temporal_response", True, *numbers())
+    if temporal:
+        step()
+    # one refusal of each family by the case number: every kind turns up in the suite
+    emit("refuse", tuple(RESPONSE_REFUSALS)[case % len(RESPONSE_REFUSALS)])
+    kinds = [k for k in MC.REFUSALS if k != ("step-while-off" if temporal else "step-after-reset") and k != "step-after-reset"]
+    emit("refused", kinds[case % len(kinds)], seed())
+    if case % 4 == 1:
+        emit("refused_materials")
+    for name in segments + tuple(n for n in ("materials", "edits", "refusals") if n not in segments):      # (what still fits)
+        saved = (len(ops), copy.deepcopy(g), copy.deepcopy(sh), copy.deepcopy(rng.bit_generator.state))
+        segs[name]()
+        if len(ops) > MAX_OPS - 1:              # (it does not fit: taken back whole, the draws with it)
+            del ops[saved[0]:]
+            g.clear()
+            g.update(saved[1])
+            sh.__dict__.clear()
+            sh.__dict__.update(saved[2].__dict__)
+            rng.bit_generator.state = saved[3]
+    emit(*CHECK)
+    assert len(ops) <= MAX_OPS and {op[0] for op in ops} <= set(UNION_VOCABULARY)
+    return p, ops
+
+
 def new_model(O, name, cls=None):
-    return MC.new_model(O, CHAINS[name][0], cls or Model)
+    return MC.new_model(O, params_and_ops(name)[0], cls or Model)
+
+
+def params_and_ops(name):
+    """a written chain by its name, a random one by its case number"""
+    return chain(name) if isinstance(name, int) else CHAINS[name]
 
 
 def new_run(name, impl, model, O, stats=None, after=None, device_checks=True):
-    return MC.Run(f"adaptive chain {name}", CHAINS[name][0], impl, model, O, stats, after, device_checks, shadow=Shadow(),
+    label = f"random adaptive chain {name} (python tests/adaptive_chains.py {name})" if isinstance(name, int) else f"adaptive chain {name}"
+    return MC.Run(label, params_and_ops(name)[0], impl, model, O, stats, after, device_checks, shadow=Shadow(),
                   compare=compare, extra_check=extra_check)
 
 
 def run(name, impl, model, O, stats=None, after=None, device_checks=True):
     """chain `name` on impl and model in lock step (motion_chains.Run); raises ChainMismatch at the first difference"""
     r = new_run(name, impl, model, O, stats, after, device_checks)
-    for op in CHAINS[name][1]:
+    for op in params_and_ops(name)[1]:
         r.step(op)
     return r
+
+
+if __name__ == "__main__":                      # the case's params and ops, one per line, for replay and bug reports (no device)
+    for case in (int(a) for a in sys.argv[1:]):
+        params, case_ops = chain(case)
+        print(f"case {case}: {params}")
+        for i, op in enumerate(case_ops):
+            print(f"{i:3d} {op!r}")

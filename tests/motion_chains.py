@@ -15,6 +15,8 @@ chain(case) draws (params, ops) from np.random.default_rng(case); ops are plain 
   ("render", k) ("reset",) ("set_frames_in_flight", n) ("set_frame_batching", 0) ("set_sweep", m)
   ("set_camera_masks", on)         False / True (1: the library's rule); the list chains: 0, 2 (the lists), 3 (the masks)
   ("set_temporal", on) ("temporal_step",) ("temporal_reset",)
+  ("temporal_response", enabled, fast_history, clamp_sigma, antilag)     mrt_set_temporal_response (no chain of this module draws
+  ("get_temporal_response",)       it: tests/adaptive_chains.py does); the getter is compared where it stands
   ("refused", kind, seed)          one call the header refuses, REFUSALS
   ("check",)
 Shadow turns an op into calls -- it follows the geometry and the camera the way the generator did when it drew the op, without
@@ -49,7 +51,14 @@ mrt_set_auto_regroup, read at the next check (or regroup, or scene) and replayed
 
 The model is host only.  It holds the spheres, the camera, the (scene, camera) of every frame queued since the last reset, the
 guides' staleness, and the temporal state (h0, h1, previous spheres, previous derived camera, dropped / stepped); frames and
-counters are the oracle's, guides denoise_ref's, a step and the image temporal_ref's.  Nothing is read back from the library."""
+counters are the oracle's, guides denoise_ref's, a step and the image temporal_ref's.  Nothing is read back from the library.
+
+The temporal response (mrt_set_temporal_response) is in the model as the header's contract paragraph has it: the setting outlives
+mrt_reset, mrt_set_world and mrt_set_camera; a change of `enabled` drops the history, a change of the three numbers alone keeps
+it; a dropped history zeroes the H2 the next step reads.  With it on a step is temporal_response_ref's (steps 3 to 4c), whose
+fractional lengths the next step, the image and its variance take as they are; a check then holds the fast history H2 too
+(mrt_debug_read_temporal_fast), a dropped one's included once a step has brought the pair."""
+import ctypes
 import itertools
 import math
 
@@ -62,6 +71,7 @@ import myraytracer_amd as M
 import refit_ref as R
 import regroup_ref as G
 import temporal_ref as T
+import temporal_response_ref as TR
 from common import mismatch_report, to_oracle_spheres
 from test_gpu_superset import _rays_for
 from test_gpu_update_spheres import DEPTH, H, HASH_LAYOUTS, KEYS, SEED, SPP, W, scene
@@ -251,7 +261,9 @@ class Shadow:
         simple = {"regroup": "regroup_spheres", "set_regroup_block": "debug_set_regroup_block", "render": "render", "reset": "reset",
                   "set_frames_in_flight": "debug_set_frames_in_flight", "set_frame_batching": "debug_set_frame_batching",
                   "set_sweep": "debug_set_sweep", "set_camera_masks": "debug_set_camera_masks", "set_temporal": "set_temporal",
-                  "temporal_step": "temporal_step", "temporal_reset": "temporal_reset"}
+                  "temporal_step": "temporal_step", "temporal_reset": "temporal_reset", "get_temporal_response": "temporal_response"}
+        if name == "temporal_response":
+            return [("set_temporal_response", dict(enabled=a[0], fast_history=a[1], clamp_sigma=a[2], antilag=a[3]))]
         return [(simple[name], a)] if name != "check" else []
 
 
@@ -503,6 +515,11 @@ class Model:
         self.temporal_on, self.stepped, self.cleared = False, False, True
         self.h0 = self.h1 = self.prev_xyzr = self.prev_cam = None
         self.found = []                         # per step: (first since a drop, pixels that found history, pixels)
+        # the temporal response (mrt_set_temporal_response): the setting, the fast history H2, and whether a step with the
+        # response on has brought the H2 pair since temporal reprojection was enabled (the diagnostic's refusal is defined then)
+        self.response = dict(enabled=False, **{k: (v if k == "fast_history" else float(np.float32(v))) for k, v in TR.R_DEFAULTS.items()})
+        self.h2, self.h2_brought = None, False
+        self.response_steps = []                # per step with the response on: (pixels the clamp moved, fractional lengths stored)
 
     # ---- what the seeded defects change
     def _after_update(self):
@@ -655,7 +672,52 @@ class Model:
     def set_temporal(self, enabled):
         if not enabled and self.temporal_on:
             self._drop_history()
+            self.h2_brought = False             # (the H2 pair is freed with the history's buffers)
         self.temporal_on = bool(enabled)
+
+    # ---- the temporal response: the header's contract paragraph.  mrt_reset, mrt_set_world*, mrt_set_camera keep the setting
+    #      (nothing here touches self.response but set_temporal_response itself)
+    def set_temporal_response(self, enabled, fast_history=None, clamp_sigma=None, antilag=None, reserved=0):
+        new = dict(self.response, enabled=bool(enabled))
+        for k, v in (("fast_history", fast_history), ("clamp_sigma", clamp_sigma), ("antilag", antilag)):
+            if v is not None:
+                new[k] = int(v) if k == "fast_history" else float(np.float32(v))
+        cs, al = new["clamp_sigma"], new["antilag"]
+        if (not 1 <= new["fast_history"] <= 16 or not (math.isfinite(cs) and cs > 0) or not 0.0 <= al <= 1.0 or reserved != 0
+                or enabled not in (0, 1, False, True)):
+            raise Refused(INVALID_ARG, "set_temporal_response")
+        if new["enabled"] != self.response["enabled"]:
+            self._response_enabled_changed()
+        self.response = new                     # (only the three numbers: the history stays, the next step takes them)
+
+    def set_temporal_response_raw(self, enabled, fast_history, clamp_sigma, antilag, reserved):
+        """the struct as it is, a reserved word included (the package's wrapper cannot write one)"""
+        self.set_temporal_response(enabled, fast_history, clamp_sigma, antilag, reserved)
+
+    def temporal_response(self):
+        return self.response["enabled"], {k: v for k, v in self.response.items() if k != "enabled"}
+
+    # what the seeded defects of tests/test_adaptive_chains_host.py change
+    def _response_enabled_changed(self):
+        self._drop_history()                    # "A call that changes `enabled` drops the history, as mrt_temporal_reset does"
+
+    def _h2_after_drop(self):
+        return np.zeros((self.h, self.w, 4), np.float32)        # "a dropped history zeroes the H2 the next step reads"
+
+    def _stored_length(self, h0):
+        return h0                               # "The stored length may therefore be fractional"
+
+    def _clamp_indices(self, h1):
+        return h1                               # 4b: "... and the index bits of H1'_q equal the pixel's own"
+
+    def _response_step(self, cur, g, now, Mx, o):
+        rp = {k: v for k, v in self.response.items() if k != "enabled"}
+        h2 = self.h2 if self.h2 is not None else np.zeros((self.h, self.w, 4), np.float32)
+        o0, o1, o2, info = TR.reproject(cur, g["rays"], g["index"], g["t"], now, self.prev_xyzr, Mx, o, self.h0, self.h1, h2, None, rp)
+        out, cinfo = TR.clamp(o0, self._clamp_indices(o1), o2, rp)
+        out = self._stored_length(out)
+        self.response_steps.append((int(cinfo["moved"].sum()), int((out[..., 3] != np.floor(out[..., 3])).sum())))
+        return out, o1, o2, info
 
     def _temporal_check(self, where, stepped):
         if not self.temporal_on:
@@ -675,10 +737,16 @@ class Model:
             self.h0 = np.zeros((self.h, self.w, 4), np.float32)
             self.h1 = np.zeros((self.h, self.w, 4), np.float32)
             self.prev_cam = self.cam_raw
+            if self.response["enabled"]:
+                self.h2 = self._h2_after_drop()
             self.cleared = False
         Mx, o = T.camera_matrix(self.prev_cam)
         now = self.xyzr()
-        self.h0, self.h1, info = T.step(self.read_framebuffer(), g["rays"], g["index"], g["t"], now, self.prev_xyzr, Mx, o, self.h0, self.h1)
+        if self.response["enabled"]:            # steps 3 and 4 with the fast history, then 4b and 4c
+            self.h0, self.h1, self.h2, info = self._response_step(self.read_framebuffer(), g, now, Mx, o)
+            self.h2_brought = True
+        else:
+            self.h0, self.h1, info = T.step(self.read_framebuffer(), g["rays"], g["index"], g["t"], now, self.prev_xyzr, Mx, o, self.h0, self.h1)
         self.prev_xyzr, self.prev_cam, self.stepped = now, self.cam_raw, True
         self.found.append((first, int(info["found"].sum()), info["found"].size))
 
@@ -694,6 +762,14 @@ class Model:
     def debug_read_temporal(self, n_spheres):
         self._temporal_check("debug_read_temporal", True)
         return {"h0": self.h0.copy(), "h1": self.h1.copy(), "prev_xyzr": self.prev_xyzr.copy()}
+
+    def debug_read_temporal_fast(self):
+        """the H2 the next step reads: a dropped history's reads as zeroes (the runner asks only once a step has brought the pair)"""
+        self._temporal_check("debug_read_temporal_fast", False)
+        if not self.response["enabled"] or not self.h2_brought:
+            raise Refused(STATE, "debug_read_temporal_fast")
+        h2 = self._h2_after_drop() if self.cleared else self.h2
+        return np.zeros((self.h, self.w, 4), np.float32) if h2 is None else h2.copy()
 
 
 def new_model(O, params, cls=None):
@@ -779,9 +855,22 @@ class CameraTables:
 
 # ------------------------------------------------------------------ applying and comparing
 
+def _raw_response(st, enabled, fast_history, clamp_sigma, antilag, reserved):
+    """mrt_set_temporal_response on a real context with the struct written out, a reserved word included"""
+    p = M._lib.MrtTemporalResponse()
+    st._L.mrt_temporal_response_default(ctypes.byref(p))
+    p.enabled, p.fast_history, p.clamp_sigma, p.antilag = int(enabled), fast_history, clamp_sigma, antilag
+    p.reserved[len(p.reserved) - 1] = reserved
+    st._check(st._L.mrt_set_temporal_response(st._ctx, ctypes.byref(p)), "mrt_set_temporal_response")
+
+
 def _call(obj, name, args):
     try:
+        if name == "set_temporal_response_raw" and not hasattr(obj, name):
+            return OK, _raw_response(obj, *args)
         v = getattr(obj, name)
+        if isinstance(args, dict):              # (keyword arguments: mrt_set_temporal_response's wrapper takes its numbers by name)
+            return OK, v(**args)
         return OK, (v(*args) if callable(v) else v)
     except (Refused, M.MrtError) as e:
         return e.status, None
@@ -901,6 +990,8 @@ class Run:
                 bad = self.compare(name, got, want)
                 if bad:
                     self._fail(f"{name}: {bad}")
+            if name == "temporal_response" and status == OK and got != want:
+                self._fail(f"temporal_response: {got} against the model's {want}")
             if name == "set_samples_per_frame" and status == OK:
                 self.spp = int(args[0])
             if name == "set_auto_regroup" and status == OK:
@@ -1030,6 +1121,16 @@ class Run:
                 for k in ("h0", "h1", "prev_xyzr"):
                     if not _same(got[k], want[k]):
                         self._fail(f"temporal {k}: " + _describe(got[k], want[k]))
+            # the fast history the next step reads, stepped or dropped (a dropped one reads as zeroes): asked wherever a step
+            # with the response on has brought the H2 pair, which is where the diagnostic's answer is defined
+            if m.response["enabled"] and m.h2_brought and m.spheres is not None:
+                status, got, want = self._both("debug_read_temporal_fast")
+                if status != OK:
+                    self._fail(f"debug_read_temporal_fast: both refuse with status {status}")
+                if not _same(got, want):
+                    self._fail("temporal h2: " + _describe(got, want))
+                self.stats["h2 checks"] = self.stats.get("h2 checks", 0) + 1
+                self.stats["h2 checks of a dropped history"] = self.stats.get("h2 checks of a dropped history", 0) + bool(m.cleared)
         if self.extra_check is not None:
             self.extra_check(self)
         if self.device and self.device_checks:

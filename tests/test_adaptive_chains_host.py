@@ -4,6 +4,12 @@ references (tests/state_model.py without an edit, motion_chains.Model without a 
 summation order); run model against model the chains meet the conditions without which the GPU tests would pass vacuously
 (selections that are neither empty nor everything, allocations with unequal and with equal counts, diverged checks, denoises over
 distinct n_t); and the runner reports every seeded defect of a stand-in, with the chains that catch it."""
+import hashlib
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -34,7 +40,7 @@ def _diverged(ops, i):
 
 def test_shape_vocabulary_and_checks():
     names, sizes, queued = set(), [], 0
-    assert 12 <= len(AC.NAMES) <= 16
+    assert 12 <= len(AC.NAMES) <= 17
     for name in AC.NAMES:
         p, ops = AC.CHAINS[name]
         assert len(ops) <= 40 and ops[0] == ("set_world", p["layout"]) and ops[-1] == ("check",), (name, len(ops))
@@ -63,12 +69,13 @@ def _windows(ops, pattern):
     return [i for i in range(len(ops) - len(pattern) + 1) if names[i:i + len(pattern)] == list(pattern)]
 
 
-def test_every_situation_is_present():
-    all_ops = {n: _ops(n) for n in AC.NAMES}
+def _situations(chains):
+    """the twelve situations read from the ops of `chains` (name or case -> (params, ops)): which chains hold each, and the
+    kinds, modes and weights that the conditions on them name"""
     found = {k: [] for k in range(1, 13)}
     kinds_1, kinds_3, denoise_6, long_6 = set(), set(), set(), []
-    for n, ops in all_ops.items():
-        p = AC.CHAINS[n][0]
+    for n, (p, ops) in chains.items():
+        n = str(n)
         # 1: subset, update, subset, update, render(2), ..., check, behind the divergence
         for i in _windows(ops, ("subset", "update", "subset", "update", "render")):
             if ops[i + 4][1] >= 2 and _diverged(ops, i + 1):
@@ -161,6 +168,11 @@ def test_every_situation_is_present():
         if (p["layout"] == "large-quad" and _windows(ops, ("subset", "update", "subset")) and "regroup" in names and
                 ("auto_regroup", True, 1.0, 1) in ops and _windows(ops, ("subset", "temporal_step")) and "read_denoised" in names):
             found[12].append(n)
+    return found, kinds_1, kinds_3, denoise_6, long_6
+
+
+def test_every_situation_is_present():
+    found, kinds_1, kinds_3, denoise_6, long_6 = _situations({n: AC.CHAINS[n] for n in AC.NAMES})
     assert kinds_1 >= {"jitter", "scatter", "partial", "shrink", "ground"} and kinds_3 == set(XC.MATERIAL_KINDS), (kinds_1, kinds_3)
     assert denoise_6 == {(m, x) for m in (0, 1, 2) for x in (False, True)}, denoise_6
     assert long_6 and {w for _, w in found[5]} == {0.0, 0.75}, (long_6, found[5])
@@ -171,14 +183,21 @@ def test_every_situation_is_present():
 def test_every_chain_is_legal(oracle):
     """the model accepts every call but the ones a chain draws as refusals, and refuses those for the one reason drawn"""
     status = {"denoise-off": MC.STATE, "adaptive-on-sums": MC.STATE, "budget-on-max-rel": MC.STATE, "old-report": MC.STATE,
-              "duplicate-tile": MC.INVALID_ARG, "counter-65": MC.INVALID_ARG}
+              "duplicate-tile": MC.INVALID_ARG, "counter-65": MC.INVALID_ARG, "present-temporal-dropped": MC.STATE,
+              **dict.fromkeys(AC.RESPONSE_REFUSALS, MC.INVALID_ARG)}
+    assert status == AC.REFUSAL_STATUS
     for name in AC.NAMES:
         m, sh = AC.new_model(oracle, name), AC.Shadow()
         for op in _ops(name):
+            before = m.temporal_response()
             for call, args in sh.calls(op):
                 got, _ = MC._call(m, call, args)
                 assert got == (status[op[1]] if op[0] == "refuse" else MC.OK), (name, op, call, got)
             if op[0] == "refuse":               # one reason at a time: the state allows the call, only the reason drawn does not
+                if op[1] in AC.RESPONSE_REFUSALS:
+                    assert m.temporal_response() == before == (sh.response[0], dict(zip(("fast_history", "clamp_sigma", "antilag"), sh.response[1:])))
+                if op[1] == "present-temporal-dropped":
+                    assert m.temporal_on and m.spheres is not None and not m.stepped
                 if op[1] in ("adaptive-on-sums", "budget-on-max-rel"):
                     assert m._oldest() <= op[2] <= m.noise_seq
                 if op[1] == "old-report":
@@ -424,7 +443,36 @@ class ResetLeavesTheDivergence(AC.Model):
         self.acc.diverged = was
 
 
-DEFECTS = [SubsetTakesTheSceneBeforeTheUpdate, SubsetTakesTheCameraBeforeTheChange, SubsetTakesTheMaterialsBeforeTheEdit,
+class ResponseSurvivesEnableChange(AC.Model):
+    """a call that changes the response's `enabled` keeps the history"""
+    def _response_enabled_changed(self):
+        pass
+
+
+class FastHistoryNotZeroedAfterDrop(AC.Model):
+    """a dropped history leaves the H2 the next step reads as it was"""
+    def _h2_after_drop(self):
+        return self.h2 if self.h2 is not None else super()._h2_after_drop()
+
+
+class AntilagRoundsTheLength(AC.Model):
+    """4c stores N'' rounded to an integer"""
+    def _stored_length(self, h0):
+        h0 = h0.copy()
+        h0[..., 3] = np.rint(h0[..., 3])
+        return h0
+
+
+class ClampCountsOtherSpheres(AC.Model):
+    """4b counts a window tap whatever sphere its H1' names"""
+    def _clamp_indices(self, h1):
+        h1 = h1.copy()
+        h1[..., 3] = 0.0
+        return h1
+
+
+RESPONSE_DEFECTS = [ResponseSurvivesEnableChange, FastHistoryNotZeroedAfterDrop, AntilagRoundsTheLength, ClampCountsOtherSpheres]
+DEFECTS = RESPONSE_DEFECTS + [SubsetTakesTheSceneBeforeTheUpdate, SubsetTakesTheCameraBeforeTheChange, SubsetTakesTheMaterialsBeforeTheEdit,
            LastFrameOfABatchNotCounted, WholeFrameAtTheUniformWeight, TileDenoiseKeepsStaleGuides,
            StepOnADivergedAccumulationKeepsStaleGuides, DenoiseTakesKOfFramesDone, SumMapSkipsTheRaggedColumn, BudgetTakesTheNewestReport,
            ResetLeavesTheDivergence]
@@ -445,6 +493,25 @@ CAUGHT_BY = {
     "ResetLeavesTheDivergence": ["reset"],
 }
 
+# ... and the two written chains with the response on, behind the fifteen the lists above were recorded on
+for _defect, _more in {"SubsetTakesTheSceneBeforeTheUpdate": ["response-0", "response-large"],
+                       "SubsetTakesTheCameraBeforeTheChange": ["response-0", "response-large"],
+                       "SubsetTakesTheMaterialsBeforeTheEdit": ["response-0"], "LastFrameOfABatchNotCounted": ["response-large"],
+                       "WholeFrameAtTheUniformWeight": ["response-large"],
+                       "StepOnADivergedAccumulationKeepsStaleGuides": ["response-0", "response-large"],
+                       "DenoiseTakesKOfFramesDone": ["response-large"]}.items():
+    CAUGHT_BY[_defect] = CAUGHT_BY[_defect] + _more
+CAUGHT_BY.update({"ResponseSurvivesEnableChange": ["response-0"], "FastHistoryNotZeroedAfterDrop": ["response-0"],
+                  "AntilagRoundsTheLength": ["response-0", "response-large"], "ClampCountsOtherSpheres": ["response-0", "response-large"]})
+# The random chains (AC.SUITE_CASES) that report each defect.  The response's: every case that does, of the cases that set the
+# response at all (no other can); the others': the first case that does, in the suite's order
+SUITE_CAUGHT_BY = {"ResponseSurvivesEnableChange": [2, 7, 8, 13, 19, 20], "FastHistoryNotZeroedAfterDrop": [2, 7, 8, 13, 19, 20],
+                   "AntilagRoundsTheLength": [1, 14, 20], "ClampCountsOtherSpheres": [1, 2, 7, 8, 13, 14, 19, 20]}
+SUITE_FIRST_CATCH = {"SubsetTakesTheSceneBeforeTheUpdate": 0, "SubsetTakesTheCameraBeforeTheChange": 0,
+                     "SubsetTakesTheMaterialsBeforeTheEdit": 3, "LastFrameOfABatchNotCounted": 0, "WholeFrameAtTheUniformWeight": 0,
+                     "TileDenoiseKeepsStaleGuides": 3, "StepOnADivergedAccumulationKeepsStaleGuides": 1, "DenoiseTakesKOfFramesDone": 2,
+                     "SumMapSkipsTheRaggedColumn": 0, "BudgetTakesTheNewestReport": 0, "ResetLeavesTheDivergence": 6}
+
 
 @pytest.mark.parametrize("defect", DEFECTS, ids=lambda c: c.__name__)
 def test_the_runner_catches_a_defective_stand_in(oracle, defect):
@@ -457,3 +524,177 @@ def test_the_runner_catches_a_defective_stand_in(oracle, defect):
     print(f"{defect.__name__}: caught by {caught}")
     assert caught, defect.__name__
     assert caught == CAUGHT_BY[defect.__name__], (defect.__name__, caught)
+
+
+# ------------------------------------------------------------------ the random chains (adaptive_chains.chain, SUITE_CASES)
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adaptive_chain_cases.json")
+# the situations of the written chains that no random chain holds, and why (at most two, none of the response's)
+NOT_REACHED = {"6, the long runs": "a run of 4100 subset frames stays in the written chain denoise-long",
+               "7, nine queries in a row": "with the refusal behind them they are ten ops, and the generator checks at least every 8"}
+
+
+def _suite():
+    return {c: AC.chain(c) for c in AC.SUITE_CASES}
+
+
+def _response_windows(ops):
+    """(steps with the response on right behind a subset frame, changes of `enabled` with a step before and a step after)"""
+    on, behind, changes, stepped, pending = False, 0, 0, False, 0
+    for i, op in enumerate(ops):
+        if op[0] == "temporal_response":
+            pending += stepped and op[1] != on
+            on = op[1]
+        if op[0] == "temporal_step":
+            behind += on and ops[i - 1][0] == "subset"
+            changes, pending, stepped = changes + pending, 0, True
+    return behind, changes
+
+
+def test_a_case_number_reproduces_its_chain():
+    with open(GOLDEN) as f:
+        golden = json.load(f)
+    assert set(golden["cases"]) == {str(c) for c in AC.SUITE_CASES}
+    for c, (p, ops) in _suite().items():
+        assert AC.chain(c) == (p, ops)
+        assert hashlib.sha256(repr(ops).encode()).hexdigest() == golden["cases"][str(c)], f"the generator changed case {c}"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join("tests", "adaptive_chains.py"), "7"], cwd=root, capture_output=True, text=True, check=True).stdout
+    p, ops = AC.chain(7)
+    assert out.splitlines() == [f"case 7: {p}"] + [f"{i:3d} {op!r}" for i, op in enumerate(ops)]
+
+
+def test_the_plan_and_the_suite_cover_what_they_promise():
+    assert len(AC.PLAN) >= 12 and {f for *_, f in AC.PLAN} == set(AC.FLAVOURS)
+    for layout in ("small", "large-quad", "large-lin"):
+        assert sum(l == layout for l, *_ in AC.PLAN) >= 3
+    suite = _suite()
+    names, refusals = dict.fromkeys(AC.UNION_VOCABULARY, 0), set()
+    for c, (p, ops) in suite.items():
+        assert (p["layout"], p["max_w"], p["size"], p["flavour"]) == AC.PLAN[c % len(AC.PLAN)]
+        assert len(ops) <= 40 and ops[0] == ("set_world", p["layout"]) and ops[-1] == ("check",), (c, len(ops))
+        assert {op[0] for op in ops} <= set(AC.UNION_VOCABULARY), c
+        checks = [-1] + [i for i, op in enumerate(ops) if op == ("check",)]
+        assert max(np.diff(checks)) <= 8, (c, checks)
+        assert all(op[2] < AC.K_TABLE_FIRST for op in ops if op[0] == "subset"), c
+        edits = 0
+        for op in ops[1:]:                      # a check after every third update
+            edits = 0 if op[0] == "check" else edits + (op[0] == "update")
+            assert edits <= 3, (c, op)
+        for n in {op[0] for op in ops}:
+            names[n] += 1
+        refusals |= {op[1] for op in ops if op[0] in ("refuse", "refused")} | {op[0] for op in ops if op[0] == "refused_materials"}
+    assert all(v >= 3 for v in names.values()), {n: v for n, v in names.items() if v < 3}
+    assert refusals == set(AC.REFUSALS) | set(MC.REFUSALS) | {"refused_materials"}
+    for layout in ("small", "large-quad", "large-lin"):
+        assert sum(p["layout"] == layout for p, _ in suite.values()) >= 3
+    for max_w in (1.0, 0.75, 0.0):
+        assert sum(p["max_w"] == max_w for p, _ in suite.values()) >= 3
+    windows = {c: _response_windows(ops) for c, (_, ops) in suite.items()}
+    assert sum(b > 0 for b, _ in windows.values()) >= 4 and sum(ch > 0 for _, ch in windows.values()) >= 2, windows
+    # the written chains' situations, read from the random chains' ops by the same reader
+    found, kinds_1, kinds_3, denoise_6, long_6 = _situations(suite)
+    assert kinds_1 >= {"jitter", "scatter", "partial", "shrink", "ground"} and kinds_3 == set(XC.MATERIAL_KINDS), (kinds_1, kinds_3)
+    assert denoise_6 == {(m, x) for m in (0, 1, 2) for x in (False, True)}, denoise_6
+    assert {w for _, w in found[5]} == {0.0, 0.75}, found[5]
+    assert all(found.values()) and any("(nine)" not in n for n in found[7]), found
+    assert len(NOT_REACHED) <= 2 and not long_6 and not any("(nine)" in n for n in found[7])       # (the two listed: indeed not there)
+
+
+@pytest.fixture(scope="module")
+def suite_runs(oracle):
+    """every random chain model against model, and on the way every call's status on a model of its own: OK but for the
+    refusals drawn, and those refuse for the reason drawn"""
+    out = {}
+    for c, (p, ops) in _suite().items():
+        m, sh = AC.new_model(oracle, c), AC.Shadow()
+        for op in ops:
+            before = m.temporal_response()
+            for call, args in sh.calls(op):
+                got, _ = MC._call(m, call, args)
+                want = AC.REFUSAL_STATUS[op[1]] if op[0] == "refuse" else MC.OK if op[0] not in ("refused", "refused_materials") else None
+                assert got == want or (want is None and got != MC.OK), (c, op, call, got)
+            if op[0] == "refuse":               # one reason at a time
+                if op[1] in ("adaptive-on-sums", "budget-on-max-rel"):
+                    assert m._oldest() <= op[2] <= m.noise_seq
+                if op[1] == "old-report":
+                    assert 0 < op[2] < m._oldest() and m.tracking
+                if op[1] == "denoise-off":
+                    assert m.tracking and m.acc.diverged and not m.denoise_adaptive_on
+                if op[1] == "counter-65":
+                    assert (m.rng_mode, m.spp) == (1, 65)
+                if op[1] in AC.RESPONSE_REFUSALS:
+                    assert m.temporal_response() == before
+                if op[1] == "present-temporal-dropped":
+                    assert m.temporal_on and m.spheres is not None and not m.stepped
+        seen = []
+
+        def after(i, op, run, seen=seen):
+            if op[0] == "check":
+                seen.append(bool(run.model.acc.diverged))
+        out[c] = (AC.run(c, AC.new_model(oracle, c), AC.new_model(oracle, c), oracle, after=after), seen)
+    return out
+
+
+def test_every_random_chain_is_legal_and_meets_the_conditions(suite_runs):
+    diverged = moved = fractional = h2 = h2_dropped = 0
+    for c, (run, seen) in suite_runs.items():
+        assert len(seen) == sum(op == ("check",) for op in AC.chain(c)[1])
+        diverged += any(seen)
+        moved += sum(a > 0 for a, _ in run.model.response_steps)
+        fractional += sum(b > 0 for _, b in run.model.response_steps)
+        h2 += run.stats.get("h2 checks", 0)
+        h2_dropped += run.stats.get("h2 checks of a dropped history", 0)
+    print(f"cases with a diverged check: {diverged} of {len(suite_runs)}; steps whose clamp moved a pixel: {moved}, that stored a fractional "
+          f"length: {fractional}; checks of H2: {h2}, of a dropped history's: {h2_dropped}")
+    assert 2 * diverged >= len(suite_runs)
+    assert moved >= 8 and fractional >= 4 and h2 >= 8 and h2_dropped >= 2
+
+
+@pytest.mark.parametrize("defect", DEFECTS, ids=lambda c: c.__name__)
+def test_a_random_chain_catches_every_defect(oracle, defect):
+    name = defect.__name__
+    caught = []
+    if defect in RESPONSE_DEFECTS:
+        for c in AC.SUITE_CASES:
+            if any(op[0] == "temporal_response" for op in AC.chain(c)[1]):
+                try:
+                    AC.run(c, AC.new_model(oracle, c, defect), AC.new_model(oracle, c), oracle)
+                except MC.ChainMismatch:
+                    caught.append(c)
+        assert caught and caught == SUITE_CAUGHT_BY[name], (name, caught)
+    else:
+        for c in AC.SUITE_CASES:
+            try:
+                AC.run(c, AC.new_model(oracle, c, defect), AC.new_model(oracle, c), oracle)
+            except MC.ChainMismatch:
+                caught.append(c)
+                break
+        assert caught == [SUITE_FIRST_CATCH[name]], (name, caught)
+
+
+# sha256 over (h0, h1, the temporal image) at every check with a history, per written chain that steps with the response never
+# enabled: recorded from the model as it was before it knew the response (the parent commit's tests/motion_chains.py)
+TEMPORAL_BEFORE_THE_RESPONSE = {
+    "materials": (3, "bdfe641f0b6c920be1547778ff8dbee5ad12bcf563c2af60f54afcc44c6ab995"),
+    "temporal-0": (3, "e131179e52b6a046b4e2cd913cd4c38e765b0eee778f9936e8b88385c373d666"),
+    "temporal-075": (3, "40fa753e8171325dd42722fa21a146d0ebc458ff048d4ed877955e7660195f23"),
+    "large": (3, "ccb2213094abc3a2f1188abcbf22a379ef819957aa33a1f7e1514dbb76ec5c3f"),
+}
+
+
+def test_with_the_response_never_enabled_the_temporal_outputs_are_what_they_were(oracle):
+    for name in AC.NAMES:
+        if any(op[0] == "temporal_response" for op in _ops(name)):
+            continue
+        h, n = hashlib.sha256(), [0]
+
+        def after(i, op, run, h=h, n=n):
+            m = run.model
+            assert m.h2 is None and not m.response_steps and m.temporal_response() == (False, {"fast_history": 4, "clamp_sigma": 2.0, "antilag": 1.0})
+            if op[0] == "check" and m.temporal_on and m.stepped:
+                for a in (m.h0, m.h1, m.read_temporal()):
+                    h.update(a.tobytes())
+                n[0] += 1
+        AC.run(name, AC.new_model(oracle, name), AC.new_model(oracle, name), oracle, after=after)
+        assert (n[0], h.hexdigest()) == TEMPORAL_BEFORE_THE_RESPONSE.get(name, (0, hashlib.sha256().hexdigest())), name

@@ -1,6 +1,6 @@
 """The adaptive chains (tests/adaptive_chains.py) on a real context against the host model: every call returns the model's status;
 every selection, allocation, read and present compares where it stands; and every check finds the model's framebuffer, counters,
-n_t, S, newest report and tile map, guides, denoised image, temporal history and image bit for bit (a report's doubles at
+n_t, S, newest report and tile map, guides, denoised image, temporal history (the response's H2 included) and image bit for bit (a report's doubles at
 state_sequences.REPORT_REL), next to everything motion_chains.Run.check_device holds a context to.  Every render launch of the
 small layout, subset launches included, got the camera table that motion_chains.CameraTables predicts from the calls alone.
 
@@ -27,7 +27,7 @@ def _guarded(f, *a, **kw):
 
 
 def _run_case(oracle, name):
-    p, ops = AC.CHAINS[name]
+    p, ops = AC.params_and_ops(name)            # (a written chain by its name, a random one by its case number)
     stats = {}
     t0 = time.perf_counter()
     with _guarded(MC.new_state, p) as st:
@@ -46,17 +46,32 @@ def test_chain_matches_the_model(oracle, name):
     stats = _run_case(oracle, name)
     ops = AC.CHAINS[name][1]
     assert _count(stats, "checks") == sum(op == ("check",) for op in ops)
-    print(f"adaptive chain {name}: {len(ops)} ops, {_count(stats, 'checks')} checks ({stats['diverged checks']} diverged), "
-          f"{_count(stats, 'regroups')} regroups, {_count(stats, 'auto regroups')} by the policy, {stats['seconds']:.2f} s")
+    print(_statistics("adaptive chain", name, ops, stats))
     if name == "regroups":
         assert _count(stats, "auto regroups") >= 1, "the policy's gate never opened"
 
 
+def _statistics(what, name, ops, stats):
+    return (f"{what} {name}: {len(ops)} ops, {_count(stats, 'checks')} checks ({stats['diverged checks']} diverged, {stats.get('h2 checks', 0)} of H2), "
+            f"{_count(stats, 'regroups')} regroups, {_count(stats, 'auto regroups')} by the policy, {stats['seconds']:.2f} s")
+
+
+@pytest.mark.parametrize("case", AC.SUITE_CASES)
+def test_random_chain_matches_the_model(oracle, case):
+    """a random chain (python tests/adaptive_chains.py CASE prints it): every call returns the model's status, every check finds
+    what the written chains' checks find, the fast history H2 of the temporal response included"""
+    stats = _run_case(oracle, case)
+    p, ops = AC.chain(case)
+    assert _count(stats, "checks") == sum(op == ("check",) for op in ops)
+    print(_statistics(f"random adaptive chain ({p['layout']}, {p['max_w']}, {p['size']}, {p['flavour']})", case, ops, stats))
+
+
 def test_two_chains_side_by_side(oracle):
     """two contexts on one device through two different chains, op by op in turn, each against its own model: forced tables with
-    frames in flight beside a temporal chain on the wider image; reports and budgets beside the large layout"""
-    for one, other in (("tables", "temporal-075"), ("reports", "large")):
-        (pa, ops_a), (pb, ops_b) = AC.CHAINS[one], AC.CHAINS[other]
+    frames in flight beside a temporal chain on the wider image; reports and budgets beside the large layout; a random chain with
+    the response on beside a random chain of a large layout"""
+    for one, other in (("tables", "temporal-075"), ("reports", "large"), (13, 18)):
+        (pa, ops_a), (pb, ops_b) = AC.params_and_ops(one), AC.params_and_ops(other)
         with _guarded(MC.new_state, pa) as a, _guarded(MC.new_state, pb) as b:
             ra = AC.new_run(one, a, AC.new_model(oracle, one), oracle)
             rb = AC.new_run(other, b, AC.new_model(oracle, other), oracle)
@@ -83,9 +98,12 @@ def test_the_comparison_is_live_on_a_real_context(oracle):
     """the other way round from tests/test_adaptive_chains_host.py: with a defective model as the reference the runner must report
     the real context as different, for every defect, in a chain that catches it on the host.  (Nothing here makes the library
     misbehave: the defect is in the Python model.  Only what a model can say is compared.)"""
-    from test_adaptive_chains_host import CAUGHT_BY, DEFECTS
+    from test_adaptive_chains_host import CAUGHT_BY, DEFECTS, RESPONSE_DEFECTS, SUITE_CAUGHT_BY
     for defect in DEFECTS:
-        name = next(n for n in CAUGHT_BY[defect.__name__] if n != "denoise-long")       # (the shortest runs)
-        with _guarded(MC.new_state, AC.CHAINS[name][0]) as st:
+        if defect in RESPONSE_DEFECTS:          # (the response's: the shortest random chain that catches it on the host)
+            name = min(SUITE_CAUGHT_BY[defect.__name__], key=lambda c: (len(AC.chain(c)[1]), c))
+        else:
+            name = next(n for n in CAUGHT_BY[defect.__name__] if n != "denoise-long")       # (the shortest runs)
+        with _guarded(MC.new_state, AC.params_and_ops(name)[0]) as st:
             with pytest.raises(MC.ChainMismatch):
                 _guarded(AC.run, name, st, AC.new_model(oracle, name, defect), oracle, device_checks=False)
