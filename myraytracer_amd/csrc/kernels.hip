@@ -199,6 +199,12 @@ __device__ __forceinline__ uint32_t rank_in(unsigned long long mask) {
 //    coalesced whole-line stores.
 constexpr uint32_t kCtrBlock = MRT_COUNTER_BLOCK;   // counter-RNG mode: samples per separately summed block
 constexpr uint32_t kRingCap = 128;        // < 64 waiting + 64 from a new tile; power of two
+// Wave votes in the small scenes' instantiations (SC = 0, 3): a lane mask that hipcc holds in SGPRs goes through a VGPR and back --
+// v_cndmask 0, 1 and v_cmp_ne, two VALU instructions of a kernel that is bound by them -- when it meets __any(), __ballot(), or a
+// ballot of anything but a comparison that has no other use.  So there a vote is `ballot != 0`, a predicate made of several
+// comparisons is the AND of their ballots, formed on the scalar side, and a lane's own flag is read back off the mask
+// (__builtin_amdgcn_inverse_ballot_w64: no instruction, the mask is the flag).  The large scenes' instantiations (SC = 1, 2)
+// keep the votes they were built with, byte for byte (scripts/isa_diff.py).
 
 // Kernel arguments that are only needed between sweeps (camera, material tables, queue and
 // framebuffer pointers) are re-read from the kernarg segment where they are used: kept in SGPRs
@@ -402,12 +408,15 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
         trips++;
 
         // ------------------------------------------------------------ world_hit, shader.wgsl:314-329
-        const bool trace = live && depth_left != 0u;                        // lanes inside the loop of :339
+        // (small scenes: a lane that is not live holds depth_left == 0 -- it starts so, and the lane that finishes its pixel's last
+        // sample clears it, below -- so the lanes that trace are one comparison, whose ballot is the mask the votes below combine)
+        const bool trace = (SMALL && !DBG) ? depth_left != 0u : live && depth_left != 0u;   // lanes inside the loop of :339
         if (trace) pix_trips++;
-        if (!PILOT) bounces += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(trace));
+        const unsigned long long trace_mask = __builtin_amdgcn_ballot_w64(trace);
+        if (!PILOT) bounces += (uint32_t)__popcll(trace_mask);
         float t_sup = 1.0e4f;                                               // :340
         int32_t best = -1;
-        if (__any(trace)) {
+        if (SMALL ? trace_mask != 0ull : __any(trace) != 0) {
             const float a = dot3(d, d);                                     // sphere_hit :277 (same for every sphere)
             // Camera-ray cluster masks (cam_mask.hip): a camera ray -- the only kind whose geometry is known before the frame --
             // can only touch the clusters set in its texel's entry, so the entry is ANDed onto the sweep's candidate words.
@@ -457,8 +466,20 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 ds = v3(dd.x * unit, dd.y * unit, dd.z * unit);
             }
             const float o_rel2 = MFMA ? dot3(o_rel, o_rel) : 0.0f;
-            const bool weird = !(a > 0.99999f && a < 1.00001f) || (MFMA && !(o_rel2 <= P.mfma_scale[3]));
-            const bool usable = trace && !weird;
+            // (small scenes: each comparison goes straight into a ballot, the ballots are ANDed on the scalar side and the lanes'
+            // `weird` and `usable` are read back off the masks, so neither a vote nor a count takes a mask through a VGPR)
+            bool weird, usable;
+            unsigned long long usable_mask = 0ull;
+            if constexpr (SMALL) {
+                const unsigned long long admitted = __builtin_amdgcn_ballot_w64(a > 0.99999f) & __builtin_amdgcn_ballot_w64(a < 1.00001f) &
+                                                    (MFMA ? __builtin_amdgcn_ballot_w64(o_rel2 <= P.mfma_scale[3]) : ~0ull);
+                usable_mask = trace_mask & admitted;
+                weird = !__builtin_amdgcn_inverse_ballot_w64(admitted);
+                usable = __builtin_amdgcn_inverse_ballot_w64(usable_mask);
+            } else {
+                weird = !(a > 0.99999f && a < 1.00001f) || (MFMA && !(o_rel2 <= P.mfma_scale[3]));
+                usable = trace && !weird;
+            }
             // The few spheres far larger than the rest (a ground sphere) are outside the hierarchy: every ray does
             // sphere_hit on them itself, record in SGPRs (sphere_root_key).
             // Their closest root is what the lane's hit slot starts from: a ground sphere is a candidate for most rays,
@@ -476,7 +497,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     key0 = key < key0 ? key : key0;
                     if (DBG && hq) atomicOr(P.dbg_cand + (size_t)texel * P.dbg_words + (sidx >> 5), 1u << (sidx & 31u));
                 }
-                if (!PILOT) mtests += (unsigned long long)n_direct * (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(usable));
+                if (!SMALL) usable_mask = __builtin_amdgcn_ballot_w64(usable);
+                if (!PILOT) mtests += (unsigned long long)n_direct * (uint32_t)__popcll(usable_mask);
             }
             // every lane leaves its ray where whoever picks up one of its work items finds it
             rays[2u * lane + 0u] = make_float4(o.x, o.y, o.z, d.x);
@@ -501,16 +523,37 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 const uint32_t blk_end = (blk + kBlockChunks * kChunk < n_padded) ? blk + kBlockChunks * kChunk : n_padded;
                 uint32_t nz = 0;                                        // bit w: records 32 w .. 32 w + 31 of this block hold a candidate
                 uint32_t rem = 0;                                       // this lane's candidate clusters in the block
+                // Small scenes read nz only as "the top-most non-zero word" (round 0), so their sweep keeps that word's number,
+                // `top`, instead of the bit set: a comparison and a select per tile in place of comparison, select and shift-or,
+                // and no count of leading zeros afterwards.  (Always a word of this block: 0 for a lane without a candidate.)
+                uint32_t top = 0;
                 if (MFMA) {
                     // 32 records per tile = one mask word per lane and ray
                     uint32_t w = 0;
+                    if constexpr (SMALL) {
+                        // (the tile's A operand by a buffer load: the descriptor and the tile's byte offset are scalars and the
+                        // lane's offset is one VGPR computed once, where the per-lane pointer took a 64-bit VALU add per tile;
+                        // the descriptor's size bounds the read to the records the scene has)
+                        const __amdgpu_buffer_rsrc_t top_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                            const_cast<void*>(static_cast<const void*>(P.top_mfma)), 0, (int)(n_padded * 32u), 0x00020000);
+                        uint32_t tile_bytes = blk * 32u;            // 32 records = 64 lanes x 16 bytes
+                        for (uint32_t i = blk; i < blk_end; i += 2u * kChunk, w++, tile_bytes += 1024u) {
+                            const uint32_t allow = cam_allow(w);
+                            uint32_t m = mfma_sweep_tile<true>(__builtin_amdgcn_raw_buffer_load_b128(top_rsrc, lane * 16u, (int)tile_bytes, 0), mr);
+                            if constexpr (CAM) m &= allow;
+                            masks[w * 64u] = m;
+                            top = m != 0u ? w : top;
+                            rem += (uint32_t)__builtin_popcount(m);
+                        }
+                    } else {
                     for (uint32_t i = blk; i < blk_end; i += 2u * kChunk, w++) {
                         const uint32_t allow = cam_allow(w);
-                        uint32_t m = mfma_sweep_tile(reinterpret_cast<const u32x4*>(P.top_mfma)[(size_t)(i / 32u) * 64u + lane], mr);
+                        uint32_t m = mfma_sweep_tile<false>(reinterpret_cast<const u32x4*>(P.top_mfma)[(size_t)(i / 32u) * 64u + lane], mr);
                         if constexpr (CAM) m &= allow;
                         masks[w * 64u] = m;
                         nz |= (m < 1u ? m : 1u) << w;
                         rem += (uint32_t)__builtin_popcount(m);
+                    }
                     }
                 } else {
                 // the 64 record SGPRs are live only during the block's sweep, not during its walk
@@ -531,7 +574,8 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         uint32_t m = ~bits;
                         if constexpr (CAM) m &= allow;
                         masks[(c >> 1) * 64u] = m;
-                        nz |= (m < 1u ? m : 1u) << (c >> 1);
+                        if constexpr (SMALL) top = m != 0u ? (c >> 1) : top;
+                        else nz |= (m < 1u ? m : 1u) << (c >> 1);
                         rem += (uint32_t)__builtin_popcount(m);
                     }
                 }
@@ -601,9 +645,10 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 // <= 0 and fail t >= 0.001 (:291) -- can never be the hit and is dropped here.  Both conditions from sign
                 // bits, in one three-input bit operation and one comparison: the discriminant of a finite ray against finite
                 // geometry is never NaN, and never -0 (b*b - a*c cancels to +0), so "not < 0" is "sign bit clear".
-                // `on`: the lanes whose item this is; returns the number of items pushed.
+                // `on`: the lanes whose item this is; small scenes: `on_ballot` is their ballot, which the caller has on the scalar
+                // side already (a ballot of `on` here takes the mask through a VGPR and back); returns the number of items pushed.
                 auto members_round = [&](const SphereRec* const ch, const V3 ro, const V3 rd, const float ra, const bool on,
-                                         const uint32_t e0, entry_t* const dst) -> uint32_t {
+                                         const unsigned long long on_ballot, const uint32_t e0, entry_t* const dst) -> uint32_t {
                     const SphereRec sr[4] = {ch[0], ch[1], ch[2], ch[3]};
                     bool h[4];
                     unsigned long long hm[4];
@@ -614,7 +659,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         h[q] = (int32_t)((__float_as_uint(bq) | __float_as_uint(cq)) & ~__float_as_uint(disc)) < 0;
                         hm[q] = __builtin_amdgcn_ballot_w64(h[q]);
                     }
-                    const unsigned long long on_mask = __builtin_amdgcn_ballot_w64(on);
+                    const unsigned long long on_mask = SMALL ? on_ballot : __builtin_amdgcn_ballot_w64(on);
                     const unsigned long long m0 = hm[0] & on_mask, m1 = hm[1] & on_mask, m2 = hm[2] & on_mask, m3 = hm[3] & on_mask;
                     // About one member in twenty passes (C3: 43 of 868 per world_hit), so a lane hardly ever holds two: when none
                     // does -- decided on the scalar side -- ONE ranked push serves the round instead of four.
@@ -649,18 +694,18 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                     const uint32_t* const masks0 = masks - lane;                    // the block's word w of lane l at masks0[w * 64 + l]
                     const uint32_t words = (blk_end - blk) / (2u * kChunk);         // 1 .. 8
                     // Round 0, in the lane: every owner tests its own item 0 -- the lowest set bit of the top-most non-zero word of
-                    // its block, the word read back from its own masks -- with its ray in registers: no table, no running maximum, no
-                    // rank, no ray fetch.  A bounce ray carries 1.84 candidates: at C3 round 0 takes about 45 of a wave's 108 items and
+                    // its block (`top`, from the sweep), the word read back from its own masks -- with its ray in registers: no table, no
+                    // running maximum, no rank, no ray fetch.  A bounce ray carries 1.84 candidates: at C3 round 0 takes about 45 of a wave's 108 items and
                     // leaves the cooperative rounds below, which level out the rest, 1.20 derivations per iteration instead of 2.14
-                    // (profiles/walk_first_item_c3_phase_profile.txt).  (A lane without an item reads word 0 and tests the block's
-                    // first record: `on` keeps it from pushing.)
+                    // (profiles/walk_first_item_c3_phase_profile.txt).  (A lane without an item reads whichever word of the block `top`
+                    // names and tests that word's first record: `on` keeps it from pushing.)
                     const bool own = rem != 0u;
                     const unsigned long long own_mask = __builtin_amdgcn_ballot_w64(own);
                     if (own_mask != 0ull) {
-                        const uint32_t w0 = own ? 31u - (uint32_t)__builtin_clz(nz) : 0u;
+                        const uint32_t w0 = top;          // (a lane without an item: some word of the block, see above)
                         const uint32_t m0 = masks[w0 * 64u];
                         const uint32_t node = blk + w0 * (2u * kChunk) + (own ? 31u - (uint32_t)__builtin_ctz(m0) : 0u);
-                        qn0 += members_round(nodes + 4u * node, o, d, a, own, (lane << kIdBits) | (4u * node), q0 + qn0);
+                        qn0 += members_round(nodes + 4u * node, o, d, a, own, own_mask, (lane << kIdBits) | (4u * node), q0 + qn0);
                         if (!PILOT) mtests += kClusterK * (uint32_t)__popcll(own_mask);
 #ifdef MRT_STAMPS
                         rounds_a_++; items_a_ += (uint32_t)__popcll(own_mask);
@@ -715,6 +760,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                             // (`act` keeps them from pushing), so every lane's reads are some real item's.
                             const uint32_t take = total_rem - g0 < 64u ? total_rem - g0 : 64u;
                             const bool act = lane < take;
+                            const unsigned long long act_mask = take < 64u ? (1ull << take) - 1ull : ~0ull;     // ballot(act), from the scalar side
                             uint32_t e = starts[g0 - base + lane];
                             e = wave_incl_max(e < carry ? carry : e);
                             carry = (uint32_t)__builtin_amdgcn_readlane((int)e, 63);
@@ -736,7 +782,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                             MRT_WALK_STAMP(6);
                             // (Round 1 rotated the four reads by node/4 to spread one read's 64 lanes over all LDS banks; the 8
                             // VALU of address arithmetic per round cost more than the bank conflicts they avoided: round 2.)
-                            qn0 += members_round(nodes + 4u * node, ro, rd, dot3(rd, rd), act, (owner << kIdBits) | (4u * node), q0 + qn0);
+                            qn0 += members_round(nodes + 4u * node, ro, rd, dot3(rd, rd), act, act_mask, (owner << kIdBits) | (4u * node), q0 + qn0);
                             if (!PILOT) mtests += kClusterK * take;
 #ifdef MRT_STAMPS
                             rounds_a_++; items_a_ += take;
@@ -861,7 +907,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         fetch_ray(owner, ro, rd);
                         if (k == 1) {
                             const uint32_t m4 = act ? 4u * (g - P.box_cluster_first) : 0u;
-                            rn += members_round(nodes + m4, ro, rd, dot3(rd, rd), act, (owner << 26) | m4, rootq + rn);
+                            rn += members_round(nodes + m4, ro, rd, dot3(rd, rd), act, 0ull, (owner << 26) | m4, rootq + rn);
                             cn = start;
                             if (!PILOT) mtests += kClusterK * take;
                         } else {
@@ -937,6 +983,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
         // They are known before any shading, so these lanes release / start their next sample in this very iteration and
         // their camera-ray draws share the rejection loop below with the hit lanes' unit-ball draws.
         bool start_sample = false;
+        unsigned long long start_mask = 0ull;   // (camera-ray lists) the ballot of start_sample, taken once in the tail
         V3 ndir = d;
         bool hit = !DBG && live && depth_left != 0u && best >= 0;      // (+ below: a camera ray's hit resolved in the lane)
         if (!DBG && live && !hit) {
@@ -966,7 +1013,10 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 s_done = 0;
                 pix_trips = 0;
                 start_sample = true;
-            } else task_done = true;
+            } else {
+                task_done = true;
+                if (SMALL) depth_left = 0u;     // (`trace`, above: a lane that is not live has nothing left to trace)
+            }
         }
         MRT_STAMP(4);
 
@@ -997,8 +1047,11 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 const uint32_t tile = lay * C->n_tiles + (C->tile_order ? C->tile_order[ti] : ti);
                 uint32_t fx, fy, ft, fl;
                 const uint32_t fq = (tile << 6) | lane;
-                const bool ok = locate(C, fq, fx, fy, ft, fl);
-                const unsigned long long m = __ballot(ok);
+                bool ok = locate(C, fq, fx, fy, ft, fl);
+                // (small scenes: the ballots of locate()'s two comparisons, ANDed on the scalar side, and `ok` read back off the mask)
+                const unsigned long long m = SMALL ? __builtin_amdgcn_ballot_w64(fx < C->locals.shape[0]) & __builtin_amdgcn_ballot_w64(fy < C->locals.shape[1])
+                                                   : __ballot(ok);
+                if constexpr (SMALL) ok = __builtin_amdgcn_inverse_ballot_w64(m);
                 if (ok) ring[(tail + rank_in(m)) & (kRingCap - 1u)] = fq;
                 const uint32_t nf = (uint32_t)__popcll(m);
                 tail += nf;
@@ -1006,6 +1059,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             }
         }
         // ---- acquire: idle lanes take the pixels at the front of the FIFO
+        uint32_t took = 0u;                     // wave-uniform: lanes that take a pixel in this iteration
         if (need != 0ull && avail != 0u) {
             const uint32_t rk = rank_in(need);
             const bool take = !has_task && rk < avail;
@@ -1046,11 +1100,13 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                 }
             }
             const uint32_t np = (uint32_t)__popcll(need);
-            const uint32_t took = np < avail ? np : avail;
+            took = np < avail ? np : avail;
             head += took;
             avail -= took;
         }
-        if (!__any(has_task)) {
+        // (small scenes: "some lane has a task" from what the scalar side knows -- a lane kept its task through the release, or a lane
+        // took one: all 64 lanes of a wave are active here)
+        if (SMALL ? (need == ~0ull && took == 0u) : !__any(has_task)) {
             if (queue_empty) break;
             continue;                       // nothing acquired (an all-invalid edge tile): pull the next one
         }
@@ -1073,7 +1129,10 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             // iteration's world_hit as before.  Compiled into the SC = 3 instantiations alone.
             bool own_ray = false;                   // this lane's camera ray was normalized here (not below)
             if constexpr (LISTS) {
-                if (__any(start_sample)) {
+                // (one ballot of start_sample serves the vote, `prim` and the count of started samples at the loop's end; `prim` and
+                // the list loop's `on` are ballots of their comparisons ANDed on the scalar side and read back off the mask)
+                start_mask = __builtin_amdgcn_ballot_w64(start_sample);
+                if (start_mask != 0ull) {
                     uint4 ent = make_uint4(kCamListOverflow, 0u, 0u, 0u);
                     if (start_sample) {
                         ent = reinterpret_cast<const uint4*>(cold_args()->cam_lists)[texel >> 3];
@@ -1087,8 +1146,10 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         own_ray = true;
                     }
                     const float a = dot3(d, d);
-                    const bool prim = start_sample && depth_left != 0u && ent.x != kCamListOverflow && a > 0.99999f && a < 1.00001f;
-                    const unsigned long long prim_mask = __builtin_amdgcn_ballot_w64(prim);
+                    const unsigned long long prim_mask = start_mask & __builtin_amdgcn_ballot_w64(depth_left != 0u) &
+                                                         __builtin_amdgcn_ballot_w64(ent.x != kCamListOverflow) &
+                                                         __builtin_amdgcn_ballot_w64(a > 0.99999f) & __builtin_amdgcn_ballot_w64(a < 1.00001f);
+                    const bool prim = __builtin_amdgcn_inverse_ballot_w64(prim_mask);
                     const KArgPtr C = cold_args();
                     const uint32_t n_direct = C->n_direct;
                     const Divisor by_a = divisor_of(a);
@@ -1100,12 +1161,11 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
                         key = kk < key ? kk : key;
                     }
                     if (!PILOT) mtests += (unsigned long long)n_direct * (uint32_t)__popcll(prim_mask);
-                    const uint32_t cnt = prim ? ent.x : 0u;
                     uint32_t w0 = ent.y, w1 = ent.z, w2 = ent.w;            // the ids left, the next one lowest
                     for (uint32_t k = 0;; k++) {
-                        const bool on = k < cnt;
-                        const unsigned long long on_mask = __builtin_amdgcn_ballot_w64(on);
+                        const unsigned long long on_mask = prim_mask & __builtin_amdgcn_ballot_w64(k < ent.x);
                         if (on_mask == 0ull) break;
+                        const bool on = __builtin_amdgcn_inverse_ballot_w64(on_mask);
                         const uint32_t slot = on ? w0 & 1023u : 0u;
                         w0 = __builtin_amdgcn_alignbit(w1, w0, 10u); w1 = __builtin_amdgcn_alignbit(w2, w1, 10u); w2 >>= 10u;
                         const SphereRec sm = nodes[slot];
@@ -1250,7 +1310,7 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) __attribute__((amdgpu_wav
             }
         }
         MRT_STAMP(0);
-        if (!PILOT) started += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(start_sample));
+        if (!PILOT) started += (uint32_t)__popcll(LISTS ? start_mask : __builtin_amdgcn_ballot_w64(start_sample));
     }
 
     // samples, world_hit calls, lane slots and member tests are wave totals kept on the scalar side (a ballot and a count per

@@ -163,7 +163,9 @@ __device__ __forceinline__ MfmaRay mfma_ray_operands(V3 o, V3 dsk, float o2, flo
 }
 // one tile of 32 records against the wave's 64 rays; `a` = this lane's 8 bf16 of the tile's A operand
 // (bounds.h, mfma_row).  Returns the candidate mask of the tile's 32 records (record i at bit 31 - i) for this
-// lane's own ray.
+// lane's own ray.  TIGHT (the small scenes' instantiations): each half's 16 signs are shifted into a word that starts at 0, so the
+// halves are below 2^16 and join in one shift-or without the mask; the other instantiations keep the form they were built with.
+template <bool TIGHT>
 __device__ __forceinline__ uint32_t mfma_sweep_tile(const u32x4 a, const MfmaRay& m) {
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const bf16x8 av = __builtin_bit_cast(bf16x8, a);
@@ -189,7 +191,15 @@ __device__ __forceinline__ uint32_t mfma_sweep_tile(const u32x4 a, const MfmaRay
         hb[h] = bb;
     }
     const auto r = __builtin_amdgcn_permlane32_swap(hb[0], hb[1], false, false);
-    return ~((r[0] << 16) | (r[1] & 0xFFFFu));         // record i of the tile at bit 31 - i
+    if constexpr (TIGHT) {
+        // (the joined word made opaque before and after the complement: hipcc otherwise forms the complement and the word it
+        // compares with all ones separately, a shift and two three-operand instructions where a shift-or and a v_not do)
+        uint32_t x = (r[0] << 16) | r[1];
+        asm("" : "+v"(x));
+        x = ~x;
+        asm("" : "+v"(x));
+        return x;
+    } else return ~((r[0] << 16) | (r[1] & 0xFFFFu));         // record i of the tile at bit 31 - i
 }
 
 }  // namespace mrt
