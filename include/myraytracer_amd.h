@@ -50,7 +50,8 @@ extern "C" {
  * denoiser's blend with the accumulation (mrt_denoise_mix, mrt_denoise_mix_default, mrt_set_denoise_mix, mrt_get_denoise_mix);
  * material edits without a rebuild (mrt_material, mrt_update_materials, MRT_MATERIALS_RESTART_HISTORY); adaptive sampling by
  * budget (MRT_TILE_MAP_MAX_REL, MRT_TILE_MAP_SUM_S, mrt_noise_query_map, mrt_budget_result, mrt_budget_allocate,
- * mrt_render_budget; mrt_noise_report::reserved carries the report's map kind). */
+ * mrt_render_budget; mrt_noise_report::reserved carries the report's map kind); budget allocation on the device
+ * (mrt_noise_query_budget, mrt_read_budget_plan, mrt_render_planned). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -638,6 +639,42 @@ int mrt_budget_allocate(const float* s, const uint32_t* n, size_t tiles, float m
                         uint32_t max_frames, uint32_t* k_out, mrt_budget_result* res);
 int mrt_render_budget(mrt_ctx* ctx, uint64_t budget, uint32_t max_frames, uint64_t report_seq, mrt_budget_result* res,
                       uint32_t* k_out, size_t cap);
+
+/* ---- budget allocation on the device: plan with the query, render the plan ----
+ * mrt_noise_query_budget is mrt_noise_query_map(ctx, rel_threshold, rel_floor, MRT_TILE_MAP_SUM_S) exactly -- the same launches,
+ * the same report bits, `reserved` = 1; mrt_render_budget and mrt_read_noise_tiles use the report as before -- and queues, on the
+ * ctx's stream behind the reduction and ahead of the report's copy, the allocation of `budget` tile-frames from the map the query
+ * has just written: the report carries a plan, finished when the report is.  Nothing waits on the host.
+ *   The plan: k_t = mrt_budget_allocate(s = the report's map, n, the ctx's max_framebuffer_weight, budget, max_frames)'s, bit for
+ *     bit, with n = n_q: the n_t of every frame queued before the call and of none after (mrt_frames_done everywhere while the
+ *     accumulation is uniform).  The device selects it as one total order: candidate (t, j) has the key (class, G, j, t), class 0
+ *     a mandatory frame (n_t + j < 2 and j < min(2, max_frames); G = 0), class 1 a gain with G = the bits of g'(t, j) as an
+ *     unsigned 64-bit integer, complemented; ascending keys are mrt_budget_allocate's order, the keys are unique, and the plan is
+ *     the `budget` smallest (all if there are fewer).  It does not depend on launch shape, dispatch order or timing.
+ *   The result: tile_frames, tiles and frames are mrt_budget_allocate's.  var_before and var_after are its sums in a blocked
+ *     order: per tile a_t = s'_t * K(n_t) (var_before) or s'_t * K(n_t + k_t) (var_after), +0.0 for a tile with n_t < 2; P_b = the
+ *     sequential sum from 0.0 of a_t over t = 64 b .. 64 b + 63, ascending; the field = the sequential sum from 0.0 of P_b over
+ *     ascending b.  (mrt_budget_allocate adds all tiles in one chain; the two agree to rounding.)
+ *   Refusals, each before anything is queued: mrt_noise_query_map's; max_frames outside 1 .. 32: MRT_ERR_INVALID_ARG; a shard:
+ *     MRT_ERR_STATE; an n_t above 2^24: MRT_ERR_INVALID_ARG.  budget == 0 is legal: a plan of zeros.  Must not be called while
+ *     the ctx's stream is being captured.  The call may grow the device's table of K(n) first, which waits (bounded) for the
+ *     ctx's stream: a handful of times per accumulation, as for a noise query of a diverged accumulation.
+ * mrt_read_budget_plan returns the plan of report `report_seq` as allocated: k_out (may be NULL; cap >= the tile count, else
+ *   MRT_ERR_TOO_SMALL) and *res (may be NULL) with used_seq = the report.  report_seq == 0: the newest finished report that
+ *   carries a plan, without waiting; none: MRT_OK, res->used_seq 0, k_out zeroed.  report_seq == k: report k, waiting (bounded)
+ *   for that query only; a report that is not held (not queued, older than the ring of 8, discarded by mrt_reset) or that
+ *   carries no plan: MRT_ERR_STATE.  Tracking off: MRT_ERR_STATE.  It reads back k_t and the 64-byte result, nothing else.
+ * mrt_render_planned reads the plan as mrt_read_budget_plan does and renders it as mrt_render_budget renders its allocation.
+ *   A plan is a target: tile t should reach n_q[t] + k_t frames, and frames queued since the query count towards it:
+ *     k'_t = max(0, n_q[t] + k_t - n_now[t]), n_now the host's n_t at this call; with nothing queued in between k' = k.
+ *   The frames: L_j = {t : k'_t >= j} in ascending tile id; consecutive equal lists are one mrt_render_tiles call; a list of
+ *     every tile renders whole frames.
+ *   k_out and *res report k' and its tile_frames, tiles and frames; var_before and var_after stay the plan's.
+ *   Every refusal of mrt_render_tiles applies before anything is queued (mrt_render_budget's list).  Nothing to render -- no
+ *     plan finished, or a plan already met --: MRT_OK. */
+int mrt_noise_query_budget(mrt_ctx* ctx, float rel_threshold, float rel_floor, uint64_t budget, uint32_t max_frames);
+int mrt_read_budget_plan(mrt_ctx* ctx, uint64_t report_seq, uint32_t* k_out, size_t cap, mrt_budget_result* res);
+int mrt_render_planned(mrt_ctx* ctx, uint64_t report_seq, mrt_budget_result* res, uint32_t* k_out, size_t cap);
 
 /* ------------------------------------------------------------------ denoiser (no reference counterpart)
  *

@@ -59,6 +59,7 @@ EXPORTS = [
     "mrt_update_materials", "mrt_debug_material_shade",
     "mrt_debug_hold", "mrt_debug_hold_stamps",
     "mrt_noise_query_map", "mrt_budget_allocate", "mrt_render_budget",
+    "mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -390,6 +391,9 @@ def load():
         "mrt_noise_query_map": (i32, [vp, f32, f32, u32]),
         "mrt_budget_allocate": (i32, [vp, vp, sz, f32, C.c_uint64, u32, vp, P(MrtBudgetResult)]),
         "mrt_render_budget": (i32, [vp, C.c_uint64, u32, C.c_uint64, P(MrtBudgetResult), vp, sz]),
+        "mrt_noise_query_budget": (i32, [vp, f32, f32, C.c_uint64, u32]),
+        "mrt_read_budget_plan": (i32, [vp, C.c_uint64, vp, sz, P(MrtBudgetResult)]),
+        "mrt_render_planned": (i32, [vp, C.c_uint64, P(MrtBudgetResult), vp, sz]),
         "mrt_noise_result": (i32, [vp, i32, P(MrtNoiseReport)]),
         "mrt_read_noise": (i32, [vp, vp, sz]),
         "mrt_read_noise_tiles": (i32, [vp, vp, sz, P(u32), P(u32)]),

@@ -803,11 +803,17 @@ class State:
         """Turn noise tracking on / off; only while frames_done == 0 (after creation or reset()).  Survives reset()."""
         self._check(self._L.mrt_set_noise_tracking(self._ctx, int(enabled)), "mrt_set_noise_tracking")
 
-    def noise_query(self, threshold: float = 0.02, floor: float = 0.01, tile_map: str = "max_rel"):
+    def noise_query(self, threshold: float = 0.02, floor: float = 0.01, tile_map: str = "max_rel", budget: Optional[int] = None,
+                    max_frames: int = 8):
         """Queue the noise report of the most recent frame (asynchronous).  threshold: the relative standard error above which a
         pixel counts as noisy; floor: the luminance below which the relative error is taken against the floor instead.
         tile_map: what the report's tile map holds -- "max_rel", the tile's largest relative error (render_adaptive selects from
-        it), or "sum_s", the tile's summed S (render_budget allocates from it); the report's scalar fields are the same."""
+        it), or "sum_s", the tile's summed S (render_budget allocates from it); the report's scalar fields are the same.
+        budget=N: a "sum_s" query that also allocates N tile-frames, at most max_frames a tile, on the device right behind the
+        reduction (mrt_noise_query_budget): budget_plan() reads the plan, render_planned() renders it."""
+        if budget is not None:                             # (always a "sum_s" query, whatever tile_map says)
+            self._check(self._L.mrt_noise_query_budget(self._ctx, threshold, floor, budget, max_frames), "mrt_noise_query_budget")
+            return
         if tile_map not in _lib.TILE_MAP_KINDS:
             raise ValueError(f"noise_query: unknown tile_map {tile_map!r} ({', '.join(_lib.TILE_MAP_KINDS)})")
         if tile_map == "max_rel":
@@ -842,7 +848,8 @@ class State:
         return out
 
     def render_until(self, target_rel_rmse: float, max_frames: int, check_every: int = 16, threshold: float = 0.02,
-                     floor: float = 0.01, adaptive: bool = False, budget: Optional[int] = None) -> Tuple[int, dict]:
+                     floor: float = 0.01, adaptive: bool = False, budget: Optional[int] = None,
+                     plan: str = "host") -> Tuple[int, dict]:
         """Render chunks of check_every frames until a noise report's rel_rmse <= target_rel_rmse or frames_done reaches
         max_frames; returns (frames_done, report).  Keeps the pipeline full by lagging one check: chunk k + 1 is queued before
         report k is waited for, so the stop overshoots the first report that meets the target by at most check_every frames
@@ -856,14 +863,23 @@ class State:
 
         budget=N (not with adaptive=True): every chunk after the first is render_budget(N, min(check_every, 32), report): N
         tile-frames allocated from the summed-S map of the report queued one chunk earlier -- the same lag -- so the queries
-        are noise_query(tile_map="sum_s").  The loop also stops when a chunk finds nothing worth a frame."""
+        are noise_query(tile_map="sum_s").  The loop also stops when a chunk finds nothing worth a frame.
+
+        plan="device" (with budget=N): the queries are noise_query(budget=N, max_frames=min(check_every, 32)), which allocate on
+        the device behind the reduction, and every chunk after the first is render_planned(report) -- the same one-check lag.
+        A plan is a target (n at its query + k), so the frames of the chunk queued between a plan's query and its rendering
+        count towards it; a chunk that finds its plan met already queues nothing and the loop goes on, and it stops when a plan
+        as allocated is empty.  A last chunk with fewer frames left than the plans' max_frames is render_budget's."""
         if check_every < 1 or max_frames < 0:
             raise ValueError("render_until: check_every >= 1, max_frames >= 0")
         if budget is not None and (adaptive or budget < 1):
             raise ValueError("render_until: budget >= 1, and not together with adaptive=True")
+        if plan not in ("host", "device") or (plan == "device" and budget is None):
+            raise ValueError('render_until: plan is "host" or "device", and "device" needs a budget')
         if self.frames_done == 0:
             self.set_noise_tracking(True)
         tile_map = "max_rel" if budget is None else "sum_s"
+        plan_frames = min(check_every, 32)
 
         def chunk(select_from=None):
             """whether the chunk had anything to queue"""
@@ -871,14 +887,22 @@ class State:
             if n > 0:
                 if select_from is None:
                     self.render(n)
+                elif budget is not None and plan == "device" and n >= plan_frames:
+                    return self.render_planned(select_from)["planned_tile_frames"] != 0
                 elif budget is not None:
                     return self.render_budget(budget, min(n, 32), select_from)["tile_frames"] != 0
                 else:
                     self.render_adaptive(n, select_from)
             return True
 
+        def query():
+            if plan == "device":
+                self.noise_query(threshold, floor, budget=budget, max_frames=plan_frames)
+            else:
+                self.noise_query(threshold, floor, tile_map)
+
         chunk()
-        self.noise_query(threshold, floor, tile_map)
+        query()
         earlier = None                                     # adaptive, budget: the report one chunk before the newest
         while True:
             lagged = adaptive or budget is not None
@@ -893,7 +917,7 @@ class State:
             if not spent:
                 return self.frames_done, rep
             earlier = rep
-            self.noise_query(threshold, floor, tile_map)
+            query()
 
     # -- adaptive sampling (include/myraytracer_amd.h, "adaptive sampling"): frames over a list of 8x8 tiles, each tile blended
     #    at its own frame count
@@ -923,6 +947,32 @@ class State:
         self._check(self._L.mrt_render_budget(self._ctx, budget, max_frames, report_seq, C.byref(r), k.ctypes.data, k.size),
                     "mrt_render_budget")
         return dict(budget_result_dict(r), k=k)
+
+    def _tile_shape(self):
+        tx, tr = C.c_uint32(), C.c_uint32()
+        self._L.mrt_read_tile_frames(self._ctx, None, 0, C.byref(tx), C.byref(tr))     # (the shape)
+        return tr.value, tx.value
+
+    def budget_plan(self, report_seq: int = 0) -> dict:
+        """The plan that noise_query(budget=N) allocated on the device with report `report_seq` (0: the newest finished report
+        that carries one, without waiting; none: used_seq is 0), as allocated: render_budget's dict, k the frames planned for
+        every tile.  Reads back k and the 64-byte result once that query has finished; waits for that query only."""
+        r = _lib.MrtBudgetResult()
+        k = np.zeros(self._tile_shape(), np.uint32)
+        self._check(self._L.mrt_read_budget_plan(self._ctx, report_seq, k.ctypes.data, k.size, C.byref(r)), "mrt_read_budget_plan")
+        return dict(budget_result_dict(r), k=k)
+
+    def render_planned(self, report_seq: int = 0) -> dict:
+        """Render the plan of report `report_seq` (budget_plan's rule) level by level through render_tiles.  The plan is a target:
+        tile t should reach its frame count at the query + k_t, so frames queued since the query count towards it and k, with
+        tile_frames, tiles and frames, is what this call queued (the plan's own k while nothing was queued in between);
+        var_before and var_after stay the plan's.  planned_tile_frames: the plan's tile_frames as allocated."""
+        r, p = _lib.MrtBudgetResult(), _lib.MrtBudgetResult()
+        k = np.zeros(self._tile_shape(), np.uint32)
+        self._check(self._L.mrt_render_planned(self._ctx, report_seq, C.byref(r), k.ctypes.data, k.size), "mrt_render_planned")
+        if r.used_seq:
+            self._check(self._L.mrt_read_budget_plan(self._ctx, r.used_seq, None, 0, C.byref(p)), "mrt_read_budget_plan")
+        return dict(budget_result_dict(r), k=k, planned_tile_frames=int(p.tile_frames))
 
     @staticmethod
     def budget_allocate(s, n, max_framebuffer_weight: float, budget: int, max_frames: int = 8) -> Tuple[np.ndarray, dict]:

@@ -236,12 +236,20 @@ struct mrt_ctx {
         hipEvent_t copied = nullptr;
         mrt_noise_report report{};                  // what the host knows at query time (seq, frames_done, K, threshold, floor)
         bool per_tile = false;                      // reduced with K per tile (adaptive sampling): the sums' sum_s is sum_var
+        // mrt_noise_query_budget: the entry carries a plan (budget.hip; k_t and the result beside the entry's map, finished when
+        // `copied` fires), and n_q, the frame counts the plan was allocated for: every tile's nq_uniform while the accumulation
+        // was uniform at the query (nq empty), else nq per tile
+        bool has_plan = false;
+        uint32_t nq_uniform = 0;
+        std::vector<uint32_t> nq;
     };
     bool noise_on = false;                          // mrt_set_noise_tracking
     float* d_noise_s = nullptr;                     // local texels (allocated with the framebuffers while noise_on)
     double noise_c2 = 1.0;                          // sum of the squared normalised weights of the frames blended so far
     void* d_noise_partials = nullptr;
-    float* d_noise_tiles = nullptr;                 // kNoiseRing x n_tiles: query seq's map at entry seq % kNoiseRing
+    // kNoiseRing x n_tiles: query seq's map at entry seq % kNoiseRing; behind the maps the entries' budget plans and the
+    // selection's scratch (mrt::budget_layout, mrt_internal.h)
+    float* d_noise_tiles = nullptr;
     mrt::NoiseSums* d_noise_sums = nullptr;         // kNoiseRing entries
     mrt::NoiseSums* h_noise_sums = nullptr;         // pinned, kNoiseRing entries
     NoiseEntry noise_ring[kNoiseRing];
@@ -299,6 +307,7 @@ struct mrt_ctx {
     uint32_t k_len = 0;
     std::vector<float> h_select_map;                // mrt_render_adaptive: the report's tile map
     std::vector<uint32_t> selection;                // ... and the tiles it selects
+    std::vector<uint32_t> h_plan;                   // mrt_read_budget_plan / mrt_render_planned: a report's result and k_t
 
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;

@@ -232,6 +232,47 @@ int launch_noise_reduce_sum(const float* S, const float* rgba, uint32_t width, u
                             uint32_t rank, uint32_t world, float K, const uint32_t* tile_frames, const float* Kf, const double* Kd,
                             float threshold, float floor_, void* partials, float* tiles, NoiseSums* out, void* stream);
 
+// budget.hip (include/myraytracer_amd.h, "budget allocation on the device"): mrt_budget_allocate's allocation as an exact selection
+// over the keys (G, j, t) -- G = 0 for a mandatory frame, else the complemented bits of g'(t, j) -- by a radix select of 8-bit
+// digits, most significant first: G's eight, then j, then t's four.  One launch per digit (a histogram of the digit over the
+// candidates that match the digits fixed so far; every workgroup derives those itself from the earlier launches' histograms), one
+// that counts every tile's keys at or below the selected one and sums each block of 64 tiles, one that adds the blocks' sums.
+// Integer atomics only; the result depends on the inputs alone.
+// Where it all lives: the tile-map allocation of alloc_noise_set, in 4-byte words from d_noise_tiles.  The `ring` maps stay first,
+// entry i at i * n_tiles; behind them entry i's plan at plan + i * plan_stride -- the mrt_budget_result (16 words), then k_t per
+// tile: one contiguous read-back --; then the selection's scratch, which the queries share in stream order: the digits'
+// histograms and the blocks' partial sums P_b (var_before's, then var_after's).
+constexpr uint32_t kBudgetDigits = 13, kBudgetBins = 256, kBudgetSumTiles = 64;
+constexpr uint32_t kBudgetMaxN = 1u << 24;       // the largest n_t an allocation accepts (mrt_budget_allocate's limit)
+struct BudgetLayout { size_t plan, plan_stride, hist, sums, words; uint32_t blocks; };
+inline BudgetLayout budget_layout(size_t n_tiles, uint32_t ring) {
+    const size_t nt = n_tiles ? n_tiles : 1;
+    BudgetLayout l{};
+    l.blocks = (uint32_t)((nt + kBudgetSumTiles - 1) / kBudgetSumTiles);
+    size_t at = (size_t)ring * nt;
+    at += at & 1;                                        // (the results hold 8-byte fields)
+    l.plan = at;
+    l.plan_stride = sizeof(mrt_budget_result) / 4 + nt + (nt & 1);
+    at += (size_t)ring * l.plan_stride;
+    at = (at + 3) & ~(size_t)3;                          // (a histogram is read 16 bytes a lane)
+    l.hist = at; at += (size_t)kBudgetDigits * kBudgetBins;
+    l.sums = at; at += 4 * (size_t)l.blocks;             // 2 x blocks doubles
+    l.words = at;
+    return l;
+}
+struct BudgetArgs {
+    const float* s;             // the summed-S map
+    const uint32_t* n;          // n_t per tile, or null: n_uniform everywhere
+    const double* K;            // K(n) for n <= the largest n_t + max_frames + 1
+    uint32_t n_uniform, n_tiles, max_frames;
+    uint64_t budget;
+    uint32_t* hist;             // kBudgetDigits x kBudgetBins
+    double* sums;               // 2 x ceil(n_tiles / 64)
+    mrt_budget_result* res;
+    uint32_t* k_out;            // n_tiles
+};
+int launch_budget_plan(const BudgetArgs& a, void* stream);
+
 // adaptive.hip (include/myraytracer_amd.h, "adaptive sampling"): the per-tile blend of a frame whose tiles have their own frame
 // counts.  One wave per tile of `list` (null: every tile 0 .. n - 1), in place on `fb` (and S with noise_s): w =
 // mrt_frame_weight(tile_frames[t], max_w) as the same float expression, the blend and S update finalize_kernel<false> /

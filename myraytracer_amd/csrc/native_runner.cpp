@@ -25,7 +25,7 @@ static void usage() {
         "                     [--max-framebuffer-weight F] [--frames N] [--warmup N] [--seed N] [--rng stream|counter]\n"
         "                     [--scene default|cover|cover-glass|stress | --scene-file FILE] [--save-scene FILE]\n"
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
-                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive | --budget N]]\n"
+                         "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive | --budget N [--plan-on-device]]]\n"
         "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]] [--denoise-mix [GAIN]]]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
@@ -35,6 +35,8 @@ static void usage() {
         "  --budget N:         with --target-noise (one GPU): every chunk after the first spends N tile-frames (one frame of one 8x8\n"
         "                      tile each) where the summed-S map of the report one check earlier says they lower the image's\n"
         "                      variance most, at most min(--check-every, 32) per tile (mrt_render_budget); prints each chunk's allocation\n"
+        "  --plan-on-device:   with --budget: the queries allocate on the device behind their reduction (mrt_noise_query_budget) and the\n"
+        "                      chunks render those plans (mrt_render_planned: a plan is a target, frames queued since its query count)\n"
         "  --denoise-out FILE: noise tracking on; also writes the denoised final frame (.pfm / .ppm / .png); with several GPUs the\n"
         "                      noise estimate is gathered with the frame and the first GPU denoises the gathered frame; with\n"
         "                      --adaptive the per-tile filter of an adaptive accumulation is turned on (mrt_set_denoise_adaptive)\n"
@@ -54,7 +56,7 @@ int main(int argc, char** argv) {
     uint32_t frames = 1, warmup = 0, rng_mode = MRT_RNG_PIXEL_STREAM; uint64_t seed = 1; int device = 0;
     uint32_t hint_div = 0, hint_mult = 0, check_every = 16, denoise_var = MRT_DENOISE_VAR_ACCUMULATED, spatial_frames = 3;
     double target_noise = -1.0;
-    bool adaptive = false;
+    bool adaptive = false, plan_on_device = false;
     uint64_t budget = 0;
     mrt_denoise_mix mix;
     mrt_denoise_mix_default(&mix);
@@ -66,6 +68,7 @@ int main(int argc, char** argv) {
         if (eq != std::string::npos) { v = a.substr(eq + 1); a = a.substr(0, eq); }
         else if (a == "--help" || a == "-h") { usage(); return 0; }
         else if (a == "--adaptive") { adaptive = true; continue; }
+        else if (a == "--plan-on-device") { plan_on_device = true; continue; }
         else if (a == "--denoise-mix" && (i + 1 >= argc || !std::strncmp(argv[i + 1], "--", 2))) { mix.enabled = 1; continue; }   // (no GAIN)
         else if (i + 1 < argc) v = argv[++i];
         else { usage(); return 2; }
@@ -166,6 +169,7 @@ int main(int argc, char** argv) {
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (budget && (adaptive || target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--budget wants --target-noise and one GPU, and not --adaptive\n"); destroy_all(); return 2; }
+    if (plan_on_device && !budget) { std::fprintf(stderr, "--plan-on-device wants --budget\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
         if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));
@@ -198,6 +202,8 @@ int main(int argc, char** argv) {
         uint64_t tile_frames = 0;         // tiles x frames queued: at most 64 x spp samples each
         mrt_budget_result spent{};        // --budget: the latest chunk's allocation
         bool idle = false;                // ... which found nothing to spend on
+        // --plan-on-device: the plans hold at most plan_frames frames a tile; a last chunk with fewer frames left is the host's
+        const uint32_t plan_frames = std::min(check_every, 32u);
         auto chunk = [&]() -> int {
             const uint32_t k = std::min(check_every, frames - done);
             for (mrt_ctx* c : ctxs) {
@@ -206,6 +212,13 @@ int main(int argc, char** argv) {
                 if (adaptive && earlier != 0) {
                     uint64_t used = 0;
                     s_ = mrt_render_adaptive(c, k, earlier, &used, &selected);
+                } else if (budget && plan_on_device && earlier != 0 && k >= plan_frames) {
+                    mrt_budget_result planned{};
+                    s_ = mrt_render_planned(c, earlier, &spent, nullptr, 0);
+                    if (s_ == MRT_OK) s_ = mrt_read_budget_plan(c, earlier, nullptr, 0, &planned);
+                    idle = planned.tile_frames == 0;        // (a plan that is met already is not the end: the next one may not be)
+                    tile_frames += spent.tile_frames;
+                    selected = 0;
                 } else if (budget && earlier != 0) {
                     s_ = mrt_render_budget(c, budget, std::min(k, 32u), earlier, &spent, nullptr, 0);
                     idle = spent.tile_frames == 0;
@@ -225,7 +238,8 @@ int main(int argc, char** argv) {
         };
         auto query = [&]() -> int {
             for (mrt_ctx* c : ctxs) {
-                const int s_ = mrt_noise_query_map(c, 0.02f, 0.01f, budget ? MRT_TILE_MAP_SUM_S : MRT_TILE_MAP_MAX_REL);
+                const int s_ = plan_on_device ? mrt_noise_query_budget(c, 0.02f, 0.01f, budget, plan_frames)
+                                              : mrt_noise_query_map(c, 0.02f, 0.01f, budget ? MRT_TILE_MAP_SUM_S : MRT_TILE_MAP_MAX_REL);
                 if (s_ != MRT_OK) return s_;
             }
             return MRT_OK;

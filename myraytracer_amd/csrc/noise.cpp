@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 
 #include "mrt_ctx.h"
 
@@ -15,7 +16,8 @@ void free_noise_buffers(mrt_ctx* c) { free_device(c->d_noise_s, c->d_noise_tiles
 int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, void** partials) {
     const size_t texels = (size_t)local_bands * kBandRows * c->args.width, n = texels ? texels : 1;
     const size_t n_tiles = (size_t)((c->args.width + kTileW - 1) / kTileW) * local_bands;
-    const size_t map_floats = (size_t)mrt_ctx::kNoiseRing * (n_tiles ? n_tiles : 1);     // a tile map per report of the ring
+    // a tile map per report of the ring; behind them the reports' budget plans and the selection's scratch (budget_layout)
+    const size_t map_floats = mrt::budget_layout(n_tiles, mrt_ctx::kNoiseRing).words;
     const int st = [&]() -> int {
         HIP_TRY(c, hipMalloc((void**)s, n * sizeof(float)));
         HIP_TRY(c, hipMemsetAsync(*s, 0, n * sizeof(float), c->stream));
@@ -133,12 +135,27 @@ int mrt_set_noise_tracking(mrt_ctx* c, int enabled) {
     return MRT_OK;
 }
 
-// mrt_noise_query and mrt_noise_query_map: map_kind 0 queues exactly what mrt_noise_query always has
-static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_kind) {
+// mrt_noise_query and mrt_noise_query_map: map_kind 0 queues exactly what mrt_noise_query always has.  With `plan`
+// (mrt_noise_query_budget: a summed-S query) the allocation of budget.hip is queued behind the reduction, ahead of the entry's
+// copy and event, from n_t as the host knows it here: the device's at this point of the stream.
+struct PlanAsk { uint64_t budget; uint32_t max_frames; };
+static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_kind, const PlanAsk* plan = nullptr) {
     if (!c || map_kind > MRT_TILE_MAP_SUM_S) return MRT_ERR_INVALID_ARG;
     if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_noise_query: noise tracking is off (mrt_set_noise_tracking)");
     if (!noise_args_ok(threshold, floor_))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
+    uint32_t plan_most = c->frames_done;                // the largest n_t the plan is allocated for
+    if (plan) {
+        if (plan->max_frames < 1 || plan->max_frames > mrt::kMaxFrameBatch)
+            return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: max_frames %u (1 .. %u)", plan->max_frames, mrt::kMaxFrameBatch);
+        if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_noise_query_budget: a shard (world %u) has no budgets", c->shard_world);
+        if (c->tiles_diverged) {
+            plan_most = 0;
+            for (uint32_t t : c->tile_frames) plan_most = std::max(plan_most, t);
+        }
+        if (plan_most > mrt::kBudgetMaxN)
+            return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: a tile has more than %u frames", mrt::kBudgetMaxN);
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t seq = c->noise_seq + 1;
     const uint32_t i = (uint32_t)(seq % kNoiseRing);
@@ -149,6 +166,8 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
         MRT_TRY(mrt::wait_event(c, E.copied, what));
     }
     float* map = c->d_noise_tiles + (size_t)i * mrt::tiles_min1(c);
+    // the plan reads K up to the largest n_t + max_frames + 1 (the first such call may grow the table: the bounded wait of ensure_k_table)
+    if (plan) MRT_TRY(mrt::ensure_k_table(c, plan_most + plan->max_frames + 2u));
     double K = mrt::noise_factor_of(c->noise_c2);
     int e = 0;
     const bool sum_s = map_kind == MRT_TILE_MAP_SUM_S;
@@ -176,8 +195,32 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
                                                map, c->d_noise_sums + i, c->stream);
     }
     if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
+    E.has_plan = false;
+    if (plan) {
+        const mrt::BudgetLayout L = mrt::budget_layout(c->n_tiles, kNoiseRing);
+        uint32_t* words = reinterpret_cast<uint32_t*>(c->d_noise_tiles);
+        uint32_t* at = words + L.plan + (size_t)i * L.plan_stride;
+        mrt::BudgetArgs a{};
+        a.s = map;
+        a.n = c->tiles_diverged ? c->d_tile_frames : nullptr;
+        a.K = c->d_k_f64;
+        a.n_uniform = c->frames_done; a.n_tiles = c->n_tiles; a.max_frames = plan->max_frames;
+        a.budget = plan->budget;
+        a.hist = words + L.hist;
+        a.sums = reinterpret_cast<double*>(words + L.sums);
+        a.res = reinterpret_cast<mrt_budget_result*>(at);
+        a.k_out = at + sizeof(mrt_budget_result) / sizeof(uint32_t);
+        e = mrt::launch_budget_plan(a, c->stream);
+        if (e) return fail(c, MRT_ERR_HIP, "budget allocation launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
     HIP_TRY(c, hipMemcpyAsync(c->h_noise_sums + i, c->d_noise_sums + i, sizeof(mrt::NoiseSums), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(E.copied, c->stream));
+    if (plan) {
+        E.has_plan = true;
+        E.nq_uniform = c->frames_done;
+        if (c->tiles_diverged) E.nq = c->tile_frames;
+        else E.nq.clear();
+    }
     E.report = mrt_noise_report{};
     E.report.seq = seq;
     E.report.frames_done = c->frames_done;
@@ -192,6 +235,11 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
 int mrt_noise_query(mrt_ctx* c, float threshold, float floor_) { return noise_query(c, threshold, floor_, MRT_TILE_MAP_MAX_REL); }
 
 int mrt_noise_query_map(mrt_ctx* c, float threshold, float floor_, uint32_t map_kind) { return noise_query(c, threshold, floor_, map_kind); }
+
+int mrt_noise_query_budget(mrt_ctx* c, float threshold, float floor_, uint64_t budget, uint32_t max_frames) {
+    const PlanAsk plan{budget, max_frames};
+    return noise_query(c, threshold, floor_, MRT_TILE_MAP_SUM_S, &plan);
+}
 
 int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
@@ -249,12 +297,14 @@ namespace {
 // report_seq == 0: the newest finished report of that kind, without waiting (*seq = 0: none); any other: that report, which must
 // be held and of that kind, after a bounded wait on the host for its copy -- so *seq != 0 names a report whose `copied` the
 // host has seen complete.
-int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kind, uint64_t* seq) {
+// plan: only a report that carries a budget plan (mrt_noise_query_budget) will do.
+int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kind, uint64_t* seq, bool plan = false) {
     const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
     *seq = 0;
     if (report_seq == 0) {
         for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
             if (c->noise_ring[k % kNoiseRing].report.reserved != kind) continue;
+            if (plan && !c->noise_ring[k % kNoiseRing].has_plan) continue;
             const hipError_t q = hipEventQuery(c->noise_ring[k % kNoiseRing].copied);
             if (q == hipErrorNotReady) { (void)hipGetLastError(); continue; }
             if (q != hipSuccess) return fail(c, MRT_ERR_HIP, "%s: %s", who, hipGetErrorString(q));
@@ -269,6 +319,8 @@ int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kin
     if (c->noise_ring[report_seq % kNoiseRing].report.reserved != kind)
         return fail(c, MRT_ERR_STATE, "%s: report %llu holds a tile map of kind %u, not %u (mrt_noise_query_map)", who,
                     (unsigned long long)report_seq, c->noise_ring[report_seq % kNoiseRing].report.reserved, kind);
+    if (plan && !c->noise_ring[report_seq % kNoiseRing].has_plan)
+        return fail(c, MRT_ERR_STATE, "%s: report %llu carries no plan (mrt_noise_query_budget)", who, (unsigned long long)report_seq);
     char what[96];
     std::snprintf(what, sizeof what, "%s: report %llu", who, (unsigned long long)report_seq);
     MRT_TRY(mrt::wait_event(c, c->noise_ring[report_seq % kNoiseRing].copied, what));
@@ -276,15 +328,60 @@ int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kin
     return MRT_OK;
 }
 
-// report `seq`'s tile map (choose_report's: its copy has landed) into c->h_select_map
-int read_report_map(mrt_ctx* c, const char* who, uint64_t seq, uint32_t nt) {
-    // the map was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
+// `bytes` of what report `seq` (choose_report's: its copy has landed) left at `src` on the device -- its tile map, or its plan --
+// into `dst`
+int read_report_data(mrt_ctx* c, const char* who, uint64_t seq, const void* src, size_t bytes, void* dst) {
+    // it was written before the report's copy: behind its event, on a stream of its own (the ctx's may hold frames)
     if (!c->noise_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->noise_stream, hipStreamNonBlocking));
-    c->h_select_map.resize(nt);
     HIP_TRY(c, hipStreamWaitEvent(c->noise_stream, c->noise_ring[seq % kNoiseRing].copied, 0));
-    HIP_TRY(c, hipMemcpyAsync(c->h_select_map.data(), c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float),
-                              hipMemcpyDeviceToHost, c->noise_stream));
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->noise_stream));
     return mrt::wait_stream(c, c->noise_stream, who);
+}
+
+// report `seq`'s tile map into c->h_select_map
+int read_report_map(mrt_ctx* c, const char* who, uint64_t seq, uint32_t nt) {
+    c->h_select_map.resize(nt);
+    return read_report_data(c, who, seq, c->d_noise_tiles + (size_t)(seq % kNoiseRing) * nt, (size_t)nt * sizeof(float), c->h_select_map.data());
+}
+
+// report `seq`'s plan as allocated (choose_report's, with a plan) into c->h_plan: the mrt_budget_result, then k_t per tile
+// (k == null: the result alone, 64 bytes)
+int read_report_plan(mrt_ctx* c, const char* who, uint64_t seq, uint32_t nt, mrt_budget_result* r, const uint32_t** k) {
+    constexpr size_t head = sizeof(mrt_budget_result) / sizeof(uint32_t);
+    const mrt::BudgetLayout L = mrt::budget_layout(nt, kNoiseRing);
+    c->h_plan.resize(head + nt);
+    const uint32_t* at = reinterpret_cast<const uint32_t*>(c->d_noise_tiles) + L.plan + (size_t)(seq % kNoiseRing) * L.plan_stride;
+    MRT_TRY(read_report_data(c, who, seq, at, (head + (k ? nt : 0)) * sizeof(uint32_t), c->h_plan.data()));
+    std::memcpy(r, c->h_plan.data(), sizeof *r);
+    r->used_seq = seq;
+    if (k) *k = c->h_plan.data() + head;
+    return MRT_OK;
+}
+
+// L_j = {t : k_t >= j}, j = 1 .. frames (the largest k_t), in ascending tile id; consecutive j with the same list (the lists
+// only shrink: the same size) are one mrt_render_tiles call
+int render_levels(mrt_ctx* c, const uint32_t* k, uint32_t nt, uint32_t frames) {
+    for (uint32_t j = 1; j <= frames;) {
+        c->selection.clear();
+        for (uint32_t t = 0; t < nt; t++)
+            if (k[t] >= j) c->selection.push_back(t);
+        uint32_t run = 1;
+        const auto listed = [&](uint32_t level) { return (size_t)std::count_if(k, k + nt, [&](uint32_t v) { return v >= level; }); };
+        while (j + run <= frames && listed(j + run) == c->selection.size()) run++;
+        MRT_TRY(mrt_render_tiles(c, c->selection.data(), c->selection.size(), run));
+        j += run;
+    }
+    return MRT_OK;
+}
+
+// mrt_render_tiles' refusals, for the callers that must refuse before anything is queued
+int render_tiles_refusals(mrt_ctx* c, const char* who) {
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) renders whole frames only", who, c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene (call mrt_set_world first)", who);
+    if (c->locals.rng_mode == MRT_RNG_COUNTER && c->locals.samples_per_frame > MRT_COUNTER_BLOCK)
+        return fail(c, MRT_ERR_INVALID_ARG, "%s: counter mode renders at most %u samples per frame by tiles (%u)", who,
+                    (unsigned)MRT_COUNTER_BLOCK, c->locals.samples_per_frame);
+    return MRT_OK;
 }
 
 }  // namespace
@@ -425,18 +522,60 @@ int mrt_render_budget(mrt_ctx* c, uint64_t budget, uint32_t max_frames, uint64_t
     r.used_seq = seq;
     if (res) *res = r;
     if (k_out) std::copy(k.begin(), k.end(), k_out);
-    // L_j = {t : k_t >= j}; consecutive j with the same list (the lists only shrink: the same size) are one call
-    for (uint32_t j = 1; j <= r.frames;) {
-        c->selection.clear();
-        for (uint32_t t = 0; t < nt; t++)
-            if (k[t] >= j) c->selection.push_back(t);
-        uint32_t run = 1;
-        const auto listed = [&](uint32_t level) { return (size_t)std::count_if(k.begin(), k.end(), [&](uint32_t v) { return v >= level; }); };
-        while (j + run <= r.frames && listed(j + run) == c->selection.size()) run++;
-        MRT_TRY(mrt_render_tiles(c, c->selection.data(), c->selection.size(), run));
-        j += run;
-    }
+    return render_levels(c, k.data(), nt, r.frames);
+}
+
+int mrt_read_budget_plan(mrt_ctx* c, uint64_t report_seq, uint32_t* k_out, size_t cap, mrt_budget_result* res) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    mrt_budget_result r{};
+    r.size = sizeof r;
+    if (res) *res = r;
+    const uint32_t nt = c->n_tiles;
+    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_budget_plan: need %u values", nt);
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_read_budget_plan: noise tracking is off (mrt_set_noise_tracking)");
+    if (k_out) std::fill(k_out, k_out + nt, 0u);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint64_t seq = 0;
+    MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq, true));
+    if (seq == 0 || nt == 0) return MRT_OK;               // no report with a plan has finished
+    const uint32_t* k = nullptr;
+    MRT_TRY(read_report_plan(c, __func__, seq, nt, &r, k_out ? &k : nullptr));
+    if (res) *res = r;
+    if (k_out) std::copy(k, k + nt, k_out);
     return MRT_OK;
+}
+
+int mrt_render_planned(mrt_ctx* c, uint64_t report_seq, mrt_budget_result* res, uint32_t* k_out, size_t cap) {
+    if (!c) return MRT_ERR_INVALID_ARG;
+    mrt_budget_result r{};
+    r.size = sizeof r;
+    if (res) *res = r;
+    const uint32_t nt = c->n_tiles;
+    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_render_planned: need %u values", nt);
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_planned: noise tracking is off (mrt_set_noise_tracking)");
+    MRT_TRY(render_tiles_refusals(c, __func__));
+    if (k_out) std::fill(k_out, k_out + nt, 0u);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint64_t seq = 0;
+    MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq, true));
+    if (seq == 0 || nt == 0) return MRT_OK;               // no report with a plan has finished: nothing to render
+    const uint32_t* k = nullptr;
+    MRT_TRY(read_report_plan(c, __func__, seq, nt, &r, &k));
+    // the plan is a target: tile t should reach n_q[t] + k_t frames, and the frames queued since the query count towards it
+    const NoiseEntry& E = c->noise_ring[seq % kNoiseRing];
+    std::vector<uint32_t> left(nt);
+    r.tile_frames = 0; r.tiles = 0; r.frames = 0;
+    for (uint32_t t = 0; t < nt; t++) {
+        const uint64_t target = (uint64_t)(E.nq.empty() ? E.nq_uniform : E.nq[t]) + k[t];
+        const uint64_t now = c->tiles_diverged ? c->tile_frames[t] : c->frames_done;
+        left[t] = target > now ? (uint32_t)(target - now) : 0u;
+        r.tile_frames += left[t];
+        r.tiles += left[t] ? 1u : 0u;
+        r.frames = std::max(r.frames, left[t]);
+    }
+    if (res) *res = r;
+    if (k_out) std::copy(left.begin(), left.end(), k_out);
+    return render_levels(c, left.data(), nt, r.frames);
 }
 
 int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32_t width, uint32_t rows, double K,

@@ -14,7 +14,17 @@
    and the cost of the call: the host time of mrt_render_budget per chunk (allocation, read-back of the map and the queueing),
    of mrt_budget_allocate alone on the last map, and the chunk's wall time.
    --trace: a short run for rocprofv3 --kernel-trace --stats: queries of both kinds on a uniform and on a diverged accumulation.
-   python scripts/adaptive_budget_quality.py [w h] [--frames 66] [--ref 2048] [--every 8] [--max-frames 4,8,16] [--chunk-frames 2]"""
+   --plan device (profiles/budget_plan_rates.txt): beside every "budget M" run, the same loop with the allocation on the device
+     budget M, device          noise_query(budget=chunk, max_frames=M) after every chunk and render_planned(the report one check
+                               before the newest): the same one-check lag, under the target rule -- frames queued since a plan's
+                               query count towards it, so a chunk may queue less than its plan and the run takes more chunks
+     budget M, host / device, lag 0   the chunk renders the plan of the query just queued (it waits for that query: nothing
+                               overlaps, nothing is discounted)
+   and the host time per chunk of the query plus mrt_render_planned against mrt_render_budget's.
+   --trace --plan device: for rocprofv3 --kernel-trace --stats, per max_frames of its own: 20 noise_query(budget=chunk) on a
+     diverged accumulation (the budget_* kernels are the allocation), and mrt_budget_allocate's host time on the same map and n_t.
+   python scripts/adaptive_budget_quality.py [w h] [--frames 66] [--ref 2048] [--every 8] [--max-frames 4,8,16] [--chunk-frames 2]
+                                             [--plan host|device]"""
 import argparse
 import os
 import sys
@@ -37,6 +47,7 @@ ap.add_argument("--max-frames", default="4,8,16")
 ap.add_argument("--chunk-frames", type=int, default=2)
 ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--trace", action="store_true")
+ap.add_argument("--plan", choices=("host", "device"), default="host")
 a = ap.parse_args()
 W, H = a.size
 SPHERES, CAM = M.scene_cover(1, True)
@@ -78,6 +89,70 @@ def budget_run(st, max_frames, total, chunk, log):
         spent += res["tile_frames"]
     return spent
 
+
+def planned_run(st, max_frames, total, chunk, log, device, lag):
+    """budget_run with the allocation on the device (device) or without the lag (lag 0: the chunk renders from the query just
+    queued); log: (host time of the query and the render call, the chunk's wall time, the result)"""
+    budgets = {}                                           # a device plan's budget is fixed at its query: what was left then
+
+    def query():
+        left = max(1, min(chunk, total - spent))
+        if device:
+            st.noise_query(a.thr, a.floor, budget=left, max_frames=max_frames)
+        else:
+            st.noise_query(a.thr, a.floor, tile_map="sum_s")
+            budgets[len(budgets) + 1] = left
+
+    def render(seq):
+        return st.render_planned(seq) if device else st.render_budget(budgets[seq], max_frames, seq)
+    spent = idle = 0
+    st.set_noise_tracking(True)
+    st.render(a.every)
+    query()
+    st.render(a.every)
+    earlier = st.noise_result(wait=True)
+    t0 = time.perf_counter()
+    query()
+    while spent < total and idle < 2:
+        if lag == 0:
+            res = render(st.noise_result(wait=True)["seq"])
+            t1 = time.perf_counter()
+        else:
+            res = render(earlier["seq"])
+            t1 = time.perf_counter()
+            earlier = st.noise_result(wait=True)
+        log.append((t1 - t0, time.perf_counter() - t0, res))
+        t0 = time.perf_counter()
+        query()
+        idle = idle + 1 if res["tile_frames"] == 0 else 0   # (a plan met by the chunk before it queues nothing: not the end)
+        spent += res["tile_frames"]
+    return spent
+
+
+if a.trace and a.plan == "device":
+    mf = int(a.max_frames.split(",")[0])
+    with state() as st:
+        st.set_noise_tracking(True)
+        st.render(16)
+        n_tiles = st.tile_frames().size
+        st.noise_query(a.thr, a.floor, budget=a.chunk_frames * n_tiles, max_frames=mf)
+        st.render_planned(st.noise_result(wait=True)["seq"])          # diverged, as a run's accumulation is
+        st.sync()
+        for _ in range(20):
+            st.noise_query(a.thr, a.floor, budget=a.chunk_frames * n_tiles, max_frames=mf)
+        seq = st.noise_result(wait=True)["seq"]
+        plan = st.budget_plan(seq)
+        s_map, n_t = st.read_noise_tiles(), st.tile_frames()
+        ts = []
+        for _ in range(9):
+            t0 = time.perf_counter()
+            k, res = M.State.budget_allocate(s_map, n_t, 1.0, a.chunk_frames * n_tiles, mf)
+            ts.append(time.perf_counter() - t0)
+        assert np.array_equal(k, plan["k"]) and res["tile_frames"] == plan["tile_frames"]
+        print(f"trace run done: {n_tiles} tiles, max_frames {mf}, budget {a.chunk_frames * n_tiles}: the plan gives {plan['tile_frames']} "
+              f"tile-frames to {plan['tiles']} tiles, equal to mrt_budget_allocate's, which took a median {np.median(ts) * 1e3:.2f} ms "
+              f"(min {min(ts) * 1e3:.2f}) on the same map and n_t", flush=True)
+    sys.exit(0)
 
 if a.trace:
     with state() as st:
@@ -140,6 +215,15 @@ for mf in [int(s) for s in a.max_frames.split(",")]:
         sec = time.perf_counter() - t0
         results[f"budget {mf}"] = line(f"budget, max_frames {mf}", st, sec, f"  chunks {len(log)}")
         last_map, last_n = st.read_noise_tiles(), st.tile_frames()
+    for name, device, lag in (("device", True, 1), ("host, lag 0", False, 0), ("device, lag 0", True, 0)) if a.plan == "device" else ():
+        with state() as st:
+            st.sync()
+            log = logs[(mf, name)] = []
+            t0 = time.perf_counter()
+            planned_run(st, mf, total, chunk, log, device, lag)
+            st.sync()
+            sec = time.perf_counter() - t0
+            results[f"budget {mf}, {name}"] = line(f"budget {mf}, {name}", st, sec, f"  chunks {len(log)}")
 slowest = max(v[1] for k, v in results.items() if k.startswith("budget"))
 frames_wall = max(1, round(a.frames * slowest / results["uniform"][1]))
 with state() as st:
@@ -160,6 +244,12 @@ for mf, log in logs.items():
     call = np.array([c for c, _, r in log if r["tile_frames"]]) * 1e3
     whole = np.array([w for _, w, r in log if r["tile_frames"]]) * 1e3
     lv = [r["frames"] for _, _, r in log if r["tile_frames"]]
+    if isinstance(mf, tuple):
+        what = "query + mrt_render_planned" if mf[1].startswith("device") else "query + mrt_render_budget"
+        print(f"  max_frames {mf[0]:2d}, {mf[1]}: {what} host time per chunk median {np.median(call):.2f} ms (min {call.min():.2f}, max "
+              f"{call.max():.2f}); chunk to its report median {np.median(whole):.2f} ms; frames per chunk {min(lv)}..{max(lv)}; "
+              f"chunks that queued nothing {sum(1 for _, _, r in log if not r['tile_frames'])}", flush=True)
+        continue
     print(f"  max_frames {mf:2d}: mrt_render_budget host time per chunk median {np.median(call):.2f} ms (min {call.min():.2f}, max {call.max():.2f}); "
           f"chunk to its report median {np.median(whole):.2f} ms; frames per chunk {min(lv)}..{max(lv)}", flush=True)
 for mf in [int(s) for s in a.max_frames.split(",")]:
