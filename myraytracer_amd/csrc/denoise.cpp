@@ -175,9 +175,7 @@ int queue_gathered_denoise(mrt_ctx* c) {
 int queue_denoise(mrt_ctx* c) {
     if (c->denoise_adaptive && c->tiles_diverged) {
         // K per tile: the device table covers every count of the host's map, which is the device's at this point of the stream
-        uint32_t most = 0;
-        for (uint32_t t : c->tile_frames) most = std::max(most, t);
-        MRT_TRY(mrt::ensure_k_table(c, most + 1u));
+        MRT_TRY(mrt::ensure_k_table(c, mrt::most_tile_frames(c) + 1u));
         MRT_TRY(ensure_guides(c));
         mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Tiles);
         job.S = c->d_noise_s;

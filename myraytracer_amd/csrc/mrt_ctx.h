@@ -339,6 +339,17 @@ inline size_t local_texels(const mrt_ctx* c) { return (size_t)c->local_bands * k
 // ... at least 1: the size of an allocation that an empty shard makes all the same
 inline size_t local_texels_min1(const mrt_ctx* c) { return local_texels(c) ? local_texels(c) : 1; }
 inline uint32_t tiles_min1(const mrt_ctx* c) { return c->n_tiles ? c->n_tiles : 1; }
+// the largest n_t of the host's tile map (0 without one): what sizes the K table of a per-tile report, plan or denoise
+inline uint32_t most_tile_frames(const mrt_ctx* c) {
+    uint32_t most = 0;
+    for (uint32_t t : c->tile_frames) most = t > most ? t : most;
+    return most;
+}
+// the oldest noise report still held: not before the last reset, and the ring keeps the newest kNoiseRing
+inline uint64_t oldest_noise_report(const mrt_ctx* c) {
+    const uint64_t in_ring = c->noise_seq >= mrt_ctx::kNoiseRing ? c->noise_seq - mrt_ctx::kNoiseRing + 1 : 1;
+    return c->noise_first > in_ring ? c->noise_first : in_ring;
+}
 // the root's gathered frame (multi_gpu.cpp): the colour's bytes -- every shard's bands, padding included -- and S behind them
 inline size_t gathered_colour_bytes(const mrt_ctx* c) { return local_texels(c) * c->shard_world * 4 * sizeof(float); }
 inline float* gathered_noise(const mrt_ctx* c) { return c->d_gather + gathered_colour_bytes(c) / sizeof(float); }

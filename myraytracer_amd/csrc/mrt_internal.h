@@ -198,10 +198,8 @@ int launch_present(const float* src, uint8_t* dst, uint32_t width, uint32_t rows
 // image_io.cpp, host: {colour, alpha} x 256 thresholds -- t[k] = the smallest float whose code is >= k (t[0] = -inf)
 const float* present_thresholds();
 
-// noise.hip: the noise report's sums over a context's texels (or a caller's buffers): S = local_bands x 8 rows of `width` floats,
-// rgba the framebuffer in the same texel order; local rows whose image row (shard rank of world) is >= height are skipped.
-// tiles: the per-8x8-tile maximum of rel_p, numbered as finalize_kernel numbers them (band x tiles_x + tile column).
-// partials: noise_partials_bytes(width, local_bands) of scratch.  Two kernels on `stream`; *out (device) gets the sums.
+// noise.hip: the noise report's sums over a context's texels (or a caller's buffers) and a map of its 8x8 tiles, numbered as
+// finalize_kernel numbers them (band x tiles_x + tile column).  Two kernels on `stream`; *out (device) gets the sums.
 struct NoiseSums {                  // 48 B
     double sum_s, sum_l;
     unsigned long long pixels, non_finite, above;
@@ -215,22 +213,41 @@ inline double noise_c2_next(double c2, float w) {
     return w == 0.0f ? 1.0 : wd * wd * c2 + (1.0 - wd) * (1.0 - wd);
 }
 inline double noise_factor_of(double c2) { return c2 >= 1.0 ? __builtin_inf() : c2 / (1.0 - c2); }
-int launch_noise_reduce(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
-                        uint32_t rank, uint32_t world, float K, float threshold, float floor_, void* partials, float* tiles,
-                        NoiseSums* out, void* stream);
-// the same after adaptive sampling has diverged (one context, world 1): pixel p of tile t takes K_t = Kf[tile_frames[t]] for var_p
-// (+inf: se_p = +inf) and sums (double)S_p * Kd[tile_frames[t]] -- sum_var itself -- into out->sum_s (tiles whose K is +inf add
-// nothing: the report is "no estimate yet" then).  Kf / Kd: K(n) = mrt_noise_factor(n, max_w) for n < k_len, as float and double.
-int launch_noise_reduce_tiles(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
-                              const uint32_t* tile_frames, const float* Kf, const double* Kd, float threshold, float floor_,
-                              void* partials, float* tiles, NoiseSums* out, void* stream);
-// either of the two with the other kind of tile map (mrt_noise_query_map, MRT_TILE_MAP_SUM_S): *out is bit for bit what
-// launch_noise_reduce (tile_frames null: K, rank and world count) or launch_noise_reduce_tiles (tile_frames, Kf and Kd given: K,
-// rank and world are not read) leaves, and tiles[t] = (float) of the tile's summed S, a double sum in the order the header
-// states.  One pass over the same 20 B per pixel, then noise_final_kernel.
-int launch_noise_reduce_sum(const float* S, const float* rgba, uint32_t width, uint32_t local_bands, uint32_t height,
-                            uint32_t rank, uint32_t world, float K, const uint32_t* tile_frames, const float* Kf, const double* Kd,
-                            float threshold, float floor_, void* partials, float* tiles, NoiseSums* out, void* stream);
+// The recursion by one frame: c2 after frame k of an accumulation whose weights are mrt_frame_weight(k, max_w).  fixed: the weight
+// is saturated -- it stays so, mrt_frame_weight being non-decreasing up to there -- and c2 did not move: every later c2 is this
+// one, so stopping here (mrt_noise_factor, mrt_budget_allocate) and going on (the context's K table) give the same values.
+struct NoiseC2Step { double c2; bool fixed; };
+inline NoiseC2Step noise_c2_step(double c2, uint32_t k, float max_w) {
+    const float w = mrt_frame_weight(k, max_w);
+    const double next = noise_c2_next(c2, w);
+    return {next, k != 0 && w == max_w && max_w < 0.99999988f && next == c2};
+}
+// The arithmetic of every form, in this order.  A pixel is counted if it lies in the image and its S_p and L_p = lum(fb_p) are
+// finite (any other: non_finite alone).  With K the launch's (uniform) or K_t = Kf[n_t], n_t = tile_frames[tile] (per tile), in
+// float: se_p = sqrtf(S_p * K), or +inf where K is +inf; rel_p = se_p / fmaxf(L_p, floor); above counts rel_p > threshold; max_se
+// from 0.  In double: sum_l adds L_p and sum_s adds S_p (uniform: the host multiplies by K) or S_p * Kd[n_t] -- sum_var itself;
+// nothing where K_t is +inf, the report being "no estimate yet" then -- (per tile).  A lane adds its four pixels by ascending
+// column, a wave its lanes by xor-shuffles (32 down to 1), a block its eight rows by ascending row, noise_final_kernel the blocks'
+// partials: thread t takes t, t + 256, ... in order, then a fixed tree.  The map entry of a tile: MRT_TILE_MAP_MAX_REL the largest
+// rel_p of its counted pixels from 0 (a NaN ignored); MRT_TILE_MAP_SUM_S (float) of their summed (double)S_p, every other pixel
+// +0.0: a row's eight columns as ((p0 + p1) + (p2 + p3)) + ((p4 + p5) + (p6 + p7)), then the eight row sums one after the other
+// from the band's bottom row, starting at 0.0.  The map kind changes nothing in *out, and no K enters a summed-S map.
+struct NoiseReduceArgs {
+    const float* S;             // local_bands x 8 rows of `width` floats
+    const float* rgba;          // the framebuffer in the same texel order
+    uint32_t width, local_bands;
+    uint32_t height, rank, world;   // local rows whose image row (shard rank of world) is >= height are skipped
+    float K;                    // the uniform K (tile_frames null)
+    const uint32_t* tile_frames;    // n_t per tile after adaptive sampling has diverged (world 1), or null: uniform
+    const float* Kf;            // with tile_frames: K(n) = mrt_noise_factor(n, max_w) for every n_t, as float ...
+    const double* Kd;           // ... and as double
+    float threshold, floor;
+    uint32_t map_kind;          // MRT_TILE_MAP_MAX_REL or MRT_TILE_MAP_SUM_S
+    void* partials;             // noise_partials_bytes(width, local_bands) of scratch
+    float* tiles;               // the map
+    NoiseSums* out;
+};
+int launch_noise_reduce(const NoiseReduceArgs& a, void* stream);
 
 // budget.hip (include/myraytracer_amd.h, "budget allocation on the device"): mrt_budget_allocate's allocation as an exact selection
 // over the keys (G, j, t) -- G = 0 for a mandatory frame, else the complemented bits of g'(t, j) -- by a radix select of 8-bit

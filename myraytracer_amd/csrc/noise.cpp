@@ -47,7 +47,7 @@ int ensure_k_table(mrt_ctx* c, uint32_t len) {
     const float max_w = c->args.max_framebuffer_weight;
     while (c->k_table.size() < cap) {
         c->k_table.push_back(mrt::noise_factor_of(c->k_c2));     // K after k_table.size() frames
-        c->k_c2 = mrt::noise_c2_next(c->k_c2, mrt_frame_weight((uint32_t)(c->k_table.size() - 1), max_w));
+        c->k_c2 = mrt::noise_c2_step(c->k_c2, (uint32_t)(c->k_table.size() - 1), max_w).c2;
     }
     std::vector<float> kf(c->k_table.begin(), c->k_table.end());
     MRT_TRY(mrt::wait_stream(c, c->stream, "growing the K table"));
@@ -108,11 +108,9 @@ extern "C" {
 double mrt_noise_factor(uint32_t frames_done, float max_w) {
     double c2 = 1.0;
     for (uint32_t k = 0; k < frames_done; k++) {
-        const float w = mrt_frame_weight(k, max_w);
-        const double next = mrt::noise_c2_next(c2, w);
-        // a saturated weight stays saturated (mrt_frame_weight is non-decreasing up to there): c2 is at its fixed point
-        if (k != 0 && w == max_w && max_w < 0.99999988f && next == c2) break;
-        c2 = next;
+        const mrt::NoiseC2Step step = mrt::noise_c2_step(c2, k, max_w);
+        if (step.fixed) break;
+        c2 = step.c2;
     }
     return mrt::noise_factor_of(c2);
 }
@@ -144,16 +142,12 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
     if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_noise_query: noise tracking is off (mrt_set_noise_tracking)");
     if (!noise_args_ok(threshold, floor_))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
-    uint32_t plan_most = c->frames_done;                // the largest n_t the plan is allocated for
+    const uint32_t most = c->tiles_diverged ? mrt::most_tile_frames(c) : c->frames_done;       // the largest n_t
     if (plan) {
         if (plan->max_frames < 1 || plan->max_frames > mrt::kMaxFrameBatch)
             return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: max_frames %u (1 .. %u)", plan->max_frames, mrt::kMaxFrameBatch);
         if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_noise_query_budget: a shard (world %u) has no budgets", c->shard_world);
-        if (c->tiles_diverged) {
-            plan_most = 0;
-            for (uint32_t t : c->tile_frames) plan_most = std::max(plan_most, t);
-        }
-        if (plan_most > mrt::kBudgetMaxN)
+        if (most > mrt::kBudgetMaxN)
             return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: a tile has more than %u frames", mrt::kBudgetMaxN);
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -167,33 +161,23 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
     }
     float* map = c->d_noise_tiles + (size_t)i * mrt::tiles_min1(c);
     // the plan reads K up to the largest n_t + max_frames + 1 (the first such call may grow the table: the bounded wait of ensure_k_table)
-    if (plan) MRT_TRY(mrt::ensure_k_table(c, plan_most + plan->max_frames + 2u));
+    if (plan) MRT_TRY(mrt::ensure_k_table(c, most + plan->max_frames + 2u));
     double K = mrt::noise_factor_of(c->noise_c2);
-    int e = 0;
-    const bool sum_s = map_kind == MRT_TILE_MAP_SUM_S;
-    if (!c->tiles_diverged && sum_s) {
-        e = mrt::launch_noise_reduce_sum(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
-                                         c->shard_rank, c->shard_world, (float)K, nullptr, nullptr, nullptr, threshold, floor_,
-                                         c->d_noise_partials, map, c->d_noise_sums + i, c->stream);
-    } else if (!c->tiles_diverged) {
-        e = mrt::launch_noise_reduce(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
-                                     c->shard_rank, c->shard_world, (float)K, threshold, floor_, c->d_noise_partials, map,
-                                     c->d_noise_sums + i, c->stream);
-    } else {                        // adaptive sampling: K per tile; the report's K is the largest (the least-sampled tile's)
-        uint32_t most = 0;
-        for (uint32_t t : c->tile_frames) most = std::max(most, t);
+    mrt::NoiseReduceArgs r{};
+    r.S = c->d_noise_s; r.rgba = c->d_fb[c->target ^ 1];
+    r.width = c->args.width; r.local_bands = c->local_bands; r.height = c->args.height;
+    r.rank = c->shard_rank; r.world = c->shard_world;
+    if (c->tiles_diverged) {        // adaptive sampling: K per tile; the report's K is the largest (the least-sampled tile's)
         MRT_TRY(mrt::ensure_k_table(c, most + 1u));
         K = 0.0;
         for (uint32_t t : c->tile_frames) K = std::max(K, c->k_table[t]);
-        if (sum_s)
-            e = mrt::launch_noise_reduce_sum(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height, 0, 1,
-                                             0.0f, c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials,
-                                             map, c->d_noise_sums + i, c->stream);
-        else
-            e = mrt::launch_noise_reduce_tiles(c->d_noise_s, c->d_fb[c->target ^ 1], c->args.width, c->local_bands, c->args.height,
-                                               c->d_tile_frames, c->d_k_f32, c->d_k_f64, threshold, floor_, c->d_noise_partials,
-                                               map, c->d_noise_sums + i, c->stream);
+        r.tile_frames = c->d_tile_frames; r.Kf = c->d_k_f32; r.Kd = c->d_k_f64;
     }
+    r.K = (float)K;
+    r.threshold = threshold; r.floor = floor_;
+    r.map_kind = map_kind;
+    r.partials = c->d_noise_partials; r.tiles = map; r.out = c->d_noise_sums + i;
+    int e = mrt::launch_noise_reduce(r, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "noise reduction launch failed: %s", hipGetErrorString((hipError_t)e));
     E.has_plan = false;
     if (plan) {
@@ -251,7 +235,7 @@ int mrt_noise_result(mrt_ctx* c, int wait, mrt_noise_report* out) {
         std::snprintf(what, sizeof what, "mrt_noise_result: report %llu", (unsigned long long)c->noise_seq);
         MRT_TRY(mrt::wait_event(c, c->noise_ring[c->noise_seq % kNoiseRing].copied, what));
     }
-    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    const uint64_t oldest = mrt::oldest_noise_report(c);
     for (uint64_t seq = c->noise_seq; seq >= oldest; seq--) {        // the newest whose copy has landed (stream order)
         const uint32_t i = (uint32_t)(seq % kNoiseRing);
         const hipError_t q = hipEventQuery(c->noise_ring[i].copied);
@@ -299,7 +283,7 @@ namespace {
 // host has seen complete.
 // plan: only a report that carries a budget plan (mrt_noise_query_budget) will do.
 int choose_report(mrt_ctx* c, const char* who, uint64_t report_seq, uint32_t kind, uint64_t* seq, bool plan = false) {
-    const uint64_t oldest = std::max<uint64_t>(c->noise_first, c->noise_seq >= kNoiseRing ? c->noise_seq - kNoiseRing + 1 : 1);
+    const uint64_t oldest = mrt::oldest_noise_report(c);
     *seq = 0;
     if (report_seq == 0) {
         for (uint64_t k = c->noise_seq; k >= oldest && k != 0; k--) {
@@ -361,13 +345,15 @@ int read_report_plan(mrt_ctx* c, const char* who, uint64_t seq, uint32_t nt, mrt
 // L_j = {t : k_t >= j}, j = 1 .. frames (the largest k_t), in ascending tile id; consecutive j with the same list (the lists
 // only shrink: the same size) are one mrt_render_tiles call
 int render_levels(mrt_ctx* c, const uint32_t* k, uint32_t nt, uint32_t frames) {
+    std::vector<uint32_t> listed(frames + 2u, 0u);          // listed[j] = |L_j|: a histogram of k, summed from the top
+    for (uint32_t t = 0; t < nt; t++) listed[std::min(k[t], frames)]++;
+    for (uint32_t j = frames; j-- > 0;) listed[j] += listed[j + 1];
     for (uint32_t j = 1; j <= frames;) {
         c->selection.clear();
         for (uint32_t t = 0; t < nt; t++)
             if (k[t] >= j) c->selection.push_back(t);
         uint32_t run = 1;
-        const auto listed = [&](uint32_t level) { return (size_t)std::count_if(k, k + nt, [&](uint32_t v) { return v >= level; }); };
-        while (j + run <= frames && listed(j + run) == c->selection.size()) run++;
+        while (j + run <= frames && listed[j + run] == listed[j]) run++;
         MRT_TRY(mrt_render_tiles(c, c->selection.data(), c->selection.size(), run));
         j += run;
     }
@@ -381,6 +367,23 @@ int render_tiles_refusals(mrt_ctx* c, const char* who) {
     if (c->locals.rng_mode == MRT_RNG_COUNTER && c->locals.samples_per_frame > MRT_COUNTER_BLOCK)
         return fail(c, MRT_ERR_INVALID_ARG, "%s: counter mode renders at most %u samples per frame by tiles (%u)", who,
                     (unsigned)MRT_COUNTER_BLOCK, c->locals.samples_per_frame);
+    return MRT_OK;
+}
+
+// What mrt_render_budget, mrt_read_budget_plan and mrt_render_planned do first, in this order: *r zeroed with its size set and
+// copied to *res, max_frames (where the call has one) in range, k_out's capacity, tracking on, for a call that renders
+// mrt_render_tiles' refusals, k_out zeroed
+int plan_call_opening(mrt_ctx* c, const char* who, const uint32_t* max_frames, bool renders, mrt_budget_result* r,
+                      mrt_budget_result* res, uint32_t* k_out, size_t cap) {
+    *r = mrt_budget_result{};
+    r->size = sizeof *r;
+    if (res) *res = *r;
+    if (max_frames && (*max_frames < 1 || *max_frames > mrt::kMaxFrameBatch))
+        return fail(c, MRT_ERR_INVALID_ARG, "%s: max_frames %u (1 .. %u)", who, *max_frames, mrt::kMaxFrameBatch);
+    if (k_out && cap < c->n_tiles) return fail(c, MRT_ERR_TOO_SMALL, "%s: need %u values", who, c->n_tiles);
+    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "%s: noise tracking is off (mrt_set_noise_tracking)", who);
+    if (renders) MRT_TRY(render_tiles_refusals(c, who));
+    if (k_out) std::fill(k_out, k_out + c->n_tiles, 0u);
     return MRT_OK;
 }
 
@@ -419,25 +422,18 @@ int mrt_render_adaptive(mrt_ctx* c, uint32_t frames, uint64_t report_seq, uint64
 // reached its fixed point at a saturated weight, as mrt_noise_factor's loop does, and K is constant from there.
 int mrt_budget_allocate(const float* s, const uint32_t* n, size_t tiles, float max_w, uint64_t budget, uint32_t max_frames,
                         uint32_t* k_out, mrt_budget_result* res) {
-    constexpr uint32_t kMaxN = 1u << 24;
     if (!s || !n || !k_out || !res || tiles == 0 || max_frames < 1 || max_frames > mrt::kMaxFrameBatch) return MRT_ERR_INVALID_ARG;
     if (!(max_w > 0.0f) || std::isinf(max_w)) return MRT_ERR_INVALID_ARG;
     uint32_t most = 0;
     for (size_t t = 0; t < tiles; t++) {
-        if (n[t] > kMaxN) return MRT_ERR_INVALID_ARG;
+        if (n[t] > mrt::kBudgetMaxN) return MRT_ERR_INVALID_ARG;
         most = std::max(most, n[t]);
     }
     std::vector<double> table;
-    {
-        const uint32_t len = most + max_frames + 1u;
-        double c2 = 1.0;
-        for (uint32_t k = 0; k < len; k++) {
-            table.push_back(mrt::noise_factor_of(c2));          // K(k)
-            const float w = mrt_frame_weight(k, max_w);
-            const double next = mrt::noise_c2_next(c2, w);
-            if (k != 0 && w == max_w && max_w < 0.99999988f && next == c2) break;
-            c2 = next;
-        }
+    mrt::NoiseC2Step at{1.0, false};
+    for (uint32_t k = 0; k < most + max_frames + 1u && !at.fixed; k++) {
+        table.push_back(mrt::noise_factor_of(at.c2));           // K(k)
+        at = mrt::noise_c2_step(at.c2, k, max_w);
     }
     const auto K = [&](uint32_t frames) { return table[std::min<size_t>(frames, table.size() - 1)]; };
     const auto clean = [&](size_t t) { return s[t] >= 0.0f ? (double)s[t] : 0.0; };      // (a NaN compares false)
@@ -490,21 +486,9 @@ int mrt_budget_allocate(const float* s, const uint32_t* n, size_t tiles, float m
 int mrt_render_budget(mrt_ctx* c, uint64_t budget, uint32_t max_frames, uint64_t report_seq, mrt_budget_result* res, uint32_t* k_out,
                       size_t cap) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    mrt_budget_result r{};
-    r.size = sizeof r;
-    if (res) *res = r;
-    if (max_frames < 1 || max_frames > mrt::kMaxFrameBatch)
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: max_frames %u (1 .. %u)", max_frames, mrt::kMaxFrameBatch);
+    mrt_budget_result r;
+    MRT_TRY(plan_call_opening(c, __func__, &max_frames, true, &r, res, k_out, cap));
     const uint32_t nt = c->n_tiles;
-    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_render_budget: need %u values", nt);
-    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_budget: noise tracking is off (mrt_set_noise_tracking)");
-    // mrt_render_tiles' refusals, before anything is queued
-    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_render_budget: a shard (world %u) renders whole frames only", c->shard_world);
-    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "mrt_render_budget: no scene (call mrt_set_world first)");
-    if (c->locals.rng_mode == MRT_RNG_COUNTER && c->locals.samples_per_frame > MRT_COUNTER_BLOCK)
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: counter mode renders at most %u samples per frame by tiles (%u)",
-                    (unsigned)MRT_COUNTER_BLOCK, c->locals.samples_per_frame);
-    if (k_out) std::fill(k_out, k_out + nt, 0u);
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t seq = 0;
     MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq));
@@ -518,7 +502,7 @@ int mrt_render_budget(mrt_ctx* c, uint64_t budget, uint32_t max_frames, uint64_t
     const uint32_t* n = c->tiles_diverged ? c->tile_frames.data() : uniform.data();
     std::vector<uint32_t> k(nt);
     if (mrt_budget_allocate(c->h_select_map.data(), n, nt, c->args.max_framebuffer_weight, budget, max_frames, k.data(), &r) != MRT_OK)
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: a tile has more than %u frames", 1u << 24);
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_render_budget: a tile has more than %u frames", mrt::kBudgetMaxN);
     r.used_seq = seq;
     if (res) *res = r;
     if (k_out) std::copy(k.begin(), k.end(), k_out);
@@ -527,13 +511,9 @@ int mrt_render_budget(mrt_ctx* c, uint64_t budget, uint32_t max_frames, uint64_t
 
 int mrt_read_budget_plan(mrt_ctx* c, uint64_t report_seq, uint32_t* k_out, size_t cap, mrt_budget_result* res) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    mrt_budget_result r{};
-    r.size = sizeof r;
-    if (res) *res = r;
+    mrt_budget_result r;
+    MRT_TRY(plan_call_opening(c, __func__, nullptr, false, &r, res, k_out, cap));
     const uint32_t nt = c->n_tiles;
-    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_budget_plan: need %u values", nt);
-    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_read_budget_plan: noise tracking is off (mrt_set_noise_tracking)");
-    if (k_out) std::fill(k_out, k_out + nt, 0u);
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t seq = 0;
     MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq, true));
@@ -547,14 +527,9 @@ int mrt_read_budget_plan(mrt_ctx* c, uint64_t report_seq, uint32_t* k_out, size_
 
 int mrt_render_planned(mrt_ctx* c, uint64_t report_seq, mrt_budget_result* res, uint32_t* k_out, size_t cap) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    mrt_budget_result r{};
-    r.size = sizeof r;
-    if (res) *res = r;
+    mrt_budget_result r;
+    MRT_TRY(plan_call_opening(c, __func__, nullptr, true, &r, res, k_out, cap));
     const uint32_t nt = c->n_tiles;
-    if (k_out && cap < nt) return fail(c, MRT_ERR_TOO_SMALL, "mrt_render_planned: need %u values", nt);
-    if (!c->noise_on) return fail(c, MRT_ERR_STATE, "mrt_render_planned: noise tracking is off (mrt_set_noise_tracking)");
-    MRT_TRY(render_tiles_refusals(c, __func__));
-    if (k_out) std::fill(k_out, k_out + nt, 0u);
     HIP_TRY(c, hipSetDevice(c->device));
     uint64_t seq = 0;
     MRT_TRY(choose_report(c, __func__, report_seq, MRT_TILE_MAP_SUM_S, &seq, true));
@@ -600,9 +575,15 @@ int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32
     HIP_CHAIN(e, what, hipMalloc((void**)&d_sums, sizeof h));
     if (e == hipSuccess) e = hipMemcpyAsync(d_s, S, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = (hipError_t)mrt::launch_noise_reduce(d_s, d_rgba, width, bands, rows, 0, 1, (float)K, threshold, floor_, d_part, d_tiles,
-                                                 d_sums, c->stream);
+    mrt::NoiseReduceArgs r{};
+    r.S = d_s; r.rgba = d_rgba;
+    r.width = width; r.local_bands = bands; r.height = rows;
+    r.rank = 0; r.world = 1;
+    r.K = (float)K;
+    r.threshold = threshold; r.floor = floor_;
+    r.map_kind = MRT_TILE_MAP_MAX_REL;
+    r.partials = d_part; r.tiles = d_tiles; r.out = d_sums;
+    if (e == hipSuccess) e = (hipError_t)mrt::launch_noise_reduce(r, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d_sums, sizeof h, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && tiles_out) e = hipMemcpyAsync(tiles_out, d_tiles, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     int ws = MRT_OK;

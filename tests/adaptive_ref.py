@@ -58,6 +58,14 @@ class Accum:
         self.frames_done = 0
         self.diverged = False
 
+    def load(self, fb: np.ndarray, S: np.ndarray, n):
+        """mrt_debug_load_accumulation with all three parts: the framebuffer, S and n_t per tile as given, the accumulation
+        adaptive from here on."""
+        assert fb.shape == self.fb.shape and S.shape == self.S.shape and np.size(n) == self.n_tiles
+        self.fb, self.S = np.array(fb, np.float32), np.array(S, np.float32)
+        self.n = np.asarray(n, np.int64).reshape(-1).copy()
+        self.diverged = True
+
     @property
     def n_tiles(self) -> int:
         return self.tr * self.tx

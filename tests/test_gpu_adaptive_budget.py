@@ -3,12 +3,11 @@ a partial last column and a partial top band.  The summed-S tile map against tes
 to the other kind's (uniform, K = +inf, per tile, a shard); render_budget against the restated allocation rendered by hand through
 render_tiles; the mandatory frames; the whole-frame path; render_until(budget=N); nothing to do, the refusals, and
 render_adaptive's choice of report left as it was."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import budget_ref
+from noise_cases import check_same_but_kind, raw_report
 
 pytestmark = pytest.mark.gpu
 
@@ -30,27 +29,14 @@ def _state(mrt, seed=5, max_w=1.0, scene=True, tracking=True, **kw):
     return st
 
 
-def _raw_report(mrt, st):
-    r = mrt._lib.MrtNoiseReport()
-    st._check(st._L.mrt_noise_result(st._ctx, 1, C.byref(r)), "mrt_noise_result")
-    return r
-
-
 def _both_kinds(mrt, st, thr=0.3, fl=0.02):
     """a kind-0 and a kind-1 query of the same state: the reports are equal in every field but seq and reserved; returns the
     kind-1 query's map"""
     st.noise_query(thr, fl)
-    a = _raw_report(mrt, st)
+    a = raw_report(mrt, st)
     st.noise_query(thr, fl, tile_map="sum_s")
-    b = _raw_report(mrt, st)
-    assert b.seq == a.seq + 1 and a.reserved == 0 and b.reserved == 1 and a.reserved2 == b.reserved2 == 0
-    for name, ctype in mrt._lib.MrtNoiseReport._fields_:
-        if name in ("seq", "reserved"):
-            continue
-        x, y = getattr(a, name), getattr(b, name)
-        if ctype in (C.c_double, C.c_float):
-            x, y = np.float64(x).view(np.uint64), np.float64(y).view(np.uint64)
-        assert x == y, (name, getattr(a, name), getattr(b, name))
+    b = raw_report(mrt, st)
+    check_same_but_kind(mrt, a, b)
     return st.read_noise_tiles()
 
 

@@ -9,6 +9,7 @@ import pytest
 
 import noise_ref
 from common import to_oracle_camera, to_oracle_spheres
+from noise_cases import check_report as _check_report, crafted
 
 pytestmark = pytest.mark.gpu
 
@@ -57,18 +58,6 @@ def _run(st, schedule, frames=FRAMES):
         for _ in range(frames):
             st.redraw()
     st.sync()
-
-
-def _check_report(rep, want, exact_seq=None):
-    for k in ("pixels", "above", "non_finite"):
-        assert rep[k] == want[k], (k, rep[k], want[k])
-    for k in ("max_se", "rmse", "rel_rmse", "sum_var"):
-        if math.isinf(want[k]):
-            assert math.isinf(rep[k]), k
-    assert rep["max_se"] == want["max_se"], (rep["max_se"], want["max_se"])
-    for k in ("sum_var", "sum_lum"):
-        if not math.isinf(want[k]):
-            assert abs(rep[k] - want[k]) <= 1e-12 * max(abs(want[k]), 1e-300), (k, rep[k], want[k])
 
 
 @pytest.mark.parametrize("schedule", ["redraw", "batch-lane", "batch-layers", "in-flight-16"])
@@ -141,32 +130,7 @@ def test_reports_agree_across_schedules(mrt):
 
 
 def _crafted():
-    rng = np.random.default_rng(3)
-    cases = []
-    for rows, width in ((1, 1), (1, 37), (3, 5), (9, 13), (17, 64), (20, 250), (8, 257), (40, 1030)):
-        S = (rng.random((rows, width), np.float32) ** 3 * 0.02).astype(np.float32)
-        rgba = rng.random((rows, width, 4), np.float32) * 1.5
-        flat_s, flat_c = S.reshape(-1), rgba.reshape(-1, 4)
-        n = flat_s.size
-        pick = rng.permutation(n)
-        specials = [(0, "s", np.nan), (1, "s", np.inf), (2, "s", -np.inf), (3, "c", np.nan), (4, "c", np.inf),
-                    (5, "c", -np.inf), (6, "zero", 0.0), (7, "s0", 0.0), (8, "big", 3.0e38)]
-        for j, kind, v in specials:
-            if j >= n:
-                break
-            i = pick[j]
-            if kind == "s":
-                flat_s[i] = v
-            elif kind == "c":
-                flat_c[i, j % 3] = v
-            elif kind == "zero":
-                flat_c[i, :3] = 0.0                                     # L = 0 < floor
-            elif kind == "s0":
-                flat_s[i] = 0.0
-            else:
-                flat_s[i] = v                                           # S * K overflows to inf
-        cases.append((S, rgba))
-    return cases
+    return crafted(((1, 1), (1, 37), (3, 5), (9, 13), (17, 64), (20, 250), (8, 257), (40, 1030)))
 
 
 @pytest.mark.parametrize("K", [0.05, 1.0 / 63.0, math.inf])

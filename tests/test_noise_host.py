@@ -124,3 +124,34 @@ def test_tile_map_skips_rows_marked_invalid():
     assert np.isinf(noise_ref.tiles(S, rgba, math.inf)).all()
     m = noise_ref.tiles(S, rgba, math.inf, valid=valid)
     assert np.isinf(m[0]).all() and (m[1] == 0).all()
+
+
+@pytest.mark.parametrize("size", __import__("noise_cases").FORM_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_the_forms_references_agree_on_the_crafted_data(mrt, size):
+    """What tests/test_gpu_noise_forms.py expects, checked without a GPU: at every size the per-tile reference with one count for
+    every tile is the uniform reference, the specials all landed, a K = +inf tile shows in the map and in the report, and the
+    summed-S map holds no K and tells its summation order from the row-major one."""
+    import adaptive_ref
+    import budget_ref
+    import noise_cases
+    w, h = size
+    S, rgba = noise_cases.form_case(size)
+    thr, fl = 0.05, 0.02
+    uni = noise_cases.form_expected(size, "uniform", thr, fl)
+    acc = adaptive_ref.Accum(h, w, noise_cases.FORM_MAX_W)
+    acc.load(rgba, S, np.full(acc.n_tiles, 3))
+    assert np.array_equal(acc.tiles(thr, fl).view(np.uint32), uni["max_rel"].view(np.uint32))
+    noise_cases.check_report(acc.report(thr, fl), uni["report"])
+    assert acc.report(thr, fl)["noise_factor"] == uni["report"]["noise_factor"] == mrt.noise_factor(3, 1.0)
+    assert uni["report"]["non_finite"] == 6 and uni["report"]["pixels"] == w * h - 6 and uni["report"]["max_se"] > 1e19
+    none = noise_cases.form_expected(size, "no-estimate", thr, fl)
+    assert none["report"]["above"] == none["report"]["pixels"] and math.isinf(none["report"]["sum_var"])
+    mixed, finite = (noise_cases.form_expected(size, f, thr, fl) for f in ("per-tile-inf", "per-tile"))
+    assert math.isinf(mixed["report"]["noise_factor"]) and np.isinf(mixed["max_rel"].ravel()[0])
+    assert finite["report"]["noise_factor"] == mrt.noise_factor(2, 1.0) and math.isfinite(finite["report"]["sum_var"])
+    assert 0 < finite["report"]["above"] < finite["report"]["pixels"]
+    for e in (none, mixed, finite):
+        assert np.array_equal(e["sum_s"].view(np.uint32), uni["sum_s"].view(np.uint32))
+        assert e["report"]["pixels"] == uni["report"]["pixels"] and e["report"]["sum_lum"] == uni["report"]["sum_lum"]
+    if w * h >= 2048:
+        assert not np.array_equal(uni["sum_s"], budget_ref.tile_sums_row_major(S, rgba))
