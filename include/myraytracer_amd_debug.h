@@ -308,6 +308,14 @@ int mrt_debug_load_accumulation(mrt_ctx* ctx, const float* rgba, const float* S,
 #define MRT_HOLD_MAX_TICKS 50000000ull
 int mrt_debug_hold(mrt_ctx* ctx, uint32_t which, uint32_t index, uint64_t ticks, uint32_t max_polls);
 int mrt_debug_hold_stamps(mrt_ctx* ctx, uint64_t out[3]);
+/* Diagnostic: the allocation of mrt_noise_query_budget on caller-supplied arrays, synchronously: s = `tiles` summed-S values
+ * (any float), n = `tiles` frame counts, or NULL: n_uniform for every tile; k_out gets `tiles` values, *res the plan's result
+ * (used_seq 0).  The same kernels, launched the same way, in temporary buffers of its own; K is the context's table for its
+ * max_framebuffer_weight, grown as the query grows it, so the yardstick is mrt_budget_allocate(s, n, that weight, ...).  Needs no
+ * noise tracking, no scene and no frames.  max_frames outside 1 .. 32 or an n_t above 2^24: MRT_ERR_INVALID_ARG before anything
+ * is allocated or grown (mrt_noise_query_budget's own checks); tiles 0 or above 2^28, or a NULL pointer: MRT_ERR_INVALID_ARG. */
+int mrt_debug_budget_plan(mrt_ctx* ctx, const float* s, const uint32_t* n, uint32_t n_uniform, size_t tiles, uint64_t budget,
+                          uint32_t max_frames, uint32_t* k_out, mrt_budget_result* res);
 
 #ifdef __cplusplus
 }

@@ -59,7 +59,7 @@ EXPORTS = [
     "mrt_update_materials", "mrt_debug_material_shade",
     "mrt_debug_hold", "mrt_debug_hold_stamps",
     "mrt_noise_query_map", "mrt_budget_allocate", "mrt_render_budget",
-    "mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned",
+    "mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned", "mrt_debug_budget_plan",
 ]
 
 # the present pass (include/myraytracer_amd.h)
@@ -441,6 +441,7 @@ def load():
         "mrt_debug_read_gathered_guides": (i32, [vp, vp, vp, vp, vp, vp, sz]),
         "mrt_debug_hold": (i32, [vp, u32, u32, u64, u32]),
         "mrt_debug_hold_stamps": (i32, [vp, P(u64)]),
+        "mrt_debug_budget_plan": (i32, [vp, vp, vp, u32, sz, C.c_uint64, u32, vp, P(MrtBudgetResult)]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

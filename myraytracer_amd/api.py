@@ -990,6 +990,22 @@ class State:
             raise MrtError(st, "mrt_budget_allocate", "")
         return k, budget_result_dict(r)
 
+    def debug_budget_plan(self, s, n, budget: int, max_frames: int = 8) -> Tuple[np.ndarray, dict]:
+        """mrt_debug_budget_plan: the device's allocation (noise_query(budget=N)'s kernels) on the summed-S values `s` and the
+        frame counts `n` (an array of s's shape, or an int: that count for every tile), synchronously: (k in s's shape, result).
+        K is this context's table, so budget_allocate(s, n, the context's max_framebuffer_weight, ...) is the yardstick."""
+        s = np.ascontiguousarray(s, np.float32)
+        uniform = np.ndim(n) == 0
+        if not uniform:
+            n = np.ascontiguousarray(n, np.uint32)
+            if s.shape != n.shape:
+                raise ValueError("debug_budget_plan: s and n differ in shape")
+        k = np.zeros(s.shape, np.uint32)
+        r = _lib.MrtBudgetResult()
+        self._check(self._L.mrt_debug_budget_plan(self._ctx, s.ctypes.data, None if uniform else n.ctypes.data, int(n) if uniform else 0,
+                                                  s.size, budget, max_frames, k.ctypes.data, C.byref(r)), "mrt_debug_budget_plan")
+        return k, budget_result_dict(r)
+
     def tile_frames(self) -> np.ndarray:
         """Every tile's frame count n_t: (tile rows, tiles_x) uint32.  Waits for the frames in flight, as read_framebuffer does."""
         tx, tr = C.c_uint32(), C.c_uint32()

@@ -101,6 +101,15 @@ void noise_fill(mrt_noise_report* r, const mrt::NoiseSums& s, bool per_tile = fa
 
 bool noise_args_ok(float threshold, float floor_) { return std::isfinite(threshold) && std::isfinite(floor_) && floor_ >= 0.0f; }
 
+// what an allocation on the device (mrt_noise_query_budget, mrt_debug_budget_plan) refuses before anything is allocated or grown;
+// most: the largest n_t
+int plan_ask_refusal(mrt_ctx* c, const char* who, uint32_t max_frames, uint32_t most) {
+    if (max_frames < 1 || max_frames > mrt::kMaxFrameBatch)
+        return fail(c, MRT_ERR_INVALID_ARG, "%s: max_frames %u (1 .. %u)", who, max_frames, mrt::kMaxFrameBatch);
+    if (most > mrt::kBudgetMaxN) return fail(c, MRT_ERR_INVALID_ARG, "%s: a tile has more than %u frames", who, mrt::kBudgetMaxN);
+    return MRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,11 +153,8 @@ static int noise_query(mrt_ctx* c, float threshold, float floor_, uint32_t map_k
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query: threshold %g, floor %g (finite, floor >= 0)", threshold, floor_);
     const uint32_t most = c->tiles_diverged ? mrt::most_tile_frames(c) : c->frames_done;       // the largest n_t
     if (plan) {
-        if (plan->max_frames < 1 || plan->max_frames > mrt::kMaxFrameBatch)
-            return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: max_frames %u (1 .. %u)", plan->max_frames, mrt::kMaxFrameBatch);
+        MRT_TRY(plan_ask_refusal(c, "mrt_noise_query_budget", plan->max_frames, most));
         if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "mrt_noise_query_budget: a shard (world %u) has no budgets", c->shard_world);
-        if (most > mrt::kBudgetMaxN)
-            return fail(c, MRT_ERR_INVALID_ARG, "mrt_noise_query_budget: a tile has more than %u frames", mrt::kBudgetMaxN);
     }
     HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t seq = c->noise_seq + 1;
@@ -595,6 +601,49 @@ int mrt_debug_noise_reduce(mrt_ctx* c, const float* S, const float* rgba, uint32
     out->threshold = threshold; out->floor = floor_;
     out->noise_factor = K;
     noise_fill(out, h);
+    return MRT_OK;
+}
+
+int mrt_debug_budget_plan(mrt_ctx* c, const float* s, const uint32_t* n, uint32_t n_uniform, size_t tiles, uint64_t budget,
+                          uint32_t max_frames, uint32_t* k_out, mrt_budget_result* res) {
+    if (!c || !s || !k_out || !res || tiles == 0 || tiles > (1ull << 28)) return MRT_ERR_INVALID_ARG;
+    uint32_t most = n ? 0u : n_uniform;
+    for (size_t t = 0; n && t < tiles; t++) most = std::max(most, n[t]);
+    MRT_TRY(plan_ask_refusal(c, __func__, max_frames, most));
+    HIP_TRY(c, hipSetDevice(c->device));
+    MRT_TRY(mrt::ensure_k_table(c, most + max_frames + 2u));
+    // one entry's layout: the map (s), its plan, the selection's scratch
+    constexpr size_t head = sizeof(mrt_budget_result) / sizeof(uint32_t);
+    const mrt::BudgetLayout L = mrt::budget_layout(tiles, 1);
+    uint32_t *d_plan_words = nullptr, *d_plan_n = nullptr;
+    std::vector<uint32_t> h(head + tiles);
+    hipError_t e = hipSuccess;
+    const char* what = "mrt_debug_budget_plan";
+    HIP_CHAIN(e, what, hipMalloc((void**)&d_plan_words, L.words * sizeof(uint32_t)));
+    if (n) HIP_CHAIN(e, what, hipMalloc((void**)&d_plan_n, tiles * sizeof(uint32_t)));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_plan_words, s, tiles * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n) e = hipMemcpyAsync(d_plan_n, n, tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+    mrt::BudgetArgs a{};
+    if (e == hipSuccess) {
+        a.s = reinterpret_cast<const float*>(d_plan_words);
+        a.n = d_plan_n;
+        a.K = c->d_k_f64;
+        a.n_uniform = n_uniform; a.n_tiles = (uint32_t)tiles; a.max_frames = max_frames;
+        a.budget = budget;
+        a.hist = d_plan_words + L.hist;
+        a.sums = reinterpret_cast<double*>(d_plan_words + L.sums);
+        a.res = reinterpret_cast<mrt_budget_result*>(d_plan_words + L.plan);
+        a.k_out = d_plan_words + L.plan + head;
+        e = (hipError_t)mrt::launch_budget_plan(a, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_plan_words + L.plan, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+    int ws = MRT_OK;
+    if (e == hipSuccess) ws = mrt::wait_stream(c, c->stream, "mrt_debug_budget_plan");
+    if (ws != MRT_OK) return ws;            // (stalled: the buffers are left to the process)
+    mrt::free_device(d_plan_words, d_plan_n);
+    if (e != hipSuccess) return fail(c, MRT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    std::memcpy(res, h.data(), sizeof *res);
+    std::copy(h.begin() + head, h.end(), k_out);
     return MRT_OK;
 }
 

@@ -120,6 +120,44 @@ def plan(s, n, max_w: float, budget: int, max_frames: int, ordered: dict = None)
     return k.reshape(shape), res
 
 
+DIGITS = 13                                                 # of a key: G's eight bytes from the top, j, t's four bytes from the top
+
+
+def sort_keys(keys):
+    """(G, lo) of keys()'s candidates in ascending key order, lo = (j << 32) | t; a mandatory candidate's G is 0 and a gain's has
+    its top bit set, so the class needs no part of its own"""
+    _, G, j, t = keys
+    lo = (np.asarray(j, np.uint64) << np.uint64(32)) | np.asarray(t, np.uint64)
+    o = np.lexsort((lo, G))
+    return G[o], lo[o]
+
+
+def digits_of(G, lo) -> list:
+    """the thirteen 8-bit digits of the key (G, j, t), most significant first"""
+    G, lo = int(G), int(lo)
+    return list(G.to_bytes(8, "big")) + [lo >> 32] + list((lo & 0xFFFFFFFF).to_bytes(4, "big"))
+
+
+def replay(keys, budget: int) -> dict:
+    """What a selection of the `budget` smallest keys by 8-bit digits, most significant first, goes through -- said from the
+    sorted keys, not by selecting: {mode, T, q, bins}.
+        mode "none": budget 0 or no candidate; "all": no more candidates than the budget; "bin": T = the budget-th smallest key
+        T    that key as (G, (j << 32) | t), or None
+        q    the digit at which the selection ends: the first at which the next larger key differs from T -- from there on every
+             key that shares T's digits 0 .. q is taken, the bin is taken whole (keys are unique: q <= 12)
+        bins T's digits 0 .. q: the bin the selection descends into at each digit it looks at
+    keys: keys()'s tuple, or sort_keys()'s pair for several budgets of one map.  It only says what a case exercises: the expected
+    allocation is mrt_budget_allocate's."""
+    G, lo = keys if len(keys) == 2 else sort_keys(keys)
+    if budget == 0 or G.size == 0:
+        return {"mode": "none", "T": None, "q": None, "bins": []}
+    if budget >= G.size:
+        return {"mode": "all", "T": None, "q": None, "bins": []}
+    T, nxt = digits_of(G[budget - 1], lo[budget - 1]), digits_of(G[budget], lo[budget])
+    q = next(i for i in range(DIGITS) if T[i] != nxt[i])
+    return {"mode": "bin", "T": (int(G[budget - 1]), int(lo[budget - 1])), "q": q, "bins": T[:q + 1]}
+
+
 def target(n_q, k, n_now) -> np.ndarray:
     """k' = max(0, n_q + k - n_now): what is left of a plan whose tiles have had frames since its query"""
     k = np.asarray(k, np.int64)

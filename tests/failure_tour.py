@@ -267,6 +267,17 @@ class Tour:
             st = L.mrt_debug_noise_reduce(self.ctx[A], S.ctypes.data, rgba.ctypes.data, W, H, 0.25, 0.02, 0.01, C.byref(r), tiles_out.ctypes.data)
             return st, bytes(r) + tiles_out.tobytes()
 
+        plan_rng = np.random.default_rng(10)
+        plan_s = np.exp(plan_rng.uniform(-9.0, 9.0, 70)).astype(np.float32)
+        plan_n = plan_rng.integers(0, 41, 70).astype(np.uint32)         # (the K table's own sites are the per-tile query's, above)
+
+        @step(f"{A}: mrt_debug_budget_plan", A)
+        def _():
+            r = lib.MrtBudgetResult()
+            k = np.zeros(70, np.uint32)
+            st = L.mrt_debug_budget_plan(self.ctx[A], plan_s.ctypes.data, plan_n.ctypes.data, 0, 70, 200, 8, k.ctypes.data, C.byref(r))
+            return st, bytes(r) + k.tobytes()
+
         @step(f"{A}: mrt_debug_denoise", A)
         def _():
             out = np.zeros((H, W, 4), np.float32)

@@ -13,7 +13,7 @@ import budget_plan_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MRT_ERR_INVALID_ARG = 1
-NEW = ("mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned")
+NEW = ("mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned", "mrt_debug_budget_plan")
 TILES = (1, 6, 65, 260, 8192)
 S_KINDS = ("equal", "zero", "log-uniform", "negative", "nan", "inf")
 N_KINDS = (0, 1, 2, 17, "random", "below-2")
@@ -121,7 +121,7 @@ def test_the_blocked_sums_are_blocked():
 
 def test_the_new_entry_points_are_declared_bound_and_exported(mrt):
     from myraytracer_amd import _lib
-    header = open(os.path.join(ROOT, "include", "myraytracer_amd.h")).read()
+    header = open(os.path.join(ROOT, "include", "myraytracer_amd.h")).read() + open(os.path.join(ROOT, "include", "myraytracer_amd_debug.h")).read()
     for lib in ("libmyraytracer_amd.so", "libmyraytracer_amd_failinject.so"):
         names = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "myraytracer_amd", "lib", lib)],
                                capture_output=True, text=True, check=True).stdout
@@ -140,3 +140,52 @@ def test_a_null_context_is_refused(mrt):
     assert L.mrt_noise_query_budget(None, 0.02, 0.01, 10, 4) == MRT_ERR_INVALID_ARG
     assert L.mrt_read_budget_plan(None, 0, k.ctypes.data, k.size, C.byref(r)) == MRT_ERR_INVALID_ARG
     assert L.mrt_render_planned(None, 0, C.byref(r), k.ctypes.data, k.size) == MRT_ERR_INVALID_ARG
+    s = np.ones(4, np.float32)
+    assert L.mrt_debug_budget_plan(None, s.ctypes.data, None, 3, 4, 10, 4, k.ctypes.data, C.byref(r)) == MRT_ERR_INVALID_ARG
+
+
+def test_replay_says_where_a_selection_ends():
+    """hand-made keys: G in the top byte, the second byte and the last; then j; then each byte of t"""
+    def keys(rows):
+        G, j, t = (np.array(c, np.uint64) for c in zip(*rows))
+        return np.ones(len(rows), np.int64), G, j.astype(np.int64), t.astype(np.int64)
+    top = 0x80 << 56
+    rows = [(top, 0, 5), (top, 0, 0x0105), (top, 0, 0x010005), (top, 0, 0x01010005), (top, 1, 0), (top | 1, 0, 0), (top | (1 << 48), 0, 0),
+            (0x81 << 56, 0, 0)]
+    got = [ref.replay(keys(rows[::-1]), b) for b in range(10)]
+    assert got[0]["mode"] == "none" and got[8]["mode"] == got[9]["mode"] == "all" and ref.replay((np.zeros(0, np.uint64),) * 2, 3)["mode"] == "none"
+    assert [g["q"] for g in got[1:8]] == [11, 10, 9, 8, 7, 1, 0]
+    assert got[1]["T"] == (top, 5) and got[1]["bins"] == [0x80] + [0] * 11 and got[7]["bins"] == [0x80]
+    assert got[5]["T"] == (top, 1 << 32) and got[5]["bins"] == [0x80, 0, 0, 0, 0, 0, 0, 0]
+    two = ref.replay(keys([(top, 0, 0xFE), (top, 0, 0xFF), (top | 2, 3, 9)]), 1)
+    assert two["q"] == 12 and two["bins"][-1] == 0xFE
+
+
+def test_the_direct_cases_end_the_selection_at_every_digit():
+    """What tests/test_gpu_budget_select.py's cases exercise of the radix select, by replay alone: over their union the selection
+    ends at every digit of 0 .. 8 and 10 .. 12 (digit 9, t's top byte, would need 2^24 tiles: not covered), in all three modes;
+    the bin it descends into is 0 and is 255 somewhere, falls on every residue mod 4 (the four counts of a lane) and in the first
+    and the last lane's four; and every case built for a digit ends there."""
+    import budget_select_cases as bc
+    ends, modes, bins = set(), set(), set()
+    per_digit = {}
+    for case in bc.cases():
+        sk = ref.sort_keys(ref.keys(case["s"], case["n"], case["max_w"], case["max_frames"]))
+        for i, budget in enumerate(case["budgets"]):
+            r = ref.replay(sk, budget)
+            modes.add(r["mode"])
+            if r["mode"] != "bin":
+                continue
+            if i == 0 and case["ends"] is not None:
+                assert r["q"] == case["ends"], (case["name"], r)
+            ends.add(r["q"])
+            bins |= set(r["bins"])
+            per_digit.setdefault(r["q"], set()).add(r["bins"][-1] % 4)
+    assert ends == set(bc.DIGITS_COVERED) == {0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 11, 12}, sorted(ends)
+    assert modes == {"bin", "all", "none"}
+    assert {0, 255} <= bins and {b % 4 for b in bins} == {0, 1, 2, 3}
+    assert bins & {0, 1, 2, 3} and bins & {252, 253, 254, 255}          # the owner is lane 0, and lane 63
+    for q in range(1, 8):                                               # at G's mantissa digits the deciding bin itself is in every slot
+        assert per_digit[q] == {0, 1, 2, 3}, (q, per_digit[q])
+    tiles = {case["s"].size for case in bc.cases()}
+    assert set(bc.TILES) <= tiles and max(tiles) == (1 << 19) + 257

@@ -213,6 +213,35 @@ def test_the_target_rule(mrt):
         assert again["used_seq"] == seq and again["tile_frames"] == 0 and not again["k"].any() and st.frames_done == done
 
 
+@pytest.mark.parametrize("max_w", [1.0, 0.9])
+def test_the_query_grows_the_k_table_with_frames_in_flight(mrt, max_w):
+    """n_t of 4,060 .. 4,100 and max_frames 32: n + j + 1 passes the 4,096 entries the first query made, so the query replaces the
+    table -- behind its bounded wait, with two frames queued and not waited for.  The plan is the host's on the map the query left
+    and on the n it saw (the loaded counts + 2)."""
+    w, h = 24, 16
+    rng = np.random.default_rng(31)
+    loaded = rng.integers(4060, 4101, 6).astype(np.uint32)
+    with _state(mrt, w, h, max_w) as st:
+        st.render(3)
+        st.noise_query(0.3, 0.02, budget=5, max_frames=4)                          # the table's first 4,096 entries
+        st.debug_load_accumulation(np.ones((h, w, 4), np.float32), _s_pixels("random", h, w, rng), loaded)
+        st.render(2)                                                               # (no sync)
+        st.noise_query(0.3, 0.02, budget=70, max_frames=32)
+        seq = _raw_report(mrt, st).seq
+        assert seq == 2
+        got, s_map = st.budget_plan(seq), st.read_noise_tiles()
+        n_seen = (loaded + 2).reshape(s_map.shape)
+        assert np.array_equal(st.tile_frames(), n_seen)
+        k, want = mrt.State.budget_allocate(s_map, n_seen, max_w, 70, 32)
+        assert np.array_equal(got["k"], k), (got["k"], k)
+        for f in ("tile_frames", "tiles", "frames"):
+            assert got[f] == want[f], (f, got[f], want[f])
+        assert (want["tile_frames"] == 70) == (max_w == 1.0)                       # (at 0.9 K has stopped falling: no gains)
+        before, after = ref.blocked_sums(s_map, n_seen, k, max_w)
+        assert _f64(got["var_before"]) == _f64(before) and _f64(got["var_after"]) == _f64(after), (got, before, after)
+        assert st.debug_check_context() is None
+
+
 def test_mandatory_frames_come_first_and_alone(mrt):
     n = np.array([0, 1, 5, 0, 1, 5], np.uint32)
     with _state(mrt, 24, 16) as st:
@@ -235,7 +264,8 @@ def _refused(mrt, status, call, *args, **kw):
 
 def test_refusals_leave_everything_as_it_was(mrt):
     """mrt_noise_query_map's refusals, max_frames outside 1 .. 32, a shard; the readers' refusals.  (The refusal of an n_t above
-    2^24 cannot be reached here: mrt_debug_load_accumulation takes counts below 2^20 and no test renders 2^24 frames.)"""
+    2^24 cannot be reached here: mrt_debug_load_accumulation takes counts below 2^20 and no test renders 2^24 frames; the check is
+    shared with mrt_debug_budget_plan, where tests/test_gpu_budget_select.py reaches it.)"""
     with _state(mrt, 24, 16, tracking=False) as st:
         _refused(mrt, MRT_ERR_STATE, st.noise_query, budget=10, max_frames=4)
         _refused(mrt, MRT_ERR_STATE, st.budget_plan)
