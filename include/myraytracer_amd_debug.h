@@ -194,7 +194,7 @@ int mrt_debug_set_schedule(mrt_ctx* ctx, uint32_t pilot_spp, int waves_per_cu);
  * large scenes: at most 4, the occupancy their kernels are built for), entries of a wave's top queue (small scenes) / work
  * stack (large scenes)}.  tests/test_hierarchy_host.py pins the residency of C3's and C5's layouts with it. */
 int mrt_debug_lds_layout(uint32_t n_members, uint32_t n_nodes, uint32_t levels, uint32_t n_top_padded, uint32_t out[3]);
-/* Diagnostic / tuning: how many frames may be in flight (each on a side stream of its own; 1..8), 0 = automatic: 2, more for
+/* Diagnostic / tuning: how many frames may be in flight (each on a side stream of its own; 1..16), 0 = automatic: 2, more for
  * pixel-starved shards.  A change waits for the frames under way.  The images are the same. */
 int mrt_debug_set_frames_in_flight(mrt_ctx* ctx, int slots);
 /* Host only, no GPU needed: the launch-width controller's policy (csrc/width_policy.h) on synthetic input, for its CPU unit
@@ -203,7 +203,25 @@ int mrt_debug_set_frames_in_flight(mrt_ctx* ctx, int slots);
  * op 1: one measurement window has closed with lane utilisation `util` and `rate` frames / s; op 2: state[0] out = the share a
  * launch gets under setting state[0] when `util` (as an integer) earlier frames are still queued or running. */
 int mrt_debug_width_policy(int op, const uint32_t workload[6], uint32_t state[7], double util, double rate);
-/* Diagnostic: how many of `streams` (2..8) side streams of this context really run side by side in this process -- identical
+/* Host only, no GPU and no context needed: a FRESH launch-width controller (csrc/width_policy.h, WidthController -- the policy
+ * above plus its bookkeeping: workloads, hint, memo, the caller's frames in flight, measurement windows) run through n_calls
+ * synthetic frame calls, for its CPU unit tests.  Call i is frame i (one frame per call) and goes through the steps of a
+ * redraw in the library's order, with what the device would have answered given by the caller:
+ *   calls[13 i ..] = {workload: n_tiles, n_waves, max_slots, spp, n_members, counter-RNG?, n_spheres; hint div, mult ((0, 0) =
+ *     none; a change is mrt_set_schedule_hint); invalidate? (what mrt_set_camera and the other setters do before this call);
+ *     earlier frames found queued or running; device start-to-start intervals of the window's frames (0 = none); landed samples}
+ *   times[2 i ..] = {the host's clock at the call (s), the sum of those intervals (ms)}
+ *   samples: 3 per landed sample, in the calls' order: {frame, cumulative world_hit calls, cumulative lane slots}
+ *   out[9 i ..] = {div, mult, settled, frames in flight, frames running as the controller sees them, the share the frame is
+ *     launched on (1 / this), a window is open after the call?, a window closed at this call?, entries of the memo}
+ *   measured[2 i ..] = {lane utilisation, frames / s} of the window that closed at this call (else 0)
+ * max_slots is what the controller holds before any probe (the first call's counts; the library: 16); probe_slots is what
+ * the stream-concurrency probe reports when a setting first asks for more than two frames (0 = all 16). */
+#define MRT_WIDTH_CALL_WORDS 13u
+#define MRT_WIDTH_DECISION_WORDS 9u
+int mrt_debug_width_replay(uint32_t probe_slots, size_t n_calls, const uint32_t* calls, const double* times, const uint64_t* samples,
+                           size_t n_samples, uint32_t* out, double* measured);
+/* Diagnostic: how many of `streams` (2..16) side streams of this context really run side by side in this process -- identical
  * short clock-bounded kernels, one per stream, each stamping its start and end on the device's clock: *out = the most of them
  * resident at one instant (hardware queues are shared round-robin: HIP's default of 4 per process gives 4).  What caps the
  * frames in flight (mrt_get_schedule). */

@@ -37,7 +37,7 @@ EXPORTS = [
     "mrt_scene_stress", "mrt_scene_save", "mrt_scene_load", "mrt_write_pfm", "mrt_write_ppm",
     "mrt_srgb8", "mrt_write_png", "mrt_gather", "mrt_gather_rccl", "mrt_gathered_device_ptr", "mrt_read_gathered",
     "mrt_shard_global_row", "mrt_shard_local_rows", "mrt_unshard_rows", "mrt_debug_last_set_world_ms", "mrt_debug_world_hit", "mrt_debug_world_hit_stats", "mrt_debug_set_frame_batching", "mrt_debug_set_gather_per_band", "mrt_debug_arith", "mrt_debug_arith_pairs", "mrt_debug_set_boxes", "mrt_debug_build_boxes", "mrt_set_draw_counting", "mrt_debug_last_launch", "mrt_debug_set_frames_in_flight", "mrt_debug_lds_layout", "mrt_debug_build_boxes_top_down",
-    "mrt_set_wait_timeout", "mrt_get_schedule", "mrt_set_schedule_hint", "mrt_debug_width_policy", "mrt_debug_stream_concurrency", "mrt_debug_wave_log_frame",
+    "mrt_set_wait_timeout", "mrt_get_schedule", "mrt_set_schedule_hint", "mrt_debug_width_policy", "mrt_debug_width_replay", "mrt_debug_stream_concurrency", "mrt_debug_wave_log_frame",
     "mrt_present", "mrt_present_acquire", "mrt_present_release", "mrt_set_present_ring", "mrt_debug_srgb8_thresholds",
     "mrt_debug_present_encode", "mrt_debug_set_present_copy",
     "mrt_set_noise_tracking", "mrt_noise_query", "mrt_noise_result", "mrt_read_noise", "mrt_read_noise_tiles", "mrt_noise_factor",
@@ -377,6 +377,7 @@ def load():
         "mrt_get_schedule": (i32, [vp, P(u32)]),
         "mrt_set_schedule_hint": (i32, [vp, u32, u32]),
         "mrt_debug_width_policy": (i32, [i32, P(u32), P(u32), C.c_double, C.c_double]),
+        "mrt_debug_width_replay": (i32, [u32, sz, vp, vp, vp, sz, vp, vp]),
         "mrt_debug_stream_concurrency": (i32, [vp, u32, P(f32)]),
         "mrt_debug_wave_log_frame": (i32, [vp, u32, vp, sz, P(sz)]),
         "mrt_present": (i32, [vp, i32, u32]),

@@ -265,6 +265,41 @@ def width_policy(op: int, workload: Sequence[int], state: Sequence[int], util: f
     return [int(sv[i]) for i in range(6)] + [struct.unpack("<f", struct.pack("<I", sv[6]))[0]]
 
 
+WIDTH_DECISION_FIELDS = ("div", "mult", "settled", "frames_in_flight", "frames_running", "launch_div", "window_open", "window_closed",
+                         "memo_entries")
+
+
+def width_replay(workload: Sequence[int], calls: Sequence[dict], hint: Optional[Tuple[int, int]] = None, probe_slots: int = 0):
+    """mrt_debug_width_replay: a fresh launch-width controller (csrc/width_policy.h, WidthController) through synthetic frame
+    calls; host only.  workload = (n_tiles, n_waves, max_slots, spp, n_members, counter[, n_spheres]); hint = (div, mult) or
+    None; probe_slots = what the stream-concurrency probe would report (0: all 16).  Every call is a dict: now (seconds,
+    required), running (earlier frames found queued or running, default 0), intervals = (n, sum_ms) of device start-to-start
+    times or None, samples = [(frame, hits, slots), ...] that have landed, invalidate (a setter was called before this call),
+    and -- from this call on -- workload / hint where they change.  Returns one dict per call: WIDTH_DECISION_FIELDS, util, rate."""
+    L = _lib.load()
+    n = len(calls)
+    words = np.zeros((n, 13), np.uint32)
+    times = np.zeros((n, 2), np.float64)
+    samples = []
+    for i, call in enumerate(calls):
+        workload = call.get("workload", workload)
+        hint = call["hint"] if "hint" in call else hint
+        n_int, sum_ms = call.get("intervals") or (0, 0.0)
+        landed = call.get("samples", ())
+        w = tuple(workload) + (0,) * (7 - len(workload))
+        words[i] = [*w, *(hint or (0, 0)), int(bool(call.get("invalidate"))), call.get("running", 0), n_int, len(landed)]
+        times[i] = [call["now"], sum_ms]
+        samples += [tuple(s) for s in landed]
+    flat = np.ascontiguousarray(np.array(samples, np.uint64).reshape(-1, 3))
+    out = np.zeros((n, len(WIDTH_DECISION_FIELDS)), np.uint32)
+    measured = np.zeros((n, 2), np.float64)
+    rc = L.mrt_debug_width_replay(int(probe_slots), n, words.ctypes.data, times.ctypes.data, flat.ctypes.data if len(samples) else None,
+                                  len(samples), out.ctypes.data, measured.ctypes.data)
+    if rc:
+        raise MrtError(rc, "mrt_debug_width_replay")
+    return [dict(zip(WIDTH_DECISION_FIELDS, map(int, out[i])), util=float(measured[i, 0]), rate=float(measured[i, 1])) for i in range(n)]
+
+
 # ------------------------------------------------------------------ State
 
 class State:

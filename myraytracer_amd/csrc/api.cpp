@@ -209,7 +209,7 @@ int alloc_frame_buffers(mrt_ctx* c, uint32_t rank, uint32_t world) {
     }
     c->frame_slots = 2;
     c->last_slot = 0;               // (what mrt_debug_read_pixel_costs reads: a slot that has colour sums)
-    c->width.div = 0;
+    c->width.invalidate();
     c->inputs_dirty = true;
     c->n_waves = B.n_waves; c->cus = B.cus;
     c->target = 0;
@@ -569,7 +569,7 @@ int mrt_set_camera(mrt_ctx* c, const mrt_camera* cam) {
     c->cam_mask_gen++;
     c->guides_stale = true;
     for (auto& S : c->slot) S.cost_valid = false;
-    c->width.div = 0;                   // (the launch-width controller starts over with the new workload)
+    c->width.invalidate();              // (the launch-width controller starts over with the new workload)
     return MRT_OK;
 }
 
@@ -700,7 +700,7 @@ int mrt_set_rng_shuffle(mrt_ctx* c, const uint32_t s[4]) {
 int mrt_set_rng_mode(mrt_ctx* c, uint32_t mode) {
     if (!c || mode > MRT_RNG_COUNTER) return MRT_ERR_INVALID_ARG;
     c->locals.rng_mode = mode;
-    c->width.div = 0;
+    c->width.invalidate();
     return MRT_OK;
 }
 
@@ -713,7 +713,7 @@ int mrt_set_draw_counting(mrt_ctx* c, int enabled) {
 int mrt_set_samples_per_frame(mrt_ctx* c, uint32_t spp) {
     if (!c) return MRT_ERR_INVALID_ARG;
     c->locals.samples_per_frame = spp;
-    c->width.div = 0;
+    c->width.invalidate();
     return MRT_OK;
 }
 

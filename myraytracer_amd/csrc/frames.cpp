@@ -1,6 +1,7 @@
 // The frame loop: the launch-width controller and the frames in flight, putting a frame on a slot (mrt_redraw / mrt_render,
 // and adaptive sampling's subset frames: mrt_render_tiles), and the scheduling diagnostics.
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -63,18 +64,17 @@ static int probe_stream_concurrency(mrt_ctx* c, uint32_t k, float* out) {
 }
 
 // The most frames in flight this process can really run side by side: kMaxFrameSlots where the probe says so, else the largest
-// power of two it supports (>= 2), with ONE line of warning behind mrt_last_error(NULL).
-static int probe_max_slots(mrt_ctx* c) {
-    if (c->slots_probed) return MRT_OK;
+// power of two it supports (>= 2), with ONE line of warning behind mrt_last_error(NULL).  Asked once per context
+// (WidthController::wants_probe, after_probe).
+static int probe_max_slots(mrt_ctx* c, uint32_t* max_slots) {
     float conc = 0.0f;
     MRT_TRY(probe_stream_concurrency(c, mrt_ctx::kMaxFrameSlots, &conc));
-    c->slots_probed = true;
     // (all sixteen or eight: with 15 of 16 -- what GPU_MAX_HW_QUEUES=16 gives, the context's own stream holds a queue too -- two
     // of the sixteen frames take turns on one queue, and C5's 1/8 share renders 2,790 Msamples/s instead of 3,750, less than
     // with eight frames in flight)
     uint32_t cap = mrt_ctx::kMaxFrameSlots;
     while (cap > 2u && conc < (cap == 8u ? 7.0f : (float)cap)) cap /= 2u;
-    c->max_slots = cap;
+    *max_slots = cap;
     if (cap < mrt_ctx::kMaxFrameSlots) {
         char buf[256];
         std::snprintf(buf, sizeof buf, "myraytracer_amd: only %.0f of %u side streams run at a time in this process: at most %u frames in flight "
@@ -88,40 +88,22 @@ static int probe_max_slots(mrt_ctx* c) {
 
 static mrt::WidthWorkload width_workload(const mrt_ctx* c, bool counter) {
     mrt::WidthWorkload w;
-    w.n_tiles = c->n_tiles; w.n_waves = c->n_waves; w.max_slots = c->max_slots;
+    w.n_tiles = c->n_tiles; w.n_waves = c->n_waves; w.max_slots = c->width.max_slots;
     w.spp = c->locals.samples_per_frame; w.n_members = c->n_members; w.counter = counter ? 1u : 0u;
+    w.n_spheres = c->n_spheres;
     return w;
 }
 
-// a new setting: the frames of the old one drain first; samples and timings count again from the THIRD generation of frames at
-// the new one (the first starts on an empty chip -- a change waits for everything in flight -- and the second still inherits
-// its convoys: judged on those, C3 read 4 % faster at a quarter width, where it renders 2 % less)
-static void width_restart_measurement(mrt_ctx* c) {
-    c->width_timing = false;
-    c->width_valid_from = c->frame_seq + 2u * mrt::width_frames_in_flight(c->width.div, c->width.mult, c->max_slots);
-    c->stat_base.valid = c->stat_last.valid = false;
-}
-
-// The launch-width controller's bookkeeping for the frame about to be launched (adaptive launches only: one frame per launch,
-// no diagnostic override): the setting for a new workload, the back-pressure, the lane-utilisation samples that have landed,
-// the measurement windows and -- through width_policy.h -- the trials.  *want = frames in flight, *frames_running = earlier
-// frames whose render kernels are still queued or running.
+// The device's side of the launch-width controller for the frame about to be launched (adaptive launches only: one frame per
+// launch, no diagnostic override): what is still running, the back-pressure, the lane-utilisation samples that have landed, the
+// clocks and the probe.  Every rule -- the setting for a new workload, the measurement windows, the trials -- is the
+// controller's (c->width: width_policy.h).  *want = frames in flight, *frames_running = earlier frames whose render kernels
+// are still queued or running, as the controller sees them.
 static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* frames_running) {
     static const bool trace = std::getenv("MRT_TRACE_WIDTH") != nullptr;      // diagnostics: every decision, on stderr
-    mrt::WidthWorkload w = width_workload(c, counter);
-    if (c->width.div == 0) {
-        if (c->hint_div != 0) {                  // the caller's setting (mrt_set_schedule_hint)
-            c->width = mrt::WidthState();
-            c->width.div = c->hint_div; c->width.mult = c->hint_mult; c->width.settled = 1u;
-        } else {
-            mrt::width_policy_start(c->width, w);
-            // a setting this context has already settled at for the same workload returns without trials
-            for (const auto& m : c->width_memo)
-                if (m.n_tiles == w.n_tiles && m.spp == w.spp && m.large == (mrt::scene_is_small(w.n_members) ? 0u : 1u) && m.counter == w.counter &&
-                    m.n_spheres == c->n_spheres) { c->width.div = m.div; c->width.mult = m.mult; c->width.settled = 1u; }
-        }
-        width_restart_measurement(c);
-    }
+    mrt::WidthController& W = c->width;
+    const mrt::WidthWorkload w = width_workload(c, counter);
+    W.begin_workload(w, c->frame_seq);
     // The host may not run further ahead than the frames in flight: before a slot is used again, its previous frame's
     // render kernel has completed (a swap-chain's back-pressure; the GPU still holds a full set of frames, queued or
     // running).  It bounds the queued work and is what lets the samples below arrive while they can still matter -- a
@@ -150,100 +132,40 @@ static int schedule_frame(mrt_ctx* c, bool counter, uint32_t* want, uint32_t* fr
         if (T.render_pending && hipEventQuery(T.render_done) == hipSuccess) T.render_pending = false;
         if (!T.stats_pending || hipEventQuery(T.stats_ready) != hipSuccess) continue;
         T.stats_pending = false;
-        if (T.stats_seq < c->width_valid_from) continue;
-        mrt_ctx::LaneStat st{T.stats_seq, c->h_stats[3 * i], c->h_stats[3 * i + 2], true};
-        if (!c->stat_base.valid || st.seq < c->stat_base.seq) c->stat_base = st;
-        if (!c->stat_last.valid || st.seq > c->stat_last.seq) c->stat_last = st;
+        W.add_sample(T.stats_seq, c->h_stats[3 * i], c->h_stats[3 * i + 2]);
     }
     (void)hipGetLastError();        // (hipEventQuery's hipErrorNotReady is not an error)
-    // How many frames the CALLER keeps in flight: the most seen still queued or running over the last (frames in flight) calls
-    // -- not this call's count alone, which dips whenever a convoy of frames has just ended (launched a little wider, the next
-    // frame then holds more of the chip and the dips feed on themselves: C5's 1/8 share 3,066 -> 2,840 Msamples/s), and which is
-    // 0, 1, 2, ... while a burst of calls fills an empty pipeline.  A new setting starts from "the caller keeps them all in
-    // flight".
-    {
-        const uint32_t window = mrt::width_frames_in_flight(c->width.div, c->width.mult, c->max_slots);
-        if (c->running_seen_n != window) {          // (a new setting, or the first call)
-            c->running_seen_n = window;
-            for (uint32_t i = 0; i < window; i++) c->running_seen[i] = window - 1u;
+    *frames_running = W.note_running(c->frame_seq, running);
+    const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    W.open_window(c->frame_seq, now);
+    if (W.window_due(c->frame_seq, now)) {
+        // start-to-start times of the window's frames, whole frames on the DEVICE's clock: the start events of frame f and of
+        // frame f + slots, the next on the same slot (what the controller prefers to the host's count: close_window)
+        const uint32_t slots = c->frame_slots;
+        double sum_ms = 0.0;
+        uint32_t n = 0;
+        for (uint64_t f = W.t0_seq; f + slots < c->frame_seq; f++) {
+            if (c->frame_seq - f > mrt_ctx::kEventRing) continue;               // (overwritten since)
+            hipEvent_t a = c->ev_start[f % mrt_ctx::kEventRing], b = c->ev_start[(f + slots) % mrt_ctx::kEventRing];
+            if (hipEventQuery(b) != hipSuccess) break;                          // (not started yet, nor are the later ones)
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, a, b) == hipSuccess && ms > 0.0f) { sum_ms += ms; n++; }
         }
-        c->running_seen[c->frame_seq % window] = running;
-        // ... except that NOTHING running at three calls in a row is a caller that waits for every frame (a pipeline that is
-        // kept full never shows that): known at once, not after a window of up to sixteen slow frames
-        c->nothing_running_calls = running == 0u ? c->nothing_running_calls + 1u : 0u;
-        if (c->nothing_running_calls >= 3u)
-            for (uint32_t i = 0; i < window; i++) c->running_seen[i] = 0u;
-        uint32_t most = 0;
-        for (uint32_t i = 0; i < window; i++) most = std::max(most, c->running_seen[i]);
-        *frames_running = most;
-    }
-    // A measurement window: from the first frame launched at the current setting with the pipeline full, over
-    // 2 x (frames in flight) + 2 frames -- their lane utilisation (the samples above) and, the calls being paced by
-    // the completions (the back-pressure above), their rate on the host's clock -- and over at least 20 ms: frames of a
-    // fifth of a millisecond (C1, 1 spp) filled a window in 2-3 ms of host time, whose jitter decided 1 trial in 9 the wrong way.
-    const uint32_t in_flight = std::max(2u, c->width.div) * c->width.mult;
-    const auto now = std::chrono::steady_clock::now();
-    if (!c->width.settled && !c->width_timing && c->frame_seq >= c->width_valid_from) {
-        c->width_timing = true;
-        c->width_t0_seq = c->frame_seq;
-        c->width_t0 = now;
-    }
-    if (c->width_timing && c->frame_seq >= c->width_t0_seq + 2u * in_flight + 2u &&
-        std::chrono::duration<double>(now - c->width_t0).count() >= 0.020 && c->stat_base.valid && c->stat_last.valid &&
-        c->stat_last.seq > c->stat_base.seq && c->stat_last.slots > c->stat_base.slots && c->stat_last.hits >= c->stat_base.hits) {
-        mrt::WidthWindow m;
-        m.util = (double)(c->stat_last.hits - c->stat_base.hits) / (double)(c->stat_last.slots - c->stat_base.slots);
-        m.rate = (double)(c->frame_seq - c->width_t0_seq) / std::max(1e-9, std::chrono::duration<double>(now - c->width_t0).count());
-        // The frame rate, better: frames END in convoys (the launches that share the chip start together), so a count of the calls
-        // the completions let through over a window of a few convoys is off by up to a convoy -- 4 frames in 18, far beyond the
-        // 3 % a trial is judged by (the first cut of this round kept a quarter width for C3 that renders 8 % less).  Every frame
-        // slot is refilled the moment its frame ends (the back-pressure), so slots / (a slot's start-to-start time) is the rate
-        // (Little's law), and start-to-start times are whole frames on the DEVICE's clock: the start events of frame f and of
-        // frame f + slots, the next on the same slot, over the window's frames.
-        {
-            const uint32_t slots = c->frame_slots;
-            double sum_ms = 0.0;
-            uint32_t n = 0;
-            for (uint64_t f = c->width_t0_seq; f + slots < c->frame_seq; f++) {
-                if (c->frame_seq - f > mrt_ctx::kEventRing) continue;               // (overwritten since)
-                hipEvent_t a = c->ev_start[f % mrt_ctx::kEventRing], b = c->ev_start[(f + slots) % mrt_ctx::kEventRing];
-                if (hipEventQuery(b) != hipSuccess) break;                          // (not started yet, nor are the later ones)
-                float ms = 0.0f;
-                if (hipEventElapsedTime(&ms, a, b) == hipSuccess && ms > 0.0f) { sum_ms += ms; n++; }
-            }
-            (void)hipGetLastError();
-            if (n >= std::max(2u, slots / 2u)) m.rate = (double)slots * 1e3 * (double)n / sum_ms;     // (else: the host's count above)
-        }
+        (void)hipGetLastError();
+        const mrt::WidthState tried = W.s;
+        const mrt::WidthWindow m = W.close_window(w, c->frame_seq, now, slots, n, sum_ms);
         if (trace) std::fprintf(stderr, "mrt width: frame %llu: div %u x %u, window %llu frames, utilisation %.4f, %.2f frames/s%s\n",
-                                (unsigned long long)c->frame_seq, c->width.div, c->width.mult, (unsigned long long)(c->frame_seq - c->width_t0_seq),
-                                m.util, m.rate, c->width.prev_div != 0 ? " (trial)" : "");
-        mrt::width_policy_step(c->width, w, m);
-        if (c->width.settled) {
-            if (trace) std::fprintf(stderr, "mrt width: settled at div %u x %u\n", c->width.div, c->width.mult);
-            const mrt_ctx::WidthMemo memo{w.n_tiles, w.spp, mrt::scene_is_small(w.n_members) ? 0u : 1u, w.counter, c->n_spheres, c->width.div, c->width.mult};
-            bool known = false;
-            for (auto& m : c->width_memo)
-                if (m.n_tiles == memo.n_tiles && m.spp == memo.spp && m.large == memo.large && m.counter == memo.counter && m.n_spheres == memo.n_spheres) {
-                    m = memo;
-                    known = true;
-                }
-            if (!known) c->width_memo.push_back(memo);
-        }
-        width_restart_measurement(c);
+                                (unsigned long long)c->frame_seq, tried.div, tried.mult, (unsigned long long)(c->frame_seq - W.t0_seq),
+                                m.util, m.rate, tried.prev_div != 0 ? " (trial)" : "");
+        if (trace && W.s.settled) std::fprintf(stderr, "mrt width: settled at div %u x %u\n", W.s.div, W.s.mult);
     }
     // more than two frames in flight only where they really run side by side (measured once, when a setting first asks for them)
-    if (mrt::width_frames_in_flight(c->width.div, c->width.mult, mrt_ctx::kMaxFrameSlots) > 2u && !c->slots_probed) {
-        MRT_TRY(probe_max_slots(c));
-        // (a pinned setting keeps its width and is held to the frames that run side by side all the same: sixteen frames on
-        // fewer queues take turns -- C5's 1/8 share 2,790 Msamples/s, less than eight in flight give)
-        if (c->max_slots < mrt_ctx::kMaxFrameSlots && c->hint_div == 0) {       // start over within what the process can do
-            w.max_slots = c->max_slots;
-            mrt::width_policy_start(c->width, w);
-            width_restart_measurement(c);
-        }
-        c->running_seen_n = 0;
+    if (W.wants_probe()) {
+        uint32_t max_slots = 0;
+        MRT_TRY(probe_max_slots(c, &max_slots));
+        W.after_probe(max_slots, w, c->frame_seq);
     }
-    *want = mrt::width_frames_in_flight(c->width.div, c->width.mult, c->max_slots);
+    *want = W.frames_in_flight();
     return MRT_OK;
 }
 
@@ -507,9 +429,7 @@ static int redraw_frames(mrt_ctx* c, uint32_t batch, bool frames_in_lane = false
         // ... and never a smaller share than the frames that really share the chip leave (width_policy.h, width_launch_div): a
         // caller that waits for every frame gets all of it
         const uint32_t whole = std::min(c->n_waves, mrt::render_resident_waves(p));
-        c->last_launch_div = mrt::width_launch_div(c->width.div, frames_running);
-        c->last_frames_running = frames_running;
-        launch_waves = std::max(whole / c->last_launch_div, 1u);
+        launch_waves = std::max(whole / c->width.launch_div(frames_running), 1u);
     }
     bool piloted = false;
     if (c->lpt_enabled && c->n_tiles > launch_waves && chain_spp >= 4u) {
@@ -663,9 +583,9 @@ static int render_subset(mrt_ctx* c, const uint32_t* tiles, uint32_t n, uint32_t
     // launch width: the setting in force (the controller's last launch), and round 3's 8 waves per CU for chains of a few bounces
     const uint32_t chain_spp = c->locals.samples_per_frame * batch;
     uint32_t launch_waves = few_bounce_launch_waves(c, chain_spp);
-    if (c->width.div != 0 && c->waves_per_cu_override == 0 && c->frame_slots_override == 0) {
+    if (c->width.s.div != 0 && c->waves_per_cu_override == 0 && c->frame_slots_override == 0) {
         const uint32_t whole = std::min(c->n_waves, mrt::render_resident_waves(p));
-        launch_waves = std::max(whole / std::max(c->last_launch_div, 1u), 1u);
+        launch_waves = std::max(whole / std::max(c->width.last_launch_div, 1u), 1u);
     }
     p.tile_order = S.d_tile_list;                // (a subset launch always passes its list: null would mean tiles 0 .. n - 1)
     if (c->lpt_enabled && S.cost_valid && n > launch_waves && chain_spp >= 4u) {
@@ -833,23 +753,19 @@ int mrt_debug_set_schedule(mrt_ctx* c, uint32_t pilot_spp, int waves_per_cu) {
 
 int mrt_get_schedule(mrt_ctx* c, uint32_t out[6]) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
-    out[0] = c->width.div; out[1] = c->width.mult; out[2] = c->width.settled;
-    out[3] = c->width.div ? mrt::width_frames_in_flight(c->width.div, c->width.mult, c->max_slots) : c->frame_slots;
-    out[4] = c->last_launch_div;
-    out[5] = c->slots_probed ? c->max_slots : 0u;        // 0 = not measured yet (no setting has asked for more than two frames)
+    const mrt::WidthController& W = c->width;
+    out[0] = W.s.div; out[1] = W.s.mult; out[2] = W.s.settled;
+    out[3] = W.s.div ? W.frames_in_flight() : c->frame_slots;
+    out[4] = W.last_launch_div;
+    out[5] = W.slots_probed ? W.max_slots : 0u;      // 0 = not measured yet (no setting has asked for more than two frames)
     return MRT_OK;
 }
 
 int mrt_set_schedule_hint(mrt_ctx* c, uint32_t div, uint32_t mult) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    if (div == 0 && mult == 0) {
-        c->hint_div = c->hint_mult = 0;
-    } else {
-        if (div < 1 || div > mrt::kMaxWidthDiv || mult < 1 || mult > 8 || std::max(2u, div) * mult > mrt_ctx::kMaxFrameSlots)
-            return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_schedule_hint: div %u x mult %u (div 1..8, mult 1..8, max(2, div) x mult <= 16)", div, mult);
-        c->hint_div = div; c->hint_mult = mult;
-    }
-    c->width.div = 0;                   // the next redraw takes the hint (or starts measuring again)
+    if (!(div == 0 && mult == 0) && !mrt::width_hint_valid(div, mult))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_set_schedule_hint: div %u x mult %u (div 1..8, mult 1..8, max(2, div) x mult <= 16)", div, mult);
+    c->width.set_hint(div, mult);       // the next redraw takes the hint (or starts measuring again)
     return MRT_OK;
 }
 
@@ -867,6 +783,43 @@ int mrt_debug_width_policy(int op, const uint32_t workload[6], uint32_t state[7]
     pr = (float)s.prev_rate;
     state[0] = s.div; state[1] = s.mult; state[2] = s.prev_div; state[3] = s.prev_mult; state[4] = s.low_windows; state[5] = s.settled;
     std::memcpy(&state[6], &pr, 4);
+    return MRT_OK;
+}
+
+// a fresh controller through the caller's synthetic frame calls: schedule_frame's sequence with the device's answers given
+int mrt_debug_width_replay(uint32_t probe_slots, size_t n_calls, const uint32_t* calls, const double* times, const uint64_t* samples,
+                           size_t n_samples, uint32_t* out, double* measured) {
+    if (!calls || !times || !out || !measured || (n_samples && !samples) || probe_slots == 1 || probe_slots > mrt::kMaxFrameSlots) return MRT_ERR_INVALID_ARG;
+    mrt::WidthController W;
+    uint32_t frame_slots = 2;           // (redraw_frames: set_frame_slots(want) after every call)
+    size_t next_sample = 0;
+    for (size_t i = 0; i < n_calls; i++) {
+        const uint32_t* in = calls + MRT_WIDTH_CALL_WORDS * i;
+        mrt::WidthWorkload w;
+        w.n_tiles = in[0]; w.n_waves = in[1]; w.max_slots = in[2]; w.spp = in[3]; w.n_members = in[4]; w.counter = in[5]; w.n_spheres = in[6];
+        const uint32_t hint_div = in[7], hint_mult = in[8], running = in[10], n = in[11];
+        if (w.n_tiles == 0 || w.n_waves == 0 || w.max_slots < 1 || w.max_slots > mrt::kMaxFrameSlots || in[12] > n_samples - next_sample ||
+            (!(hint_div == 0 && hint_mult == 0) && !mrt::width_hint_valid(hint_div, hint_mult)))
+            return MRT_ERR_INVALID_ARG;
+        if (i == 0) W.max_slots = w.max_slots;
+        if (hint_div != W.hint_div || hint_mult != W.hint_mult) W.set_hint(hint_div, hint_mult);
+        if (in[9]) W.invalidate();
+        const uint64_t frame_seq = i;
+        const double now = times[2 * i];
+        W.begin_workload(w, frame_seq);
+        for (uint32_t k = 0; k < in[12]; k++, next_sample++) W.add_sample(samples[3 * next_sample], samples[3 * next_sample + 1], samples[3 * next_sample + 2]);
+        const uint32_t frames_running = W.note_running(frame_seq, running);
+        W.open_window(frame_seq, now);
+        mrt::WidthWindow m{0.0, 0.0};
+        const bool due = W.window_due(frame_seq, now);
+        if (due) m = W.close_window(w, frame_seq, now, frame_slots, n, times[2 * i + 1]);
+        if (W.wants_probe()) W.after_probe(probe_slots ? probe_slots : mrt::kMaxFrameSlots, w, frame_seq);
+        frame_slots = W.frames_in_flight();
+        uint32_t* o = out + MRT_WIDTH_DECISION_WORDS * i;
+        o[0] = W.s.div; o[1] = W.s.mult; o[2] = W.s.settled; o[3] = frame_slots; o[4] = frames_running; o[5] = W.launch_div(frames_running);
+        o[6] = W.timing ? 1u : 0u; o[7] = due ? 1u : 0u; o[8] = (uint32_t)W.memo.size();
+        measured[2 * i] = m.util; measured[2 * i + 1] = m.rate;
+    }
     return MRT_OK;
 }
 

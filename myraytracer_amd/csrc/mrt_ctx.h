@@ -4,7 +4,6 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
-#include <chrono>
 #include <string>
 #include <vector>
 
@@ -113,7 +112,7 @@ struct mrt_ctx {
     // C5) is different: its launch is as long as its heaviest pixel's chain while most of its waves end much earlier, and a
     // wave instruction costs the same with 40 % of its lanes active as with all -- so it runs more frames at once, each on
     // fewer, better packed waves (redraw_frames; round 4).  frame_slots is the count in use, slot[] the capacity.
-    static constexpr uint32_t kMaxFrameSlots = 16;
+    static constexpr uint32_t kMaxFrameSlots = mrt::kMaxFrameSlots;
     uint32_t frame_slots = 2;
     uint32_t last_slot = 0;                         // the slot of the most recent redraw
     int frame_slots_override = 0;                   // mrt_debug_set_frames_in_flight: 0 = automatic
@@ -151,30 +150,17 @@ struct mrt_ctx {
         uint32_t order_kind = 0, order_n = 0;
         bool order_pilot = false;
     } slot[kMaxFrameSlots];
-    // Launch width (redraw_frames; the policy itself: width_policy.h): a frame is launched on 1 / width.div of the persistent
-    // waves the chip holds and max(2, width.div) x width.mult frames are in flight, so that the chip stays full.  Narrow launches
+    // Launch width (redraw_frames; the policy and the controller: width_policy.h): a frame is launched on 1 / width.s.div of the
+    // persistent waves the chip holds and max(2, width.s.div) x width.s.mult frames are in flight, so that the chip stays full.  Narrow launches
     // pack the lanes better (more pixels per lane in sequence: the launch's tail, in which lanes idle until their wave's longest
     // pixel ends, is the same length but a smaller share) at the price of a longer frame latency -- and they do not always pay
     // (C3 / C4, 0.98 / 0.99 lane utilisation at full width, lose 1-4 % at a half; C2 loses 4 % at a half and gains 18 % at a
     // quarter).  So the setting is MEASURED: trials while the utilisation is low, kept only if the frame rate rises by 3 %.
     // Scheduling only: the images do not change.
-    mrt::WidthState width;                          // div 0 = not chosen yet for the current workload
-    uint32_t hint_div = 0, hint_mult = 0;           // mrt_set_schedule_hint: the caller's setting (0 = the controller decides)
-    uint32_t max_slots = kMaxFrameSlots;            // frames that can really run side by side (probe_stream_concurrency)
-    bool slots_probed = false;
+    // All of the controller's state, the memo of settled settings included (which does NOT let a viewer that moves its camera
+    // every frame reach a setting: see the comment above WidthController::Memo, and ADVICE.md).
+    mrt::WidthController width;
     unsigned long long dbg_world_hit_stats[2] = {0, 0};     // mrt_debug_world_hit_stats
-    uint32_t last_launch_div = 1, last_frames_running = 0;   // mrt_get_schedule: what the most recent launch was issued with
-    uint32_t running_seen[kMaxFrameSlots] = {}, running_seen_n = 0;    // frames seen queued or running at the last calls (schedule_frame)
-    uint32_t nothing_running_calls = 0;             // consecutive calls that found no earlier frame queued or running
-    // settled settings by workload, so that a change of camera / samples per frame / scene and back does not start the trials
-    // over (and a viewer that moves its camera every frame still reaches one)
-    struct WidthMemo { uint32_t n_tiles, spp, large, counter, n_spheres, div, mult; };
-    std::vector<WidthMemo> width_memo;
-    uint64_t width_valid_from = 0;                  // frame_seq from which samples and timings belong to the current setting
-    bool width_timing = false;                      // a measurement window is open: since frame width_t0_seq, at width_t0
-    uint64_t width_t0_seq = 0;
-    std::chrono::steady_clock::time_point width_t0;
-    struct LaneStat { uint64_t seq = 0, hits = 0, slots = 0; bool valid = false; } stat_base, stat_last;
     unsigned long long* h_stats = nullptr;          // pinned, 3 x kMaxFrameSlots (+ 2 x kMaxFrameSlots: the concurrency probe's stamps)
     uint32_t hold_polls = 0;                        // mrt_debug_hold: the polls its most recent kernel was given (its stamps: the probe's last pair)
     hipEvent_t ev_inputs = nullptr;            // scene / seeds uploads on the caller's stream

@@ -51,7 +51,7 @@ int present_discard_queued(mrt_ctx* c, const char* who) {
 // the depth the next present uses: pinned, or the frames in flight + 2 (never less than before); held to the pinned-memory budget
 uint32_t present_depth_for(const mrt_ctx* c) {
     uint32_t fif = c->frame_slots;
-    if (c->width.div) fif = std::max(fif, mrt::width_frames_in_flight(c->width.div, c->width.mult, c->max_slots));
+    if (c->width.s.div) fif = std::max(fif, c->width.frames_in_flight());
     uint32_t want = c->present_depth_pin ? c->present_depth_pin : std::max(c->present_depth, fif + 2u);
     const size_t cap = std::max<size_t>(2, kPresentPinnedBudget / std::max<size_t>(c->present_entry_bytes, 1));
     return (uint32_t)std::min<size_t>({(size_t)want, cap, (size_t)kPresentMaxDepth});

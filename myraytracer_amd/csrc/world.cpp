@@ -1,6 +1,7 @@
 // The scene: mrt_set_world_raw / mrt_set_world (validation, the hierarchy of hierarchy.cpp, the uploads), the scene's part of
 // the kernel arguments, and the scene-related diagnostics.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -358,7 +359,7 @@ int mrt_set_world_raw(mrt_ctx* c, const void* world, size_t world_bytes, const f
     MRT_TRY(upload((void**)&c->d_f32, f32, n_f32 * sizeof(float)));
     MRT_TRY(upload((void**)&c->d_i32, i32, n_i32 * sizeof(int32_t)));
     for (auto& S : c->slot) S.cost_valid = false;
-    c->width.div = 0;                   // (the launch-width controller starts over with the new workload)
+    c->width.invalidate();              // (the launch-width controller starts over with the new workload)
     c->inputs_dirty = true;
     c->world = *w;
     c->n_spheres = (uint32_t)n;
