@@ -51,7 +51,8 @@ extern "C" {
  * material edits without a rebuild (mrt_material, mrt_update_materials, MRT_MATERIALS_RESTART_HISTORY); adaptive sampling by
  * budget (MRT_TILE_MAP_MAX_REL, MRT_TILE_MAP_SUM_S, mrt_noise_query_map, mrt_budget_result, mrt_budget_allocate,
  * mrt_render_budget; mrt_noise_report::reserved carries the report's map kind); budget allocation on the device
- * (mrt_noise_query_budget, mrt_read_budget_plan, mrt_render_planned). */
+ * (mrt_noise_query_budget, mrt_read_budget_plan, mrt_render_planned); the present pass's linear formats
+ * (MRT_PRESENT_RGBA16F_LINEAR, MRT_PRESENT_RGBA32F_LINEAR, mrt_half_bits, mrt_half_from_floats). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -437,8 +438,23 @@ int mrt_set_draw_counting(mrt_ctx* ctx, int enabled);
  * and an event: automatic depth = the frames in flight + 2 (grown at present time, never shrunk), all entries' pinned bytes
  * held to 256 MB (18 entries of 1920x1080, 7 of 3840x2160).  When every entry but the one the caller holds has a copy still
  * in flight, mrt_present waits for the oldest on the host (bounded, mrt_set_wait_timeout): a ring capped by the budget or by
- * mrt_set_present_ring thus narrows the frames in flight. */
+ * mrt_set_present_ring thus narrows the frames in flight.
+ *
+ * The linear formats hand out the floats themselves through the same ring, for a caller that needs linear values of every frame
+ * without draining the frames in flight (its own tone curve, exact snapshots of a long accumulation, an Rgba16Float surface):
+ * no OETF, no clamp, alpha like colour, every source flag and every refusal as for the 8-bit formats.  RGBA32F_LINEAR is a bit
+ * copy of the source's texels (a NaN keeps its payload), 16 bytes per pixel, what the mrt_read_* call of the same source
+ * returns.  RGBA16F_LINEAR stores mrt_half_bits (image output, below) of every channel, 8 bytes per pixel.  An entry holds
+ * rows x width x bytes-per-pixel bytes.  A present whose image is larger than the ring's entries -- a larger source, or the
+ * first present of a wider format -- regrows them: the images queued but not acquired are discarded and counted in `dropped`,
+ * the call is MRT_ERR_STATE while the caller holds an image (mrt_present_release first), and entries are never shrunk, so they
+ * fit the largest format presented so far.  The 256 MB budget holds the depth to max(2, budget / entry bytes): 7 entries of
+ * 1920x1080 RGBA32F, 15 of 1920x1080 RGBA16F, 2 of 3840x2160 RGBA32F -- fewer than the frames in flight + 2 a wide launch
+ * schedule asks for, so such a ring narrows the frames in flight, as above. */
 enum { MRT_PRESENT_RGBA8_SRGB = 1, MRT_PRESENT_BGRA8_SRGB = 2 };   /* Rgba8UnormSrgb / Bgra8UnormSrgb surfaces */
+/* the linear formats (values of the same `format` argument; 3 stays invalid) */
+#define MRT_PRESENT_RGBA16F_LINEAR 16   /* four IEEE binary16 per pixel, r g b a, 8 bytes (an Rgba16Float surface) */
+#define MRT_PRESENT_RGBA32F_LINEAR 32   /* four float32 per pixel, r g b a, 16 bytes: the source's bits */
 enum {
     MRT_PRESENT_FLIP_Y = 1,    /* rows top-down, as on the surface (sample_framebuffer.wgsl:24) and in mrt_write_ppm */
     MRT_PRESENT_GATHERED = 2   /* the root's full frame from the latest mrt_gather / mrt_gather_rccl, not this ctx's framebuffer */
@@ -453,13 +469,14 @@ enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
 typedef struct {               /* 40 bytes */
     uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
     uint32_t frames_done;      /* mrt_frames_done at the present: the accumulation the image shows */
-    uint32_t width, rows, row_bytes;   /* rows of width pixels, row_bytes = 4 width apart */
+    uint32_t width, rows, row_bytes;   /* rows of width pixels, row_bytes = 4, 8 (RGBA16F) or 16 (RGBA32F) x width apart */
     uint32_t format, flags;    /* as passed to mrt_present */
     uint32_t dropped;          /* images finished but never acquired since the previous acquire (skipped or overwritten) */
     uint32_t ring_depth;       /* the ring's current depth */
 } mrt_present_info;
 /* Queues the present of the most recent frame (after mrt_render(k): its last frame) on the ctx's stream, behind that frame's
- * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB; flags: MRT_PRESENT_FLIP_Y |
+ * blend, and returns at once unless the ring is full (above).  format: MRT_PRESENT_*_SRGB or MRT_PRESENT_*_LINEAR (any
+ * other value: MRT_ERR_INVALID_ARG); flags: MRT_PRESENT_FLIP_Y |
  * MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL | MRT_PRESENT_GATHERED_DENOISED.  Source rows: world == 1, the `height` image rows; a shard (world > 1), its packed
  * local rows in mrt_read_framebuffer's order (FLIP_Y refused: MRT_ERR_INVALID_ARG); GATHERED, the `height` rows of the root's full
  * frame (MRT_ERR_STATE before the first gather); DENOISED, the `height` rows of the denoised frame, queued on the same stream
@@ -477,7 +494,8 @@ int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
  * (bounded) for one that is queued (*pixels = NULL only if none is; NEWEST with an older image
  * finished returns that one at once, it does not wait for a newer one in flight).  MRT_ERR_STATE before the context's first present
  * (numbering and this rule span mrt_reset: after a reset the call is MRT_OK with *pixels = NULL).  info may be
- * NULL.  Releases the image held before. */
+ * NULL.  Releases the image held before.  The bytes are info->format's: the caller reinterprets *pixels as uint16_t
+ * (RGBA16F_LINEAR) or float (RGBA32F_LINEAR) texels; the pinned buffer is aligned for either. */
 int mrt_present_acquire(mrt_ctx* ctx, int mode, int wait, const uint8_t** pixels, mrt_present_info* info);
 int mrt_present_release(mrt_ctx* ctx);            /* MRT_ERR_STATE if no image is held */
 /* Pins the ring's depth (2..18, held to the 256 MB budget); 0 = automatic.  Waits (bounded) for the copies in flight and
@@ -1075,6 +1093,12 @@ int mrt_write_pfm(const char* path, const float* rgba, uint32_t width, uint32_t 
 int mrt_write_ppm(const char* path, const float* rgba, uint32_t width, uint32_t height);
 int mrt_write_png(const char* path, const float* rgba, uint32_t width, uint32_t height);   /* 8-bit RGB, same encoding as the PPM, + sRGB chunk */
 uint8_t mrt_srgb8(float linear);      /* the per-channel conversion mrt_write_ppm / mrt_write_png apply */
+/* float32 -> the bits of an IEEE binary16, the per-channel conversion of MRT_PRESENT_RGBA16F_LINEAR (the device computes the
+ * same bits for every float): round to nearest, ties to even; subnormal halves are produced; a magnitude at or above 65520
+ * gives +-inf, one at or below 2^-25 gives +-0 (the tie at 2^-25 included); zero and infinity keep their sign; every NaN gives
+ * 0x7E00, whatever its sign or payload.  mrt_half_from_floats converts n floats (MRT_ERR_INVALID_ARG: a null pointer with n > 0). */
+uint16_t mrt_half_bits(float v);
+int mrt_half_from_floats(const float* in, size_t n, uint16_t* out);
 
 #ifdef __cplusplus
 }

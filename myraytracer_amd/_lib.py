@@ -35,7 +35,7 @@ EXPORTS = [
     "mrt_kernel_ms_history", "mrt_debug_read_counters", "mrt_debug_wave_log", "mrt_debug_set_tile_sort", "mrt_debug_set_cluster_factor", "mrt_debug_set_hierarchy", "mrt_debug_set_sweep", "mrt_debug_sweep_variant", "mrt_debug_build_hierarchy", "mrt_debug_read_pixel_costs", "mrt_debug_set_schedule", "mrt_debug_mfma_scale", "mrt_debug_build_sweep", "mrt_debug_set_sweep_axes", "mrt_debug_sweep_axes",
     "mrt_last_error", "mrt_status_string", "mrt_abi_version", "mrt_build_id", "mrt_scene_default", "mrt_scene_cover",
     "mrt_scene_stress", "mrt_scene_save", "mrt_scene_load", "mrt_write_pfm", "mrt_write_ppm",
-    "mrt_srgb8", "mrt_write_png", "mrt_gather", "mrt_gather_rccl", "mrt_gathered_device_ptr", "mrt_read_gathered",
+    "mrt_srgb8", "mrt_half_bits", "mrt_half_from_floats", "mrt_write_png", "mrt_gather", "mrt_gather_rccl", "mrt_gathered_device_ptr", "mrt_read_gathered",
     "mrt_shard_global_row", "mrt_shard_local_rows", "mrt_unshard_rows", "mrt_debug_last_set_world_ms", "mrt_debug_world_hit", "mrt_debug_world_hit_stats", "mrt_debug_set_frame_batching", "mrt_debug_set_gather_per_band", "mrt_debug_arith", "mrt_debug_arith_pairs", "mrt_debug_set_boxes", "mrt_debug_build_boxes", "mrt_set_draw_counting", "mrt_debug_last_launch", "mrt_debug_set_frames_in_flight", "mrt_debug_lds_layout", "mrt_debug_build_boxes_top_down",
     "mrt_set_wait_timeout", "mrt_get_schedule", "mrt_set_schedule_hint", "mrt_debug_width_policy", "mrt_debug_width_replay", "mrt_debug_stream_concurrency", "mrt_debug_wave_log_frame",
     "mrt_present", "mrt_present_acquire", "mrt_present_release", "mrt_set_present_ring", "mrt_debug_srgb8_thresholds",
@@ -64,6 +64,7 @@ EXPORTS = [
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
+PRESENT_RGBA16F_LINEAR, PRESENT_RGBA32F_LINEAR = 16, 32
 PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED, PRESENT_TEMPORAL, PRESENT_GATHERED_DENOISED = 1, 2, 8, 16, 32
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
 # how a slot's tile queue was ordered (mrt_debug_read_tile_schedule, MRT_TILE_ORDER_*)
@@ -351,6 +352,8 @@ def load():
         "mrt_write_pfm": (i32, [C.c_char_p, vp, u32, u32]),
         "mrt_write_ppm": (i32, [C.c_char_p, vp, u32, u32]),
         "mrt_srgb8": (C.c_uint8, [f32]),
+        "mrt_half_bits": (C.c_uint16, [f32]),
+        "mrt_half_from_floats": (i32, [vp, sz, vp]),
         "mrt_write_png": (i32, [C.c_char_p, vp, u32, u32]),
         "mrt_gather": (i32, [P(vp), u32, u32]),
         "mrt_gather_rccl": (i32, [vp, vp, u32]),
@@ -450,3 +453,15 @@ def load():
         fn.restype, fn.argtypes = res, args
     _lib = L
     return L
+
+
+def half_bits(values):
+    """mrt_half_from_floats (host only): the IEEE binary16 bits of every float32 of `values`, as a uint16 array of its shape --
+    what MRT_PRESENT_RGBA16F_LINEAR stores per channel (every NaN becomes 0x7E00)."""
+    import numpy as np
+    v = np.ascontiguousarray(values, np.float32)
+    out = np.empty(v.shape, np.uint16)
+    st = load().mrt_half_from_floats(v.ctypes.data, v.size, out.ctypes.data)
+    if st != 0:
+        raise ValueError(f"mrt_half_from_floats: status {st}")
+    return out

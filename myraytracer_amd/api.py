@@ -781,24 +781,28 @@ class State:
         return g
 
     # -- present pass (the reference's pass 2, lib.rs:270-297 / sample_framebuffer.wgsl): 8-bit sRGB images, read back without
-    #    waiting for the frames in flight
-    _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB}
+    #    waiting for the frames in flight; and the linear floats themselves, as binary16 or as the source's float32 bits
+    _PRESENT_FORMATS = {"rgba8": _lib.PRESENT_RGBA8_SRGB, "bgra8": _lib.PRESENT_BGRA8_SRGB,
+                        "rgba16f": _lib.PRESENT_RGBA16F_LINEAR, "rgba32f": _lib.PRESENT_RGBA32F_LINEAR}
+    _PRESENT_DTYPES = {_lib.PRESENT_RGBA16F_LINEAR: np.float16, _lib.PRESENT_RGBA32F_LINEAR: np.float32}
 
     def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False, temporal: bool = False,
                 gathered_denoised: bool = False):
-        """mrt_present: queue the most recent frame's 8-bit sRGB image ("rgba8" / "bgra8"; flip = rows top-down; gathered = the
+        """mrt_present: queue the most recent frame's image: 8-bit sRGB ("rgba8" / "bgra8") or linear ("rgba16f": binary16,
+        _lib.half_bits of every channel; "rgba32f": the source's float32 bits).  flip = rows top-down; gathered = the
         root's full frame of the last gather; denoise = the denoised frame, read_denoised's image; temporal = the temporal image,
         read_temporal's; gathered_denoised = the last gathered frame denoised on the root, read_gathered_denoised's image, a
-        source of its own: with flip only).  Asynchronous."""
+        source of its own: with flip only.  Asynchronous."""
         if fmt not in self._PRESENT_FORMATS:
-            raise ValueError(f"present: format {fmt!r} (rgba8, bgra8)")
+            raise ValueError(f"present: format {fmt!r} ({', '.join(self._PRESENT_FORMATS)})")
         flags = ((_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0) |
                  (_lib.PRESENT_DENOISED if denoise else 0) | (_lib.PRESENT_TEMPORAL if temporal else 0) |
                  (_lib.PRESENT_GATHERED_DENOISED if gathered_denoised else 0))
         self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
 
     def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):
-        """mrt_present_acquire: (uint8 [rows, width, 4], info dict) or None if no image has finished (wait=False) or none is
+        """mrt_present_acquire: ([rows, width, 4] of the image's format -- uint8, float16 for "rgba16f", float32 for "rgba32f" --
+        and the info dict) or None if no image has finished (wait=False) or none is
         queued.  newest: the most recent finished image (older ones are dropped), else the oldest.  copy=False returns a view
         of the library's pinned buffer, valid until release_presented() / the next acquire / reset / close."""
         px = C.POINTER(C.c_uint8)()
@@ -807,8 +811,9 @@ class State:
         self._check(self._L.mrt_present_acquire(self._ctx, mode, int(wait), C.byref(px), C.byref(info)), "mrt_present_acquire")
         if not px:
             return None
-        img = np.ctypeslib.as_array(px, shape=(info.rows, info.width, 4))
-        d = {k: int(getattr(info, k)) for k, _ in _lib.MrtPresentInfo._fields_}
+        dtype = self._PRESENT_DTYPES.get(info.format, np.uint8)
+        img = np.ctypeslib.as_array(px, shape=(info.rows, info.row_bytes)).view(dtype).reshape(info.rows, info.width, 4)
+        d ={k: int(getattr(info, k)) for k, _ in _lib.MrtPresentInfo._fields_}
         return (img.copy() if copy else img), d
 
     def release_presented(self):

@@ -67,6 +67,15 @@ extern "C" {
 
 uint8_t mrt_srgb8(float linear) { return srgb8(linear); }
 
+// the present pass's binary16 channels (MRT_PRESENT_RGBA16F_LINEAR): the definition present.hip compiles too (mrt_internal.h)
+uint16_t mrt_half_bits(float v) { return mrt::half_bits(v); }
+
+int mrt_half_from_floats(const float* in, size_t n, uint16_t* out) {
+    if (n && (!in || !out)) return MRT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n; i++) out[i] = mrt::half_bits(in[i]);
+    return MRT_OK;
+}
+
 int mrt_debug_srgb8_thresholds(float out[256]) {
     if (!out) return MRT_ERR_INVALID_ARG;
     std::memcpy(out, mrt::present_thresholds(), 256 * sizeof(float));

@@ -195,6 +195,25 @@ int launch_arith_pairs(const float* d_x, const float* d_y, uint32_t n, uint32_t*
 // top-down with `flip`; d_tables: the 2 x 256 floats of present_thresholds() in device memory
 int launch_present(const float* src, uint8_t* dst, uint32_t width, uint32_t rows, uint32_t flip, uint32_t bgra,
                    const float* d_tables, void* stream);
+// present.hip: the linear formats -- the same rows as 4 x binary16 per pixel (half: half_bits of every channel) or as the
+// source's own 4 x float32 bits, top-down with `flip`; no table
+int launch_present_float(const float* src, uint8_t* dst, uint32_t width, uint32_t rows, uint32_t flip, uint32_t half, void* stream);
+// mrt_half_bits (include/myraytracer_amd.h), the one definition the host and present.hip share: float32 -> IEEE binary16,
+// round to nearest even in integer arithmetic.  Subnormal halves are produced; |v| >= 65520 -> +-inf; |v| <= 2^-25 -> +-0
+// (the tie included); every NaN -> 0x7E00.
+__host__ __device__ inline uint16_t half_bits(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v), sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+    if (a > 0x7F800000u) return 0x7E00u;
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);                  // 65520 and above, inf
+    if (a >= 0x38800000u) {                                                    // 2^-14 and above: a normal half
+        const uint32_t r = a - 0x38000000u;                                    // (exponent rebiased: 127 -> 15)
+        return (uint16_t)(sign | ((r + 0xFFFu + ((r >> 13) & 1u)) >> 13));     // (a carry out of the mantissa raises the exponent)
+    }
+    if (a <= 0x33000000u) return (uint16_t)sign;                               // 2^-25 and below
+    const uint32_t shift = 126u - (a >> 23), m = (a & 0x7FFFFFu) | 0x800000u;  // a subnormal half: m 2^-shift units of 2^-24, shift 14..24
+    const uint32_t h = m >> shift, rem = m & ((1u << shift) - 1u), tie = 1u << (shift - 1u);
+    return (uint16_t)(sign | (h + ((rem > tie || (rem == tie && (h & 1u))) ? 1u : 0u)));
+}
 // image_io.cpp, host: {colour, alpha} x 256 thresholds -- t[k] = the smallest float whose code is >= k (t[0] = -inf)
 const float* present_thresholds();
 

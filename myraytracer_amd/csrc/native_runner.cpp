@@ -27,6 +27,7 @@ static void usage() {
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
                          "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive | --budget N [--plan-on-device]]]\n"
         "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]] [--denoise-mix [GAIN]]]\n"
+        "                     [--snapshot-every N --snapshot-out PREFIX]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
@@ -43,7 +44,10 @@ static void usage() {
         "  --denoise-variance: the luminance stop's variance (mrt_set_denoise_variance): the pixel's own accumulated estimate\n"
         "                      (default), its 3 x 3 prefilter, or a spatial estimate while fewer than N frames (default 3) are done\n"
         "  --denoise-mix [GAIN]: with --denoise-out: blend the filtered with the accumulated image per pixel by the estimated error\n"
-        "                      (mrt_set_denoise_mix); GAIN 0.25 .. 16, default the library's\n");
+        "                      (mrt_set_denoise_mix); GAIN 0.25 .. 16, default the library's\n"
+        "  --snapshot-every N --snapshot-out PREFIX: (one GPU, not with --target-noise) the frames are queued N at a time and the\n"
+        "                      accumulation after each N is written as PREFIX<frames done, 5 digits>.pfm: the exact floats, presented\n"
+        "                      through the ring (MRT_PRESENT_RGBA32F_LINEAR) without draining the frames in flight\n");
 }
 
 int main(int argc, char** argv) {
@@ -58,6 +62,8 @@ int main(int argc, char** argv) {
     double target_noise = -1.0;
     bool adaptive = false, plan_on_device = false;
     uint64_t budget = 0;
+    uint32_t snapshot_every = 0;
+    std::string snapshot_out;
     mrt_denoise_mix mix;
     mrt_denoise_mix_default(&mix);
     std::string scene = "default", scene_file, save_scene, out, denoise_out;
@@ -108,6 +114,8 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = std::atoi(v.c_str());
         else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
         else if (a == "--budget") budget = std::strtoull(v.c_str(), nullptr, 10);
+        else if (a == "--snapshot-every") snapshot_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
+        else if (a == "--snapshot-out") snapshot_out = v;
         else if (a == "--check-every") check_every = (uint32_t)std::strtoul(v.c_str(), nullptr, 10);
         else if (a == "--gpus") { devices.clear(); for (int d = 0; d < std::atoi(v.c_str()); d++) devices.push_back(d); }
         else if (a == "--devices") {
@@ -170,6 +178,8 @@ int main(int argc, char** argv) {
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (budget && (adaptive || target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--budget wants --target-noise and one GPU, and not --adaptive\n"); destroy_all(); return 2; }
     if (plan_on_device && !budget) { std::fprintf(stderr, "--plan-on-device wants --budget\n"); destroy_all(); return 2; }
+    if ((snapshot_every != 0) != !snapshot_out.empty()) { std::fprintf(stderr, "--snapshot-every N (>= 1) and --snapshot-out PREFIX go together\n"); destroy_all(); return 2; }
+    if (snapshot_every && (target_noise >= 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--snapshot-every wants one GPU and the plain --frames mode (not --target-noise)\n"); destroy_all(); return 2; }
     if (warmup) {           // untimed: the tile-cost estimate, buffers and peer mappings exist afterwards
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, warmup));
         if (n_gpus > 1) TRY(ctxs[0], mrt_gather(ctxs.data(), n_gpus, 0));
@@ -187,7 +197,44 @@ int main(int argc, char** argv) {
     // only the final accumulated image is wanted, so every GPU renders all its frames (mrt_render may share a launch
     // among several frames when its shard is too small to fill the GPU) and the shards are gathered once
     mrt_noise_report report{};
-    if (target_noise < 0.0) {
+    if (snapshot_every) {
+        // --snapshot-every: chunks of N frames, each followed by a present of the exact floats (bottom-up, as PFM wants them);
+        // the images are taken in FIFO order as their copies land -- polled between chunks, waited for only after the last --
+        // and the frames stay in flight: no mrt_read_framebuffer before the final --out.  At most depth - 1 presents are kept
+        // outstanding (nothing is dropped then: a full ring waits for its oldest image); the depth is known from the first image on
+        mrt_ctx* c = ctxs[0];
+        uint32_t outstanding = 0, keep = 1, written = 0;
+        auto take = [&](int wait) -> int {                   // 1: wrote one, 0: none has finished, < 0: failed
+            const uint8_t* px = nullptr;
+            mrt_present_info info{};
+            const int s_ = mrt_present_acquire(c, MRT_ACQUIRE_OLDEST, wait, &px, &info);
+            if (s_ != MRT_OK) { std::fprintf(stderr, "mrt_present_acquire: %s (%s)\n", mrt_status_string(s_), mrt_last_error(c)); return -1; }
+            if (!px) return 0;
+            if (info.dropped) { std::fprintf(stderr, "--snapshot-every: %u snapshot(s) before frame %u were dropped\n", info.dropped, info.frames_done); return -1; }
+            char name[16];
+            std::snprintf(name, sizeof name, "%05u.pfm", info.frames_done);
+            const std::string path = snapshot_out + name;
+            if (mrt_write_pfm(path.c_str(), reinterpret_cast<const float*>(px), info.width, info.rows) != MRT_OK) {
+                std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                return -1;
+            }
+            keep = std::max(1u, info.ring_depth - 1u);
+            outstanding--; written++;
+            return 1;
+        };
+        for (uint32_t done = 0; done < frames;) {
+            const uint32_t k = std::min(snapshot_every, frames - done);
+            TRY(c, mrt_render(c, k));
+            done += k;
+            while (outstanding >= keep) if (take(1) <= 0) { destroy_all(); return 1; }
+            TRY(c, mrt_present(c, MRT_PRESENT_RGBA32F_LINEAR, 0));
+            outstanding++;
+            for (int r = 1; r == 1 && outstanding;) if ((r = take(0)) < 0) { destroy_all(); return 1; }
+        }
+        while (outstanding) if (take(1) <= 0) { destroy_all(); return 1; }
+        TRY(c, mrt_present_release(c));
+        std::printf("wrote %u snapshots %s<frames done>.pfm\n", written, snapshot_out.c_str());
+    } else if (target_noise < 0.0) {
         for (mrt_ctx* c : ctxs) TRY(c, mrt_render(c, frames));               // asynchronous: all GPUs render at once
     } else {
         // --target-noise: chunks of check_every frames; chunk k + 1 is queued before report k is waited for (the pipeline stays

@@ -58,7 +58,9 @@ uint32_t present_depth_for(const mrt_ctx* c) {
 }
 
 // entries of `bytes` each, at least `depth` of them: added without synchronising anything (hipMalloc, hipHostMalloc); entries
-// too small for `bytes` are released first, after their copies have landed (a larger source than before: rare)
+// too small for `bytes` are released first, after their copies have landed (a larger source or a wider format than before:
+// rare; the queued images are discarded and counted as dropped, MRT_ERR_STATE while the caller holds one).  Entries are never
+// shrunk: they fit the largest image presented so far, whatever its format
 int present_ring_reserve(mrt_ctx* c, size_t bytes, uint32_t depth) {
     if (bytes > c->present_entry_bytes) {
         for (const auto& E : c->present_ring)
@@ -118,7 +120,13 @@ int present_pick(mrt_ctx* c, uint32_t* out) {
     return MRT_OK;
 }
 
-bool present_format_ok(int format) { return format == MRT_PRESENT_RGBA8_SRGB || format == MRT_PRESENT_BGRA8_SRGB; }
+bool present_format_8bit(int format) { return format == MRT_PRESENT_RGBA8_SRGB || format == MRT_PRESENT_BGRA8_SRGB; }
+
+// bytes per pixel of a present format; 0: no such format
+uint32_t present_pixel_bytes(int format) {
+    if (present_format_8bit(format)) return 4;
+    return format == MRT_PRESENT_RGBA16F_LINEAR ? 8u : format == MRT_PRESENT_RGBA32F_LINEAR ? 16u : 0u;
+}
 
 }  // namespace
 
@@ -126,7 +134,8 @@ extern "C" {
 
 int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    if (!present_format_ok(format)) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: format %d", format);
+    const uint32_t pixel_bytes = present_pixel_bytes(format);
+    if (!pixel_bytes) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: format %d", format);
     if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL | MRT_PRESENT_GATHERED_DENOISED))
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
     const bool gathered = (flags & MRT_PRESENT_GATHERED) != 0, denoised = (flags & MRT_PRESENT_DENOISED) != 0;
@@ -159,10 +168,11 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
         src = c->d_fb[c->target ^ 1];
         rows = c->args.height;
     }
-    const size_t bytes = (size_t)rows * width * 4;
+    // (an image larger than the ring's entries -- a larger source, or a wider format than any presented so far -- regrows them)
+    const size_t bytes = (size_t)rows * width * pixel_bytes;
     if (bytes == 0) return fail(c, MRT_ERR_STATE, "mrt_present: empty image");
     HIP_TRY(c, hipSetDevice(c->device));
-    MRT_TRY(ensure_present_tables(c));
+    if (pixel_bytes == 4) MRT_TRY(ensure_present_tables(c));        // (the linear formats search no table)
     MRT_TRY(present_ring_reserve(c, bytes, present_depth_for(c)));
     uint32_t i = 0;
     MRT_TRY(present_pick(c, &i));
@@ -171,8 +181,10 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (denoised) MRT_TRY(mrt::present_denoised(c, &src));
     if (temporal) MRT_TRY(mrt::present_temporal(c, &src));
     if (gathered_denoised) MRT_TRY(mrt::present_gathered_denoised(c, &src));
-    const int e = mrt::launch_present(src, E.d_img, width, rows, (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u,
-                                      format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u, c->d_present_tables, c->stream);
+    const uint32_t flip = (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u;
+    const int e = pixel_bytes == 4 ? mrt::launch_present(src, E.d_img, width, rows, flip, format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u,
+                                                         c->d_present_tables, c->stream)
+                                   : mrt::launch_present_float(src, E.d_img, width, rows, flip, pixel_bytes == 8 ? 1u : 0u, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "present launch failed: %s", hipGetErrorString((hipError_t)e));
     hipStream_t copy_stream = c->stream;
     if (c->present_copy_mode == 0) {
@@ -188,7 +200,7 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     E.info = mrt_present_info{};
     E.info.seq = ++c->present_seq;
     E.info.frames_done = gathered_denoised ? c->gather_frames : c->frames_done;      // (the gather's snapshot: what the image shows)
-    E.info.width = width; E.info.rows = rows; E.info.row_bytes = width * 4;
+    E.info.width = width; E.info.rows = rows; E.info.row_bytes = width * pixel_bytes;
     E.info.format = (uint32_t)format; E.info.flags = flags;
     E.state = PresentEntry::kQueued;
     return MRT_OK;
@@ -268,7 +280,7 @@ int mrt_debug_set_present_copy(mrt_ctx* c, int mode) {
 
 int mrt_debug_present_encode(mrt_ctx* c, const float* rgba, uint32_t width, uint32_t rows, int format, uint32_t flags,
                              uint8_t* out) {
-    if (!c || !rgba || !out || !width || !rows || !present_format_ok(format) || (flags & ~(uint32_t)MRT_PRESENT_FLIP_Y) ||
+    if (!c || !rgba || !out || !width || !rows || !present_format_8bit(format) || (flags & ~(uint32_t)MRT_PRESENT_FLIP_Y) ||
         (uint64_t)width * rows > (1ull << 28))
         return MRT_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));

@@ -61,8 +61,20 @@ def _budget(line_pattern, pattern):
     raise KeyError(line_pattern)
 
 
+def _present_float(label):
+    """Msamples/s of the run "== float <label>" of the section "float formats" of profiles/present_rates.txt (round 1 of two)"""
+    lines = open(os.path.join(ROOT, "profiles", "present_rates.txt")).read().split("\n")
+    at = lines.index(f"== float {label}")
+    return float(re.search(r": (\d+) Msamples/s", lines[at + 1]).group(1))
+
+
 # token -> (how to get the value, format)
 TOKENS = {
+    "PRESENT_F32_RATE": (lambda: _present_float("c1080 rgba32f r1"), ",.0f"),
+    "PRESENT_F16_RATE": (lambda: _present_float("c1080 rgba16f r1"), ",.0f"),
+    "PRESENT_RGBA8_RATE": (lambda: _present_float("c1080 rgba8 r1"), ",.0f"),
+    "PRESENT_READ_RATE": (lambda: _present_float("c1080 read r1"), ",.0f"),
+    "PRESENT_NONE_RATE": (lambda: _present_float("c1080 none r1"), ",.0f"),
     "C3_VALUE": (lambda: _json(f"{R}_bench_n1.json")["value"], ",.0f"),
     "C3_MS": (lambda: _json(f"{R}_bench_n1.json")["ms_per_step"], ".1f"),
     "CPU_CORES": (lambda: _json(f"{R}_bench_n1.json")["cpu_baseline"]["cores"], "d"),

@@ -2,6 +2,7 @@
 """Dev helper (GPU box): pipelined wall-clock Msamples/s of one workload under the tuning switches.
    [MRT_HIER=levels,top] [MRT_BOXES=0|1] [MRT_RNG=1] [MRT_HINT=div,mult] [MRT_READ_EVERY=1] [MRT_SHARD=rank,world] [MRT_STEADY=1]
    [MRT_PRESENT_EVERY=1 (a viewer on the present pass: mrt_present after every redraw, the newest image acquired without waiting)]
+   [MRT_PRESENT_FORMAT=rgba8|bgra8|rgba16f|rgba32f (the format of those presents; default bgra8)]
    [MRT_PRESENT_COPY=0|1 (the present's copy on a stream of its own / on the context's stream)]
    [MRT_PRESENT_DENOISE=1 (the presents are denoised: noise tracking on, MRT_PRESENT_DENOISED; with MRT_PRESENT_EVERY=k, every k
     frames)]
@@ -30,9 +31,10 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     read_every = bool(os.environ.get("MRT_READ_EVERY"))     # a viewer: the framebuffer is read back after every redraw
     present_every = int(os.environ.get("MRT_PRESENT_EVERY", "0") or "0")      # 1: after every redraw; k: every k-th
     present_denoise = bool(os.environ.get("MRT_PRESENT_DENOISE"))
+    present_format = os.environ.get("MRT_PRESENT_FORMAT") or "bgra8"
     if os.environ.get("MRT_PRESENT_COPY"):
         st.debug_set_present_copy(int(os.environ["MRT_PRESENT_COPY"]))
-    acquired = 0
+    acquired, ring_depth = 0, 0
     noise_every = int(os.environ.get("MRT_NOISE_EVERY", "0"))
     if noise_every or os.environ.get("MRT_NOISE") or present_denoise:
         st.set_noise_tracking(True)
@@ -51,15 +53,17 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
         stamps.append(time.perf_counter())         # (a call returns when the oldest frame in flight has ended: the back-pressure)
         if read_every: st.read_framebuffer()
         if present_every and (k + 1) % present_every == 0:
-            st.present("bgra8", flip=shard is None, denoise=present_denoise)
-            acquired += st.acquire_presented(newest=True, wait=False, copy=False) is not None
+            st.present(present_format, flip=shard is None, denoise=present_denoise)
+            got = st.acquire_presented(newest=True, wait=False, copy=False)
+            acquired += got is not None
+            ring_depth = got[1]["ring_depth"] if got else ring_depth
         if noise_every and (k + 1) % noise_every == 0:
             st.noise_query()
             reports += st.noise_result(wait=False) is not None
     st.sync()
     dt = time.perf_counter() - t0
-    present_note = (f"presented{' denoised' if present_denoise else ''} every {'frame' if present_every == 1 else f'{present_every} frames'} "
-                    f"({acquired} of {steps // max(present_every, 1)} acquired without waiting, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), ")
+    present_note = (f"presented{' denoised' if present_denoise else ''} as {present_format} every {'frame' if present_every == 1 else f'{present_every} frames'} "
+                    f"({acquired} of {steps // max(present_every, 1)} acquired without waiting, ring depth {ring_depth}, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), ")
     c1 = st.read_counters()
     util = (c1["world_hit_calls"] - c0["world_hit_calls"]) / max(1, c1["lane_slots"] - c0["lane_slots"])
     print(f"{scene} {w}x{h}x{spp} HIER={os.environ.get('MRT_HIER')} BOXES={os.environ.get('MRT_BOXES')} RNG={os.environ.get('MRT_RNG')}: "
