@@ -854,19 +854,18 @@ int mrt_debug_check_context(mrt_ctx* c, char* why, size_t cap) {
         if (!E.d_img || !E.h_img || !E.copied) return check_finding(why, cap, "present ring entry %zu lacks its device image, pinned image or event", i);
     }
     if (!c->present_ring.empty() && (c->present_entry_bytes == 0 || !c->d_present_tables)) return check_finding(why, cap, "a present ring without entry size or tables");
-    if (!c->guides_stale && (!c->d_guides || !c->d_guide_rays || !c->d_guide_hits || !c->d_guide_queue || !c->d_guide_cand || !c->d_den[0] || !c->d_den[1] || !c->d_den[2]))
+    if (!c->guides_stale && (!c->d_guides || !c->d_guide_rays || !c->d_guide_hits || !c->d_guide_queue || !c->d_guide_cand || !c->den.have_filter()))
         return check_finding(why, cap, "the guides are marked current without the denoiser's buffers");
     if (c->gather_has_s && (!c->d_gather || c->gather_bytes < mrt::gathered_colour_bytes(c) + mrt::gathered_colour_bytes(c) / 4))
         return check_finding(why, cap, "a gathered S is marked readable in a gathered frame of %zu bytes (%zu of colour)", c->gather_bytes, mrt::gathered_colour_bytes(c));
     if (c->temporal_on && c->shard_world != 1) return check_finding(why, cap, "temporal reprojection is on on shard %u of %u", c->shard_rank, c->shard_world);
     if (c->temporal_cur > 1) return check_finding(why, cap, "temporal history pair %u", c->temporal_cur);
-    if (c->temporal_stepped && (!c->temporal_on || c->temporal_clear || !c->have_world || !c->d_guides || !c->d_den[0] || !c->d_den[1] || !c->d_den[2] ||
-                                !c->d_den[3] || !c->d_den[4] || !c->d_den[5] || !c->d_den[6]))
+    if (c->temporal_stepped && (!c->temporal_on || c->temporal_clear || !c->have_world || !c->d_guides || !c->den.have_filter() || !c->den.all_history(false)))
         return check_finding(why, cap, "a temporal history is marked readable without temporal reprojection, a scene, the guides or its buffers");
-    if (!c->temporal_on && (c->d_den[3] || c->d_den[4] || c->d_den[5] || c->d_den[6])) return check_finding(why, cap, "history buffers exist while temporal reprojection is off");
-    if (c->temporal_stepped && c->temporal_response.enabled && (!c->d_den[7] || !c->d_den[8]))
+    if (!c->temporal_on && c->den.any_history(false)) return check_finding(why, cap, "history buffers exist while temporal reprojection is off");
+    if (c->temporal_stepped && c->temporal_response.enabled && !c->den.all_history(true))
         return check_finding(why, cap, "a temporal history with the response on is marked readable without the fast history's buffers");
-    if (!c->temporal_on && (c->d_den[7] || c->d_den[8])) return check_finding(why, cap, "fast history buffers exist while temporal reprojection is off");
+    if (!c->temporal_on && c->den.any_history(true)) return check_finding(why, cap, "fast history buffers exist while temporal reprojection is off");
     if (c->temporal_response.enabled > 1 || c->temporal_response.size != sizeof(mrt_temporal_response))
         return check_finding(why, cap, "temporal response enabled %u, size %u", c->temporal_response.enabled, c->temporal_response.size);
     if (c->auto_regroup.enabled > 1 || c->auto_regroup.size != sizeof(mrt_auto_regroup) || c->auto_regroup.check_every < 1 || c->auto_regroup.check_every > 1024)

@@ -1,35 +1,18 @@
-// The denoiser of include/myraytracer_amd.h: the first-hit guides and the filter (denoise.hip).
+// The denoiser and the temporal reprojection of include/myraytracer_amd.h: the first-hit guides, the filter (denoise.hip), the
+// history's step and image (temporal.hip), and what mrt_present and the float read-backs share of them (ImageSource, mrt_ctx.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "mrt_ctx.h"
 
-using mrt::fail, mrt::fill_scene_params;
-
-namespace mrt {
-
-// the denoiser's guides and buffers (sized for the image; allocated at the first denoise, ensure_denoise_buffers)
-void free_denoise_buffers(mrt_ctx* c) {
-    free_device(c->d_guide_rays, c->d_guide_hits, c->d_guide_cand, c->d_guide_queue, c->d_guides, c->d_den[0], c->d_den[1], c->d_den[2]);
-    free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6], c->d_den[7], c->d_den[8]);
-    c->guide_cand_words = 0;
-    c->guides_stale = true;
-    drop_temporal_history(c);
-}
-
-void drop_temporal_history(mrt_ctx* c) {
-    c->temporal_clear = true;
-    c->temporal_stepped = false;
-}
-
-}  // namespace mrt
+using mrt::fail, mrt::fill_scene_params, mrt::ImageSource;
 
 // ---- denoiser (include/myraytracer_amd.h, "denoiser") ----------------------------------------------------------------------
 // queue_denoise queues, on the ctx's stream right behind the most recent frame's blend, the guide rebuild when the guides are
 // stale (denoise.hip: the centre rays; render_kernel's DBG instantiation: their closest hits; the guide records) and the filter's
-// iterations into d_den[2]; nothing here waits on the host.  Ordering: every reader of d_den[2] (the present kernel, the read-back
-// copy) is queued behind it on the same stream, and the next denoise is queued behind those readers.
+// iterations into den.out(); nothing here waits on the host.  Ordering: every reader of den.out() (the present kernel, the
+// read-back copy) is queued behind it on the same stream, and the next denoise is queued behind those readers.
 namespace {
 
 bool denoise_params_ok(const mrt_denoise_params* p) {
@@ -53,13 +36,13 @@ int ensure_denoise_buffers(mrt_ctx* c) {
     const size_t n = (size_t)c->args.width * c->args.height;
     // the filter's three buffers; with temporal reprojection on -- and only then -- the history's four behind them, and with its
     // response on as well the fast history's two behind those
-    const size_t n_den = !c->temporal_on ? 3 : c->temporal_response.enabled ? 9 : 7;
-    if (!c->d_guides || !c->d_den[n_den - 1]) {     // (each of them unless it is there already, an earlier, refused attempt's included)
+    const size_t n_den = mrt::DenoiseBuffers::wanted(c->temporal_on, c->temporal_response.enabled != 0);
+    if (!c->d_guides || !c->den.have_filter() || (c->temporal_on && !c->den.have_history(c->temporal_response.enabled != 0))) {  // (each of them unless it is there already, an earlier, refused attempt's included)
         if (!c->d_guide_rays) HIP_TRY(c, hipMalloc((void**)&c->d_guide_rays, n * 6 * sizeof(float)));
         if (!c->d_guide_hits) HIP_TRY(c, hipMalloc((void**)&c->d_guide_hits, n * 2 * sizeof(int32_t)));
         if (!c->d_guide_queue) HIP_TRY(c, hipMalloc((void**)&c->d_guide_queue, 64));
-        for (auto& d : c->d_den) {
-            if ((size_t)(&d - c->d_den) >= n_den) break;
+        for (auto& d : c->den.buf) {
+            if (&d == c->den.buf + n_den) break;
             if (!d) HIP_TRY(c, hipMalloc((void**)&d, n * 16));
         }
         if (!c->d_guides) {
@@ -98,7 +81,7 @@ int rebuild_guides(mrt_ctx* c) {
     fill_scene_params(c, p);
     p.shard_rank = 0; p.shard_world = 1;
     const bool shard = c->shard_world != 1;
-    p.seeds = shard ? reinterpret_cast<const uint32_t*>(c->d_den[0]) : c->d_seeds;
+    p.seeds = shard ? reinterpret_cast<const uint32_t*>(c->den.ping()) : c->d_seeds;
     p.tiles_x = c->tiles_x; p.n_tiles = shard ? c->tiles_x * mrt::total_bands(H) : c->n_tiles;
     p.tile_queue = c->d_guide_queue;
     p.n_blocks = 1; p.pix_stride = 0; p.queue_layers = 1; p.lane_frames = 1;
@@ -138,12 +121,12 @@ mrt::UniformVariance variance_of(uint32_t mode, uint32_t frames_done, uint32_t s
     return mode == MRT_DENOISE_VAR_PREFILTERED ? V::Prefiltered : V::Accumulated;
 }
 
-// what every denoise of the context shares: frame `fb` through the context's guides, scratch and parameters into d_den[2]
+// what every denoise of the context shares: frame `fb` through the context's guides, scratch and parameters into den.out()
 mrt::DenoiseJob denoise_job(const mrt_ctx* c, const float* fb, mrt::DenoiseSource source) {
     mrt::DenoiseJob j{};
     j.fb = fb;
     j.guides = c->d_guides;
-    j.ping = c->d_den[0]; j.pong = c->d_den[1]; j.out = c->d_den[2];
+    j.ping = c->den.ping(); j.pong = c->den.pong(); j.out = c->den.out();
     j.width = c->args.width; j.height = c->args.height;
     j.prm = c->denoise;
     j.source = source;
@@ -160,36 +143,20 @@ int gathered_denoise_check(mrt_ctx* c, const char* who, bool tracking) {
     return MRT_OK;
 }
 
-// the latest gathered frame, denoised into d_den[2] with the gather's snapshot of K and the frame count (after gathered_denoise_check)
-int queue_gathered_denoise(mrt_ctx* c) {
+// The most recent frame denoised into den.out() (after denoise_check): with one K, or -- an adaptive accumulation -- K per tile.
+// `gathered`: the latest gathered frame, with the gather's snapshot of K and the frame count (after gathered_denoise_check).
+int queue_denoise(mrt_ctx* c, bool gathered) {
+    const bool per_tile = !gathered && c->denoise_adaptive && c->tiles_diverged;
+    // K per tile: the device table covers every count of the host's map, which is the device's at this point of the stream
+    if (per_tile) MRT_TRY(mrt::ensure_k_table(c, mrt::most_tile_frames(c) + 1u));
     MRT_TRY(ensure_guides(c));
-    mrt::DenoiseJob job = denoise_job(c, c->d_gather, mrt::DenoiseSource::Uniform);
-    job.S = mrt::gathered_noise(c);
-    job.uniform = {(float)c->gather_k, variance_of(c->denoise_var_mode, c->gather_frames, c->denoise_spatial_frames)};
+    mrt::DenoiseJob job = denoise_job(c, gathered ? c->d_gather : c->d_fb[c->target ^ 1], per_tile ? mrt::DenoiseSource::Tiles : mrt::DenoiseSource::Uniform);
+    job.S = gathered ? mrt::gathered_noise(c) : c->d_noise_s;
+    if (per_tile) job.tiles = {c->d_tile_frames, c->d_k_f32, c->tiles_x, c->denoise_var_mode, c->denoise_spatial_frames};
+    else job.uniform = {(float)(gathered ? c->gather_k : mrt::noise_factor_of(c->noise_c2)),
+                        variance_of(c->denoise_var_mode, gathered ? c->gather_frames : c->frames_done, c->denoise_spatial_frames)};
     const int e = mrt::launch_denoise(job, c->stream);
-    if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
-    return MRT_OK;
-}
-
-// the most recent frame, denoised into d_den[2] (after denoise_check)
-int queue_denoise(mrt_ctx* c) {
-    if (c->denoise_adaptive && c->tiles_diverged) {
-        // K per tile: the device table covers every count of the host's map, which is the device's at this point of the stream
-        MRT_TRY(mrt::ensure_k_table(c, mrt::most_tile_frames(c) + 1u));
-        MRT_TRY(ensure_guides(c));
-        mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Tiles);
-        job.S = c->d_noise_s;
-        job.tiles = {c->d_tile_frames, c->d_k_f32, c->tiles_x, c->denoise_var_mode, c->denoise_spatial_frames};
-        const int e = mrt::launch_denoise(job, c->stream);
-        if (e) return fail(c, MRT_ERR_HIP, "per-tile denoise launch failed: %s", hipGetErrorString((hipError_t)e));
-        return MRT_OK;
-    }
-    MRT_TRY(ensure_guides(c));
-    mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Uniform);
-    job.S = c->d_noise_s;
-    job.uniform = {(float)mrt::noise_factor_of(c->noise_c2), variance_of(c->denoise_var_mode, c->frames_done, c->denoise_spatial_frames)};
-    const int e = mrt::launch_denoise(job, c->stream);
-    if (e) return fail(c, MRT_ERR_HIP, "denoise launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e) return fail(c, MRT_ERR_HIP, "%sdenoise launch failed: %s", per_tile ? "per-tile " : "", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
 
@@ -260,26 +227,32 @@ bool temporal_response_ok(const mrt_temporal_response* p) {
     return true;
 }
 
-// the history's buffers are there: the four, and with the response on the fast history's two
-bool have_history_buffers(const mrt_ctx* c) { return c->d_den[6] && (!c->temporal_response.enabled || c->d_den[8]); }
-
 // A dropped history, made what the next step reads: every length 0 (no tap counts), the fast history zeroed with it, "previous"
-// camera the current one.  Queued on the ctx's stream.
-int clear_history(mrt_ctx* c) {
+// camera the current one.  Queued on the ctx's stream.  (h0, cam false: mrt_debug_load_temporal brings that part itself.)
+int clear_history(mrt_ctx* c, bool h0 = true, bool cam = true) {
     const size_t n = (size_t)c->args.width * c->args.height;
     const uint32_t cur = c->temporal_cur;
-    HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
-    if (c->temporal_response.enabled && c->d_den[7 + cur]) HIP_TRY(c, hipMemsetAsync(c->d_den[7 + cur], 0, n * 16, c->stream));
-    c->temporal_prev_cam = c->cam_raw;
+    if (h0) HIP_TRY(c, hipMemsetAsync(c->den.h0(cur), 0, n * 16, c->stream));
+    if (c->temporal_response.enabled && c->den.h2(cur)) HIP_TRY(c, hipMemsetAsync(c->den.h2(cur), 0, n * 16, c->stream));
+    if (cam) c->temporal_prev_cam = c->cam_raw;
     c->temporal_clear = false;
     return MRT_OK;
 }
 
-// the temporal image into d_den[2]: the history's field (its variance made first), then the filter's iterations
+// What the four debug reads and loads of the history (`who`) open with: a step's refusals, the response's, the buffers'.  The rest
+// stays with each: the capacity refusals (before hipSetDevice) differ -- one counts spheres too, the loads have none -- as does the clearing
+int history_io_opening(mrt_ctx* c, const char* who, bool needs_response) {
+    MRT_TRY(temporal_check(c, who, false));
+    if (needs_response && !c->temporal_response.enabled) return fail(c, MRT_ERR_STATE, "%s: the response is off (mrt_set_temporal_response)", who);
+    if (!c->den.have_history(c->temporal_response.enabled != 0)) return fail(c, MRT_ERR_STATE, "%s: no history buffers yet (mrt_temporal_step)", who);
+    return MRT_OK;
+}
+
+// the temporal image into den.out(): the history's field (its variance made first), then the filter's iterations
 int queue_temporal_image(mrt_ctx* c) {
     const uint32_t cur = c->temporal_cur;
     mrt::DenoiseJob job = denoise_job(c, c->d_fb[c->target ^ 1], mrt::DenoiseSource::Temporal);
-    job.temporal = {c->d_den[3 + 2 * cur], c->d_den[4 + 2 * cur], c->temporal.spatial_len};
+    job.temporal = {c->den.h0(cur), c->den.h1(cur), c->temporal.spatial_len};
     const int e = mrt::launch_denoise(job, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "temporal image launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
@@ -325,28 +298,59 @@ int debug_denoise(mrt_ctx* c, const float* rgba, const float* S, double K, const
     return MRT_OK;
 }
 
+// mrt_read_denoised, mrt_read_temporal and mrt_read_gathered_denoised (`who`): a source's image, queued and read back
+int read_source(mrt_ctx* c, ImageSource source, const char* who, float* out, size_t cap) {
+    MRT_TRY(mrt::source_check(c, source, who));
+    const size_t n = (size_t)c->args.width * c->args.height * 4;
+    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "%s: need %zu floats", who, n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    mrt::SourceImage S;
+    MRT_TRY(mrt::source_queue(c, source, &S));
+    HIP_TRY(c, hipMemcpyAsync(out, S.img, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return mrt::wait_stream(c, c->stream, who);
+}
+
 }  // namespace
 
 namespace mrt {
-int present_temporal_check(mrt_ctx* c) { return temporal_check(c, "mrt_present", true); }
-int present_temporal(mrt_ctx* c, const float** src) {
-    MRT_TRY(queue_temporal_image(c));
-    *src = c->d_den[2];
+
+// the denoiser's guides and buffers (sized for the image; allocated at the first denoise, ensure_denoise_buffers)
+void free_denoise_buffers(mrt_ctx* c) {
+    free_device(c->d_guide_rays, c->d_guide_hits, c->d_guide_cand, c->d_guide_queue, c->d_guides);
+    c->den.free_all();
+    c->guide_cand_words = 0;
+    c->guides_stale = true;
+    drop_temporal_history(c);
+}
+
+void drop_temporal_history(mrt_ctx* c) {
+    c->temporal_clear = true;
+    c->temporal_stepped = false;
+}
+
+int source_check(mrt_ctx* c, ImageSource source, const char* who) {
+    switch (source) {
+        case ImageSource::Denoised: return denoise_check(c, who, true);
+        case ImageSource::Temporal: return temporal_check(c, who, true);
+        case ImageSource::GatheredDenoised: return gathered_denoise_check(c, who, true);
+        case ImageSource::Gathered:
+            if (!c->d_gather) return fail(c, MRT_ERR_STATE, "%s: nothing gathered yet (mrt_gather / mrt_gather_rccl on the root)", who);
+            if (c->gather_bytes < (size_t)c->args.height * c->args.width * 16) return fail(c, MRT_ERR_STATE, "%s: the gathered frame is smaller than the image", who);
+            return MRT_OK;
+        case ImageSource::Accumulated: break;        // (always there)
+    }
     return MRT_OK;
 }
-// mrt_present's part (present.cpp): checks, then queues the denoise; *src = the denoised frame
-int present_denoised(mrt_ctx* c, const float** src) {
-    MRT_TRY(queue_denoise(c));
-    *src = c->d_den[2];
+
+int source_queue(mrt_ctx* c, ImageSource source, SourceImage* out) {
+    if (source == ImageSource::Denoised || source == ImageSource::GatheredDenoised) MRT_TRY(queue_denoise(c, source == ImageSource::GatheredDenoised));
+    if (source == ImageSource::Temporal) MRT_TRY(queue_temporal_image(c));
+    // (den.out() is read behind the queue, which may allocate it; the frame count is what the image shows: the gather's snapshot)
+    const float* img = source == ImageSource::Accumulated ? c->d_fb[c->target ^ 1] : source == ImageSource::Gathered ? c->d_gather : c->den.out();
+    *out = {img, source_rows(c, source), source == ImageSource::GatheredDenoised ? c->gather_frames : c->frames_done};
     return MRT_OK;
 }
-int present_denoised_check(mrt_ctx* c) { return denoise_check(c, "mrt_present", true); }
-int present_gathered_denoised_check(mrt_ctx* c) { return gathered_denoise_check(c, "mrt_present", true); }
-int present_gathered_denoised(mrt_ctx* c, const float** src) {
-    MRT_TRY(queue_gathered_denoise(c));
-    *src = c->d_den[2];
-    return MRT_OK;
-}
+
 }  // namespace mrt
 
 extern "C" {
@@ -420,24 +424,12 @@ int mrt_get_denoise_adaptive(mrt_ctx* c, int* enabled) {
 
 int mrt_read_denoised(mrt_ctx* c, float* out, size_t cap) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(denoise_check(c, "mrt_read_denoised", true));
-    const size_t n = (size_t)c->args.width * c->args.height * 4;
-    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_denoised: need %zu floats", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    MRT_TRY(queue_denoise(c));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return mrt::wait_stream(c, c->stream, __func__);
+    return read_source(c, ImageSource::Denoised, __func__, out, cap);
 }
 
 int mrt_read_gathered_denoised(mrt_ctx* c, float* out, size_t cap) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(gathered_denoise_check(c, "mrt_read_gathered_denoised", true));
-    const size_t n = (size_t)c->args.width * c->args.height * 4;
-    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_gathered_denoised: need %zu floats", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    MRT_TRY(queue_gathered_denoise(c));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return mrt::wait_stream(c, c->stream, __func__);
+    return read_source(c, ImageSource::GatheredDenoised, __func__, out, cap);
 }
 
 void mrt_temporal_params_default(mrt_temporal_params* out) {
@@ -455,7 +447,7 @@ int mrt_set_temporal(mrt_ctx* c, int enabled, const mrt_temporal_params* params)
     if (!enabled && c->temporal_on) {   // the history goes; queued steps and reads may still use it
         HIP_TRY(c, hipSetDevice(c->device));
         MRT_TRY(mrt::wait_stream(c, c->stream, "mrt_set_temporal: releasing the history"));
-        mrt::free_device(c->d_den[3], c->d_den[4], c->d_den[5], c->d_den[6], c->d_den[7], c->d_den[8]);
+        c->den.free_history();
         mrt::drop_temporal_history(c);
     }
     if (params) c->temporal = *params;
@@ -507,22 +499,19 @@ int mrt_temporal_step(mrt_ctx* c) {
     std::memset(&a, 0, sizeof a);
     a.fb = c->d_fb[c->target ^ 1];
     a.rays = c->d_guide_rays; a.guides = c->d_guides; a.shade = c->d_shade; a.prev_xyzr = c->d_prev_xyzr;
-    a.h0_in = c->d_den[3 + 2 * cur]; a.h1_in = c->d_den[4 + 2 * cur];
-    a.h0_out = c->d_den[3 + 2 * (cur ^ 1)]; a.h1_out = c->d_den[4 + 2 * (cur ^ 1)];
+    a.h0_in = c->den.h0(cur); a.h1_in = c->den.h1(cur);
+    a.h0_out = c->den.h0(cur ^ 1); a.h1_out = c->den.h1(cur ^ 1);
     a.width = c->args.width; a.height = c->args.height; a.n_spheres = c->n_spheres;
     temporal_camera(c->temporal_prev_cam, a.M, a.o_prev);
     a.max_history = (float)c->temporal.max_history; a.depth_tol = c->temporal.depth_tol;
-    int e;
-    if (resp.enabled) {                 // the same step with the fast history, then the clamp in place on its output
-        const mrt::TemporalFastArgs f{c->d_den[7 + cur], c->d_den[7 + (cur ^ 1)], (float)resp.fast_history};
-        e = mrt::launch_temporal_reproject_fast(a, f, c->stream);
-        if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+    // with the response on: the same step with the fast history, then the clamp in place on its output
+    const mrt::TemporalFastArgs f{c->den.h2(cur), c->den.h2(cur ^ 1), (float)resp.fast_history};
+    int e = resp.enabled ? mrt::launch_temporal_reproject_fast(a, f, c->stream) : mrt::launch_temporal_reproject(a, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (resp.enabled) {
         const mrt::TemporalClampArgs k{a.h0_out, a.h1_out, f.h2_out, a.width, a.height, f.fast_history, resp.clamp_sigma, resp.antilag};
         e = mrt::launch_temporal_clamp(k, c->stream);
         if (e) return fail(c, MRT_ERR_HIP, "temporal clamp launch failed: %s", hipGetErrorString((hipError_t)e));
-    } else {
-        e = mrt::launch_temporal_reproject(a, c->stream);
-        if (e) return fail(c, MRT_ERR_HIP, "temporal reprojection launch failed: %s", hipGetErrorString((hipError_t)e));
     }
     // "previous" from here on: the state at this step
     e = mrt::launch_temporal_snapshot(c->d_shade, c->d_prev_xyzr, c->n_spheres, c->stream);
@@ -542,26 +531,19 @@ int mrt_temporal_reset(mrt_ctx* c) {
 
 int mrt_read_temporal(mrt_ctx* c, float* out, size_t cap) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(temporal_check(c, "mrt_read_temporal", true));
-    const size_t n = (size_t)c->args.width * c->args.height * 4;
-    if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_read_temporal: need %zu floats", n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    MRT_TRY(queue_temporal_image(c));
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_den[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return mrt::wait_stream(c, c->stream, __func__);
+    return read_source(c, ImageSource::Temporal, __func__, out, cap);
 }
 
 int mrt_debug_read_temporal(mrt_ctx* c, float* h0, float* h1, float* prev_xyzr, size_t cap) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(temporal_check(c, "mrt_debug_read_temporal", false));
-    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal: no history buffers yet (mrt_temporal_step)");
+    MRT_TRY(history_io_opening(c, __func__, false));
     const size_t n = (size_t)c->args.width * c->args.height;
     if (cap < n || (prev_xyzr && cap < c->n_spheres)) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_temporal: need %zu pixels, %u spheres", n, c->n_spheres);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t cur = c->temporal_cur;
     if (c->temporal_clear) MRT_TRY(clear_history(c));       // (a dropped history reads as what the next step will see)
-    if (h0) HIP_TRY(c, hipMemcpyAsync(h0, c->d_den[3 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
-    if (h1) HIP_TRY(c, hipMemcpyAsync(h1, c->d_den[4 + 2 * cur], n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (h0) HIP_TRY(c, hipMemcpyAsync(h0, c->den.h0(cur), n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (h1) HIP_TRY(c, hipMemcpyAsync(h1, c->den.h1(cur), n * 16, hipMemcpyDeviceToHost, c->stream));
     if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(prev_xyzr, c->d_prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyDeviceToHost, c->stream));
     return mrt::wait_stream(c, c->stream, __func__);
 }
@@ -569,18 +551,14 @@ int mrt_debug_read_temporal(mrt_ctx* c, float* h0, float* h1, float* prev_xyzr, 
 int mrt_debug_load_temporal(mrt_ctx* c, const float* h0, const float* h1, const float* prev_xyzr, size_t n_spheres,
                             const mrt_camera_raw* prev_cam) {
     if (!c) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(temporal_check(c, "mrt_debug_load_temporal", false));
-    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal: no history buffers yet (mrt_temporal_step)");
+    MRT_TRY(history_io_opening(c, __func__, false));
     if (prev_xyzr && n_spheres != c->n_spheres) return fail(c, MRT_ERR_INVALID_ARG, "mrt_debug_load_temporal: %zu spheres for a scene of %u", n_spheres, c->n_spheres);
     const size_t n = (size_t)c->args.width * c->args.height;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t cur = c->temporal_cur;
-    if (c->temporal_clear && !h0) HIP_TRY(c, hipMemsetAsync(c->d_den[3 + 2 * cur], 0, n * 16, c->stream));
-    if (c->temporal_clear && c->temporal_response.enabled) HIP_TRY(c, hipMemsetAsync(c->d_den[7 + cur], 0, n * 16, c->stream));
-    if (c->temporal_clear && !prev_cam) c->temporal_prev_cam = c->cam_raw;
-    c->temporal_clear = false;
-    if (h0) HIP_TRY(c, hipMemcpyAsync(c->d_den[3 + 2 * cur], h0, n * 16, hipMemcpyHostToDevice, c->stream));
-    if (h1) HIP_TRY(c, hipMemcpyAsync(c->d_den[4 + 2 * cur], h1, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (c->temporal_clear) MRT_TRY(clear_history(c, !h0, !prev_cam));       // (only where the caller brings nothing in its place)
+    if (h0) HIP_TRY(c, hipMemcpyAsync(c->den.h0(cur), h0, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (h1) HIP_TRY(c, hipMemcpyAsync(c->den.h1(cur), h1, n * 16, hipMemcpyHostToDevice, c->stream));
     if (prev_xyzr && c->n_spheres) HIP_TRY(c, hipMemcpyAsync(c->d_prev_xyzr, prev_xyzr, (size_t)c->n_spheres * 16, hipMemcpyHostToDevice, c->stream));
     MRT_TRY(mrt::wait_stream(c, c->stream, __func__));      // (the caller's arrays are pageable: theirs again on return)
     if (prev_cam) c->temporal_prev_cam = *prev_cam;
@@ -590,26 +568,22 @@ int mrt_debug_load_temporal(mrt_ctx* c, const float* h0, const float* h1, const 
 
 int mrt_debug_read_temporal_fast(mrt_ctx* c, float* h2, size_t cap) {
     if (!c || !h2) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(temporal_check(c, "mrt_debug_read_temporal_fast", false));
-    if (!c->temporal_response.enabled) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal_fast: the response is off (mrt_set_temporal_response)");
-    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_read_temporal_fast: no history buffers yet (mrt_temporal_step)");
+    MRT_TRY(history_io_opening(c, __func__, true));
     const size_t n = (size_t)c->args.width * c->args.height;
     if (cap < n) return fail(c, MRT_ERR_TOO_SMALL, "mrt_debug_read_temporal_fast: need %zu pixels", n);
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->temporal_clear) MRT_TRY(clear_history(c));
-    HIP_TRY(c, hipMemcpyAsync(h2, c->d_den[7 + c->temporal_cur], n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h2, c->den.h2(c->temporal_cur), n * 16, hipMemcpyDeviceToHost, c->stream));
     return mrt::wait_stream(c, c->stream, __func__);
 }
 
 int mrt_debug_load_temporal_fast(mrt_ctx* c, const float* h2) {
     if (!c || !h2) return MRT_ERR_INVALID_ARG;
-    MRT_TRY(temporal_check(c, "mrt_debug_load_temporal_fast", false));
-    if (!c->temporal_response.enabled) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal_fast: the response is off (mrt_set_temporal_response)");
-    if (!have_history_buffers(c)) return fail(c, MRT_ERR_STATE, "mrt_debug_load_temporal_fast: no history buffers yet (mrt_temporal_step)");
+    MRT_TRY(history_io_opening(c, __func__, true));
     const size_t n = (size_t)c->args.width * c->args.height;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->temporal_clear) MRT_TRY(clear_history(c));
-    HIP_TRY(c, hipMemcpyAsync(c->d_den[7 + c->temporal_cur], h2, n * 16, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->den.h2(c->temporal_cur), h2, n * 16, hipMemcpyHostToDevice, c->stream));
     MRT_TRY(mrt::wait_stream(c, c->stream, __func__));      // (the caller's array is pageable: theirs again on return)
     c->temporal_stepped = true;
     return MRT_OK;

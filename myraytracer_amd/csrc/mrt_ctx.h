@@ -10,6 +10,41 @@
 #include "mrt_internal.h"
 #include "width_policy.h"
 
+namespace mrt {
+// free device / pinned allocations (those there are) and forget them
+template <typename... T> void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
+template <typename T> void free_pinned(T*& p) { if (p) (void)hipHostFree(p); p = nullptr; }
+
+// The filter's buffers (denoise.cpp), a float4 per pixel each, in the order they are allocated: ping, pong and the denoised frame;
+// with temporal reprojection on also the history, H0 and H1 of pair 0 and of pair 1; with its response on as well the fast
+// history, H2 of pair 0 and of pair 1.  The only place that knows which index is what.
+struct DenoiseBuffers {
+    float* buf[9] = {};
+    float* ping() const { return buf[0]; }
+    float* pong() const { return buf[1]; }
+    float* out() const { return buf[2]; }
+    float* h0(uint32_t pair) const { return buf[3 + 2 * pair]; }
+    float* h1(uint32_t pair) const { return buf[4 + 2 * pair]; }
+    float* h2(uint32_t pair) const { return buf[7 + pair]; }
+    // how many of them a denoise needs: buf[0, wanted), allocated in this order
+    static size_t wanted(bool temporal_on, bool response_on) { return !temporal_on ? 3 : response_on ? 9 : 7; }
+    bool have_filter() const { return buf[0] && buf[1] && buf[2]; }
+    // all / any of the history's four (fast: of the fast history's two); all that a step needs
+    bool all_history(bool fast) const { return fast ? buf[7] && buf[8] : buf[3] && buf[4] && buf[5] && buf[6]; }
+    bool any_history(bool fast) const { return fast ? buf[7] || buf[8] : buf[3] || buf[4] || buf[5] || buf[6]; }
+    bool have_history(bool response_on) const { return all_history(false) && (!response_on || all_history(true)); }
+    void free_history() { free_device(buf[3], buf[4], buf[5], buf[6], buf[7], buf[8]); }
+    void free_all() { free_device(buf[0], buf[1], buf[2]); free_history(); }
+};
+
+// What mrt_present shows and the float read-backs return: one definition per source (denoise.cpp: source_check, source_queue;
+// present.cpp: the flag bits).  Accumulated and Gathered are present-only in this table: their read-backs, mrt_read_framebuffer
+// and mrt_read_gathered, deal with shards and packed rows (read_rows), which the other three never see.
+enum class ImageSource { Accumulated, Gathered, Denoised, Temporal, GatheredDenoised };
+// a source's image once queued: `rows` rows of the image's width, and the frame count the image shows
+struct SourceImage { const float* img; uint32_t rows, frames_done; };
+}  // namespace mrt
+
 struct mrt_ctx {
     int device = 0;
     mrt_args args{};
@@ -260,13 +295,11 @@ struct mrt_ctx {
     size_t guide_cand_words = 0;
     uint32_t* d_guide_queue = nullptr;              // the DBG launch's tile queue counter
     float* d_guides = nullptr;                      // 2 float4 per pixel
-    // ping, pong, the denoised frame; with temporal reprojection on also the history, H0 and H1 of pair 0 and of pair 1, and with
-    // its response on as well H2 of pair 0 and of pair 1: a float4 per pixel each
-    float* d_den[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    mrt::DenoiseBuffers den;                        // the filter's buffers and the temporal history's
 
     // temporal reprojection (mrt_set_temporal / mrt_temporal_step / mrt_read_temporal, denoise.cpp; temporal.hip): the history
-    // the next step reads is pair temporal_cur (d_den[3 + 2 cur] = H0, d_den[4 + 2 cur] = H1), the step writes the other pair and
-    // swaps.  temporal_clear: the pair to read holds nothing valid (just allocated, or the history was dropped): the next step
+    // the next step reads is pair temporal_cur (den.h0(cur), den.h1(cur)), the step writes the other pair and swaps.
+    // temporal_clear: the pair to read holds nothing valid (just allocated, or the history was dropped): the next step
     // zeroes its H0 first.  temporal_stepped: a step since then (what the reads need).  "Previous": the spheres' (cx, cy, cz, r)
     // at the last step, a scene buffer (mrt_set_world_raw makes it, free_world frees it), and the derived camera.
     bool temporal_on = false;
@@ -275,7 +308,7 @@ struct mrt_ctx {
     bool temporal_clear = true, temporal_stepped = false;
     float* d_prev_xyzr = nullptr;
     mrt_camera_raw temporal_prev_cam{};
-    // the response (mrt_set_temporal_response): the fast history H2 of pair p is d_den[7 + p]; zeroed with H0 where the history
+    // the response (mrt_set_temporal_response): the fast history H2 of pair p is den.h2(p); zeroed with H0 where the history
     // was dropped
     mrt_temporal_response temporal_response = mrt::temporal_response_defaults();
 
@@ -340,10 +373,6 @@ inline uint64_t oldest_noise_report(const mrt_ctx* c) {
 inline size_t gathered_colour_bytes(const mrt_ctx* c) { return local_texels(c) * c->shard_world * 4 * sizeof(float); }
 inline float* gathered_noise(const mrt_ctx* c) { return c->d_gather + gathered_colour_bytes(c) / sizeof(float); }
 
-// free device / pinned allocations (those there are) and forget them
-template <typename... T> void free_device(T*&... p) { ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...); }
-template <typename T> void free_pinned(T*& p) { if (p) (void)hipHostFree(p); p = nullptr; }
-
 // Bounded host waits (api.cpp): poll the event / stream until it is complete or the context's deadline has passed; `what`
 // names the wait in the error message.  Return an mrt_status.
 int wait_event(mrt_ctx* c, hipEvent_t ev, const char* what);
@@ -372,19 +401,20 @@ int alloc_noise_set(mrt_ctx* c, uint32_t local_bands, float** s, float** tiles, 
 // ... and adaptive sampling's device tables K(n), n < k_len, grown to at least `len` entries (a per-tile noise report's and a
 // per-tile denoise's: both read d_k_f32 on the ctx's stream, which is drained once before a larger table replaces the old one)
 int ensure_k_table(mrt_ctx* c, uint32_t len);
-// denoise.cpp: the denoiser's buffers released; its part of mrt_present (present.cpp): the refusals; the denoise queued, *src = its output
+// denoise.cpp: the denoiser's buffers released; the temporal history dropped (mrt_set_world*, mrt_set_shard: nothing queued,
+// nothing freed)
 void free_denoise_buffers(mrt_ctx* c);
-int present_denoised_check(mrt_ctx* c);
-int present_denoised(mrt_ctx* c, const float** src);
-// ... the same two for the temporal image, and the history dropped (mrt_set_world*, mrt_set_shard: nothing queued, nothing freed)
-int present_temporal_check(mrt_ctx* c);
-int present_temporal(mrt_ctx* c, const float** src);
 void drop_temporal_history(mrt_ctx* c);
-// ... and for the gathered frame's denoise (mrt_read_gathered_denoised's refusals; the guides over the full image, then the filter)
-// (multi_gpu.cpp: is there a gathered S -- MRT_ERR_STATE before the first gather and when the latest carried none)
+// ... and the image sources, for mrt_present and the float read-backs.  source_check: the refusals of the state, before any
+// runtime call (`who`: the entry point, for the messages); source_rows: a shard's own accumulation is its packed rows;
+// source_queue: what the source needs queued on the ctx's stream (nothing, or the guides where stale and a filter), and the result
+int source_check(mrt_ctx* c, ImageSource source, const char* who);
+inline uint32_t source_rows(const mrt_ctx* c, ImageSource source) {
+    return source == ImageSource::Accumulated && c->shard_world > 1 ? c->local_bands * kBandRows : c->args.height;
+}
+int source_queue(mrt_ctx* c, ImageSource source, SourceImage* out);
+// multi_gpu.cpp: is there a gathered S -- MRT_ERR_STATE before the first gather and when the latest carried none
 int gathered_noise_check(mrt_ctx* R, const char* who);
-int present_gathered_denoised_check(mrt_ctx* c);
-int present_gathered_denoised(mrt_ctx* c, const float** src);
 
 }  // namespace mrt
 

@@ -4,7 +4,7 @@
 
 #include "mrt_ctx.h"
 
-using mrt::fail, mrt::local_texels;
+using mrt::fail, mrt::ImageSource, mrt::local_texels;
 
 // ---- present pass (include/myraytracer_amd.h, "present pass") -------------------------------------------------------------
 // mrt_present queues, on the ctx's stream right behind the most recent frame's blend, the present kernel (present.hip) into a
@@ -128,6 +128,27 @@ uint32_t present_pixel_bytes(int format) {
     return format == MRT_PRESENT_RGBA16F_LINEAR ? 8u : format == MRT_PRESENT_RGBA32F_LINEAR ? 16u : 0u;
 }
 
+// The source a flag word names (FLIP_Y is no source).  The rule is "at most one source bit", and the table's order gives the
+// refusals: of a word with several, the second in this order is refused, with that source's own reason why it is none of those
+// before it.  A new source is one more row and one more reason.
+int source_of_flags(mrt_ctx* c, uint32_t flags, ImageSource* out) {
+    static constexpr struct { uint32_t bit; ImageSource source; } kSources[] = {
+        {MRT_PRESENT_GATHERED, ImageSource::Gathered}, {MRT_PRESENT_DENOISED, ImageSource::Denoised},
+        {MRT_PRESENT_TEMPORAL, ImageSource::Temporal}, {MRT_PRESENT_GATHERED_DENOISED, ImageSource::GatheredDenoised}};
+    uint32_t known = MRT_PRESENT_FLIP_Y;
+    for (const auto& s : kSources) known |= s.bit;
+    if (flags & ~known) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
+    *out = ImageSource::Accumulated;
+    for (const auto& s : kSources) {
+        if (!(flags & s.bit)) continue;
+        if (*out == ImageSource::Accumulated) { *out = s.source; continue; }
+        if (s.source == ImageSource::Denoised) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the gathered frame cannot be denoised (it has no S)");
+        if (s.source == ImageSource::Temporal) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the temporal image is neither the gathered nor the denoised frame (flags 0x%x)", flags);
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the denoised gathered frame is a source of its own (flags 0x%x: with FLIP_Y only)", flags);
+    }
+    return MRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -136,38 +157,13 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     if (!c) return MRT_ERR_INVALID_ARG;
     const uint32_t pixel_bytes = present_pixel_bytes(format);
     if (!pixel_bytes) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: format %d", format);
-    if (flags & ~(uint32_t)(MRT_PRESENT_FLIP_Y | MRT_PRESENT_GATHERED | MRT_PRESENT_DENOISED | MRT_PRESENT_TEMPORAL | MRT_PRESENT_GATHERED_DENOISED))
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
-    const bool gathered = (flags & MRT_PRESENT_GATHERED) != 0, denoised = (flags & MRT_PRESENT_DENOISED) != 0;
-    const bool temporal = (flags & MRT_PRESENT_TEMPORAL) != 0;
-    if (gathered && denoised) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the gathered frame cannot be denoised (it has no S)");
-    if (temporal && (gathered || denoised))
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the temporal image is neither the gathered nor the denoised frame (flags 0x%x)", flags);
-    const bool gathered_denoised = (flags & MRT_PRESENT_GATHERED_DENOISED) != 0;
-    if (gathered_denoised && (gathered || denoised || temporal))
-        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the denoised gathered frame is a source of its own (flags 0x%x: with FLIP_Y only)", flags);
-    if (denoised) MRT_TRY(mrt::present_denoised_check(c));
-    if (gathered_denoised) MRT_TRY(mrt::present_gathered_denoised_check(c));
-    if (temporal) MRT_TRY(mrt::present_temporal_check(c));
-    const uint32_t width = c->args.width;
-    const float* src;
-    uint32_t rows;
-    if (denoised || temporal || gathered_denoised) {
-        src = nullptr;              // (queued below, right before the encode)
-        rows = c->args.height;
-    } else if (gathered) {
-        if (!c->d_gather) return fail(c, MRT_ERR_STATE, "mrt_present: nothing gathered yet (mrt_gather / mrt_gather_rccl on the root)");
-        src = c->d_gather;
-        rows = c->args.height;
-        if (c->gather_bytes < (size_t)rows * width * 16) return fail(c, MRT_ERR_STATE, "mrt_present: the gathered frame is smaller than the image");
-    } else if (c->shard_world > 1) {
-        if (flags & MRT_PRESENT_FLIP_Y) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: a shard's packed rows cannot be flipped (gather them first)");
-        src = c->d_fb[c->target ^ 1];
-        rows = c->local_bands * mrt::kBandRows;
-    } else {
-        src = c->d_fb[c->target ^ 1];
-        rows = c->args.height;
-    }
+    ImageSource source;
+    MRT_TRY(source_of_flags(c, flags, &source));
+    MRT_TRY(mrt::source_check(c, source, "mrt_present"));
+    // (the one refusal of a source that stays here: it is FLIP_Y's, and source_check sees the state alone, not the flags)
+    if (source == ImageSource::Accumulated && c->shard_world > 1 && (flags & MRT_PRESENT_FLIP_Y))
+        return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: a shard's packed rows cannot be flipped (gather them first)");
+    const uint32_t width = c->args.width, rows = mrt::source_rows(c, source);
     // (an image larger than the ring's entries -- a larger source, or a wider format than any presented so far -- regrows them)
     const size_t bytes = (size_t)rows * width * pixel_bytes;
     if (bytes == 0) return fail(c, MRT_ERR_STATE, "mrt_present: empty image");
@@ -178,13 +174,12 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     MRT_TRY(present_pick(c, &i));
     PresentEntry& E = c->present_ring[i];
     E.state = PresentEntry::kFree;
-    if (denoised) MRT_TRY(mrt::present_denoised(c, &src));
-    if (temporal) MRT_TRY(mrt::present_temporal(c, &src));
-    if (gathered_denoised) MRT_TRY(mrt::present_gathered_denoised(c, &src));
+    mrt::SourceImage S;
+    MRT_TRY(mrt::source_queue(c, source, &S));
     const uint32_t flip = (flags & MRT_PRESENT_FLIP_Y) ? 1u : 0u;
-    const int e = pixel_bytes == 4 ? mrt::launch_present(src, E.d_img, width, rows, flip, format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u,
+    const int e = pixel_bytes == 4 ? mrt::launch_present(S.img, E.d_img, width, rows, flip, format == MRT_PRESENT_BGRA8_SRGB ? 1u : 0u,
                                                          c->d_present_tables, c->stream)
-                                   : mrt::launch_present_float(src, E.d_img, width, rows, flip, pixel_bytes == 8 ? 1u : 0u, c->stream);
+                                   : mrt::launch_present_float(S.img, E.d_img, width, rows, flip, pixel_bytes == 8 ? 1u : 0u, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "present launch failed: %s", hipGetErrorString((hipError_t)e));
     hipStream_t copy_stream = c->stream;
     if (c->present_copy_mode == 0) {
@@ -199,7 +194,7 @@ int mrt_present(mrt_ctx* c, int format, uint32_t flags) {
     HIP_TRY(c, hipEventRecord(E.copied, copy_stream));
     E.info = mrt_present_info{};
     E.info.seq = ++c->present_seq;
-    E.info.frames_done = gathered_denoised ? c->gather_frames : c->frames_done;      // (the gather's snapshot: what the image shows)
+    E.info.frames_done = S.frames_done;
     E.info.width = width; E.info.rows = rows; E.info.row_bytes = width * pixel_bytes;
     E.info.format = (uint32_t)format; E.info.flags = flags;
     E.state = PresentEntry::kQueued;
