@@ -52,7 +52,8 @@ extern "C" {
  * budget (MRT_TILE_MAP_MAX_REL, MRT_TILE_MAP_SUM_S, mrt_noise_query_map, mrt_budget_result, mrt_budget_allocate,
  * mrt_render_budget; mrt_noise_report::reserved carries the report's map kind); budget allocation on the device
  * (mrt_noise_query_budget, mrt_read_budget_plan, mrt_render_planned); the present pass's linear formats
- * (MRT_PRESENT_RGBA16F_LINEAR, MRT_PRESENT_RGBA32F_LINEAR, mrt_half_bits, mrt_half_from_floats). */
+ * (MRT_PRESENT_RGBA16F_LINEAR, MRT_PRESENT_RGBA32F_LINEAR, mrt_half_bits, mrt_half_from_floats); the diagnostic views
+ * (mrt_view, MRT_VIEW_*, mrt_view_default, mrt_set_view, mrt_get_view, mrt_read_view, MRT_PRESENT_VIEW). */
 #define MRT_ABI_VERSION 4
 
 typedef enum {
@@ -465,6 +466,8 @@ enum {
 #define MRT_PRESENT_TEMPORAL 16u
 /* the latest gathered frame, denoised on the root (mrt_read_gathered_denoised's image; "multi-GPU" below) */
 #define MRT_PRESENT_GATHERED_DENOISED 32u
+/* the current diagnostic view (mrt_read_view's image; "diagnostic views" below); 4 and 64 stay undefined */
+#define MRT_PRESENT_VIEW 128u
 enum { MRT_ACQUIRE_NEWEST = 0, MRT_ACQUIRE_OLDEST = 1 };
 typedef struct {               /* 40 bytes */
     uint64_t seq;              /* the present's number on this ctx: 1, 2, ... */
@@ -484,7 +487,9 @@ typedef struct {               /* 40 bytes */
  * DENOISED | GATHERED: MRT_ERR_INVALID_ARG); TEMPORAL, the `height` rows of the temporal image, queued the same way (refusals as
  * mrt_read_temporal's; TEMPORAL | DENOISED and TEMPORAL | GATHERED: MRT_ERR_INVALID_ARG); GATHERED_DENOISED, the `height` rows of
  * the latest gathered frame denoised on the root, queued the same way (refusals as mrt_read_gathered_denoised's; with FLIP_Y only:
- * together with GATHERED, DENOISED or TEMPORAL it is MRT_ERR_INVALID_ARG; mrt_present_info::frames_done is then the gather's).
+ * together with GATHERED, DENOISED or TEMPORAL it is MRT_ERR_INVALID_ARG; mrt_present_info::frames_done is then the gather's);
+ * VIEW, the `height` rows of the current diagnostic view, queued the same way (refusals as mrt_read_view's; with FLIP_Y only:
+ * together with any other source it is MRT_ERR_INVALID_ARG).
  * Must not be called while the ctx's stream is being captured into a graph. */
 int mrt_present(mrt_ctx* ctx, int format, uint32_t flags);
 /* A finished image: *pixels = rows x row_bytes bytes, valid until mrt_present_release, the next acquire, mrt_reset,
@@ -974,6 +979,62 @@ void mrt_temporal_response_default(mrt_temporal_response* out);
 /* ctx NULL: checks the setting only (host only). */
 int mrt_set_temporal_response(mrt_ctx* ctx, const mrt_temporal_response* response);
 int mrt_get_temporal_response(mrt_ctx* ctx, mrt_temporal_response* out);
+
+/* ------------------------------------------------------------------ diagnostic views (no reference counterpart)
+ *
+ * What the renderer decides by, as pictures: the per-pixel noise estimate that stops a render and picks adaptive tiles, the per-tile
+ * frame count n_t that shows where adaptive and budget sampling spent their frames, and the first-hit guides that drive the
+ * denoiser and the temporal reprojection.  A view is an RGBA32F image the size of the frame, computed by one kernel (views.hip) on
+ * the ctx's stream, behind the newest blend and with no host wait, from buffers the context already holds, into the denoised
+ * frame's buffer.  It is one more image source: mrt_present(.., flags | MRT_PRESENT_VIEW) shows it in any format, with FLIP_Y,
+ * through the ring, and mrt_read_view returns its floats.  World 1 only (a view is image-sized and the guides are unsharded).
+ *
+ * The definition.  Everything is float32, in the stated order, for pixel p of tile t (8 x 8 pixels).  Scalar kinds give a value q:
+ *   NOISE_SE, NOISE_REL  With s = S_p and L = lum(framebuffer_p), as the noise report has them ("noise estimate"): if s or L is not
+ *                finite, q is a NaN.  Otherwise se = isinf(K_p) ? +inf : sqrtf(s * K_p) and rel = se / fmaxf(L, rel_floor); q is se or
+ *                rel.  K_p: for a uniform accumulation, (float) of the factor a noise report queried at this point of the stream
+ *                carries; for an adaptive accumulation (mrt_render_tiles since the last reset), (float)mrt_noise_factor(n_t, max_w)
+ *                of the pixel's tile.  An adaptive accumulation is not refused: showing it is the point.
+ *   TILE_FRAMES  q = (float)n_t; while the accumulation is uniform, (float)mrt_frames_done.
+ *   DEPTH        q = the distance t of the first hit along the pixel's centre ray, +inf on a miss.
+ * A scalar is mapped by u = (q - lo) * inv, with inv = 1.0f / (hi - lo) computed once on the host:
+ *   GREY   rgb = (u, u, u), not clamped: with lo 0 and hi 1 the float formats return q bit for bit for every non-NaN q.
+ *   HEAT   a NaN q gives (1, 0, 1).  Otherwise v = fminf(fmaxf(u, 0), 1), x = v * 4.0f, r = c01(x - 2), g = c01(fminf(x, 4 - x)),
+ *          b = c01(2 - x) with c01(y) = fminf(fmaxf(y, 0), 1): blue, cyan, green, yellow, red, and +inf is red (hi > lo).
+ * Vector kinds ignore ramp, lo and hi (which are validated all the same):
+ *   NORMAL  rgb = n * 0.5f + 0.5f per component of the first hit's unit normal (a miss: the guide's normal as it is).
+ *   ALBEDO  rgb = the bits of the first hit's albedo as the denoiser's guides hold it (a Dielectric reads (1, 1, 1)).
+ *   SPHERE  for the first hit's sphere index i: a miss (-1) gives (0, 0, 0); otherwise h = (uint32_t)(i + 1) * 2654435761u, then
+ *           h ^= h >> 15, r = ((float)(h >> 24) + 0.5f) * (1.0f / 256.0f), g the same of bits 16..23 and b of bits 8..15.
+ * Alpha is 1.0f in every view.  Every operation above except the report's own sqrtf and / is exact or a single rounding in
+ * float32, so nothing depends on contraction.
+ *
+ * The guide kinds rebuild stale guides first (after mrt_set_camera, mrt_set_world*, mrt_update_spheres / _materials), as a denoise
+ * does.  A view's buffers are the denoiser's, allocated at the first view or denoise, whichever comes first; a view changes no
+ * accumulation, no S, no tile map and no counter, and the next denoise or view overwrites its image. */
+enum { MRT_VIEW_NOISE_SE = 1, MRT_VIEW_NOISE_REL = 2, MRT_VIEW_TILE_FRAMES = 3, MRT_VIEW_DEPTH = 4,
+       MRT_VIEW_NORMAL = 5, MRT_VIEW_ALBEDO = 6, MRT_VIEW_SPHERE = 7 };
+enum { MRT_VIEW_RAMP_GREY = 0, MRT_VIEW_RAMP_HEAT = 1 };
+typedef struct {            /* sizeof 32 */
+    uint32_t size;          /* sizeof(mrt_view): the version of this struct */
+    uint32_t kind;          /* MRT_VIEW_* (default NOISE_REL) */
+    uint32_t ramp;          /* MRT_VIEW_RAMP_* (default HEAT) */
+    float    lo, hi;        /* finite, hi != lo, 1.0f / (hi - lo) finite; hi < lo reverses the ramp (default 0 and 0.1) */
+    float    rel_floor;     /* finite, >= 0: NOISE_REL's floor under the luminance (default 0.01) */
+    uint32_t reserved[2];   /* 0 */
+} mrt_view;
+/* Host only: the defaults. */
+void mrt_view_default(mrt_view* out);
+/* Anything out of range, size or reserved wrong: MRT_ERR_INVALID_ARG with nothing changed.  ctx NULL: checks v only (host only).
+ * The setting creates nothing, takes effect at the next view and survives mrt_reset, mrt_set_shard, mrt_set_world* and
+ * mrt_set_camera. */
+int mrt_set_view(mrt_ctx* ctx, const mrt_view* v);
+int mrt_get_view(mrt_ctx* ctx, mrt_view* out);
+/* Computes the current view of the most recent frame (queued on the ctx's stream behind its blend) and reads it back: height *
+ * width * 4 floats, row 0 = bottom; synchronises as mrt_read_denoised does.  Refused, in this order and before any runtime call
+ * (MRT_PRESENT_VIEW alike): MRT_ERR_STATE on a shard (world > 1), MRT_ERR_NO_SCENE without a scene, MRT_ERR_STATE for an empty
+ * image, MRT_ERR_STATE for a NOISE_* kind with noise tracking off. */
+int mrt_read_view(mrt_ctx* ctx, float* rgba_out, size_t cap_floats);
 
 /* ------------------------------------------------------------------ multi-GPU (no reference counterpart)
  *

@@ -60,13 +60,20 @@ EXPORTS = [
     "mrt_debug_hold", "mrt_debug_hold_stamps",
     "mrt_noise_query_map", "mrt_budget_allocate", "mrt_render_budget",
     "mrt_noise_query_budget", "mrt_read_budget_plan", "mrt_render_planned", "mrt_debug_budget_plan",
+    "mrt_view_default", "mrt_set_view", "mrt_get_view", "mrt_read_view",
 ]
 
 # the present pass (include/myraytracer_amd.h)
 PRESENT_RGBA8_SRGB, PRESENT_BGRA8_SRGB = 1, 2
 PRESENT_RGBA16F_LINEAR, PRESENT_RGBA32F_LINEAR = 16, 32
 PRESENT_FLIP_Y, PRESENT_GATHERED, PRESENT_DENOISED, PRESENT_TEMPORAL, PRESENT_GATHERED_DENOISED = 1, 2, 8, 16, 32
+PRESENT_VIEW = 128
 ACQUIRE_NEWEST, ACQUIRE_OLDEST = 0, 1
+# the diagnostic views (mrt_set_view): MRT_VIEW_* by name, and the ramps
+VIEW_NOISE_SE, VIEW_NOISE_REL, VIEW_TILE_FRAMES, VIEW_DEPTH, VIEW_NORMAL, VIEW_ALBEDO, VIEW_SPHERE = 1, 2, 3, 4, 5, 6, 7
+VIEW_KINDS = {"noise_se": 1, "noise_rel": 2, "tile_frames": 3, "depth": 4, "normal": 5, "albedo": 6, "sphere": 7}
+VIEW_RAMP_GREY, VIEW_RAMP_HEAT = 0, 1
+VIEW_RAMPS = {"grey": 0, "heat": 1}
 # how a slot's tile queue was ordered (mrt_debug_read_tile_schedule, MRT_TILE_ORDER_*)
 TILE_ORDER_KINDS = ("none", "index", "sorted", "sorted-list", "list")
 # the denoiser's variance modes (mrt_set_denoise_variance)
@@ -142,6 +149,11 @@ class MrtDenoiseParams(C.Structure):
 
 class MrtDenoiseMix(C.Structure):
     _fields_ = [("size", C.c_uint32), ("enabled", C.c_uint32), ("gain", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
+class MrtView(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("kind", C.c_uint32), ("ramp", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float),
+                ("rel_floor", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
 class MrtTemporalParams(C.Structure):
@@ -446,6 +458,10 @@ def load():
         "mrt_debug_hold": (i32, [vp, u32, u32, u64, u32]),
         "mrt_debug_hold_stamps": (i32, [vp, P(u64)]),
         "mrt_debug_budget_plan": (i32, [vp, vp, vp, u32, sz, C.c_uint64, u32, vp, P(MrtBudgetResult)]),
+        "mrt_view_default": (None, [P(MrtView)]),
+        "mrt_set_view": (i32, [vp, P(MrtView)]),
+        "mrt_get_view": (i32, [vp, P(MrtView)]),
+        "mrt_read_view": (i32, [vp, vp, sz]),
     }
     assert sorted(sig) == sorted(EXPORTS)
     for name, (res, args) in sig.items():

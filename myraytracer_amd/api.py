@@ -787,17 +787,18 @@ class State:
     _PRESENT_DTYPES = {_lib.PRESENT_RGBA16F_LINEAR: np.float16, _lib.PRESENT_RGBA32F_LINEAR: np.float32}
 
     def present(self, fmt: str = "rgba8", flip: bool = True, gathered: bool = False, denoise: bool = False, temporal: bool = False,
-                gathered_denoised: bool = False):
+                gathered_denoised: bool = False, view: bool = False):
         """mrt_present: queue the most recent frame's image: 8-bit sRGB ("rgba8" / "bgra8") or linear ("rgba16f": binary16,
         _lib.half_bits of every channel; "rgba32f": the source's float32 bits).  flip = rows top-down; gathered = the
         root's full frame of the last gather; denoise = the denoised frame, read_denoised's image; temporal = the temporal image,
         read_temporal's; gathered_denoised = the last gathered frame denoised on the root, read_gathered_denoised's image, a
-        source of its own: with flip only.  Asynchronous."""
+        source of its own: with flip only; view = the current diagnostic view (set_view), read_view's image, with flip only.
+        Asynchronous."""
         if fmt not in self._PRESENT_FORMATS:
             raise ValueError(f"present: format {fmt!r} ({', '.join(self._PRESENT_FORMATS)})")
         flags = ((_lib.PRESENT_FLIP_Y if flip else 0) | (_lib.PRESENT_GATHERED if gathered else 0) |
                  (_lib.PRESENT_DENOISED if denoise else 0) | (_lib.PRESENT_TEMPORAL if temporal else 0) |
-                 (_lib.PRESENT_GATHERED_DENOISED if gathered_denoised else 0))
+                 (_lib.PRESENT_GATHERED_DENOISED if gathered_denoised else 0) | (_lib.PRESENT_VIEW if view else 0))
         self._check(self._L.mrt_present(self._ctx, self._PRESENT_FORMATS[fmt], flags), "mrt_present")
 
     def acquire_presented(self, newest: bool = True, wait: bool = True, copy: bool = True):
@@ -1147,6 +1148,34 @@ class State:
         self._check(self._L.mrt_read_denoised(self._ctx, out.ctypes.data, out.size), "mrt_read_denoised")
         return out
 
+    # -- diagnostic views (include/myraytracer_amd.h, "diagnostic views"): the noise estimate, the per-tile frame counts and the
+    #    first-hit guides as an image, through read_view() or present(view=True)
+    def set_view(self, kind: str = "noise_rel", ramp: str = "heat", lo: float = 0.0, hi: float = 0.1, rel_floor: Optional[float] = None):
+        """mrt_set_view: what read_view() and present(view=True) show.  kind: "noise_se", "noise_rel", "tile_frames", "depth"
+        (scalars, mapped from lo..hi through ramp "grey" -- unclamped -- or "heat"), "normal", "albedo", "sphere".  rel_floor
+        None keeps the State's (the default is render_until's floor)."""
+        if kind not in _lib.VIEW_KINDS or ramp not in _lib.VIEW_RAMPS:
+            raise ValueError(f"set_view: kind {kind!r} ({', '.join(_lib.VIEW_KINDS)}), ramp {ramp!r} ({', '.join(_lib.VIEW_RAMPS)})")
+        p = _lib.MrtView()
+        self._check(self._L.mrt_get_view(self._ctx, C.byref(p)), "mrt_get_view")
+        p.kind, p.ramp, p.lo, p.hi = _lib.VIEW_KINDS[kind], _lib.VIEW_RAMPS[ramp], lo, hi
+        if rel_floor is not None:
+            p.rel_floor = rel_floor
+        self._check(self._L.mrt_set_view(self._ctx, C.byref(p)), "mrt_set_view")
+
+    def view(self) -> dict:
+        """The view as set_view left it: kind and ramp by name, lo, hi, rel_floor."""
+        p = _lib.MrtView()
+        self._check(self._L.mrt_get_view(self._ctx, C.byref(p)), "mrt_get_view")
+        return view_dict(p)
+
+    def read_view(self) -> np.ndarray:
+        """The current view of the most recent frame: (H, W, 4) f32, row 0 = bottom.  World 1 only; the noise kinds need noise
+        tracking; waits for the frames in flight, as read_denoised does."""
+        out = np.empty((self.args.height, self.args.width, 4), np.float32)
+        self._check(self._L.mrt_read_view(self._ctx, out.ctypes.data, out.size), "mrt_read_view")
+        return out
+
     def debug_read_guides(self) -> dict:
         """The denoiser's guides (rebuilt first if stale), row 0 = bottom: rays (H, W, 6), index (H, W) i32, t (H, W),
         normal (H, W, 3), albedo (H, W, 3)."""
@@ -1318,6 +1347,18 @@ def denoise_params_default() -> dict:
     p = _lib.MrtDenoiseParams()
     _lib.load().mrt_denoise_params_default(C.byref(p))
     return denoise_params_dict(p)
+
+
+def view_dict(p) -> dict:
+    kinds = {v: k for k, v in _lib.VIEW_KINDS.items()}
+    ramps = {v: k for k, v in _lib.VIEW_RAMPS.items()}
+    return {"kind": kinds[p.kind], "ramp": ramps[p.ramp], "lo": float(p.lo), "hi": float(p.hi), "rel_floor": float(p.rel_floor)}
+
+
+def view_default() -> dict:
+    p = _lib.MrtView()
+    _lib.load().mrt_view_default(C.byref(p))
+    return view_dict(p)
 
 
 def denoise_mix_default() -> dict:

@@ -38,6 +38,7 @@ static_assert(sizeof(mrt_auto_regroup) == 32 && sizeof(mrt_regroup_stats) == 72 
               offsetof(mrt_regroup_stats, levels) == 64, "mrt_auto_regroup / mrt_regroup_stats layout");
 static_assert(sizeof(mrt_present_info) == 40 && offsetof(mrt_present_info, frames_done) == 8 &&
               offsetof(mrt_present_info, ring_depth) == 36, "mrt_present_info layout");
+static_assert(sizeof(mrt_view) == 32 && offsetof(mrt_view, rel_floor) == 20, "mrt_view layout");
 
 using mrt::fail, mrt::free_device, mrt::free_pinned, mrt::local_texels, mrt::local_texels_min1, mrt::tiles_min1, mrt::total_bands, mrt::alloc_frame_buffers, mrt::free_world;
 

@@ -1,5 +1,6 @@
 // The denoiser and the temporal reprojection of include/myraytracer_amd.h: the first-hit guides, the filter (denoise.hip), the
-// history's step and image (temporal.hip), and what mrt_present and the float read-backs share of them (ImageSource, mrt_ctx.h).
+// history's step and image (temporal.hip), the diagnostic views (views.hip), which write the filter's output buffer, and what
+// mrt_present and the float read-backs share of them (ImageSource, mrt_ctx.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -157,6 +158,51 @@ int queue_denoise(mrt_ctx* c, bool gathered) {
                         variance_of(c->denoise_var_mode, gathered ? c->gather_frames : c->frames_done, c->denoise_spatial_frames)};
     const int e = mrt::launch_denoise(job, c->stream);
     if (e) return fail(c, MRT_ERR_HIP, "%sdenoise launch failed: %s", per_tile ? "per-tile " : "", hipGetErrorString((hipError_t)e));
+    return MRT_OK;
+}
+
+// ---- diagnostic views (include/myraytracer_amd.h, "diagnostic views") ------------------------------------------------------
+bool view_ok(const mrt_view* v) {
+    if (v->size != sizeof(mrt_view) || v->kind < MRT_VIEW_NOISE_SE || v->kind > MRT_VIEW_SPHERE || v->ramp > MRT_VIEW_RAMP_HEAT) return false;
+    if (!std::isfinite(v->lo) || !std::isfinite(v->hi) || v->hi == v->lo || !std::isfinite(1.0f / (v->hi - v->lo))) return false;
+    if (!(std::isfinite(v->rel_floor) && v->rel_floor >= 0.0f)) return false;
+    for (uint32_t r : v->reserved)
+        if (r != 0) return false;
+    return true;
+}
+
+bool view_reads_noise(const mrt_view& v) { return v.kind == MRT_VIEW_NOISE_SE || v.kind == MRT_VIEW_NOISE_REL; }
+
+// the refusals of a view, in the header's order
+int view_check(mrt_ctx* c, const char* who) {
+    if (c->shard_world != 1) return fail(c, MRT_ERR_STATE, "%s: a shard (world %u) has no views (a view is image-sized, the guides unsharded)", who, c->shard_world);
+    if (!c->have_world) return fail(c, MRT_ERR_NO_SCENE, "%s: no scene", who);
+    if ((size_t)c->args.width * c->args.height == 0) return fail(c, MRT_ERR_STATE, "%s: empty image", who);
+    if (view_reads_noise(c->view) && !c->noise_on) return fail(c, MRT_ERR_STATE, "%s: a noise view with noise tracking off (mrt_set_noise_tracking)", who);
+    return MRT_OK;
+}
+
+// The current view of the most recent frame into den.out() (after view_check), queued on the ctx's stream: a writer of den.out()
+// like the filter, behind the earlier readers and ahead of its own.  The noise kinds and TILE_FRAMES of a diverged accumulation
+// read the device's tile map, which is the host's at this point of the stream, and K per tile as queue_denoise does; a uniform
+// one reads neither (the map may not exist).  The guide kinds rebuild stale guides first.
+int queue_view(mrt_ctx* c) {
+    const mrt_view& v = c->view;
+    const bool noise = view_reads_noise(v), guides = v.kind >= MRT_VIEW_DEPTH;
+    const bool per_tile = (noise || v.kind == MRT_VIEW_TILE_FRAMES) && c->tiles_diverged;
+    if (per_tile && noise) MRT_TRY(mrt::ensure_k_table(c, mrt::most_tile_frames(c) + 1u));
+    if (guides) MRT_TRY(ensure_guides(c));
+    else MRT_TRY(ensure_denoise_buffers(c));
+    mrt::ViewArgs a{};
+    a.fb = c->d_fb[c->target ^ 1]; a.S = c->d_noise_s; a.guides = c->d_guides;
+    if (per_tile) { a.tile_frames = c->d_tile_frames; a.Kf = c->d_k_f32; }
+    a.out = c->den.out();
+    a.width = c->args.width; a.height = c->args.height; a.tiles_x = c->tiles_x;
+    a.kind = v.kind; a.ramp = v.ramp;
+    a.K = (float)mrt::noise_factor_of(c->noise_c2); a.frames = (float)c->frames_done;
+    a.lo = v.lo; a.inv = 1.0f / (v.hi - v.lo); a.rel_floor = v.rel_floor;
+    const int e = mrt::launch_view(a, c->stream);
+    if (e) return fail(c, MRT_ERR_HIP, "view launch failed: %s", hipGetErrorString((hipError_t)e));
     return MRT_OK;
 }
 
@@ -333,6 +379,7 @@ int source_check(mrt_ctx* c, ImageSource source, const char* who) {
         case ImageSource::Denoised: return denoise_check(c, who, true);
         case ImageSource::Temporal: return temporal_check(c, who, true);
         case ImageSource::GatheredDenoised: return gathered_denoise_check(c, who, true);
+        case ImageSource::View: return view_check(c, who);
         case ImageSource::Gathered:
             if (!c->d_gather) return fail(c, MRT_ERR_STATE, "%s: nothing gathered yet (mrt_gather / mrt_gather_rccl on the root)", who);
             if (c->gather_bytes < (size_t)c->args.height * c->args.width * 16) return fail(c, MRT_ERR_STATE, "%s: the gathered frame is smaller than the image", who);
@@ -345,6 +392,7 @@ int source_check(mrt_ctx* c, ImageSource source, const char* who) {
 int source_queue(mrt_ctx* c, ImageSource source, SourceImage* out) {
     if (source == ImageSource::Denoised || source == ImageSource::GatheredDenoised) MRT_TRY(queue_denoise(c, source == ImageSource::GatheredDenoised));
     if (source == ImageSource::Temporal) MRT_TRY(queue_temporal_image(c));
+    if (source == ImageSource::View) MRT_TRY(queue_view(c));
     // (den.out() is read behind the queue, which may allocate it; the frame count is what the image shows: the gather's snapshot)
     const float* img = source == ImageSource::Accumulated ? c->d_fb[c->target ^ 1] : source == ImageSource::Gathered ? c->d_gather : c->den.out();
     *out = {img, source_rows(c, source), source == ImageSource::GatheredDenoised ? c->gather_frames : c->frames_done};
@@ -532,6 +580,31 @@ int mrt_temporal_reset(mrt_ctx* c) {
 int mrt_read_temporal(mrt_ctx* c, float* out, size_t cap) {
     if (!c || !out) return MRT_ERR_INVALID_ARG;
     return read_source(c, ImageSource::Temporal, __func__, out, cap);
+}
+
+void mrt_view_default(mrt_view* out) {
+    if (out) *out = mrt::view_defaults();
+}
+
+int mrt_set_view(mrt_ctx* c, const mrt_view* v) {
+    if (!v) return MRT_ERR_INVALID_ARG;
+    if (!view_ok(v))
+        return !c ? (int)MRT_ERR_INVALID_ARG : fail(c, MRT_ERR_INVALID_ARG, "mrt_set_view: size %u (%zu), kind %u (1..7), ramp %u (0, 1), lo %g, hi %g (finite, "
+                    "hi != lo, 1 / (hi - lo) finite), rel_floor %g (finite, >= 0), reserved 0", v->size, sizeof(mrt_view), v->kind, v->ramp,
+                    v->lo, v->hi, v->rel_floor);
+    if (c) c->view = *v;                  // (ctx NULL: a check of the setting alone)
+    return MRT_OK;
+}
+
+int mrt_get_view(mrt_ctx* c, mrt_view* out) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    *out = c->view;
+    return MRT_OK;
+}
+
+int mrt_read_view(mrt_ctx* c, float* out, size_t cap) {
+    if (!c || !out) return MRT_ERR_INVALID_ARG;
+    return read_source(c, ImageSource::View, __func__, out, cap);
 }
 
 int mrt_debug_read_temporal(mrt_ctx* c, float* h0, float* h1, float* prev_xyzr, size_t cap) {

@@ -39,8 +39,9 @@ struct DenoiseBuffers {
 
 // What mrt_present shows and the float read-backs return: one definition per source (denoise.cpp: source_check, source_queue;
 // present.cpp: the flag bits).  Accumulated and Gathered are present-only in this table: their read-backs, mrt_read_framebuffer
-// and mrt_read_gathered, deal with shards and packed rows (read_rows), which the other three never see.
-enum class ImageSource { Accumulated, Gathered, Denoised, Temporal, GatheredDenoised };
+// and mrt_read_gathered, deal with shards and packed rows (read_rows), which the other four never see.  View: the current
+// diagnostic view (mrt_ctx::view), computed into den.out() as a denoise is.
+enum class ImageSource { Accumulated, Gathered, Denoised, Temporal, GatheredDenoised, View };
 // a source's image once queued: `rows` rows of the image's width, and the frame count the image shows
 struct SourceImage { const float* img; uint32_t rows, frames_done; };
 }  // namespace mrt
@@ -286,6 +287,7 @@ struct mrt_ctx {
     uint32_t denoise_spatial_frames = 3;                       // SPATIAL_EARLY: the spatial estimate while frames_done < this
     bool denoise_adaptive = false;                  // mrt_set_denoise_adaptive: a diverged accumulation is filtered per tile, not refused
     mrt_denoise_mix denoise_mix = mrt::denoise_mix_defaults();  // mrt_set_denoise_mix: the blend behind every denoise of an accumulation
+    mrt_view view = mrt::view_defaults();           // mrt_set_view: what mrt_read_view / MRT_PRESENT_VIEW compute (views.hip)
     bool guides_stale = true;
     float* d_guide_rays = nullptr;                  // 6 floats per pixel
     int32_t* d_guide_hits = nullptr;                // {sphere | -1, bits of t} per pixel (the DBG render kernel's output)

@@ -214,6 +214,30 @@ __host__ __device__ inline uint16_t half_bits(float v) {
     const uint32_t h = m >> shift, rem = m & ((1u << shift) - 1u), tie = 1u << (shift - 1u);
     return (uint16_t)(sign | (h + ((rem > tie || (rem == tie && (h & 1u))) ? 1u : 0u)));
 }
+// views.hip (include/myraytracer_amd.h, "diagnostic views"): view `kind` of width x height world-1 texels (y * width + x) into
+// `out`, RGBA32F.  Read per kind only: NOISE_* fb and S, with K the launch's (tile_frames null) or Kf[n_t] per tile; TILE_FRAMES
+// `frames` or (float)n_t; DEPTH / NORMAL / ALBEDO / SPHERE the guides (2 float4 per pixel, launch_guide_fill's).  inv: 1 / (hi - lo).
+struct ViewArgs {
+    const float* fb;
+    const float* S;
+    const float* guides;
+    const uint32_t* tile_frames;    // n_t per tile, tiles_x a row: a diverged accumulation (NOISE_*, TILE_FRAMES); else null
+    const float* Kf;                // K(n) as float for every n the map holds (NOISE_* per tile)
+    float* out;
+    uint32_t width, height, tiles_x;
+    uint32_t kind, ramp;
+    float K, frames;                // a uniform accumulation's K and (float)frames_done
+    float lo, inv, rel_floor;
+};
+int launch_view(const ViewArgs& a, void* stream);
+inline mrt_view view_defaults() {
+    mrt_view v{};
+    v.size = sizeof(mrt_view);
+    v.kind = MRT_VIEW_NOISE_REL; v.ramp = MRT_VIEW_RAMP_HEAT;
+    v.lo = 0.0f; v.hi = 0.1f;       // the README's "no pixel above 10 %"
+    v.rel_floor = 0.01f;            // State.render_until's floor
+    return v;
+}
 // image_io.cpp, host: {colour, alpha} x 256 thresholds -- t[k] = the smallest float whose code is >= k (t[0] = -inf)
 const float* present_thresholds();
 

@@ -27,7 +27,7 @@ static void usage() {
         "                     [--out FILE.pfm|FILE.ppm|FILE.png] [--device N | --gpus N | --devices a,b,...]\n"
                          "                     [--schedule div,mult] [--target-noise REL [--check-every N] [--adaptive | --budget N [--plan-on-device]]]\n"
         "                     [--denoise-out FILE [--denoise-variance accumulated|prefiltered|spatial-early[:N]] [--denoise-mix [GAIN]]]\n"
-        "                     [--snapshot-every N --snapshot-out PREFIX]\n"
+        "                     [--snapshot-every N --snapshot-out PREFIX] [--view KIND[:LO:HI[:RAMP]] --view-out FILE]\n"
         "  --target-noise REL: render until the noise estimate's relative RMSE is <= REL (--frames is then the cap), checking\n"
         "                      every --check-every frames (default 16); prints the final report\n"
         "  --adaptive:         with --target-noise (one GPU): every chunk after the first renders only the tiles the report one\n"
@@ -47,7 +47,11 @@ static void usage() {
         "                      (mrt_set_denoise_mix); GAIN 0.25 .. 16, default the library's\n"
         "  --snapshot-every N --snapshot-out PREFIX: (one GPU, not with --target-noise) the frames are queued N at a time and the\n"
         "                      accumulation after each N is written as PREFIX<frames done, 5 digits>.pfm: the exact floats, presented\n"
-        "                      through the ring (MRT_PRESENT_RGBA32F_LINEAR) without draining the frames in flight\n");
+        "                      through the ring (MRT_PRESENT_RGBA32F_LINEAR) without draining the frames in flight\n"
+        "  --view KIND[:LO:HI[:RAMP]] --view-out FILE: (one GPU) after the last frame, writes a diagnostic view (mrt_set_view /\n"
+        "                      mrt_read_view; .pfm / .ppm / .png): KIND noise_se | noise_rel | tile_frames | depth | normal | albedo |\n"
+        "                      sphere, a scalar kind mapped from LO..HI (default 0:0.1) through RAMP grey | heat (default heat); the\n"
+        "                      noise kinds turn noise tracking on\n");
 }
 
 int main(int argc, char** argv) {
@@ -66,7 +70,10 @@ int main(int argc, char** argv) {
     std::string snapshot_out;
     mrt_denoise_mix mix;
     mrt_denoise_mix_default(&mix);
-    std::string scene = "default", scene_file, save_scene, out, denoise_out;
+    std::string scene = "default", scene_file, save_scene, out, denoise_out, view_out;
+    mrt_view view;
+    mrt_view_default(&view);
+    bool have_view = false;
     std::vector<int> devices;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i], v;
@@ -111,6 +118,28 @@ int main(int argc, char** argv) {
                 spatial_frames = (uint32_t)std::strtoul(v.c_str() + colon + 1, nullptr, 10);
             }
         }
+        else if (a == "--view") {           // KIND[:LO:HI[:RAMP]]
+            static const char* const kinds[] = {"noise_se", "noise_rel", "tile_frames", "depth", "normal", "albedo", "sphere"};
+            std::vector<std::string> part;
+            for (size_t p0 = 0; p0 <= v.size();) {
+                const size_t p1 = v.find(':', p0) == std::string::npos ? v.size() : v.find(':', p0);
+                part.push_back(v.substr(p0, p1 - p0));
+                p0 = p1 + 1;
+            }
+            view.kind = 0;
+            for (uint32_t k = 0; k < 7; k++)
+                if (part[0] == kinds[k]) view.kind = k + 1;
+            if (!view.kind || part.size() == 2 || part.size() > 4) { std::fprintf(stderr, "--view wants KIND[:LO:HI[:RAMP]], got %s\n", v.c_str()); return 2; }
+            if (part.size() >= 3) { view.lo = std::strtof(part[1].c_str(), nullptr); view.hi = std::strtof(part[2].c_str(), nullptr); }
+            if (part.size() == 4) {
+                if (part[3] == "grey") view.ramp = MRT_VIEW_RAMP_GREY;
+                else if (part[3] == "heat") view.ramp = MRT_VIEW_RAMP_HEAT;
+                else { std::fprintf(stderr, "unknown --view ramp %s\n", part[3].c_str()); return 2; }
+            }
+            if (mrt_set_view(nullptr, &view) != MRT_OK) { std::fprintf(stderr, "--view %s: LO and HI must be finite and differ\n", v.c_str()); return 2; }
+            have_view = true;
+        }
+        else if (a == "--view-out") view_out = v;
         else if (a == "--device") device = std::atoi(v.c_str());
         else if (a == "--target-noise") target_noise = std::strtod(v.c_str(), nullptr);
         else if (a == "--budget") budget = std::strtoull(v.c_str(), nullptr, 10);
@@ -165,7 +194,9 @@ int main(int argc, char** argv) {
         TRY(ctxs[i], mrt_set_camera(ctxs[i], &cam));
         if (rng_mode != MRT_RNG_PIXEL_STREAM) TRY(ctxs[i], mrt_set_rng_mode(ctxs[i], rng_mode));
         if (hint_div) TRY(ctxs[i], mrt_set_schedule_hint(ctxs[i], hint_div, hint_mult));
-        if (target_noise >= 0.0 || !denoise_out.empty()) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
+        const bool noise_view = have_view && (view.kind == MRT_VIEW_NOISE_SE || view.kind == MRT_VIEW_NOISE_REL);
+        if (target_noise >= 0.0 || !denoise_out.empty() || noise_view) TRY(ctxs[i], mrt_set_noise_tracking(ctxs[i], 1));
+        if (have_view) TRY(ctxs[i], mrt_set_view(ctxs[i], &view));
         TRY(ctxs[i], mrt_set_denoise_variance(ctxs[i], denoise_var, spatial_frames));
         // an adaptive run's tiles end at their own frame counts: its denoise is the per-tile filter (one GPU: checked below)
         if ((adaptive || budget) && !denoise_out.empty()) TRY(ctxs[i], mrt_set_denoise_adaptive(ctxs[i], 1));
@@ -174,6 +205,7 @@ int main(int argc, char** argv) {
     // several GPUs: the noise estimate travels with the gather, and the first GPU denoises the gathered frame
     if (!denoise_out.empty() && n_gpus > 1) TRY(ctxs[0], mrt_set_gather_noise(ctxs[0], 1));
     if (mix.enabled && denoise_out.empty()) { std::fprintf(stderr, "--denoise-mix wants --denoise-out\n"); destroy_all(); return 2; }
+    if (have_view != !view_out.empty() || (have_view && n_gpus > 1)) { std::fprintf(stderr, "--view KIND and --view-out FILE go together, on one GPU\n"); destroy_all(); return 2; }
     if (check_every == 0) { std::fprintf(stderr, "--check-every wants N >= 1\n"); destroy_all(); return 2; }
     if (adaptive && (target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--adaptive wants --target-noise and one GPU\n"); destroy_all(); return 2; }
     if (budget && (adaptive || target_noise < 0.0 || n_gpus > 1)) { std::fprintf(stderr, "--budget wants --target-noise and one GPU, and not --adaptive\n"); destroy_all(); return 2; }
@@ -360,6 +392,11 @@ int main(int argc, char** argv) {
         if (n_gpus > 1) TRY(ctxs[0], mrt_read_gathered_denoised(ctxs[0], fb.data(), fb.size()));
         else TRY(ctxs[0], mrt_read_denoised(ctxs[0], fb.data(), fb.size()));
         if (write_image(denoise_out, fb)) { destroy_all(); return 1; }
+    }
+    if (have_view) {
+        std::vector<float> fb((size_t)args.width * args.height * 4);
+        TRY(ctxs[0], mrt_read_view(ctxs[0], fb.data(), fb.size()));
+        if (write_image(view_out, fb)) { destroy_all(); return 1; }
     }
     destroy_all();
     return 0;

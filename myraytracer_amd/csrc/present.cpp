@@ -134,7 +134,8 @@ uint32_t present_pixel_bytes(int format) {
 int source_of_flags(mrt_ctx* c, uint32_t flags, ImageSource* out) {
     static constexpr struct { uint32_t bit; ImageSource source; } kSources[] = {
         {MRT_PRESENT_GATHERED, ImageSource::Gathered}, {MRT_PRESENT_DENOISED, ImageSource::Denoised},
-        {MRT_PRESENT_TEMPORAL, ImageSource::Temporal}, {MRT_PRESENT_GATHERED_DENOISED, ImageSource::GatheredDenoised}};
+        {MRT_PRESENT_TEMPORAL, ImageSource::Temporal}, {MRT_PRESENT_GATHERED_DENOISED, ImageSource::GatheredDenoised},
+        {MRT_PRESENT_VIEW, ImageSource::View}};
     uint32_t known = MRT_PRESENT_FLIP_Y;
     for (const auto& s : kSources) known |= s.bit;
     if (flags & ~known) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: flags 0x%x", flags);
@@ -144,6 +145,7 @@ int source_of_flags(mrt_ctx* c, uint32_t flags, ImageSource* out) {
         if (*out == ImageSource::Accumulated) { *out = s.source; continue; }
         if (s.source == ImageSource::Denoised) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the gathered frame cannot be denoised (it has no S)");
         if (s.source == ImageSource::Temporal) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the temporal image is neither the gathered nor the denoised frame (flags 0x%x)", flags);
+        if (s.source == ImageSource::View) return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: a view is computed from the accumulation, not from another source (flags 0x%x: with FLIP_Y only)", flags);
         return fail(c, MRT_ERR_INVALID_ARG, "mrt_present: the denoised gathered frame is a source of its own (flags 0x%x: with FLIP_Y only)", flags);
     }
     return MRT_OK;

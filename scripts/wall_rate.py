@@ -6,6 +6,8 @@
    [MRT_PRESENT_COPY=0|1 (the present's copy on a stream of its own / on the context's stream)]
    [MRT_PRESENT_DENOISE=1 (the presents are denoised: noise tracking on, MRT_PRESENT_DENOISED; with MRT_PRESENT_EVERY=k, every k
     frames)]
+   [MRT_PRESENT_VIEW=kind[:ramp] (the presents show a diagnostic view, MRT_PRESENT_VIEW: noise_se | noise_rel | tile_frames | depth |
+    normal | albedo | sphere, ramp grey | heat; noise tracking on for the noise kinds)]
    [MRT_NOISE=1 (noise tracking on, no queries)] [MRT_NOISE_EVERY=k (tracking on, mrt_noise_query every k frames, the newest
     report taken without waiting)]
    python scripts/wall_rate.py scene w h spp steps"""
@@ -32,17 +34,19 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
     present_every = int(os.environ.get("MRT_PRESENT_EVERY", "0") or "0")      # 1: after every redraw; k: every k-th
     present_denoise = bool(os.environ.get("MRT_PRESENT_DENOISE"))
     present_format = os.environ.get("MRT_PRESENT_FORMAT") or "bgra8"
+    present_view = (os.environ.get("MRT_PRESENT_VIEW") or "").split(":")
     if os.environ.get("MRT_PRESENT_COPY"):
         st.debug_set_present_copy(int(os.environ["MRT_PRESENT_COPY"]))
     acquired, ring_depth = 0, 0
     noise_every = int(os.environ.get("MRT_NOISE_EVERY", "0"))
-    if noise_every or os.environ.get("MRT_NOISE") or present_denoise:
+    if noise_every or os.environ.get("MRT_NOISE") or present_denoise or present_view[0].startswith("noise"):
         st.set_noise_tracking(True)
     reports = 0
     st.set_world(sp)
     if cam is not None: st.set_camera(cam)
     if os.environ.get("MRT_RNG"): st.set_rng_mode(int(os.environ["MRT_RNG"]))
     st.set_draw_counting(False)
+    if present_view[0]: st.set_view(present_view[0], *present_view[1:2])
     for _ in range(int(os.environ.get('MRT_WARMUP', max(2, int(os.environ.get('MRT_SLOTS', '2')))))): st.redraw()      # (the launch-width controller settles within ~3 x the frames in flight)
     st.sync()
     c0 = st.read_counters()
@@ -53,7 +57,7 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
         stamps.append(time.perf_counter())         # (a call returns when the oldest frame in flight has ended: the back-pressure)
         if read_every: st.read_framebuffer()
         if present_every and (k + 1) % present_every == 0:
-            st.present(present_format, flip=shard is None, denoise=present_denoise)
+            st.present(present_format, flip=shard is None, denoise=present_denoise, **({"view": True} if present_view[0] else {}))
             got = st.acquire_presented(newest=True, wait=False, copy=False)
             acquired += got is not None
             ring_depth = got[1]["ring_depth"] if got else ring_depth
@@ -62,7 +66,7 @@ with M.State(M.Args(w, h, spp, 50, 1.0), seed=1, shard=shard) as st:
             reports += st.noise_result(wait=False) is not None
     st.sync()
     dt = time.perf_counter() - t0
-    present_note = (f"presented{' denoised' if present_denoise else ''} as {present_format} every {'frame' if present_every == 1 else f'{present_every} frames'} "
+    present_note = (f"presented{' denoised' if present_denoise else ''}{' view ' + ':'.join(present_view) if present_view[0] else ''} as {present_format} every {'frame' if present_every == 1 else f'{present_every} frames'} "
                     f"({acquired} of {steps // max(present_every, 1)} acquired without waiting, ring depth {ring_depth}, copy placement {os.environ.get('MRT_PRESENT_COPY', 'default (1)')}), ")
     c1 = st.read_counters()
     util = (c1["world_hit_calls"] - c0["world_hit_calls"]) / max(1, c1["lane_slots"] - c0["lane_slots"])
